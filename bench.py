@@ -1,6 +1,6 @@
 """bench.py - PPO env-steps/s of the MI355X hot path on BASELINE.json's headline workload.
 
-    python bench.py --gpus 1 --steps K --warmup W [--workload humanoid|ant|lstm]
+    python bench.py --gpus 1 --steps K --warmup W [--workload humanoid|ant|lstm] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     RLG_BENCH_CONFIG='{"native_allreduce": false}' ... bench.py --gpus N ...   (second row: RCCL gradient all-reduce
@@ -218,6 +218,43 @@ def collective_preflight(agent, device, world):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, epoch_result, agent):
+    """--dump-outputs: what the last timed epoch handed its caller - train_epoch's per-minibatch losses, entropies and KLs,
+    the learning rate and its multiplier - and the model it left (every floating tensor of the state dict: weights,
+    normaliser statistics), as DIR/<name>.npy in float32 (float64 where the value is a python float).  Arrays that would
+    take the total past 64 MB are replaced by a fixed, seeded sample of their elements (`<name>.sample_index.npy`)."""
+    import numpy as np
+    _, _, _, _, a_losses, c_losses, b_losses, entropies, kls, last_lr, lr_mul = epoch_result
+    arrays = {}
+    for name, vals in (('a_losses', a_losses), ('c_losses', c_losses), ('b_losses', b_losses), ('entropies', entropies),
+                       ('kls', kls)):
+        arrays[name] = torch.stack([torch.as_tensor(v, dtype=torch.float32).reshape(-1).cpu() for v in vals]).numpy()
+    for name, v in (('last_lr', last_lr), ('lr_mul', lr_mul)):
+        if isinstance(v, torch.Tensor):
+            arrays[name] = v.detach().float().cpu().reshape(-1).numpy()
+        else:
+            arrays[name] = np.array([v], dtype=np.float64)
+    for name, t in agent.model.state_dict().items():
+        if t.is_floating_point():
+            arrays['model.' + name] = t.detach().float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name in sorted(arrays, key=lambda n: arrays[n].nbytes):
+        a = arrays[name]
+        if total + a.nbytes > DUMP_LIMIT_BYTES:
+            keep = max(1, (DUMP_LIMIT_BYTES - total) // (2 * a.itemsize))
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randperm(a.size, generator=g)[:keep].sort().values.numpy()
+            np.save(os.path.join(out_dir, name + '.sample_index.npy'), idx.astype(np.int64))
+            a = a.reshape(-1)[idx]
+            total += idx.nbytes
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a))
+        total += a.nbytes
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -230,6 +267,8 @@ def main():
     ap.add_argument('--cpu-sample-envs', type=int, default=0, help='0: 4096 (humanoid) / 1024 (ant, lstm)')
     ap.add_argument('--max-seconds', type=int, default=1500, help='watchdog: the process exits non-zero with a '
                     'message instead of hanging (a peer rank that died, a collective that never completes)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps, write what the last '
+                    'timed step computed (losses, KLs, lr, the model state) as DIR/<name>.npy (rank 0)')
     args = ap.parse_args()
     w = WORKLOADS[args.workload]
 
@@ -315,9 +354,10 @@ def main():
     barrier()
     t0 = time.perf_counter()
     marks[0].record()
+    epoch_result = None
     for k in range(args.steps):
         agent.update_epoch()
-        agent.train_epoch()
+        epoch_result = agent.train_epoch()
         marks[k + 1].record()
     barrier()
     elapsed = time.perf_counter() - t0
@@ -326,6 +366,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     per_epoch_ms = [marks[k].elapsed_time(marks[k + 1]) for k in range(args.steps)]
+    if args.dump_outputs and rank == 0:       # before anything after the timed region touches the agent
+        dump_outputs(args.dump_outputs, epoch_result, agent)
 
     in_sync = params_finite = None
     if multi:   # outside the timed region: every rank must hold bit-identical parameters and lr

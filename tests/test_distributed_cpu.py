@@ -263,55 +263,73 @@ def _dp_oracle_agents(world):
     return agents
 
 
-def _dp_oracle_worker(rank, world):
+DP_REFERENCE_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'dp_reference_steps.pt')
+
+
+def _dp_oracle_worker(rank, world, record_dir):
     """oracle.ppo_epoch_oracle.data_parallel_minibatch_step against the REAL reference method: every rank computes its
     own minibatch gradients with the oracle, then runs rl_games' A2CBase.trancate_gradients_and_step (a2c_common.py:
     493-514: cat -> all_reduce(SUM) -> / world_size -> copy back -> clip_grad_norm_ -> optimizer.step) under gloo on a
     stand-in object with exactly the attributes that method reads.  The oracle's single-process restatement of the same
-    step must leave the same gradients and parameters, bit for bit, for all steps of a mini-epoch."""
+    step must leave the same gradients and parameters, bit for bit, for all steps of a mini-epoch.
+
+    The reference's run is a recording (tests/golden/dp_reference_steps.pt: per rank and step the averaged KL, the
+    losses, the learning rate, the gradients and parameters behind the step); record_dir set (RLG_RECORD_REFERENCE=1,
+    a machine with the reference checkout) runs the reference method live, checks it, and writes this rank's part."""
     import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    sys.path.insert(0, os.path.join(here, 'golden'))
-    import ref_import
-    ref_import.enable()
-    from rl_games.common import a2c_common
     from oracle.ppo_epoch_oracle import data_parallel_minibatch_step
-    import types
-    mine = _dp_oracle_agents(world)[rank]               # the reference run: this rank's agent only
+    torch.set_num_threads(1)                            # (bit for bit against a recording: one reduction order)
     both = _dp_oracle_agents(world)                     # the oracle run: all ranks in this process
     assert all(torch.equal(p, q) for p, q in zip(both[0].model.a2c_network.parameters(),
                                                  both[1].model.a2c_network.parameters()))
-    cfg = mine.cfg
-    stub = types.SimpleNamespace(multi_gpu=True, world_size=world, model=mine.model.a2c_network,
-                                 truncate_grads=cfg['truncate_grads'], grad_norm=cfg['grad_norm'], optimizer=mine.optimizer)
-    for i in range(mine.B // mine.mb):
-        out = mine.minibatch_backward(i)
-        a2c_common.A2CBase.trancate_gradients_and_step(stub)
-        kl = out['kl'].clone()
-        dist.all_reduce(kl)                                             # a2c_common.py:1559-1561
-        kl /= world
+    if record_dir is not None:
+        here = os.path.dirname(os.path.abspath(__file__))
+        sys.path.insert(0, os.path.join(here, 'golden'))
+        import ref_import
+        ref_import.enable()
+        from rl_games.common import a2c_common
+        import types
+        mine = _dp_oracle_agents(world)[rank]           # the reference run: this rank's agent only
+        cfg = mine.cfg
+        stub = types.SimpleNamespace(multi_gpu=True, world_size=world, model=mine.model.a2c_network,
+                                     truncate_grads=cfg['truncate_grads'], grad_norm=cfg['grad_norm'], optimizer=mine.optimizer)
+        steps = []
+        for i in range(mine.B // mine.mb):
+            out = mine.minibatch_backward(i)
+            a2c_common.A2CBase.trancate_gradients_and_step(stub)
+            kl = out['kl'].clone()
+            dist.all_reduce(kl)                                         # a2c_common.py:1559-1561
+            kl /= world
+            mine_lr = mine.lr
+            # the lr rule on the averaged KL (python floats), like minibatch_apply does for the oracle ranks
+            mine.lr = O.adaptive_lr(mine.lr, kl.item(), cfg['kl_threshold'], cfg.get('min_lr', 1e-6), cfg.get('max_lr', 1e-2),
+                                    cfg.get('lr_multiplier', 1.5))
+            for g in mine.optimizer.param_groups:
+                g['lr'] = mine.lr
+            steps.append({'kl_mean': kl.clone(), 'losses': {k: out[k].detach().clone() for k in ('a_loss', 'c_loss', 'entropy', 'b_loss', 'kl')},
+                          'lr': mine_lr, 'next_lr': mine.lr,
+                          'grads': [p.grad.detach().clone() for p in mine.model.a2c_network.parameters()],
+                          'params': [p.detach().clone() for p in mine.model.a2c_network.parameters()]})
+        torch.save(steps, os.path.join(record_dir, f'rank{rank}.pt'))
+    else:
+        steps = torch.load(DP_REFERENCE_FILE, map_location='cpu', weights_only=False)[rank]
+    assert len(steps) == both[rank].B // both[rank].mb
+    for i, ref in enumerate(steps):
         want = data_parallel_minibatch_step(both, i)
-        assert torch.equal(kl, want[rank]['kl_mean'])
+        assert torch.equal(ref['kl_mean'], want[rank]['kl_mean'])
         for k in ('a_loss', 'c_loss', 'entropy', 'b_loss', 'kl'):
-            assert torch.equal(out[k], want[rank][k]), (i, k)
-        mine_lr = mine.lr
-        # the lr rule on the averaged KL (python floats), like minibatch_apply does for the oracle ranks
-        mine.lr = O.adaptive_lr(mine.lr, kl.item(), cfg['kl_threshold'], cfg.get('min_lr', 1e-6), cfg.get('max_lr', 1e-2),
-                                cfg.get('lr_multiplier', 1.5))
-        for g in mine.optimizer.param_groups:
-            g['lr'] = mine.lr
-        assert want[rank]['lr'] == mine_lr and both[rank].lr == mine.lr
-        for (n, p), q in zip(mine.model.a2c_network.named_parameters(), both[rank].model.a2c_network.parameters()):
-            assert torch.equal(p.grad, q.grad), (i, n)                  # averaged, clipped
+            assert torch.equal(ref['losses'][k], want[rank][k]), (i, k)
+        assert want[rank]['lr'] == ref['lr'] and both[rank].lr == ref['next_lr']
+        for (n, q), g, p in zip(both[rank].model.a2c_network.named_parameters(), ref['grads'], ref['params']):
+            assert torch.equal(g, q.grad), (i, n)                       # averaged, clipped
             assert torch.equal(p, q), (i, n)                            # stepped
     # the ranks of the oracle run stay identical
     for p, q in zip(both[0].model.a2c_network.parameters(), both[1].model.a2c_network.parameters()):
         assert torch.equal(p, q)
 
 
-def test_oracle_data_parallel_step_equals_the_reference_method_two_ranks():
-    sys_path_ok = os.path.isdir('/root/reference/rl_games') or os.path.isfile(
-        os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'oracle', '_ref', 'rl_games_ref.zip'))
-    if not sys_path_ok:
-        pytest.skip('reference not present')
-    _spawn(_dp_oracle_worker, 2)
+def test_oracle_data_parallel_step_equals_the_reference_method_two_ranks(tmp_path):
+    record = os.environ.get('RLG_RECORD_REFERENCE') == '1'
+    _spawn(_dp_oracle_worker, 2, str(tmp_path) if record else None)
+    if record:
+        torch.save([torch.load(str(tmp_path / f'rank{r}.pt'), weights_only=False) for r in range(2)], DP_REFERENCE_FILE)
