@@ -302,6 +302,45 @@ int rlg_ppo_loss_discrete_strided(const float* logits, long long ld_logits, cons
                                   long long ld_d_logits, float* d_values, long long ld_d_values, double* partials,
                                   int minibatch, float e_clip, float critic_coef, float entropy_coef, int clip_value,
                                   int use_smooth_clamp, void* stream);
+/* rlg_ppo_loss_discrete_strided that also stores each row's neglogp (the sum over the branches, as the loss used it)
+ * into new_neglogp_or_null [mb] - the per-minibatch diagnostics read it (rlg_ppo_diag).  NULL: no store. */
+int rlg_ppo_loss_discrete_nlp(const float* logits, long long ld_logits, const float* values, long long ld_values,
+                              const long long* actions, const unsigned char* action_masks_or_null,
+                              const int* branch_sizes, int num_branches, const float* old_neglogp,
+                              const float* advantages, const float* old_values, const float* returns,
+                              const float* mask_or_null, const float* mask_sum_or_null, float* d_logits,
+                              long long ld_d_logits, float* d_values, long long ld_d_values, double* partials,
+                              int minibatch, float e_clip, float critic_coef, float entropy_coef, int clip_value,
+                              int use_smooth_clamp, float* new_neglogp_or_null, void* stream);
+
+/* PPO diagnostics (`use_diagnostics`; rl_games/common/diagnostics.py, torch_ext.py:182-227), csrc/ppo_diag.hip.  A row of
+ * the diagnostics table is rlg_ppo_diag_stats() = 10 fp64: {rows, W = sum m, C = sum m*clipped, mean_ret, M2_ret,
+ * mean_val, M2_val, mean_d, M2_d, elements}.  Both launches write (do not accumulate) their columns, fold their
+ * workgroups' partials in a fixed order (no float atomics: bit-reproducible), take one zero-initialised uint ticket per
+ * output row and leave it at zero; no host synchronisation: capturable.
+ *
+ * rlg_ppo_diag - one minibatch, columns 0..2; m = mask[i] (1 without a mask).  Row i is clipped when
+ * (old_neglogp[i] - new_nlp) in fp32 is < log_lo or > log_hi, log_lo / log_hi = fp32(log(1 -/+ e_clip)).
+ * new_nlp: new_neglogp_or_null[i], or - NULL - recomputed with the continuous loss tile's arithmetic from mu [mb, A]
+ * (row stride ld_mu), logstd [A] and actions [mb, A]: z = (x - mu) / expf(logstd),
+ * nlp = (0.5 fp32(sum_f64 z^2) + fp32(0.9189385332046727 A)) + fp32(sum_f64 logstd); 1 <= A <= 32.
+ * neglogp_out_or_null [mb] receives the new_nlp of every row.  partials: rlg_ppo_diag_num_blocks(mb) x 3 doubles.
+ *
+ * rlg_ppo_diag_moments - `slices` consecutive minibatch slices of rows x cols values / returns (row-major) and
+ * rows masks each, columns 3..9 of the row out + s * ld_out of slice s: the m(row)-weighted centred moments
+ * (mean, M2 = sum m (x - mean)^2, fp64 Welford + Chan merges) of returns, values and d = returns - values (fp32) over
+ * the slice's rows x cols elements, and the element count.  partials: slices x rlg_ppo_diag_moments_num_blocks(rows,
+ * cols) x 9 doubles; tickets: slices uints. */
+int rlg_ppo_diag_stats(void);
+int rlg_ppo_diag_num_blocks(int minibatch);
+int rlg_ppo_diag(const float* mu, long long ld_mu, const float* logstd, const float* actions, long long ld_actions,
+                 const float* new_neglogp_or_null, const float* old_neglogp, const float* mask_or_null, int minibatch,
+                 int actions_num, float log_lo, float log_hi, double* partials, unsigned int* ticket, double* out,
+                 float* neglogp_out_or_null, void* stream);
+int rlg_ppo_diag_moments_num_blocks(int rows, int cols);
+int rlg_ppo_diag_moments(const float* values, const float* returns, const float* mask_or_null, int slices, int rows,
+                         int cols, double* partials, unsigned int* tickets, double* out, long long ld_out,
+                         void* stream);
 
 /* scalars8 = {a_loss, c_loss, entropy, b_loss, kl, loss, sum(mask), 0}; d_logstd [A];
  * kl_slot_or_null receives the KL as well (e.g. the tail slot of the flat gradient arena);

@@ -114,6 +114,14 @@ _PROTOTYPES = {
                               _c_float, _c_float, _c_float, _c_int, _c_int, _P],
     'rlg_ppo_loss_discrete_strided': [_P, _c_ll, _P, _c_ll, _P, _P, _P, _c_int, _P, _P, _P, _P, _P, _P, _P, _c_ll, _P,
                                       _c_ll, _P, _c_int, _c_float, _c_float, _c_float, _c_int, _c_int, _P],
+    'rlg_ppo_loss_discrete_nlp': [_P, _c_ll, _P, _c_ll, _P, _P, _P, _c_int, _P, _P, _P, _P, _P, _P, _P, _c_ll, _P,
+                                  _c_ll, _P, _c_int, _c_float, _c_float, _c_float, _c_int, _c_int, _P, _P],
+    # ppo_diag.hip
+    'rlg_ppo_diag_stats': [],
+    'rlg_ppo_diag_num_blocks': [_c_int],
+    'rlg_ppo_diag': [_P, _c_ll, _P, _P, _c_ll, _P, _P, _P, _c_int, _c_int, _c_float, _c_float, _P, _P, _P, _P, _P],
+    'rlg_ppo_diag_moments_num_blocks': [_c_int, _c_int],
+    'rlg_ppo_diag_moments': [_P, _P, _P, _c_int, _c_int, _c_int, _P, _P, _P, _c_ll, _P],
     'rlg_ppo_loss_finalize': [_P, _c_int, _c_int, _c_int, _c_int, _c_float, _c_float, _c_float, _P,
                               _P, _P, _P, _P, _P],
     # mlp_fused.hip

@@ -33,6 +33,7 @@ import torch
 
 from . import distributed as rdist
 from . import ops
+from .diagnostics import DefaultDiagnostics, PpoDiagnostics
 from .flat_optim import FlatAdam
 from .gae import compute_gae, gae_returns_advantages
 from .lr_control import AdaptiveScheduler, IdentityScheduler, LinearScheduler
@@ -276,6 +277,10 @@ class A2CAgent:
         self.zero_rnn_on_done = config.get('zero_rnn_on_done', True)
         self.normalize_advantage = config['normalize_advantage']
         self.normalize_rms_advantage = config.get('normalize_rms_advantage', False)
+        # a2c_common.py:222-227: the PPO health curves, collected on rank 0 only
+        self.use_diagnostics = config.get('use_diagnostics', False)
+        self.diagnostics = PpoDiagnostics() if self.use_diagnostics and self.global_rank == 0 else DefaultDiagnostics()
+        self._diag_slot = None
         self.normalize_input = config['normalize_input']
         self.normalize_value = config.get('normalize_value', False)
         self.truncate_grads = config.get('truncate_grads', False)
@@ -444,6 +449,10 @@ class A2CAgent:
         self._rnn_state_store = None
         self._eager_epochs = 0
         self._graph_rows = torch.zeros(max(1, self.num_minibatches), 8, dtype=torch.float32, device=dev)
+        if isinstance(self.diagnostics, PpoDiagnostics):
+            # the device table every minibatch launch writes its row of (captured graphs included): allocated here
+            self.diagnostics.allocate(self.mini_epochs_num, max(1, self.num_minibatches), self.minibatch_size, dev,
+                                     value_size=self.value_size)
         self._obs_norm_mb = (torch.empty((mb,) + tuple(self.obs_shape), dtype=torch.float32, device=dev)
                              if self.normalize_input else None)
         self.algo_observer.after_init(self)
@@ -1167,6 +1176,7 @@ class A2CAgent:
             opt.kl_slot.copy_(kl.reshape(1))
             input_dict['mu'].copy_(mu.detach())                                         # datasets.py:33-43
             input_dict['sigma'].copy_(sig)
+            self._diag_minibatch(input_dict, new_neglogp=scalars['neglogp'])
         self._norm_ready = None
 
     # ================================================================== update
@@ -1306,6 +1316,21 @@ class A2CAgent:
                     eng.backward(d_heads)
         if eng is None:
             torch.autograd.backward([mu, values], [d_mu, d_val.view(mb, 1)])
+        # the step's mu is in the dataset now (write_back) and logstd is still the pre-step one (Adam comes behind)
+        self._diag_minibatch(input_dict, mu=input_dict['mu'], logstd=logstd.detach(), actions=input_dict['actions'])
+
+    def _diag_minibatch(self, input_dict, **new_policy):
+        """The diagnostics launch of this minibatch (a2c_continuous.py:223-230, a2c_discrete.py:200-207): writes the
+        minibatch's row of the device table; nothing when `use_diagnostics` is off or on ranks other than 0.
+        new_policy: new_neglogp [mb], or mu / logstd / actions (the neglogp recomputed in the launch)."""
+        if not isinstance(self.diagnostics, PpoDiagnostics):
+            return
+        slot = self._diag_slot if self._diag_slot is not None else (self._mb_index - 1) % len(self.dataset)
+        masks = input_dict.get('rnn_masks', None)
+        batch = dict(values=input_dict['old_values'], returns=input_dict['returns'],
+                     old_neglogp=input_dict['old_logp_actions'], masks=masks, **new_policy)
+        with torch.no_grad():
+            self.diagnostics.mini_batch(self, batch, self.e_clip, slot)
 
     def _native_comm(self):
         """The in-graph gradient collective, created on first use: the hipIpc all-reduce kernel
@@ -1454,10 +1479,11 @@ class A2CAgent:
         """Run fn with the minibatch index visible to _forward_loss_backward (the in-kernel statistics
         fold needs it); a no-op wrapper when the epoch has no precomputed minibatch moments."""
         self._fold_index = mb_index if self._fold_ready else None
+        self._diag_slot = mb_index
         try:
             return fn(*args)
         finally:
-            self._fold_index = None
+            self._fold_index = self._diag_slot = None
 
     def _prepare_obs_fold(self):
         """Once per epoch, after prepare_dataset: column moments of every minibatch's observations in
@@ -1687,6 +1713,7 @@ class A2CAgent:
             if self.schedule_type == 'standard':
                 self._host_schedule(float(av_kls.item()))
             kls.append(av_kls)
+            self.diagnostics.mini_epoch(self, mini_ep)                 # a2c_common.py:1574
             if self.normalize_input:
                 self.model.running_mean_std.eval()
         if self.schedule_type == 'standard_epoch':
@@ -1965,6 +1992,7 @@ class A2CAgent:
             self.dataset.update_values_dict(None)
             should_exit = False
             if self.global_rank == 0:
+                self.diagnostics.epoch(self, current_epoch=epoch_num)         # a2c_common.py:1695
                 if self.print_stats:
                     fps_step = curr_frames / max(step_time, 1e-9)
                     fps_inf = curr_frames / (self.num_agents * play_time)
@@ -1973,6 +2001,7 @@ class A2CAgent:
                           f'fps total: {fps_total:.0f} epoch: {epoch_num:.0f}/{self.max_epochs:.0f} '
                           f'frames: {frame:.0f}/{self.max_frames:.0f}')
                 w = self.writer
+                self.diagnostics.send_info(w)                                 # write_stats, a2c_common.py:529
                 w.add_scalar('performance/step_inference_rl_update_fps', curr_frames / sum_time, frame)
                 w.add_scalar('performance/step_inference_fps', curr_frames / play_time, frame)
                 w.add_scalar('performance/rl_update_time', update_time, frame)

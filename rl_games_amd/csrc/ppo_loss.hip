@@ -166,6 +166,7 @@ struct DiscreteLossArgs {
   int off[kMaxBranches + 1]; // branch b covers logits [off[b], off[b+1])
   float e_clip, critic_coef, entropy_coef;
   int clip_value, smooth;
+  float* new_neglogp;        // [mb] or nullptr: each row's neglogp (the diagnostics read it, rlg_ppo_diag)
 };
 
 // CategoricalMasked (rl_games/common/extensions/distributions.py:24-47): disallowed logits are
@@ -204,6 +205,7 @@ __global__ __launch_bounds__(256) void ppo_loss_discrete_kernel(DiscreteLossArgs
       H_b[b] = Hb;
       H += Hb;
     }
+    if (p.new_neglogp) p.new_neglogp[i] = nlp;
     const float lo = 1.0f - p.e_clip, hi = 1.0f + p.e_clip;
     const float adv = p.advantages[i];
     const float old_nlp = p.old_neglogp[i];
@@ -401,14 +403,14 @@ int rlg_value_loss(const float* values, const float* old_values, const float* re
 
 int rlg_ppo_loss_discrete_num_blocks(int minibatch) { return (minibatch + 255) / 256; }
 
-int rlg_ppo_loss_discrete_strided(const float* logits, long long ld_logits, const float* values, long long ld_values,
-                                  const long long* actions, const unsigned char* action_masks_or_null,
-                                  const int* branch_sizes, int num_branches, const float* old_neglogp,
-                                  const float* advantages, const float* old_values, const float* returns,
-                                  const float* mask_or_null, const float* mask_sum_or_null, float* d_logits,
-                                  long long ld_d_logits, float* d_values, long long ld_d_values, double* partials,
-                                  int minibatch, float e_clip, float critic_coef, float entropy_coef, int clip_value,
-                                  int use_smooth_clamp, void* stream) {
+int rlg_ppo_loss_discrete_nlp(const float* logits, long long ld_logits, const float* values, long long ld_values,
+                              const long long* actions, const unsigned char* action_masks_or_null,
+                              const int* branch_sizes, int num_branches, const float* old_neglogp,
+                              const float* advantages, const float* old_values, const float* returns,
+                              const float* mask_or_null, const float* mask_sum_or_null, float* d_logits,
+                              long long ld_d_logits, float* d_values, long long ld_d_values, double* partials,
+                              int minibatch, float e_clip, float critic_coef, float entropy_coef, int clip_value,
+                              int use_smooth_clamp, float* new_neglogp_or_null, void* stream) {
   using namespace rlg;
   if (minibatch <= 0 || num_branches <= 0 || num_branches > kMaxBranches)
     return static_cast<int>(hipErrorInvalidValue);
@@ -446,9 +448,24 @@ int rlg_ppo_loss_discrete_strided(const float* logits, long long ld_logits, cons
   p.entropy_coef = entropy_coef;
   p.clip_value = clip_value;
   p.smooth = use_smooth_clamp;
+  p.new_neglogp = new_neglogp_or_null;
   hipLaunchKernelGGL(ppo_loss_discrete_kernel, dim3(rlg_ppo_loss_discrete_num_blocks(minibatch)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), p);
   RLG_RETURN_LAUNCH_STATUS();
+}
+
+int rlg_ppo_loss_discrete_strided(const float* logits, long long ld_logits, const float* values, long long ld_values,
+                                  const long long* actions, const unsigned char* action_masks_or_null,
+                                  const int* branch_sizes, int num_branches, const float* old_neglogp,
+                                  const float* advantages, const float* old_values, const float* returns,
+                                  const float* mask_or_null, const float* mask_sum_or_null, float* d_logits,
+                                  long long ld_d_logits, float* d_values, long long ld_d_values, double* partials,
+                                  int minibatch, float e_clip, float critic_coef, float entropy_coef, int clip_value,
+                                  int use_smooth_clamp, void* stream) {
+  return rlg_ppo_loss_discrete_nlp(logits, ld_logits, values, ld_values, actions, action_masks_or_null, branch_sizes,
+                                   num_branches, old_neglogp, advantages, old_values, returns, mask_or_null,
+                                   mask_sum_or_null, d_logits, ld_d_logits, d_values, ld_d_values, partials, minibatch,
+                                   e_clip, critic_coef, entropy_coef, clip_value, use_smooth_clamp, nullptr, stream);
 }
 
 int rlg_ppo_loss_discrete(const float* logits, long long ld_logits, const float* values,

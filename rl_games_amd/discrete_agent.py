@@ -92,6 +92,9 @@ class DiscreteA2CAgent(A2CAgent):
         self._loss_partials = torch.empty(self._loss_blocks, ops.ppo_loss_partials_per_block(0),
                                           dtype=torch.float64, device=dev)
         self._no_logstd = torch.zeros(1, dtype=torch.float32, device=dev)
+        # each row's neglogp out of the loss launch, for the diagnostics (only allocated when they are on)
+        self._diag_nlp = (torch.empty(mb, dtype=torch.float32, device=dev) if self.use_diagnostics and self.global_rank == 0
+                          else None)
 
     def _rollout_fields(self):
         fields = ['actions', 'neglogpacs', 'values']               # a2c_common.py:1224-1229
@@ -168,7 +171,8 @@ class DiscreteA2CAgent(A2CAgent):
                                   input_dict['returns'].reshape(-1), d_logits, d_val, self._loss_partials,
                                   self.e_clip, self.critic_coef if self.has_value_loss else 0.0,
                                   self.entropy_coef, self.clip_value, self.surrogate, mask, mask_sum,
-                                  branch_sizes=self.branch_sizes, action_masks=input_dict.get('action_masks'))
+                                  branch_sizes=self.branch_sizes, action_masks=input_dict.get('action_masks'),
+                                  new_neglogp=None if self._diag_nlp is None else self._diag_nlp[:mb])
             ops.ppo_loss_finalize(self._loss_partials, ops.ppo_loss_discrete_blocks(mb), 0, mb,
                                   mask is not None, self.critic_coef if self.has_value_loss else 0.0,
                                   self.entropy_coef, 0.0, row,
@@ -178,6 +182,8 @@ class DiscreteA2CAgent(A2CAgent):
                 c.backward()
         else:
             torch.autograd.backward([logits, values], [d_logits, d_val.view(mb, 1)])
+        if self._diag_nlp is not None:
+            self._diag_minibatch(input_dict, new_neglogp=self._diag_nlp[:mb])
 
     def train_epoch(self):
         """a2c_common.py:1232-1289: (step_time, play_time, update_time, total_time, a_losses,

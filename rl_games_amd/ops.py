@@ -3,6 +3,7 @@ point, taking torch CUDA tensors, launching on torch's current stream.  No arith
 happens here - shapes/dtypes are checked and raw pointers are handed to librlg_hip.so.
 """
 import ctypes
+import math
 
 import numpy as np
 import os
@@ -425,10 +426,11 @@ def ppo_loss_discrete_blocks(minibatch):
 
 def ppo_loss_discrete(logits, values, actions, old_neglogp, advantages, old_values, returns, d_logits,
                       d_values, partials, e_clip, critic_coef, entropy_coef, clip_value=True,
-                      smooth=False, mask=None, mask_sum=None, branch_sizes=None, action_masks=None):
+                      smooth=False, mask=None, mask_sum=None, branch_sizes=None, action_masks=None,
+                      new_neglogp=None):
     """Categorical PPO loss + gradients.  branch_sizes: widths of the multi-discrete heads
     (default: one head of logits.shape[1]); actions [mb] or [mb, branches] int64; action_masks
-    [mb, n] bool/uint8 or None."""
+    [mb, n] bool/uint8 or None; new_neglogp: fp32 [mb] that receives each row's neglogp, or None."""
     import ctypes
     lib = _lib.load()
     mb, n = logits.shape
@@ -453,7 +455,9 @@ def ppo_loss_discrete(logits, values, actions, old_neglogp, advantages, old_valu
         if t.dtype != F32 or tuple(t.shape) != shape or (t.dim() == 2 and t.stride(1) != 1):
             raise ValueError(f'{name}: fp32 {shape} with unit inner stride expected')
     arr = (ctypes.c_int * len(sizes))(*sizes)
-    _lib.check(lib.rlg_ppo_loss_discrete_strided(
+    if new_neglogp is not None and tuple(new_neglogp.shape) != (mb,):
+        raise ValueError('new_neglogp must be [minibatch]')
+    _lib.check(lib.rlg_ppo_loss_discrete_nlp(
         logits.data_ptr(), logits.stride(0), values.data_ptr(), max(values.stride(0), 1),
         _need(actions, torch.int64, 'actions'), am, arr, len(sizes), _need(old_neglogp, F32, 'old_neglogp'),
         _need(advantages, F32, 'advantages'), _need(old_values, F32, 'old_values'),
@@ -461,7 +465,81 @@ def ppo_loss_discrete(logits, values, actions, old_neglogp, advantages, old_valu
         d_logits.data_ptr(), d_logits.stride(0), d_values.data_ptr(), max(d_values.stride(0), 1),
         _need(partials, F64, 'partials'),
         mb, float(np.float32(e_clip)), float(np.float32(critic_coef)), float(np.float32(entropy_coef)),
-        1 if clip_value else 0, _surrogate_kind(smooth), _stream(logits)), 'rlg_ppo_loss_discrete_strided')
+        1 if clip_value else 0, _surrogate_kind(smooth), _opt(new_neglogp, F32, 'new_neglogp'), _stream(logits)),
+        'rlg_ppo_loss_discrete_nlp')
+
+
+def ppo_diag_stats():
+    """Doubles per row of the diagnostics table (rlg_ppo_diag)."""
+    return _lib.load().rlg_ppo_diag_stats()
+
+
+def ppo_diag_blocks(minibatch):
+    return _lib.load().rlg_ppo_diag_num_blocks(int(minibatch))
+
+
+def ppo_diag_log_bounds(e_clip):
+    """fp32(log(1 - e)), fp32(log(1 + e)): the clip-fraction thresholds of torch_ext.policy_clip_fraction."""
+    return float(np.float32(math.log(1.0 - e_clip))), float(np.float32(math.log(1.0 + e_clip)))
+
+
+def ppo_diag(out, old_neglogp, e_clip, partials, ticket, mask=None, new_neglogp=None, mu=None, logstd=None,
+             actions=None, neglogp_out=None):
+    """Clip columns (rows, sum of the mask, masked clipped count) of one minibatch's diagnostics row `out` (fp64
+    [ppo_diag_stats()]; columns 0..2 written, not accumulated; include/rlg_hip.h).  The new neglogp is `new_neglogp`
+    [mb], or - None - recomputed from mu [mb, A] (row stride free), logstd [A] and actions [mb, A] with the continuous
+    loss's arithmetic.  partials: fp64, >= ppo_diag_blocks(mb) * 3; ticket: int32 [1], zero, left at zero."""
+    lib = _lib.load()
+    mb = old_neglogp.numel()
+    for name, t in (('mask', mask), ('new_neglogp', new_neglogp), ('neglogp_out', neglogp_out)):
+        if t is not None and t.numel() != mb:
+            raise ValueError(f'{name}: {mb} elements expected, got {t.numel()}')
+    if out.numel() != lib.rlg_ppo_diag_stats() or partials.numel() < ppo_diag_blocks(mb) * 3:
+        raise ValueError('ppo_diag: out / partials too small')
+    mu_p = ls_p = act_p = None
+    ld_mu = ld_act = A = 0
+    if new_neglogp is None:
+        if mu is None or logstd is None or actions is None:
+            raise ValueError('ppo_diag: mu, logstd and actions are needed to recompute the neglogp')
+        mu_p, ld_mu = _rows_view(mu, 'mu')
+        act_p, ld_act = _rows_view(actions, 'actions')
+        A = mu.shape[1]
+        if tuple(actions.shape) != (mb, A) or logstd.numel() != A or tuple(mu.shape) != (mb, A):
+            raise ValueError('ppo_diag: mu / actions [mb, A] and logstd [A] expected')
+        ls_p = _need(logstd, F32, 'logstd')
+    lo, hi = ppo_diag_log_bounds(e_clip)
+    _lib.check(lib.rlg_ppo_diag(
+        mu_p, ld_mu, ls_p, act_p, ld_act, _opt(new_neglogp, F32, 'new_neglogp'), _need(old_neglogp, F32, 'old_neglogp'),
+        _opt(mask, F32, 'mask'), mb, A, lo, hi, _need(partials, F64, 'partials'), _need(ticket, torch.int32, 'ticket'),
+        _need(out, F64, 'out'), _opt(neglogp_out, F32, 'neglogp_out'), _stream(old_neglogp)), 'rlg_ppo_diag')
+
+
+def ppo_diag_moments_blocks(rows, cols=1):
+    return _lib.load().rlg_ppo_diag_moments_num_blocks(int(rows), int(cols))
+
+
+def ppo_diag_moments(table, values, returns, slices, rows, partials, tickets, mask=None):
+    """Moment columns (3..9) of the diagnostics rows table[:slices] (fp64 [>= slices, ppo_diag_stats()], row-contiguous)
+    for `slices` consecutive minibatch slices of `rows` rows: values / returns [slices * rows, cols] (or flat), mask
+    [slices * rows] or None.  partials: fp64 >= slices * ppo_diag_moments_blocks(rows, cols) * 9; tickets: int32 [>= slices],
+    zero, left at zero."""
+    lib = _lib.load()
+    n = int(slices) * int(rows)
+    if values.numel() % n or values.numel() != returns.numel() or values.numel() < n:
+        raise ValueError('ppo_diag_moments: values / returns must hold slices * rows rows of equal width')
+    cols = values.numel() // n
+    k = lib.rlg_ppo_diag_stats()
+    if table.dim() != 2 or table.shape[0] < slices or table.shape[1] != k or table.stride(1) != 1:
+        raise ValueError('ppo_diag_moments: table [>= slices, stats] expected')
+    if mask is not None and mask.numel() != n:
+        raise ValueError(f'ppo_diag_moments: mask of {n} rows expected')
+    if partials.numel() < slices * ppo_diag_moments_blocks(rows, cols) * 9 or tickets.numel() < slices:
+        raise ValueError('ppo_diag_moments: partials / tickets too small')
+    _lib.require_gpu(table, 'table')
+    _lib.check(lib.rlg_ppo_diag_moments(
+        _need(values, F32, 'values'), _need(returns, F32, 'returns'), _opt(mask, F32, 'mask'), int(slices), int(rows),
+        cols, _need(partials, F64, 'partials'), _need(tickets, torch.int32, 'tickets'), table.data_ptr(),
+        table.stride(0), _stream(values)), 'rlg_ppo_diag_moments')
 
 
 def ppo_loss_finalize(partials, num_blocks, actions_num, minibatch, masked, critic_coef,

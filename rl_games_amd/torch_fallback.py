@@ -29,7 +29,7 @@ def ppo_loss(mu, logstd, values, actions, old_neglogp, advantages, old_values, r
     True / 2 = ppo: False).
     sigma_fn: None (sigma = exp(logstd)) or the network's raw -> (sigma, log sigma) map (`apply_sigma_parametrization`,
     models.py:272-301: bounds, a floor, the softplus / linear forms).
-    Returns (loss, dict of the detached scalars a_loss / c_loss / entropy / b_loss, sigma [A])."""
+    Returns (loss, dict of the detached scalars a_loss / c_loss / entropy / b_loss and the rows' neglogp, sigma [A])."""
     mb, A = mu.shape
     if sigma_fn is None:
         sigma = torch.exp(logstd)
@@ -67,6 +67,7 @@ def ppo_loss(mu, logstd, values, actions, old_neglogp, advantages, old_values, r
     ent, b_loss = mean(entropy.unsqueeze(1)), mean(b_rows.unsqueeze(1))
     loss = a_loss + 0.5 * c_loss * critic_coef - ent * entropy_coef + b_loss * bounds_coef
     scalars = {'a_loss': a_loss.detach(), 'c_loss': c_loss.detach(), 'entropy': ent.detach(), 'b_loss': b_loss.detach()}
+    scalars['neglogp'] = neglogp.detach()                   # per row: the diagnostics' new neglogp
     return loss, scalars, sigma
 
 

@@ -1,0 +1,299 @@
+"""GPU: `use_diagnostics` - the reduction launch (csrc/ppo_diag.hip, ops.ppo_diag) against a torch fp64 restatement, the
+agents' diagnostics against the REAL reference's (tests/golden/epoch_diagnostics.pt), and the headline epoch with
+diagnostics on and off (the launch only reads: parameters and Adam moments stay bit-identical)."""
+import copy
+
+import numpy as np
+import pytest
+import torch
+
+from rl_games_amd import diagnostics as D
+from rl_games_amd import ops
+from rl_games_amd.synthetic_env import SyntheticTensorEnv
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda:0'
+
+
+def _launch(out, values, returns, old, e_clip, mask=None, new=None, mu=None, logstd=None, actions=None, nlp_out=None):
+    """The clip launch and the moments launch (one slice) into the row `out`."""
+    mb = old.numel()
+    partials = torch.zeros(ops.ppo_diag_blocks(mb) * 3, dtype=torch.float64, device=DEV)
+    ticket = torch.zeros(1, dtype=torch.int32, device=DEV)
+    ops.ppo_diag(out, old, e_clip, partials, ticket, mask=mask, new_neglogp=new, mu=mu,
+                 logstd=logstd, actions=actions, neglogp_out=nlp_out)
+    cols = values.numel() // mb
+    mpart = torch.zeros(ops.ppo_diag_moments_blocks(mb, cols) * 9, dtype=torch.float64, device=DEV)
+    mtick = torch.zeros(1, dtype=torch.int32, device=DEV)
+    ops.ppo_diag_moments(out.view(1, -1), values, returns, 1, mb, mpart, mtick, mask=mask)
+    torch.cuda.synchronize()
+    # left at zero for the next launch / replay
+    assert int(ticket.item()) == 0 and int(mtick.item()) == 0
+    return out
+
+
+def _nlp_f32(mu, logstd, actions):
+    """The loss tile's neglogp in torch: fp32 elements, fp64 row sums rounded once."""
+    A = mu.shape[1]
+    z = (actions - mu) / torch.exp(logstd)
+    s_z2 = (z * z).double().sum(1).float()
+    s_ls = logstd.double().sum().float().expand_as(s_z2)
+    return (0.5 * s_z2 + np.float32(0.9189385332046727 * A)) + s_ls
+
+
+def _masks(kind, mb, g):
+    if kind == 'none':
+        return None
+    if kind == 'ones':
+        return torch.ones(mb, device=DEV)
+    if kind == 'random':
+        return (torch.rand(mb, generator=g, device=DEV) > 0.4).float()
+    m = torch.zeros(mb, device=DEV)
+    if kind == 'one':
+        m[mb // 2] = 1.0
+    return m
+
+
+def _check_row(got, want):
+    got, want = got.cpu(), want.cpu()
+    # rows, mask sum, clipped count, element count: exact
+    assert torch.equal(got[:3], want[:3]) and got[D.ELEMENTS] == want[D.ELEMENTS], (got, want)
+    for k in (D.MEAN_RET, D.MEAN_VAL, D.MEAN_DIFF):
+        scale = max(1.0, float(want[k + 1].abs().sqrt()))
+        assert abs(float(got[k] - want[k])) <= 1e-12 * scale, k
+        assert abs(float(got[k + 1] - want[k + 1])) <= 1e-12 * max(float(want[k + 1].abs()), 1e-300) + 1e-300, k
+
+
+@pytest.mark.parametrize('rows', (1, 16, 4096, 32768))
+@pytest.mark.parametrize('A', (1, 3, 21, 32))
+@pytest.mark.parametrize('mask_kind', ('none', 'ones', 'random', 'one', 'zero'))
+def test_kernel_matches_fp64_restatement(rows, A, mask_kind):
+    g = torch.Generator(device=DEV).manual_seed(rows * 97 + A)
+    e_clip = 0.2
+    # mu as the columns of a wider head matrix (row stride A + 3), as the fused chain writes it
+    heads = torch.randn(rows, A + 3, generator=g, device=DEV)
+    mu = heads[:, 2:2 + A]
+    logstd = torch.randn(A, generator=g, device=DEV) * 0.3
+    actions = mu + torch.randn(rows, A, generator=g, device=DEV) * torch.exp(logstd)
+    values = torch.randn(rows, generator=g, device=DEV) * 2 + 0.5
+    returns = values + torch.randn(rows, generator=g, device=DEV)
+    mask = _masks(mask_kind, rows, g)
+    nlp = _nlp_f32(mu, logstd, actions)
+    old = nlp + torch.randn(rows, generator=g, device=DEV) * 0.3
+    # rows exactly at the thresholds (not clipped: the comparisons are strict) and one ulp outside
+    lo, hi = ops.ppo_diag_log_bounds(e_clip)
+    if rows >= 16:
+        new_given = old.clone()
+        old[:4] = torch.tensor([lo, hi, np.nextafter(np.float32(lo), np.float32(-1)),
+                                np.nextafter(np.float32(hi), np.float32(1))], device=DEV)
+        new_given[4:] = old[4:] + torch.randn(rows - 4, generator=g, device=DEV) * 0.3
+        new_given[:4] = 0.0
+    out = torch.full((D.STATS,), float('nan'), dtype=torch.float64, device=DEV)
+    nlp_out = torch.empty(rows, device=DEV)
+    _launch(out, values, returns, old, e_clip, mask=mask, mu=mu, logstd=logstd, actions=actions, nlp_out=nlp_out)
+    # the recomputed neglogp: within 1 ulp of the formula (torch's exp may differ from the device expf by an ulp)
+    ulp = torch.abs(torch.nextafter(nlp, torch.full_like(nlp, float('inf'))) - nlp)
+    assert bool((torch.abs(nlp_out - nlp) <= ulp).all())
+    _check_row(out, D.reference_row(values, returns, nlp_out, old, e_clip, mask))
+    # repeat launches: bit-identical
+    again = torch.zeros_like(out)
+    _launch(again, values, returns, old, e_clip, mask=mask, mu=mu, logstd=logstd, actions=actions)
+    assert torch.equal(out, again)
+    if rows >= 16:
+        # the given form, with the boundary rows
+        out2 = torch.zeros_like(out)
+        _launch(out2, values, returns, old, e_clip, mask=mask, new=new_given)
+        want = D.reference_row(values, returns, new_given, old, e_clip, mask)
+        _check_row(out2, want)
+        lr = (old - new_given)[:4].cpu()
+        assert lr[0].item() == lo and lr[1].item() == hi
+        assert out2[D.CLIPPED] > 0 or mask_kind in ('one', 'zero')
+
+
+@pytest.mark.parametrize('slices,rows,cols', ((1, 1, 1), (3, 16, 2), (4, 4096, 1), (2, 32768, 1), (5, 300, 3)))
+@pytest.mark.parametrize('mask_kind', ('none', 'random', 'zero'))
+def test_moments_launch_over_slices(slices, rows, cols, mask_kind):
+    """One moments launch over consecutive minibatch slices (blockIdx.y) against the fp64 restatement of each slice;
+    value columns (value_size > 1) weighted by their row's mask; repeat launches bit-identical."""
+    g = torch.Generator(device=DEV).manual_seed(slices * 1000 + rows + cols)
+    n = slices * rows
+    values = torch.randn(n, cols, generator=g, device=DEV) * 2 + 3.0
+    returns = values + torch.randn(n, cols, generator=g, device=DEV)
+    mask = _masks(mask_kind, n, g)
+    table = torch.zeros(slices, D.STATS, dtype=torch.float64, device=DEV)
+    part = torch.zeros(slices * ops.ppo_diag_moments_blocks(rows, cols) * 9, dtype=torch.float64, device=DEV)
+    tick = torch.zeros(slices, dtype=torch.int32, device=DEV)
+    ops.ppo_diag_moments(table, values, returns, slices, rows, part, tick, mask=mask)
+    again = torch.zeros_like(table)
+    ops.ppo_diag_moments(again, values, returns, slices, rows, part, tick, mask=mask)
+    torch.cuda.synchronize()
+    assert torch.equal(table, again) and int(tick.sum().item()) == 0
+    nlp = torch.zeros(n, device=DEV)
+    for s_ in range(slices):
+        sl = slice(s_ * rows, (s_ + 1) * rows)
+        want = D.reference_row(values[sl], returns[sl], nlp[sl], nlp[sl], 0.2, None if mask is None else mask[sl])
+        got = table[s_].cpu().clone()
+        got[:3] = want[:3]                      # (the clip launch's columns)
+        _check_row(got, want)
+
+
+def _epoch(agent, cap):
+    """The recorded rollout through this agent's dataset preparation and every minibatch step (the train_epoch loop)."""
+    agent.model.load_state_dict(cap['state_after_rollout'])
+    batch = {k: ([s.to(DEV) for s in v] if isinstance(v, (list, tuple)) else v.to(DEV)) for k, v in cap['batch'].items()}
+    agent.set_train()
+    agent.prepare_dataset(batch)
+    agent._mb_index = 0
+    for mini_ep in range(agent.mini_epochs_num):
+        for i in range(len(agent.dataset)):
+            agent._with_fold(i, agent.train_actor_critic, agent.dataset[i])
+        agent.diagnostics.mini_epoch(agent, mini_ep)
+    agent.diagnostics.epoch(agent, current_epoch=1)
+    return agent.diagnostics.diag_dict
+
+
+def _make(cap):
+    params = copy.deepcopy(cap['params'])
+    params['config'].update(device=DEV, use_diagnostics=True)
+    if cap.get('discrete'):
+        from rl_games_amd.discrete_agent import DiscreteA2CAgent
+        env = SyntheticTensorEnv(cap['num_envs'], device=DEV, **params['config']['env_config'])
+        cls = DiscreteA2CAgent
+    else:
+        from rl_games_amd.agent import A2CAgent
+        env = SyntheticTensorEnv(cap['env']['num_envs'], cap['env']['obs_dim'], cap['env']['act_dim'],
+                                 device=DEV, seed=cap['env']['seed'])
+        cls = A2CAgent
+    params['config']['vec_env'] = env
+    params['config']['env_info'] = env.get_env_info()
+    agent = cls('test', params)
+    agent.init_tensors()
+    return agent
+
+
+@pytest.mark.parametrize('variant', ('default', 'smooth_reg_ema', 'lstm', 'discrete_masked', 'multi_discrete_masked'))
+def test_agent_diagnostics_match_reference(golden, variant):
+    """diag_dict of this agent's epoch against the reference's on the same rollout.  Explained variance to 1e-5 absolute
+    (the project's parity tolerance): the reference forms its variances in fp32 - the masked form as E[x^2] - E[x]^2,
+    whose cancellation at |mean| ~ std leaves a relative error of a few 1e-7 - while the kernel's are fp64 centred
+    moments.  Clip fraction: a row may flip only where the reference's logratio lies within 1e-5 of a threshold."""
+    cap = golden('epoch_diagnostics.pt')[variant]
+    want = cap['diag']['diag_dict']
+    got = _epoch(_make(cap), cap)
+    assert list(got) == list(want)
+    mbs = cap['diag']['minibatches']
+    nmb = len(mbs) // cap['diag']['mini_epochs']
+    lo, hi = ops.ppo_diag_log_bounds(cap['diag']['e_clip'])
+    for k, v in want.items():
+        g = got[k].cpu()
+        assert g.shape == v.shape and g.dtype == v.dtype, k
+        if k.startswith('diagnostics/clip_frac/'):
+            me = int(k.rsplit('/', 1)[1])
+            near, rows = 0, 0
+            for m in mbs[me * nmb:(me + 1) * nmb]:
+                lr = m['old_neglogp'] - m['new_neglogp']
+                near += int(((lr - lo).abs() < 1e-5).sum() + ((lr - hi).abs() < 1e-5).sum())
+                rows += lr.numel()
+            assert abs(float(g) - float(v)) <= (near + 0.5) / rows, (k, float(g), float(v), near)
+        elif k == 'diagnostics/exp_var':
+            assert abs(float(g) - float(v)) <= 1e-5, (float(g), float(v))
+        else:
+            assert torch.allclose(g, v, rtol=1e-5, atol=1e-6), (k, g, v)
+
+
+def _headline_epoch(use_diagnostics, monkeypatch):
+    from rl_games_amd import configs
+    from rl_games_amd.agent import A2CAgent
+    calls = []
+    real = ops.ppo_diag
+
+    def counted(*a, **k):
+        calls.append(1)
+        return real(*a, **k)
+    monkeypatch.setattr(ops, 'ppo_diag', counted)
+    params = configs.humanoid_65536(num_actors=65536, minibatch_size=32768, hip_graphs=True,
+                                    use_diagnostics=use_diagnostics)
+    torch.manual_seed(5)
+    agent = A2CAgent('headline', copy.deepcopy(params))
+    agent.init_tensors()
+    agent.obs = agent.env_reset()
+    agent._eager_epochs = 1                # the mini-epoch graph from the first epoch
+    if use_diagnostics:
+        # each slot's new neglogp, written by the captured launches: after the epoch, the last mini-epoch's
+        agent.diagnostics.debug_neglogp = torch.full((len(agent.dataset), agent.minibatch_size), float('nan'), device=DEV)
+    agent.update_epoch()
+    res = agent.train_epoch()
+    assert agent._graph_epoch is not None and not agent._graph_failed
+    if use_diagnostics:
+        agent.diagnostics.epoch(agent, current_epoch=1)
+    torch.cuda.synchronize()
+    opt = agent.optimizer
+    state = [opt.flat_params.clone(), opt.exp_avg.clone(), opt.exp_avg_sq.clone(),
+             torch.cat([torch.stack(x).reshape(-1) for x in res[4:9] if len(x)])]
+    monkeypatch.setattr(ops, 'ppo_diag', real)
+    return agent, state, len(calls)
+
+
+def test_headline_epoch_with_and_without_diagnostics(monkeypatch):
+    off, s_off, n_off = _headline_epoch(False, monkeypatch)
+    assert n_off == 0 and not isinstance(off.diagnostics, D.PpoDiagnostics)
+    del off
+    on, s_on, n_on = _headline_epoch(True, monkeypatch)
+    nmb = len(on.dataset)
+    assert n_on == nmb                     # captured once: nmb launches in the mini-epoch graph
+    for a, b in zip(s_off, s_on):
+        assert torch.equal(a, b)
+    dd = on.diagnostics.diag_dict
+    assert [k for k in dd if 'clip_frac' in k] == [f'diagnostics/clip_frac/{me}' for me in range(on.mini_epochs_num)]
+    # the last mini-epoch's clip fraction against the host evaluation of each slot's logratio (slot mapping and counts
+    # inside the replayed graph)
+    mb = on.minibatch_size
+    old = on.dataset.values_dict['old_logp_actions'].reshape(-1)[:nmb * mb].reshape(nmb, mb)
+    nlp = on.diagnostics.debug_neglogp
+    assert not bool(torch.isnan(nlp).any())
+    lo, hi = ops.ppo_diag_log_bounds(on.e_clip)
+    lr = old - nlp
+    counts = ((lr < lo) | (lr > hi)).double().sum(1).cpu()
+    last = on.mini_epochs_num - 1
+    assert torch.equal(on.diagnostics._table[last, :, D.CLIPPED].cpu(), counts)
+    assert torch.equal(dd[f'diagnostics/clip_frac/{last}'], (counts / mb).mean().float())
+    # explained variance: the dataset's values / returns stay fixed through the epoch
+    vd = on.dataset.values_dict
+    v, r = vd['old_values'].reshape(-1).double().cpu(), vd['returns'].reshape(-1).double().cpu()
+    evs = []
+    for i in range(nmb):
+        vs, rs = v[i * mb:(i + 1) * mb], r[i * mb:(i + 1) * mb]
+        d = (r[i * mb:(i + 1) * mb].float() - v[i * mb:(i + 1) * mb].float()).double()
+        evs.append(1 - d.var(unbiased=False) / rs.var(unbiased=False))
+    assert abs(float(dd['diagnostics/exp_var']) - float(torch.stack(evs).mean())) <= 1e-6
+
+
+def test_value_size_two_epoch_with_diagnostics():
+    """value_size = 2 (the torch-form update): diagnostics on, one epoch through train_epoch; the explained variance is
+    over the rows x 2 elements of each minibatch slice (torch.var of the [rows, 2] tensor)."""
+    from rl_games_amd import configs
+    from rl_games_amd.agent import A2CAgent
+    N, H, V = 64, 8, 2
+    params = configs.tiny(num_actors=N, horizon=H, obs_dim=10, act_dim=4, use_diagnostics=True)
+    params['config']['env_config']['value_size'] = V
+    torch.manual_seed(3)
+    agent = A2CAgent('v2', copy.deepcopy(params))
+    assert agent.value_size == V and agent._engine is None
+    agent.init_tensors()
+    agent.obs = agent.env_reset()
+    agent.update_epoch()
+    agent.train_epoch()
+    vd = agent.dataset.values_dict
+    v, r = vd['old_values'].double().cpu(), vd['returns'].double().cpu()
+    agent.diagnostics.epoch(agent, current_epoch=1)
+    dd = agent.diagnostics.diag_dict
+    assert [k for k in dd if 'clip_frac' in k] == [f'diagnostics/clip_frac/{me}' for me in range(agent.mini_epochs_num)]
+    mb, nmb = agent.minibatch_size, len(agent.dataset)
+    evs = []
+    for i in range(nmb):
+        rs = r[i * mb:(i + 1) * mb]
+        d = (r[i * mb:(i + 1) * mb].float() - v[i * mb:(i + 1) * mb].float()).double()
+        evs.append(1 - d.var(unbiased=False) / rs.var(unbiased=False))
+    assert abs(float(dd['diagnostics/exp_var']) - float(torch.stack(evs).mean())) <= 1e-6
+    for me in range(agent.mini_epochs_num):
+        assert 0.0 <= float(dd[f'diagnostics/clip_frac/{me}']) <= 1.0
