@@ -142,6 +142,31 @@ int rlg_rollout_policy_head(const float* heads, int ld_heads, const float* logst
                             float* env_actions_out_or_null, const float* act_low, const float* act_high,
                             int num_envs, int horizon, int actions_num, int step, void* stream);
 
+/* Categorical rollout head (discrete_a2c / multi_discrete_a2c eval branch: rl_games/algos_torch/models.py:95-125,
+ * :157-206, CategoricalMasked common/extensions/distributions.py:24-47, denorm_value :58-60) fused with the
+ * update_data writes of its outputs (a2c_common.py:1008-1009).  logits [N, sum(sizes)] and value [N] (column 0) with
+ * any row strides (the chain's heads: one tensor [value | logits] for a shared trunk); branch_sizes a HOST array of
+ * num_branches <= 16 sizes (more: hipErrorNotSupported); masks bool [N, sum(sizes)] or NULL.  Writes actions_out
+ * [N, B] (int64, what env_step receives), de-normalised values_out [N], and slot `step` of the env-major buffer
+ * fields actions [N][H][B], neglogpacs [N][H], values [N][H].
+ *
+ * Numeric contract: per row and branch, in fp32, one rounding per op, the op sequence of DiscreteA2CModel.forward:
+ * masked logits set to exactly -1e8 (an all-masked row stays uniform); norm = l - (log(sum exp(l - m)) + m) with
+ * m = max l (0 when infinite); p = exp(norm - max norm) / sum; a = argmax p / q (lowest index on ties); neglogp =
+ * sum over the branches, left to right, of -norm[a].  The two exp sums are added in the order of torch's logsumexp
+ * and softmax kernels for branches of < 128 actions, so norm and p are torch's bits on the same logits (wider branches:
+ * last-bit differences).  Values: sqrt(var + eps) * clamp(v, -5, 5) + mean, as rlg_rollout_policy_head.
+ * RNG contract: exp_noise holds the Exp(1) draws q in branch-major blocks, block b = [N, sizes[b]] contiguous at
+ * N * (sizes[0] + ... + sizes[b-1]).  Drawing block b with exponential_ on the default generator, in branch order,
+ * is exactly what Categorical(logits).sample() draws (multinomial's one-sample path: argmax(probs / Exp(1))), so
+ * the actions are the torch path's, except where its top two p/q lie within a few ulps of each other. */
+int rlg_rollout_categorical_head(const float* logits, int ld_logits, const float* value, int ld_value,
+                                 const int* branch_sizes, int num_branches, const float* exp_noise,
+                                 const uint8_t* masks_or_null, int ld_masks, const double* v_mean_or_null,
+                                 const double* v_var_or_null, float eps, int64_t* actions_out, float* values_out,
+                                 int64_t* buf_actions, float* buf_neglogp, float* buf_values, int num_envs,
+                                 int horizon, int step, void* stream);
+
 /* play_steps_rnn zero-on-done: s[:, done_envs, :] = 0 (a2c_common.py:1150-1153).
  * states [layers][num_envs][units] contiguous. */
 int rlg_rnn_zero_done_states(float* states, const uint8_t* dones, int layers, int num_envs,

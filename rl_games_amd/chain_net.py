@@ -36,7 +36,7 @@ class ChainNet:
     weights (and biases) are adjacent in `arena`, in that order (arena_layout) - their columns side by side are the
     chain's last layer.  Raises NotImplementedError for networks outside the kernels' envelope."""
 
-    def __init__(self, trunk, heads, arena, max_rows):
+    def __init__(self, trunk, heads, arena, max_rows, infer_rows=0):
         self.linears = [m for m in trunk if isinstance(m, nn.Linear)]
         acts = [m for m in trunk if not isinstance(m, nn.Linear)]
         if not self.linears or len(acts) != len(self.linears):
@@ -69,6 +69,7 @@ class ChainNet:
         self.heads = torch.empty(max_rows, self.head_cols, device=dev)
         self.d_heads = torch.empty(max_rows, self.head_cols, device=dev)
         self.xn = torch.empty(max_rows, self.linears[0].in_features, device=dev)
+        self.infer_heads = torch.empty(infer_rows, self.head_cols, device=dev)
         nb = (max_rows + 15) // 16                          # one partial row per 16-row group at most
         self.partials = [torch.empty(nb * w, dtype=torch.float64, device=dev) for w in widths]
         self._plans = {}
@@ -87,6 +88,18 @@ class ChainNet:
         xn = self.xn[:rows] if rms is not None else None
         self.chain.forward(x, heads, act_out=[h[:rows] for h in self.Hs], rms=rms, eps=eps, xn_out=xn)
         self._rows, self._x = rows, (xn if rms is not None else x)
+        return heads
+
+    @torch.no_grad()
+    def infer(self, x, rms, eps):
+        """Inference forward of a rollout step: x [rows, in] RAW inputs with any row stride (e.g. the buffer slot of the
+        step), normalised inside the launch with the statistics as they are (eval mode).  Keeps no activations; the heads
+        go to a buffer of their own (`infer_rows` rows, grown when `rows` is larger).  Returns heads [rows, head_cols]."""
+        rows = x.shape[0]
+        if self.infer_heads.shape[0] < rows:
+            self.infer_heads = torch.empty(rows, self.head_cols, device=self.infer_heads.device)
+        heads = self.infer_heads[:rows]
+        self.chain.forward(x, heads, rms=rms, eps=eps)
         return heads
 
     @torch.no_grad()

@@ -13,6 +13,10 @@ Shares the rollout / GAE / dataset-preparation / optimiser path with `A2CAgent`;
     [value | logits] behind a shared trunk, one chain per trunk with `separate: True` (ppo_cartpole.yaml:17) - where the
     network has that form (plain Linear + ELU / ReLU / tanh trunks, widths that are multiples of 4, value_size 1);
     anything else, or `fused_mlp: False`, keeps autograd around the loss kernel (`torch.autograd.backward` on the heads);
+  * the rollout runs on the same chains (`fused_rollout`, _policy_step_kernels): each chain's inference forward, the
+    Exp(1) draws of Categorical.sample(), and one launch of the categorical head (csrc/rollout_categorical.hip) that
+    samples, scores and writes the step into the buffer - replayed as one HIP graph per step index like the continuous
+    agent's rollout;
   * the lr schedule is stepped once per mini-epoch on the mean KL (a2c_common.py:1271-1278),
     whatever `schedule_type` says, and `train_epoch` returns the 10-tuple without bound losses.
 """
@@ -80,10 +84,123 @@ class DiscreteA2CAgent(A2CAgent):
             rows = self.minibatch_size
             groups = self._chain_heads()
             trunks = [net.actor_mlp, net.critic_mlp] if net.is_separate_critic() else [net.actor_mlp]
-            self._chains = [ChainNet(t, g, self.optimizer, rows) for t, g in zip(trunks, groups)]
+            roll = self.num_actors * self.num_agents
+            self._chains = [ChainNet(t, g, self.optimizer, rows, infer_rows=roll) for t, g in zip(trunks, groups)]
         except NotImplementedError as e:
             print(f'rl_games_amd: discrete network outside the fused chain kernels ({e}); using autograd')
             self._chains = None
+
+    # ------------------------------------------------------------------ fused rollout
+    def _fast_rollout_ok(self):
+        """The rollout on the chains: feed-forward network on the fused chain kernels, one value column, no central value,
+        `fused_rollout` on (recurrent policies keep the torch path: _init_chains leaves them without chains)."""
+        return (self._chains is not None and not self.is_rnn and self.value_size == 1 and not self.has_central_value
+                and len(self.branch_sizes) <= ops.CATEGORICAL_MAX_BRANCHES and self.config.get('fused_rollout', True))
+
+    def init_tensors(self):
+        super().init_tensors()
+        if self._fast_rollout_ok():
+            rows, dev = self.num_actors * self.num_agents, self.ppo_device
+            # Exp(1) draws, branch b as a contiguous [rows, n_b] block (the tensor Categorical.sample() draws into)
+            self._roll_noise = torch.empty(rows * sum(self.branch_sizes), dtype=torch.float32, device=dev)
+            self._roll_actions = torch.empty((rows, len(self.branch_sizes)) if self.is_multi_discrete else (rows,),
+                                             dtype=torch.int64, device=dev)
+            self._roll_values = torch.empty(rows, dtype=torch.float32, device=dev)
+
+    @staticmethod
+    def _fp32_after_preproc(obs):
+        return obs.dtype in (torch.float32, torch.uint8)         # (_preproc_obs: uint8 / 255 -> fp32)
+
+    def _fast_policy_step(self, n):
+        """The step's action masks go into the buffer slot first (the head kernel reads them there); observations that
+        are not fp32 after preprocessing take the torch path for this step, as the update does."""
+        buf = self.experience_buffer
+        masks = None
+        if self.use_action_masks:                                # a2c_common.py:995-997
+            masks = torch.as_tensor(self.vec_env.get_action_masks(), dtype=torch.bool, device=self.ppo_device)
+        if not self._fp32_after_preproc(self.obs['obs']):
+            res = (self.get_action_values(self.obs) if masks is None
+                   else self.get_masked_action_values(self.obs, masks))
+            fields = {'obses': self.obs['obs'], 'dones': self.dones}
+            for k in self.update_list:
+                fields[k] = res[k]
+            buf.store_step(n, fields)
+            return res
+        if masks is not None:
+            buf.store_step(n, {'action_masks': masks.contiguous()})
+        return super()._fast_policy_step(n)
+
+    def _chain_heads_of(self, obs):
+        """(logits [N, sum(sizes)], value [N, 1]) of fp32 observations (any row stride): each chain's inference
+        forward, the observation normaliser in eval mode inside the launch."""
+        if obs.stride(-1) != 1:
+            obs = obs.contiguous()
+        heads = [c.infer(obs, self._obs_rms(), self._obs_eps()) for c in self._chains]
+        if len(heads) == 1:                                      # [value | logits]
+            return heads[0][:, 1:], heads[0][:, :1]
+        return heads[0], heads[1]
+
+    def _draw_exp_noise(self, rows):
+        """The Exp(1) draws of Categorical.sample() (multinomial's one-sample path): one exponential_ per branch, in
+        branch order, on a contiguous [rows, n_b] block."""
+        at = 0
+        for size in self.branch_sizes:
+            self._roll_noise[at:at + rows * size].view(rows, size).exponential_()
+            at += rows * size
+
+    def _policy_step_kernels(self, n, obs_raw, dones, rnn_states, store=True):
+        """Chain forward(s) -> Exp(1) draws -> categorical head (actions / neglogpacs / values into the buffer) -> obs +
+        dones into the buffer.  Same maths and the same generator use as get_(masked_)action_values + update_data; no
+        host read, so the step can be captured."""
+        buf = self.experience_buffer
+        logits, value = self._chain_heads_of(self._preproc_obs(obs_raw))
+        rows = value.shape[0]
+        self._draw_exp_noise(rows)
+        vs, eps = None, 1e-5
+        if self.normalize_value:
+            vm = self.model.value_mean_std
+            vs, eps = (vm.running_mean, vm.running_var), vm.epsilon
+        masks = buf.storage['action_masks'][:, n] if self.use_action_masks else None
+        ops.rollout_categorical_head(logits, value, self.branch_sizes, self._roll_noise, masks, vs, eps,
+                                     self._roll_actions, self._roll_values, buf.storage, self.horizon_length, n)
+        if store:
+            buf.store_step(n, {'obses': obs_raw if obs_raw.is_contiguous() else obs_raw.contiguous(), 'dones': dones})
+        return {'actions': self._roll_actions, 'values': self._roll_values.view(rows, 1)}
+
+    def _fast_values(self, obs):
+        """get_values on the chains: the critic column, de-normalised."""
+        x = obs['obs']
+        if not self._fp32_after_preproc(x):
+            return self.get_values(obs)
+        x = self._preproc_obs(x)
+        if x.stride(-1) != 1:
+            x = x.contiguous()
+        # the critic is column 0 of the last chain's heads ([value | logits], or the critic trunk's [value])
+        v = self._chains[-1].infer(x, self._obs_rms(), self._obs_eps())[:, :1].contiguous()
+        # get_values runs the model's whole eval forward, which samples actions: the same draws keep the generator where
+        # the torch path leaves it
+        self._draw_exp_noise(x.shape[0])
+        if self.normalize_value:
+            vm = self.model.value_mean_std
+            v = ops.rms_apply(v, vm.running_mean, vm.running_var, vm.epsilon, 1)
+        return v.view(-1)
+
+    def _planes_before_replay(self):
+        """The step graphs contain no pack launch: bring the forms the chains' inference forward reads (lean fragments or
+        split planes) up to the weights as they are - behind an optimiser step as behind restore() / set_weights."""
+        super()._planes_before_replay()
+        if self._chains is None:
+            return
+        rows = self.num_actors * self.num_agents
+        for c in self._chains:
+            if c.chain.lean_used(rows, 0):
+                c.chain.ensure_frags(self.optimizer.flat_params)
+            elif c.chain.split_products(rows, 0):
+                c.chain.ensure_planes(self.optimizer.flat_params)
+
+    def _chain_cache_states(self):
+        states = super()._chain_cache_states()
+        return states + [(c.chain, c.chain.cache_state()) for c in self._chains or ()]
 
     def _alloc_loss_scratch(self, mb, dev):
         self._d_logits = torch.empty(mb, sum(self.branch_sizes), dtype=torch.float32, device=dev)

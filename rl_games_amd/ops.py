@@ -129,6 +129,58 @@ def rollout_policy_head(heads, logstd, noise, value_stats, eps, actions_out, val
         N, horizon, A, step, _stream(heads)), 'rlg_rollout_policy_head')
 
 
+CATEGORICAL_MAX_BRANCHES = 16
+
+
+def _row_view(t, dtype, rows, cols, name):
+    """[rows, cols] view with unit column stride and any row stride -> (address, row stride)."""
+    _lib.require_gpu(t, name)
+    if t.dtype != dtype:
+        raise ValueError(f'{name}: expected {dtype}, got {t.dtype}')
+    if t.dim() != 2 or tuple(t.shape) != (rows, cols) or (cols > 1 and t.stride(1) != 1) or t.stride(0) < cols:
+        raise ValueError(f'{name}: expected a [{rows}, {cols}] view with unit column stride, got {tuple(t.shape)} '
+                         f'strides {t.stride()}')
+    return t.data_ptr(), t.stride(0)
+
+
+def rollout_categorical_head(logits, value, branch_sizes, noise, masks, value_stats, eps, actions_out, values_out,
+                             storage, horizon, step):
+    """Categorical rollout head (csrc/rollout_categorical.hip).  logits [N, sum(sizes)] and value [N, 1] (views of the
+    chain's heads, any row stride; value may also be [N]); noise: fp32 Exp(1) draws, >= N * sum(sizes), branch b's block [N, sizes[b]] at
+    N * sum(sizes[:b]); masks: bool [N, sum(sizes)] view (the buffer slot of the step) or None; value_stats =
+    (mean, var) or None; actions_out int64 [N] / [N, B]; values_out fp32 [N]; storage: ExperienceBuffer.storage
+    (env-major 'actions', 'neglogpacs', 'values').  Slot `step` of those fields is written."""
+    lib = _lib.load()
+    sizes = [int(s) for s in branch_sizes]
+    if value.dim() == 1:
+        value = value.unsqueeze(1)
+    N, S, B = value.shape[0], sum(sizes), len(sizes)
+    lg, ld_lg = _row_view(logits, F32, N, S, 'logits')
+    vp, ld_v = _row_view(value, F32, N, 1, 'value')
+    _need(noise, F32, 'noise')
+    if noise.numel() < N * S:
+        raise ValueError(f'noise: {noise.numel()} draws for {N} x {S}')
+    mp, ld_m = None, 0
+    if masks is not None:
+        mp, ld_m = _row_view(masks.view(U8) if masks.dtype == torch.bool else masks, U8, N, S, 'masks')
+    vm = vv = None
+    if value_stats is not None:
+        vm, vv = _need(value_stats[0], F64, 'value mean'), _need(value_stats[1], F64, 'value var')
+    if actions_out.numel() != N * B or values_out.numel() != N:
+        raise ValueError('actions_out [N, B] / values_out [N] expected')
+    fields = ((storage['actions'], torch.int64, N * horizon * B), (storage['neglogpacs'], F32, N * horizon),
+              (storage['values'], F32, N * horizon))
+    for t, dtype, numel in fields:
+        if t.numel() != numel:
+            raise ValueError(f'buffer field of {t.numel()} elements, expected {numel}')
+    arr = (ctypes.c_int * B)(*sizes)
+    _lib.check(lib.rlg_rollout_categorical_head(
+        lg, ld_lg, vp, ld_v, arr, B, noise.data_ptr(), mp, ld_m, vm, vv, float(np.float32(eps)),
+        _need(actions_out, torch.int64, 'actions_out'), _need(values_out, F32, 'values_out'),
+        *[_need(t, dtype, 'buffer field') for t, dtype, _ in fields], N, horizon, step, _stream(value)),
+        'rlg_rollout_categorical_head')
+
+
 def rnn_zero_done_states(states, dones):
     lib = _lib.load()
     L, N, U = states.shape
