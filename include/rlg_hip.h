@@ -142,6 +142,21 @@ int rlg_rollout_policy_head(const float* heads, int ld_heads, const float* logst
                             float* env_actions_out_or_null, const float* act_low, const float* act_high,
                             int num_envs, int horizon, int actions_num, int step, void* stream);
 
+/* rlg_rollout_policy_head with the value taken from a separate column: the rollout of an agent with a central value
+ * network (a2c_common.py:593-600, central_value.py:208-228), whose critic's value replaces the actor's.
+ * Value-source contract: row r (env-major, r = env * value_repeat + agent) reads value[(r / value_repeat) * ld_value],
+ * de-normalised with the statistics passed here (the critic's value_mean_std), and the heads' column 0 is not read:
+ * value.repeat(1, A).view(N * A, -1) of central_value.py:223-225 with value_repeat = A.  value_repeat < 1 or
+ * ld_value < 1: hipErrorInvalidValue.  Numeric contract as rlg_rollout_policy_head, whose outputs are this entry's
+ * with (value, ld_value, value_repeat) = (heads, ld_heads, 1), bit for bit. */
+int rlg_rollout_policy_head_cv(const float* heads, int ld_heads, const float* value, int ld_value, int value_repeat,
+                               const float* logstd, const float* noise, const double* value_mean_or_null,
+                               const double* value_var_or_null, float eps, float* actions_out, float* values_out,
+                               float* buf_actions, float* buf_mus, float* buf_sigmas, float* buf_neglogp,
+                               float* buf_values, float* env_actions_out_or_null, const float* act_low,
+                               const float* act_high, int num_envs, int horizon, int actions_num, int step,
+                               void* stream);
+
 /* Categorical rollout head (discrete_a2c / multi_discrete_a2c eval branch: rl_games/algos_torch/models.py:95-125,
  * :157-206, CategoricalMasked common/extensions/distributions.py:24-47, denorm_value :58-60) fused with the
  * update_data writes of its outputs (a2c_common.py:1008-1009).  logits [N, sum(sizes)] and value [N] (column 0) with
@@ -166,6 +181,17 @@ int rlg_rollout_categorical_head(const float* logits, int ld_logits, const float
                                  const double* v_var_or_null, float eps, int64_t* actions_out, float* values_out,
                                  int64_t* buf_actions, float* buf_neglogp, float* buf_values, int num_envs,
                                  int horizon, int step, void* stream);
+
+/* rlg_rollout_categorical_head with value_repeat rows per value row (a central value network's one state row per env
+ * for num_agents = value_repeat agents).  Value-source contract: row r reads value[(r / value_repeat) * ld_value];
+ * value_repeat < 1: hipErrorInvalidValue.  Numeric and RNG contracts as rlg_rollout_categorical_head, which is this
+ * entry with value_repeat = 1. */
+int rlg_rollout_categorical_head_cv(const float* logits, int ld_logits, const float* value, int ld_value,
+                                    int value_repeat, const int* branch_sizes, int num_branches,
+                                    const float* exp_noise, const uint8_t* masks_or_null, int ld_masks,
+                                    const double* v_mean_or_null, const double* v_var_or_null, float eps,
+                                    int64_t* actions_out, float* values_out, int64_t* buf_actions, float* buf_neglogp,
+                                    float* buf_values, int num_envs, int horizon, int step, void* stream);
 
 /* play_steps_rnn zero-on-done: s[:, done_envs, :] = 0 (a2c_common.py:1150-1153).
  * states [layers][num_envs][units] contiguous. */

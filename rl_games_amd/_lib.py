@@ -47,9 +47,13 @@ _PROTOTYPES = {
     'rlg_rnn_zero_done_states': [_P, _P, _c_int, _c_int, _c_int, _P],
     'rlg_rollout_policy_head': [_P, _c_int, _P, _P, _P, _P, _c_float, _P, _P, _P, _P, _P, _P, _P,
                                 _P, _P, _P, _c_int, _c_int, _c_int, _c_int, _P],
+    'rlg_rollout_policy_head_cv': [_P, _c_int, _P, _c_int, _c_int, _P, _P, _P, _P, _c_float, _P, _P, _P, _P, _P, _P,
+                                   _P, _P, _P, _P, _c_int, _c_int, _c_int, _c_int, _P],
     # rollout_categorical.hip
     'rlg_rollout_categorical_head': [_P, _c_int, _P, _c_int, ctypes.POINTER(_c_int), _c_int, _P, _P, _c_int, _P, _P,
                                      _c_float, _P, _P, _P, _P, _P, _c_int, _c_int, _c_int, _P],
+    'rlg_rollout_categorical_head_cv': [_P, _c_int, _P, _c_int, _c_int, ctypes.POINTER(_c_int), _c_int, _P, _P, _c_int,
+                                        _P, _P, _c_float, _P, _P, _P, _P, _P, _c_int, _c_int, _c_int, _P],
     # running_stats.hip
     'rlg_column_moments_num_blocks': [_c_ll, _c_int],
     'rlg_column_moments': [_P, _P, _c_ll, _c_int, _P, _c_int, _P],

@@ -669,6 +669,9 @@ class A2CAgent:
             self._roll_noise = torch.empty(rows, self.actions_num, dtype=torch.float32, device=dev)
             self._roll_actions = torch.empty(rows, self.actions_num, dtype=torch.float32, device=dev)
             self._roll_values = torch.empty(rows, dtype=torch.float32, device=dev)
+        if self._critic_chain() is not None and self._fast_rollout_ok():
+            # the critic's rollout heads [num_actors, 1]: allocated here, not inside the first step's capture
+            self._critic_chain().reserve_infer(self.num_actors)
         if self.is_rnn:
             self.rnn_states = [s.to(dev) for s in self.model.get_default_rnn_state()]
             num_seqs = self.horizon_length // self.seq_length
@@ -770,28 +773,39 @@ class A2CAgent:
         on the launches of a step are replayed as one HIP graph per step index; its inputs must live at
         fixed addresses: the buffer slot of the step (plain float observations) or static copies of the
         env-owned tensors (recurrent policies, integer observations)."""
+        states = self.obs['states'] if self.has_central_value else None
         if not self._rollout_graphs_usable():
-            return self._policy_step_kernels(n, self.obs['obs'], self.dones, self.rnn_states)
+            return self._policy_step_kernels(n, self.obs['obs'], self.dones, self.rnn_states, states=states)
         key = (id(self.experience_buffer), tuple(self.obs['obs'].shape), self.obs['obs'].dtype)
+        if states is not None:
+            key += (tuple(states.shape), states.dtype)
         buf = self.experience_buffer
         obs = self.obs['obs']
-        # Plain float observations without recurrent state: the step's observations / done flags go from the
-        # env's tensors straight into the buffer (the one launch that had to happen anyway) and the captured
-        # forward reads the observations from that buffer slot - no staging copies in front of the graph.
+        # Plain float observations without recurrent state: the step's observations / done flags (and a central value
+        # network's states) go from the env's tensors straight into the buffer (the one launch that had to happen
+        # anyway) and the captured forwards read them from that buffer slot - no staging copies in front of the graph.
         direct = (not self.is_rnn and obs.dtype == torch.float32 and obs.dim() == 2 and obs.is_contiguous()
-                  and torch.is_tensor(buf.storage['obses']) and self.config.get('rollout_obs_from_buffer', True))
+                  and torch.is_tensor(buf.storage['obses']) and self.config.get('rollout_obs_from_buffer', True)
+                  and (states is None or (states.dtype == torch.float32 and states.dim() == 2
+                                          and states.is_contiguous() and torch.is_tensor(buf.storage['states']))))
         if self._rollout_graph_key != key:
             self._rollout_graphs.clear()
             self._rollout_graph_key = key
             self._rollout_static = None
         if direct:
-            buf.store_step(n, {'obses': obs, 'dones': self.dones})
-            args = (n, buf.storage['obses'][:, n, :], None, None, False)
+            fields = {'obses': obs, 'dones': self.dones}
+            if states is not None:
+                fields['states'] = states
+            buf.store_step(n, fields)
+            args = (n, buf.storage['obses'][:, n, :], None, None, False,
+                    None if states is None else buf.storage['states'][:, n, :])
         else:
             if self._rollout_static is None:
                 st = {'obs': torch.empty_like(obs).contiguous(), 'dones': torch.empty_like(self.dones)}
                 if self.is_rnn:
                     st['rnn'] = [torch.empty_like(s) for s in self.rnn_states]
+                if states is not None:
+                    st['states'] = torch.empty_like(states).contiguous()
                 self._rollout_static = st
             st = self._rollout_static
             st['obs'].copy_(obs)
@@ -799,7 +813,9 @@ class A2CAgent:
             if self.is_rnn:
                 for dst, src in zip(st['rnn'], self.rnn_states):
                     dst.copy_(src)
-            args = (n, st['obs'], st['dones'], st.get('rnn'), True)
+            if states is not None:
+                st['states'].copy_(states)
+            args = (n, st['obs'], st['dones'], st.get('rnn'), True, st.get('states'))
         entry = self._rollout_graphs.get((n, direct))
         if entry is None:
             if self._graph_pool is None:
@@ -819,10 +835,10 @@ class A2CAgent:
         return (self._hip_graphs and self.config.get('rollout_graphs', True) and self._eager_epochs >= 1
                 and not self._graph_failed and isinstance(self.obs['obs'], torch.Tensor))
 
-    def _policy_step_kernels(self, n, obs_raw, dones, rnn_states, store=True):
-        """obs normalise -> engine GEMMs -> fused policy-head kernel that also writes actions / mus /
-        sigmas / neglogpacs / values of the step into the buffer -> obs + dones into the buffer ->
-        action clamp/rescale for the env.  Same maths as get_action_values + update_data +
+    def _policy_step_kernels(self, n, obs_raw, dones, rnn_states, store=True, states=None):
+        """obs normalise -> engine GEMMs -> (central value: the critic's chain forward on `states`) -> fused policy-head
+        kernel that also writes actions / mus / sigmas / neglogpacs / values of the step into the buffer -> obs + dones
+        (+ states) into the buffer -> action clamp/rescale for the env.  Same maths as get_action_values + update_data +
         preprocess_actions; no autograd, nothing that depends on the host."""
         eng, buf = self._engine, self.experience_buffer
         obs = self._preproc_obs(obs_raw)
@@ -846,12 +862,9 @@ class A2CAgent:
                 heads = eng.forward(obs_n, keep=False, rnn_states=rnn_states, seq_length=1)
             else:
                 heads = eng.forward(obs_n, keep=False)
+        value = self._critic_infer(states) if self.has_central_value else None
         torch.randn(self._roll_noise.shape, device=self._roll_noise.device, out=self._roll_noise)
-        vs = None
-        eps = 1e-5
-        if self.normalize_value:
-            vm = self.model.value_mean_std
-            vs, eps = (vm.running_mean, vm.running_var), vm.epsilon
+        vs, eps = self._rollout_value_stats()
         env_actions = None
         if self.clip_actions:
             # clamp + rescale for the env ride along in the same launch (3 element-wise launches less per step)
@@ -860,19 +873,78 @@ class A2CAgent:
             env_actions = (self._roll_env_actions, self.actions_low, self.actions_high)
         ops.rollout_policy_head(heads, self.model.a2c_network.sigma.data, self._roll_noise, vs, eps,
                                 self._roll_actions, self._roll_values, buf.storage, self.horizon_length, n,
-                                env_actions=env_actions)
+                                env_actions=env_actions, value=value, value_repeat=self.num_agents if value is not None else 1)
         # the buffer keeps the observation as the env delivered it (a2c_common.py:1000), not the
         # /255-preprocessed copy
         if store:
-            buf.store_step(n, {'obses': obs_raw if obs_raw.is_contiguous() else obs_raw.contiguous(), 'dones': dones})
+            self._store_step_inputs(n, obs_raw, dones, states)
         res = {'actions': self._roll_actions, 'values': self._roll_values.view(rows, 1)}
         res['env_actions'] = self._roll_env_actions if self.clip_actions else self._roll_actions
         if self.is_rnn:
             res['rnn_states'] = eng.last_states
         return res
 
+    def _store_step_inputs(self, n, obs_raw, dones, states):
+        """update_data('obses' / 'dones' (/ 'states'), n) of a fused step (a2c_common.py:1000-1011): one launch per row
+        count (a multi-agent env's states have one row per env)."""
+        fields = {'obses': obs_raw if obs_raw.is_contiguous() else obs_raw.contiguous(), 'dones': dones}
+        if states is not None:
+            fields['states'] = states
+        self.experience_buffer.store_step(n, fields)
+
+    def _critic_chain(self):
+        """The central value network on the fused chain kernels (chain_net.ChainNet), or None."""
+        cv = getattr(self, 'central_value_net', None)
+        return None if cv is None else cv._engine
+
+    def _critic_infer(self, states):
+        """CentralValueTrain.get_value's forward on the chain (central_value.py:208-222, ModelCentralValue.forward
+        models.py:452-458): the states normalised in eval mode inside the launch; raw values [num_actors, 1] (any row
+        stride of `states`)."""
+        cv = self.central_value_net
+        if states.stride(-1) != 1:
+            states = states.contiguous()
+        rms, eps = None, 1e-5
+        if cv.normalize_input:
+            m = cv.model.running_mean_std
+            rms, eps = (m.running_mean, m.running_var), m.epsilon
+        return cv._engine.infer(states, rms, eps)
+
+    def _rollout_value_stats(self):
+        """(mean, var) and epsilon of the value de-normaliser of the rollout: the critic's with a central value network
+        (its values replace the actor's, a2c_common.py:593-600), else the actor model's; (None, 1e-5) when off."""
+        if not self.normalize_value:
+            return None, 1e-5
+        vm = self.central_value_net.model.value_mean_std if self.has_central_value else self.model.value_mean_std
+        return (vm.running_mean, vm.running_var), vm.epsilon
+
+    def _central_fast_values(self, states):
+        """get_values with a central value network (a2c_common.py:605-614): the critic's forward only - the actor does
+        not run and nothing is drawn from the generator - de-normalised, every agent of an env given the env's value
+        (central_value.py:223-225).  [num_actors * num_agents]."""
+        v = self._critic_infer(states)
+        vs, eps = self._rollout_value_stats()
+        if vs is not None:
+            v = ops.rms_apply(v.contiguous(), vs[0], vs[1], eps, 1)
+        return v.expand(-1, self.num_agents).reshape(-1)
+
+    def _critic_forms_before_replay(self):
+        """The step graphs contain no pack launch: bring the forms the critic chain's inference forward reads at the
+        rollout's row count (lean fragments or split planes) up to the critic's weights as they are - behind its own
+        Adam steps as behind restore() / set_central_value_function_weights / a broadcast."""
+        c = self._critic_chain()
+        if c is None:
+            return
+        chain, arena = c.chain, self.central_value_net.optimizer.flat_params
+        if chain.lean_used(self.num_actors, 0):
+            chain.ensure_frags(arena)
+        elif chain.split_products(self.num_actors, 0):
+            chain.ensure_planes(arena)
+
     def _fast_values(self, obs):
         """get_values on the engine: de-normalised critic values [N] of `obs`."""
+        if self.has_central_value:
+            return self._central_fast_values(obs['states'])
         eng = self._engine
         x = self._preproc_obs(obs['obs'])
         if not x.is_contiguous():
@@ -905,8 +977,16 @@ class A2CAgent:
     def _obs_eps(self):
         return self.model.running_mean_std.epsilon if self.normalize_input else 1e-5
 
+    def _central_value_fused_ok(self):
+        """No central value network, or one the fused step can run: a critic on the chain kernels (feed-forward, one
+        value column, `fused_mlp` not off in its config) over fp32 states.  Recurrent critics keep the torch rollout."""
+        if not self.has_central_value:
+            return True
+        dtype = getattr(self.state_space, 'dtype', None)
+        return (self._critic_chain() is not None and dtype is not None and np.dtype(dtype) == np.float32)
+
     def _fast_rollout_ok(self):
-        return (self._engine is not None and self.value_size == 1 and not self.has_central_value
+        return (self._engine is not None and self.value_size == 1 and self._central_value_fused_ok()
                 and self.config.get('fused_rollout', True))
 
     def play_steps(self):
@@ -921,6 +1001,7 @@ class A2CAgent:
             # the step graphs contain no pack launch: the weights' derived forms (plane fragments of both kernel families) must belong
             # to the weights as they are - they do behind an optimiser step, not behind set_weights / a broadcast
             self._planes_before_replay()
+            self._critic_forms_before_replay()
         if self.mask_autoreset_rows:
             mb_valid = torch.ones((self.horizon_length, self.num_actors * self.num_agents),
                                   dtype=torch.float32, device=self.ppo_device)
@@ -964,6 +1045,7 @@ class A2CAgent:
         fast = self._fast_rollout_ok()
         if fast:
             self._planes_before_replay()          # (see play_steps)
+            self._critic_forms_before_replay()
         if self.mask_autoreset_rows:
             mb_valid = torch.ones((self.horizon_length, rows), dtype=torch.float32, device=self.ppo_device)
         for n in range(self.horizon_length):
@@ -1551,6 +1633,8 @@ class A2CAgent:
     def _chain_cache_states(self):
         eng = self._engine
         chains = [c for c in (getattr(eng, 'chain', None), getattr(eng, 'chain_rnn', None)) if c is not None]
+        if self._critic_chain() is not None:
+            chains.append(self._critic_chain().chain)
         return [(c, c.cache_state()) for c in chains]
 
     @staticmethod

@@ -96,11 +96,15 @@ class ChainNet:
         step), normalised inside the launch with the statistics as they are (eval mode).  Keeps no activations; the heads
         go to a buffer of their own (`infer_rows` rows, grown when `rows` is larger).  Returns heads [rows, head_cols]."""
         rows = x.shape[0]
-        if self.infer_heads.shape[0] < rows:
-            self.infer_heads = torch.empty(rows, self.head_cols, device=self.infer_heads.device)
+        self.reserve_infer(rows)
         heads = self.infer_heads[:rows]
         self.chain.forward(x, heads, rms=rms, eps=eps)
         return heads
+
+    def reserve_infer(self, rows):
+        """Allocate infer()'s heads buffer for `rows` rows now (not on first use, e.g. inside a graph capture)."""
+        if self.infer_heads.shape[0] < rows:
+            self.infer_heads = torch.empty(rows, self.head_cols, device=self.infer_heads.device)
 
     @torch.no_grad()
     def backward(self):

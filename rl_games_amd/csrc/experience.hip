@@ -260,10 +260,15 @@ __global__ __launch_bounds__(256) void episode_meters_kernel(
 //   sigma = exp(logstd);  action = mu + sigma * noise   (= Normal(mu, sigma).sample())
 //   neglogp = 0.5*sum(((action-mu)/sigma)^2) + 0.5*log(2pi)*A + sum(logstd)
 //   value   = sqrt(var+eps)*clamp(v,-5,5) + mean        (running_mean_std.py:106-107)
-// heads: [N, 1+A] fused (value | mu) output of the MLP.  One thread per env.
+// heads: [N, 1+A] fused (value | mu) output of the MLP.  One thread per env.  The value of row r is read from
+// value[(r / value_repeat) * ld_value]: column 0 of the heads (value = heads, ld_value = ld, value_repeat = 1), or a
+// central value network's output with one row per env for num_agents = value_repeat rows (central_value.py:223-225).
 struct PolicyHeadArgs {
   const float* heads;      // [N, ld]
   int ld;
+  const float* value;      // [ceil(N / value_repeat), ld_value], column 0
+  long long ld_value;
+  int value_repeat;
   const float* logstd;     // [A]
   const float* noise;      // [N, A] standard normal
   const double* v_mean;    // value RunningMeanStd (fp64) or nullptr when normalize_value is off
@@ -309,7 +314,7 @@ __global__ __launch_bounds__(256) void rollout_policy_head_kernel(PolicyHeadArgs
     }
     const float nlp = (0.5f * s_z2 + static_cast<float>(0.9189385332046727 * p.A)) + s_ls;
     p.buf_neglogp[slot] = nlp;
-    float v = h[0];
+    float v = p.value[static_cast<long long>(env / p.value_repeat) * p.ld_value];
     if (p.v_mean) {
       const float m = static_cast<float>(p.v_mean[0]);
       const float d = sqrt_rn(static_cast<float>(p.v_var[0]) + p.eps);
@@ -375,7 +380,7 @@ __global__ __launch_bounds__(kB) void rollout_policy_head_lds_kernel(PolicyHeadA
     }
     const float nlp = (0.5f * s_z2 + static_cast<float>(0.9189385332046727 * p.A)) + s_ls;
     p.buf_neglogp[slot] = nlp;
-    float v = h[0];
+    float v = p.value[static_cast<long long>(env / p.value_repeat) * p.ld_value];
     if (p.v_mean) {
       const float m = static_cast<float>(p.v_mean[0]);
       const float d = sqrt_rn(static_cast<float>(p.v_var[0]) + p.eps);
@@ -517,18 +522,22 @@ int rlg_episode_meters_update(const double* ep_partials, int horizon, int num_bl
   RLG_RETURN_LAUNCH_STATUS();
 }
 
-int rlg_rollout_policy_head(const float* heads, int ld_heads, const float* logstd, const float* noise,
-                            const double* value_mean_or_null, const double* value_var_or_null,
-                            float eps, float* actions_out, float* values_out, float* buf_actions,
-                            float* buf_mus, float* buf_sigmas, float* buf_neglogp, float* buf_values,
-                            float* env_actions_out, const float* act_low, const float* act_high,
-                            int num_envs, int horizon, int actions_num, int step, void* stream) {
+int rlg_rollout_policy_head_cv(const float* heads, int ld_heads, const float* value, int ld_value, int value_repeat,
+                               const float* logstd, const float* noise, const double* value_mean_or_null,
+                               const double* value_var_or_null, float eps, float* actions_out, float* values_out,
+                               float* buf_actions, float* buf_mus, float* buf_sigmas, float* buf_neglogp,
+                               float* buf_values, float* env_actions_out, const float* act_low, const float* act_high,
+                               int num_envs, int horizon, int actions_num, int step, void* stream) {
   if (num_envs <= 0) return 0;
   if (step < 0 || step >= horizon || actions_num <= 0) return static_cast<int>(hipErrorInvalidValue);
   if (env_actions_out && (!act_low || !act_high)) return static_cast<int>(hipErrorInvalidValue);
+  if (!value || ld_value < 1 || value_repeat < 1) return static_cast<int>(hipErrorInvalidValue);
   rlg::PolicyHeadArgs p;
   p.heads = heads;
   p.ld = ld_heads;
+  p.value = value;
+  p.ld_value = ld_value;
+  p.value_repeat = value_repeat;
   p.logstd = logstd;
   p.noise = noise;
   p.v_mean = value_mean_or_null;
@@ -566,6 +575,18 @@ int rlg_rollout_policy_head(const float* heads, int ld_heads, const float* logst
                        static_cast<hipStream_t>(stream), p);
   }
   RLG_RETURN_LAUNCH_STATUS();
+}
+
+int rlg_rollout_policy_head(const float* heads, int ld_heads, const float* logstd, const float* noise,
+                            const double* value_mean_or_null, const double* value_var_or_null,
+                            float eps, float* actions_out, float* values_out, float* buf_actions,
+                            float* buf_mus, float* buf_sigmas, float* buf_neglogp, float* buf_values,
+                            float* env_actions_out, const float* act_low, const float* act_high,
+                            int num_envs, int horizon, int actions_num, int step, void* stream) {
+  return rlg_rollout_policy_head_cv(heads, ld_heads, heads, ld_heads, 1, logstd, noise, value_mean_or_null,
+                                    value_var_or_null, eps, actions_out, values_out, buf_actions, buf_mus, buf_sigmas,
+                                    buf_neglogp, buf_values, env_actions_out, act_low, act_high, num_envs, horizon,
+                                    actions_num, step, stream);
 }
 
 int rlg_rnn_zero_done_states(float* states, const uint8_t* dones, int layers, int num_envs,

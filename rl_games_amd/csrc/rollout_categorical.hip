@@ -27,7 +27,7 @@ constexpr int kCatWaveBlock = 256;      // wave form: 4 rows per workgroup
 
 struct CategoricalHeadArgs {
   const float* logits;      // [N, ld_logits], columns 0 .. S-1
-  const float* value;       // [N, ld_value], column 0
+  const float* value;       // [ceil(N / value_repeat), ld_value], column 0: row r reads row r / value_repeat
   const float* noise;       // branch-major blocks: block b = [N, size[b]] contiguous at N * off[b]
   const uint8_t* masks;     // [N, ld_masks] bool, or nullptr
   const double* v_mean;     // value RunningMeanStd (fp64) or nullptr when normalize_value is off
@@ -40,6 +40,7 @@ struct CategoricalHeadArgs {
   long long ld_logits, ld_value, ld_masks;
   float eps;
   int N, H, step, B, S;
+  int value_repeat;         // rows per value row (a central value network's num_agents; 1: one value per row)
   int pow2;                 // next power of two >= the widest branch
   int size[kMaxBranches];
   int off[kMaxBranches];    // first column of each branch
@@ -109,7 +110,7 @@ __global__ __launch_bounds__(kCatTileRows) void rollout_categorical_tile_kernel(
   float* const snlp = cat_lds + 2 * kCatTileRows * ld;
   float* const scratch = snlp + kCatTileRows * B + threadIdx.x * (p.pow2 + 1);
   const int t = threadIdx.x;
-  const float v = t < rows ? p.value[static_cast<long long>(env0 + t) * p.ld_value] : 0.0f;
+  const float v = t < rows ? p.value[static_cast<long long>((env0 + t) / p.value_repeat) * p.ld_value] : 0.0f;
   for (int i = t; i < rows * S; i += kCatTileRows) {
     const int r = i / S;
     const int c = i - r * S;
@@ -222,7 +223,7 @@ __global__ __launch_bounds__(kCatWaveBlock) void rollout_categorical_wave_kernel
   }
   if (lane == 0) {
     const long long slot = env * p.H + p.step;
-    const float vd = denorm_value(p, p.value[env * p.ld_value]);
+    const float vd = denorm_value(p, p.value[(env / p.value_repeat) * p.ld_value]);
     p.buf_neglogp[slot] = nlp;
     p.values_out[env] = vd;
     p.buf_values[slot] = vd;
@@ -233,18 +234,20 @@ __global__ __launch_bounds__(kCatWaveBlock) void rollout_categorical_wave_kernel
 
 extern "C" {
 
-int rlg_rollout_categorical_head(const float* logits, int ld_logits, const float* value, int ld_value,
-                                 const int* branch_sizes, int num_branches, const float* exp_noise,
-                                 const uint8_t* masks_or_null, int ld_masks, const double* v_mean_or_null,
-                                 const double* v_var_or_null, float eps, int64_t* actions_out, float* values_out,
-                                 int64_t* buf_actions, float* buf_neglogp, float* buf_values, int num_envs,
-                                 int horizon, int step, void* stream) {
+int rlg_rollout_categorical_head_cv(const float* logits, int ld_logits, const float* value, int ld_value,
+                                    int value_repeat, const int* branch_sizes, int num_branches,
+                                    const float* exp_noise, const uint8_t* masks_or_null, int ld_masks,
+                                    const double* v_mean_or_null, const double* v_var_or_null, float eps,
+                                    int64_t* actions_out, float* values_out, int64_t* buf_actions, float* buf_neglogp,
+                                    float* buf_values, int num_envs, int horizon, int step, void* stream) {
   using namespace rlg;
   if (num_envs <= 0) return 0;
   if (num_branches > kMaxBranches) return static_cast<int>(hipErrorNotSupported);
-  if (num_branches < 1 || !branch_sizes || step < 0 || step >= horizon || (v_mean_or_null && !v_var_or_null))
+  if (num_branches < 1 || !branch_sizes || step < 0 || step >= horizon || (v_mean_or_null && !v_var_or_null) ||
+      value_repeat < 1)
     return static_cast<int>(hipErrorInvalidValue);
   CategoricalHeadArgs p;
+  p.value_repeat = value_repeat;
   p.B = num_branches;
   p.S = 0;
   for (int b = 0; b < num_branches; ++b) {
@@ -287,6 +290,18 @@ int rlg_rollout_categorical_head(const float* logits, int ld_logits, const float
                        dim3(kCatWaveBlock), 0, static_cast<hipStream_t>(stream), p);
   }
   RLG_RETURN_LAUNCH_STATUS();
+}
+
+int rlg_rollout_categorical_head(const float* logits, int ld_logits, const float* value, int ld_value,
+                                 const int* branch_sizes, int num_branches, const float* exp_noise,
+                                 const uint8_t* masks_or_null, int ld_masks, const double* v_mean_or_null,
+                                 const double* v_var_or_null, float eps, int64_t* actions_out, float* values_out,
+                                 int64_t* buf_actions, float* buf_neglogp, float* buf_values, int num_envs,
+                                 int horizon, int step, void* stream) {
+  return rlg_rollout_categorical_head_cv(logits, ld_logits, value, ld_value, 1, branch_sizes, num_branches, exp_noise,
+                                         masks_or_null, ld_masks, v_mean_or_null, v_var_or_null, eps, actions_out,
+                                         values_out, buf_actions, buf_neglogp, buf_values, num_envs, horizon, step,
+                                         stream);
 }
 
 }  // extern "C"

@@ -92,9 +92,10 @@ class DiscreteA2CAgent(A2CAgent):
 
     # ------------------------------------------------------------------ fused rollout
     def _fast_rollout_ok(self):
-        """The rollout on the chains: feed-forward network on the fused chain kernels, one value column, no central value,
-        `fused_rollout` on (recurrent policies keep the torch path: _init_chains leaves them without chains)."""
-        return (self._chains is not None and not self.is_rnn and self.value_size == 1 and not self.has_central_value
+        """The rollout on the chains: feed-forward network on the fused chain kernels, one value column, no central value
+        or a feed-forward one on the chains (_central_value_fused_ok), `fused_rollout` on (recurrent policies keep the
+        torch path: _init_chains leaves them without chains)."""
+        return (self._chains is not None and not self.is_rnn and self.value_size == 1 and self._central_value_fused_ok()
                 and len(self.branch_sizes) <= ops.CATEGORICAL_MAX_BRANCHES and self.config.get('fused_rollout', True))
 
     def init_tensors(self):
@@ -124,21 +125,25 @@ class DiscreteA2CAgent(A2CAgent):
             fields = {'obses': self.obs['obs'], 'dones': self.dones}
             for k in self.update_list:
                 fields[k] = res[k]
+            if self.has_central_value:
+                fields['states'] = self.obs['states']
             buf.store_step(n, fields)
             return res
         if masks is not None:
             buf.store_step(n, {'action_masks': masks.contiguous()})
         return super()._fast_policy_step(n)
 
-    def _chain_heads_of(self, obs):
+    def _chain_heads_of(self, obs, logits_only=False):
         """(logits [N, sum(sizes)], value [N, 1]) of fp32 observations (any row stride): each chain's inference
-        forward, the observation normaliser in eval mode inside the launch."""
+        forward, the observation normaliser in eval mode inside the launch.  logits_only (a central value network
+        supplies the values): the separate critic trunk does not run, value is None."""
         if obs.stride(-1) != 1:
             obs = obs.contiguous()
-        heads = [c.infer(obs, self._obs_rms(), self._obs_eps()) for c in self._chains]
-        if len(heads) == 1:                                      # [value | logits]
+        chains = self._chains[:1] if logits_only else self._chains
+        heads = [c.infer(obs, self._obs_rms(), self._obs_eps()) for c in chains]
+        if len(self._chains) == 1:                               # [value | logits]
             return heads[0][:, 1:], heads[0][:, :1]
-        return heads[0], heads[1]
+        return heads[0], (None if logits_only else heads[1])
 
     def _draw_exp_noise(self, rows):
         """The Exp(1) draws of Categorical.sample() (multinomial's one-sample path): one exponential_ per branch, in
@@ -148,27 +153,30 @@ class DiscreteA2CAgent(A2CAgent):
             self._roll_noise[at:at + rows * size].view(rows, size).exponential_()
             at += rows * size
 
-    def _policy_step_kernels(self, n, obs_raw, dones, rnn_states, store=True):
-        """Chain forward(s) -> Exp(1) draws -> categorical head (actions / neglogpacs / values into the buffer) -> obs +
-        dones into the buffer.  Same maths and the same generator use as get_(masked_)action_values + update_data; no
-        host read, so the step can be captured."""
+    def _policy_step_kernels(self, n, obs_raw, dones, rnn_states, store=True, states=None):
+        """Chain forward(s) -> (central value: the critic's chain forward on `states`) -> Exp(1) draws -> categorical
+        head (actions / neglogpacs / values into the buffer) -> obs + dones (+ states) into the buffer.  Same maths and
+        the same generator use as get_(masked_)action_values + update_data; no host read, so the step can be captured."""
         buf = self.experience_buffer
-        logits, value = self._chain_heads_of(self._preproc_obs(obs_raw))
-        rows = value.shape[0]
+        cv = self.has_central_value
+        logits, value = self._chain_heads_of(self._preproc_obs(obs_raw), logits_only=cv)
+        if cv:
+            value = self._critic_infer(states)
+        rows = logits.shape[0]
         self._draw_exp_noise(rows)
-        vs, eps = None, 1e-5
-        if self.normalize_value:
-            vm = self.model.value_mean_std
-            vs, eps = (vm.running_mean, vm.running_var), vm.epsilon
+        vs, eps = self._rollout_value_stats()
         masks = buf.storage['action_masks'][:, n] if self.use_action_masks else None
         ops.rollout_categorical_head(logits, value, self.branch_sizes, self._roll_noise, masks, vs, eps,
-                                     self._roll_actions, self._roll_values, buf.storage, self.horizon_length, n)
+                                     self._roll_actions, self._roll_values, buf.storage, self.horizon_length, n,
+                                     value_repeat=self.num_agents if cv else 1)
         if store:
-            buf.store_step(n, {'obses': obs_raw if obs_raw.is_contiguous() else obs_raw.contiguous(), 'dones': dones})
+            self._store_step_inputs(n, obs_raw, dones, states)
         return {'actions': self._roll_actions, 'values': self._roll_values.view(rows, 1)}
 
     def _fast_values(self, obs):
         """get_values on the chains: the critic column, de-normalised."""
+        if self.has_central_value:
+            return self._central_fast_values(obs['states'])     # (the critic only: no actor forward, no draws)
         x = obs['obs']
         if not self._fp32_after_preproc(x):
             return self.get_values(obs)

@@ -109,16 +109,24 @@ def episode_meters_update(ep_partials, horizon, num_blocks, value_size, max_size
 
 
 def rollout_policy_head(heads, logstd, noise, value_stats, eps, actions_out, values_out, storage, horizon,
-                        step, env_actions=None):
+                        step, env_actions=None, value=None, value_repeat=1):
     """storage: ExperienceBuffer.storage (env-major fields).  value_stats = (mean, var) or None.
-    env_actions = (out [N, A], low [A], high [A]): also rescale_actions(low, high, clamp(actions, -1, 1))."""
+    env_actions = (out [N, A], low [A], high [A]): also rescale_actions(low, high, clamp(actions, -1, 1)).
+    value: None (column 0 of the heads) or a [N / value_repeat, 1] view with any row stride (a central value network's
+    output): row r of the step gets the value of row r // value_repeat (rlg_rollout_policy_head_cv)."""
     lib = _lib.load()
     N, A = noise.shape
     vm = vv = None
     if value_stats is not None:
         vm, vv = _need(value_stats[0], F64, 'value mean'), _need(value_stats[1], F64, 'value var')
-    _lib.check(lib.rlg_rollout_policy_head(
-        _need(heads, F32, 'heads'), heads.stride(0), _need(logstd, F32, 'logstd'), _need(noise, F32, 'noise'),
+    if value is None:
+        if value_repeat != 1:
+            raise ValueError('value_repeat needs a value tensor')
+        entry, source = 'rlg_rollout_policy_head', ()
+    else:
+        entry, source = 'rlg_rollout_policy_head_cv', _value_column(value, N, value_repeat) + (int(value_repeat),)
+    _lib.check(getattr(lib, entry)(
+        _need(heads, F32, 'heads'), heads.stride(0), *source, _need(logstd, F32, 'logstd'), _need(noise, F32, 'noise'),
         vm, vv, float(np.float32(eps)), _need(actions_out, F32, 'actions_out'),
         _need(values_out, F32, 'values_out'), _need(storage['actions'], F32, 'actions'),
         _need(storage['mus'], F32, 'mus'), _need(storage['sigmas'], F32, 'sigmas'),
@@ -126,7 +134,7 @@ def rollout_policy_head(heads, logstd, noise, value_stats, eps, actions_out, val
         None if env_actions is None else _need(env_actions[0], F32, 'env actions'),
         None if env_actions is None else _need(env_actions[1], F32, 'actions low'),
         None if env_actions is None else _need(env_actions[2], F32, 'actions high'),
-        N, horizon, A, step, _stream(heads)), 'rlg_rollout_policy_head')
+        N, horizon, A, step, _stream(heads)), entry)
 
 
 CATEGORICAL_MAX_BRANCHES = 16
@@ -143,20 +151,29 @@ def _row_view(t, dtype, rows, cols, name):
     return t.data_ptr(), t.stride(0)
 
 
+def _value_column(value, N, value_repeat):
+    """(address, row stride) of the value column that serves N rollout rows, value_repeat rows per value row."""
+    if int(value_repeat) < 1 or N % int(value_repeat):
+        raise ValueError(f'value_repeat {value_repeat} does not divide {N} rows')
+    if value.dim() == 1:
+        value = value.unsqueeze(1)
+    return _row_view(value, F32, N // int(value_repeat), 1, 'value')
+
+
 def rollout_categorical_head(logits, value, branch_sizes, noise, masks, value_stats, eps, actions_out, values_out,
-                             storage, horizon, step):
+                             storage, horizon, step, value_repeat=1):
     """Categorical rollout head (csrc/rollout_categorical.hip).  logits [N, sum(sizes)] and value [N, 1] (views of the
     chain's heads, any row stride; value may also be [N]); noise: fp32 Exp(1) draws, >= N * sum(sizes), branch b's block [N, sizes[b]] at
     N * sum(sizes[:b]); masks: bool [N, sum(sizes)] view (the buffer slot of the step) or None; value_stats =
     (mean, var) or None; actions_out int64 [N] / [N, B]; values_out fp32 [N]; storage: ExperienceBuffer.storage
-    (env-major 'actions', 'neglogpacs', 'values').  Slot `step` of those fields is written."""
+    (env-major 'actions', 'neglogpacs', 'values').  Slot `step` of those fields is written.  value_repeat > 1: value
+    has N / value_repeat rows (a central value network's output), row r of the step gets the value of row
+    r // value_repeat (rlg_rollout_categorical_head_cv)."""
     lib = _lib.load()
     sizes = [int(s) for s in branch_sizes]
-    if value.dim() == 1:
-        value = value.unsqueeze(1)
-    N, S, B = value.shape[0], sum(sizes), len(sizes)
+    N, S, B = logits.shape[0], sum(sizes), len(sizes)
     lg, ld_lg = _row_view(logits, F32, N, S, 'logits')
-    vp, ld_v = _row_view(value, F32, N, 1, 'value')
+    vp, ld_v = _value_column(value, N, value_repeat)
     _need(noise, F32, 'noise')
     if noise.numel() < N * S:
         raise ValueError(f'noise: {noise.numel()} draws for {N} x {S}')
@@ -174,11 +191,14 @@ def rollout_categorical_head(logits, value, branch_sizes, noise, masks, value_st
         if t.numel() != numel:
             raise ValueError(f'buffer field of {t.numel()} elements, expected {numel}')
     arr = (ctypes.c_int * B)(*sizes)
-    _lib.check(lib.rlg_rollout_categorical_head(
-        lg, ld_lg, vp, ld_v, arr, B, noise.data_ptr(), mp, ld_m, vm, vv, float(np.float32(eps)),
+    if value_repeat == 1:
+        entry, source = 'rlg_rollout_categorical_head', (vp, ld_v)
+    else:
+        entry, source = 'rlg_rollout_categorical_head_cv', (vp, ld_v, int(value_repeat))
+    _lib.check(getattr(lib, entry)(
+        lg, ld_lg, *source, arr, B, noise.data_ptr(), mp, ld_m, vm, vv, float(np.float32(eps)),
         _need(actions_out, torch.int64, 'actions_out'), _need(values_out, F32, 'values_out'),
-        *[_need(t, dtype, 'buffer field') for t, dtype, _ in fields], N, horizon, step, _stream(value)),
-        'rlg_rollout_categorical_head')
+        *[_need(t, dtype, 'buffer field') for t, dtype, _ in fields], N, horizon, step, _stream(value)), entry)
 
 
 def rnn_zero_done_states(states, dones):
