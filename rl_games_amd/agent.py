@@ -27,6 +27,7 @@ import gc
 import os
 import time
 from datetime import datetime
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -136,23 +137,17 @@ class DeviceAverageMeter:
         self.mean = (self.mean * old_size + new_mean * size) / size_sum
 
 
-class _LeanChains:
-    """The fp32 weight fragments of the lean 16-row kernels of one or two ops.MlpChain objects, handled together."""
-
-    def __init__(self, chains):
-        self.chains = chains
-
-    def pack_frags(self, stream_of):
-        for c in self.chains:
-            c.pack_frags(stream_of)
-
-    def mark_frags(self, version):
-        for c in self.chains:
-            c.mark_frags(version)
-
-    def ensure_frags(self, stream_of):
-        for c in self.chains:
-            c.ensure_frags(stream_of)
+class _ChainForms(NamedTuple):
+    """A fused chain (ops.MlpChain) that this agent's captured graphs read, and what keeps its derived weight forms
+    current.  launches: [(rows, kind), ...] the launches run on it (ops.MlpChain.forms_read); arena: the flat parameters
+    its weights live in.  actor: the actor's chain - the update graphs read it too, and the lean fragments are packed
+    behind every optimiser step.  planes: the split planes are brought up to date in front of a replay; False for the
+    actor's chains unless the Adam launch writes them (`adam_writes_planes`): their graphs pack the planes themselves."""
+    chain: ops.MlpChain
+    launches: tuple
+    arena: torch.Tensor
+    actor: bool = False
+    planes: bool = True
 
 
 class A2CAgent:
@@ -406,6 +401,8 @@ class A2CAgent:
             momentum = config.get('adv_rms_momentum', 0.5)
             self.advantage_mean_std = GeneralizedMovingStats((1,), decay=momentum).to(dev)
         self.has_value_loss = self.use_experimental_cv or not self.has_central_value
+        self._fused_rollout = self._fused_rollout_eligible()      # (with the critic in place)
+        self._form_chains = self._graph_chains()
 
         # device-side episode meters (game_rewards / game_shaped_rewards / game_lengths)
         self._meter_sizes = torch.zeros(3, dtype=torch.int32, device=dev)
@@ -439,8 +436,6 @@ class A2CAgent:
         self._fin_norm_ok = None      # decided on first use (_norm_in_finalize)
         self._fin_norm_partials = None
         self._norm_ready = None       # (partials, count) when the finalise / all-reduce launch produced the gradient norm
-        self._adam_pack = None        # decided on first use (_adam_pack_chain)
-        self._lean_pack = None        # decided on first use (_lean_chain)
         self._roll_env_actions = None
         self._ar_norm_partials = None
         self._fold_index = None
@@ -477,7 +472,8 @@ class A2CAgent:
         return None
 
     def _init_chains(self, config):
-        """Hook behind the optimiser: the discrete agent puts its trunks on the fused chain kernels here."""
+        """Hook behind the optimiser: the discrete agent puts its trunks on the fused chain kernels here (ChainNet list)."""
+        self._chains = None
 
     def _alloc_loss_scratch(self, mb, dev):
         A = self.actions_num
@@ -818,16 +814,9 @@ class A2CAgent:
             args = (n, st['obs'], st['dones'], st.get('rnn'), True, st.get('states'))
         entry = self._rollout_graphs.get((n, direct))
         if entry is None:
-            if self._graph_pool is None:
-                self._graph_pool = torch.cuda.graph_pool_handle()
-            g = torch.cuda.CUDAGraph()
-            cached0 = self._chain_cache_states()
-            try:
-                with torch.cuda.graph(g, pool=self._graph_pool, capture_error_mode='thread_local'):
-                    out = self._policy_step_kernels(*args)
-            finally:
-                self._restore_chain_cache_states(cached0)       # (launches of the body were recorded, not run)
-            entry = self._rollout_graphs[(n, direct)] = (g, out)
+            out = []
+            g = self._capture(lambda: out.append(self._policy_step_kernels(*args)))
+            entry = self._rollout_graphs[(n, direct)] = (g, out[0])
         entry[0].replay()
         return entry[1]
 
@@ -842,26 +831,8 @@ class A2CAgent:
         preprocess_actions; no autograd, nothing that depends on the host."""
         eng, buf = self._engine, self.experience_buffer
         obs = self._preproc_obs(obs_raw)
-        if not obs.is_contiguous() and (eng.chain is None or obs.stride(-1) != 1):
-            obs = obs.contiguous()          # (the fused forward takes any row stride: a buffer slot [:, n, :])
         rows = obs.shape[0]
-        if eng.chain is not None:
-            # normaliser + every layer + heads in one launch; nothing but the heads is written
-            heads = eng.forward_obs(obs, self._obs_rms(), self._obs_eps(), keep=False)
-        elif self.is_rnn and eng.chain_rnn is not None and obs.dtype == torch.float32:
-            # recurrent policy: normaliser + trunk + gate-input product in one launch, then the LSTM step + heads
-            heads = eng.forward(obs, keep=False, rnn_states=rnn_states, seq_length=1,
-                                raw_rms=self._obs_rms() or (), eps=self._obs_eps())
-        else:
-            if self.normalize_input:
-                m = self.model.running_mean_std
-                obs_n = ops.rms_apply(obs, m.running_mean, m.running_var, m.epsilon, 0, out=self._roll_obs_norm)
-            else:
-                obs_n = obs
-            if self.is_rnn:
-                heads = eng.forward(obs_n, keep=False, rnn_states=rnn_states, seq_length=1)
-            else:
-                heads = eng.forward(obs_n, keep=False)
+        heads = self._actor_heads(obs, rnn_states)
         value = self._critic_infer(states) if self.has_central_value else None
         torch.randn(self._roll_noise.shape, device=self._roll_noise.device, out=self._roll_noise)
         vs, eps = self._rollout_value_stats()
@@ -883,6 +854,26 @@ class A2CAgent:
         if self.is_rnn:
             res['rnn_states'] = eng.last_states
         return res
+
+    def _actor_heads(self, obs, rnn_states):
+        """The actor's inference forward on the engine: heads [rows, ...] of preprocessed observations (any row stride
+        on the fused chain: a buffer slot [:, n, :]), the normaliser in eval mode.  No autograd, no host read."""
+        eng = self._engine
+        if not obs.is_contiguous() and (eng.chain is None or obs.stride(-1) != 1):
+            obs = obs.contiguous()
+        if eng.chain is not None:
+            # normaliser + every layer + heads in one launch; nothing but the heads is written
+            return eng.forward_obs(obs, self._obs_rms(), self._obs_eps(), keep=False)
+        if self.is_rnn and eng.chain_rnn is not None and obs.dtype == torch.float32:
+            # recurrent policy: normaliser + trunk + gate-input product in one launch, then the LSTM step + heads
+            return eng.forward(obs, keep=False, rnn_states=rnn_states, seq_length=1,
+                               raw_rms=self._obs_rms() or (), eps=self._obs_eps())
+        if self.normalize_input:
+            m = self.model.running_mean_std
+            obs = ops.rms_apply(obs, m.running_mean, m.running_var, m.epsilon, 0, out=self._roll_obs_norm)
+        if self.is_rnn:
+            return eng.forward(obs, keep=False, rnn_states=rnn_states, seq_length=1)
+        return eng.forward(obs, keep=False)
 
     def _store_step_inputs(self, n, obs_raw, dones, states):
         """update_data('obses' / 'dones' (/ 'states'), n) of a fused step (a2c_common.py:1000-1011): one launch per row
@@ -918,55 +909,26 @@ class A2CAgent:
         vm = self.central_value_net.model.value_mean_std if self.has_central_value else self.model.value_mean_std
         return (vm.running_mean, vm.running_var), vm.epsilon
 
+    def _denorm_values(self, v):
+        """Raw values [rows, 1] -> de-normalised with the rollout's statistics (_rollout_value_stats)."""
+        vs, eps = self._rollout_value_stats()
+        if vs is None:
+            return v
+        return ops.rms_apply(v.contiguous(), vs[0], vs[1], eps, 1)
+
     def _central_fast_values(self, states):
         """get_values with a central value network (a2c_common.py:605-614): the critic's forward only - the actor does
         not run and nothing is drawn from the generator - de-normalised, every agent of an env given the env's value
         (central_value.py:223-225).  [num_actors * num_agents]."""
-        v = self._critic_infer(states)
-        vs, eps = self._rollout_value_stats()
-        if vs is not None:
-            v = ops.rms_apply(v.contiguous(), vs[0], vs[1], eps, 1)
+        v = self._denorm_values(self._critic_infer(states))
         return v.expand(-1, self.num_agents).reshape(-1)
-
-    def _critic_forms_before_replay(self):
-        """The step graphs contain no pack launch: bring the forms the critic chain's inference forward reads at the
-        rollout's row count (lean fragments or split planes) up to the critic's weights as they are - behind its own
-        Adam steps as behind restore() / set_central_value_function_weights / a broadcast."""
-        c = self._critic_chain()
-        if c is None:
-            return
-        chain, arena = c.chain, self.central_value_net.optimizer.flat_params
-        if chain.lean_used(self.num_actors, 0):
-            chain.ensure_frags(arena)
-        elif chain.split_products(self.num_actors, 0):
-            chain.ensure_planes(arena)
 
     def _fast_values(self, obs):
         """get_values on the engine: de-normalised critic values [N] of `obs`."""
         if self.has_central_value:
             return self._central_fast_values(obs['states'])
-        eng = self._engine
-        x = self._preproc_obs(obs['obs'])
-        if not x.is_contiguous():
-            x = x.contiguous()
-        if eng.chain is not None:
-            heads = eng.forward_obs(x, self._obs_rms(), self._obs_eps(), keep=False)
-        elif self.is_rnn and eng.chain_rnn is not None and x.dtype == torch.float32:
-            heads = eng.forward(x, keep=False, rnn_states=self.rnn_states, seq_length=1,
-                                raw_rms=self._obs_rms() or (), eps=self._obs_eps())
-        else:
-            if self.normalize_input:
-                m = self.model.running_mean_std
-                x = ops.rms_apply(x, m.running_mean, m.running_var, m.epsilon, 0, out=self._roll_obs_norm)
-            if self.is_rnn:
-                heads = eng.forward(x, keep=False, rnn_states=self.rnn_states, seq_length=1)
-            else:
-                heads = eng.forward(x, keep=False)
-        v = heads[:, 0].contiguous()
-        if self.normalize_value:
-            vm = self.model.value_mean_std
-            v = ops.rms_apply(v.view(-1, 1), vm.running_mean, vm.running_var, vm.epsilon, 1).view(-1)
-        return v
+        heads = self._actor_heads(self._preproc_obs(obs['obs']).contiguous(), self.rnn_states)
+        return self._denorm_values(heads[:, 0].contiguous().view(-1, 1)).view(-1)
 
     def _obs_rms(self):
         if not self.normalize_input:
@@ -985,9 +947,44 @@ class A2CAgent:
         dtype = getattr(self.state_space, 'dtype', None)
         return (self._critic_chain() is not None and dtype is not None and np.dtype(dtype) == np.float32)
 
+    def _fused_rollout_eligible(self):
+        """The rollout on the fused forwards: one value column, no central value network or one the fused step can run,
+        `fused_rollout` on, and the agent's own conditions (_fused_rollout_network_ok)."""
+        return (self.value_size == 1 and self._central_value_fused_ok() and self.config.get('fused_rollout', True)
+                and self._fused_rollout_network_ok())
+
+    def _fused_rollout_network_ok(self):
+        """The actor on the manual engine."""
+        return self._engine is not None
+
     def _fast_rollout_ok(self):
-        return (self._engine is not None and self.value_size == 1 and self._central_value_fused_ok()
-                and self.config.get('fused_rollout', True))
+        """Does the rollout run fused (decided when the agent was built)."""
+        return self._fused_rollout
+
+    def _torch_action_values(self):
+        """get_(masked_)action_values of the current observations (a2c_common.py:995-997)."""
+        if self.use_action_masks:
+            return self.get_masked_action_values(self.obs, self.vec_env.get_action_masks())
+        return self.get_action_values(self.obs)
+
+    def _store_torch_step(self, n, res_dict):
+        """update_data of a step on the torch path (a2c_common.py:1000-1011): observations, done flags, the model's
+        outputs (and a central value network's states) into the buffer, one launch."""
+        fields = {'obses': self.obs['obs'], 'dones': self.dones}
+        for k in self.update_list:
+            fields[k] = res_dict[k]
+        if self.has_central_value:
+            fields['states'] = self.obs['states']
+        self.experience_buffer.store_step(n, fields)
+
+    def _mark_autoreset_rows(self, mb_valid, n):
+        """next_step autoreset: mb_valid[n] = 0 for the rows whose previous step ended an episode (this step's
+        observation is the reset filler).  Returns those done flags."""
+        prev = self._autoreset_prev_dones
+        if prev is None:
+            prev = torch.zeros_like(self.dones)
+        mb_valid[n] = 1.0 - prev.float()
+        return prev
 
     def play_steps(self):
         """a2c_common.py:985-1069."""
@@ -998,10 +995,7 @@ class A2CAgent:
         mb_valid = None
         fast = self._fast_rollout_ok()
         if fast:
-            # the step graphs contain no pack launch: the weights' derived forms (plane fragments of both kernel families) must belong
-            # to the weights as they are - they do behind an optimiser step, not behind set_weights / a broadcast
-            self._planes_before_replay()
-            self._critic_forms_before_replay()
+            self._forms_before_replay(rollout=True)
         if self.mask_autoreset_rows:
             mb_valid = torch.ones((self.horizon_length, self.num_actors * self.num_agents),
                                   dtype=torch.float32, device=self.ppo_device)
@@ -1009,21 +1003,10 @@ class A2CAgent:
             if fast:
                 res_dict = self._fast_policy_step(n)
             else:
-                if self.use_action_masks:                        # a2c_common.py:995-997
-                    res_dict = self.get_masked_action_values(self.obs, self.vec_env.get_action_masks())
-                else:
-                    res_dict = self.get_action_values(self.obs)
-                fields = {'obses': self.obs['obs'], 'dones': self.dones}
-                for k in self.update_list:
-                    fields[k] = res_dict[k]
-                if self.has_central_value:
-                    fields['states'] = self.obs['states']
-                buf.store_step(n, fields)
+                res_dict = self._torch_action_values()
+                self._store_torch_step(n, res_dict)
             if mb_valid is not None:
-                prev = self._autoreset_prev_dones
-                if prev is None:
-                    prev = torch.zeros_like(self.dones)
-                mb_valid[n] = 1.0 - prev.float()
+                self._mark_autoreset_rows(mb_valid, n)
             t0 = time.perf_counter()
             self.obs, rewards, dones, infos = self.env_step(res_dict['actions'], res_dict.get('env_actions'))
             self.dones = self._as_u8(dones)
@@ -1044,8 +1027,7 @@ class A2CAgent:
         rows = self.num_actors * self.num_agents
         fast = self._fast_rollout_ok()
         if fast:
-            self._planes_before_replay()          # (see play_steps)
-            self._critic_forms_before_replay()
+            self._forms_before_replay(rollout=True)
         if self.mask_autoreset_rows:
             mb_valid = torch.ones((self.horizon_length, rows), dtype=torch.float32, device=self.ppo_device)
         for n in range(self.horizon_length):
@@ -1054,30 +1036,17 @@ class A2CAgent:
                     mb_s[n // self.seq_length, :, :, :] = s
             if self.has_central_value:
                 self.central_value_net.pre_step_rnn(n)           # a2c_common.py:1085-1086
-            if fast:
-                res_dict = self._fast_policy_step(n)
-            elif self.use_action_masks:                          # a2c_common.py:1088-1090
-                res_dict = self.get_masked_action_values(self.obs, self.vec_env.get_action_masks())
-            else:
-                res_dict = self.get_action_values(self.obs)
+            res_dict = self._fast_policy_step(n) if fast else self._torch_action_values()
             self.rnn_states = [s.contiguous() for s in res_dict['rnn_states']]
-            fields = {'obses': self.obs['obs'], 'dones': self.dones}
             if mb_valid is not None:
-                prev = self._autoreset_prev_dones
-                if prev is None:
-                    prev = torch.zeros_like(self.dones)
-                mb_valid[n] = 1.0 - prev.float()
+                prev = self._mark_autoreset_rows(mb_valid, n)
                 if self.zero_rnn_on_done:
                     for s in self.rnn_states:
                         ops.rnn_zero_done_states(s, prev)
                     if self.has_central_value:                   # (the critic absorbed the same filler row: :1112-1115)
                         self.central_value_net.zero_states_where(prev)
             if not fast:
-                for k in self.update_list:
-                    fields[k] = res_dict[k]
-                if self.has_central_value:
-                    fields['states'] = self.obs['states']
-                buf.store_step(n, fields)
+                self._store_torch_step(n, res_dict)
             t0 = time.perf_counter()
             self.obs, rewards, dones, infos = self.env_step(res_dict['actions'], res_dict.get('env_actions'))
             self.dones = self._as_u8(dones)
@@ -1500,7 +1469,6 @@ class A2CAgent:
 
     def _optimizer_kernels(self):
         opt = self.optimizer
-        lean = self._lean_chain()
         # behind the in-graph all-reduce the step takes the collective's error word: a step whose gradients
         # are invalid (a peer never arrived) changes nothing
         skip = self._ipc_comm.error_word if (self.multi_gpu and self._ipc_comm) else None
@@ -1510,51 +1478,58 @@ class A2CAgent:
         # apart and is gone - profiles/r5_two_rank_sync.txt.)
         opt.step(norm_ready=self._norm_ready, skip_flag=skip, pack=self._adam_pack_chain(), **self._step_arguments())
         self._norm_ready = None
+        lean = self._lean_chain()
         if lean is not None:
             lean.pack_frags(opt.flat_params)
             lean.mark_frags(opt.weights_token())
 
+    def _graph_chains(self):
+        """The fused chains that this agent's captured graphs read, in the order their forms are brought up to date: the
+        actor engine's, the discrete agent's, the critic's (_ChainForms)."""
+        roll, eng = self.num_actors * self.num_agents, self._engine
+        arena = self.optimizer.flat_params
+        # the update's training forward (2) and backward (1), the rollout's inference forward (0)
+        actor = ((self.minibatch_size, 2), (self.minibatch_size, 1), (roll, 0))
+        forms = []
+        if eng is not None and eng.chain is not None:
+            forms.append(_ChainForms(eng.chain, actor, arena, True, bool(self.config.get('adam_writes_planes', True))))
+        if eng is not None and eng.chain_rnn is not None:
+            forms.append(_ChainForms(eng.chain_rnn, actor, arena, True, False))
+        forms += [_ChainForms(c.chain, ((roll, 0),), arena) for c in self._chains or ()]
+        if self._critic_chain() is not None:
+            forms.append(_ChainForms(self._critic_chain().chain, ((self.num_actors, 0),),
+                                     self.central_value_net.optimizer.flat_params))
+        return forms
+
     def _lean_chain(self):
-        """The fused chains (the MLP's, or the trunk in front of a recurrent layer) whose launches run the lean 16-row
-        kernels at one of this agent's sizes (csrc/mlp_chain_lean.hip: minibatches / rollouts of < 16,384 rows on exact
-        products), as one object with pack_frags / mark_frags / ensure_frags - or None."""
-        c = self._lean_pack
-        if c is None:
-            c = False
-            eng = self._engine
-            # (launch kinds: the update's training forward (2) and backward (1), the rollout's inference forward (0))
-            kinds = ((self.minibatch_size, 2), (self.minibatch_size, 1), (self.num_actors * self.num_agents, 0))
-            chains = [ch for ch in (getattr(eng, 'chain', None), getattr(eng, 'chain_rnn', None))
-                      if ch is not None and any(ch.lean_used(r, d) for r, d in kinds)]
-            if chains:
-                c = _LeanChains(chains)
-            self._lean_pack = c
-        return c or None
+        """The actor's chain (the MLP's, or the trunk in front of a recurrent layer: the engine has one of the two) whose
+        launches run the lean 16-row kernels at one of this agent's sizes (csrc/mlp_chain_lean.hip: minibatches /
+        rollouts of < 16,384 rows on exact products) - its fragments are packed behind every optimiser step - or None."""
+        return next((f.chain for f in self._form_chains if f.actor and f.chain.forms_read(f.launches)[0]), None)
 
     def _adam_pack_chain(self):
         """The fused chain whose bf16 weight planes the Adam launch writes itself (csrc/mlp_chain_bx.hip,
         adam_pack_kernel: one launch instead of Adam + pack per optimiser step, no pack in front of the rollout
-        forwards), or None: no fused chain, or none of this agent's launch sizes runs on planes."""
-        c = self._adam_pack
-        if c is None:
-            c = False
-            eng = self._engine
-            chain = getattr(eng, 'chain', None) if eng is not None else None
-            if chain is not None and self.config.get('adam_writes_planes', True):
-                kinds = ((self.minibatch_size, 2), (self.minibatch_size, 1), (self.num_actors * self.num_agents, 0))
-                if any(chain.split_products(r, d) for r, d in kinds):
-                    c = chain
-            self._adam_pack = c
-        return c or None
+        forwards), or None: no fused chain, `adam_writes_planes` off, or none of this agent's launch sizes runs on planes."""
+        return next((f.chain for f in self._form_chains if f.actor and f.planes and f.chain.forms_read(f.launches)[1]),
+                    None)
 
-    def _planes_before_replay(self):
-        """A captured graph of this mode contains no pack launch: the planes must belong to the weights as they are
-        (they do behind the previous step's Adam launch; not behind a restore / broadcast / set_weights)."""
-        chain = self._adam_pack_chain()
-        if chain is not None:
-            chain.ensure_planes(self.optimizer.flat_params)
+    def _forms_before_replay(self, rollout=False):
+        """A captured graph contains no pack launch: the derived forms of the chains it reads must belong to the weights
+        as they are (they do behind this agent's optimiser step; not behind a restore / broadcast / set_weights, nor
+        behind the critic's own steps).  The update graphs read the actor's chains, the rollout's step graphs all."""
+        for f in self._form_chains:
+            if rollout or f.actor:
+                f.chain.ensure_forms(f.launches, f.arena, planes=f.planes)
+
+    def _mark_forms_after_replay(self):
+        """Behind a replayed update graph: its last optimiser step left the actor's planes (Adam launch) and fragments
+        (pack launch) those of the weights as they are now."""
+        token = self.optimizer.weights_token()
+        if self._adam_pack_chain() is not None:
+            self._adam_pack_chain().mark_planes(token)
         if self._lean_chain() is not None:
-            self._lean_chain().ensure_frags(self.optimizer.flat_params)
+            self._lean_chain().mark_frags(token)
 
     # ------------------------------------------------------------------ HIP graphs
     def _with_fold(self, mb_index, fn, *args):
@@ -1606,7 +1581,8 @@ class A2CAgent:
     def _capture(self, body):
         """Capture `body` into a HIP graph.  Capturing executes nothing on the device; host mirrors
         that the body advances (the optimiser's step count) are restored afterwards, also when the
-        capture fails (GraphCaptureError: the caller then continues on the eager path)."""
+        capture fails (GraphCaptureError: the update then continues on the eager path).  A rollout step
+        advances none of them."""
         if self._graph_pool is None:
             self._graph_pool = torch.cuda.graph_pool_handle()
         g = torch.cuda.CUDAGraph()
@@ -1631,11 +1607,7 @@ class A2CAgent:
         return g
 
     def _chain_cache_states(self):
-        eng = self._engine
-        chains = [c for c in (getattr(eng, 'chain', None), getattr(eng, 'chain_rnn', None)) if c is not None]
-        if self._critic_chain() is not None:
-            chains.append(self._critic_chain().chain)
-        return [(c, c.cache_state()) for c in chains]
+        return [(f.chain, f.chain.cache_state()) for f in self._form_chains]
 
     @staticmethod
     def _restore_chain_cache_states(states):
@@ -1657,7 +1629,7 @@ class A2CAgent:
             g = self._graphs[i] = self._capture(lambda: self._with_fold(i, self._forward_loss_backward, item,
                                                                        self._graph_rows[i]))
             self._graph_norm_state = self._norm_ready      # what the captured launches will have produced
-        self._planes_before_replay()
+        self._forms_before_replay()
         if self._graph_opt is None:
             # Captured BEFORE anything of this minibatch runs (a failed capture then leaves minibatch i untouched
             # for the eager path), knowing which launch in front of it produces the gradient norm - the
@@ -1673,10 +1645,7 @@ class A2CAgent:
         self._norm_ready = None
         self._graph_opt.replay()
         self.optimizer.step_done()
-        if self._adam_pack_chain() is not None:
-            self._adam_pack_chain().mark_planes(self.optimizer.weights_token())
-        if self._lean_chain() is not None:
-            self._lean_chain().mark_frags(self.optimizer.weights_token())
+        self._mark_forms_after_replay()
 
     def _graph_mini_epoch(self, nmb):
         """Single-GPU runs with nothing to do on the host between minibatches (device-side or
@@ -1698,14 +1667,11 @@ class A2CAgent:
                 if self._fold_ready:
                     self.model.running_mean_std.fold_sync(nmb)
             self._graph_epoch = self._capture(body)
-        self._planes_before_replay()
+        self._forms_before_replay()
         self._graph_epoch.replay()
         self.optimizer.step_count += nmb
         self.optimizer.weights_version += nmb
-        if self._adam_pack_chain() is not None:
-            self._adam_pack_chain().mark_planes(self.optimizer.weights_token())
-        if self._lean_chain() is not None:
-            self._lean_chain().mark_frags(self.optimizer.weights_token())
+        self._mark_forms_after_replay()
 
     def _host_schedule(self, kl_value):
         lr, self.entropy_coef = self.scheduler.update(self._host_lr, self.entropy_coef, self.epoch_num,

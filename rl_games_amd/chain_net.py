@@ -9,7 +9,9 @@ as ONE forward launch, the dX / activation-backward / bias-sum chain as ONE back
 
 Users: the central value network (central_value.py, one value column) and the discrete-action agent (discrete_agent.py:
 [value | logits] behind a shared trunk, or one chain per trunk with `separate: True` as in ppo_cartpole.yaml).  The
-continuous actor has its own engine (mlp_engine.ManualMLP: loss inside the backward launch, LSTM, HIP graphs).
+continuous actor has its own engine (mlp_engine.ManualMLP: loss inside the backward launch, LSTM, HIP graphs).  The
+agents' rollout graphs read these chains too; they hold no pack launch, so the agent brings each chain's weight fragments
+/ planes up to date in front of a replay along with its other chains (A2CAgent._forms_before_replay).
 """
 import torch
 from torch import nn

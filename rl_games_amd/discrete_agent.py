@@ -91,12 +91,10 @@ class DiscreteA2CAgent(A2CAgent):
             self._chains = None
 
     # ------------------------------------------------------------------ fused rollout
-    def _fast_rollout_ok(self):
-        """The rollout on the chains: feed-forward network on the fused chain kernels, one value column, no central value
-        or a feed-forward one on the chains (_central_value_fused_ok), `fused_rollout` on (recurrent policies keep the
-        torch path: _init_chains leaves them without chains)."""
-        return (self._chains is not None and not self.is_rnn and self.value_size == 1 and self._central_value_fused_ok()
-                and len(self.branch_sizes) <= ops.CATEGORICAL_MAX_BRANCHES and self.config.get('fused_rollout', True))
+    def _fused_rollout_network_ok(self):
+        """A feed-forward network on the chains (recurrent policies keep the torch path) of at most
+        ops.CATEGORICAL_MAX_BRANCHES action branches."""
+        return self._chains is not None and not self.is_rnn and len(self.branch_sizes) <= ops.CATEGORICAL_MAX_BRANCHES
 
     def init_tensors(self):
         super().init_tensors()
@@ -115,22 +113,16 @@ class DiscreteA2CAgent(A2CAgent):
     def _fast_policy_step(self, n):
         """The step's action masks go into the buffer slot first (the head kernel reads them there); observations that
         are not fp32 after preprocessing take the torch path for this step, as the update does."""
-        buf = self.experience_buffer
         masks = None
         if self.use_action_masks:                                # a2c_common.py:995-997
             masks = torch.as_tensor(self.vec_env.get_action_masks(), dtype=torch.bool, device=self.ppo_device)
         if not self._fp32_after_preproc(self.obs['obs']):
             res = (self.get_action_values(self.obs) if masks is None
                    else self.get_masked_action_values(self.obs, masks))
-            fields = {'obses': self.obs['obs'], 'dones': self.dones}
-            for k in self.update_list:
-                fields[k] = res[k]
-            if self.has_central_value:
-                fields['states'] = self.obs['states']
-            buf.store_step(n, fields)
+            self._store_torch_step(n, res)
             return res
         if masks is not None:
-            buf.store_step(n, {'action_masks': masks.contiguous()})
+            self.experience_buffer.store_step(n, {'action_masks': masks.contiguous()})
         return super()._fast_policy_step(n)
 
     def _chain_heads_of(self, obs, logits_only=False):
@@ -188,27 +180,7 @@ class DiscreteA2CAgent(A2CAgent):
         # get_values runs the model's whole eval forward, which samples actions: the same draws keep the generator where
         # the torch path leaves it
         self._draw_exp_noise(x.shape[0])
-        if self.normalize_value:
-            vm = self.model.value_mean_std
-            v = ops.rms_apply(v, vm.running_mean, vm.running_var, vm.epsilon, 1)
-        return v.view(-1)
-
-    def _planes_before_replay(self):
-        """The step graphs contain no pack launch: bring the forms the chains' inference forward reads (lean fragments or
-        split planes) up to the weights as they are - behind an optimiser step as behind restore() / set_weights."""
-        super()._planes_before_replay()
-        if self._chains is None:
-            return
-        rows = self.num_actors * self.num_agents
-        for c in self._chains:
-            if c.chain.lean_used(rows, 0):
-                c.chain.ensure_frags(self.optimizer.flat_params)
-            elif c.chain.split_products(rows, 0):
-                c.chain.ensure_planes(self.optimizer.flat_params)
-
-    def _chain_cache_states(self):
-        states = super()._chain_cache_states()
-        return states + [(c.chain, c.chain.cache_state()) for c in self._chains or ()]
+        return self._denorm_values(v).view(-1)
 
     def _alloc_loss_scratch(self, mb, dev):
         self._d_logits = torch.empty(mb, sum(self.branch_sizes), dtype=torch.float32, device=dev)

@@ -860,6 +860,7 @@ class MlpChain:
         self._planes_fresh = None  # (rows, weights version) of the training forward that packed the backward planes
         self._planes_for = None    # weights version for which BOTH directions' planes are valid (optimiser-written or packed)
         self._planes_packed_once = False
+        self._forms_read = {}      # forms_read() per launch list
         # split-fp16 backward: per 64-row workgroup the largest magnitude of every dZ tensor (csrc/bx_form.hpp), for the
         # weight-gradient launch that follows it; rows of the last backward that left them
         self._grad_maxima = None
@@ -965,6 +966,26 @@ class MlpChain:
         if not self.planes_current():
             self.pack_planes(2, stream_of)
             self._planes_for = self._version()
+
+    def forms_read(self, launches):
+        """(fragments, planes): whether any of `launches` [(rows, kind), ...] (kinds as in split_products) runs the lean
+        16-row kernels, which read the fragments, or the split-product kernels, which read the planes."""
+        key = tuple(launches)
+        forms = self._forms_read.get(key)
+        if forms is None:
+            forms = self._forms_read[key] = (any(self.lean_used(r, k) for r, k in key),
+                                             any(self.split_products(r, k) for r, k in key))
+        return forms
+
+    def ensure_forms(self, launches, stream_of, planes=True):
+        """In front of a graph replay (a captured graph contains no pack launch): pack the derived forms that `launches`
+        read again if the weights changed since they were packed.  planes=False leaves the planes to the caller's
+        launches (they pack them themselves)."""
+        frags, split = self.forms_read(launches)
+        if split and planes:
+            self.ensure_planes(stream_of)
+        if frags:
+            self.ensure_frags(stream_of)
 
     def adam_pack_target(self):
         """(n, weights, in, out, planes address) for ops.adam_step(pack=...), or None when this network has no use for
