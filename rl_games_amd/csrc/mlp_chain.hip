@@ -1339,12 +1339,11 @@ static int chain_lds(int num_layers, const int* in_features, const int* out_feat
   return bytes <= 160 * 1024 ? static_cast<int>(bytes) : -1;
 }
 
-int chain_fill(ChainArgs& args, int num_layers, const float* const* weights, const int* in_features,
-                      const int* out_features, const int* acts) {
+int chain_fill_shape(ChainArgs& args, int num_layers, const int* in_features, const int* out_features, const int* acts) {
   if (num_layers < 1 || num_layers > kChainMaxLayers) return 1;
   for (int L = 0; L < num_layers; ++L) {
     ChainLayer& ly = args.layer[L];
-    ly.w = weights[L];
+    ly.w = nullptr;
     ly.in = in_features[L];
     ly.out = out_features[L];
     ly.act = acts[L];
@@ -1355,7 +1354,6 @@ int chain_fill(ChainArgs& args, int num_layers, const float* const* weights, con
     ly.ldh = ly.lddz = 0;
     if (ly.in <= 0 || ly.out <= 0 || (L > 0 && ly.in != out_features[L - 1])) return 1;
     if (static_cast<long long>(ly.in) * ly.out * 4 >= static_cast<long long>(kOob)) return 1;
-    if (reinterpret_cast<uintptr_t>(ly.w) % 4 != 0) return 1;
   }
   args.num_layers = num_layers;
   args.dbg = nullptr;
@@ -1365,6 +1363,122 @@ int chain_fill(ChainArgs& args, int num_layers, const float* const* weights, con
   args.pack.dst = nullptr;
   args.planes = nullptr;
   return 0;
+}
+
+int chain_fill(ChainArgs& args, int num_layers, const float* const* weights, const int* in_features,
+               const int* out_features, const int* acts) {
+  if (chain_fill_shape(args, num_layers, in_features, out_features, acts)) return 1;
+  for (int L = 0; L < num_layers; ++L) {
+    args.layer[L].w = weights[L];
+    if (reinterpret_cast<uintptr_t>(weights[L]) % 4 != 0) return 1;
+  }
+  return 0;
+}
+
+int chain_fill_forward(ChainArgs& args, const float* const* biases_or_null, float* const* act_out, const long long* act_ld,
+                       const float* x, long long ldx, const double* rms_mean, const double* rms_var, float rms_eps,
+                       float* xn_out, const double* rms_batch, const long long* rms_count, double* rms_mean_out,
+                       double* rms_var_out, long long* rms_count_out, long long rows) {
+  for (int L = 0; L < args.num_layers; ++L) {
+    args.layer[L].bias = biases_or_null ? biases_or_null[L] : nullptr;
+    args.layer[L].h = act_out[L];
+    args.layer[L].ldh = act_ld[L];
+  }
+  args.x = x;
+  args.ldx = ldx;
+  args.rms_mean = rms_mean;
+  args.rms_var = rms_mean ? rms_var : nullptr;
+  args.rms_eps = rms_eps;
+  args.rms_batch = rms_mean ? rms_batch : nullptr;
+  if (args.rms_batch) {
+    if (!rms_count || !rms_mean_out || !rms_var_out || !rms_count_out || rms_mean_out == rms_mean ||
+        rms_var_out == rms_var || rms_count_out == rms_count)
+      return static_cast<int>(hipErrorInvalidValue);      // the fold publishes into a second buffer set
+  }
+  args.rms_count = rms_count;
+  args.rms_mean_out = rms_mean_out;
+  args.rms_var_out = rms_var_out;
+  args.rms_count_out = rms_count_out;
+  args.xn = xn_out;
+  args.rows = rows;
+  return 0;
+}
+
+void chain_fill_backward(ChainArgs& args, const float* const* act_in, const long long* act_ld, const float* d_out,
+                         long long ld_dout, float* const* dz_out, const long long* dz_ld, double* const* bias_partials_or_null,
+                         long long rows) {
+  for (int L = 0; L + 1 < args.num_layers; ++L) {
+    ChainLayer& ly = args.layer[L];
+    ly.h = const_cast<float*>(act_in[L]);
+    ly.ldh = act_ld[L];
+    ly.dz = dz_out[L];
+    ly.lddz = dz_ld[L];
+    ly.bias_partials = bias_partials_or_null ? bias_partials_or_null[L] : nullptr;
+  }
+  args.x = d_out;
+  args.ldx = ld_dout;
+  args.rms_mean = args.rms_var = nullptr;
+  args.rms_eps = 0.0f;
+  args.rms_batch = nullptr;
+  args.rms_count = nullptr;
+  args.rms_mean_out = args.rms_var_out = nullptr;
+  args.rms_count_out = nullptr;
+  args.xn = nullptr;
+  args.rows = rows;
+}
+
+static bool vec4_ok_host(const void* p, long long ld) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0 && (ld & 3) == 0; }
+
+int chain_rows16_status(const ChainArgs& args) {
+  for (int L = 0; L + 1 < args.num_layers; ++L) {
+    const ChainLayer& ly = args.layer[L];
+    if (ly.h == nullptr || ly.dz == nullptr) return static_cast<int>(hipErrorInvalidValue);
+    if (!(vec4_ok_host(ly.h, ly.ldh) && vec4_ok_host(ly.dz, ly.lddz) && (ly.out & 3) == 0 && ly.ldh < (1 << 20) && ly.lddz < (1 << 20)))
+      return static_cast<int>(hipErrorNotSupported);
+  }
+  return 0;
+}
+
+int chain_loss_args(LossArgs& loss, const rlg_ppo_loss_desc& d, long long rows) {
+  if (d.minibatch != rows || d.actions_num <= 0 || (d.mask_or_null && !d.mask_sum_or_null) || !d.partials ||
+      !d.mu || !d.values || !d.d_mu || !d.d_values)
+    return static_cast<int>(hipErrorInvalidValue);
+  loss.mu = d.mu;
+  loss.logstd = d.logstd;
+  loss.values = d.values;
+  loss.actions = d.actions;
+  loss.old_neglogp = d.old_neglogp;
+  loss.advantages = d.advantages;
+  loss.old_values = d.old_values;
+  loss.returns = d.returns;
+  loss.old_mu = d.old_mu;
+  loss.old_sigma = d.old_sigma;
+  loss.mask = d.mask_or_null;
+  loss.mask_sum = d.mask_sum_or_null;
+  loss.d_mu = d.d_mu;
+  loss.d_values = d.d_values;
+  loss.partials = d.partials;
+  loss.mb = d.minibatch;
+  loss.A = d.actions_num;
+  loss.ld_mu = d.ld_mu;
+  loss.ld_val = d.ld_values;
+  loss.ld_dmu = d.ld_d_mu;
+  loss.ld_dval = d.ld_d_values;
+  loss.e_clip = d.e_clip;
+  loss.critic_coef = d.critic_coef;
+  loss.bounds_coef = d.bounds_coef;
+  loss.clip_value = d.clip_value;
+  loss.smooth = d.use_smooth_clamp;
+  loss.bound_kind = d.bound_kind;
+  loss.write_back = d.write_back;
+  return 0;
+}
+
+bool chain_elu_only(const ChainArgs& args) {
+  bool elu_only = true;
+  for (int L = 0; L < args.num_layers; ++L)
+    elu_only = elu_only && (args.layer[L].act == kChElu || args.layer[L].act == kChIdentity);
+  return elu_only;
 }
 
 static bool g_chain_prepared = false;     // rlg_mlp_chain_prepare raised the LDS limit of every kernel
@@ -1389,25 +1503,10 @@ static int chain_launch_as(const ChainArgs& args_in, int lds_bytes, hipStream_t 
       raised = true;
     }
   }
-  hipEvent_t ev0 = g_chain_ev_start, ev1 = g_chain_ev_stop;
-  g_chain_ev_start = g_chain_ev_stop = nullptr;
-  if constexpr (kBackward) {
-    LossArgs none = {};
-    if (ev0 != nullptr)
-      hipExtLaunchKernelGGL((mlp_chain_bwd_kernel<G, W>), dim3(grid), dim3(64 * W), static_cast<size_t>(lds_bytes), st,
-                            ev0, ev1, 0, args, loss ? *loss : none);
-    else
-      hipLaunchKernelGGL((mlp_chain_bwd_kernel<G, W>), dim3(grid), dim3(64 * W), static_cast<size_t>(lds_bytes), st,
-                         args, loss ? *loss : none);
-  } else {
-    if (ev0 != nullptr)
-      hipExtLaunchKernelGGL((mlp_chain_fwd_kernel<G, HACT, W>), dim3(grid), dim3(64 * W),
-                            static_cast<size_t>(lds_bytes), st, ev0, ev1, 0, args);
-    else
-      hipLaunchKernelGGL((mlp_chain_fwd_kernel<G, HACT, W>), dim3(grid), dim3(64 * W),
-                         static_cast<size_t>(lds_bytes), st, args);
-  }
-  RLG_RETURN_LAUNCH_STATUS();
+  if constexpr (kBackward)
+    return chain_launch_kernel(mlp_chain_bwd_kernel<G, W>, grid, 64 * W, lds_bytes, st, args, loss ? *loss : LossArgs{});
+  else
+    return chain_launch_kernel(mlp_chain_fwd_kernel<G, HACT, W>, grid, 64 * W, lds_bytes, st, args);
 }
 
 // The pipelined kernels address every weight matrix and bias vector through ONE buffer resource: fills w_base /
@@ -1480,14 +1579,7 @@ static int chain_launch_fwd_pipe(const ChainArgs& args_in, int lds_bytes, hipStr
   int grid = static_cast<int>((args.rows + 16 * G - 1) / (16 * G));
   args.fwd_blocks = grid;
   if (args.pack.total_pairs > 0) grid += chain_bx_pack_blocks(args.pack);
-  hipEvent_t ev0 = g_chain_ev_start, ev1 = g_chain_ev_stop;
-  g_chain_ev_start = g_chain_ev_stop = nullptr;
-  if (ev0 != nullptr)
-    hipExtLaunchKernelGGL((mlp_chain_fwd_pipe_kernel<G, HACT, W>), dim3(grid), dim3(64 * W), static_cast<size_t>(lds_bytes), st,
-                          ev0, ev1, 0, args);
-  else
-    hipLaunchKernelGGL((mlp_chain_fwd_pipe_kernel<G, HACT, W>), dim3(grid), dim3(64 * W), static_cast<size_t>(lds_bytes), st, args);
-  RLG_RETURN_LAUNCH_STATUS();
+  return chain_launch_kernel(mlp_chain_fwd_pipe_kernel<G, HACT, W>, grid, 64 * W, lds_bytes, st, args);
 }
 // 16-row pipelined kernels: waves per workgroup (tools: RLG_PIPE1_WAVES=4|8)
 static int chain_pipe1_waves() {
@@ -1515,11 +1607,7 @@ static int chain_waves(int G, long long rows) {
 template <int G, bool kBackward, int W>
 static int chain_launch_w(const ChainArgs& args, int lds_bytes, hipStream_t st, const LossArgs* loss) {
   if constexpr (!kBackward) {
-    // forward: the ELU-or-identity network (every BASELINE configuration) gets its own instance
-    bool elu_only = true;
-    for (int L = 0; L < args.num_layers; ++L)
-      elu_only = elu_only && (args.layer[L].act == kChElu || args.layer[L].act == kChIdentity);
-    if (elu_only) return chain_launch_as<G, false, kChElu, W>(args, lds_bytes, st, loss);
+    if (chain_elu_only(args)) return chain_launch_as<G, false, kChElu, W>(args, lds_bytes, st, loss);
   }
   return chain_launch_as<G, kBackward, kChAny, W>(args, lds_bytes, st, loss);
 }
@@ -1658,29 +1746,10 @@ int rlg_mlp_chain_forward(int num_layers, const float* const* weights, const flo
     if (const int e = chain_bx_pack_launch(args.pack, static_cast<hipStream_t>(stream))) return e;
     args.pack.total_pairs = 0;
   }
-  for (int L = 0; L < num_layers; ++L) {
-    args.layer[L].bias = biases[L];
-    args.layer[L].h = act_out[L];
-    args.layer[L].ldh = act_ld[L];
-  }
   if (act_out[num_layers - 1] == nullptr) return static_cast<int>(hipErrorInvalidValue);
-  args.x = x;
-  args.ldx = ldx;
-  args.rms_mean = rms_mean;
-  args.rms_var = rms_mean ? rms_var : nullptr;
-  args.rms_eps = rms_eps;
-  args.rms_batch = rms_mean ? rms_batch : nullptr;
-  if (args.rms_batch) {
-    if (!rms_count || !rms_mean_out || !rms_var_out || !rms_count_out || rms_mean_out == rms_mean ||
-        rms_var_out == rms_var || rms_count_out == rms_count)
-      return static_cast<int>(hipErrorInvalidValue);      // the fold publishes into a second buffer set
-  }
-  args.rms_count = rms_count;
-  args.rms_mean_out = rms_mean_out;
-  args.rms_var_out = rms_var_out;
-  args.rms_count_out = rms_count_out;
-  args.xn = xn_out;
-  args.rows = rows;
+  if (const int e = chain_fill_forward(args, biases, act_out, act_ld, x, ldx, rms_mean, rms_var, rms_eps, xn_out, rms_batch,
+                                       rms_count, rms_mean_out, rms_var_out, rms_count_out, rows))
+    return e;
   args.dbg = g_chain_dbg;
   bool training = false;
   for (int L = 0; L + 1 < num_layers; ++L) training = training || act_out[L] != nullptr;
@@ -1703,14 +1772,13 @@ int rlg_mlp_chain_forward(int num_layers, const float* const* weights, const flo
     bx.planes_bytes = static_cast<unsigned>(total);
     const int bx_lds = chain_bx_fwd_plan(bx);
     if (bx_lds >= 0 && total < static_cast<long long>(kOob) && chain_bx_fwd_eligible(bx)) {
-      hipEvent_t ev0 = g_chain_ev_start, ev1 = g_chain_ev_stop;
-      g_chain_ev_start = g_chain_ev_stop = nullptr;
+      hipEvent_t ev0 = nullptr, ev1 = nullptr;
+      chain_take_events(&ev0, &ev1);
       return chain_bx_launch_fwd(bx, bx_lds, st, ev0, ev1);
     }
   }
   if ((G >= 2 || chain_pipe1_enabled()) && chain_pipe_enabled() && chain_pipe_fill(args, true)) {
-    bool elu_only = true;
-    for (int L = 0; L < num_layers; ++L) elu_only = elu_only && (acts[L] == kChElu || acts[L] == kChIdentity);
+    const bool elu_only = chain_elu_only(args);
     if (G == 1 && chain_pipe1_waves() == 8)
       return elu_only ? chain_launch_fwd_pipe<1, kChElu, 8>(args, lds_bytes, st) : chain_launch_fwd_pipe<1, kChAny, 8>(args, lds_bytes, st);
     if (G == 1 && chain_pipe1_waves() == 16)
@@ -1740,24 +1808,10 @@ int rlg_mlp_chain_backward(int num_layers, const float* const* weights, const in
   if (chain_fill(args, num_layers, weights, in_features, out_features, acts)) return static_cast<int>(hipErrorInvalidValue);
   args.amax = nullptr;
   args.amax_stride = 0;
+  chain_fill_backward(args, act_in, act_ld, d_out, ld_dout, dz_out, dz_ld, bias_partials, rows);
   for (int L = 0; L + 1 < num_layers; ++L) {
-    args.layer[L].h = const_cast<float*>(act_in[L]);
-    args.layer[L].ldh = act_ld[L];
-    args.layer[L].dz = dz_out[L];
-    args.layer[L].lddz = dz_ld[L];
-    args.layer[L].bias_partials = bias_partials ? bias_partials[L] : nullptr;
     if (act_in[L] == nullptr || dz_out[L] == nullptr) return static_cast<int>(hipErrorInvalidValue);
   }
-  args.x = d_out;
-  args.ldx = ld_dout;
-  args.rms_mean = args.rms_var = nullptr;
-  args.rms_eps = 0.0f;
-  args.rms_batch = nullptr;
-  args.rms_count = nullptr;
-  args.rms_mean_out = args.rms_var_out = nullptr;
-  args.rms_count_out = nullptr;
-  args.xn = nullptr;
-  args.rows = rows;
   const int G = pick_groups(rows, groups, 1);
   int b_floats = 0;
   int lds_bytes = chain_lds(num_layers, in_features, out_features, G, 1, &b_floats);
@@ -1766,39 +1820,8 @@ int rlg_mlp_chain_backward(int num_layers, const float* const* weights, const in
   LossArgs loss = {};
   args.with_loss = ppo_loss ? 1 : 0;
   if (ppo_loss) {
-    const rlg_ppo_loss_desc& d = *ppo_loss;
-    if (d.minibatch != rows || d.actions_num <= 0 || (d.mask_or_null && !d.mask_sum_or_null) || !d.partials ||
-        !d.mu || !d.values || !d.d_mu || !d.d_values)
-      return static_cast<int>(hipErrorInvalidValue);
-    loss.mu = d.mu;
-    loss.logstd = d.logstd;
-    loss.values = d.values;
-    loss.actions = d.actions;
-    loss.old_neglogp = d.old_neglogp;
-    loss.advantages = d.advantages;
-    loss.old_values = d.old_values;
-    loss.returns = d.returns;
-    loss.old_mu = d.old_mu;
-    loss.old_sigma = d.old_sigma;
-    loss.mask = d.mask_or_null;
-    loss.mask_sum = d.mask_sum_or_null;
-    loss.d_mu = d.d_mu;
-    loss.d_values = d.d_values;
-    loss.partials = d.partials;
-    loss.mb = d.minibatch;
-    loss.A = d.actions_num;
-    loss.ld_mu = d.ld_mu;
-    loss.ld_val = d.ld_values;
-    loss.ld_dmu = d.ld_d_mu;
-    loss.ld_dval = d.ld_d_values;
-    loss.e_clip = d.e_clip;
-    loss.critic_coef = d.critic_coef;
-    loss.bounds_coef = d.bounds_coef;
-    loss.clip_value = d.clip_value;
-    loss.smooth = d.use_smooth_clamp;
-    loss.bound_kind = d.bound_kind;
-    loss.write_back = d.write_back;
-    const int need = static_cast<int>(ppo_loss_lds_bytes(16 * G, d.actions_num, 512));
+    if (const int e = chain_loss_args(loss, *ppo_loss, rows)) return e;
+    const int need = static_cast<int>(ppo_loss_lds_bytes(16 * G, ppo_loss->actions_num, 512));
     if (need > 160 * 1024) return static_cast<int>(hipErrorInvalidValue);
     if (need > lds_bytes) lds_bytes = need;
   }
@@ -1849,39 +1872,10 @@ int rlg_mlp_chain_backward(int num_layers, const float* const* weights, const in
   if (G == 2) return chain_launch<2, true>(args, lds_bytes, st, lp);
   // 16-row workgroups: the pipelined kernel when every H / dZ array takes 16-byte row accesses
   if (chain_pipe1_enabled() && chain_pipe_enabled()) {
-    bool ok = g_chain_dbg == nullptr;
-    for (int L = 0; L + 1 < num_layers && ok; ++L) {
-      const ChainLayer& ly = args.layer[L];
-      ok = vec4_ok_host(ly.h, ly.ldh) && vec4_ok_host(ly.dz, ly.lddz) && (ly.out & 3) == 0 && ly.ldh < (1 << 20) && ly.lddz < (1 << 20);
-    }
-    if (ok) {
-      const int grid = static_cast<int>((rows + 15) / 16);
-      hipEvent_t ev0 = g_chain_ev_start, ev1 = g_chain_ev_stop;
-      g_chain_ev_start = g_chain_ev_stop = nullptr;
-      LossArgs none = {};
-      if (chain_pipe1_waves() == 16) {
-        if (ev0 != nullptr)
-          hipExtLaunchKernelGGL(mlp_chain_bwd_pipe_kernel<16>, dim3(grid), dim3(1024), static_cast<size_t>(lds_bytes), st, ev0, ev1, 0,
-                                args, lp ? *lp : none);
-        else
-          hipLaunchKernelGGL(mlp_chain_bwd_pipe_kernel<16>, dim3(grid), dim3(1024), static_cast<size_t>(lds_bytes), st, args,
-                             lp ? *lp : none);
-      } else if (chain_pipe1_waves() == 8) {
-        if (ev0 != nullptr)
-          hipExtLaunchKernelGGL(mlp_chain_bwd_pipe_kernel<8>, dim3(grid), dim3(512), static_cast<size_t>(lds_bytes), st, ev0, ev1, 0,
-                                args, lp ? *lp : none);
-        else
-          hipLaunchKernelGGL(mlp_chain_bwd_pipe_kernel<8>, dim3(grid), dim3(512), static_cast<size_t>(lds_bytes), st, args,
-                             lp ? *lp : none);
-      } else {
-        if (ev0 != nullptr)
-          hipExtLaunchKernelGGL(mlp_chain_bwd_pipe_kernel<4>, dim3(grid), dim3(256), static_cast<size_t>(lds_bytes), st, ev0, ev1, 0,
-                                args, lp ? *lp : none);
-        else
-          hipLaunchKernelGGL(mlp_chain_bwd_pipe_kernel<4>, dim3(grid), dim3(256), static_cast<size_t>(lds_bytes), st, args,
-                             lp ? *lp : none);
-      }
-      RLG_RETURN_LAUNCH_STATUS();
+    if (g_chain_dbg == nullptr && chain_rows16_status(args) == 0) {
+      const int W = chain_pipe1_waves();
+      const auto kern = W == 16 ? mlp_chain_bwd_pipe_kernel<16> : (W == 8 ? mlp_chain_bwd_pipe_kernel<8> : mlp_chain_bwd_pipe_kernel<4>);
+      return chain_launch_kernel(kern, static_cast<int>((rows + 15) / 16), 64 * W, lds_bytes, st, args, lp ? *lp : LossArgs{});
     }
   }
   return chain_launch<1, true>(args, lds_bytes, st, lp);
@@ -1919,28 +1913,11 @@ int rlg_mlp_chain_step(int num_layers, const float* const* weights, const float*
   ChainArgs fa;
   if (chain_fill(fa, num_layers, weights, in_features, out_features, acts)) return static_cast<int>(hipErrorInvalidValue);
   for (int L = 0; L < num_layers; ++L) {
-    fa.layer[L].bias = biases[L];
-    fa.layer[L].h = act_out[L];
-    fa.layer[L].ldh = act_ld[L];
     if (act_out[L] == nullptr) return static_cast<int>(hipErrorNotSupported);       // training form only
   }
-  fa.x = x;
-  fa.ldx = ldx;
-  fa.rms_mean = rms_mean;
-  fa.rms_var = rms_mean ? rms_var : nullptr;
-  fa.rms_eps = rms_eps;
-  fa.rms_batch = rms_mean ? rms_batch : nullptr;
-  if (fa.rms_batch) {
-    if (!rms_count || !rms_mean_out || !rms_var_out || !rms_count_out || rms_mean_out == rms_mean ||
-        rms_var_out == rms_var || rms_count_out == rms_count)
-      return static_cast<int>(hipErrorInvalidValue);
-  }
-  fa.rms_count = rms_count;
-  fa.rms_mean_out = rms_mean_out;
-  fa.rms_var_out = rms_var_out;
-  fa.rms_count_out = rms_count_out;
-  fa.xn = xn_out;
-  fa.rows = rows;
+  if (const int e = chain_fill_forward(fa, biases, act_out, act_ld, x, ldx, rms_mean, rms_var, rms_eps, xn_out, rms_batch,
+                                       rms_count, rms_mean_out, rms_var_out, rms_count_out, rows))
+    return e;
   fa.dbg = nullptr;
   int fb = 0;
   const int fwd_lds = chain_lds(num_layers, in_features, out_features, 1, 0, &fb);
@@ -1952,87 +1929,23 @@ int rlg_mlp_chain_step(int num_layers, const float* const* weights, const float*
   // ---- backward arguments (as rlg_mlp_chain_backward); H of the hidden layers = what the forward half writes
   ChainArgs ba;
   if (chain_fill(ba, num_layers, weights, in_features, out_features, acts)) return static_cast<int>(hipErrorInvalidValue);
-  for (int L = 0; L + 1 < num_layers; ++L) {
-    ba.layer[L].h = act_out[L];
-    ba.layer[L].ldh = act_ld[L];
-    ba.layer[L].dz = dz_out[L];
-    ba.layer[L].lddz = dz_ld[L];
-    ba.layer[L].bias_partials = bias_partials ? bias_partials[L] : nullptr;
-    if (dz_out[L] == nullptr) return static_cast<int>(hipErrorInvalidValue);
-    const ChainLayer& ly = ba.layer[L];
-    if (!(vec4_ok_host(ly.h, ly.ldh) && vec4_ok_host(ly.dz, ly.lddz) && (ly.out & 3) == 0 && ly.ldh < (1 << 20) && ly.lddz < (1 << 20)))
-      return static_cast<int>(hipErrorNotSupported);
-  }
-  ba.x = d_out;
-  ba.ldx = ld_dout;
-  ba.rms_mean = ba.rms_var = nullptr;
-  ba.rms_eps = 0.0f;
-  ba.rms_batch = nullptr;
-  ba.rms_count = nullptr;
-  ba.rms_mean_out = ba.rms_var_out = nullptr;
-  ba.rms_count_out = nullptr;
-  ba.xn = nullptr;
-  ba.rows = rows;
+  chain_fill_backward(ba, act_out, act_ld, d_out, ld_dout, dz_out, dz_ld, bias_partials, rows);
+  if (const int e = chain_rows16_status(ba)) return e;
   ba.with_loss = 1;
   int bb = 0;
   int bwd_lds = chain_lds(num_layers, in_features, out_features, 1, 1, &bb);
   if (bwd_lds < 0) return static_cast<int>(hipErrorNotSupported);
   ba.lds_b_floats = bb;
   const rlg_ppo_loss_desc& d = *ppo_loss;
-  if (d.minibatch != rows || d.actions_num <= 0 || d.actions_num > 4 * kQuadK || (d.mask_or_null && !d.mask_sum_or_null) ||
-      !d.partials || !d.mu || !d.values || !d.d_mu || !d.d_values)
-    return d.actions_num > 4 * kQuadK ? static_cast<int>(hipErrorNotSupported) : static_cast<int>(hipErrorInvalidValue);
+  if (d.actions_num > 4 * kQuadK) return static_cast<int>(hipErrorNotSupported);
   LossArgs loss = {};
-  loss.mu = d.mu;
-  loss.logstd = d.logstd;
-  loss.values = d.values;
-  loss.actions = d.actions;
-  loss.old_neglogp = d.old_neglogp;
-  loss.advantages = d.advantages;
-  loss.old_values = d.old_values;
-  loss.returns = d.returns;
-  loss.old_mu = d.old_mu;
-  loss.old_sigma = d.old_sigma;
-  loss.mask = d.mask_or_null;
-  loss.mask_sum = d.mask_sum_or_null;
-  loss.d_mu = d.d_mu;
-  loss.d_values = d.d_values;
-  loss.partials = d.partials;
-  loss.mb = d.minibatch;
-  loss.A = d.actions_num;
-  loss.ld_mu = d.ld_mu;
-  loss.ld_val = d.ld_values;
-  loss.ld_dmu = d.ld_d_mu;
-  loss.ld_dval = d.ld_d_values;
-  loss.e_clip = d.e_clip;
-  loss.critic_coef = d.critic_coef;
-  loss.bounds_coef = d.bounds_coef;
-  loss.clip_value = d.clip_value;
-  loss.smooth = d.use_smooth_clamp;
-  loss.bound_kind = d.bound_kind;
-  loss.write_back = d.write_back;
+  if (const int e = chain_loss_args(loss, d, rows)) return e;
   const int need = static_cast<int>(ppo_loss_lds_bytes(16, d.actions_num, 512));
   int lds_bytes = fwd_lds > bwd_lds ? fwd_lds : bwd_lds;
   if (need > lds_bytes) lds_bytes = need;
   if (lds_bytes > 160 * 1024) return static_cast<int>(hipErrorNotSupported);
-  bool elu_only = true;
-  for (int L = 0; L < num_layers; ++L) elu_only = elu_only && (acts[L] == kChElu || acts[L] == kChIdentity);
-  const int grid = static_cast<int>((rows + 15) / 16);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  hipEvent_t ev0 = g_chain_ev_start, ev1 = g_chain_ev_stop;
-  g_chain_ev_start = g_chain_ev_stop = nullptr;
-  if (elu_only) {
-    if (ev0 != nullptr)
-      hipExtLaunchKernelGGL((mlp_chain_step_pipe_kernel<kChElu, 8>), dim3(grid), dim3(512), static_cast<size_t>(lds_bytes), st, ev0, ev1, 0, fa, ba, loss);
-    else
-      hipLaunchKernelGGL((mlp_chain_step_pipe_kernel<kChElu, 8>), dim3(grid), dim3(512), static_cast<size_t>(lds_bytes), st, fa, ba, loss);
-  } else {
-    if (ev0 != nullptr)
-      hipExtLaunchKernelGGL((mlp_chain_step_pipe_kernel<kChAny, 8>), dim3(grid), dim3(512), static_cast<size_t>(lds_bytes), st, ev0, ev1, 0, fa, ba, loss);
-    else
-      hipLaunchKernelGGL((mlp_chain_step_pipe_kernel<kChAny, 8>), dim3(grid), dim3(512), static_cast<size_t>(lds_bytes), st, fa, ba, loss);
-  }
-  RLG_RETURN_LAUNCH_STATUS();
+  const auto kern = chain_elu_only(fa) ? mlp_chain_step_pipe_kernel<kChElu, 8> : mlp_chain_step_pipe_kernel<kChAny, 8>;
+  return chain_launch_kernel(kern, static_cast<int>((rows + 15) / 16), 512, lds_bytes, static_cast<hipStream_t>(stream), fa, ba, loss);
 }
 
 

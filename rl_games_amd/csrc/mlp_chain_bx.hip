@@ -33,6 +33,7 @@
 #endif
 
 #include "mlp_chain_bx.hpp"
+#include "mlp_chain_shared.hpp"
 #include "optim_common.hpp"
 
 #ifndef RLG_BX_TRACK
@@ -426,14 +427,7 @@ template <int G, int PACT>
 static int chain_bx_launch_bwd_as(const ChainArgs& args, int lds_bytes, hipStream_t st, const LossArgs* loss, hipEvent_t ev0,
                                   hipEvent_t ev1) {
   const int grid = static_cast<int>((args.rows + 16 * G - 1) / (16 * G));
-  LossArgs none = {};
-  if (ev0 != nullptr)
-    hipExtLaunchKernelGGL((mlp_chain_bwd_bx_kernel<G, PACT>), dim3(grid), dim3(64 * kBwW), static_cast<size_t>(lds_bytes), st, ev0,
-                          ev1, 0, args, loss ? *loss : none);
-  else
-    hipLaunchKernelGGL((mlp_chain_bwd_bx_kernel<G, PACT>), dim3(grid), dim3(64 * kBwW), static_cast<size_t>(lds_bytes), st, args,
-                       loss ? *loss : none);
-  RLG_RETURN_LAUNCH_STATUS();
+  return chain_launch_timed(mlp_chain_bwd_bx_kernel<G, PACT>, grid, 64 * kBwW, lds_bytes, st, ev0, ev1, args, loss ? *loss : LossArgs{});
 }
 // raises the dynamic-LDS limit of the kernels once, outside any stream capture (rlg_mlp_chain_prepare)
 int chain_bx_prepare() {

@@ -33,6 +33,7 @@
 #endif
 
 #include "mlp_chain_bx.hpp"
+#include "mlp_chain_shared.hpp"
 
 namespace rlg {
 
@@ -532,12 +533,7 @@ static int chain_bx_launch_fwd_as(const ChainArgs& args_in, int lds_bytes, hipSt
   int grid = static_cast<int>((args.rows + 16 * kFwG - 1) / (16 * kFwG));
   args.fwd_blocks = grid;
   if (args.pack.total_pairs > 0) grid += chain_bx_pack_blocks(args.pack);
-  if (ev0 != nullptr)
-    hipExtLaunchKernelGGL((mlp_chain_fwd_bx_kernel<HACT>), dim3(grid), dim3(64 * kFwW), static_cast<size_t>(lds_bytes), st, ev0,
-                          ev1, 0, args);
-  else
-    hipLaunchKernelGGL((mlp_chain_fwd_bx_kernel<HACT>), dim3(grid), dim3(64 * kFwW), static_cast<size_t>(lds_bytes), st, args);
-  RLG_RETURN_LAUNCH_STATUS();
+  return chain_launch_timed(mlp_chain_fwd_bx_kernel<HACT>, grid, 64 * kFwW, lds_bytes, st, ev0, ev1, args);
 }
 int chain_bx_fwd_prepare() {
   static bool raised = false;
@@ -552,10 +548,7 @@ int chain_bx_fwd_prepare() {
 }
 int chain_bx_launch_fwd(const ChainArgs& args, int lds_bytes, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
   if (const int e = chain_bx_fwd_prepare()) return e;
-  bool elu_only = true;
-  for (int L = 0; L < args.num_layers; ++L)
-    elu_only = elu_only && (args.layer[L].act == kChElu || args.layer[L].act == kChIdentity);
-  return elu_only ? chain_bx_launch_fwd_as<kChElu>(args, lds_bytes, st, ev0, ev1)
+  return chain_elu_only(args) ? chain_bx_launch_fwd_as<kChElu>(args, lds_bytes, st, ev0, ev1)
                   : chain_bx_launch_fwd_as<kChAny>(args, lds_bytes, st, ev0, ev1);
 }
 

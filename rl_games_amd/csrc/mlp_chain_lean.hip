@@ -736,41 +736,19 @@ int rlg_mlp_chain_forward_lean(int num_layers, const float* const* biases, const
                                void* stream) {
   using namespace rlg;
   if (rows <= 0) return 0;
-  if (frags == nullptr) return static_cast<int>(hipErrorInvalidValue);
+  if (frags == nullptr || reinterpret_cast<uintptr_t>(frags) % 4 != 0) return static_cast<int>(hipErrorInvalidValue);
   ChainArgs args;
-  const float* none[kChainMaxLayers] = {};
-  {
-    // chain_fill wants weight pointers for its alignment check only: the fragments stand in
-    for (int L = 0; L < num_layers && L < kChainMaxLayers; ++L) none[L] = static_cast<const float*>(frags);
-  }
-  if (chain_fill(args, num_layers, none, in_features, out_features, acts)) return static_cast<int>(hipErrorInvalidValue);
+  if (chain_fill_shape(args, num_layers, in_features, out_features, acts)) return static_cast<int>(hipErrorInvalidValue);
   LeanPackArgs pk = {};
   const long long plan = chain_lean_plan(num_layers, in_features, out_features, 0, &pk);
   if (plan < 0) return static_cast<int>(hipErrorNotSupported);
   for (int L = 0; L < num_layers; ++L) {
-    args.layer[L].bias = biases ? biases[L] : nullptr;
-    args.layer[L].h = act_out[L];
-    args.layer[L].ldh = act_ld[L];
-    if (reinterpret_cast<uintptr_t>(args.layer[L].bias) % 4 != 0) return static_cast<int>(hipErrorInvalidValue);
+    if (biases && reinterpret_cast<uintptr_t>(biases[L]) % 4 != 0) return static_cast<int>(hipErrorInvalidValue);
   }
   if (act_out[num_layers - 1] == nullptr) return static_cast<int>(hipErrorInvalidValue);
-  args.x = x;
-  args.ldx = ldx;
-  args.rms_mean = rms_mean;
-  args.rms_var = rms_mean ? rms_var : nullptr;
-  args.rms_eps = rms_eps;
-  args.rms_batch = rms_mean ? rms_batch : nullptr;
-  if (args.rms_batch) {
-    if (!rms_count || !rms_mean_out || !rms_var_out || !rms_count_out || rms_mean_out == rms_mean ||
-        rms_var_out == rms_var || rms_count_out == rms_count)
-      return static_cast<int>(hipErrorInvalidValue);
-  }
-  args.rms_count = rms_count;
-  args.rms_mean_out = rms_mean_out;
-  args.rms_var_out = rms_var_out;
-  args.rms_count_out = rms_count_out;
-  args.xn = xn_out;
-  args.rows = rows;
+  if (const int e = chain_fill_forward(args, biases, act_out, act_ld, x, ldx, rms_mean, rms_var, rms_eps, xn_out, rms_batch,
+                                       rms_count, rms_mean_out, rms_var_out, rms_count_out, rows))
+    return e;
   args.dbg = chain_debug_stamps();
   args.lds_b_floats = pk.la.tile_b_floats;
   args.lds_split_floats = 0;
@@ -779,19 +757,8 @@ int rlg_mlp_chain_forward_lean(int num_layers, const float* const* biases, const
   la.wf = static_cast<const float*>(frags);
   const int lds_bytes = chain_lean_tile_floats(plan) * 4;
   if (lds_bytes > 64 * 1024) return static_cast<int>(hipErrorNotSupported);
-  bool elu_only = true;
-  for (int L = 0; L < num_layers; ++L) elu_only = elu_only && (acts[L] == kChElu || acts[L] == kChIdentity);
-  const int grid = static_cast<int>((rows + 15) / 16);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  // (rlg_mlp_chain_time_next: the events ride on this dispatch)
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  chain_take_events(&ev0, &ev1);
-  const auto kern = elu_only ? mlp_chain_fwd_lean_kernel<kChElu> : mlp_chain_fwd_lean_kernel<kChAny>;
-  if (ev0 != nullptr)       // (the plain launch otherwise: the one that stream capture takes)
-    hipExtLaunchKernelGGL(kern, dim3(grid), dim3(64 * kLeanW), static_cast<size_t>(lds_bytes), st, ev0, ev1, 0, args, la);
-  else
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * kLeanW), static_cast<size_t>(lds_bytes), st, args, la);
-  RLG_RETURN_LAUNCH_STATUS();
+  const auto kern = chain_elu_only(args) ? mlp_chain_fwd_lean_kernel<kChElu> : mlp_chain_fwd_lean_kernel<kChAny>;
+  return chain_launch_kernel(kern, static_cast<int>((rows + 15) / 16), 64 * kLeanW, lds_bytes, static_cast<hipStream_t>(stream), args, la);
 }
 
 int rlg_mlp_chain_backward_lean(int num_layers, const int* in_features, const int* out_features, const int* acts,
@@ -800,73 +767,21 @@ int rlg_mlp_chain_backward_lean(int num_layers, const int* in_features, const in
                                 const rlg_ppo_loss_desc* ppo_loss, long long rows, const void* frags, void* stream) {
   using namespace rlg;
   if (rows <= 0) return 0;
-  if (num_layers < 2 || frags == nullptr) return static_cast<int>(hipErrorInvalidValue);
+  if (num_layers < 2 || frags == nullptr || reinterpret_cast<uintptr_t>(frags) % 4 != 0) return static_cast<int>(hipErrorInvalidValue);
   ChainArgs args;
-  const float* none[kChainMaxLayers] = {};
-  for (int L = 0; L < num_layers && L < kChainMaxLayers; ++L) none[L] = static_cast<const float*>(frags);
-  if (chain_fill(args, num_layers, none, in_features, out_features, acts)) return static_cast<int>(hipErrorInvalidValue);
+  if (chain_fill_shape(args, num_layers, in_features, out_features, acts)) return static_cast<int>(hipErrorInvalidValue);
   LeanPackArgs pk = {};
   const long long plan = chain_lean_plan(num_layers, in_features, out_features, 1, &pk);
   if (plan < 0) return static_cast<int>(hipErrorNotSupported);
-  for (int L = 0; L + 1 < num_layers; ++L) {
-    ChainLayer& ly = args.layer[L];
-    ly.h = const_cast<float*>(act_in[L]);
-    ly.ldh = act_ld[L];
-    ly.dz = dz_out[L];
-    ly.lddz = dz_ld[L];
-    ly.bias_partials = bias_partials ? bias_partials[L] : nullptr;
-    if (act_in[L] == nullptr || dz_out[L] == nullptr) return static_cast<int>(hipErrorInvalidValue);
-    if (!(vec4_ok_host(ly.h, ly.ldh) && vec4_ok_host(ly.dz, ly.lddz) && (ly.out & 3) == 0 && ly.ldh < (1 << 20) && ly.lddz < (1 << 20)))
-      return static_cast<int>(hipErrorNotSupported);
-  }
-  args.x = d_out;
-  args.ldx = ld_dout;
-  args.rms_mean = args.rms_var = nullptr;
-  args.rms_eps = 0.0f;
-  args.rms_batch = nullptr;
-  args.rms_count = nullptr;
-  args.rms_mean_out = args.rms_var_out = nullptr;
-  args.rms_count_out = nullptr;
-  args.xn = nullptr;
-  args.rows = rows;
+  chain_fill_backward(args, act_in, act_ld, d_out, ld_dout, dz_out, dz_ld, bias_partials, rows);
+  if (const int e = chain_rows16_status(args)) return e;
   args.lds_b_floats = pk.la.tile_b_floats;
   int lds_bytes = chain_lean_tile_floats(plan) * 4;
   LossArgs loss = {};
   args.with_loss = ppo_loss ? 1 : 0;
   if (ppo_loss) {
-    const rlg_ppo_loss_desc& d = *ppo_loss;
-    if (d.minibatch != rows || d.actions_num <= 0 || (d.mask_or_null && !d.mask_sum_or_null) || !d.partials ||
-        !d.mu || !d.values || !d.d_mu || !d.d_values)
-      return static_cast<int>(hipErrorInvalidValue);
-    loss.mu = d.mu;
-    loss.logstd = d.logstd;
-    loss.values = d.values;
-    loss.actions = d.actions;
-    loss.old_neglogp = d.old_neglogp;
-    loss.advantages = d.advantages;
-    loss.old_values = d.old_values;
-    loss.returns = d.returns;
-    loss.old_mu = d.old_mu;
-    loss.old_sigma = d.old_sigma;
-    loss.mask = d.mask_or_null;
-    loss.mask_sum = d.mask_sum_or_null;
-    loss.d_mu = d.d_mu;
-    loss.d_values = d.d_values;
-    loss.partials = d.partials;
-    loss.mb = d.minibatch;
-    loss.A = d.actions_num;
-    loss.ld_mu = d.ld_mu;
-    loss.ld_val = d.ld_values;
-    loss.ld_dmu = d.ld_d_mu;
-    loss.ld_dval = d.ld_d_values;
-    loss.e_clip = d.e_clip;
-    loss.critic_coef = d.critic_coef;
-    loss.bounds_coef = d.bounds_coef;
-    loss.clip_value = d.clip_value;
-    loss.smooth = d.use_smooth_clamp;
-    loss.bound_kind = d.bound_kind;
-    loss.write_back = d.write_back;
-    const int need = static_cast<int>(ppo_loss_lds_bytes(16, d.actions_num, 512));
+    if (const int e = chain_loss_args(loss, *ppo_loss, rows)) return e;
+    const int need = static_cast<int>(ppo_loss_lds_bytes(16, ppo_loss->actions_num, 512));
     if (need > lds_bytes) lds_bytes = need;
   }
   // gradient maxima for the weight-gradient launch (rlg_mlp_chain_gradient_maxima; one entry per 16-row workgroup here): the
@@ -888,16 +803,8 @@ int rlg_mlp_chain_backward_lean(int num_layers, const int* in_features, const in
   if (lds_bytes > 64 * 1024) return static_cast<int>(hipErrorNotSupported);
   LeanArgs la = pk.la;
   la.wf = static_cast<const float*>(frags);
-  const int grid = static_cast<int>((rows + 15) / 16);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  chain_take_events(&ev0, &ev1);
-  const auto kern = mlp_chain_bwd_lean_kernel;
-  if (ev0 != nullptr)
-    hipExtLaunchKernelGGL(kern, dim3(grid), dim3(64 * kLeanW), static_cast<size_t>(lds_bytes), st, ev0, ev1, 0, args, la, loss);
-  else
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * kLeanW), static_cast<size_t>(lds_bytes), st, args, la, loss);
-  RLG_RETURN_LAUNCH_STATUS();
+  return chain_launch_kernel(mlp_chain_bwd_lean_kernel, static_cast<int>((rows + 15) / 16), 64 * kLeanW, lds_bytes,
+                             static_cast<hipStream_t>(stream), args, la, loss);
 }
 
 // forward and backward fragments of the lean kernels in ONE launch (behind every optimiser step of an agent whose
@@ -944,100 +851,34 @@ int rlg_mlp_chain_step_lean(int num_layers, const float* const* biases, const in
       return static_cast<int>(hipErrorNotSupported);
     if ((rows + 15) / 16 > cus) return static_cast<int>(hipErrorNotSupported);
   }
-  const float* none[kChainMaxLayers] = {};
-  for (int L = 0; L < num_layers && L < kChainMaxLayers; ++L) none[L] = static_cast<const float*>(frags_fwd);
   ChainArgs fa;
-  if (chain_fill(fa, num_layers, none, in_features, out_features, acts)) return static_cast<int>(hipErrorInvalidValue);
+  if (chain_fill_shape(fa, num_layers, in_features, out_features, acts) || reinterpret_cast<uintptr_t>(frags_fwd) % 4 != 0)
+    return static_cast<int>(hipErrorInvalidValue);
   LeanPackArgs fpk = {}, bpk = {};
   const long long fplan = chain_lean_plan(num_layers, in_features, out_features, 0, &fpk);
   const long long bplan = chain_lean_plan(num_layers, in_features, out_features, 1, &bpk);
   if (fplan < 0 || bplan < 0) return static_cast<int>(hipErrorNotSupported);
   for (int L = 0; L < num_layers; ++L) {
-    fa.layer[L].bias = biases ? biases[L] : nullptr;
-    fa.layer[L].h = act_out[L];
-    fa.layer[L].ldh = act_ld[L];
     if (act_out[L] == nullptr) return static_cast<int>(hipErrorNotSupported);       // training form only
-    if (reinterpret_cast<uintptr_t>(fa.layer[L].bias) % 4 != 0) return static_cast<int>(hipErrorInvalidValue);
+    if (biases && reinterpret_cast<uintptr_t>(biases[L]) % 4 != 0) return static_cast<int>(hipErrorInvalidValue);
   }
-  fa.x = x;
-  fa.ldx = ldx;
-  fa.rms_mean = rms_mean;
-  fa.rms_var = rms_mean ? rms_var : nullptr;
-  fa.rms_eps = rms_eps;
-  fa.rms_batch = rms_mean ? rms_batch : nullptr;
-  if (fa.rms_batch) {
-    if (!rms_count || !rms_mean_out || !rms_var_out || !rms_count_out || rms_mean_out == rms_mean ||
-        rms_var_out == rms_var || rms_count_out == rms_count)
-      return static_cast<int>(hipErrorInvalidValue);
-  }
-  fa.rms_count = rms_count;
-  fa.rms_mean_out = rms_mean_out;
-  fa.rms_var_out = rms_var_out;
-  fa.rms_count_out = rms_count_out;
-  fa.xn = xn_out;
-  fa.rows = rows;
+  if (const int e = chain_fill_forward(fa, biases, act_out, act_ld, x, ldx, rms_mean, rms_var, rms_eps, xn_out, rms_batch,
+                                       rms_count, rms_mean_out, rms_var_out, rms_count_out, rows))
+    return e;
   fa.dbg = nullptr;
   fa.lds_b_floats = fpk.la.tile_b_floats;
   fa.lds_split_floats = 0;
   fa.no_ksplit = 1;
   ChainArgs ba;
-  if (chain_fill(ba, num_layers, none, in_features, out_features, acts)) return static_cast<int>(hipErrorInvalidValue);
-  for (int L = 0; L + 1 < num_layers; ++L) {
-    ChainLayer& ly = ba.layer[L];
-    ly.h = act_out[L];
-    ly.ldh = act_ld[L];
-    ly.dz = dz_out[L];
-    ly.lddz = dz_ld[L];
-    ly.bias_partials = bias_partials ? bias_partials[L] : nullptr;
-    if (dz_out[L] == nullptr) return static_cast<int>(hipErrorInvalidValue);
-    if (!(vec4_ok_host(ly.h, ly.ldh) && vec4_ok_host(ly.dz, ly.lddz) && (ly.out & 3) == 0 && ly.ldh < (1 << 20) && ly.lddz < (1 << 20)))
-      return static_cast<int>(hipErrorNotSupported);
-  }
-  ba.x = d_out;
-  ba.ldx = ld_dout;
-  ba.rms_mean = ba.rms_var = nullptr;
-  ba.rms_eps = 0.0f;
-  ba.rms_batch = nullptr;
-  ba.rms_count = nullptr;
-  ba.rms_mean_out = ba.rms_var_out = nullptr;
-  ba.rms_count_out = nullptr;
-  ba.xn = nullptr;
-  ba.rows = rows;
+  if (chain_fill_shape(ba, num_layers, in_features, out_features, acts)) return static_cast<int>(hipErrorInvalidValue);
+  chain_fill_backward(ba, act_out, act_ld, d_out, ld_dout, dz_out, dz_ld, bias_partials, rows);
+  if (const int e = chain_rows16_status(ba)) return e;
   ba.with_loss = 1;
   ba.lds_b_floats = bpk.la.tile_b_floats;
   const rlg_ppo_loss_desc& d = *ppo_loss;
-  if (d.minibatch != rows || d.actions_num <= 0 || d.actions_num > 4 * kQuadK || (d.mask_or_null && !d.mask_sum_or_null) ||
-      !d.partials || !d.mu || !d.values || !d.d_mu || !d.d_values)
-    return d.actions_num > 4 * kQuadK ? static_cast<int>(hipErrorNotSupported) : static_cast<int>(hipErrorInvalidValue);
+  if (d.actions_num > 4 * kQuadK) return static_cast<int>(hipErrorNotSupported);
   LossArgs loss = {};
-  loss.mu = d.mu;
-  loss.logstd = d.logstd;
-  loss.values = d.values;
-  loss.actions = d.actions;
-  loss.old_neglogp = d.old_neglogp;
-  loss.advantages = d.advantages;
-  loss.old_values = d.old_values;
-  loss.returns = d.returns;
-  loss.old_mu = d.old_mu;
-  loss.old_sigma = d.old_sigma;
-  loss.mask = d.mask_or_null;
-  loss.mask_sum = d.mask_sum_or_null;
-  loss.d_mu = d.d_mu;
-  loss.d_values = d.d_values;
-  loss.partials = d.partials;
-  loss.mb = d.minibatch;
-  loss.A = d.actions_num;
-  loss.ld_mu = d.ld_mu;
-  loss.ld_val = d.ld_values;
-  loss.ld_dmu = d.ld_d_mu;
-  loss.ld_dval = d.ld_d_values;
-  loss.e_clip = d.e_clip;
-  loss.critic_coef = d.critic_coef;
-  loss.bounds_coef = d.bounds_coef;
-  loss.clip_value = d.clip_value;
-  loss.smooth = d.use_smooth_clamp;
-  loss.bound_kind = d.bound_kind;
-  loss.write_back = d.write_back;
+  if (const int e = chain_loss_args(loss, d, rows)) return e;
   int lds_bytes = chain_lean_tile_floats(fplan) * 4;
   if (chain_lean_tile_floats(bplan) * 4 > lds_bytes) lds_bytes = chain_lean_tile_floats(bplan) * 4;
   const int need = static_cast<int>(ppo_loss_lds_bytes(16, d.actions_num, 512));
@@ -1062,18 +903,9 @@ int rlg_mlp_chain_step_lean(int num_layers, const float* const* biases, const in
   LeanArgs fla = fpk.la, bla = bpk.la;
   fla.wf = static_cast<const float*>(frags_fwd);
   bla.wf = static_cast<const float*>(frags_bwd);
-  bool elu_only = true;
-  for (int L = 0; L < num_layers; ++L) elu_only = elu_only && (acts[L] == kChElu || acts[L] == kChIdentity);
-  const int grid = static_cast<int>((rows + 15) / 16);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  chain_take_events(&ev0, &ev1);
-  const auto kern = elu_only ? mlp_chain_step_lean_kernel<kChElu> : mlp_chain_step_lean_kernel<kChAny>;
-  if (ev0 != nullptr)
-    hipExtLaunchKernelGGL(kern, dim3(grid), dim3(64 * kLeanW), static_cast<size_t>(lds_bytes), st, ev0, ev1, 0, fa, fla, ba, bla, loss);
-  else
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * kLeanW), static_cast<size_t>(lds_bytes), st, fa, fla, ba, bla, loss);
-  RLG_RETURN_LAUNCH_STATUS();
+  const auto kern = chain_elu_only(fa) ? mlp_chain_step_lean_kernel<kChElu> : mlp_chain_step_lean_kernel<kChAny>;
+  return chain_launch_kernel(kern, static_cast<int>((rows + 15) / 16), 64 * kLeanW, lds_bytes, static_cast<hipStream_t>(stream), fa, fla,
+                             ba, bla, loss);
 }
 
 }  // extern "C"

@@ -813,6 +813,16 @@ def _untime_chain_launch(kind):
     _lib.load().rlg_mlp_chain_time_next(None, None)
 
 
+def _timed_chain_call(kind, entry, *args):
+    """Announces the timing of a launch of `kind` and calls the entry.  An entry that declines the shape
+    (hipErrorNotSupported, 801) has launched nothing: the announcement is withdrawn.  Returns the entry's code."""
+    _time_chain_launch(kind)
+    err = entry(*args)
+    if err == 801:
+        _untime_chain_launch(kind)
+    return err
+
+
 class MlpChain:
     """The whole MLP (hidden layers + the fused value|mu head as the last layer) as ONE forward and
     ONE backward launch (csrc/mlp_chain.hip).  `layers`: list of (weight [out, in], bias [out], act
@@ -1049,20 +1059,10 @@ class MlpChain:
     def num_blocks(self, rows, direction, requested=0):
         return _lib.load().rlg_mlp_chain_num_blocks(int(rows), self.groups(rows, direction, requested))
 
-    def forward(self, x, heads, act_out=None, rms=None, eps=1e-5, xn_out=None, groups=0, rms_fold=None,
-                split_products=None):
-        """x [rows, in0] (row stride free), heads [rows, out_last] out.  act_out: per hidden layer a
-        [rows, out_l] tensor or None.  rms = (running_mean, running_var) fp64 -> the observations are
-        normalised on the way in (xn_out [rows, in0] optionally receives them).  rms_fold =
-        (moments_row [2*in0+1] fp64, count int64, mean_out, var_out, count_out): training-mode
-        RunningMeanStd - the minibatch's moments are folded into the state first, the new state is
-        written to the *_out tensors (a second buffer set).
-        split_products: None = the library's choice (split-bf16 products on 64-row tiles for minibatches of
-        >= 16,384 rows, csrc/mlp_chain_bx_fwd.hip), False = exact f32 products."""
-        rows = x.shape[0]
-        n = self.n
-        outs = list(act_out) if act_out is not None else [None] * (n - 1)
-        outs = outs + [heads]
+    def _forward_args(self, x, outs, rms, eps, xn_out, rms_fold):
+        """What every forward entry takes from act_out to rms_count_out, in that order: pointers and row strides of
+        `outs` (per layer the activation output or None, the heads last), x and its row stride, the normaliser state,
+        eps, xn_out, the five rms_fold pointers."""
         ptrs = self._P(*[None if t is None else _need(t, F32, 'act_out', contiguous=False) for t in outs])
         lds = self._L(*[0 if t is None else t.stride(0) for t in outs])
         _lib.require_gpu(x, 'x')
@@ -1080,6 +1080,32 @@ class MlpChain:
                 raise ValueError('rms_fold: moments row of 2*in0+1 doubles expected')
             fold = [_need(row, F64, 'moments row'), _need(cnt, torch.int64, 'count'), _need(mean_o, F64, 'mean out'),
                     _need(var_o, F64, 'var out'), _need(cnt_o, torch.int64, 'count out')]
+        return (ptrs, lds, x.data_ptr(), x.stride(0), mean, var, float(np.float32(eps)), _opt(xn_out, F32, 'xn_out'), *fold)
+
+    def _backward_args(self, dz_out, bias_partials):
+        """What every backward entry takes from dz_out to bias_partials: per hidden layer the dZ output and its row
+        stride, the fp64 bias partials or None."""
+        dz = self._P(*([_need(t, F32, 'dz', contiguous=False) for t in dz_out] + [None]))
+        dl = self._L(*([t.stride(0) for t in dz_out] + [0]))
+        bp = None
+        if bias_partials is not None:
+            bp = self._P(*([_need(t, F64, 'bias partials') for t in bias_partials] + [None]))
+        return dz, dl, bp
+
+    def forward(self, x, heads, act_out=None, rms=None, eps=1e-5, xn_out=None, groups=0, rms_fold=None,
+                split_products=None):
+        """x [rows, in0] (row stride free), heads [rows, out_last] out.  act_out: per hidden layer a
+        [rows, out_l] tensor or None.  rms = (running_mean, running_var) fp64 -> the observations are
+        normalised on the way in (xn_out [rows, in0] optionally receives them).  rms_fold =
+        (moments_row [2*in0+1] fp64, count int64, mean_out, var_out, count_out): training-mode
+        RunningMeanStd - the minibatch's moments are folded into the state first, the new state is
+        written to the *_out tensors (a second buffer set).
+        split_products: None = the library's choice (split-bf16 products on 64-row tiles for minibatches of
+        >= 16,384 rows, csrc/mlp_chain_bx_fwd.hip), False = exact f32 products."""
+        rows = x.shape[0]
+        n = self.n
+        outs = list(act_out) if act_out is not None else [None] * (n - 1)
+        fwd = self._forward_args(x, outs + [heads], rms, eps, xn_out, rms_fold)
         # A training forward also has the weights split for the backward launch that follows it: by the forward's own
         # pack launch when the forward runs on planes as well (one launch, both directions), else in extra workgroups
         # of the exact-product forward launch.  backward() uses those planes once; any other caller packs for itself.
@@ -1087,14 +1113,11 @@ class MlpChain:
         if split_products is not False and groups in (0, 1) and self.lean_used(rows, kind):
             self._planes_fresh = None
             self.ensure_frags(x)
-            _time_chain_launch('fwd_train' if act_out is not None else 'fwd_infer')
-            err = _lib.load().rlg_mlp_chain_forward_lean(
-                n, self._b, self._in, self._out, self._act, ptrs, lds, x.data_ptr(), x.stride(0), mean, var,
-                float(np.float32(eps)), _opt(xn_out, F32, 'xn_out'), *fold, rows, self._frags_ptr(0), _stream(x))
+            err = _timed_chain_call('fwd_train' if act_out is not None else 'fwd_infer', _lib.load().rlg_mlp_chain_forward_lean,
+                                    n, self._b, self._in, self._out, self._act, *fwd, rows, self._frags_ptr(0), _stream(x))
             if err != 801:                              # (hipErrorNotSupported: the pipelined / unit-structured launch)
                 _lib.check(err, 'rlg_mlp_chain_forward_lean')
                 return
-            _untime_chain_launch('fwd_train' if act_out is not None else 'fwd_infer')
         train = act_out is not None and self.n > 1
         bwd_split = train and self.split_products(rows, 1)
         planes = fwd_planes = None
@@ -1109,8 +1132,7 @@ class MlpChain:
             planes = self._planes_ptr(1)
         _time_chain_launch('fwd_train' if act_out is not None else 'fwd_infer')
         _lib.check(_lib.load().rlg_mlp_chain_forward(
-            n, self._w, self._b, self._in, self._out, self._act, ptrs, lds, x.data_ptr(), x.stride(0),
-            mean, var, float(np.float32(eps)), _opt(xn_out, F32, 'xn_out'), *fold, rows,
+            n, self._w, self._b, self._in, self._out, self._act, *fwd, rows,
             self.groups(rows, kind, groups), planes, fwd_planes, _stream(x)), 'rlg_mlp_chain_forward')
         if bwd_split:
             # only behind a launch that succeeded, and only for the weights as they are now
@@ -1130,57 +1152,27 @@ class MlpChain:
         if self.split_products(rows, 2) or self.split_products(rows, 1) or self.groups(rows, 2) != 1 or self.groups(rows, 1) != 1:
             return False
         lean = self.lean_used(rows, 2) and self.lean_used(rows, 1)
-        outs = list(act_out) + [heads]
-        ptrs = self._P(*[_need(t, F32, 'act_out', contiguous=False) for t in outs])
-        lds = self._L(*[t.stride(0) for t in outs])
-        _lib.require_gpu(x, 'x')
-        if x.dtype != F32 or (x.dim() == 2 and x.shape[1] != 1 and x.stride(1) != 1):
-            raise ValueError('x: fp32 rows with unit inner stride expected')
-        mean = var = None
-        if rms is not None:
-            mean, var = _need(rms[0], F64, 'running_mean'), _need(rms[1], F64, 'running_var')
-        fold = [None] * 5
-        if rms_fold is not None:
-            if rms is None:
-                raise ValueError('rms_fold needs rms')
-            row, cnt, mean_o, var_o, cnt_o = rms_fold
-            if row.numel() != 2 * self.ins[0] + 1:
-                raise ValueError('rms_fold: moments row of 2*in0+1 doubles expected')
-            fold = [_need(row, F64, 'moments row'), _need(cnt, torch.int64, 'count'), _need(mean_o, F64, 'mean out'),
-                    _need(var_o, F64, 'var out'), _need(cnt_o, torch.int64, 'count out')]
-        dz = self._P(*([_need(t, F32, 'dz', contiguous=False) for t in dz_out] + [None]))
-        dl = self._L(*([t.stride(0) for t in dz_out] + [0]))
-        bp = None
-        if bias_partials is not None:
-            bp = self._P(*([_need(t, F64, 'bias partials') for t in bias_partials] + [None]))
+        fwd = self._forward_args(x, list(act_out) + [heads], rms, eps, xn_out, rms_fold)
+        bwd = (_need(d_heads, F32, 'd_heads', contiguous=False), d_heads.stride(0), *self._backward_args(dz_out, bias_partials),
+               ctypes.addressof(ppo_loss), rows)
         if lean:
             # the lean form of the same launch (fp32 weight fragments); outside its envelope: the lean forward and the lean
             # backward as two launches (the caller's fallback), which beat the pipelined one-launch step
             self.ensure_frags(x)
             self._maxima_bwd = None
             lean_maxima = self._request_lean_maxima(rows)
-            _time_chain_launch('step16')
-            err = _lib.load().rlg_mlp_chain_step_lean(
-                n, self._b, self._in, self._out, self._act, ptrs, lds, x.data_ptr(), x.stride(0),
-                mean, var, float(np.float32(eps)), _opt(xn_out, F32, 'xn_out'), *fold,
-                _need(d_heads, F32, 'd_heads', contiguous=False), d_heads.stride(0), dz, dl, bp,
-                ctypes.addressof(ppo_loss), rows, self._frags_ptr(0), self._frags_ptr(1), _stream(x))
+            err = _timed_chain_call('step16', _lib.load().rlg_mlp_chain_step_lean, n, self._b, self._in, self._out, self._act,
+                                    *fwd, *bwd, self._frags_ptr(0), self._frags_ptr(1), _stream(x))
             if err == 801:
-                _untime_chain_launch('step16')
                 return False
             _lib.check(err, 'rlg_mlp_chain_step_lean')
             self._planes_fresh = None
             if lean_maxima:
                 self._maxima_bwd, self.maxima_rows_per_entry = rows, 16
             return True
-        _time_chain_launch('step16')
-        err = _lib.load().rlg_mlp_chain_step(
-            n, self._w, self._b, self._in, self._out, self._act, ptrs, lds, x.data_ptr(), x.stride(0),
-            mean, var, float(np.float32(eps)), _opt(xn_out, F32, 'xn_out'), *fold,
-            _need(d_heads, F32, 'd_heads', contiguous=False), d_heads.stride(0), dz, dl, bp,
-            ctypes.addressof(ppo_loss), rows, _stream(x))
+        err = _timed_chain_call('step16', _lib.load().rlg_mlp_chain_step, n, self._w, self._b, self._in, self._out, self._act,
+                                *fwd, *bwd, _stream(x))
         if err == 801:                                  # hipErrorNotSupported: outside the fused kernel's envelope
-            _untime_chain_launch('step16')
             return False
         _lib.check(err, 'rlg_mlp_chain_step')
         self._planes_fresh = None
@@ -1197,19 +1189,15 @@ class MlpChain:
         n = self.n
         h = self._P(*([_need(t, F32, 'H', contiguous=False) for t in acts] + [None]))
         hl = self._L(*([t.stride(0) for t in acts] + [0]))
-        dz = self._P(*([_need(t, F32, 'dz', contiguous=False) for t in dz_out] + [None]))
-        dl = self._L(*([t.stride(0) for t in dz_out] + [0]))
-        bp = None
-        if bias_partials is not None:
-            bp = self._P(*([_need(t, F64, 'bias partials') for t in bias_partials] + [None]))
+        dz, dl, bp = self._backward_args(dz_out, bias_partials)
         _lib.require_gpu(d_heads, 'd_heads')
         if split_products is not False and groups in (0, 1) and self.lean_used(rows, 1):
             self._planes_fresh = None
             self._maxima_bwd = None
             self.ensure_frags(d_heads)
             lean_maxima = self._request_lean_maxima(rows)
-            _time_chain_launch('bwd_loss' if ppo_loss is not None else 'bwd')
-            err = _lib.load().rlg_mlp_chain_backward_lean(
+            err = _timed_chain_call(
+                'bwd_loss' if ppo_loss is not None else 'bwd', _lib.load().rlg_mlp_chain_backward_lean,
                 n, self._in, self._out, self._act, h, hl, d_heads.data_ptr(), d_heads.stride(0), dz, dl, bp,
                 None if ppo_loss is None else ctypes.addressof(ppo_loss), rows, self._frags_ptr(1), _stream(d_heads))
             if err != 801:
@@ -1217,7 +1205,6 @@ class MlpChain:
                 if lean_maxima:
                     self._maxima_bwd, self.maxima_rows_per_entry = rows, 16
                 return
-            _untime_chain_launch('bwd_loss' if ppo_loss is not None else 'bwd')
         planes = None
         if split_products is not False and self.split_products(rows, 1, groups):
             if not self.planes_current() and (self._planes_fresh is None or self._planes_fresh != (rows, self._version())):
