@@ -709,7 +709,12 @@ int rlg_mlp_chain_bx_supported(int num_layers, const int* in_features, const int
  * (rl_games/algos_torch/network_builder.py:447-512, rnn after the MLP) and autograd's BPTT.
  * gates [S*T, 4H] (row = seq*T + t) holds x_t W_ih^T + b_ih + b_hh on entry and the activated
  * gates (i, f, g, o) on exit; the state entering step t is zeroed where dones[seq*T+t] != 0.
- * hidden must satisfy rlg_lstm_supported (W_hh stays in LDS for the whole sequence). */
+ * rlg_lstm_supported(hidden): 1 for 16, 32, 64 and 128, else 0.  The recurrent weights are fetched once per launch and
+ * stay on the CU for all T steps: W_hh [4H, H] in LDS as fp32 up to 64 units (64 KB; csrc/lstm.hip), at 128 units
+ * (256 KB, more than a CU's 160 KB of LDS) in the registers of a 1,024-thread workgroup as operand fragments of
+ * v_mfma_f32_16x16x4_f32 (csrc/lstm_wide.hip; w_hh must then be 16-byte aligned).  256 units and more (>= 1 MB) fit
+ * neither a CU's 512 KB register file nor registers + LDS together, and other widths have no instantiation: the entry
+ * points return hipErrorInvalidValue for them. */
 int rlg_lstm_supported(int hidden);
 int rlg_lstm_seq_forward(float* gates, const float* w_hh, const float* h0, const float* c0,
                          const unsigned char* dones_or_null, float* out, float* c_all_or_null,

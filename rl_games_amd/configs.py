@@ -54,10 +54,11 @@ def ant_4096(num_actors=4096, **over):
                               {'obs_dim': 60, 'act_dim': 8}, **over)}
 
 
-def pendulum_lstm_4096(num_actors=4096, **over):
-    """BASELINE.json config #5: LSTM policy, Pendulum-shaped obs 3 / act 1, 4,096 x seq_len 16."""
+def pendulum_lstm_4096(num_actors=4096, units=64, **over):
+    """BASELINE.json config #5: LSTM policy, Pendulum-shaped obs 3 / act 1, 4,096 x seq_len 16.
+    units: width of the LSTM (config #5 itself: 64; 128 is the width of the reference's ppo_continuous_lstm.yaml)."""
     return {'algo': {'name': 'a2c_continuous'}, 'model': {'name': 'continuous_a2c_logstd'},
-            'network': _network([64, 64], rnn={'name': 'lstm', 'units': 64, 'layers': 1}),
+            'network': _network([64, 64], rnn={'name': 'lstm', 'units': units, 'layers': 1}),
             'config': _config('pendulum_lstm', num_actors, 16, min(16384, num_actors * 16), 4,
                               {'obs_dim': 3, 'act_dim': 1}, seq_length=16, **over)}
 

@@ -286,11 +286,19 @@ static int launch_lstm_bwd(const float* gates, const float* c_all, const float* 
   }
 }
 
+// 128 units: W_hh (256 KB) does not fit LDS; csrc/lstm_wide.hip keeps it in registers as MFMA fragments.
+int launch_lstm_fwd_wide(float* gates, const float* w_hh, const float* h0, const float* c0, const uint8_t* dones,
+                         float* out, float* c_all, float* hprev, float* hT, float* cT, int S, int T, hipStream_t st);
+int launch_lstm_bwd_wide(const float* gates, const float* c_all, const float* c0, const uint8_t* dones,
+                         const float* w_hh, const float* d_out, float* d_gates, int S, int T, hipStream_t st);
+
 }  // namespace rlg
 
 extern "C" {
 
-int rlg_lstm_supported(int hidden) { return (hidden == 16 || hidden == 32 || hidden == 64) ? 1 : 0; }
+int rlg_lstm_supported(int hidden) {
+  return (hidden == 16 || hidden == 32 || hidden == 64 || hidden == 128) ? 1 : 0;
+}
 
 int rlg_lstm_seq_forward(float* gates, const float* w_hh, const float* h0, const float* c0,
                          const unsigned char* dones_or_null, float* out, float* c_all_or_null,
@@ -306,6 +314,8 @@ int rlg_lstm_seq_forward(float* gates, const float* w_hh, const float* h0, const
                                         h_final_or_null, c_final_or_null, num_seqs, seq_len, st);
     case 64: return launch_lstm_fwd<64>(gates, w_hh, h0, c0, dones_or_null, out, c_all_or_null, hprev_or_null,
                                         h_final_or_null, c_final_or_null, num_seqs, seq_len, st);
+    case 128: return launch_lstm_fwd_wide(gates, w_hh, h0, c0, dones_or_null, out, c_all_or_null, hprev_or_null,
+                                          h_final_or_null, c_final_or_null, num_seqs, seq_len, st);
     default: return static_cast<int>(hipErrorInvalidValue);
   }
 }
@@ -320,6 +330,7 @@ int rlg_lstm_seq_backward(const float* gates, const float* c_all, const float* c
     case 16: return launch_lstm_bwd<16>(gates, c_all, c0, dones_or_null, w_hh, d_out, d_gates, num_seqs, seq_len, st);
     case 32: return launch_lstm_bwd<32>(gates, c_all, c0, dones_or_null, w_hh, d_out, d_gates, num_seqs, seq_len, st);
     case 64: return launch_lstm_bwd<64>(gates, c_all, c0, dones_or_null, w_hh, d_out, d_gates, num_seqs, seq_len, st);
+    case 128: return launch_lstm_bwd_wide(gates, c_all, c0, dones_or_null, w_hh, d_out, d_gates, num_seqs, seq_len, st);
     default: return static_cast<int>(hipErrorInvalidValue);
   }
 }

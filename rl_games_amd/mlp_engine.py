@@ -13,7 +13,7 @@ so the backward pass is written out explicitly instead of being recorded by auto
     run as one [1+A, K] GEMM operand; their bias gradients come out of the loss kernel.
   * an optional single-layer LSTM between the trunk and the heads (BASELINE config #5,
     `rnn: {name: lstm, layers: 1}`, network_builder.py:447-512) runs as ONE sequence-persistent
-    kernel per direction (csrc/lstm.hip) instead of a Python loop of per-timestep MIOpen calls
+    kernel per direction (csrc/lstm.hip; 128 units: csrc/lstm_wide.hip) instead of a Python loop of per-timestep MIOpen calls
     with done resets (rl_games/common/layers/recurrent.py:26-58) and autograd BPTT through it;
     its input projection and all four weight/bias gradients are whole-sequence GEMMs.
 Numerics: aten's formulas - by default (in-place activations) act' from the layer output like
@@ -65,7 +65,7 @@ class ManualMLP:
         self.lstm = None
         if getattr(net, 'has_rnn', False):
             if net.rnn_name != 'lstm' or net.rnn_layers != 1 or not ops.lstm_supported(net.rnn_units):
-                raise NotImplementedError('manual engine: only a single-layer LSTM with 16/32/64 units')
+                raise NotImplementedError('manual engine: only a single-layer LSTM with 16/32/64/128 units')
             self.lstm = net.rnn.rnn
             self.Hr = net.rnn_units
         wp, wg = arena.span(net.value.weight, net.mu.weight)

@@ -1334,12 +1334,16 @@ class MlpDwPlan:
 # ------------------------------------------------------------------ recurrent policy (LSTM)
 
 def lstm_supported(hidden):
+    """16, 32, 64 (W_hh in LDS, csrc/lstm.hip) and 128 (W_hh in registers as MFMA fragments, csrc/lstm_wide.hip)."""
     return bool(_lib.load().rlg_lstm_supported(int(hidden)))
 
 
 def lstm_seq_forward(gates, w_hh, h0, c0, dones, out, c_all=None, hprev=None, h_final=None, c_final=None,
                      seq_len=1):
-    """gates [S*T, 4H]: input projection (+ both biases) in, activated gates out.  See csrc/lstm.hip."""
+    """gates [S*T, 4H] (row = seq*seq_len + t): input projection (+ both biases) in, activated gates out; out [S*T, H].
+    c_all / hprev [S*T, H] (cell states, state entering each step after the reset) are kept for backward when given,
+    h_final / c_final [S, H] likewise.  H must satisfy lstm_supported: csrc/lstm.hip (16/32/64) or
+    csrc/lstm_wide.hip (128, w_hh 16-byte aligned)."""
     lib = _lib.load()
     B, G = gates.shape
     H = G // 4
@@ -1354,6 +1358,8 @@ def lstm_seq_forward(gates, w_hh, h0, c0, dones, out, c_all=None, hprev=None, h_
 
 
 def lstm_seq_backward(gates, c_all, c0, dones, w_hh, d_out, d_gates, seq_len):
+    """d_gates [S*T, 4H] = d loss / d gate pre-activations from d_out [S*T, H] and what lstm_seq_forward kept.
+    Same widths as lstm_seq_forward; the weight gradients are whole-sequence products of d_gates outside."""
     lib = _lib.load()
     B, G = gates.shape
     _lib.check(lib.rlg_lstm_seq_backward(

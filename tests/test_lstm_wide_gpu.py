@@ -1,0 +1,312 @@
+"""GPU: 128-unit LSTM policies on the register-resident MFMA kernels (csrc/lstm_wide.hip).
+
+Kernel level: against a CPU evaluation in fp64 of torch.nn.LSTM stepped with the reference's done resets
+(rl_games/common/layers/recurrent.py:26-58), backward through autograd on the CPU side - the procedure and the
+tolerances of tests/test_lstm_gpu.py, restated here.  Agent level: the engine against torch autograd, one epoch of
+the real reference agent (tests/golden/lstm_wide.pt.gz, written by tests/golden/make_lstm_wide_golden.py), and three
+training epochs including the HIP-graph replays."""
+import copy
+import gzip
+import io
+import os
+
+import pytest
+import torch
+
+from rl_games_amd.synthetic_env import SyntheticTensorEnv
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda:0'
+H = 128
+
+
+def _reference(x, lstm, h0, c0, dones, T):
+    """x [S*T, I] rows (seq, t).  Returns out [S*T, H], (hT, cT), the cell states [S*T, H] and the states entering
+    each step after the reset [S*T, H]."""
+    S = x.shape[0] // T
+    xs = x.reshape(S, T, -1).transpose(0, 1)
+    d = dones.reshape(S, T).t() if dones is not None else None
+    st = (h0.unsqueeze(0), c0.unsqueeze(0))
+    outs, cells, entering = [], [], []
+    for t in range(T):
+        if d is not None:
+            keep = (1.0 - d[t].float()).reshape(1, -1, 1).to(st[0].dtype)
+            st = (st[0] * keep, st[1] * keep)
+        entering.append(st[0])
+        o, st = lstm(xs[t:t + 1], st)
+        outs.append(o)
+        cells.append(st[1])
+
+    def rows(parts):
+        return torch.cat(parts, 0).transpose(0, 1).reshape(S * T, -1)
+    return rows(outs), st, rows(cells), rows(entering)
+
+
+def _inputs(S, T, I, with_dones):
+    g = torch.Generator().manual_seed(S * 7 + T)
+    lstm32 = torch.nn.LSTM(I, H, 1)
+    x32 = torch.randn(S * T, I, generator=g)
+    h0 = (0.5 * torch.randn(S, H, generator=g)).to(DEV)
+    c0 = (0.5 * torch.randn(S, H, generator=g)).to(DEV)
+    dones = (torch.rand(S * T, generator=g) < 0.2).to(torch.uint8).to(DEV) if with_dones else None
+    d_out = torch.randn(S * T, H, generator=g).to(DEV)
+    return lstm32, x32, h0, c0, dones, d_out
+
+
+def _forward(ops, lstm32, x, h0, c0, dones, T, train=True):
+    S = h0.shape[0]
+    w_ih, w_hh = lstm32.weight_ih_l0.detach().to(DEV), lstm32.weight_hh_l0.detach().to(DEV).contiguous()
+    bias = (lstm32.bias_ih_l0 + lstm32.bias_hh_l0).detach().to(DEV)
+    gates = torch.addmm(bias, x, w_ih.t())
+    out = torch.empty(S * T, H, device=DEV)
+    c_all = torch.empty(S * T, H, device=DEV) if train else None
+    hprev = torch.empty(S * T, H, device=DEV) if train else None
+    hT, cT = torch.empty(S, H, device=DEV), torch.empty(S, H, device=DEV)
+    ops.lstm_seq_forward(gates, w_hh, h0, c0, dones, out, c_all, hprev, hT, cT, seq_len=T)
+    return dict(gates=gates, out=out, c_all=c_all, hprev=hprev, hT=hT, cT=cT, w_ih=w_ih, w_hh=w_hh)
+
+
+@pytest.mark.parametrize('S,T,I,with_dones', [(64, 16, 64, True), (37, 4, 12, True), (1024, 16, 64, True),
+                                            (5, 1, 7, False), (130, 8, 20, False), (256, 32, 100, True)])
+def test_wide_lstm_forward_backward_match_fp64(S, T, I, with_dones):
+    from rl_games_amd import ops
+    lstm32, x32, h0, c0, dones, d_out = _inputs(S, T, I, with_dones)
+
+    # the reference: CPU, fp64, the fp32 parameters and inputs upcast exactly
+    lstm = torch.nn.LSTM(I, H, 1).double()
+    lstm.load_state_dict({k: v.double() for k, v in lstm32.state_dict().items()})
+    x = x32.double().requires_grad_(True)
+    ref_out, (ref_h, ref_c), ref_cells, ref_enter = _reference(x, lstm, h0.cpu().double(), c0.cpu().double(),
+                                                               None if dones is None else dones.cpu(), T)
+    ref_out.backward(d_out.cpu().double())
+    ref_out, ref_h, ref_c = ref_out.detach().float().to(DEV), ref_h.detach().float().to(DEV), ref_c.detach().float().to(DEV)
+    ref_cells, ref_enter = ref_cells.detach().float().to(DEV), ref_enter.detach().float().to(DEV)
+    ref_grads = {n: getattr(lstm, n).grad.float().to(DEV)
+                 for n in ('weight_ih_l0', 'weight_hh_l0', 'bias_ih_l0', 'bias_hh_l0')}
+    x_grad = x.grad.float().to(DEV)
+    x = x32.to(DEV)
+
+    r = _forward(ops, lstm32, x, h0, c0, dones, T)
+    tol = dict(rtol=1e-5, atol=2e-6)
+    for name, got, want in (('out', r['out'], ref_out), ('hT', r['hT'], ref_h[0]), ('cT', r['cT'], ref_c[0]),
+                            ('c_all', r['c_all'], ref_cells), ('hprev', r['hprev'], ref_enter)):
+        print(name, 'max |diff|', (got - want).abs().max().item())
+        assert torch.allclose(got, want, **tol), (name, (got - want).abs().max().item())
+    # hprev IS the state entering each step: the previous row of out (h0 at t = 0), zeroed where done - bit for bit
+    enter = torch.cat([h0.unsqueeze(1), r['out'].reshape(S, T, H)[:, :-1]], 1).reshape(S * T, H)
+    if dones is not None:
+        enter = enter * (1.0 - dones.float()).unsqueeze(1)
+    assert torch.equal(r['hprev'], enter)
+
+    # an inference call (nothing kept for backward) and a second training call: bit-identical
+    inf = _forward(ops, lstm32, x, h0, c0, dones, T, train=False)
+    again = _forward(ops, lstm32, x, h0, c0, dones, T)
+    for k in ('out', 'hT', 'cT', 'gates'):
+        assert torch.equal(inf[k], r[k]), k
+    for k in ('out', 'hT', 'cT', 'gates', 'c_all', 'hprev'):
+        assert torch.equal(again[k], r[k]), k
+
+    d_gates = torch.empty(S * T, 4 * H, device=DEV)
+    ops.lstm_seq_backward(r['gates'], r['c_all'], c0, dones, r['w_hh'], d_out, d_gates, T)
+    d_gates2 = torch.empty(S * T, 4 * H, device=DEV)
+    ops.lstm_seq_backward(r['gates'], r['c_all'], c0, dones, r['w_hh'], d_out, d_gates2, T)
+    assert torch.equal(d_gates, d_gates2)
+    dx = d_gates @ r['w_ih']
+    dw_ih = d_gates.t() @ x
+    dw_hh = d_gates.t() @ r['hprev']
+    db = d_gates.sum(0)
+
+    def close(a, b, name):
+        scale = b.abs().max().item()
+        err = (a - b).abs().max().item()
+        print(name, 'max |diff|', err, 'bound', 2e-5 * scale + 1e-7)
+        assert err <= 2e-5 * scale + 1e-7, (name, err, scale)
+    close(dx, x_grad, 'dx')
+    close(dw_ih, ref_grads['weight_ih_l0'], 'dw_ih')
+    close(dw_hh, ref_grads['weight_hh_l0'], 'dw_hh')
+    close(db, ref_grads['bias_ih_l0'], 'db_ih')
+    close(db, ref_grads['bias_hh_l0'], 'db_hh')
+
+
+def test_wide_lstm_rows_do_not_depend_on_tile_neighbours():
+    """Sequences 0 - 4 of a 130-sequence launch (a full 16-sequence tile) and the same five alone (a ragged tile):
+    bit-identical rows, forward and backward."""
+    from rl_games_amd import ops
+    S, T, I, n = 130, 8, 20, 5
+    lstm32, x32, h0, c0, dones, d_out = _inputs(S, T, I, True)
+    x = x32.to(DEV)
+    full = _forward(ops, lstm32, x, h0, c0, dones, T)
+    part = _forward(ops, lstm32, x[:n * T].contiguous(), h0[:n].contiguous(), c0[:n].contiguous(),
+                    dones[:n * T].contiguous(), T)
+    for k in ('out', 'gates', 'c_all', 'hprev'):
+        assert torch.equal(full[k][:n * T], part[k]), k
+    for k in ('hT', 'cT'):
+        assert torch.equal(full[k][:n], part[k]), k
+    dg_full = torch.empty(S * T, 4 * H, device=DEV)
+    ops.lstm_seq_backward(full['gates'], full['c_all'], c0, dones, full['w_hh'], d_out, dg_full, T)
+    dg_part = torch.empty(n * T, 4 * H, device=DEV)
+    ops.lstm_seq_backward(part['gates'], part['c_all'], c0[:n].contiguous(), dones[:n * T].contiguous(), part['w_hh'],
+                          d_out[:n * T].contiguous(), dg_part, T)
+    assert torch.equal(dg_full[:n * T], dg_part)
+
+
+def test_wide_lstm_supported_widths():
+    from rl_games_amd import ops
+    assert all(ops.lstm_supported(h) for h in (16, 32, 64, 128))
+    assert not ops.lstm_supported(100) and not ops.lstm_supported(256)
+    with pytest.raises(RuntimeError):
+        ops.lstm_seq_forward(torch.zeros(4, 1024, device=DEV), torch.zeros(1024, 256, device=DEV),
+                             torch.zeros(4, 256, device=DEV), torch.zeros(4, 256, device=DEV), None,
+                             torch.zeros(4, 256, device=DEV))
+
+
+def test_wide_lstm_engine_matches_autograd_gradients_and_rollout():
+    """tests/test_agent_gpu.py::test_lstm_engine_matches_autograd_gradients_and_rollout at 128 units: (i) the engine's
+    rollout step (T = 1 launches of the wide kernel) leaves the values / mus the torch model gives step by step, and
+    (ii) for one minibatch the hand-written BPTT produces autograd's scalars and gradients."""
+    from rl_games_amd import configs
+    from rl_games_amd.agent import A2CAgent
+    base = configs.pendulum_lstm_4096(num_actors=128, units=128, minibatch_size=1024, grad_norm=1e9,
+                                      lr_schedule=None, learning_rate=0.0)
+    base['config']['env_config']['p_done'] = 0.2          # plenty of mid-sequence resets
+    torch.manual_seed(0)
+    a1 = A2CAgent('eng', copy.deepcopy(base))
+    p2 = copy.deepcopy(base)
+    p2['config']['manual_lstm'] = False
+    a2 = A2CAgent('auto', p2)
+    assert a1._engine is not None and a1._engine.lstm is not None and a2._engine is None
+    assert a1.model.a2c_network.rnn_units == 128
+    a2.model.load_state_dict(a1.model.state_dict())
+    a1.init_tensors()
+    a1.obs = a1.env_reset()
+    a1.set_eval()
+    with torch.no_grad():
+        batch = a1.play_steps_rnn()
+    a2.init_tensors()
+    a2.set_eval()
+    Hz, N = a1.horizon_length, a1.num_actors
+    obs = batch['obses'].reshape(N, Hz, -1)
+    with torch.no_grad():
+        st = [s[:, :N].contiguous() for s in batch['rnn_states']]     # states at t = 0 (one seq per env)
+        assert st[0].shape == (1, N, 128)
+        for t in range(Hz):
+            keep = (1.0 - a1.experience_buffer.tensor_dict['dones'][t].float()).reshape(1, -1, 1)
+            st = [s * keep for s in st] if t > 0 else st
+            res = a2.model({'is_train': False, 'obs': obs[:, t], 'rnn_states': st})
+            st = res['rnn_states']
+            assert torch.allclose(res['mus'], batch['mus'].reshape(N, Hz, -1)[:, t], rtol=1e-4, atol=2e-6), t
+            assert torch.allclose(res['values'], batch['values'].reshape(N, Hz, 1)[:, t], rtol=1e-4, atol=2e-5), t
+    snapshot = {k: v.detach().clone() for k, v in a1.model.state_dict().items()}
+    grads = []
+    for ag in (a1, a2):
+        b = {k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in batch.items() if k != '_fused'}
+        ag.model.load_state_dict(snapshot)
+        ag.set_train()
+        ag.prepare_dataset(b)
+        ag.train_actor_critic(ag.dataset[1])
+        grads.append({n: p.grad.detach().clone() for n, p in ag.model.named_parameters()})
+        res = ag.train_result
+        grads[-1]['_scalars'] = torch.stack([res[0], res[1], res[2], res[3], res[8]])
+    g1, g2 = grads
+    assert a1._engine.last_dw_path == 'mfma'
+    print('scalars', g1['_scalars'].tolist(), g2['_scalars'].tolist())
+    assert torch.allclose(g1.pop('_scalars'), g2.pop('_scalars'), rtol=1e-5, atol=1e-7)
+    for n in g2:
+        scale = g2[n].abs().max().item() + 1e-12
+        print(n, 'max |diff|', (g1[n] - g2[n]).abs().max().item(), 'scale', scale)
+        assert torch.allclose(g1[n], g2[n], rtol=1e-4, atol=5e-6 * scale), (n, (g1[n] - g2[n]).abs().max().item(), scale)
+
+
+# ---- one epoch of the real reference agent ------------------------------------------------------------------------
+
+COLS = {'a_loss': 0, 'c_loss': 1, 'entropy': 2, 'kl': 3, 'b_loss': 4}
+RTOL = {'a_loss': 1e-5, 'c_loss': 1e-5, 'entropy': 1e-5, 'kl': 1e-4, 'b_loss': 1e-5}
+ATOL = {'a_loss': 2e-6, 'c_loss': 2e-6, 'entropy': 2e-6, 'kl': 2e-7, 'b_loss': 1e-7}
+TRUTH_FACTOR = 1.5      # the agent may be this much farther from the fp64 trajectory than the reference's own fp32 arithmetic
+CEILING = 1e-3          # ... and never farther than this fraction of a scalar's scale
+
+
+def _check_against_truth(got, ref, tru, key):
+    """The criterion of tests/test_headline_gpu.py::_check_against_truth for one scalar's series (steps, or mini-epochs
+    for the KL): every entry EITHER agrees with the recorded fp32 value at the plain bound OR the agent is, up to
+    there, at most TRUTH_FACTOR x as far from the fp64 trajectory as the recorded fp32 values are (running maxima) -
+    and in no case farther than CEILING of the scalar's scale.  Returns the entries that needed the fp64 yardstick."""
+    got, ref, tru = got.double(), ref.double(), tru.double()
+    scale = float(ref.abs().max())
+    env_a = env_o = 0.0
+    needed = []
+    for i in range(got.shape[0]):
+        strict = bool((got[i] - ref[i]).abs() <= RTOL[key] * ref[i].abs() + ATOL[key])
+        env_a = max(env_a, float((got[i] - tru[i]).abs()))
+        env_o = max(env_o, float((ref[i] - tru[i]).abs()))
+        print(f'{key}[{i}] |agent - ref| {float((got[i] - ref[i]).abs()):.3e} |agent - fp64| {env_a:.3e} '
+              f'|ref - fp64| {env_o:.3e} strict {strict}')
+        if not strict:
+            needed.append(i)
+            assert env_a <= TRUTH_FACTOR * env_o + ATOL[key], (key, i, env_a, env_o)
+        assert env_a <= CEILING * scale + ATOL[key], (key, i, 'ceiling', env_a, scale)
+    return needed
+
+
+def test_wide_lstm_matches_reference_epoch():
+    """MLP [64, 64] + LSTM 128, obs 3, act 1, 512 envs x seq_len 16, minibatch 2,048 x 4 mini-epochs = 16 optimiser
+    steps against one train_epoch of the REAL reference agent on the recorded rollout and rnn states, through the
+    register-resident LSTM kernels of the manual engine.  Bounds of
+    tests/test_agent_gpu.py::test_lstm_config5_at_its_own_size_matches_reference_epoch: a / c / entropy losses
+    rtol 1e-5 + 2e-6, b_loss + 1e-7, mini-epoch KL rtol 1e-4 + 2e-7, final learning rate bit for bit.  An entry
+    outside its plain bound is held to the fp64 trajectory recorded next to it (truth_*; _check_against_truth).
+    As measured on an MI355X: all 16 steps and all 4 mini-epoch KLs meet the plain bounds (largest |agent - reference|:
+    a_loss 3.7e-9, c_loss 2.4e-7, entropy 3.6e-7, b_loss 0, KL 2.8e-9) - no entry needed the fp64 yardstick; the agent
+    ends 1.0e-7 from the fp64 c_loss where the recorded fp32 reference ends 2.9e-7 from it."""
+    from conftest import GOLDEN_DIR
+    from rl_games_amd.agent import A2CAgent
+    with gzip.open(os.path.join(GOLDEN_DIR, 'lstm_wide.pt.gz'), 'rb') as f:
+        cap = torch.load(io.BytesIO(f.read()), map_location='cpu', weights_only=False)
+    params = copy.deepcopy(cap['params'])
+    params['config'].update(device=DEV, manual_lstm=True)
+    env = SyntheticTensorEnv(cap['env']['num_envs'], cap['env']['obs_dim'], cap['env']['act_dim'], device=DEV,
+                             seed=cap['env']['seed'])
+    params['config']['vec_env'] = env
+    params['config']['env_info'] = env.get_env_info()
+    agent = A2CAgent('test', params)
+    agent.init_tensors()
+    assert agent.is_rnn and agent._engine is not None and agent._engine.lstm is not None
+    assert agent.model.a2c_network.rnn_units == 128
+    assert (agent.num_actors, agent.horizon_length, agent.seq_length, agent.minibatch_size) == (512, 16, 16, 2048)
+    agent.model.load_state_dict(cap['state_after_rollout'])
+    batch = {k: (v.to(DEV) if isinstance(v, torch.Tensor) else [s.to(DEV) for s in v])
+             for k, v in cap['batch'].items()}
+    agent.set_train()
+    agent.prepare_dataset(batch)
+    rows = []
+    for mini_ep in range(agent.mini_epochs_num):
+        for i in range(len(agent.dataset)):
+            a, c, e, kl, lr, lr_mul, mu, sigma, b = agent.train_actor_critic(agent.dataset[i])
+            rows.append(torch.stack([a, c, e, kl, b]).clone())
+    rows = torch.stack(rows).cpu()
+    assert rows.shape[0] == 16
+    kls = rows[:, 3].reshape(agent.mini_epochs_num, len(agent.dataset)).mean(1)
+    needed = {}
+    for key, name in (('a_loss', 'a_losses'), ('c_loss', 'c_losses'), ('entropy', 'entropies'), ('b_loss', 'b_losses')):
+        needed[key] = _check_against_truth(rows[:, COLS[key]], cap[name].reshape(-1), cap['truth_' + name].reshape(-1), key)
+    needed['kl'] = _check_against_truth(kls, cap['mini_epoch_kls'].reshape(-1), cap['truth_mini_epoch_kls'].reshape(-1), 'kl')
+    print('entries that needed the fp64 yardstick:', needed)
+    # the learning-rate trajectory of the 16 steps (update_lr calls of the reference), bit for bit
+    assert agent.optimizer.last_and_next_lr()[1] == cap['lrs'][-1]
+
+
+def test_wide_lstm_config_train_epoch_runs():
+    from rl_games_amd import configs
+    from rl_games_amd.agent import A2CAgent
+    params = configs.pendulum_lstm_4096(num_actors=256, units=128)
+    agent = A2CAgent('lstm', params)
+    assert agent._engine is not None and agent._engine.lstm is not None
+    agent.init_tensors()
+    agent.obs = agent.env_reset()
+    for _ in range(3):                      # 1 eager epoch, then HIP-graph replays on the engine path
+        agent.update_epoch()
+        out = agent.train_epoch()
+    assert len(out[4]) == agent.mini_epochs_num * agent.num_minibatches
+    assert all(torch.isfinite(x).item() for x in out[4])
+    st = agent.dataset.values_dict
+    assert st is not None and st['rnn_states'][0].shape == (1, 256 * (16 // 16), 128)
