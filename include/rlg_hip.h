@@ -725,6 +725,32 @@ int rlg_lstm_seq_backward(const float* gates, const float* c_all, const float* c
                           const unsigned char* dones_or_null, const float* w_hh, const float* d_out,
                           float* d_gates, int num_seqs, int seq_len, int hidden, void* stream);
 
+/* Sequence-persistent GRU layer: the same position in the network and the same contract (rows seq*T + t, done rule,
+ * one launch for all T steps, weights fetched once per launch) for `rnn: {name: gru, layers: 1}`
+ * (rl_games/common/layers/recurrent.py GRUWithDones, network_builder.py:250-276).  The cell is torch.nn.GRU's, gate
+ * order (r, z, n):
+ *   r = sigmoid(gx_r + W_hr h + b_hr)   z = sigmoid(gx_z + W_hz h + b_hz)
+ *   hn = W_hn h + b_hn                  n = tanh(gx_n + r * hn)              h' = (1 - z) * n + z * h
+ * gates [S*T, 3H] holds gx = x_t W_ih^T + b_ih on entry and the activated (r, z, n) on exit.  b_hn sits inside the
+ * product with r and cannot be folded into the input side, so b_hh [3H] is an argument of its own.
+ * For training the forward keeps hn_all [S*T, H] (hn, before the gating by r) and hprev [S*T, H] (the state entering
+ * each step after the reset); for inference h_final [S, H].
+ * rlg_gru_supported(hidden): 1 for 16, 32, 64 and 128, else 0.  W_hh [3H, H] in LDS as fp32 up to 64 units (48 KB;
+ * csrc/gru.hip); at 128 units (192 KB, more than a CU's 160 KB of LDS) in the registers of a 1,024-thread workgroup as
+ * operand fragments of v_mfma_f32_16x16x4_f32 (csrc/gru_wide.hip; w_hh must then be 16-byte aligned).  Other widths:
+ * hipErrorInvalidValue. */
+int rlg_gru_supported(int hidden);
+int rlg_gru_seq_forward(float* gates, const float* w_hh, const float* b_hh, const float* h0,
+                        const unsigned char* dones_or_null, float* out, float* hn_all_or_null,
+                        float* hprev_or_null, float* h_final_or_null,
+                        int num_seqs, int seq_len, int hidden, void* stream);
+/* Given d_out = d loss / d h_t:  d_gx [S*T, 3H] = (dr_pre, dz_pre, dn_pre), the gradient of the input side (dW_ih,
+ * db_ih, the trunk's dX), and d_gh [S*T, 3H] = (dr_pre, dz_pre, dn_pre * r), the gradient of the hidden side
+ * (dW_hh = d_gh^T hprev, db_hh). */
+int rlg_gru_seq_backward(const float* gates, const float* hn_all, const float* hprev,
+                         const unsigned char* dones_or_null, const float* w_hh, const float* d_out,
+                         float* d_gx, float* d_gh, int num_seqs, int seq_len, int hidden, void* stream);
+
 /* ---- products too narrow for the MFMA kernels (csrc/mlp_narrow.hip; BASELINE config #5: obs 3, act 1) ----------
  * rlg_narrow_dx: dX [rows, in] = dZ [rows, out] W [out, in] for out <= 8 - autograd's grad_output.mm(weight) of the fused
  *   (value | mu) head (rl_games/algos_torch/network_builder.py:295-311, :506-512).

@@ -115,6 +115,9 @@ _PROTOTYPES = {
     'rlg_lstm_supported': [_c_int],
     'rlg_lstm_seq_forward': [_P] * 10 + [_c_int, _c_int, _c_int, _P],
     'rlg_lstm_seq_backward': [_P] * 7 + [_c_int, _c_int, _c_int, _P],
+    'rlg_gru_supported': [_c_int],
+    'rlg_gru_seq_forward': [_P] * 9 + [_c_int, _c_int, _c_int, _P],
+    'rlg_gru_seq_backward': [_P] * 8 + [_c_int, _c_int, _c_int, _P],
     'rlg_value_loss': [_P, _P, _P, _P, _P, _P, _P, _c_int, _c_float, _c_int, _P],
     'rlg_ppo_loss_discrete_num_blocks': [_c_int],
     'rlg_ppo_loss_discrete': [_P, _c_ll, _P, _P, _P, _P, _c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _c_int,

@@ -63,6 +63,14 @@ def pendulum_lstm_4096(num_actors=4096, units=64, **over):
                               {'obs_dim': 3, 'act_dim': 1}, seq_length=16, **over)}
 
 
+def pendulum_gru_4096(num_actors=4096, units=64, **over):
+    """Config #5's shape with a GRU in the LSTM's place (`rnn: {name: gru, layers: 1}`; 128 units is the cell of the
+    reference's configs/smac/v1/runs/MMM2_rnn.yaml).  Everything but the cell's name is pendulum_lstm_4096's."""
+    params = pendulum_lstm_4096(num_actors=num_actors, units=units, **over)
+    params['network']['rnn']['name'] = 'gru'
+    return params
+
+
 def tiny(num_actors=256, horizon=8, obs_dim=12, act_dim=3, **over):
     """Small config for smoke tests."""
     return {'algo': {'name': 'a2c_continuous'}, 'model': {'name': 'continuous_a2c_logstd'},

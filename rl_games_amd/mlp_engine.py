@@ -16,6 +16,10 @@ so the backward pass is written out explicitly instead of being recorded by auto
     kernel per direction (csrc/lstm.hip; 128 units: csrc/lstm_wide.hip) instead of a Python loop of per-timestep MIOpen calls
     with done resets (rl_games/common/layers/recurrent.py:26-58) and autograd BPTT through it;
     its input projection and all four weight/bias gradients are whole-sequence GEMMs.
+  * a single-layer GRU in that position (`rnn: {name: gru, layers: 1}`, network_builder.py:250-276) likewise
+    (csrc/gru.hip; 128 units: csrc/gru_wide.hip): one state tensor instead of two, 3H gate columns, b_hh added inside
+    the kernel, and a backward that emits the gradient of the input side (W_ih, b_ih, the trunk) and of the hidden
+    side (W_hh, b_hh) as two arrays for the same weight-gradient and column-sum launches.
 Numerics: aten's formulas - by default (in-place activations) act' from the layer output like
 elu_backward(is_result=True): h > 0 ? 1 : h + 1; with `inplace_act=False` from the pre-activation
 (exp(z)); GEMM
@@ -62,12 +66,19 @@ class ManualMLP:
         self.A = net.mu.out_features
         self.V = net.value.out_features
         K = net.mu.in_features
-        self.lstm = None
+        self.lstm = self.gru = None      # the recurrent cell's torch module (parameters only), by kind
+        self.rnn = None                  # ... whichever of the two it is
         if getattr(net, 'has_rnn', False):
-            if net.rnn_name != 'lstm' or net.rnn_layers != 1 or not ops.lstm_supported(net.rnn_units):
-                raise NotImplementedError('manual engine: only a single-layer LSTM with 16/32/64/128 units')
-            self.lstm = net.rnn.rnn
+            supported = {'lstm': ops.lstm_supported, 'gru': ops.gru_supported}.get(net.rnn_name)
+            if supported is None or net.rnn_layers != 1 or not supported(net.rnn_units):
+                raise NotImplementedError('manual engine: only a single-layer LSTM or GRU with 16/32/64/128 units')
+            self.rnn = net.rnn.rnn
+            if net.rnn_name == 'lstm':
+                self.lstm = self.rnn
+            else:
+                self.gru = self.rnn
             self.Hr = net.rnn_units
+            self.Gr = (4 if self.lstm is not None else 3) * self.Hr      # gate columns
         wp, wg = arena.span(net.value.weight, net.mu.weight)
         bp, bg = arena.span(net.value.bias, net.mu.bias)
         self.head_w, self.head_w_grad = wp.view(self.V + self.A, K), wg.view(self.V + self.A, K)
@@ -95,7 +106,7 @@ class ManualMLP:
         self.last_step_fused = False     # the last backward() ran forward + loss + backward as one launch
         self._pending_backward = False
         self._fused_trunk = False
-        if fused_chain and self.lstm is None:
+        if fused_chain and self.rnn is None:
             try:
                 layers = [(l.weight, l.bias, self.act_name) for l in self.linears]
                 layers.append((self.head_w, self.head_b, 'None'))
@@ -106,11 +117,18 @@ class ManualMLP:
         # the gate-input product W_ih x + (b_ih + b_hh) as the chain's last (linear) layer - is the same fused
         # forward / backward launch pair; the sequence-persistent LSTM kernels and the head product follow.
         self.chain_rnn = None
-        if fused_chain and self.lstm is not None:
+        if self.rnn is not None:
+            # the bias of the gate-input product.  LSTM: b_ih + b_hh, summed into bias_sum by every forward.  GRU: b_hn is
+            # multiplied by r inside the cell, so only b_ih belongs to the input side - bias_ih_l0 itself; the kernel
+            # adds b_hh.
+            if self.lstm is not None:
+                self.gate_bias = self.bias_sum = torch.empty(self.Gr, device=dev)
+            else:
+                self.gate_bias, self.bias_sum = self.rnn.bias_ih_l0, None
+        if fused_chain and self.rnn is not None:
             try:
-                self.bias_sum = torch.empty(4 * self.Hr, device=dev)
                 layers = [(l.weight, l.bias, self.act_name) for l in self.linears]
-                layers.append((self.lstm.weight_ih_l0, self.bias_sum, 'None'))
+                layers.append((self.rnn.weight_ih_l0, self.gate_bias, 'None'))
                 self.chain_rnn = ops.MlpChain(layers, dev, weights_version=arena.weights_token)
             except NotImplementedError:
                 self.chain_rnn = None
@@ -118,20 +136,25 @@ class ManualMLP:
             self.nb = [(max_rows + 15) // 16 for _ in widths]      # one partial row per 16-row group at most
             self.xn = torch.empty(max_rows, self.linears[0].in_features, device=dev)
         self.partials = [torch.empty(nb * w, dtype=torch.float64, device=dev) for nb, w in zip(self.nb, widths)]
-        if self.lstm is not None:
-            Hr = self.Hr
-            self.gates = torch.empty(max_rows, 4 * Hr, device=dev)
-            self.d_gates = torch.empty(max_rows, 4 * Hr, device=dev)
+        if self.rnn is not None:
+            Hr, Gr = self.Hr, self.Gr
+            self.gates = torch.empty(max_rows, Gr, device=dev)
+            d_gates = torch.empty(max_rows, Gr, device=dev)
             self.rnn_out = torch.empty(max_rows, Hr, device=dev)
             self.d_rnn_out = torch.empty(max_rows, Hr, device=dev)
-            self.c_all = torch.empty(max_rows, Hr, device=dev)
+            kept = torch.empty(max_rows, Hr, device=dev)
             self.hprev = torch.empty(max_rows, Hr, device=dev)
-            if self.chain_rnn is None:
-                self.bias_sum = torch.empty(4 * Hr, device=dev)
-            self.gate_partials = torch.empty(ops.act_bwd_blocks(max_rows, 4 * Hr) * 4 * Hr,
-                                             dtype=torch.float64, device=dev)
-            # final states of the last forward, ping-pong so that a caller may feed them back in
-            self._state_buf = [[torch.empty(1, max_rows, Hr, device=dev) for _ in range(2)] for _ in range(2)]
+            self.gate_partials = torch.empty(ops.act_bwd_blocks(max_rows, Gr) * Gr, dtype=torch.float64, device=dev)
+            if self.lstm is not None:
+                self.d_gates, self.c_all = d_gates, kept
+            else:
+                self.hn_all = kept                                       # W_hn h + b_hn, before the gating by r
+                self.d_gx = d_gates                                      # gradient of the input side (dr, dz, dn)
+                self.d_gh = torch.empty(max_rows, Gr, device=dev)        # ... of the hidden side (dr, dz, dn * r)
+                self.gate_partials_h = torch.empty_like(self.gate_partials)
+            # final states of the last forward (LSTM: h and c, GRU: h), ping-pong so that a caller may feed them back in
+            nstates = 2 if self.lstm is not None else 1
+            self._state_buf = [[torch.empty(1, max_rows, Hr, device=dev) for _ in range(nstates)] for _ in range(2)]
             self._state_flip = 0
             self.last_states = None
 
@@ -160,7 +183,7 @@ class ManualMLP:
     def forward(self, x, keep=True, rnn_states=None, dones=None, seq_length=1, raw_rms=None, eps=1e-5):
         """x: [rows, in] normalised observations.  Returns heads [rows, V+A] (col 0..V-1 value,
         then mu).  `keep` retains what backward() needs (activations, LSTM cell states).  LSTM policies: rows are
-        ordered (sequence, t) with `seq_length` steps each, rnn_states = (h0, c0) of shape
+        ordered (sequence, t) with `seq_length` steps each, rnn_states = (h0, c0) - GRU: (h0,) - of shape
         [1, rows/seq_length, H], dones [rows] u8 resets the state entering a step (or None);
         the final states are left in `self.last_states`.
         raw_rms (recurrent policies on the fused trunk, `chain_rnn`): x holds RAW observations and raw_rms =
@@ -173,7 +196,7 @@ class ManualMLP:
         self._pending_backward = bool(keep)
         a = x
         fused_trunk = raw_rms is not None
-        if fused_trunk and (self.chain_rnn is None or self.lstm is None):
+        if fused_trunk and (self.chain_rnn is None or self.rnn is None):
             raise ValueError('raw_rms: the fused recurrent trunk is not available for this policy')
         for l, lin in enumerate(() if fused_trunk else self.linears):
             z = self.Z[l][:rows]
@@ -188,15 +211,17 @@ class ManualMLP:
             else:
                 h = z
             a = h
-        if self.lstm is not None:
-            rnn = self.lstm
+        if self.rnn is not None:
+            rnn = self.rnn
             S = rows // seq_length
             if S * seq_length != rows:
                 raise ValueError(f'rows ({rows}) must be a multiple of seq_length ({seq_length})')
-            h0, c0 = rnn_states[0][0], rnn_states[1][0]
-            if h0.shape[0] != S or not h0.is_contiguous() or not c0.is_contiguous():
+            h0 = rnn_states[0][0]
+            c0 = rnn_states[1][0] if self.lstm is not None else None
+            if h0.shape[0] != S or not h0.is_contiguous() or not (c0 is None or c0.is_contiguous()):
                 raise ValueError(f'rnn_states must be contiguous [1, {S}, {self.Hr}] tensors')
-            torch.add(rnn.bias_ih_l0, rnn.bias_hh_l0, out=self.bias_sum)
+            if self.lstm is not None:
+                torch.add(rnn.bias_ih_l0, rnn.bias_hh_l0, out=self.bias_sum)
             gates = self.gates[:rows]
             if fused_trunk:
                 rms = raw_rms if len(raw_rms) else None
@@ -210,7 +235,7 @@ class ManualMLP:
                     self.chain_rnn.forward(x, gates, rms=rms, eps=eps)
                     a = None
             else:
-                torch.addmm(self.bias_sum, a, rnn.weight_ih_l0.t(), out=gates)
+                torch.addmm(self.gate_bias, a, rnn.weight_ih_l0.t(), out=gates)
             out = self.rnn_out[:rows]
             # Final states are produced for inference calls only (keep=False: rollout / get_values),
             # into whichever buffer pair the inputs do NOT live in.  A training forward must not touch
@@ -219,12 +244,19 @@ class ManualMLP:
             if not keep:
                 self._state_flip = 1 if h0.data_ptr() == self._state_buf[0][0].data_ptr() else 0
                 hT = self._state_buf[self._state_flip][0][:, :S]
-                cT = self._state_buf[self._state_flip][1][:, :S]
-            ops.lstm_seq_forward(gates, rnn.weight_hh_l0, h0, c0, dones, out,
-                                 self.c_all[:rows] if keep else None, self.hprev[:rows] if keep else None,
-                                 None if hT is None else hT[0], None if cT is None else cT[0],
-                                 seq_len=seq_length)
-            self.last_states = None if hT is None else (hT, cT)
+                if self.lstm is not None:
+                    cT = self._state_buf[self._state_flip][1][:, :S]
+            if self.lstm is not None:
+                ops.lstm_seq_forward(gates, rnn.weight_hh_l0, h0, c0, dones, out,
+                                     self.c_all[:rows] if keep else None, self.hprev[:rows] if keep else None,
+                                     None if hT is None else hT[0], None if cT is None else cT[0],
+                                     seq_len=seq_length)
+                self.last_states = None if hT is None else (hT, cT)
+            else:
+                ops.gru_seq_forward(gates, rnn.weight_hh_l0, rnn.bias_hh_l0, h0, dones, out,
+                                    self.hn_all[:rows] if keep else None, self.hprev[:rows] if keep else None,
+                                    None if hT is None else hT[0], seq_len=seq_length)
+                self.last_states = None if hT is None else (hT,)
             self._rnn_in, self._c0, self._dones, self._T = a, c0, dones, seq_length
             a = out
         heads = self.heads[:rows]
@@ -327,23 +359,36 @@ class ManualMLP:
             return self._weight_grads(jobs, rows, colsums, loss_finalize, norm, maxima=maxima)
         jobs = [(d_heads, self._last, self.head_w_grad)]           # (dZ, X, grad) per weight matrix
         colsums = []                                               # (partials, blocks, cols, bias.grad)
-        if self.lstm is not None:
-            rnn = self.lstm
+        if self.rnn is not None:
+            rnn = self.rnn
             d_out = self.d_rnn_out[:rows]
             if self.V + self.A <= ops.NARROW_MAX:
                 ops.narrow_dx(d_heads, self.head_w, d_out)
             else:
                 torch.mm(d_heads, self.head_w, out=d_out)
-            gates, dg = self.gates[:rows], self.d_gates[:rows]
-            ops.lstm_seq_backward(gates, self.c_all[:rows], self._c0, self._dones, rnn.weight_hh_l0, d_out, dg,
-                                  self._T)
-            G = 4 * self.Hr
+            gates = self.gates[:rows]
+            G = self.Gr
             nbg = ops.act_bwd_blocks(rows, G)
             gpart = self.gate_partials[:nbg * G]
-            ops.act_bwd_colsum(dg, None, dg, 0, gpart, nbg)          # identity: column sums only
-            colsums.append((gpart, nbg, G, rnn.bias_ih_l0.grad))
-            colsums.append((gpart, nbg, G, rnn.bias_hh_l0.grad))     # d b_hh = d b_ih
-            jobs.append((dg, self.hprev[:rows], rnn.weight_hh_l0.grad))
+            if self.lstm is not None:
+                dg = self.d_gates[:rows]
+                ops.lstm_seq_backward(gates, self.c_all[:rows], self._c0, self._dones, rnn.weight_hh_l0, d_out, dg,
+                                      self._T)
+                dgh = dg
+                ops.act_bwd_colsum(dg, None, dg, 0, gpart, nbg)          # identity: column sums only
+                colsums.append((gpart, nbg, G, rnn.bias_ih_l0.grad))
+                colsums.append((gpart, nbg, G, rnn.bias_hh_l0.grad))     # d b_hh = d b_ih
+            else:
+                # dg = d_gx: the input side - W_ih, b_ih and the trunk; dgh = d_gh: the hidden side - W_hh, b_hh
+                dg, dgh = self.d_gx[:rows], self.d_gh[:rows]
+                ops.gru_seq_backward(gates, self.hn_all[:rows], self.hprev[:rows], self._dones, rnn.weight_hh_l0, d_out,
+                                     dg, dgh, self._T)
+                gpart_h = self.gate_partials_h[:nbg * G]
+                ops.act_bwd_colsum(dg, None, dg, 0, gpart, nbg)
+                ops.act_bwd_colsum(dgh, None, dgh, 0, gpart_h, nbg)
+                colsums.append((gpart, nbg, G, rnn.bias_ih_l0.grad))
+                colsums.append((gpart_h, nbg, G, rnn.bias_hh_l0.grad))
+            jobs.append((dgh, self.hprev[:rows], rnn.weight_hh_l0.grad))
             jobs.append((dg, self._rnn_in, rnn.weight_ih_l0.grad))
             if self._fused_trunk:
                 # dX chain of the trunk in ONE launch, from d gates down: dZ of every hidden layer + the

@@ -1367,3 +1367,51 @@ def lstm_seq_backward(gates, c_all, c0, dones, w_hh, d_out, d_gates, seq_len):
         _opt(dones, torch.uint8, 'dones'), _need(w_hh, F32, 'w_hh'), _need(d_out, F32, 'd_out'),
         _need(d_gates, F32, 'd_gates'), B // seq_len, seq_len, G // 4, _stream(gates)),
         'rlg_lstm_seq_backward')
+
+
+# ------------------------------------------------------------------ recurrent policy (GRU)
+
+def gru_supported(hidden):
+    """16, 32, 64 (W_hh in LDS, csrc/gru.hip) and 128 (W_hh in registers as MFMA fragments, csrc/gru_wide.hip)."""
+    return bool(_lib.load().rlg_gru_supported(int(hidden)))
+
+
+def gru_seq_forward(gates, w_hh, b_hh, h0, dones, out, hn_all=None, hprev=None, h_final=None, seq_len=1):
+    """gates [S*T, 3H] (row = seq*seq_len + t): x W_ih^T + b_ih in, activated (r, z, n) out; b_hh [3H]; out [S*T, H].
+    hn_all / hprev [S*T, H] (W_hn h + b_hn before the gating by r, state entering each step after the reset) are kept
+    for backward when given, h_final [S, H] likewise.  H must satisfy gru_supported: csrc/gru.hip (16/32/64) or
+    csrc/gru_wide.hip (128, w_hh 16-byte aligned)."""
+    lib = _lib.load()
+    B, G = gates.shape
+    H = G // 3
+    S = B // seq_len
+    if S * seq_len != B:
+        raise ValueError(f'rows ({B}) must be a multiple of seq_len ({seq_len})')
+    if G != 3 * H or tuple(w_hh.shape) != (G, H) or b_hh.numel() != G:
+        raise ValueError(f'gates [rows, 3H], w_hh [3H, H] and b_hh [3H] do not agree: {tuple(gates.shape)}, '
+                         f'{tuple(w_hh.shape)}, {tuple(b_hh.shape)}')
+    _lib.check(lib.rlg_gru_seq_forward(
+        _need(gates, F32, 'gates'), _need(w_hh, F32, 'w_hh'), _need(b_hh, F32, 'b_hh'), _need(h0, F32, 'h0'),
+        _opt(dones, torch.uint8, 'dones'), _need(out, F32, 'out'), _opt(hn_all, F32, 'hn_all'),
+        _opt(hprev, F32, 'hprev'), _opt(h_final, F32, 'h_final'),
+        S, seq_len, H, _stream(gates)), 'rlg_gru_seq_forward')
+
+
+def gru_seq_backward(gates, hn_all, hprev, dones, w_hh, d_out, d_gx, d_gh, seq_len):
+    """From d_out [S*T, H] and what gru_seq_forward kept: d_gx [S*T, 3H] = (dr_pre, dz_pre, dn_pre), the gradient of
+    x W_ih^T + b_ih, and d_gh [S*T, 3H] = (dr_pre, dz_pre, dn_pre * r), the gradient of h W_hh^T + b_hh.  The weight
+    gradients are whole-sequence products of the two outside (dW_ih = d_gx^T x, dW_hh = d_gh^T hprev)."""
+    lib = _lib.load()
+    B, G = gates.shape
+    H = G // 3
+    S = B // seq_len
+    if S * seq_len != B:
+        raise ValueError(f'rows ({B}) must be a multiple of seq_len ({seq_len})')
+    if G != 3 * H or tuple(w_hh.shape) != (G, H) or d_gx.shape != gates.shape or d_gh.shape != gates.shape:
+        raise ValueError(f'gates / d_gx / d_gh [rows, 3H] and w_hh [3H, H] do not agree: {tuple(gates.shape)}, '
+                         f'{tuple(d_gx.shape)}, {tuple(d_gh.shape)}, {tuple(w_hh.shape)}')
+    _lib.check(lib.rlg_gru_seq_backward(
+        _need(gates, F32, 'gates'), _need(hn_all, F32, 'hn_all'), _need(hprev, F32, 'hprev'),
+        _opt(dones, torch.uint8, 'dones'), _need(w_hh, F32, 'w_hh'), _need(d_out, F32, 'd_out'),
+        _need(d_gx, F32, 'd_gx'), _need(d_gh, F32, 'd_gh'), S, seq_len, H, _stream(gates)),
+        'rlg_gru_seq_backward')
