@@ -1362,6 +1362,8 @@ def lstm_seq_backward(gates, c_all, c0, dones, w_hh, d_out, d_gates, seq_len):
     Same widths as lstm_seq_forward; the weight gradients are whole-sequence products of d_gates outside."""
     lib = _lib.load()
     B, G = gates.shape
+    if (B // seq_len) * seq_len != B:
+        raise ValueError(f'rows ({B}) must be a multiple of seq_len ({seq_len})')
     _lib.check(lib.rlg_lstm_seq_backward(
         _need(gates, F32, 'gates'), _need(c_all, F32, 'c_all'), _need(c0, F32, 'c0'),
         _opt(dones, torch.uint8, 'dones'), _need(w_hh, F32, 'w_hh'), _need(d_out, F32, 'd_out'),

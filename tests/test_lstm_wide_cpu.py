@@ -75,3 +75,16 @@ def test_wide_lstm_ops_reject_cpu_tensors():
         ops.lstm_seq_forward(gates, w_hh, state, state, None, rows, seq_len=T)
     with pytest.raises(HipLibraryError):
         ops.lstm_seq_backward(gates, rows, state, None, w_hh, rows, torch.zeros(S * T, 4 * H), T)
+
+
+def test_lstm_ops_reject_rows_that_are_no_multiple_of_seq_len():
+    from rl_games_amd import ops
+    H = 16
+    gates = torch.zeros(7, 4 * H)
+    w_hh = torch.zeros(4 * H, H)
+    state = torch.zeros(3, H)
+    rows = torch.zeros(7, H)
+    with pytest.raises(ValueError, match='multiple of seq_len'):
+        ops.lstm_seq_forward(gates, w_hh, state, state, None, rows, seq_len=2)
+    with pytest.raises(ValueError, match='multiple of seq_len'):
+        ops.lstm_seq_backward(gates, rows, state, None, w_hh, rows, torch.zeros(7, 4 * H), 2)

@@ -362,6 +362,197 @@ def test_ppo_loss_max_tie_and_clip_edges():
     assert torch.allclose(d_val.cpu(), ref['d_values'].reshape(-1), rtol=RTOL, atol=1e-10)
 
 
+# ----------------------------------------------------------------------------- central-value critic loss
+
+_VL_E = 0.25                     # e_clip: 16 steps of the 1/64 grid
+_VL_KINDS = 11                   # planted row kinds, one per i % 16 below 11; the other rows stay random
+
+
+def _value_loss_inputs(mb, seed):
+    """values, old_values, returns on the 1/64 grid in [-4, 4].  Rows with i % 16 = k < 11 are planted:
+       k 0 / 1: delta = v - v_old = -e / +e (the inclusive clip edge)      k 2 / 4: one grid step inside +e / -e
+       k 3 / 5: one step outside +e / -e                                   k 6: delta = 0
+       k 7 / 8: outside the range with the return half-way between v and the clipped value: c1 == c2 exactly
+       k 9: outside, return = v (the clipped branch wins, its gradient is 0)
+       k 10: outside, return = v_old (the unclipped branch wins)."""
+    gen = g(seed)
+
+    def grid(lo, hi):
+        return torch.randint(lo, hi + 1, (mb,), generator=gen).float() / 64
+    vo = grid(-192, 192)
+    delta = grid(-48, 48)
+    ret = grid(-256, 256)
+    k = torch.arange(mb) % 16
+    for kind, steps in enumerate((-16, 16, 15, 17, -15, -17, 0, 40, -40, 40, 40)):
+        delta[k == kind] = steps / 64
+    v = vo + delta
+    ret = torch.where(k == 7, vo + 28 / 64, ret)
+    ret = torch.where(k == 8, vo - 28 / 64, ret)
+    ret = torch.where(k == 9, v, ret)
+    ret = torch.where(k == 10, vo, ret)
+    assert v.abs().max() <= 4 and ret.abs().max() <= 4 and all(torch.equal(t * 64, (t * 64).round()) for t in (v, vo, ret))
+    return v, vo, ret, k
+
+
+def _value_loss_reference(mb, clip_value, masked):
+    """The inputs of one case, the fp64 reference (d_values, sum c m, sum m, denom), and the check that the planted
+    branches are there, counted on the reference's own fp64 quantities."""
+    v, vo, ret, k = _value_loss_inputs(mb, seed=mb)
+    mask = None
+    if masked:
+        mask = (torch.rand(mb, generator=g(mb + 1)) < 0.75).float()
+        mask[(torch.arange(mb) // 16) % 3 == 1] = 0.0        # whole groups of planted rows masked out
+        if mb == 1:
+            mask[:] = 0.0                                    # mask_sum 0: denom = max(0, 1)
+
+    # the reference, fp64
+    v64 = v.double().requires_grad_(True)
+    vo64, r64 = vo.double(), ret.double()
+    if clip_value:
+        d64 = v64 - vo64
+        clipped = vo64 + d64.clamp(-_VL_E, _VL_E)
+        c1, c2 = (v64 - r64) ** 2, (clipped - r64) ** 2
+        c = torch.max(c1, c2)
+    else:
+        c = (r64 - v64) ** 2
+    m64 = torch.ones(mb, dtype=torch.float64) if mask is None else mask.double()
+    denom = float(mb) if mask is None else max(float(m64.sum()), 1.0)
+    ((c * m64).sum() / denom).backward()
+    want_d, want_sum, want_msum = v64.grad, float((c.detach() * m64).sum()), float(m64.sum())
+
+    # the planted branches are there (counted on the reference's own fp64 quantities)
+    if mb >= 255:
+        planted = [int((k == kind).sum()) for kind in range(_VL_KINDS)]
+        assert min(planted) >= mb // 16
+        if clip_value:
+            dd, a, b = d64.detach(), c1.detach(), c2.detach()
+            assert int((dd == -_VL_E).sum()) >= planted[0] and int((dd == _VL_E).sum()) >= planted[1]
+            assert int(((dd.abs() < _VL_E) & (dd != 0)).sum()) >= planted[2] + planted[4]
+            assert int((dd.abs() > _VL_E).sum()) >= sum(planted[i] for i in (3, 5, 7, 8, 9, 10))
+            assert int((dd == 0).sum()) >= planted[6]
+            assert int(((a == b) & (dd.abs() > _VL_E)).sum()) >= planted[7] + planted[8]      # the 1/2 : 1/2 split
+            assert int(((b > a) & (want_d == 0)).sum()) >= (planted[9] if mask is None else 1)
+            assert int((a > b).sum()) >= planted[10]
+            assert int(((a == b) & (dd.abs() > _VL_E) & (want_d != 0)).sum()) >= 1
+        if mask is not None:
+            assert 0 < want_msum < mb and all(int(((k == kind) & (mask == 0)).sum()) >= 1 for kind in range(_VL_KINDS))
+            assert all(int(((k == kind) & (mask == 1)).sum()) >= 1 for kind in range(_VL_KINDS))
+    return v, vo, ret, mask, want_d, want_sum, want_msum, denom
+
+
+@pytest.mark.parametrize('masked', [False, True])
+@pytest.mark.parametrize('clip_value', [True, False])
+@pytest.mark.parametrize('mb', [1, 255, 256, 257, 1000, 4096])
+def test_value_loss_matches_fp64(mb, clip_value, masked):
+    """rlg_value_loss (the central-value critic loss, its gradient and the block partials that rlg_ppo_loss_finalize
+    reduces) against common_losses.critic_loss restated in fp64 torch, d_values by autograd of (c m).sum() / denom with
+    denom = mb, or max(mask_sum, 1) under a mask.  On the 1/64 grid with e_clip = 1/4 every fp32 operation of the
+    kernel up to the last is exact (differences below 8 in steps of 2^-6, squares below 64 in steps of 2^-12: at most
+    19 significant bits), so no clip-side or max decision can differ between fp32 and fp64 and the only inexact step is
+    g (m / denom): two fp32 roundings, 1.2e-7 relative - d_values to rtol 1e-6 with no absolute term; sum c m to 1e-12
+    relative; sum m exact; every other slot exactly 0.  Then ppo_loss_finalize as central_value.py calls it
+    (actions_num 0, critic_coef 2) leaves mean(c) in the c_loss and the total-loss slots: rtol 1e-6.
+    As measured on an MI355X over the 24 cases: d_values 1.2e-7 relative at most, sum c m exact, mean(c) 3.2e-8."""
+    from rl_games_amd import ops
+    v, vo, ret, mask, want_d, want_sum, want_msum, denom = _value_loss_reference(mb, clip_value, masked)
+
+    d = lambda t: t.contiguous().to(DEV)
+    nb = (mb + 255) // 256
+    d_values = torch.full((mb,), float('nan'), device=DEV)
+    partials = torch.full((nb, 7), float('nan'), dtype=torch.float64, device=DEV)
+    mask_d = None if mask is None else d(mask)
+    mask_sum = None if mask is None else mask_d.sum().reshape(1)
+    ops.value_loss(d(v), d(vo), d(ret), d_values, partials, _VL_E, clip_value, mask_d, mask_sum)
+    got_d, p = d_values.cpu().double(), partials.cpu()
+    err = ((got_d - want_d).abs() / want_d.abs().clamp_min(1e-300)).max().item()
+    print('d_values max relative |diff|', err, 'sum c m relative |diff|', abs(float(p[:, 1].sum()) - want_sum) / max(want_sum, 1e-300))
+    assert torch.allclose(got_d, want_d, rtol=1e-6, atol=0)
+    assert abs(float(p[:, 1].sum()) - want_sum) <= 1e-12 * want_sum
+    assert float(p[:, 5].sum()) == want_msum
+    assert (p[:, [0, 2, 3, 4, 6]] == 0).all()
+
+    scalars = torch.full((8,), float('nan'), device=DEV)
+    no_logstd = torch.zeros(1, device=DEV)
+    ops.ppo_loss_finalize(partials, nb, 0, mb, mask is not None, 2.0, 0.0, 0.0, scalars, no_logstd)
+    s = scalars.cpu().double()
+    mean_c = torch.tensor(want_sum / denom, dtype=torch.float64)
+    print('mean(c) relative |diff|', (abs(s[5] - mean_c) / mean_c.clamp_min(1e-300)).item())
+    assert torch.allclose(s[1], mean_c, rtol=1e-6, atol=0) and torch.allclose(s[5], mean_c, rtol=1e-6, atol=0)
+    assert s[6].item() == want_msum and s[0] == 0 and s[2] == 0 and s[3] == 0 and s[4] == 0
+    assert no_logstd.item() == 0.0
+
+
+# ----------------------------------------------------------------------------- moments of user-built batches
+
+@pytest.mark.parametrize('mask_kind', [None, 'binary', 'fractional'])
+@pytest.mark.parametrize('B', [1, 255, 2049, 100_000, 512 * 2048 + 77])
+def test_triple_moments_matches_fp64(B, mask_kind):
+    """rlg_triple_moments: fp64 block partials {sum a w, sum a^2 w, sum v w, sum v^2 w, sum r w, sum r^2 w[, sum w]} of
+    advantages ~ 1e-3, values and returns ~ 1e3, one row per block; ceil(B / 2048) blocks capped at 512, so the last B
+    wraps the grid-stride loop (some threads take nine elements, the others eight).  The kernel forms every term in
+    fp64 from exactly upcast fp32 inputs, as the reference does; the two differ in summation order only.  The
+    advantages carry a mean of a quarter of their spread so that sum a w is not a cancelled remainder (sum |a| / |sum a|
+    stays about 3): fp64 sums of 1e6 terms in either order then agree to a few 1e-16 log2(B) relative - bound 1e-12.
+    As measured on an MI355X over the 15 cases: 3.1e-16 relative at most in any column, sum w exact."""
+    from rl_games_amd import _lib, ops
+    gen = g(B % 1000 + 3)
+    adv = 1e-3 * (torch.randn(B, generator=gen) + 0.25)
+    values = 1e3 + 50.0 * torch.randn(B, generator=gen)
+    returns = values + 20.0 * torch.randn(B, generator=gen)
+    mask = None
+    if mask_kind == 'binary':
+        mask = (torch.rand(B, generator=gen) < 0.7).float()
+        mask[0] = 1.0
+    elif mask_kind == 'fractional':
+        mask = torch.rand(B, generator=gen)
+    nb = _lib.load().rlg_triple_moments_num_blocks(B)
+    assert nb == min(512, max(1, -(-B // 2048)))
+    d = lambda t: None if t is None else t.to(DEV)
+    part = ops.triple_moments(d(adv), d(values), d(returns), d(mask))
+    assert part.dtype == torch.float64 and tuple(part.shape) == (nb, 6 if mask is None else 7)
+    a, v, r = adv.double(), values.double(), returns.double()
+    w = torch.ones(B, dtype=torch.float64) if mask is None else mask.double()
+    want = torch.stack([(a * w).sum(), (a * a * w).sum(), (v * w).sum(), (v * v * w).sum(), (r * w).sum(),
+                        (r * r * w).sum(), w.sum()])[:part.shape[1]]
+    got = part.cpu().sum(0)
+    rel = ((got - want).abs() / want.abs()).tolist()
+    print('relative |diff| per column', rel)
+    assert max(rel) <= 1e-12, rel
+
+
+# ----------------------------------------------------------------------------- recurrent states at episode ends
+
+@pytest.mark.parametrize('draw', ['random', 'all', 'none'])
+@pytest.mark.parametrize('L,N,U', [(1, 5, 16), (2, 300, 64), (1, 4099, 128), (3, 1, 1), (2, 4099, 130)])
+def test_rnn_zero_done_states(L, N, U, draw):
+    """rlg_rnn_zero_done_states on [L, N, U] states: the rows of done envs become +0.0 in every layer, every other
+    element keeps its bits (compared as int32: a -0.0 and a denormal planted among the kept ones survive, the same two
+    planted in a done row become +0.0).  About 20 % dones, all done and none done.  One thread per element up to 4,096
+    blocks of 256: (2, 4099, 130) is past that and wraps the grid-stride loop, (3, 1, 1) is three threads."""
+    from rl_games_amd import ops
+    gen = g(L * 1000 + N + U)
+    states = torch.randn(L, N, U, generator=gen)
+    dones = {'random': torch.rand(N, generator=gen) < 0.2, 'all': torch.ones(N, dtype=torch.bool),
+             'none': torch.zeros(N, dtype=torch.bool)}[draw]
+    if draw == 'random' and N >= 5:
+        dones[0], dones[1] = True, False
+        assert 0 < int(dones.sum()) < N
+    bits = states.view(torch.int32)
+    for env in {0, min(1, N - 1), N - 1}:                     # a done row and a kept one wherever the draw has both
+        bits[L - 1, env, 0] = -2 ** 31                        # -0.0
+        bits[0, env, U - 1] = 0x123                           # a denormal
+        assert states[L - 1, env, 0] == 0 and torch.signbit(states[L - 1, env, 0])
+        assert 0 < states[0, env, U - 1] < 1e-38
+    want = states.clone()
+    want[:, dones] = 0.0
+    dev_states = states.to(DEV)
+    ops.rnn_zero_done_states(dev_states, dones.to(torch.uint8).to(DEV))
+    got = dev_states.cpu()
+    assert torch.equal(got.view(torch.int32), want.view(torch.int32))
+    assert (got[:, dones].view(torch.int32) == 0).all()
+    assert torch.equal(got[:, ~dones].view(torch.int32), states[:, ~dones].view(torch.int32))
+
+
 # ----------------------------------------------------------------------------- optimiser
 
 @pytest.mark.parametrize('truncate', [True, False])
