@@ -10,13 +10,13 @@
 // gx = x W_ih^T + b_ih for every timestep is ONE product before the launch (rows ordered seq*T + t).  b_hn is
 // multiplied by r and cannot be folded into gx the way lstm.hip folds b_hh: the kernel takes b_hh [3H] and adds it.
 //
-// One launch runs ALL timesteps of a tile of sequences, as in lstm.hip:
+// One launch runs ALL timesteps of a tile of sequences, as in lstm.hip (the product scheme, shared with it, the cell
+// formulas, shared with gru_wide.hip, and the launch and dispatch helpers are in rnn_seq.hpp):
 //   * W_hh [3H, H] (48 KB for H = 64) lives in LDS for the whole kernel;
 //   * thread (j, group) owns hidden unit j of R sequences; the hidden state goes through a double-buffered LDS tile
 //     (one barrier per timestep);
 //   * the kernel overwrites gx with the activated gates (r, z, n); for training it also keeps hn (before the gating
-//     by r - what c_all is to the LSTM) and the state entering each step;
-//   * where dones[seq, t] is set the state ENTERING step t is zeroed (policy.RnnWithDones).
+//     by r - what c_all is to the LSTM) and the state entering each step.
 // Backward walks the same tile in reverse and emits TWO arrays: d_gx = (dr, dz, dn), the gradient of the input side
 // (dW_ih = d_gx^T X, db_ih, the trunk's dX), and d_gh = (dr, dz, dn * r), the gradient of the hidden side
 // (dW_hh = d_gh^T Hprev, db_hh); the weight gradients are whole-sequence products outside the kernel.
@@ -26,17 +26,12 @@
 // The matvec per step is H*3H MACs per sequence: latency-bound by the timestep chain, VALU FMAs out of LDS.
 // 128 units: csrc/gru_wide.hip.
 
-#include "rlg_device.hpp"
+#include "rnn_seq.hpp"
 
 namespace rlg {
 
-constexpr int kGruMaxSeqPerBlock = 16;
-constexpr int kGruThreads = 256;
-
-__device__ __forceinline__ float gru_sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 template <int H, int SB>
-__global__ __launch_bounds__(kGruThreads) void gru_seq_fwd_kernel(
+__global__ __launch_bounds__(kSeqThreads) void gru_seq_fwd_kernel(
     float* __restrict__ gates,           // [S*T, 3H]  in: x-part + b_ih, out: activated gates (r, z, n)
     const float* __restrict__ w_hh,      // [3H, H]
     const float* __restrict__ b_hh,      // [3H]
@@ -48,28 +43,22 @@ __global__ __launch_bounds__(kGruThreads) void gru_seq_fwd_kernel(
     float* __restrict__ hT,              // [S, H] final h (nullptr)
     int S, int T) {
   constexpr int G = 3 * H;
-  constexpr int kGroups = kGruThreads / H;             // sequence groups per block
+  constexpr int kGroups = kSeqThreads / H;             // sequence groups per block
   constexpr int R = SB / kGroups;                      // sequences per thread
-  static_assert(kGruThreads % H == 0 && SB % kGroups == 0, "tile shape");
+  static_assert(kSeqThreads % H == 0 && SB % kGroups == 0, "tile shape");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* wT = smem;                                     // [H][3H]: wT[k][r] = w_hh[r][k]
   float* hbuf = smem + H * G;                           // [2][SB][H]
   const int tid = threadIdx.x;
   const int j = tid % H;
   const int grp = tid / H;
-  for (int idx = tid; idx < G * H; idx += kGruThreads) {
-    const int k = idx / G, r = idx - k * G;             // LDS write contiguous, global read strided (L2)
-    wT[idx] = w_hh[r * H + k];
-  }
-  const float b_r = b_hh[0 * H + j], b_z = b_hh[1 * H + j], b_n = b_hh[2 * H + j];
-  const int seq0 = blockIdx.x * SB;
+  narrow_stage_w_transposed<3, H>(wT, w_hh);
+  const float bias[3] = {b_hh[0 * H + j], b_hh[1 * H + j], b_hh[2 * H + j]};
   int seq[R];
   bool live[R];
 #pragma unroll
   for (int r = 0; r < R; ++r) {
-    const int s = seq0 + grp * R + r;
-    live[r] = s < S;
-    seq[r] = live[r] ? s : S - 1;
+    tile_slot(blockIdx.x * SB + grp * R + r, S, seq[r], live[r]);
     hbuf[(grp * R + r) * H + j] = h0[static_cast<long long>(seq[r]) * H + j];
   }
   __syncthreads();
@@ -99,24 +88,21 @@ __global__ __launch_bounds__(kGruThreads) void gru_seq_fwd_kernel(
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       const long long row = static_cast<long long>(seq[r]) * T + t;
-      const float keep = (dones && dones[row]) ? 0.0f : 1.0f;
+      const float keep = step_keep(dones, row);
       float* grow = gates + row * G;
       const float hp = hcur[(grp * R + r) * H + j] * keep;
       // a slot past S aliases sequence S - 1, whose gates its owner overwrites in this very step: it loads none of
       // them (its state only ever reaches its own column of the LDS tile and is never stored)
-      const float xr = live[r] ? grow[0 * H + j] : 0.0f;
-      const float xz = live[r] ? grow[1 * H + j] : 0.0f;
-      const float xn = live[r] ? grow[2 * H + j] : 0.0f;
-      const float gr = gru_sigmoid_f(xr + (keep * acc[0][r] + b_r));
-      const float gz = gru_sigmoid_f(xz + (keep * acc[1][r] + b_z));
-      const float hn = keep * acc[2][r] + b_n;
-      const float gn = tanhf(xn + gr * hn);
-      const float hnew = (1.0f - gz) * gn + gz * hp;
+      const float x[3] = {live[r] ? grow[0 * H + j] : 0.0f, live[r] ? grow[1 * H + j] : 0.0f,
+                          live[r] ? grow[2 * H + j] : 0.0f};
+      const float a[3] = {acc[0][r], acc[1][r], acc[2][r]};
+      float g[3], hn;
+      const float hnew = gru_fwd_point(x, a, bias, keep, hp, g, hn);
       hnext[(grp * R + r) * H + j] = hnew;
       if (live[r]) {
-        grow[0 * H + j] = gr;
-        grow[1 * H + j] = gz;
-        grow[2 * H + j] = gn;
+        grow[0 * H + j] = g[0];
+        grow[1 * H + j] = g[1];
+        grow[2 * H + j] = g[2];
         out[row * H + j] = hnew;
         if (hn_all) hn_all[row * H + j] = hn;
         if (hprev) hprev[row * H + j] = hp;
@@ -133,7 +119,7 @@ __global__ __launch_bounds__(kGruThreads) void gru_seq_fwd_kernel(
 }
 
 template <int H, int SB>
-__global__ __launch_bounds__(kGruThreads) void gru_seq_bwd_kernel(
+__global__ __launch_bounds__(kSeqThreads) void gru_seq_bwd_kernel(
     const float* __restrict__ gates,     // [S*T, 3H] activated gates of the forward pass
     const float* __restrict__ hn_all,    // [S*T, H]
     const float* __restrict__ hprev,     // [S*T, H]
@@ -144,7 +130,7 @@ __global__ __launch_bounds__(kGruThreads) void gru_seq_bwd_kernel(
     float* __restrict__ d_gh,            // [S*T, 3H] d loss / d (h W_hh^T + b_hh)
     int S, int T) {
   constexpr int G = 3 * H;
-  constexpr int kGroups = kGruThreads / H;
+  constexpr int kGroups = kSeqThreads / H;
   constexpr int R = SB / kGroups;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* w = smem;                                      // [3H][H] as stored
@@ -153,17 +139,14 @@ __global__ __launch_bounds__(kGruThreads) void gru_seq_bwd_kernel(
   const int j = tid % H;
   const int grp = tid / H;
   if (T > 1) {                                          // (T = 1: no state before step 0 to send a gradient to)
-    for (int idx = tid; idx < G * H; idx += kGruThreads) w[idx] = w_hh[idx];
+    narrow_stage_w<3, H>(w, w_hh);
   }
-  const int seq0 = blockIdx.x * SB;
   int seq[R];
   bool live[R];
   float dh_next[R];
 #pragma unroll
   for (int r = 0; r < R; ++r) {
-    const int s = seq0 + grp * R + r;
-    live[r] = s < S;
-    seq[r] = live[r] ? s : S - 1;                       // a slot past S re-reads S - 1 (inputs only), stores nothing
+    tile_slot(blockIdx.x * SB + grp * R + r, S, seq[r], live[r]);
     dh_next[r] = 0.0f;
   }
   __syncthreads();
@@ -173,120 +156,36 @@ __global__ __launch_bounds__(kGruThreads) void gru_seq_bwd_kernel(
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       const long long row = static_cast<long long>(seq[r]) * T + t;
-      keep[r] = (dones && dones[row]) ? 0.0f : 1.0f;
+      keep[r] = step_keep(dones, row);
       const float* grow = gates + row * G;
-      const float gr = grow[0 * H + j], gz = grow[1 * H + j], gn = grow[2 * H + j];
+      const float g[3] = {grow[0 * H + j], grow[1 * H + j], grow[2 * H + j]};
       const float hn = hn_all[row * H + j];
       const float hp = hprev[row * H + j];
       const float dh = d_out[row * H + j] + dh_next[r];
-      const float dn = (dh * (1.0f - gz)) * (1.0f - gn * gn);
-      const float dz = (dh * (hp - gn)) * (gz * (1.0f - gz));
-      const float dr = (dn * hn) * (gr * (1.0f - gr));
-      const float dnr = dn * gr;
-      dhz[r] = dh * gz;
+      float dgx[3], dnr;
+      dhz[r] = gru_bwd_point(g, hn, hp, dh, dgx, dnr);
       float* db = dgb + (grp * R + r) * G;
-      db[0 * H + j] = dr;
-      db[1 * H + j] = dz;
+      db[0 * H + j] = dgx[0];
+      db[1 * H + j] = dgx[1];
       db[2 * H + j] = dnr;
       if (live[r]) {
         float* xrow = d_gx + row * G;
         float* hrow = d_gh + row * G;
-        xrow[0 * H + j] = dr;
-        xrow[1 * H + j] = dz;
-        xrow[2 * H + j] = dn;
-        hrow[0 * H + j] = dr;
-        hrow[1 * H + j] = dz;
+        xrow[0 * H + j] = dgx[0];
+        xrow[1 * H + j] = dgx[1];
+        xrow[2 * H + j] = dgx[2];
+        hrow[0 * H + j] = dgx[0];
+        hrow[1 * H + j] = dgx[1];
         hrow[2 * H + j] = dnr;
       }
     }
     if (t == 0) break;                                  // nothing consumes d h_{-1}
     __syncthreads();
     float acc[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = 0.0f;
-#pragma unroll 4
-    for (int row = 0; row < G; ++row) {
-      const float wv = w[row * H + j];
-#pragma unroll
-      for (int r = 0; r < R; ++r) acc[r] = __builtin_fmaf(dgb[(grp * R + r) * G + row], wv, acc[r]);
-    }
+    narrow_bwd_product<3, H, R>(acc, w, dgb, j, grp);
 #pragma unroll
     for (int r = 0; r < R; ++r) dh_next[r] = (dhz[r] + acc[r]) * keep[r];
     __syncthreads();
-  }
-}
-
-// Sequences per block as in lstm.hip: 16 (4 per thread at H = 64) when that still gives >= 256 blocks, otherwise
-// fewer, so that a 1,024-sequence minibatch uses the whole chip.
-static int gru_seq_per_block(int S, int H) {
-  const int min_sb = kGruThreads / H;                  // one sequence per thread group at least
-  int sb = kGruMaxSeqPerBlock;
-  while (sb > min_sb && (S + sb - 1) / sb < 256) sb >>= 1;
-  return sb;
-}
-
-template <int H, int SB>
-static int launch_gru_fwd_sb(float* gates, const float* w_hh, const float* b_hh, const float* h0,
-                             const uint8_t* dones, float* out, float* hn_all, float* hprev, float* hT, int S, int T,
-                             hipStream_t st) {
-  if constexpr (SB < kGruThreads / H) {
-    return static_cast<int>(hipErrorInvalidValue);
-  } else {
-    const size_t shm = (static_cast<size_t>(3) * H * H + 2 * SB * H) * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gru_seq_fwd_kernel<H, SB>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(shm));
-      if (e != hipSuccess) return static_cast<int>(e);
-      attr_set = true;
-    }
-    const int grid = (S + SB - 1) / SB;
-    hipLaunchKernelGGL((gru_seq_fwd_kernel<H, SB>), dim3(grid), dim3(kGruThreads), shm, st, gates, w_hh, b_hh, h0,
-                       dones, out, hn_all, hprev, hT, S, T);
-    RLG_RETURN_LAUNCH_STATUS();
-  }
-}
-
-template <int H>
-static int launch_gru_fwd(float* gates, const float* w_hh, const float* b_hh, const float* h0, const uint8_t* dones,
-                          float* out, float* hn_all, float* hprev, float* hT, int S, int T, hipStream_t st) {
-  switch (gru_seq_per_block(S, H)) {
-    case 16: return launch_gru_fwd_sb<H, 16>(gates, w_hh, b_hh, h0, dones, out, hn_all, hprev, hT, S, T, st);
-    case 8: return launch_gru_fwd_sb<H, 8>(gates, w_hh, b_hh, h0, dones, out, hn_all, hprev, hT, S, T, st);
-    default: return launch_gru_fwd_sb<H, 4>(gates, w_hh, b_hh, h0, dones, out, hn_all, hprev, hT, S, T, st);
-  }
-}
-
-template <int H, int SB>
-static int launch_gru_bwd_sb(const float* gates, const float* hn_all, const float* hprev, const uint8_t* dones,
-                             const float* w_hh, const float* d_out, float* d_gx, float* d_gh, int S, int T,
-                             hipStream_t st) {
-  if constexpr (SB < kGruThreads / H) {
-    return static_cast<int>(hipErrorInvalidValue);
-  } else {
-    const size_t shm = (static_cast<size_t>(3) * H * H + SB * 3 * H) * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gru_seq_bwd_kernel<H, SB>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(shm));
-      if (e != hipSuccess) return static_cast<int>(e);
-      attr_set = true;
-    }
-    const int grid = (S + SB - 1) / SB;
-    hipLaunchKernelGGL((gru_seq_bwd_kernel<H, SB>), dim3(grid), dim3(kGruThreads), shm, st, gates, hn_all, hprev,
-                       dones, w_hh, d_out, d_gx, d_gh, S, T);
-    RLG_RETURN_LAUNCH_STATUS();
-  }
-}
-
-template <int H>
-static int launch_gru_bwd(const float* gates, const float* hn_all, const float* hprev, const uint8_t* dones,
-                          const float* w_hh, const float* d_out, float* d_gx, float* d_gh, int S, int T,
-                          hipStream_t st) {
-  switch (gru_seq_per_block(S, H)) {
-    case 16: return launch_gru_bwd_sb<H, 16>(gates, hn_all, hprev, dones, w_hh, d_out, d_gx, d_gh, S, T, st);
-    case 8: return launch_gru_bwd_sb<H, 8>(gates, hn_all, hprev, dones, w_hh, d_out, d_gx, d_gh, S, T, st);
-    default: return launch_gru_bwd_sb<H, 4>(gates, hn_all, hprev, dones, w_hh, d_out, d_gx, d_gh, S, T, st);
   }
 }
 
@@ -297,51 +196,42 @@ int launch_gru_bwd_wide(const float* gates, const float* hn_all, const float* hp
                         const float* w_hh, const float* d_out, float* d_gx, float* d_gh, int S, int T,
                         hipStream_t st);
 
+// kernel families for rnn_seq.hpp's launch_seq
+struct GruFwd {
+  template <int H, int SB>
+  static constexpr auto kernel = gru_seq_fwd_kernel<H, SB>;
+  static constexpr size_t lds_floats(int H, int SB) { return static_cast<size_t>(3) * H * H + 2 * SB * H; }
+  static constexpr auto wide = launch_gru_fwd_wide;
+};
+
+struct GruBwd {
+  template <int H, int SB>
+  static constexpr auto kernel = gru_seq_bwd_kernel<H, SB>;
+  static constexpr size_t lds_floats(int H, int SB) { return static_cast<size_t>(3) * H * H + SB * 3 * H; }
+  static constexpr auto wide = launch_gru_bwd_wide;
+};
+
 }  // namespace rlg
 
 extern "C" {
 
-int rlg_gru_supported(int hidden) {
-  return (hidden == 16 || hidden == 32 || hidden == 64 || hidden == 128) ? 1 : 0;
-}
+int rlg_gru_supported(int hidden) { return rlg::seq_hidden_supported(hidden) ? 1 : 0; }
 
 int rlg_gru_seq_forward(float* gates, const float* w_hh, const float* b_hh, const float* h0,
                         const unsigned char* dones_or_null, float* out, float* hn_all_or_null,
                         float* hprev_or_null, float* h_final_or_null, int num_seqs, int seq_len, int hidden,
                         void* stream) {
-  using namespace rlg;
   if (num_seqs <= 0 || seq_len <= 0) return static_cast<int>(hipErrorInvalidValue);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  switch (hidden) {
-    case 16: return launch_gru_fwd<16>(gates, w_hh, b_hh, h0, dones_or_null, out, hn_all_or_null, hprev_or_null,
-                                       h_final_or_null, num_seqs, seq_len, st);
-    case 32: return launch_gru_fwd<32>(gates, w_hh, b_hh, h0, dones_or_null, out, hn_all_or_null, hprev_or_null,
-                                       h_final_or_null, num_seqs, seq_len, st);
-    case 64: return launch_gru_fwd<64>(gates, w_hh, b_hh, h0, dones_or_null, out, hn_all_or_null, hprev_or_null,
-                                       h_final_or_null, num_seqs, seq_len, st);
-    case 128: return launch_gru_fwd_wide(gates, w_hh, b_hh, h0, dones_or_null, out, hn_all_or_null, hprev_or_null,
-                                         h_final_or_null, num_seqs, seq_len, st);
-    default: return static_cast<int>(hipErrorInvalidValue);
-  }
+  return rlg::launch_seq<rlg::GruFwd>(hidden, num_seqs, seq_len, static_cast<hipStream_t>(stream), gates, w_hh, b_hh,
+                                      h0, dones_or_null, out, hn_all_or_null, hprev_or_null, h_final_or_null);
 }
 
 int rlg_gru_seq_backward(const float* gates, const float* hn_all, const float* hprev,
                          const unsigned char* dones_or_null, const float* w_hh, const float* d_out, float* d_gx,
                          float* d_gh, int num_seqs, int seq_len, int hidden, void* stream) {
-  using namespace rlg;
   if (num_seqs <= 0 || seq_len <= 0) return static_cast<int>(hipErrorInvalidValue);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  switch (hidden) {
-    case 16: return launch_gru_bwd<16>(gates, hn_all, hprev, dones_or_null, w_hh, d_out, d_gx, d_gh, num_seqs,
-                                       seq_len, st);
-    case 32: return launch_gru_bwd<32>(gates, hn_all, hprev, dones_or_null, w_hh, d_out, d_gx, d_gh, num_seqs,
-                                       seq_len, st);
-    case 64: return launch_gru_bwd<64>(gates, hn_all, hprev, dones_or_null, w_hh, d_out, d_gx, d_gh, num_seqs,
-                                       seq_len, st);
-    case 128: return launch_gru_bwd_wide(gates, hn_all, hprev, dones_or_null, w_hh, d_out, d_gx, d_gh, num_seqs,
-                                         seq_len, st);
-    default: return static_cast<int>(hipErrorInvalidValue);
-  }
+  return rlg::launch_seq<rlg::GruBwd>(hidden, num_seqs, seq_len, static_cast<hipStream_t>(stream), gates, hn_all,
+                                      hprev, dones_or_null, w_hh, d_out, d_gx, d_gh);
 }
 
 }  // extern "C"

@@ -12,25 +12,23 @@
 //   * the input projection  x_t W_ih^T + b_ih + b_hh  for every timestep is ONE library GEMM
 //     before the kernel (rows ordered seq*T + t, the dataset's order); the kernel overwrites it
 //     with the activated gates (i, f, g, o - torch.nn.LSTM's gate order), which backward reuses;
-//   * done handling: where dones[seq, t] is set the state ENTERING step t is zeroed
-//     (recurrent.py:45-55 semantics; the mirror is policy.RnnWithDones).
+//   * done handling: the zeroing of the state entering a done step is recurrent.py:45-55's semantics; the mirror is
+//     policy.RnnWithDones.
 // Backward walks the same tile in reverse, emitting d(gates pre-activation) [B, 4H]; the weight
 // gradients are then plain GEMMs over all timesteps at once (dW_ih = dG^T X, dW_hh = dG^T Hprev).
 //
 // The matvec per step is H*4H MACs per sequence (16 K at H = 64): far below MFMA tile sizes per
 // block and latency-bound by the timestep chain, so it runs on VALU FMAs out of LDS.
+//
+// The product scheme (shared with gru.hip), the cell formulas (shared with lstm_wide.hip) and the launch and dispatch
+// helpers are in rnn_seq.hpp.
 
-#include "rlg_device.hpp"
+#include "rnn_seq.hpp"
 
 namespace rlg {
 
-constexpr int kLstmMaxSeqPerBlock = 16;
-constexpr int kLstmThreads = 256;
-
-__device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-template <int H, int kLstmSeqPerBlock>
-__global__ __launch_bounds__(kLstmThreads) void lstm_seq_fwd_kernel(
+template <int H, int SB>
+__global__ __launch_bounds__(kSeqThreads) void lstm_seq_fwd_kernel(
     float* __restrict__ gates,           // [S*T, 4H]  in: x-part + biases, out: activated gates
     const float* __restrict__ w_hh,      // [4H, H]
     const float* __restrict__ h0,        // [S, H]
@@ -43,36 +41,30 @@ __global__ __launch_bounds__(kLstmThreads) void lstm_seq_fwd_kernel(
     float* __restrict__ cT,              // [S, H] final c (nullptr)
     int S, int T) {
   constexpr int G = 4 * H;
-  constexpr int kGroups = kLstmThreads / H;            // sequence groups per block
-  constexpr int R = kLstmSeqPerBlock / kGroups;        // sequences per thread
-  static_assert(kLstmThreads % H == 0 && kLstmSeqPerBlock % kGroups == 0, "tile shape");
+  constexpr int kGroups = kSeqThreads / H;              // sequence groups per block
+  constexpr int R = SB / kGroups;                       // sequences per thread
+  static_assert(kSeqThreads % H == 0 && SB % kGroups == 0, "tile shape");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* wT = smem;                                     // [H][4H]: wT[k][r] = w_hh[r][k]
   float* hbuf = smem + H * G;                           // [2][SB][H]
   const int tid = threadIdx.x;
   const int j = tid % H;
   const int grp = tid / H;
-  for (int idx = tid; idx < G * H; idx += kLstmThreads) {
-    const int k = idx / G, r = idx - k * G;             // LDS write contiguous, global read strided (L2)
-    wT[idx] = w_hh[r * H + k];
-  }
-  const int seq0 = blockIdx.x * kLstmSeqPerBlock;
+  narrow_stage_w_transposed<4, H>(wT, w_hh);
   int seq[R];
   bool live[R];
   float c[R];
 #pragma unroll
   for (int r = 0; r < R; ++r) {
-    const int s = seq0 + grp * R + r;
-    live[r] = s < S;
-    seq[r] = live[r] ? s : S - 1;
+    tile_slot(blockIdx.x * SB + grp * R + r, S, seq[r], live[r]);
     c[r] = c0[static_cast<long long>(seq[r]) * H + j];
     hbuf[(grp * R + r) * H + j] = h0[static_cast<long long>(seq[r]) * H + j];
   }
   __syncthreads();
 
   for (int t = 0; t < T; ++t) {
-    const float* hcur = hbuf + (t & 1) * kLstmSeqPerBlock * H;
-    float* hnext = hbuf + ((t + 1) & 1) * kLstmSeqPerBlock * H;
+    const float* hcur = hbuf + (t & 1) * SB * H;
+    float* hnext = hbuf + ((t + 1) & 1) * SB * H;
     float acc[4][R];
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -97,24 +89,20 @@ __global__ __launch_bounds__(kLstmThreads) void lstm_seq_fwd_kernel(
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       const long long row = static_cast<long long>(seq[r]) * T + t;
-      const float keep = (dones && dones[row]) ? 0.0f : 1.0f;
+      const float keep = step_keep(dones, row);
       float* grow = gates + row * G;
-      const float gi = sigmoid_f(grow[0 * H + j] + keep * acc[0][r]);
-      const float gf = sigmoid_f(grow[1 * H + j] + keep * acc[1][r]);
-      const float gg = tanhf(grow[2 * H + j] + keep * acc[2][r]);
-      const float go = sigmoid_f(grow[3 * H + j] + keep * acc[3][r]);
-      const float cn = gf * (c[r] * keep) + gi * gg;
-      const float hn = go * tanhf(cn);
+      const float a[4] = {acc[0][r], acc[1][r], acc[2][r], acc[3][r]};
+      float g[4];
+      const float hn = lstm_fwd_point(grow + j, H, a, keep, c[r], g);
       const float hp = hcur[(grp * R + r) * H + j] * keep;
-      c[r] = cn;
       hnext[(grp * R + r) * H + j] = hn;
       if (live[r]) {
-        grow[0 * H + j] = gi;
-        grow[1 * H + j] = gf;
-        grow[2 * H + j] = gg;
-        grow[3 * H + j] = go;
+        grow[0 * H + j] = g[0];
+        grow[1 * H + j] = g[1];
+        grow[2 * H + j] = g[2];
+        grow[3 * H + j] = g[3];
         out[row * H + j] = hn;
-        if (c_all) c_all[row * H + j] = cn;
+        if (c_all) c_all[row * H + j] = c[r];
         if (hprev) hprev[row * H + j] = hp;
       }
     }
@@ -123,13 +111,13 @@ __global__ __launch_bounds__(kLstmThreads) void lstm_seq_fwd_kernel(
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     if (!live[r]) continue;
-    if (hT) hT[static_cast<long long>(seq[r]) * H + j] = hbuf[(T & 1) * kLstmSeqPerBlock * H + (grp * R + r) * H + j];
+    if (hT) hT[static_cast<long long>(seq[r]) * H + j] = hbuf[(T & 1) * SB * H + (grp * R + r) * H + j];
     if (cT) cT[static_cast<long long>(seq[r]) * H + j] = c[r];
   }
 }
 
-template <int H, int kLstmSeqPerBlock>
-__global__ __launch_bounds__(kLstmThreads) void lstm_seq_bwd_kernel(
+template <int H, int SB>
+__global__ __launch_bounds__(kSeqThreads) void lstm_seq_bwd_kernel(
     const float* __restrict__ gates,     // [S*T, 4H] activated gates of the forward pass
     const float* __restrict__ c_all,     // [S*T, H]
     const float* __restrict__ c0,        // [S, H]
@@ -139,24 +127,21 @@ __global__ __launch_bounds__(kLstmThreads) void lstm_seq_bwd_kernel(
     float* __restrict__ d_gates,         // [S*T, 4H] d loss / d gate pre-activations
     int S, int T) {
   constexpr int G = 4 * H;
-  constexpr int kGroups = kLstmThreads / H;
-  constexpr int R = kLstmSeqPerBlock / kGroups;
+  constexpr int kGroups = kSeqThreads / H;
+  constexpr int R = SB / kGroups;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* w = smem;                                      // [4H][H] as stored
   float* dgb = smem + G * H;                            // [SB][4H]
   const int tid = threadIdx.x;
   const int j = tid % H;
   const int grp = tid / H;
-  for (int idx = tid; idx < G * H; idx += kLstmThreads) w[idx] = w_hh[idx];
-  const int seq0 = blockIdx.x * kLstmSeqPerBlock;
+  narrow_stage_w<4, H>(w, w_hh);
   int seq[R];
   bool live[R];
   float dh_next[R], dc_next[R];
 #pragma unroll
   for (int r = 0; r < R; ++r) {
-    const int s = seq0 + grp * R + r;
-    live[r] = s < S;
-    seq[r] = live[r] ? s : S - 1;
+    tile_slot(blockIdx.x * SB + grp * R + r, S, seq[r], live[r]);
     dh_next[r] = 0.0f;
     dc_next[r] = 0.0f;
   }
@@ -167,122 +152,33 @@ __global__ __launch_bounds__(kLstmThreads) void lstm_seq_bwd_kernel(
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       const long long row = static_cast<long long>(seq[r]) * T + t;
-      keep[r] = (dones && dones[row]) ? 0.0f : 1.0f;
+      keep[r] = step_keep(dones, row);
       const float* grow = gates + row * G;
-      const float gi = grow[0 * H + j], gf = grow[1 * H + j], gg = grow[2 * H + j], go = grow[3 * H + j];
+      const float g[4] = {grow[0 * H + j], grow[1 * H + j], grow[2 * H + j], grow[3 * H + j]};
       const float ct = c_all[row * H + j];
       const float c_in = (t > 0 ? c_all[(row - 1) * H + j] : c0[static_cast<long long>(seq[r]) * H + j]) * keep[r];
       const float dh = d_out[row * H + j] + dh_next[r];
-      const float tc = tanhf(ct);
-      const float d_o = dh * tc;
-      const float dc = dc_next[r] + (dh * go) * (1.0f - tc * tc);
-      const float dgi = (dc * gg) * (gi * (1.0f - gi));
-      const float dgf = (dc * c_in) * (gf * (1.0f - gf));
-      const float dgg = (dc * gi) * (1.0f - gg * gg);
-      const float dgo = d_o * (go * (1.0f - go));
-      dc_next[r] = (dc * gf) * keep[r];
+      float dg[4];
+      lstm_bwd_point(g, ct, c_in, dh, keep[r], dc_next[r], dg);
       float* db = dgb + (grp * R + r) * G;
-      db[0 * H + j] = dgi;
-      db[1 * H + j] = dgf;
-      db[2 * H + j] = dgg;
-      db[3 * H + j] = dgo;
+      db[0 * H + j] = dg[0];
+      db[1 * H + j] = dg[1];
+      db[2 * H + j] = dg[2];
+      db[3 * H + j] = dg[3];
       if (live[r]) {
         float* drow = d_gates + row * G;
-        drow[0 * H + j] = dgi;
-        drow[1 * H + j] = dgf;
-        drow[2 * H + j] = dgg;
-        drow[3 * H + j] = dgo;
+        drow[0 * H + j] = dg[0];
+        drow[1 * H + j] = dg[1];
+        drow[2 * H + j] = dg[2];
+        drow[3 * H + j] = dg[3];
       }
     }
     __syncthreads();
     float acc[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = 0.0f;
-#pragma unroll 4
-    for (int row = 0; row < G; ++row) {
-      const float wv = w[row * H + j];
-#pragma unroll
-      for (int r = 0; r < R; ++r) acc[r] = __builtin_fmaf(dgb[(grp * R + r) * G + row], wv, acc[r]);
-    }
+    narrow_bwd_product<4, H, R>(acc, w, dgb, j, grp);
 #pragma unroll
     for (int r = 0; r < R; ++r) dh_next[r] = acc[r] * keep[r];
     __syncthreads();
-  }
-}
-
-// Sequences per block: 16 (4 per thread: every W_hh value read from LDS feeds 4 FMAs) when that still
-// gives >= 256 blocks, otherwise fewer, so that a 1,024-sequence minibatch uses the whole chip instead
-// of 64 CUs.
-static int lstm_seq_per_block(int S, int H) {
-  const int min_sb = kLstmThreads / H;                 // one sequence per thread group at least
-  int sb = kLstmMaxSeqPerBlock;
-  while (sb > min_sb && (S + sb - 1) / sb < 256) sb >>= 1;
-  return sb;
-}
-
-template <int H, int SB>
-static int launch_lstm_fwd_sb(float* gates, const float* w_hh, const float* h0, const float* c0,
-                              const uint8_t* dones, float* out, float* c_all, float* hprev, float* hT,
-                              float* cT, int S, int T, hipStream_t st) {
-  if constexpr (SB < kLstmThreads / H) {
-    return static_cast<int>(hipErrorInvalidValue);
-  } else {
-    const size_t shm = (static_cast<size_t>(4) * H * H + 2 * SB * H) * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_seq_fwd_kernel<H, SB>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(shm));
-      if (e != hipSuccess) return static_cast<int>(e);
-      attr_set = true;
-    }
-    const int grid = (S + SB - 1) / SB;
-    hipLaunchKernelGGL((lstm_seq_fwd_kernel<H, SB>), dim3(grid), dim3(kLstmThreads), shm, st, gates, w_hh, h0,
-                       c0, dones, out, c_all, hprev, hT, cT, S, T);
-    RLG_RETURN_LAUNCH_STATUS();
-  }
-}
-
-template <int H>
-static int launch_lstm_fwd(float* gates, const float* w_hh, const float* h0, const float* c0,
-                           const uint8_t* dones, float* out, float* c_all, float* hprev, float* hT,
-                           float* cT, int S, int T, hipStream_t st) {
-  switch (lstm_seq_per_block(S, H)) {
-    case 16: return launch_lstm_fwd_sb<H, 16>(gates, w_hh, h0, c0, dones, out, c_all, hprev, hT, cT, S, T, st);
-    case 8: return launch_lstm_fwd_sb<H, 8>(gates, w_hh, h0, c0, dones, out, c_all, hprev, hT, cT, S, T, st);
-    default: return launch_lstm_fwd_sb<H, 4>(gates, w_hh, h0, c0, dones, out, c_all, hprev, hT, cT, S, T, st);
-  }
-}
-
-template <int H, int SB>
-static int launch_lstm_bwd_sb(const float* gates, const float* c_all, const float* c0, const uint8_t* dones,
-                              const float* w_hh, const float* d_out, float* d_gates, int S, int T,
-                              hipStream_t st) {
-  if constexpr (SB < kLstmThreads / H) {
-    return static_cast<int>(hipErrorInvalidValue);
-  } else {
-    const size_t shm = (static_cast<size_t>(4) * H * H + SB * 4 * H) * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_seq_bwd_kernel<H, SB>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(shm));
-      if (e != hipSuccess) return static_cast<int>(e);
-      attr_set = true;
-    }
-    const int grid = (S + SB - 1) / SB;
-    hipLaunchKernelGGL((lstm_seq_bwd_kernel<H, SB>), dim3(grid), dim3(kLstmThreads), shm, st, gates, c_all, c0,
-                       dones, w_hh, d_out, d_gates, S, T);
-    RLG_RETURN_LAUNCH_STATUS();
-  }
-}
-
-template <int H>
-static int launch_lstm_bwd(const float* gates, const float* c_all, const float* c0, const uint8_t* dones,
-                           const float* w_hh, const float* d_out, float* d_gates, int S, int T,
-                           hipStream_t st) {
-  switch (lstm_seq_per_block(S, H)) {
-    case 16: return launch_lstm_bwd_sb<H, 16>(gates, c_all, c0, dones, w_hh, d_out, d_gates, S, T, st);
-    case 8: return launch_lstm_bwd_sb<H, 8>(gates, c_all, c0, dones, w_hh, d_out, d_gates, S, T, st);
-    default: return launch_lstm_bwd_sb<H, 4>(gates, c_all, c0, dones, w_hh, d_out, d_gates, S, T, st);
   }
 }
 
@@ -292,47 +188,43 @@ int launch_lstm_fwd_wide(float* gates, const float* w_hh, const float* h0, const
 int launch_lstm_bwd_wide(const float* gates, const float* c_all, const float* c0, const uint8_t* dones,
                          const float* w_hh, const float* d_out, float* d_gates, int S, int T, hipStream_t st);
 
+// kernel families for rnn_seq.hpp's launch_seq
+struct LstmFwd {
+  template <int H, int SB>
+  static constexpr auto kernel = lstm_seq_fwd_kernel<H, SB>;
+  static constexpr size_t lds_floats(int H, int SB) { return static_cast<size_t>(4) * H * H + 2 * SB * H; }
+  static constexpr auto wide = launch_lstm_fwd_wide;
+};
+
+struct LstmBwd {
+  template <int H, int SB>
+  static constexpr auto kernel = lstm_seq_bwd_kernel<H, SB>;
+  static constexpr size_t lds_floats(int H, int SB) { return static_cast<size_t>(4) * H * H + SB * 4 * H; }
+  static constexpr auto wide = launch_lstm_bwd_wide;
+};
+
 }  // namespace rlg
 
 extern "C" {
 
-int rlg_lstm_supported(int hidden) {
-  return (hidden == 16 || hidden == 32 || hidden == 64 || hidden == 128) ? 1 : 0;
-}
+int rlg_lstm_supported(int hidden) { return rlg::seq_hidden_supported(hidden) ? 1 : 0; }
 
 int rlg_lstm_seq_forward(float* gates, const float* w_hh, const float* h0, const float* c0,
                          const unsigned char* dones_or_null, float* out, float* c_all_or_null,
                          float* hprev_or_null, float* h_final_or_null, float* c_final_or_null,
                          int num_seqs, int seq_len, int hidden, void* stream) {
-  using namespace rlg;
   if (num_seqs <= 0 || seq_len <= 0) return static_cast<int>(hipErrorInvalidValue);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  switch (hidden) {
-    case 16: return launch_lstm_fwd<16>(gates, w_hh, h0, c0, dones_or_null, out, c_all_or_null, hprev_or_null,
-                                        h_final_or_null, c_final_or_null, num_seqs, seq_len, st);
-    case 32: return launch_lstm_fwd<32>(gates, w_hh, h0, c0, dones_or_null, out, c_all_or_null, hprev_or_null,
-                                        h_final_or_null, c_final_or_null, num_seqs, seq_len, st);
-    case 64: return launch_lstm_fwd<64>(gates, w_hh, h0, c0, dones_or_null, out, c_all_or_null, hprev_or_null,
-                                        h_final_or_null, c_final_or_null, num_seqs, seq_len, st);
-    case 128: return launch_lstm_fwd_wide(gates, w_hh, h0, c0, dones_or_null, out, c_all_or_null, hprev_or_null,
-                                          h_final_or_null, c_final_or_null, num_seqs, seq_len, st);
-    default: return static_cast<int>(hipErrorInvalidValue);
-  }
+  return rlg::launch_seq<rlg::LstmFwd>(hidden, num_seqs, seq_len, static_cast<hipStream_t>(stream), gates, w_hh, h0,
+                                       c0, dones_or_null, out, c_all_or_null, hprev_or_null, h_final_or_null,
+                                       c_final_or_null);
 }
 
 int rlg_lstm_seq_backward(const float* gates, const float* c_all, const float* c0,
                           const unsigned char* dones_or_null, const float* w_hh, const float* d_out,
                           float* d_gates, int num_seqs, int seq_len, int hidden, void* stream) {
-  using namespace rlg;
   if (num_seqs <= 0 || seq_len <= 0) return static_cast<int>(hipErrorInvalidValue);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  switch (hidden) {
-    case 16: return launch_lstm_bwd<16>(gates, c_all, c0, dones_or_null, w_hh, d_out, d_gates, num_seqs, seq_len, st);
-    case 32: return launch_lstm_bwd<32>(gates, c_all, c0, dones_or_null, w_hh, d_out, d_gates, num_seqs, seq_len, st);
-    case 64: return launch_lstm_bwd<64>(gates, c_all, c0, dones_or_null, w_hh, d_out, d_gates, num_seqs, seq_len, st);
-    case 128: return launch_lstm_bwd_wide(gates, c_all, c0, dones_or_null, w_hh, d_out, d_gates, num_seqs, seq_len, st);
-    default: return static_cast<int>(hipErrorInvalidValue);
-  }
+  return rlg::launch_seq<rlg::LstmBwd>(hidden, num_seqs, seq_len, static_cast<hipStream_t>(stream), gates, c_all, c0,
+                                       dones_or_null, w_hh, d_out, d_gates);
 }
 
 }  // extern "C"
