@@ -570,7 +570,7 @@ int rlg_mlp_chain_debug_stamps(long long* buffer);
 int rlg_mlp_chain_gradient_maxima(float* entries, int stride);
 int rlg_mlp_dw_gradient_maxima(const float* entries, int stride, int rows_per_entry, const int* dz_slot, const float* x_scale,
                                int num_layers);
-/* plane products per fp32 product of the split-product chain kernels of this build: 3 (fp16 planes) or 6 (bf16 planes) */
+/* plane products per fp32 product of the split-product chain kernels: 3 (two fp16 planes per operand) */
 int rlg_mlp_chain_split_products(void);
 int rlg_mlp_chain_time_next(void* ev_start, void* ev_stop);
 
@@ -647,7 +647,7 @@ int rlg_mlp_chain_step(int num_layers, const float* const* weights, const float*
  * padding instead of out-of-range selects; the backward's fragments are the transposed matrices (one 16-byte load per lane and chunk where the row-major matrix
  * needs four strided dword loads).  Same maths as rlg_mlp_chain_forward / rlg_mlp_chain_backward in their 16-row form
  * (network_builder.py:447-512 and autograd's backward of it); round 6: three fp16 plane products per fp32 product - results
- * within the split kernels' tolerance of the pipelined exact-product kernels (bit-identical to them in a -DRLG_LEAN_F16=0 build).
+ * within the split kernels' tolerance of the pipelined exact-product kernels.
  *   rlg_mlp_chain_frags_bytes: size of one direction's fragment buffer (0 forward, 1 backward), < 0: shape
  *     outside the format.
  *   rlg_mlp_chain_pack_frags / _both: weights -> fragments, one launch (the bias pointers are not read); to be repeated behind every change of
@@ -683,8 +683,8 @@ int rlg_mlp_chain_backward_lean(int num_layers, const int* in_features, const in
                                 const rlg_ppo_loss_desc* ppo_loss, long long rows, const void* frags, void* stream);
 
 /* Split-product form of the chain (csrc/mlp_chain_bx.hip): every fp32 product as three exact fp16 plane products on
- * v_mfma_f32_16x16x32_f16 (round 6, csrc/split_f16.hpp; six bf16 plane products in a -DRLG_BX_F16=0 build: results within
- * 3 * 2^-24 |x||w| per product of the exact-product kernels).  The weights
+ * v_mfma_f32_16x16x32_f16 (round 6, csrc/split_f16.hpp: results within 3 * 2^-22 |x||w| per product of the exact-product
+ * kernels in the worst case, ~2^-24 rms).  The weights
  * are split ONCE per optimizer step into plane fragments; the launch that is given them (weight_planes_or_null of
  * rlg_mlp_chain_backward, direction 1) uses the split kernel when rlg_mlp_chain_bx_supported says so and the
  * activation arrays are 16-byte aligned, else the exact-product kernel.  Same autograd nodes as above

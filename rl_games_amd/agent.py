@@ -1806,7 +1806,7 @@ class A2CAgent:
         from it - never a finite wrong value, but the reason deserves a sentence (a warning, once: the reference would train on
         with NaNs as well).  One host read per epoch."""
         chain = getattr(self._engine, 'chain', None) if self._engine is not None else None
-        if chain is None or ops.chain_split_form()[1] != 'fp16' or self._mb_index == 0:
+        if chain is None or self._mb_index == 0:
             return
         n = min(self._mb_index, self._mb_scalars.shape[0])
         if not getattr(self, '_split_range_warned', False) and \

@@ -69,7 +69,7 @@ __device__ __forceinline__ void chain_units(rsrc_t wr, int I, int K, int ld, con
   const unsigned astep = kTransposedA ? static_cast<unsigned>(16 * ld * 4) : 64u;
   const int bstride = G * 256;
   auto a_base = [&](int j, int f) -> unsigned {
-    if (j >= nunits || (kAbl & 64)) return kOob;
+    if (j >= nunits) return kOob;
     const int i = (ob_of(j) + f) * 16 + (lane & 15);
     if (i >= I) return kOob;
     const unsigned first = static_cast<unsigned>(kc_begin) * astep;
@@ -297,6 +297,72 @@ __device__ __forceinline__ void chain_units(rsrc_t wr, int I, int K, int ld, con
 // ------------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------------
+// Forward prologue of a workgroup of W waves that owns 16 * G rows from row0 on: observation tile -> LDS (fragment
+// layout) in tile_a, normalised on the way (RunningMeanStd state folded first when a.rms_batch is given; the
+// mean / denominator scratch lives in tile_b), normalised observations written to a.xn.  Ends with a barrier.
+template <int G, int W>
+__device__ __forceinline__ void chain_fwd_prologue(const ChainArgs& a, float* tile_a, float* tile_b, long long row0, int lane,
+                                                   int wave, int& stamp) {
+  const int in0 = a.layer[0].in;
+  const int in0p = (in0 + 3) & ~3;
+  const bool norm = a.rms_mean != nullptr;
+  const int KC0 = (in0 + 15) >> 4;
+  const int nfrag = KC0 * G;
+  const bool xv = vec4_ok(a.x, a.ldx);
+  const bool xnv = a.xn != nullptr && vec4_ok(a.xn, in0);
+  // kProBatch fragments per wave at a time: every load is issued before the first one is used (a
+  // rolled loop would pay one HBM round trip per fragment), and the first batch is requested
+  // BEFORE the normaliser statistics are prepared, so both latencies overlap.
+  constexpr int kProBatch = 8;
+  f32x4 xin[kProBatch];
+  auto load_frags = [&](int u0) {
+#pragma unroll
+    for (int k = 0; k < kProBatch; ++k) {
+      const int u = u0 + k * W;
+      const int c = u / G;
+      const int g = u - c * G;
+      const long long row = row0 + g * 16 + (lane & 15);
+      xin[k] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+      if (u < nfrag && row < a.rows) xin[k] = load_row4(a.x, a.ldx, row, c * 16 + 4 * (lane >> 4), in0, xv);
+    }
+  };
+  auto put_frags = [&](int u0) {
+#pragma unroll
+    for (int k = 0; k < kProBatch; ++k) {
+      const int u = u0 + k * W;
+      if (u < nfrag) {
+        const int c = u / G;
+        const int g = u - c * G;
+        const long long row = row0 + g * 16 + (lane & 15);
+        const int f = c * 16 + 4 * (lane >> 4);
+        f32x4 v = xin[k];
+        if (row < a.rows) {
+          if (norm) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              if (f + e < in0) v[e] = clamp_nan((v[e] - tile_b[f + e]) / tile_b[in0p + f + e], -5.0f, 5.0f);
+            }
+          }
+          if (a.xn) store_row4(a.xn, in0, row, f, in0, v, xnv);
+        }
+        *reinterpret_cast<f32x4*>(tile_a + (u * 64 + lane) * 4) = v;
+      }
+    }
+  };
+  load_frags(wave);
+  if (norm) {
+    chain_norm_stats<W>(a, tile_b, in0, in0p);
+    __syncthreads();
+  }
+  put_frags(wave);
+  for (int u0 = wave + W * kProBatch; u0 < nfrag; u0 += W * kProBatch) {
+    load_frags(u0);
+    put_frags(u0);
+  }
+  chain_stamp(a.dbg, wave, stamp);
+  __syncthreads();
+}
+
 template <int G, int HACT, int W>
 __global__ __launch_bounds__(64 * W) void mlp_chain_fwd_kernel(ChainArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -350,11 +416,9 @@ __global__ __launch_bounds__(64 * W) void mlp_chain_fwd_kernel(ChainArgs a) {
     };
     auto epilogue = [&](int ob, int g, const f32x4& accv, const f32x4& bias) {
       const int f = ob * 16 + 4 * (lane >> 4);
-      if ((kAbl & 4) && n_rows >= 0) return;
-      const f32x4 v = (kAbl & 1) ? accv : chain_act4<HACT>(accv + bias, l_act);
+      const f32x4 v = chain_act4<HACT>(accv + bias, l_act);
       if (!last) *reinterpret_cast<f32x4*>(tout + ((ob * G + g) * 64 + lane) * 4) = v;
       const long long row = row0 + g * 16 + (lane & 15);
-      if ((kAbl & 2) && !last) return;
       if (h_fast) {
         if (row < n_rows && f < l_out) *(glob_t<f32x4>*)as_global(l_h + row * l_ldh + f) = v;
       } else if (h_on && row < n_rows) {
@@ -388,7 +452,7 @@ __global__ __launch_bounds__(64 * W) void mlp_chain_fwd_kernel(ChainArgs a) {
     chain_stamp(a.dbg, wave, stamp);
     // remainder blocks: dealt out per (block, row group) so that every wave gets the same share
     const int rem_first = full * W;
-    const int rem_units = (kAbl & 8) ? 0 : (NOB - rem_first) * G;
+    const int rem_units = (NOB - rem_first) * G;
     // Fewer (block, row group) units than waves (the one remainder block of the 400- and 200-wide layers):
     // the idle waves take a share of the reduction instead - `ksplit` waves per unit, each over a part
     // of the k-chunks, partial fragments combined through LDS in a fixed order by the unit's first wave.
@@ -424,7 +488,7 @@ __global__ __launch_bounds__(64 * W) void mlp_chain_fwd_kernel(ChainArgs a) {
         });
     }
     chain_stamp(a.dbg, wave, stamp);
-    if (!(kAbl & 16)) __syncthreads();
+    __syncthreads();
     chain_stamp(a.dbg, wave, stamp);
     float* t = tin;
     tin = tout;
@@ -435,8 +499,8 @@ __global__ __launch_bounds__(64 * W) void mlp_chain_fwd_kernel(ChainArgs a) {
 // ------------------------------------------------------------------------------------------------
 // Pipelined forward for large minibatches: 64-row workgroups (G = 4), 4 waves = one per SIMD.
 //
-// What the ablation builds of the unit-structured kernel above showed (tools/ablate_chain.sh,
-// profiles/r3_chain_ablation.txt; 32,768 rows): of its 131 us, 20 are epilogues that no MFMA overlaps at one
+// What timing-only ablation builds of the unit-structured kernel above showed in round 3
+// (profiles/r3_chain_ablation_unit_kernels.txt; 32,768 rows): of its 131 us, 20 are epilogues that no MFMA overlaps at one
 // wave per SIMD, 10 the inefficiency of the remainder units (a cold weight fetch and a barrier behind a handful of
 // MFMAs each), 12 weight-fetch latency at the head of every chain_units call.  This kernel keeps ONE stream of
 // chunk steps going per wave and layer instead:
@@ -500,7 +564,7 @@ __device__ __forceinline__ void chain_fwd_pipe_body(const ChainArgs& a, float* l
   // per-lane byte offset of chunk 0 of block ob's weight rows; out-of-range rows read zero
   auto a_base = [&](const PipeGeo& g, int ob) -> unsigned {
     const int i = ob * 16 + (lane & 15);
-    return (!(kAbl & 64) && g.nunits > 0 && i < g.out) ? g.w_off + static_cast<unsigned>((i * g.in + q4) * 4) : kOob;
+    return (g.nunits > 0 && i < g.out) ? g.w_off + static_cast<unsigned>((i * g.in + q4) * 4) : kOob;
   };
   // ---- the first unit's weights are requested before anything else
   PipeGeo cur = geo(0);
@@ -551,7 +615,6 @@ __device__ __forceinline__ void chain_fwd_pipe_body(const ChainArgs& a, float* l
     // B fragments of chunk c: all G row groups, or the one group g1 of a remainder unit
     auto load_b = [&](auto ng_tag, f32x4 (&bv)[4], int c, int g1) {
       constexpr int NG = decltype(ng_tag)::value;
-      if (kAbl & 128) return;
       if constexpr (NG == G) {
 #pragma unroll
         for (int g = 0; g < G; ++g) bv[g] = *reinterpret_cast<const f32x4*>(bp + (c * G + g) * 256);
@@ -565,10 +628,8 @@ __device__ __forceinline__ void chain_fwd_pipe_body(const ChainArgs& a, float* l
       constexpr int U = decltype(u_tag)::value;
       const int g = pend_ng == G ? U : pend_g;
       const int f = pend_ob * 16 + q4;
-      if ((kAbl & 4) && n_rows >= 0) return;
-      const f32x4 v = (kAbl & 1) ? accP[U] : chain_act4<HACT>(accP[U] + biasP, l_act);
+      const f32x4 v = chain_act4<HACT>(accP[U] + biasP, l_act);
       if (!last) *reinterpret_cast<f32x4*>(tout + ((pend_ob * G + g) * 64 + lane) * 4) = v;
-      if ((kAbl & 2) && !last) return;
       if (h_on) {
         const unsigned off = h_lane + static_cast<unsigned>(g) * h_group + static_cast<unsigned>(pend_ob) * 64u;
         if (h_fast) {
@@ -714,7 +775,7 @@ __device__ __forceinline__ void chain_fwd_pipe_body(const ChainArgs& a, float* l
     }
     chain_stamp(a.dbg, wave, stamp);                                 // per layer: whole units done
     // remainder blocks, one row group at a time: every wave the same number of MFMAs (+- one unit)
-    for (int r = 0; r < ((kAbl & 8) ? 0 : cur.nrem); ++r) {
+    for (int r = 0; r < cur.nrem; ++r) {
       const int idx = cur.full + r;
       const bool more = r + 1 < cur.nrem;
       const unsigned base_nxt = more ? a_base(cur, unit_ob(cur, idx + 1)) : a_base(nxt, unit_ob(nxt, 0));
@@ -734,7 +795,7 @@ __device__ __forceinline__ void chain_fwd_pipe_body(const ChainArgs& a, float* l
       }
     }
     chain_stamp(a.dbg, wave, stamp);                                 // last epilogue flushed
-    if (!(kAbl & 16)) __syncthreads();
+    __syncthreads();
     chain_stamp(a.dbg, wave, stamp);                                 // behind the barrier
     float* t = tin;
     tin = tout;
@@ -820,11 +881,9 @@ __global__ __launch_bounds__(64 * W) void mlp_chain_bwd_kernel(ChainArgs a, Loss
     auto epilogue = [&](int ob, int g, int slot, bool to_lds, const f32x4& accv, const f32x4& hval) -> f32x4 {
       const int f = ob * 16 + 4 * (lane >> 4);
       const long long row = row0 + g * 16 + (lane & 15);
-      if ((kAbl & 4) && n_rows >= 0) return accv;
-      f32x4 v = (kAbl & 1) ? accv : chain_act_grad4(accv, hval, p_act);
+      f32x4 v = chain_act_grad4(accv, hval, p_act);
       if (row >= n_rows) v = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
       if (to_lds) *reinterpret_cast<f32x4*>(tout + (slot * 64 + lane) * 4) = v;
-      if (kAbl & 2) return v;
       if (fast) {
         if (row < n_rows && f < width) *(glob_t<f32x4>*)as_global(p_dz + row * p_lddz + f) = v;
       } else if (row < n_rows) {
@@ -833,7 +892,6 @@ __global__ __launch_bounds__(64 * W) void mlp_chain_bwd_kernel(ChainArgs a, Loss
       return v;
     };
     auto load_h = [&](int ob, int g) -> f32x4 {
-      if (kAbl & 4) return f32x4{0.0f, 0.0f, 0.0f, 0.0f};
       const int f = ob * 16 + 4 * (lane >> 4);
       const long long row = row0 + g * 16 + (lane & 15);
       if (fast) {
@@ -900,7 +958,7 @@ __global__ __launch_bounds__(64 * W) void mlp_chain_bwd_kernel(ChainArgs a, Loss
     // feeds the next step, else in the first slots) and, after the barrier, one wave per block adds
     // the G groups in order.
     const int rem_first = full * W;
-    const int rem_blocks = (kAbl & 8) ? 0 : NOB - rem_first;
+    const int rem_blocks = NOB - rem_first;
     const int rem_units = rem_blocks * G;
     const int my_rem = (rem_units > wave) ? (rem_units - wave + W - 1) / W : 0;
     chain_units<1, 1, true>(
@@ -915,7 +973,7 @@ __global__ __launch_bounds__(64 * W) void mlp_chain_bwd_kernel(ChainArgs a, Loss
           const int ob = rem_first + u / G, g = u % G;
           epilogue(ob, g, keep_tile ? ob * G + g : u, true, acc[0][0], hval[0][0]);
         });
-    if (!(kAbl & 16)) __syncthreads();
+    __syncthreads();
     if (bpart != nullptr) {
       for (int rb = wave; rb < rem_blocks; rb += W) {
         const int slot0 = keep_tile ? (rem_first + rb) * G : rb * G;
@@ -1229,25 +1287,6 @@ __global__ __launch_bounds__(64 * W) void mlp_chain_step_pipe_kernel(ChainArgs f
 }
 
 
-static bool chain_pipe_enabled() {
-  static const bool on = [] {
-    const char* e = std::getenv("RLG_CHAIN_PIPE");       // tools: A/B against the unit-structured kernels
-    return !(e && std::atoi(e) == 0);
-  }();
-  return on;
-}
-
-// round 4: the pipelined forward for 16-row workgroups as well (minibatches < 16,384 rows: a data-parallel rank's
-// shapes) - the unit-structured kernel pays a cold weight fetch at the head of each of its 8 chain_units calls there
-// (profiles/r4_rank_chain_phases.txt: 58k cycles per tile for 21k of MFMA issue)
-static bool chain_pipe1_enabled() {
-  static const bool on = [] {
-    const char* e = std::getenv("RLG_CHAIN_PIPE1");      // tools: A/B against the unit-structured 16-row kernels
-    return !(e && std::atoi(e) == 0);
-  }();
-  return on;
-}
-
 static bool chain_bx_enabled() {
   static const bool on = [] {
     const char* e = std::getenv("RLG_CHAIN_BX");         // tools: A/B against the exact-f32-product kernels
@@ -1260,23 +1299,12 @@ static bool chain_bx_enabled() {
 // (activations kept).  Launches of at least chain_bx_min_rows(kind) rows run the 64-row split-product kernels: 16,384 for
 // inference forwards, 8,192 for the training pair (round 6: a rank of 4's 8,192-row update is faster on the fp16 kernels on
 // half the CUs than on the 16-row exact-product kernels - 46.1 -> 43.8 ms per rank epoch - while 8,192-row ROLLOUT forwards
-// are not: a rank of 8 went 31.0 -> 32.7 ms with them).  RLG_CHAIN_BX_MIN_ROWS: one threshold for all kinds (tools, A/B).
-static long long chain_bx_min_rows(int kind) {
-  static const long long forced = [] {
-    const char* e = std::getenv("RLG_CHAIN_BX_MIN_ROWS");
-    return (e && std::atoll(e) > 0) ? std::atoll(e) : 0LL;
-  }();
-  if (forced > 0) return forced;
-  return kind == 0 ? 16384LL : 8192LL;
-}
+// are not: a rank of 8 went 31.0 -> 32.7 ms with them).
+static long long chain_bx_min_rows(int kind) { return kind == 0 ? 16384LL : 8192LL; }
 
 static bool chain_bx_fwd_wanted(long long rows, int groups, bool training) {
-  static const bool on = [] {
-    const char* e = std::getenv("RLG_CHAIN_BX_FWD");     // tools: A/B against the exact-product forward kernels
-    return !(e && std::atoi(e) == 0);
-  }();
   // (2: what pick_groups resolves the automatic choice to at these sizes - the callers pass the resolved value)
-  return on && chain_bx_enabled() && rows >= chain_bx_min_rows(training ? 2 : 0) && (groups == 0 || groups == 2 || groups == 4);
+  return chain_bx_enabled() && rows >= chain_bx_min_rows(training ? 2 : 0) && (groups == 0 || groups == 2 || groups == 4);
 }
 
 // Row groups per workgroup when the caller does not ask for one.  Measured on MI355X (humanoid MLP,
@@ -1285,12 +1313,6 @@ static bool chain_bx_fwd_wanted(long long rows, int groups, bool training) {
 // and unit-boundary stalls of the first; below 16,384 rows G = 1 keeps every CU busy.
 static int pick_groups(long long rows, int requested, int direction = 0) {
   if (requested == 1 || requested == 2 || requested == 4) return requested;
-  {
-    static const int forced_fwd = [] { const char* e = std::getenv("RLG_CHAIN_FWD_GROUPS"); return e ? std::atoi(e) : 0; }();
-    static const int forced_bwd = [] { const char* e = std::getenv("RLG_CHAIN_BWD_GROUPS"); return e ? std::atoi(e) : 0; }();
-    const int f = direction == 1 ? forced_bwd : forced_fwd;       // tools: A/B measurements inside bench.py
-    if (rows >= chain_bx_min_rows(direction) && (f == 1 || f == 2 || f == 4)) return f;
-  }
   // backward: its LDS footprint is half the forward's, so G = 4 already runs two workgroups per CU.
   // forward: two 32-row workgroups per CU (two waves per SIMD) - in the epoch that beats one 64-row workgroup for
   // both forward kernels (bench.py roofline_fwd via tools/bench_ab.sh: 122.8 / 132.6 us pipelined, 125 / 130.4 us
@@ -1581,25 +1603,17 @@ static int chain_launch_fwd_pipe(const ChainArgs& args_in, int lds_bytes, hipStr
   if (args.pack.total_pairs > 0) grid += chain_bx_pack_blocks(args.pack);
   return chain_launch_kernel(mlp_chain_fwd_pipe_kernel<G, HACT, W>, grid, 64 * W, lds_bytes, st, args);
 }
-// 16-row pipelined kernels: waves per workgroup (tools: RLG_PIPE1_WAVES=4|8)
-static int chain_pipe1_waves() {
-  // default 8: two waves per SIMD - at one wave the four-chunk look-ahead of the weight stream (512 MFMA cycles at one
-  // 16-row group) is shorter than the loaded L2 latency (~900 cycles) and every chunk waits; 16 waves were slower
-  // again (profiles/r4_rank_chain_probe.txt: 4,096 rows forward 30.6 / 26.5 / 26.0 us, backward 28.6 / 22.8 / 27.6 us)
-  static const int w = [] { const char* e = std::getenv("RLG_PIPE1_WAVES"); const int v = e ? std::atoi(e) : 0; return (v == 4 || v == 16) ? v : 8; }();
-  return w;
-}
+// 16-row pipelined kernels: 8 waves per workgroup, two per SIMD - at one wave the four-chunk look-ahead of the weight stream
+// (512 MFMA cycles at one 16-row group) is shorter than the loaded L2 latency (~900 cycles) and every chunk waits; 16 waves
+// were slower again (profiles/r4_rank_chain_probe.txt: 4,096 rows forward 30.6 / 26.5 / 26.0 us, backward 28.6 / 22.8 /
+// 27.6 us at 4 / 8 / 16 waves)
+constexpr int kPipe1Waves = 8;
 
 // Waves per workgroup.  Small minibatches (one data-parallel rank's 4,096 rows: 256 workgroups of 16
 // rows, at most one or two per CU) are bound by the serial chain of a workgroup, not by MFMA
 // throughput: 8 waves halve each wave's share of every layer and put two waves on every SIMD.
 static int chain_waves(int G, long long rows) {
-  static const int forced = [] {
-    const char* e = std::getenv("RLG_CHAIN_WAVES");      // tools: A/B measurements
-    return e ? std::atoi(e) : 0;
-  }();
   if (G != 1) return 4;
-  if (forced == 4 || forced == 8) return forced;
   const long long grid = (rows + 15) / 16;
   return grid <= kChainWideBlocks ? 8 : 4;
 }
@@ -1649,14 +1663,11 @@ int rlg_mlp_chain_prepare(void) {
       reinterpret_cast<const void*>(mlp_chain_fwd_kernel<1, kChElu, 8>), reinterpret_cast<const void*>(mlp_chain_fwd_kernel<1, kChAny, 8>),
       reinterpret_cast<const void*>(mlp_chain_fwd_pipe_kernel<4, kChElu>), reinterpret_cast<const void*>(mlp_chain_fwd_pipe_kernel<4, kChAny>),
       reinterpret_cast<const void*>(mlp_chain_fwd_pipe_kernel<2, kChElu>), reinterpret_cast<const void*>(mlp_chain_fwd_pipe_kernel<2, kChAny>),
-      reinterpret_cast<const void*>(mlp_chain_fwd_pipe_kernel<1, kChElu>), reinterpret_cast<const void*>(mlp_chain_fwd_pipe_kernel<1, kChAny>),
       reinterpret_cast<const void*>(mlp_chain_bwd_kernel<1, 4>), reinterpret_cast<const void*>(mlp_chain_bwd_kernel<2, 4>),
       reinterpret_cast<const void*>(mlp_chain_bwd_kernel<4, 4>), reinterpret_cast<const void*>(mlp_chain_bwd_kernel<1, 8>),
-      reinterpret_cast<const void*>(mlp_chain_bwd_pipe_kernel<4>), reinterpret_cast<const void*>(mlp_chain_bwd_pipe_kernel<8>),
-      reinterpret_cast<const void*>(mlp_chain_fwd_pipe_kernel<1, kChElu, 8>), reinterpret_cast<const void*>(mlp_chain_fwd_pipe_kernel<1, kChAny, 8>),
-      reinterpret_cast<const void*>(mlp_chain_bwd_pipe_kernel<16>),
-      reinterpret_cast<const void*>(mlp_chain_step_pipe_kernel<kChElu, 8>), reinterpret_cast<const void*>(mlp_chain_step_pipe_kernel<kChAny, 8>),
-      reinterpret_cast<const void*>(mlp_chain_fwd_pipe_kernel<1, kChElu, 16>), reinterpret_cast<const void*>(mlp_chain_fwd_pipe_kernel<1, kChAny, 16>)};
+      reinterpret_cast<const void*>(mlp_chain_bwd_pipe_kernel<kPipe1Waves>),
+      reinterpret_cast<const void*>(mlp_chain_fwd_pipe_kernel<1, kChElu, kPipe1Waves>), reinterpret_cast<const void*>(mlp_chain_fwd_pipe_kernel<1, kChAny, kPipe1Waves>),
+      reinterpret_cast<const void*>(mlp_chain_step_pipe_kernel<kChElu, kPipe1Waves>), reinterpret_cast<const void*>(mlp_chain_step_pipe_kernel<kChAny, kPipe1Waves>)};
   for (const void* k : kernels) {
     const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return static_cast<int>(e);
@@ -1759,10 +1770,7 @@ int rlg_mlp_chain_forward(int num_layers, const float* const* weights, const flo
   if (lds_bytes < 0) return static_cast<int>(hipErrorInvalidValue);
   args.lds_b_floats = b_floats;
   args.lds_split_floats = lds_bytes / 4 - chain_split_floats(G);
-  {
-    static const int off = [] { const char* e = std::getenv("RLG_CHAIN_KSPLIT"); return (e && std::atoi(e) == 0) ? 1 : 0; }();
-    args.no_ksplit = off;
-  }
+  args.no_ksplit = 0;
   hipStream_t st = static_cast<hipStream_t>(stream);
   // split-bf16 products on pre-split weight planes (mlp_chain_bx_fwd.hip): 64-row workgroups
   if (weight_planes_or_null != nullptr && chain_bx_fwd_wanted(rows, groups, training)) {
@@ -1777,13 +1785,13 @@ int rlg_mlp_chain_forward(int num_layers, const float* const* weights, const flo
       return chain_bx_launch_fwd(bx, bx_lds, st, ev0, ev1);
     }
   }
-  if ((G >= 2 || chain_pipe1_enabled()) && chain_pipe_enabled() && chain_pipe_fill(args, true)) {
+  // (round 4: the pipelined forward for 16-row workgroups as well - minibatches < 16,384 rows, a data-parallel rank's shapes:
+  //  the unit-structured kernel pays a cold weight fetch at the head of each of its 8 chain_units calls there,
+  //  profiles/r4_rank_chain_phases.txt: 58k cycles per tile for 21k of MFMA issue)
+  if (chain_pipe_fill(args, true)) {
     const bool elu_only = chain_elu_only(args);
-    if (G == 1 && chain_pipe1_waves() == 8)
-      return elu_only ? chain_launch_fwd_pipe<1, kChElu, 8>(args, lds_bytes, st) : chain_launch_fwd_pipe<1, kChAny, 8>(args, lds_bytes, st);
-    if (G == 1 && chain_pipe1_waves() == 16)
-      return elu_only ? chain_launch_fwd_pipe<1, kChElu, 16>(args, lds_bytes, st) : chain_launch_fwd_pipe<1, kChAny, 16>(args, lds_bytes, st);
-    if (G == 1) return elu_only ? chain_launch_fwd_pipe<1, kChElu>(args, lds_bytes, st) : chain_launch_fwd_pipe<1, kChAny>(args, lds_bytes, st);
+    if (G == 1)
+      return elu_only ? chain_launch_fwd_pipe<1, kChElu, kPipe1Waves>(args, lds_bytes, st) : chain_launch_fwd_pipe<1, kChAny, kPipe1Waves>(args, lds_bytes, st);
     if (G == 4) return elu_only ? chain_launch_fwd_pipe<4, kChElu>(args, lds_bytes, st) : chain_launch_fwd_pipe<4, kChAny>(args, lds_bytes, st);
     return elu_only ? chain_launch_fwd_pipe<2, kChElu>(args, lds_bytes, st) : chain_launch_fwd_pipe<2, kChAny>(args, lds_bytes, st);
   }
@@ -1871,13 +1879,9 @@ int rlg_mlp_chain_backward(int num_layers, const float* const* weights, const in
   if (G == 4) return chain_launch<4, true>(args, lds_bytes, st, lp);
   if (G == 2) return chain_launch<2, true>(args, lds_bytes, st, lp);
   // 16-row workgroups: the pipelined kernel when every H / dZ array takes 16-byte row accesses
-  if (chain_pipe1_enabled() && chain_pipe_enabled()) {
-    if (g_chain_dbg == nullptr && chain_rows16_status(args) == 0) {
-      const int W = chain_pipe1_waves();
-      const auto kern = W == 16 ? mlp_chain_bwd_pipe_kernel<16> : (W == 8 ? mlp_chain_bwd_pipe_kernel<8> : mlp_chain_bwd_pipe_kernel<4>);
-      return chain_launch_kernel(kern, static_cast<int>((rows + 15) / 16), 64 * W, lds_bytes, st, args, lp ? *lp : LossArgs{});
-    }
-  }
+  if (g_chain_dbg == nullptr && chain_rows16_status(args) == 0)
+    return chain_launch_kernel(mlp_chain_bwd_pipe_kernel<kPipe1Waves>, static_cast<int>((rows + 15) / 16), 64 * kPipe1Waves, lds_bytes, st,
+                               args, lp ? *lp : LossArgs{});
   return chain_launch<1, true>(args, lds_bytes, st, lp);
 }
 
@@ -1886,7 +1890,7 @@ int rlg_mlp_chain_backward(int num_layers, const float* const* weights, const in
 // rlg_mlp_chain_forward (training form: every act_out given) and of rlg_mlp_chain_backward with a loss descriptor.
 // hipErrorNotSupported when the shape is outside the kernel's envelope (the caller then issues the two launches):
 // minibatches of >= 16,384 rows (they run the split-bf16 kernels), weights not in one arena, H / dZ rows not 16-byte
-// aligned, more than 32 actions, RLG_CHAIN_PIPE1=0 / RLG_CHAIN_STEP1=0.
+// aligned, more than 32 actions.
 int rlg_mlp_chain_step(int num_layers, const float* const* weights, const float* const* biases,
                        const int* in_features, const int* out_features, const int* acts,
                        float* const* act_out, const long long* act_ld, const float* x, long long ldx,
@@ -1896,10 +1900,8 @@ int rlg_mlp_chain_step(int num_layers, const float* const* weights, const float*
                        float* const* dz_out, const long long* dz_ld, double* const* bias_partials,
                        const rlg_ppo_loss_desc* ppo_loss, long long rows, void* stream) {
   using namespace rlg;
-  static const bool enabled = [] { const char* e = std::getenv("RLG_CHAIN_STEP1"); return !(e && std::atoi(e) == 0); }();
   if (rows <= 0) return 0;
-  if (!enabled || !chain_pipe1_enabled() || !chain_pipe_enabled() || chain_pipe1_waves() != 8 || g_chain_dbg != nullptr ||
-      num_layers < 2 || ppo_loss == nullptr || pick_groups(rows, 0, 2) != 1 || pick_groups(rows, 0, 1) != 1)
+  if (g_chain_dbg != nullptr || num_layers < 2 || ppo_loss == nullptr || pick_groups(rows, 0, 2) != 1 || pick_groups(rows, 0, 1) != 1)
     return static_cast<int>(hipErrorNotSupported);
   // one 8-wave workgroup per CU (200 registers per wave): beyond one round of workgroups the two separate launches,
   // which run two workgroups per CU, are faster (8,192 rows: 52.3 vs 50.0 ms per rank epoch, profiles/r4_rank_shapes.txt)
@@ -1944,8 +1946,8 @@ int rlg_mlp_chain_step(int num_layers, const float* const* weights, const float*
   int lds_bytes = fwd_lds > bwd_lds ? fwd_lds : bwd_lds;
   if (need > lds_bytes) lds_bytes = need;
   if (lds_bytes > 160 * 1024) return static_cast<int>(hipErrorNotSupported);
-  const auto kern = chain_elu_only(fa) ? mlp_chain_step_pipe_kernel<kChElu, 8> : mlp_chain_step_pipe_kernel<kChAny, 8>;
-  return chain_launch_kernel(kern, static_cast<int>((rows + 15) / 16), 512, lds_bytes, static_cast<hipStream_t>(stream), fa, ba, loss);
+  const auto kern = chain_elu_only(fa) ? mlp_chain_step_pipe_kernel<kChElu, kPipe1Waves> : mlp_chain_step_pipe_kernel<kChAny, kPipe1Waves>;
+  return chain_launch_kernel(kern, static_cast<int>((rows + 15) / 16), 64 * kPipe1Waves, lds_bytes, static_cast<hipStream_t>(stream), fa, ba, loss);
 }
 
 

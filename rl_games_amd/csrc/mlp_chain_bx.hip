@@ -1,14 +1,15 @@
-// The fused MLP chain on split-bf16 products (gfx950): the same vertical fusion as mlp_chain.hip - every layer of a
+// The fused MLP chain on split products (gfx950): the same vertical fusion as mlp_chain.hip - every layer of a
 // 64-row tile in ONE launch, activations resident in LDS, weights streamed from L2 - but every fp32 product is the
-// sum of six exact bf16 plane products on v_mfma_f32_16x16x32_bf16 (the scheme of mlp_dw.hip, split_bf16.hpp):
-// 6 x 16 cycles per 16x16x32 tile instead of 8 x 32 on the f32 MFMA.
+// sum of three fp16 plane products on v_mfma_f32_16x16x32_f16 (bx_form.hpp, split_f16.hpp; rounds 3 - 5: six exact bf16
+// plane products, the scheme of mlp_dw.hip / split_bf16.hpp): 3 x 16 cycles per 16x16x32 tile instead of 8 x 32 on the
+// f32 MFMA.
 //
 // The f32 MFMA kernels are bound by everything that is NOT an MFMA (v_mfma_f32_16x16x4_f32 and VALU instructions do not
-// co-execute, profiles/r3_coexec_and_launch_probes.txt; beside the bf16 MFMA of this file one or two PLAIN VALU instructions
+// co-execute, profiles/r3_coexec_and_launch_probes.txt; beside the 16-bit MFMA of this file one or two PLAIN VALU instructions
 // per MFMA do, v_pk_add_f32 does not - profiles/r6_coexec_bf16.txt), so the split must not cost inner-loop VALU:
 //   * the WEIGHTS are split once per optimizer step by rlg_mlp_chain_pack_planes into fragment order: fragment
-//     (block ib, chunk c, plane p) = 64 lanes x 8 bf16 = 1 KiB, lane l holds A[16 ib + (l & 15)][k] for its 8 k slots
-//     of chunk c.  A wave's A operands of a chunk are three 16-byte buffer loads at SCALAR addresses (no address VALU),
+//     (block ib, chunk c, plane p) = 64 lanes x 8 fp16 = 1 KiB, lane l holds A[16 ib + (l & 15)][k] for its 8 k slots
+//     of chunk c.  A wave's A operands of a chunk are two 16-byte buffer loads at SCALAR addresses (no address VALU),
 //     1 KiB contiguous each; out-of-range rows / k are zero in the fragments, so the kernels need no masks;
 //   * the ACTIVATIONS are split once, by the epilogue that produces them, and live in LDS as planes: fragment
 //     (chunk c, row group g, plane p) = 1 KiB, read back with one ds_read_b128 per lane.
@@ -16,29 +17,16 @@
 // block 2c (elements 0..3) and of block 2c+1 (elements 4..7).  The MFMA output D[4q + r][row] of a 16-feature block
 // is exactly elements 4*(block & 1) .. +3 of the SAME lane's B fragment for the next layer: the epilogue writes 8
 // bytes per plane, no transposes (a sum does not care which k sits in which slot as long as A and B agree).
-// Numerics: products exact up to 3 * 2^-24 |x||w| (the three dropped plane products), fp32 accumulation; see
+// Numerics: products within 3 * 2^-22 |x||w| in the worst case, ~2^-24 rms (split_f16.hpp), fp32 accumulation; see
 // tests/test_mlp_chain_gpu.py for the bounds against fp64.
 //
 // Backward (this file, round 3):  d heads -> ((dZ W) * act'(H)) x L with the PPO loss tile in front, like
 // mlp_chain_bwd_kernel<4, 4>; replaces the autograd dX / activation-backward / bias-sum nodes behind
 // rl_games/algos_torch/network_builder.py:447-512.
 
-// waves per workgroup of the backward (see mlp_chain_bx_fwd.hip: 8 = two per SIMD, 256 registers each, accumulators in
-// VGPRs, one block per unit)
-#ifndef RLG_BX_BWD_W
-#define RLG_BX_BWD_W 8
-#endif
-#if RLG_BX_BWD_W == 8 && !defined(RLG_ACC_CLASS)
-#define RLG_ACC_CLASS "+v"
-#endif
-
 #include "mlp_chain_bx.hpp"
 #include "mlp_chain_shared.hpp"
 #include "optim_common.hpp"
-
-#ifndef RLG_BX_TRACK
-#define RLG_BX_TRACK 1          // tools: 0 = no gradient maxima, 2 = tracked but not published (timing experiments)
-#endif
 
 namespace rlg {
 
@@ -106,13 +94,13 @@ bool chain_bx_fill_pack(PackArgs& args, int num_layers, const float* const* weig
   return args.total_pairs > 0;
 }
 
-// PACT: the activation of every hidden layer when the launch knows it (the usual network), else kChAny: per layer
-constexpr int kBwW = RLG_BX_BWD_W;
-constexpr int kBwNF = (kBwW == 8) ? 1 : 2;      // blocks of the widest unit
+// Eight waves per workgroup (see mlp_chain_bx_fwd.hip: two per SIMD, 256 registers each, accumulators in VGPRs), one block
+// per unit.  PACT: the activation of every hidden layer when the launch knows it (the usual network), else kChAny: per layer
+constexpr int kBwW = kBxWaves;
 
 template <int G, int PACT>
 __global__ __launch_bounds__(64 * kBwW) void mlp_chain_bwd_bx_kernel(ChainArgs a, LossArgs loss) {
-  constexpr int W = kBwW, NFM = kBwNF;
+  constexpr int W = kBwW, NFM = 1;           // NFM: blocks per unit
   static_assert(W % G == 0, "the prologue deals row group (wave % G) to a wave");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   char* const ldsb = reinterpret_cast<char*>(lds);
@@ -147,7 +135,7 @@ __global__ __launch_bounds__(64 * kBwW) void mlp_chain_bwd_bx_kernel(ChainArgs a
   f32x4 hval[NFM][G], hnext[NFM][G];
   auto wave_blocks = [&](int nob) -> int { return nob / W + (wave < nob % W ? 1 : 0); };
   auto wave_first = [&](int nob) -> int { return wave * (nob / W) + (wave < nob % W ? wave : nob % W); };
-  // blocks ob .. ob + nf - 1 (nf <= 2) of H_{L-1}, the layer whose dZ step L produces; every global access is a
+  // blocks ob .. ob + nf - 1 (nf <= NFM) of H_{L-1}, the layer whose dZ step L produces; every global access is a
   // buffer instruction with the tile's row range as the bound: ragged tiles need no masks, out of range reads 0
   auto request_h = [&](int L, int ob, int nf) {
     const float* ph = pin_s(a.layer[L - 1].h);
@@ -158,7 +146,7 @@ __global__ __launch_bounds__(64 * kBwW) void mlp_chain_bwd_bx_kernel(ChainArgs a
     const unsigned h_group = static_cast<unsigned>(16 * static_cast<int>(ld) * 4);
 #pragma unroll
     for (int f = 0; f < NFM; ++f) {
-      const bool ok = !(kAbl & 4) && f < nf && (ob + f) * 16 + q4 < width;
+      const bool ok = f < nf && (ob + f) * 16 + q4 < width;
 #pragma unroll
       for (int g = 0; g < G; ++g)
         hnext[f][g] = buf_load4(hr, ok ? h_lane + static_cast<unsigned>(g) * h_group + static_cast<unsigned>(ob + f) * 64u : kOob);
@@ -171,8 +159,7 @@ __global__ __launch_bounds__(64 * kBwW) void mlp_chain_bwd_bx_kernel(ChainArgs a
   }
 
   // ---- prologue: d heads tile -> planes in LDS -----------------------------------------------------
-  // scales of the rows (lane & 15 of every row group) of the tile the current step reads (fp16 form: from each row's
-  // largest magnitude; 1 in the bf16 form)
+  // scales of the rows (lane & 15 of every row group) of the tile the current step reads: from each row's largest magnitude
   float scale_in[G];
 #pragma unroll
   for (int g = 0; g < G; ++g) scale_in[g] = 1.0f;
@@ -184,7 +171,7 @@ __global__ __launch_bounds__(64 * kBwW) void mlp_chain_bwd_bx_kernel(ChainArgs a
     const int group = wave % G;
     float* row_scales = reinterpret_cast<float*>(ldsb + a.bx_scales_off);
     float* wg_max = row_scales + 16 * G + (num_layers - 1) * W;      // [layers][W]: the waves' maxima of every dZ tensor
-    if (RLG_BX_F16) {
+    {
       float mine = 0.0f;
       const long long row = row0 + group * 16 + (lane & 15);
       if (row < n_rows) {
@@ -235,10 +222,8 @@ __global__ __launch_bounds__(64 * kBwW) void mlp_chain_bwd_bx_kernel(ChainArgs a
       for (int p = 0; p < kBxPlanes; ++p) *reinterpret_cast<u32x4*>(tile_a + (u * kBxPlanes + p) * kBxFrag + lane * 16) = plane[p];
     }
     __syncthreads();
-    if (RLG_BX_F16) {
 #pragma unroll
-      for (int g = 0; g < G; ++g) scale_in[g] = row_scales[g * 16 + (lane & 15)];
-    }
+    for (int g = 0; g < G; ++g) scale_in[g] = row_scales[g * 16 + (lane & 15)];
   }
   float* const wg_max_all = reinterpret_cast<float*>(ldsb + a.bx_scales_off) + 16 * G;
   chain_stamp(a.dbg, wave, stamp);                                   // prologue + barrier
@@ -277,8 +262,7 @@ __global__ __launch_bounds__(64 * kBwW) void mlp_chain_bwd_bx_kernel(ChainArgs a
     auto epilogue = [&](int ob, int g, const f32x4& acc_scaled, const f32x4& hval) -> f32x4 {
       const int f = ob * 16 + q4;
       f32x4 v;
-      f32x4 accv = acc_scaled;
-      if constexpr (RLG_BX_F16) accv = acc_scaled * inv[g];
+      const f32x4 accv = acc_scaled * inv[g];
       if constexpr (PACT == kChElu) {
         // h > 0 ? 1 : h + 1  ==  min(h, 0) + 1, the same bits with one VALU instruction less per element
 #pragma unroll
@@ -286,11 +270,9 @@ __global__ __launch_bounds__(64 * kBwW) void mlp_chain_bwd_bx_kernel(ChainArgs a
       } else {
         v = chain_act_grad4(accv, hval, p_act);
       }
-      if constexpr (RLG_BX_F16 && RLG_BX_TRACK != 0) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) dz_max = __builtin_fmaxf(dz_max, __builtin_fabsf(v[e]));
-      }
-      if (!(kAbl & 2)) buf_store4(dr, f < width ? d_lane + static_cast<unsigned>(g) * d_group + static_cast<unsigned>(ob) * 64u : kOob, v);
+      for (int e = 0; e < 4; ++e) dz_max = __builtin_fmaxf(dz_max, __builtin_fabsf(v[e]));
+      buf_store4(dr, f < width ? d_lane + static_cast<unsigned>(g) * d_group + static_cast<unsigned>(ob) * 64u : kOob, v);
       if (keep_tile) {
         unsigned plane[kBxPlanes][2];
         bx_split4(v, scale_out[g], plane);
@@ -316,14 +298,11 @@ __global__ __launch_bounds__(64 * kBwW) void mlp_chain_bwd_bx_kernel(ChainArgs a
     // This wave's blocks of the layer: NOB / W each, the first NOB % W waves one more (a whole extra block on some
     // waves costs less than the row-group-split remainder units of mlp_chain.hip: one 16-wide block has 6 x 4
     // MFMAs per chunk here, a unit of one row group would expose every load's latency behind 6 of them).
-    // Two blocks per unit, then one.
+    // One block per unit.
     const int nb_w = wave_blocks(NOB), first_ob = wave_first(NOB);
-    const int units2 = (NFM == 2) ? nb_w >> 1 : 0, left = nb_w - 2 * units2;
-    // what follows a call's last unit: the single-block unit of this layer, else the next layer's first unit
-    auto request_after = [&](bool after_pairs) {
-      if (after_pairs && left) {
-        request_h(L, first_ob + 2 * units2, 1);
-      } else if (L >= 2) {
+    // what follows the layer's last unit: the next layer's first unit
+    auto request_after = [&]() {
+      if (L >= 2) {
         const int nob_n = (pin_s(a.layer[L - 1].in) + 15) >> 4;
         request_h(L - 1, wave_first(nob_n), wave_blocks(nob_n) >= NFM ? NFM : wave_blocks(nob_n));
       }
@@ -334,7 +313,7 @@ __global__ __launch_bounds__(64 * kBwW) void mlp_chain_bwd_bx_kernel(ChainArgs a
           pr, l_off, KC, tin + lane * 16, nunits, [&](int j) { return first + j * NF; }, [&](int) { return 0; },
           [&](int j) {
             if (j < nunits) request_h(L, first + j * NF, NF);
-            else request_after(NF == 2);
+            else request_after();
           },
           [&]() {
 #pragma unroll
@@ -356,17 +335,15 @@ __global__ __launch_bounds__(64 * kBwW) void mlp_chain_bwd_bx_kernel(ChainArgs a
               colsum_store(ob, s);
             }
           },
-          true, (NF == 2 && L == 1) ? a.dbg : nullptr, wave, &stamp);
+          true);
     };
-    if constexpr (NFM == 2) whole(std::integral_constant<int, 2>{}, first_ob, units2);
-    whole(std::integral_constant<int, 1>{}, first_ob + 2 * units2, left);
+    whole(std::integral_constant<int, 1>{}, first_ob, nb_w);
     float* const wg_max = wg_max_all + (L - 1) * W;
-    if (RLG_BX_F16 && RLG_BX_TRACK == 1 && a.amax != nullptr) {
+    if (a.amax != nullptr) {
       const float wmax = bx_wave_max(dz_max);
       if (lane == 0) wg_max[wave] = wmax;
     }
-    if (RLG_BX_TRACK == 2) asm volatile("" :: "v"(dz_max));
-    if (nb_w == 0) request_after(false);        // a wave without a block here still owes itself the next layer's first H
+    if (nb_w == 0) request_after();        // a wave without a block here still owes itself the next layer's first H
     chain_stamp(a.dbg, wave, stamp);                                 // per layer: units done
     // an odd number of blocks leaves half a chunk of the output tile unwritten: zero it (the weights there are zero,
     // but 0 x stale bits may be NaN)
@@ -386,7 +363,7 @@ __global__ __launch_bounds__(64 * kBwW) void mlp_chain_bwd_bx_kernel(ChainArgs a
   // largest |dZ_l| it produced in LDS, thread l combines layer l's.  (Stored BETWEEN the layers by a thread that kept
   // them in registers, the launch lost 7 us: 8 more live registers across the unit engine cost 260 accumulator moves and
   // turned 22 exact vmcnt waits into vmcnt(0).)
-  if (RLG_BX_F16 && a.amax != nullptr && static_cast<int>(threadIdx.x) < num_layers) {
+  if (a.amax != nullptr && static_cast<int>(threadIdx.x) < num_layers) {
     const float* m = wg_max_all + threadIdx.x * W;
     float top = m[0];
 #pragma unroll
@@ -458,8 +435,7 @@ int chain_bx_launch_bwd(const ChainArgs& args, int G, int lds_bytes, hipStream_t
 // ---------------------------------------------------------------------------------
 extern "C" {
 
-/* plane products per fp32 product of the chain's split-product kernels: 3 = two fp16 planes per operand (round 6), 6 = three
- * bf16 planes (a build with -DRLG_BX_F16=0) */
+/* plane products per fp32 product of the chain's split-product kernels: 3 = two fp16 planes per operand (round 6) */
 int rlg_mlp_chain_split_products(void) { return rlg::kBxProducts; }
 
 long long rlg_mlp_chain_planes_bytes(int num_layers, const int* in_features, const int* out_features, int direction) {

@@ -6,16 +6,13 @@
 
 namespace rlg {
 
-// register class the accumulators are pinned to: AGPRs ("+a") in the 512-register kernels; a build that must fit two waves
-// per SIMD defines it as "+v" - without an AGPR constraint anywhere the compiler gives the kernel ONE file of 256
-// registers and issues the MFMAs on VGPR accumulators (with one it splits the file 128 + 128)
-#ifndef RLG_ACC_CLASS
-#define RLG_ACC_CLASS "+a"
-#endif
-#define RLG_ACC_REG(x) RLG_ACC_CLASS(x)
-// (waves per workgroup: RLG_BX_FWD_W / RLG_BX_BWD_W in the two kernels' files.  The tiles fill the LDS - one workgroup per
-//  CU; rounds 3 - 5 ran one wave per SIMD because eight waves on the same tile had measured 1.7x SLOWER - with AGPR-pinned
-//  accumulators, i.e. 128 + 128 registers and scratch; see RLG_ACC_CLASS above.)
+// The accumulators are pinned to VGPRs: the kernels run eight waves per workgroup, two per SIMD, and without an AGPR
+// constraint anywhere the compiler gives a kernel ONE file of 256 registers and issues the MFMAs on VGPR accumulators (with
+// an "+a" constraint it splits the file 128 + 128).  (The tiles fill the LDS - one workgroup per CU; rounds 3 - 5 ran four
+// waves, one per SIMD, on AGPR accumulators because eight waves on the same tile had measured 1.7x SLOWER - with AGPR-pinned
+// accumulators, i.e. 128 + 128 registers and scratch.)
+#define RLG_ACC_REG(x) "+v"(x)
+constexpr int kBxWaves = 8;
 
 static inline int bx_kc(int K) { return (K + 31) >> 5; }
 static inline int bx_nb(int I) { return (I + 15) >> 4; }
@@ -39,7 +36,6 @@ __device__ __forceinline__ void bx_units(rsrc_t pr, unsigned layer_off, int KC, 
   u32x4 a0[NF][kBxPlanes], a1[NF][kBxPlanes], b0[NG][kBxPlanes], b1[NG][kBxPlanes];
   auto unit_off = [&](int j) -> int {
     const int jj = j < nunits ? j : nunits - 1;
-    if (kAbl & 64) return static_cast<int>(layer_off);      // timing only: every A load from the same fragments
     return __builtin_amdgcn_readfirstlane(static_cast<int>(layer_off) + ob_of(jj) * block_stride);
   };
   auto group_of = [&](int j) -> int {
@@ -48,17 +44,15 @@ __device__ __forceinline__ void bx_units(rsrc_t pr, unsigned layer_off, int KC, 
     return g_of(jj);
   };
   auto load_a = [&](u32x4 (&av)[NF][kBxPlanes], int soff) {
-    if ((kAbl & 256) && soff != static_cast<int>(layer_off)) return;       // timing only: no weight loads after the first
 #pragma unroll
     for (int f = 0; f < NF; ++f) {
 #pragma unroll
       for (int p = 0; p < kBxPlanes; ++p)
         av[f][p] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(pr, lane16 + static_cast<unsigned>(p * kBxFrag),
-                                                                                  (kAbl & 64) ? soff : soff + f * block_stride, 0));
+                                                                                  soff + f * block_stride, 0));
     }
   };
   auto load_b = [&](u32x4 (&bv)[NG][kBxPlanes], int c, int g0) {
-    if (kAbl & 128) return;                                  // timing only: no LDS reads
     const char* p = tile_lane + (c * G + g0) * kBxChunk;
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
@@ -67,17 +61,6 @@ __device__ __forceinline__ void bx_units(rsrc_t pr, unsigned layer_off, int KC, 
     }
   };
 
-  if (kAbl & 128) {
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-#pragma unroll
-      for (int pl = 0; pl < kBxPlanes; ++pl) {
-        b0[g][pl] = u32x4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};
-        b1[g][pl] = b0[g][pl];
-        asm volatile("" : "+v"(b0[g][pl]), "+v"(b1[g][pl]));
-      }
-    }
-  }
   int uoff = unit_off(0);
   int g0 = group_of(0);
   load_a(a0, uoff);
@@ -92,7 +75,7 @@ __device__ __forceinline__ void bx_units(rsrc_t pr, unsigned layer_off, int KC, 
   rot();
 
   f32x4 acc[NF][NG];
-  // The six plane products of one accumulator are issued back to back, small ones first: a dependent chain runs at
+  // The plane products of one accumulator are issued back to back, small ones first: a dependent chain runs at
   // the full rate (16.3 cycles per MFMA: the accumulator is forwarded inside the matrix core), a rotation through
   // many accumulators does not (21.7 cycles with 16 of them, profiles/r3_mfma_peak_probe.txt).
   // (a unit's first chunk starts from the constant 0 as SrcC: no accumulator is zeroed by hand)
@@ -105,7 +88,7 @@ __device__ __forceinline__ void bx_units(rsrc_t pr, unsigned layer_off, int KC, 
 #pragma unroll
         for (int t = 0; t < kBxProducts; ++t)
           acc[f][g] = bx_mfma(av[f][kBxPa[t]], bv[g][kBxPb[t]], (kFirst && t == 0) ? f32x4{0.0f, 0.0f, 0.0f, 0.0f} : acc[f][g]);
-        if constexpr (kFirst) asm volatile("" : RLG_ACC_REG(acc[f][g]));      // accumulators live in AGPRs
+        if constexpr (kFirst) asm volatile("" : RLG_ACC_REG(acc[f][g]));      // pins the accumulator's register class
       }
     }
   };
@@ -114,7 +97,7 @@ __device__ __forceinline__ void bx_units(rsrc_t pr, unsigned layer_off, int KC, 
     constexpr bool kCur1 = decltype(cur_tag)::value;
     constexpr bool kPf = decltype(pf_tag)::value;
     if constexpr (kPf) {
-      load_a(kCur1 ? a0 : a1, (kAbl & 64) ? uoff : uoff + (c + 1) * kBxChunk);
+      load_a(kCur1 ? a0 : a1, uoff + (c + 1) * kBxChunk);
       load_b(kCur1 ? b0 : b1, c + 1, g0);
     }
     mfmas(first_tag, kCur1 ? a1 : a0, kCur1 ? b1 : b0);

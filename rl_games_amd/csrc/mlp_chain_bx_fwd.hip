@@ -7,30 +7,13 @@
 // (rl_games/algos_torch/models.py:54-56) in front of it, like mlp_chain_fwd_kernel; same interface and outputs
 // (activations fp32 in global memory for the backward / weight-gradient launches, heads fp32).
 //
-// 64-row workgroups (G = 4), 8 waves (RLG_BX_FWD_W below), activations as planes in LDS: 12 KiB per 32-feature chunk (bf16
-// form; 8 KiB in the fp16 form).  A
-// 400-wide layer (156 KiB) does not fit next to its neighbours, so ONE tile of the chain may be WINDOWED: its
+// 64-row workgroups (G = 4), 8 waves (kFwW below), activations as planes in LDS: 8 KiB per 32-feature chunk.  A 400-wide
+// layer does not fit next to its neighbours, so ONE tile of the chain may be WINDOWED: its
 // producer layer p-1 and its consumer layer p run interleaved in passes over windows of the tile's chunks -
 //   [units of layer p-1 for the blocks of the window]  barrier  [layer p accumulates the window's chunks]  barrier
 // - with layer p's accumulators (all of a wave's blocks, at most 4) kept in registers across the passes; layer p's
 // epilogue follows the last pass.  The host picks the window (chain_bx_fwd_plan).
 
-// waves per workgroup: 8 = two per SIMD with 256 registers each - a wave's epilogue (VALU: bias, activation, the split
-// into planes, stores) issues under the other wave's MFMAs - every wave with half the column blocks of a layer; 4 = one per
-// SIMD with all 512 registers (rounds 3 - 6 until profiles/r6_fwd_two_waves.txt).  Two waves per SIMD need accumulators
-// in VGPRs: with an AGPR constraint anywhere in the kernel hipcc splits the 256 registers 128 + 128 and spills 163 of them,
-// without one it allocates one file of 256 and issues the MFMAs on VGPR accumulators.
-#ifndef RLG_BX_FWD_W
-#define RLG_BX_FWD_W 8
-#endif
-#if RLG_BX_FWD_W == 8 && !defined(RLG_ACC_CLASS)
-#define RLG_ACC_CLASS "+v"
-#endif
-// blocks of the widest unit (a B fragment read from LDS feeds that many MFMA chains).  One at two waves per SIMD: pairs
-// need 90 registers more than the 256 there are (scratch: + 5 % instead of - 11 %)
-#ifndef RLG_BX_FWD_NF
-#define RLG_BX_FWD_NF (RLG_BX_FWD_W == 8 ? 1 : 2)
-#endif
 
 #include "mlp_chain_bx.hpp"
 #include "mlp_chain_shared.hpp"
@@ -38,8 +21,15 @@
 namespace rlg {
 
 constexpr int kFwG = 4;
-constexpr int kFwUnitBlocks = RLG_BX_FWD_NF;
-constexpr int kFwW = RLG_BX_FWD_W;
+// Eight waves per workgroup: two per SIMD with 256 registers each - a wave's epilogue (VALU: bias, activation, the split
+// into planes, stores) issues under the other wave's MFMAs - every wave with half the column blocks of a layer.  (Rounds
+// 3 - 6 ran four, one per SIMD with all 512 registers, until profiles/r6_fwd_two_waves.txt.)  Two waves per SIMD need
+// accumulators in VGPRs: with an AGPR constraint anywhere in the kernel hipcc splits the 256 registers 128 + 128 and spills
+// 163 of them, without one it allocates one file of 256 and issues the MFMAs on VGPR accumulators.
+constexpr int kFwW = kBxWaves;
+// blocks of a unit (a B fragment read from LDS feeds that many MFMA chains).  One at two waves per SIMD: pairs need 90
+// registers more than the 256 there are (scratch: + 5 % instead of - 11 %)
+constexpr int kFwUnitBlocks = 1;
 static_assert(kFwW % kFwG == 0, "the prologue deals row group (wave % G) to a wave");
 constexpr int kFwMaxPersist = 16 / kFwW;   // blocks of the windowed tile's consumer per wave (accumulators across passes)
 
@@ -83,7 +73,7 @@ __device__ __forceinline__ void bx_span(rsrc_t pr, unsigned layer_off, int KC, c
 #pragma unroll
         for (int t = 0; t < kBxProducts; ++t)
           acc[f][g] = bx_mfma(av[f][kBxPa[t]], bv[g][kBxPb[t]], (kFirst && t == 0) ? f32x4{0.0f, 0.0f, 0.0f, 0.0f} : acc[f][g]);
-        asm volatile("" : RLG_ACC_REG(acc[f][g]));      // accumulators live in AGPRs
+        asm volatile("" : RLG_ACC_REG(acc[f][g]));      // pins the accumulator's register class
       }
     }
   };
@@ -156,7 +146,7 @@ __global__ __launch_bounds__(64 * kFwW) void mlp_chain_fwd_bx_kernel(ChainArgs a
   int stamp = 0;
   chain_stamp(a.dbg, wave, stamp);
 
-  // scales of the rows (lane & 15 of every row group) of the tile the current layer reads (fp16 form; 1 in the bf16 form)
+  // scales of the rows (lane & 15 of every row group) of the tile the current layer reads
   float scale_in[G];
 #pragma unroll
   for (int g = 0; g < G; ++g) scale_in[g] = kBxScaleObsNorm;
@@ -244,7 +234,7 @@ __global__ __launch_bounds__(64 * kFwW) void mlp_chain_fwd_bx_kernel(ChainArgs a
     }
     chain_stamp(a.dbg, wave, stamp);                                 // (tools: statistics visible)
     float scale_mine = kBxScaleObsNorm;         // of row (lane & 15) of row group wave % G: a wave splits ITS group's rows
-    if (RLG_BX_F16 && !norm) {
+    if (!norm) {
       // raw observations have no bound: every row gets its scale from its largest magnitude (one more pass over the
       // rows, which the loads behind it find in the cache)
       float mine = 0.0f;
@@ -266,7 +256,7 @@ __global__ __launch_bounds__(64 * kFwW) void mlp_chain_fwd_bx_kernel(ChainArgs a
       put_frags(u0, scale_mine);
     }
     __syncthreads();
-    if (RLG_BX_F16 && !norm) {
+    if (!norm) {
 #pragma unroll
       for (int g = 0; g < G; ++g) scale_in[g] = stats[g * 16 + (lane & 15)];
       __syncthreads();                          // (the scratch shares its bytes with a later tile)
@@ -306,12 +296,8 @@ __global__ __launch_bounds__(64 * kFwW) void mlp_chain_fwd_bx_kernel(ChainArgs a
       return [=](int ob, int g, const f32x4& accv, const f32x4& bias) {
         const int f = ob * 16 + q4;
         f32x4 z;
-        if constexpr (RLG_BX_F16) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) z[e] = __builtin_fmaf(accv[e], inv[g], bias[e]);
-        } else {
-          z = accv + bias;
-        }
+        for (int e = 0; e < 4; ++e) z[e] = __builtin_fmaf(accv[e], inv[g], bias[e]);
         const f32x4 v = chain_act4<HACT>(z, act);
         if (h_on) {
           const unsigned off = h_lane + static_cast<unsigned>(g) * h_group + static_cast<unsigned>(ob) * 64u;
@@ -345,15 +331,10 @@ __global__ __launch_bounds__(64 * kFwW) void mlp_chain_fwd_bx_kernel(ChainArgs a
     auto bias_fast = [&](int layer) -> bool {
       return pin_s(static_cast<int>(aligned16(a.layer[layer].bias) && (a.layer[layer].out & 3) == 0)) != 0;
     };
-    // blocks [b0, b1) of layer L for all row groups: this wave's share, four blocks per unit, then two, then one
+    // blocks [b0, b1) of layer L for all row groups: this wave's share, one block per unit
     auto run_blocks = [&](int b0, int b1, char* dst_tile, int chunk_base) {
       const int nb = b1 - b0;
       const int nb_w = wave_blocks(nb), first_ob = b0 + wave_first(nb);
-      // widest units first: kFwUnitBlocks blocks each, then (unless the widest is 3: pairs would be a third instantiation of
-      // the engine and its registers) pairs, then single blocks
-      const int unitsw = (kFwUnitBlocks > 2) ? nb_w / kFwUnitBlocks : 0;
-      const int rest = nb_w - kFwUnitBlocks * unitsw;
-      const int units2 = (kFwUnitBlocks == 3 || kFwUnitBlocks == 1) ? 0 : rest >> 1, left = rest - 2 * units2;
       const rsrc_t br = bias_rsrc(L);
       const bool bfast = bias_fast(L);
       auto epilogue = make_epilogue(L, dst_tile, chunk_base, scale_in);
@@ -384,10 +365,7 @@ __global__ __launch_bounds__(64 * kFwW) void mlp_chain_fwd_bx_kernel(ChainArgs a
             },
             false);
       };
-      if constexpr (kFwUnitBlocks > 2) whole(std::integral_constant<int, kFwUnitBlocks>{}, first_ob, unitsw);
-      if constexpr (kFwUnitBlocks != 3 && kFwUnitBlocks != 1)
-        whole(std::integral_constant<int, 2>{}, first_ob + kFwUnitBlocks * unitsw, units2);
-      whole(std::integral_constant<int, 1>{}, first_ob + kFwUnitBlocks * unitsw + 2 * units2, left);
+      whole(std::integral_constant<int, kFwUnitBlocks>{}, first_ob, nb_w);
     };
     // an odd number of blocks leaves half a chunk of a tile unwritten: zero it (the weights there are zero, but
     // 0 x stale bits may be NaN)

@@ -12,17 +12,8 @@
 #include <type_traits>
 #include <utility>
 
-// Timing-only ablations for tools/ablate_chain.sh (-DRLG_ABL=mask builds a library that computes WRONG results and
-// shows what a phase costs): 1 no bias/activation maths, 2 no global stores of the epilogues, 4 no epilogue at all,
-// 8 no remainder units, 16 no barriers between layers, 32 no prologue loads, 64 no weight traffic (A loads out of range),
-// 128 (pipelined kernels) no LDS reads of the B fragments
-#ifndef RLG_ABL
-#define RLG_ABL 0
-#endif
-
 namespace rlg {
 
-constexpr int kAbl = RLG_ABL;
 constexpr int kChainMaxLayers = 8;
 // K-split scratch of the forward (partial fragments of 256 floats): G = 1: up to 2 units x 3 parts (8 waves) or
 // 4 x 1; G = 2: up to 2 units x 1 part; G = 4: no split (a remainder block already has one unit per wave)
@@ -78,7 +69,7 @@ struct ChainArgs {
   long long rows;
   int lds_b_floats;
   int lds_split_floats;        // forward: offset of the K-split scratch (partial fragments of remainder units)
-  int no_ksplit;               // tools (RLG_CHAIN_KSPLIT=0): remainder units without the K-split            // start of the second LDS region, in floats
+  int no_ksplit;               // remainder units without the K-split (the lean entries; the chain entries pass 0)
   // pipelined kernels: ONE buffer resource over every weight matrix and bias vector (the flat parameter arena)
   const float* w_base;
   unsigned w_bytes;

@@ -1,9 +1,9 @@
 // The lean 16-row kernels of the fused MLP chain (round 4; a file of their own since round 5): forward, backward and the
-// one-launch forward + PPO loss + backward step for minibatches / rollouts of < 16,384 rows on exact fp32 products
-// (v_mfma_f32_16x16x4_f32) - a data-parallel rank's 4,096 - 8,192-row minibatches, BASELINE configs[1] and [4] - with the
-// weights as fp32 FRAGMENTS in the order each wave consumes them.  Same products in the same order as the pipelined
-// kernels of mlp_chain.hip (bit-identical results, tests/test_mlp_chain_gpu.py); MFMA mapping, tile layout and what the
-// launches replace in the reference: see the head of mlp_chain.hip.
+// one-launch forward + PPO loss + backward step for minibatches / rollouts of < 16,384 rows - a data-parallel rank's
+// 4,096 - 8,192-row minibatches, BASELINE configs[1] and [4] - with the weights as FRAGMENTS in the order each wave consumes
+// them.  Rounds 4 - 5: exact fp32 products (v_mfma_f32_16x16x4_f32) in the order of the pipelined kernels of mlp_chain.hip,
+// bit-identical to them; since round 6 the split-fp16 form described below, within the split kernels' tolerance of them
+// (tests/test_mlp_chain_gpu.py).  Tile layout and what the launches replace in the reference: see the head of mlp_chain.hip.
 
 #include "mlp_chain_shared.hpp"
 #include "optim_common.hpp"
@@ -16,14 +16,9 @@
 // their 4 floats each, so the pack launch splits exactly the values it used to copy, and an epilogue writes 8 bytes per
 // plane where it wrote 16 bytes of fp32.  Scales as in the 64-row kernels: weights 2^6, hidden activations 2^4, normalised
 // observations 2^12, raw observations and gradient rows by their own maxima (a 16-row tile: a lane's row is lane & 15).
-// RLG_LEAN_F16=0 (or a -DRLG_BX_F16=0 build): exact fp32 products, bit-identical to the pipelined kernels of mlp_chain.hip.
-#ifndef RLG_LEAN_F16
-#define RLG_LEAN_F16 RLG_BX_F16
-#endif
 
 namespace rlg {
 
-#if RLG_LEAN_F16
 // block `ob` (16 features) of a tile in the group layout: this lane's 4 features -> 8 bytes of each plane
 __device__ __forceinline__ void lean_put_planes(float* tile, int ob, int lane, const f32x4& v, float scale) {
   unsigned pl[kBxPlanes][2];
@@ -127,7 +122,6 @@ __device__ __forceinline__ float lean_fwd_prologue_f16(const ChainArgs& a, float
   __syncthreads();
   return scale;
 }
-#endif
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Lean 16-row forward (round 4, experimental - the C entry rlg_mlp_chain_forward_lean; tools/exp/lean_probe.py).
@@ -184,29 +178,18 @@ __device__ __forceinline__ void chain_fwd_lean_body(const ChainArgs& a, const Le
   request(0);
   request(1);
   request(2);
-#if RLG_LEAN_F16
   auto zero_chunk = [&](float* tile, int c) { lean_zero_block(tile, c, lane); };        // (block c of the group layout)
-#else
-  auto zero_chunk = [&](float* tile, int c) { *reinterpret_cast<f32x4*>(tile + (c * 64 + lane) * 4) = f32x4{0.0f, 0.0f, 0.0f, 0.0f}; };
-#endif
   int stamp = 0;
   chain_stamp(a.dbg, wave, stamp);
   float scale_in = 1.0f;          // fp16 form: scale of this lane's row in the tile the current layer reads
   {
     const int in0 = pin_s(a.layer[0].in);
     const int KC0 = (in0 + 15) >> 4;
-#if RLG_LEAN_F16
     if (wave == W - 1) {
       // (behind the last group the prologue writes: its second block when KC0 is odd is written - as zeros - by the prologue)
       for (int c = (KC0 + 1) & ~1; c < la.kc2[0]; ++c) zero_chunk(tile_a, c);
     }
     scale_in = lean_fwd_prologue_f16<W>(a, tile_a, tile_b, row0, lane, wave, stamp);     // (ends with a barrier)
-#else
-    if (wave == W - 1) {
-      for (int c = KC0; c < la.kc2[0]; ++c) zero_chunk(tile_a, c);
-    }
-    chain_fwd_prologue<1, W>(a, tile_a, tile_b, row0, lane, wave, stamp);     // (ends with a barrier)
-#endif
   }
   chain_stamp(a.dbg, wave, stamp);
 
@@ -254,22 +237,15 @@ __device__ __forceinline__ void chain_fwd_lean_body(const ChainArgs& a, const Le
     };
     f32x4 acc0 = {0.0f, 0.0f, 0.0f, 0.0f}, acc1 = acc0;
     int gu = 0, unit = 0;
-#if RLG_LEAN_F16
     const float inv = 1.0f / (kBxScaleW * scale_in);
-#endif
     auto epilogue = [&]() {
       const int ob = unit_block(unit);
       const int f = ob * 16 + q4;
-#if RLG_LEAN_F16
       f32x4 z;
 #pragma unroll
       for (int e = 0; e < 4; ++e) z[e] = __builtin_fmaf(acc0[e] + acc1[e], inv, bv[e]);
       const f32x4 v = chain_act4<HACT>(z, l_act);
       if (!last) lean_put_planes(tout, ob, lane, v, kBxScaleH);
-#else
-      const f32x4 v = chain_act4<HACT>((acc0 + acc1) + bv, l_act);
-      if (!last) *reinterpret_cast<f32x4*>(tout + (ob * 64 + lane) * 4) = v;
-#endif
       const long long row = row0 + (lane & 15);
       if (h_on && row < n_rows) store_row4(l_h, l_ldh, row, f, l_out, v, h_vec);
     };
@@ -283,17 +259,7 @@ __device__ __forceinline__ void chain_fwd_lean_body(const ChainArgs& a, const Le
       for (int s = 0; s < 4; ++s) {
         request((s + 3) & 3);
         read_b((s + 1) & 1);
-#if RLG_LEAN_F16
         lean_group_mfma(aq[s], bq[s & 1], acc0, acc1);
-#else
-#pragma unroll
-        for (int ch = 0; ch < 2; ++ch) {
-          acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(aq[s][ch][0], bq[s & 1][ch][0], acc0, 0, 0, 0);
-          acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(aq[s][ch][1], bq[s & 1][ch][1], acc1, 0, 0, 0);
-          acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(aq[s][ch][2], bq[s & 1][ch][2], acc0, 0, 0, 0);
-          acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(aq[s][ch][3], bq[s & 1][ch][3], acc1, 0, 0, 0);
-        }
-#endif
         ++gu;
         if (gu == gpu) {
           gu = 0;
@@ -347,11 +313,7 @@ __device__ __forceinline__ void chain_bwd_lean_body(const ChainArgs& a, const Le
   request(0);
   request(1);
   request(2);
-#if RLG_LEAN_F16
   auto zero_chunk = [&](float* tile, int c) { lean_zero_block(tile, c, lane); };        // (block c of the group layout)
-#else
-  auto zero_chunk = [&](float* tile, int c) { *reinterpret_cast<f32x4*>(tile + (c * 64 + lane) * 4) = f32x4{0.0f, 0.0f, 0.0f, 0.0f}; };
-#endif
   // ---- the PPO loss of this row tile (training steps), as in mlp_chain_bwd_pipe_kernel
   if (a.with_loss) {
     if constexpr (kPreloaded) ppo_loss_quad_run<16, 64 * W>(loss, lds, blockIdx.x, preloaded);   // (inputs requested long ago)
@@ -365,7 +327,6 @@ __device__ __forceinline__ void chain_bwd_lean_body(const ChainArgs& a, const Le
     const int w = a.layer[num_layers - 1].out;
     const int KC0 = (w + 15) >> 4;
     const bool xv = vec4_ok(a.x, a.ldx);
-#if RLG_LEAN_F16
     // the row's scale from its largest magnitude (every wave reads the whole row of d heads: a few loads), then the groups
     // of two 16-feature blocks, dealt to the waves, as planes
     const long long row = row0 + r16;
@@ -396,14 +357,6 @@ __device__ __forceinline__ void chain_bwd_lean_body(const ChainArgs& a, const Le
       *reinterpret_cast<u32x4*>(tile_a + ((2 * u) * 64 + lane) * 4) = plane[0];
       *reinterpret_cast<u32x4*>(tile_a + ((2 * u + 1) * 64 + lane) * 4) = plane[1];
     }
-#else
-    for (int u = wave; u < la.kc2[0]; u += W) {
-      const long long row = row0 + r16;
-      f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-      if (u < KC0 && row < n_rows) v = load_row4(a.x, a.ldx, row, u * 16 + q4, w, xv);
-      *reinterpret_cast<f32x4*>(tile_a + (u * 64 + lane) * 4) = v;
-    }
-#endif
     __syncthreads();
   }
   float* tin = tile_a;
@@ -447,27 +400,19 @@ __device__ __forceinline__ void chain_bwd_lean_body(const ChainArgs& a, const Le
       const int f = unit_block(u) * 16 + q4;
       hv = buf_load4(hr, (u < nun && f < width) ? h_lane + static_cast<unsigned>(unit_block(u)) * 64u : kOob);
     };
-#if RLG_LEAN_F16
     // the accumulators hold (weight scale x row scale) x the sums; the tile this step writes is split one step below the one
     // it reads (csrc/bx_form.hpp)
     const float inv = 1.0f / (kBxScaleW * scale_in);
     const float scale_out = scale_in * kBxScaleStepBwd;
     float dz_max = 0.0f;
-#endif
     auto epilogue = [&]() {
       const int ob = unit_block(unit);
       const int f = ob * 16 + q4;
-#if RLG_LEAN_F16
       f32x4 v = chain_act_grad4((acc0 + acc1) * inv, hv, p_act);
       if (!row_ok) v = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
       for (int e = 0; e < 4; ++e) dz_max = __builtin_fmaxf(dz_max, __builtin_fabsf(v[e]));
       if (keep_tile) lean_put_planes(tout, ob, lane, v, scale_out);
-#else
-      f32x4 v = chain_act_grad4(acc0 + acc1, hv, p_act);
-      if (!row_ok) v = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-      if (keep_tile) *reinterpret_cast<f32x4*>(tout + (ob * 64 + lane) * 4) = v;
-#endif
       buf_store4(dzr, f < width ? dz_lane + static_cast<unsigned>(ob) * 64u : kOob, v);
       if (bpart != nullptr) {
         f32x4 sm;
@@ -491,17 +436,7 @@ __device__ __forceinline__ void chain_bwd_lean_body(const ChainArgs& a, const Le
       for (int s = 0; s < 4; ++s) {
         request((s + 3) & 3);
         read_b((s + 1) & 1);
-#if RLG_LEAN_F16
         lean_group_mfma(aq[s], bq[s & 1], acc0, acc1);
-#else
-#pragma unroll
-        for (int ch = 0; ch < 2; ++ch) {
-          acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(aq[s][ch][0], bq[s & 1][ch][0], acc0, 0, 0, 0);
-          acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(aq[s][ch][1], bq[s & 1][ch][1], acc1, 0, 0, 0);
-          acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(aq[s][ch][2], bq[s & 1][ch][2], acc0, 0, 0, 0);
-          acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(aq[s][ch][3], bq[s & 1][ch][3], acc1, 0, 0, 0);
-        }
-#endif
         ++gu;
         if (gu == gpu) {
           gu = 0;
@@ -512,21 +447,16 @@ __device__ __forceinline__ void chain_bwd_lean_body(const ChainArgs& a, const Le
         }
       }
     }
-#if RLG_LEAN_F16
     if (a.amax != nullptr) {
       const float m = bx_wave_max(dz_max);
       if (lane == 0) (lds + (a.bx_scales_off >> 2))[(L - 1) * W + wave] = m;
     }
-#endif
     __syncthreads();
-#if RLG_LEAN_F16
     scale_in = scale_out;
-#endif
     float* tt = tin;
     tin = tout;
     tout = tt;
   }
-#if RLG_LEAN_F16
   if (a.amax != nullptr && static_cast<int>(threadIdx.x) < num_layers) {
     const float* m = lds + (a.bx_scales_off >> 2) + threadIdx.x * W;
     float t = m[0];
@@ -534,7 +464,6 @@ __device__ __forceinline__ void chain_bwd_lean_body(const ChainArgs& a, const Le
     for (int w = 1; w < W; ++w) t = __builtin_fmaxf(t, m[w]);
     a.amax[static_cast<long long>(kBxAmaxDz + threadIdx.x) * a.amax_stride + blockIdx.x] = t;
   }
-#endif
 }
 
 __global__ __launch_bounds__(64 * kLeanW) void mlp_chain_bwd_lean_kernel(ChainArgs a, LeanArgs la, LossArgs loss) {
@@ -580,11 +509,7 @@ __global__ __launch_bounds__(256) void chain_pack_frags2_kernel(LeanPackArgs p0,
 }
 __device__ __forceinline__ void chain_pack_frags_block(const LeanPackArgs& p) {
   const unsigned t = blockIdx.x * 256u + threadIdx.x;
-#if RLG_LEAN_F16
   const unsigned frag = 2u * (t >> 6);           // one thread per (group = fragment pair, lane)
-#else
-  const unsigned frag = t >> 6;
-#endif
   const int lane = static_cast<int>(t & 63u);
   if (frag >= p.total_frags) return;
   int w = 0, st = 0;
@@ -626,7 +551,6 @@ __device__ __forceinline__ void chain_pack_frags_block(const LeanPackArgs& p) {
     }
     return v;
   };
-#if RLG_LEAN_F16
   // a group = the two chunks (c, c + 1), c even: their 8 values per lane as two fp16 planes - plane 0 where chunk c was,
   // plane 1 where chunk c + 1 was (the slack fragments behind the last stream stay zero: q runs past every unit there)
   const f32x4 lo = chunk_values(c), hi = chunk_values(c + 1);       // (c is even: segments and units hold whole groups)
@@ -635,9 +559,6 @@ __device__ __forceinline__ void chain_pack_frags_block(const LeanPackArgs& p) {
   bx_split8(x, kBxScaleW, plane);
   *reinterpret_cast<u32x4*>(p.dst + (static_cast<long long>(frag) * 64 + lane) * 4) = plane[0];
   *reinterpret_cast<u32x4*>(p.dst + (static_cast<long long>(frag + 1) * 64 + lane) * 4) = plane[1];
-#else
-  *reinterpret_cast<f32x4*>(p.dst + (static_cast<long long>(frag) * 64 + lane) * 4) = chunk_values(c);
-#endif
 }
 
 // host: the stream layout of one direction.  Returns the buffer size in bytes (incl. the slack the 3-groups-ahead requests
@@ -723,7 +644,7 @@ int rlg_mlp_chain_pack_frags(int num_layers, const float* const* weights, const 
     pk.bias[L] = biases_or_null ? biases_or_null[L] : nullptr;
   }
   pk.dst = static_cast<float*>(frags);
-  const unsigned threads = pk.total_frags * 64u / (RLG_LEAN_F16 ? 2u : 1u);
+  const unsigned threads = pk.total_frags * 64u / 2u;        // one thread per (group = fragment pair, lane)
   hipLaunchKernelGGL(chain_pack_frags_kernel, dim3((threads + 255u) / 256u), dim3(256), 0, static_cast<hipStream_t>(stream), pk);
   RLG_RETURN_LAUNCH_STATUS();
 }
@@ -792,7 +713,7 @@ int rlg_mlp_chain_backward_lean(int num_layers, const int* in_features, const in
     float* entries = nullptr;
     int stride = 0;
     chain_take_gradient_maxima(&entries, &stride);
-    if (RLG_LEAN_F16 && entries != nullptr) {
+    if (entries != nullptr) {
       if (stride < (rows + 15) / 16) return static_cast<int>(hipErrorInvalidValue);
       args.amax = entries;
       args.amax_stride = stride;
@@ -826,7 +747,7 @@ int rlg_mlp_chain_pack_frags_both(int num_layers, const float* const* weights, c
   }
   p0.dst = static_cast<float*>(frags_fwd);
   p1.dst = static_cast<float*>(frags_bwd_or_null);
-  const unsigned threads = (p0.total_frags > p1.total_frags ? p0.total_frags : p1.total_frags) * 64u / (RLG_LEAN_F16 ? 2u : 1u);
+  const unsigned threads = (p0.total_frags > p1.total_frags ? p0.total_frags : p1.total_frags) * 64u / 2u;
   hipLaunchKernelGGL(chain_pack_frags2_kernel, dim3((threads + 255u) / 256u, 2), dim3(256), 0, static_cast<hipStream_t>(stream), p0, p1);
   RLG_RETURN_LAUNCH_STATUS();
 }
@@ -891,7 +812,7 @@ int rlg_mlp_chain_step_lean(int num_layers, const float* const* biases, const in
     float* entries = nullptr;
     int stride = 0;
     chain_take_gradient_maxima(&entries, &stride);
-    if (RLG_LEAN_F16 && entries != nullptr) {
+    if (entries != nullptr) {
       if (stride < (rows + 15) / 16) return static_cast<int>(hipErrorInvalidValue);
       ba.amax = entries;
       ba.amax_stride = stride;

@@ -45,16 +45,10 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr int kDwMaxLayers = 8;
 constexpr int kDwMaxTiles = 16;    // tiles per dimension of one layer (<= 1024 features in 64-wide tiles)
 constexpr int kDwBatch = 4;        // k-steps (of 4 rows) per prefetch batch
-#ifndef RLG_DW_SETS
-#define RLG_DW_SETS 3
-#endif
-constexpr int kDwSets = RLG_DW_SETS;   // register sets: kDwSets-1 batches of loads in flight
-#ifndef RLG_DW_PK_A
-#define RLG_DW_PK_A 1
-#endif
-#ifndef RLG_DW_PK_B
-#define RLG_DW_PK_B 1
-#endif
+// register sets: kDwSets-1 batches of loads in flight (two sets: one batch of look-ahead did not cover the first-touch
+// latency, launch pair 133 instead of 117 us; four: no further gain at 210 instead of 178 registers -
+// profiles/r2_mlp_pmc_kouter_experiment.txt)
+constexpr int kDwSets = 3;
 constexpr int kDwSplitBatch = 8;       // k-steps per batch of the split-bf16 form (K = 32 of one bf16 MFMA)
 
 // Product forms of the launch
@@ -320,9 +314,10 @@ __device__ __forceinline__ void dw_tile(const DwLayer& L, int rows, int o0, int 
     };
     auto compute8_bf16 = [&](const VA (&av)[KB], const VB (&bv)[KB]) {
       RLG_DW_PIN();
-      // blocks are split two at a time where a lane's row vector holds two (dw_split8x2: packed residuals)
+      // blocks are split two at a time where a lane's row vector holds two (dw_split8x2: packed residuals, 9 instead of 11
+      // VALU per pair; the loop splits, then multiplies, so no v_pk_add_f32 sits between MFMAs - profiles/r6_dw_stage.txt)
       u32x4 pb[BI][3];
-      if constexpr (BI >= 2 && RLG_DW_PK_B) {
+      if constexpr (BI >= 2) {
 #pragma unroll
         for (int b = 0; b < BI; b += 2) {
           split_f32x2 x[8];
@@ -352,7 +347,7 @@ __device__ __forceinline__ void dw_tile(const DwLayer& L, int rows, int o0, int 
                                                                 acc[a][b], 0, 0, 0);
         }
       };
-      if constexpr (BO >= 2 && RLG_DW_PK_A) {
+      if constexpr (BO >= 2) {
 #pragma unroll
         for (int a = 0; a < BO; a += 2) {
           split_f32x2 x[8];

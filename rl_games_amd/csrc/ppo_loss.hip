@@ -30,18 +30,9 @@
 
 #include "ppo_loss_tile.hpp"
 
-#include <cstdlib>
-
 namespace rlg {
 
-static int loss_tile_rows(int minibatch) {
-  static const int forced = [] {
-    const char* e = std::getenv("RLG_LOSS_ROWS");       // tools: A/B measurements (16 / 32 / 64)
-    return e ? std::atoi(e) : 0;
-  }();
-  if (forced == 16 || forced == 32 || forced == 64) return forced;
-  return minibatch <= kLossSmallBatch ? kLossRowsSmall : kLossRows;
-}
+static int loss_tile_rows(int minibatch) { return minibatch <= kLossSmallBatch ? kLossRowsSmall : kLossRows; }
 
 template <int kRows>
 __global__ __launch_bounds__(kLossThreads) void ppo_loss_kernel(LossArgs p) {
@@ -379,9 +370,6 @@ int rlg_ppo_loss_fused(const float* mu, const float* logstd, const float* values
   const int grid = rlg_ppo_loss_num_blocks(minibatch);
   if (tile_rows == kLossRows) {
     hipLaunchKernelGGL(ppo_loss_kernel<kLossRows>, dim3(grid), dim3(kLossThreads), shm,
-                       static_cast<hipStream_t>(stream), p);
-  } else if (tile_rows == 32) {
-    hipLaunchKernelGGL(ppo_loss_kernel<32>, dim3(grid), dim3(kLossThreads), shm,
                        static_cast<hipStream_t>(stream), p);
   } else {
     hipLaunchKernelGGL(ppo_loss_kernel<kLossRowsSmall>, dim3(grid), dim3(kLossThreads), shm,

@@ -21,15 +21,8 @@ constexpr int kSurrogateClip = 0, kSurrogateSmooth = 1, kSurrogateNone = 2;
 // the reference reduces in yet another order; measured on 200,000 rows of A = 21 (profiles/r6_row_sum_order.txt): the order
 // a = 0 .. A-1 reproduces the bits of torch.sum on the AVX-512 host in 38 % of the rows, four partial sums + butterfly
 // (rounds 3 - 5) in 51 %, the correctly rounded sum in 56 % - and it is the only one of them that is within half an ulp
-// of EVERY fp32 summation order's target, on any machine.  RLG_LOSS_ROWSUM_F64=0: fp32 partial sums (the round-5 bits).
-#ifndef RLG_LOSS_ROWSUM_F64
-#define RLG_LOSS_ROWSUM_F64 1
-#endif
-#if RLG_LOSS_ROWSUM_F64
+// of EVERY fp32 summation order's target, on any machine.  (fp32 partial sums, rounds 3 - 5: right in 51 % of the rows.)
 typedef double row_acc_t;
-#else
-typedef float row_acc_t;
-#endif
 
 struct LossArgs {
   // network outputs

@@ -8,10 +8,6 @@ namespace rlg {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-#ifndef RLG_SPLIT_PK
-#define RLG_SPLIT_PK 1           // 0: scalar residuals (v_sub_f32), the round-2 form - same bits, 11 instead of 9 VALU per pair
-#endif
-
 typedef float split_f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 split_bf16x2 __attribute__((ext_vector_type(2)));
 
@@ -29,26 +25,16 @@ __device__ __forceinline__ unsigned cvt_pk_bf16(float lo, float hi) {
 // operand (exact: the residual has <= 16 (8) significant bits) = 9 VALU instructions; the splitting is the largest
 // VALU item of every split-product kernel.  (Round 6, profiles/r6_coexec_bf16.txt: beside v_mfma_f32_16x16x32_bf16 plain
 // VALU instructions overlap, v_pk_add_f32 does NOT - one per MFMA costs + 16.5 cycles.  The loops that call this split do not
-// interleave it with MFMAs - they split, then multiply - and with RLG_SPLIT_PK=0 -fno-slp-vectorize (scalar residuals) they
-// measured 3 us faster in the weight-gradient launch and 4 us slower in the forward: the packed form stays the default; a loop
-// that DOES deal the split out between MFMAs must use the scalar form.)
+// interleave it with MFMAs - they split, then multiply.  Scalar residuals (two v_sub_f32, the round-2 form: the same bits,
+// 11 instead of 9 VALU per pair) measured 3 us faster in the weight-gradient launch and 4 us slower in the forward: the
+// packed form stays; a loop that DOES deal the split out between MFMAs must use scalar residuals.)
 __device__ __forceinline__ void split_pair(split_f32x2 r, unsigned& p0, unsigned& p1, unsigned& p2) {
   unsigned w = cvt_pk_bf16(r[0], r[1]);
   p0 = w;
-#if RLG_SPLIT_PK
   r = r - split_f32x2{__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)};
-#else
-  r[0] -= __uint_as_float(w << 16);
-  r[1] -= __uint_as_float(w & 0xffff0000u);
-#endif
   w = cvt_pk_bf16(r[0], r[1]);
   p1 = w;
-#if RLG_SPLIT_PK
   r = r - split_f32x2{__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)};
-#else
-  r[0] -= __uint_as_float(w << 16);
-  r[1] -= __uint_as_float(w & 0xffff0000u);
-#endif
   w = cvt_pk_bf16(r[0], r[1]);
   p2 = w;
 }
@@ -70,17 +56,6 @@ __device__ __forceinline__ void dw_split8(const float (&x)[8], u32x4 (&plane)[3]
 // (adjacent registers as loaded - pairing the rows would cost two moves per pair), the conversion pairs the rows of a
 // column as the MFMA operand wants them.  Same values as two dw_split8 calls.
 __device__ __forceinline__ void dw_split8x2(const split_f32x2 (&x)[8], u32x4 (&plane_a)[3], u32x4 (&plane_b)[3]) {
-#if !RLG_SPLIT_PK
-  float xa[8], xb[8];
-#pragma unroll
-  for (int u = 0; u < 8; ++u) {
-    xa[u] = x[u][0];
-    xb[u] = x[u][1];
-  }
-  dw_split8(xa, plane_a);
-  dw_split8(xb, plane_b);
-  return;
-#endif
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     split_f32x2 r0 = x[2 * q], r1 = x[2 * q + 1];           // rows 2q, 2q + 1; [0] = column a, [1] = column a + 1
@@ -95,13 +70,6 @@ __device__ __forceinline__ void dw_split8x2(const split_f32x2 (&x)[8], u32x4 (&p
       }
     }
   }
-}
-
-// 4 floats -> 3 planes of 2 dwords (4 packed bf16), same pairing as dw_split8
-__device__ __forceinline__ void split4_planes(const f32x4& x, unsigned (&plane)[3][2]) {
-#pragma unroll
-  for (int q = 0; q < 2; ++q)
-    split_pair(split_f32x2{x[2 * q], x[2 * q + 1]}, plane[0][q], plane[1][q], plane[2][q]);
 }
 
 }  // namespace rlg

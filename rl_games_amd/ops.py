@@ -790,9 +790,8 @@ SPLIT_SCALE_OBS_NORM = 4096.0
 
 
 def chain_split_form():
-    """(plane products per fp32 product, plane type) of this build's split-product chain kernels: (3, 'fp16') or (6, 'bf16')."""
-    k = int(_lib.load().rlg_mlp_chain_split_products())
-    return k, ('fp16' if k == 3 else 'bf16')
+    """(plane products per fp32 product, plane type) of the split-product chain kernels: (3, 'fp16')."""
+    return int(_lib.load().rlg_mlp_chain_split_products()), 'fp16'
 
 
 def _time_chain_launch(kind):
@@ -884,12 +883,9 @@ class MlpChain:
         return self._grad_maxima
 
     def _request_lean_maxima(self, rows):
-        """The lean 16-row backward / one-launch step (fp16 form) leaves one gradient-maxima entry per 16-row workgroup."""
-        if chain_split_form()[1] != 'fp16':
-            return False
+        """The lean 16-row backward / one-launch step leaves one gradient-maxima entry per 16-row workgroup."""
         buf = self._grad_maxima_buffer(rows, 16)
         _lib.load().rlg_mlp_chain_gradient_maxima(buf.data_ptr(), buf.shape[1])
-        return True
 
     def gradient_maxima(self, rows):
         """[8, entries] fp32: row l = per 64-row workgroup the largest |dZ of layer l| of the backward of this step - when
@@ -1160,15 +1156,14 @@ class MlpChain:
             # backward as two launches (the caller's fallback), which beat the pipelined one-launch step
             self.ensure_frags(x)
             self._maxima_bwd = None
-            lean_maxima = self._request_lean_maxima(rows)
+            self._request_lean_maxima(rows)
             err = _timed_chain_call('step16', _lib.load().rlg_mlp_chain_step_lean, n, self._b, self._in, self._out, self._act,
                                     *fwd, *bwd, self._frags_ptr(0), self._frags_ptr(1), _stream(x))
             if err == 801:
                 return False
             _lib.check(err, 'rlg_mlp_chain_step_lean')
             self._planes_fresh = None
-            if lean_maxima:
-                self._maxima_bwd, self.maxima_rows_per_entry = rows, 16
+            self._maxima_bwd, self.maxima_rows_per_entry = rows, 16
             return True
         err = _timed_chain_call('step16', _lib.load().rlg_mlp_chain_step, n, self._w, self._b, self._in, self._out, self._act,
                                 *fwd, *bwd, _stream(x))
@@ -1195,15 +1190,14 @@ class MlpChain:
             self._planes_fresh = None
             self._maxima_bwd = None
             self.ensure_frags(d_heads)
-            lean_maxima = self._request_lean_maxima(rows)
+            self._request_lean_maxima(rows)
             err = _timed_chain_call(
                 'bwd_loss' if ppo_loss is not None else 'bwd', _lib.load().rlg_mlp_chain_backward_lean,
                 n, self._in, self._out, self._act, h, hl, d_heads.data_ptr(), d_heads.stride(0), dz, dl, bp,
                 None if ppo_loss is None else ctypes.addressof(ppo_loss), rows, self._frags_ptr(1), _stream(d_heads))
             if err != 801:
                 _lib.check(err, 'rlg_mlp_chain_backward_lean')
-                if lean_maxima:
-                    self._maxima_bwd, self.maxima_rows_per_entry = rows, 16
+                self._maxima_bwd, self.maxima_rows_per_entry = rows, 16
                 return
         planes = None
         if split_products is not False and self.split_products(rows, 1, groups):
@@ -1213,7 +1207,7 @@ class MlpChain:
         # the split-fp16 launch leaves the gradient maxima the weight-gradient launch scales by - claimed only where the
         # library is sure to take that launch (chain_bx_bwd_eligible: 16-byte aligned H / dZ rows of 4-float groups)
         left_maxima = False
-        if planes is not None and chain_split_form()[1] == 'fp16' and all(
+        if planes is not None and all(
                 t.data_ptr() % 16 == 0 and t.stride(0) % 4 == 0 and t.shape[1] % 4 == 0 for t in list(acts) + list(dz_out)):
             buf = self._grad_maxima_buffer(rows)
             _lib.load().rlg_mlp_chain_gradient_maxima(buf.data_ptr(), buf.shape[1])

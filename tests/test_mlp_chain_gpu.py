@@ -554,17 +554,11 @@ def test_dw_exact_f32_product_form_passes_the_same_tests():
 
 # ------------------------------------------------------------------ split-bf16 chain (csrc/mlp_chain_bx.hip)
 
-def _bf16_bits_to_f64(u16):
-    return (u16.to(torch.int32) << 16).view(torch.float32).double()
-
-
 def _split_form():
-    """(planes per operand, plane bits -> fp64, weight scale) of this build's split-product chain kernels."""
+    """(planes per operand, weight scale) of the split-product chain kernels."""
     from rl_games_amd import ops
-    products, ptype = ops.chain_split_form()
-    if ptype == 'fp16':
-        return 2, (lambda u16: u16.view(torch.float16).double()), 64.0           # csrc/bx_form.hpp kBxScaleW
-    return 3, _bf16_bits_to_f64, 1.0
+    assert ops.chain_split_form() == (3, 'fp16')
+    return 2, 64.0           # csrc/bx_form.hpp kBxPlanes, kBxScaleW
 
 
 @pytest.mark.parametrize('direction', [0, 1])
@@ -572,15 +566,14 @@ def _split_form():
 def test_weight_planes_are_a_split_in_fragment_order(in_dim, units, out_dim, act, direction):
     """rlg_mlp_chain_pack_planes: fragment (block, chunk, plane) = 64 lanes x 8 half-width values; lane l, element e holds
     A[16 block + (l & 15)][32 chunk + (e < 4 ? 4 (l >> 4) + e : 16 + 4 (l >> 4) + e - 4)], A = W (forward) or W^T
-    (backward), zero outside the matrix.  fp16 form (the default build): two planes of 64 W, h0 = RN16(64 W) and
-    h1 = RN16(64 W - h0) bit for bit, their sum within 2^-22 of 64 W (2^-25 absolute below the fp16 normal range);
-    bf16 form: the three planes add up to the fp32 weight EXACTLY."""
+    (backward), zero outside the matrix.  Two fp16 planes of 64 W, h0 = RN16(64 W) and h1 = RN16(64 W - h0) bit for bit,
+    their sum within 2^-22 of 64 W (2^-25 absolute below the fp16 normal range)."""
     from rl_games_amd import ops
     layers, _ = _net(in_dim, units, out_dim, act, seed=5 + in_dim)
     chain = ops.MlpChain(layers, DEV)
     planes = chain.pack_planes(direction, layers[0][0])
     torch.cuda.synchronize()
-    np_, to64, wscale = _split_form()
+    np_, wscale = _split_form()
     raw = planes.cpu().view(torch.int16)
     off = 0
     lane = torch.arange(64)
@@ -600,16 +593,12 @@ def test_weight_planes_are_a_split_in_fragment_order(in_dim, units, out_dim, act
         inside = (i < I) & (k < K)
         want = torch.zeros(nb, kc, 64, 8, dtype=torch.float32)
         want[inside] = A[i[inside], k[inside]] * wscale
-        if np_ == 3:
-            total = sum(to64(frag[:, :, p]) for p in range(3))          # [nb, kc, 64, 8]
-            assert torch.equal(total, want.double())
-        else:
-            h0 = want.half()
-            h1 = (want - h0.float()).half()
-            assert torch.equal(frag[:, :, 0].contiguous().view(torch.float16), h0)
-            assert torch.equal(frag[:, :, 1].contiguous().view(torch.float16), h1)
-            err = (h0.double() + h1.double() - want.double()).abs()
-            assert torch.all(err <= torch.maximum(want.double().abs() * 2.0 ** -22, torch.tensor(2.0 ** -25, dtype=torch.float64)))
+        h0 = want.half()
+        h1 = (want - h0.float()).half()
+        assert torch.equal(frag[:, :, 0].contiguous().view(torch.float16), h0)
+        assert torch.equal(frag[:, :, 1].contiguous().view(torch.float16), h1)
+        err = (h0.double() + h1.double() - want.double()).abs()
+        assert torch.all(err <= torch.maximum(want.double().abs() * 2.0 ** -22, torch.tensor(2.0 ** -25, dtype=torch.float64)))
     assert off == planes.numel()
     if direction == 1:
         # one launch for both directions leaves the same fragments (the backward ones behind the forward ones)
@@ -895,8 +884,7 @@ def test_lean_kernels_against_the_pipelined_ones(rows, monkeypatch):
     they replace (RLG_CHAIN_LEAN=0; their own one-launch step included) - heads, activations, normalised observations, d heads,
     loss partials, dZ and bias partial sums, ragged last tile included.  Round 6: the lean kernels run three fp16 plane
     products per fp32 product - within the split kernels' tolerance of the exact-product kernels (4e-6 of a tensor's scale),
-    the lean forward + backward pair and the lean one-launch step bit-identical to each other; a -DRLG_BX_F16=0 build runs
-    exact fp32 products in the pipelined kernels' order: everything bit for bit.  Both: within 1e-6 of fp64."""
+    the lean forward + backward pair and the lean one-launch step bit-identical to each other.  Both: within 1e-6 of fp64."""
     from rl_games_amd import ops
     layers, g = _net(108, [400, 200, 100], 22, 'elu', seed=3)
     x = (3 * torch.randn(rows, 108, generator=g) + 1).to(DEV)
@@ -932,12 +920,11 @@ def test_lean_kernels_against_the_pipelined_ones(rows, monkeypatch):
             chain.backward(dh, acts, dzs, parts, ppo_loss=desc)
         torch.cuda.synchronize()
         out[mode] = [heads, xn, dh, partials, om, osg] + acts + dzs + parts
-    exact_lean = ops.chain_split_form()[1] != 'fp16'
     for k, (a, b, c, d) in enumerate(zip(out['pipe'], out['lean'], out['lean_step'], out['pipe_step'])):
         assert torch.isfinite(a.double()).all(), k
         assert torch.equal(a, d), k
         assert torch.equal(b, c), k
-        if exact_lean or k == 1:                                   # (k = 1: the normalised observations - no product in them)
+        if k == 1:                                                 # (the normalised observations - no product in them)
             assert torch.equal(a, b), k
         else:
             assert torch.isfinite(b.double()).all(), k
@@ -958,11 +945,6 @@ def test_lean_kernels_against_the_pipelined_ones(rows, monkeypatch):
 
 # ----------------------------------------------------------------------------- split-fp16 form (round 6)
 
-def _fp16_form():
-    from rl_games_amd import ops
-    return ops.chain_split_form()[1] == 'fp16'
-
-
 @pytest.mark.parametrize('rows,per', [(32768, 64), (16384 + 640, 64), (4096, 64), (4096, 16), (1000, 16)])
 def test_dw_fp16_form_with_per_wave_gradient_scales_matches_fp64(rows, per):
     """The weight-gradient launch on three fp16 plane products (MlpDwPlan.launch(maxima=...)): dZ whose magnitude varies
@@ -971,8 +953,6 @@ def test_dw_fp16_form_with_per_wave_gradient_scales_matches_fp64(rows, per):
     all-zero rows (entry 0), activations under the forward's fixed scales - against fp64, judged like the bf16 form, and
     beside it."""
     from rl_games_amd import ops
-    if not _fp16_form():
-        pytest.skip('bf16 build')
     g = torch.Generator().manual_seed(rows)
     shapes = [(200, 400), (400, 108), (100, 200), (22, 100)]
     nblk = -(-rows // per)
@@ -1011,8 +991,6 @@ def test_split_fp16_backward_scales_gradient_rows_by_their_own_maxima(rows):
     neighbours gives the same dZ bits as in a tile of rows like itself, and the gradient maxima it leaves for the
     weight-gradient launch are the per-workgroup maxima (64 rows; 16 for the lean kernels of a 4,096-row launch) of what it wrote."""
     from rl_games_amd import ops
-    if not _fp16_form():
-        pytest.skip('bf16 build')
     layers, g = _net(60, [256, 128], 9, 'elu', seed=31)
     chain = ops.MlpChain(layers, DEV)
     assert chain.split_products(rows, 1) == (rows >= 8192) and chain.lean_used(rows, 1) == (rows < 8192)
@@ -1049,8 +1027,6 @@ def test_split_fp16_range_limits_end_in_non_finite_values_never_in_wrong_ones():
     Inf and what is computed from them is Inf / NaN - in the rows concerned (an activation) or everywhere (a weight) -
     while everything inside the range is what the exact-product kernels give."""
     from rl_games_amd import ops
-    if not _fp16_form():
-        pytest.skip('bf16 build')
     rows = 16384
     layers, g = _net(60, [256, 128], 9, 'elu', seed=32)
     x = torch.randn(rows, 60, generator=g).to(DEV)

@@ -135,8 +135,7 @@ def _arr(vals):
 
 def test_chain_plane_buffer_sizes_and_envelope_of_the_split_kernels():
     """rlg_mlp_chain_planes_bytes / _offset / _bx_supported are host logic of the C ABI: fragment counts (16-row blocks
-    x 32-column chunks x the planes of 1 KiB - two fp16 planes, or three bf16 planes in a -DRLG_BX_F16=0 build; the
-    backward needs none for layer 0), the combined buffer of both
+    x 32-column chunks x two fp16 planes of 1 KiB; the backward needs none for layer 0), the combined buffer of both
     directions, and the envelope - minibatches of >= 16,384 rows; the forward's LDS plan must fit (a windowed
     400- or 512-wide tile is fine, a windowed tile whose consumer has more than 256 outputs is not)."""
     from rl_games_amd import _lib
@@ -145,9 +144,8 @@ def test_chain_plane_buffer_sizes_and_envelope_of_the_split_kernels():
     n = len(ins)
     blocks = lambda v: -(-v // 16)
     chunks = lambda v: -(-v // 32)
-    products = lib.rlg_mlp_chain_split_products()
-    assert products in (3, 6)
-    chunk = 1024 * {3: 2, 6: 3}[products]
+    assert lib.rlg_mlp_chain_split_products() == 3
+    chunk = 1024 * 2
     fwd = sum(blocks(o) * chunks(i) * chunk for i, o in zip(ins, outs))
     bwd = sum(blocks(i) * chunks(o) * chunk for i, o in list(zip(ins, outs))[1:])
     assert lib.rlg_mlp_chain_planes_bytes(n, _arr(ins), _arr(outs), 0) == fwd

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B rows of bench.py inside ONE gpurun call (box-to-box spread is +-3 %): each argument is "label:ENV=VAL,ENV=VAL"
-#     gpurun -- tools/bench_ab.sh "pipe4:RLG_CHAIN_FWD_GROUPS=4" "old2:RLG_CHAIN_PIPE=0"
+#     tools/bench_ab.sh "product:" "exact:RLG_CHAIN_BX=0" "variant:RLG_HIP_LIB=tools/exp/_build/name.so"
 cd "$(dirname "$0")/.."
 OUT=gpurun_out/ab; mkdir -p $OUT
 for spec in "$@"; do

@@ -1,5 +1,5 @@
-"""Forward chain: split-bf16 kernel (csrc/mlp_chain_bx_fwd.hip, RLG_CHAIN_BX_FWD=1) against fp64 torch and the
-exact-product kernels, then timing.    RLG_CHAIN_BX_FWD=1 python tools/exp/bx_fwd_check.py [rows]"""
+"""Forward chain: split-product kernel (csrc/mlp_chain_bx_fwd.hip) against fp64 torch and the
+exact-product kernels, then timing.    python tools/exp/bx_fwd_check.py [rows]"""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))

@@ -30,7 +30,7 @@ for L in range(3, 0, -1):
     full, rem = NOB // 4, (NOB % 4) * 4
     names += [f'dZ{L - 1} units', f'dZ{L - 1} barrier']
     ideal += [-(-NOB // 4) * KC * 4 * 6 * 16, 0]
-# (the fine stamps inside the two-block units of the last step exist only in a 4-wave build, RLG_BX_BWD_W=4: the 8-wave
+# (the fine stamps inside the two-block units of the last step went with the 4-wave kernel of rounds 3 - 5: the 8-wave
 #  kernel runs one block per unit and stamps the layers only; `ideal`: MFMA issue cycles of the wave with the most blocks at
 #  3 products x 16 cycles per chunk and row group)
 ideal = [0, 0, 0]

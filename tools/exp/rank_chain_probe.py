@@ -1,7 +1,7 @@
 """Chain launches at a data-parallel rank's minibatch sizes (4,096 / 8,192 rows) on the network laid out like the
 optimiser's arena (the pipelined kernels need it): time per launch of the training / inference forward and of the
-backward, and the forward's phase stamps.  Variants are selected by the environment (RLG_CHAIN_PIPE1, RLG_PIPE1_WAVES,
-RLG_CHAIN_WAVES), one process each.      python tools/exp/rank_chain_probe.py [rows ...] [--phases]"""
+backward, and the forward's phase stamps.  Variants are selected by the environment (RLG_CHAIN_LEAN, RLG_CHAIN_BX), one
+process each.      python tools/exp/rank_chain_probe.py [rows ...] [--phases]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
@@ -25,7 +25,7 @@ for u, i in shapes:
 layers[-1] = (layers[-1][0], layers[-1][1], 'None')
 chain = ops.MlpChain(layers, dev)
 macs_f = sum(u * i for u, i in shapes); macs_b = sum(u * i for u, i in shapes[1:])
-env = {k: os.environ.get(k) for k in ('RLG_CHAIN_PIPE1', 'RLG_PIPE1_WAVES', 'RLG_CHAIN_WAVES')}
+env = {k: os.environ.get(k) for k in ('RLG_CHAIN_LEAN', 'RLG_CHAIN_BX')}
 
 def timeit(fn, reps=100):
     for _ in range(5):

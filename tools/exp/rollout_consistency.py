@@ -1,6 +1,6 @@
 """Is the agent's rollout (mus, values stored in the buffer) what the oracle's network computes from the same
 observations and the model state the rollout was played with?  Per epoch: max |mu_rollout - mu_oracle| etc., and the
-3-epoch parameter drift.   python tools/exp/rollout_consistency.py   (variants by environment, e.g. RLG_CHAIN_PIPE1=0)"""
+3-epoch parameter drift.   python tools/exp/rollout_consistency.py   (variants by environment, e.g. RLG_CHAIN_LEAN=0)"""
 import copy, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
@@ -26,7 +26,7 @@ agent.play_steps = play
 cpu = copy.deepcopy(params); cpu['config']['device'] = 'cpu'
 torch.set_num_threads(16)
 oracle = None
-print('env', {k: os.environ.get(k) for k in ('RLG_CHAIN_PIPE1', 'RLG_PIPE1_WAVES')})
+print('env', {k: os.environ.get(k) for k in ('RLG_CHAIN_LEAN', 'RLG_CHAIN_BX')})
 for epoch in range(3):
     agent.update_epoch(); res = agent.train_epoch()
     cap = caps[epoch]
