@@ -435,8 +435,9 @@ int rlg_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq
  * matrix writes its rows as forward fragments and its columns as backward fragments (csrc/mlp_chain_bx.hip,
  * adam_pack_kernel) - one launch instead of rlg_adam_step + rlg_mlp_chain_pack_planes per optimiser step, and no pack
  * launch in front of the rollout forwards.  Same Adam arithmetic, same plane bytes.  hipErrorInvalidValue (use the
- * two launches) unless every weights[l] lies inside [params, params + n) at a multiple of 4 floats with
- * in_features[l] % 4 == 0; `planes` must have been packed in full once (the zero padding of the fragments). */
+ * two launches) unless the four arenas are 16-byte aligned (as for rlg_adam_step) and every weights[l] lies inside
+ * [params, params + n) at a multiple of 4 floats with in_features[l] % 4 == 0; `planes` must have been packed in full
+ * once (the zero padding of the fragments). */
 int rlg_adam_step_pack(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long long n,
                        const double* norm_partials_or_null, int norm_blocks, float grad_scale, float max_norm,
                        double* lr_slots, const long long* step_counter, double beta1, double beta2, double eps,

@@ -438,6 +438,70 @@ def clip_and_adam_reference(params, grads, exp_avg, exp_avg_sq, step, lr, grad_n
             [opt.state[p]['exp_avg_sq'] for p in ps], total_norm)
 
 
+def adam_step_fp64(p, g, m, v, step, lr, grad_scale, max_norm, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    """One optimiser step in fp64 on fp32 inputs (numpy arrays): the formulas of the comment block of
+    csrc/optim_common.hpp, i.e. g * grad_scale, clip_grad_norm_ with clip_coef = min(max_norm / (norm + 1e-6), 1)
+    (max_norm None: no truncation, norm 0 and coefficient 1) and torch's single-tensor Adam.  `step` is the 1-based count
+    of THIS update.  grad_scale is rounded to fp32 first, as ops.adam_step hands it to the kernel.  NaN propagates like
+    torch.clamp: a NaN norm gives a NaN coefficient.
+    Returns a dict: p, g (the clipped gradient), m, v, norm, clip and `scale` - per element the magnitude that the
+    rounding errors of an fp32 evaluation are proportional to: p: |p| + |update|, g: |g * scale|,
+    m: max(|m|, |g_c| + |wd * p|), v: max(v, v')."""
+    p, g, m, v = (np.asarray(x, dtype=np.float32).astype(np.float64) for x in (p, g, m, v))
+    gs = g * float(np.float32(grad_scale))
+    norm, clip = 0.0, 1.0
+    if max_norm is not None:
+        with np.errstate(all='ignore'):
+            norm = math.sqrt(float(np.sum(gs * gs)))
+        clip = float(max_norm) / (norm + 1e-6)
+        if not clip != clip and clip > 1.0:
+            clip = 1.0
+    with np.errstate(all='ignore'):
+        gc = gs * clip
+        gg = gc + weight_decay * p if weight_decay != 0 else gc
+        m2 = m + (1.0 - betas[0]) * (gg - m)
+        v2 = v * betas[1] + (1.0 - betas[1]) * gg * gg
+        bc1 = 1.0 - betas[0] ** step
+        bc2 = 1.0 - betas[1] ** step
+        denom = np.sqrt(v2) / math.sqrt(bc2) + eps
+        update = (lr / bc1) * (m2 / denom)
+        scale = dict(p=np.abs(p) + np.abs(update), g=np.abs(gs),
+                     m=np.maximum(np.abs(m), np.abs(gc) + np.abs(weight_decay * p)), v=np.maximum(v, v2))
+    return dict(p=p - update, g=gc, m=m2, v=v2, norm=norm, clip=clip, scale=scale)
+
+
+def adam_step_f32_emulation(p, g, m, v, step, lr, grad_scale, max_norm, betas=(0.9, 0.999), eps=1e-8,
+                            weight_decay=0.0):
+    """The same step as the kernels evaluate it: adam_update's op chain (csrc/optim_common.hpp) in numpy fp32, one
+    rounding per operation and in the order written there, with the scalar prologue in Python doubles rounded to fp32
+    once.  The norm is the fp64 sum of squares of the fp32-rounded g * grad_scale, then float32(sqrt).  It exists to
+    calibrate the tolerance of the device tests (tests/test_optim_cpu.py), not as a reference.
+    Returns a dict: p, g, m, v (fp32 arrays), norm, clip (np.float32)."""
+    f32 = np.float32
+    p, g, m, v = (np.asarray(x, dtype=f32) for x in (p, g, m, v))
+    with np.errstate(all='ignore'):
+        gs = g * f32(grad_scale)
+        norm, clip = f32(0.0), f32(1.0)
+        if max_norm is not None:
+            norm = f32(math.sqrt(float(np.sum(gs.astype(np.float64) ** 2))))
+            clip = f32(max_norm) / (norm + f32(1e-6))
+            if not clip != clip and clip > f32(1.0):
+                clip = f32(1.0)
+        gc = gs * clip
+        step_size = f32(lr / (1.0 - betas[0] ** step))
+        bc2_sqrt = f32(math.sqrt(1.0 - betas[1] ** step))
+        w1, b2, w2 = f32(1.0 - betas[0]), f32(betas[1]), f32(1.0 - betas[1])
+        wd = f32(weight_decay)
+        gg = gc + wd * p if wd != 0 else gc
+        m2 = m + w1 * (gg - m)
+        v2 = v * b2 + (w2 * gg) * gg
+        denom = np.sqrt(v2) / bc2_sqrt + f32(eps)
+        p2 = p - step_size * (m2 / denom)
+    for x in (gc, m2, v2, p2):
+        assert x.dtype == f32
+    return dict(p=p2, g=gc, m=m2, v=v2, norm=norm, clip=f32(clip))
+
+
 # --------------------------------------------------------------------------------------
 # a19 - cross-rank pooled merge of RunningMeanStd
 # --------------------------------------------------------------------------------------

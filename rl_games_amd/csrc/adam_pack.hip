@@ -225,7 +225,8 @@ extern "C" {
 // rlg_adam_step that also leaves the chain's weight planes (both directions, the layout of rlg_mlp_chain_pack_planes
 // direction 2) for the NEW weights - see adam_pack_kernel.  Requirements (else hipErrorInvalidValue, and the caller
 // uses rlg_adam_step + rlg_mlp_chain_pack_planes): every weight matrix lies inside [params, params + n), 16-byte
-// aligned relative to it, with in_features % 4 == 0; `planes` has been packed in full once (the zero padding).
+// aligned relative to it, with in_features % 4 == 0; the four arenas are 16-byte aligned; `planes` has been packed in
+// full once (the zero padding).
 int rlg_adam_step_pack(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long long n,
                        const double* norm_partials_or_null, int norm_blocks, float grad_scale, float max_norm,
                        double* lr_slots, const long long* step_counter, double beta1, double beta2, double eps,
@@ -237,6 +238,10 @@ int rlg_adam_step_pack(float* params, float* grads, float* exp_avg, float* exp_a
   if (n <= 0 || !step_counter || num_layers < 1 || num_layers > kChainMaxLayers || planes == nullptr)
     return static_cast<int>(hipErrorInvalidValue);
   if (schedule_kind == 1 && !kl_or_null) return static_cast<int>(hipErrorInvalidValue);
+  // (16-byte loads relative to the arenas, like rlg_adam_step)
+  if ((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grads) | reinterpret_cast<uintptr_t>(exp_avg) |
+       reinterpret_cast<uintptr_t>(exp_avg_sq)) % 16 != 0)
+    return static_cast<int>(hipErrorInvalidValue);
   AdamPackArgs ap;
   AdamArgs& a = ap.adam;
   a.params = params;

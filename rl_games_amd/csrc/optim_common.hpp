@@ -1,4 +1,5 @@
-// Pieces of the optimiser step shared by adam_step_kernel (optim.hip) and the fused finalise + Adam launch (mlp_dw.hip).
+// Pieces of the optimiser step shared by adam_step_kernel (optim.hip) and adam_pack_kernel (adam_pack.hip).  (mlp_dw.hip
+// only produces the norm partials these read.)
 #pragma once
 
 #include "rlg_device.hpp"
@@ -66,8 +67,12 @@ __device__ __forceinline__ void adam_update(const AdamArgs& a, const AdamScalars
   a.params[i] = p;
 }
 // clip_coef = max_norm / (total_norm + 1e-6); clamp(max=1.0)       torch clip_grad_norm_
+// torch.clamp propagates NaN while fminf returns its non-NaN operand: a NaN norm (one NaN gradient) is passed on, so that
+// every gradient, moment and parameter becomes NaN as in the reference, and stats_out[1] is NaN.  An infinite norm gives
+// 0 on both sides (only the infinite gradients turn into NaN).
 __device__ __forceinline__ float adam_clip_coef(float max_norm, float total_norm) {
-  return fminf(max_norm / (total_norm + 1e-6f), 1.0f);
+  const float coef = fminf(max_norm / (total_norm + 1e-6f), 1.0f);
+  return total_norm != total_norm ? total_norm : coef;
 }
 // AdaptiveScheduler.update in python-float arithmetic (schedulers.py:27-33) + the statistics row; one thread
 __device__ __forceinline__ void adam_finish(const AdamArgs& a, int cur, double lr, bool skip, float total_norm, float clip) {

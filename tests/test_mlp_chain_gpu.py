@@ -876,6 +876,161 @@ def test_adam_step_pack_equals_adam_then_pack(in_dim, units, out_dim):
     assert torch.equal(res['fused_skipped'][6], chain._plane_buffer())
 
 
+def _arena_net(in_dim, units, out_dim, seed, front=0, back=0):
+    """_net's layout - every weight matrix followed by its bias - as views into a larger arena with `front` parameters
+    in front of the first matrix and `back` behind the last bias (where sigma sits in the agent's arena): flat ranges of
+    adam_pack_kernel at both ends.  Returns (layers, arena, generator)."""
+    g = torch.Generator().manual_seed(seed)
+    shapes, last = [], in_dim
+    for u in list(units) + [out_dim]:
+        shapes.append((u, last))
+        last = u
+    n = front + sum(u * i + u for u, i in shapes) + back
+    flat = (0.1 * torch.randn(n, generator=g)).to(DEV)
+    assert flat.data_ptr() % 16 == 0 and front % 4 == 0
+    layers, off = [], front
+    for u, i in shapes:
+        wv, bv = flat[off:off + u * i].view(u, i), flat[off + u * i:off + u * i + u]
+        wv.copy_(torch.randn(u, i, generator=g) / i ** 0.5)
+        off += u * i + u
+        layers.append((wv, bv, 'elu'))
+    return layers, flat, g
+
+
+def _bit_equal(a, b):
+    view = {1: torch.uint8, 4: torch.int32, 8: torch.int64}[a.element_size()]
+    return a.dtype == b.dtype and torch.equal(a.contiguous().view(view), b.contiguous().view(view))
+
+
+ADAM_PACK_LR = 3e-4
+
+
+def _adam_pack_forms(layers, params, gen, counter, weight_decay=0.0, truncate=True, schedule_kind=1, partials=None,
+                     nan_at=None, twins=()):
+    """One optimiser step at step count `counter` as rlg_adam_step + pack ('pair'), as rlg_adam_step_pack ('fused') and
+    as rlg_adam_step_pack behind a set skip flag ('fused_skipped'), each from the same state.  partials: a norm-partials
+    tensor of another launch instead of the gradients' own sums.  twins: (source, destination) element pairs that are
+    given the same (p, g, m, v).  Returns ({form: (p, g, m, v, lr slots, stats, planes)}, the inputs (p, g, m, v),
+    the planes of the old weights)."""
+    from rl_games_amd import ops
+    n = params.numel()
+    grads = (0.1 * torch.randn(n, generator=gen)).to(DEV)
+    m0 = (0.01 * torch.randn(n, generator=gen)).to(DEV)
+    v0 = (0.001 * torch.rand(n, generator=gen)).to(DEV)
+    if nan_at is not None:
+        grads[nan_at] = float('nan')
+    for src, dst in twins:
+        for t in (params, grads, m0, v0):
+            t[dst] = t[src]
+    init = params.clone()
+    chain = ops.MlpChain(layers, DEV, weights_version=lambda: 0)
+    cur = (counter - 1) & 1
+    res = {}
+    for mode in ('pair', 'fused', 'fused_skipped'):
+        params.copy_(init)
+        g_, m_, v_ = grads.clone(), m0.clone(), v0.clone()
+        slots = [7.0, 7.0]                                  # (the slot that is not read holds something else)
+        slots[cur] = ADAM_PACK_LR
+        lr_slots = torch.tensor(slots, dtype=torch.float64, device=DEV)
+        step_counter = torch.tensor([counter], dtype=torch.int64, device=DEV)
+        norm = None
+        if partials is not None:
+            norm = partials
+        elif truncate:
+            norm = torch.zeros(ops.grad_norm_blocks(n), dtype=torch.float64, device=DEV)
+            ops.grad_sumsq(g_, 1.0, norm, None)
+        kl = torch.tensor([0.001], device=DEV)
+        stats = torch.full((4,), -1.0, device=DEV)
+        skip = torch.tensor([1 if mode == 'fused_skipped' else 0], dtype=torch.int32, device=DEV)
+        kw = dict(betas=(0.9, 0.999), eps=1e-8, weight_decay=weight_decay, schedule_kind=schedule_kind, kl=kl, kl_scale=1.0,
+                  kl_threshold=0.008, min_lr=1e-6, max_lr=1e-2, lr_multiplier=1.5, stats_out=stats, skip_flag=skip.data_ptr())
+        target = chain.adam_pack_target()
+        if mode == 'pair':
+            ops.adam_step(params, g_, m_, v_, norm, 1.0, 0.5, lr_slots, step_counter, **kw)
+            chain._plane_buffer().fill_(0x5a)
+            chain.pack_planes(2, params)
+        else:
+            chain.pack_planes(2, params)
+            ops.adam_step(params, g_, m_, v_, norm, 1.0, 0.5, lr_slots, step_counter, pack=target, **kw)
+        torch.cuda.synchronize()
+        res[mode] = (params.clone(), g_, m_, v_, lr_slots.clone(), stats.clone(), chain._plane_buffer().clone())
+    params.copy_(init)
+    chain.pack_planes(2, params)
+    torch.cuda.synchronize()
+    return res, (init, grads, m0, v0), chain._plane_buffer().clone()
+
+
+def _check_adam_pack_forms(res, inputs, old_planes, counter, twins=()):
+    names = ('params', 'clipped gradients', 'exp_avg', 'exp_avg_sq', 'lr slots', 'stats', 'planes')
+    for name, a, b in zip(names, res['pair'], res['fused']):
+        assert _bit_equal(a, b), name
+    # a skipped step: all four arenas and the planes are those of the old state, the lr is carried over, the statistics
+    # row is written
+    skipped = res['fused_skipped']
+    for name, a, b in zip(names[:4], skipped[:4], inputs):
+        assert _bit_equal(a, b), name
+    assert _bit_equal(skipped[6], old_planes)
+    cur = (counter - 1) & 1
+    assert skipped[4][cur].item() == ADAM_PACK_LR and skipped[4][cur ^ 1].item() == ADAM_PACK_LR
+    assert _bit_equal(skipped[5][:3], res['fused'][5][:3]) and skipped[5][3].item() == res['fused'][5][2].item()
+    # the 4 x 4 blocks of the matrices and the flat ranges compute the same function of (p, g, m, v)
+    for src, dst in twins:
+        for name, t in zip(names[:4], res['fused'][:4]):
+            assert _bit_equal(t[src:src + 1], t[dst:dst + 1]), (name, src, dst)
+
+
+@pytest.mark.parametrize('variant', ['weight_decay', 'no_truncation', 'keep_lr', 'nan_gradient'])
+@pytest.mark.parametrize('in_dim,units,out_dim,front,back', [(12, [100, 52], 22, 0, 0), (20, [44, 28], 22, 8, 21)])
+def test_adam_step_pack_options_equal_adam_then_pack(in_dim, units, out_dim, front, back, variant):
+    """The options that test_adam_step_pack_equals_adam_then_pack leaves out, bit for bit between the two forms: weight
+    decay, no truncation, both counter parities (the slot that is not read holds 7.0), schedule_kind 0 and a NaN
+    gradient; an arena with flat ranges in front of the first matrix (8 parameters) and behind the last bias (21);
+    one (p, g, m, v) quadruple given to a matrix element and to elements of the flat ranges."""
+    layers, params, g = _arena_net(in_dim, units, out_dim, seed=11, front=front, back=back)
+    n = params.numel()
+    src = front + 5                                              # an element of the first matrix
+    twins = [(src, front + layers[0][0].numel() + 1)]            # ... and one of its bias
+    if front:
+        twins += [(src, 3), (src, n - 2)]
+    opts = {'weight_decay': dict(counter=3, weight_decay=1e-2),
+            'no_truncation': dict(counter=4, truncate=False),
+            'keep_lr': dict(counter=4, weight_decay=1e-2, schedule_kind=0),
+            'nan_gradient': dict(counter=3, nan_at=front + layers[0][0].numel() + layers[0][1].numel() + 9)}[variant]
+    res, inputs, old_planes = _adam_pack_forms(layers, params, g, twins=twins, **opts)
+    _check_adam_pack_forms(res, inputs, old_planes, opts['counter'], twins)
+    p, _, _, _, lr_slots, stats, _ = res['fused']
+    cur = (opts['counter'] - 1) & 1
+    assert lr_slots[cur].item() == ADAM_PACK_LR
+    assert lr_slots[cur ^ 1].item() == (ADAM_PACK_LR if variant == 'keep_lr' else ADAM_PACK_LR * 1.5)   # kl 0.001
+    if variant == 'nan_gradient':
+        # torch.clamp propagates the NaN norm (clip_grad_norm_): everything is NaN, as in the reference
+        assert all(torch.isnan(t).all() for t in res['fused'][:4]) and torch.isnan(stats[:2]).all()
+    else:
+        assert torch.isfinite(p).all() and not _bit_equal(p, inputs[0])
+        assert (stats[1].item() == 1.0 and stats[0].item() == 0.0) if variant == 'no_truncation' else 0 < stats[1].item() < 1
+
+
+def _norm_partial_counts():
+    from test_optim_gpu import NORM_PARTIAL_COUNTS
+    return NORM_PARTIAL_COUNTS
+
+
+@pytest.mark.parametrize('count', _norm_partial_counts())
+def test_adam_step_pack_sums_the_norm_partials_of_another_launch(count):
+    """adam_pack_kernel's own copy of the 4-way unrolled reduction (it starts at 769 partials), on the counts of
+    tests/test_optim_gpu.py with NaN behind the partials: the same bits as the pair, the norm of the partials."""
+    import numpy as np
+    from test_optim_gpu import _ulps, norm_partials_case
+    layers, params, g = _arena_net(12, [100, 52], 22, seed=13)
+    buf, want = norm_partials_case(count)
+    res, inputs, old_planes = _adam_pack_forms(layers, params, g, counter=3, partials=buf[:count])
+    _check_adam_pack_forms(res, inputs, old_planes, 3)
+    stats = res['fused'][5].cpu().numpy()
+    assert _ulps(stats[0], want) <= 1, (stats[0], want)
+    assert _ulps(stats[1], min(np.float32(0.5) / (np.float32(stats[0]) + np.float32(1e-6)), np.float32(1.0))) <= 2
+    assert all(torch.isfinite(t).all() for t in res['fused'][:6])
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize('rows', [4096, 1000, 37])
 def test_lean_kernels_against_the_pipelined_ones(rows, monkeypatch):
