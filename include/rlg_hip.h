@@ -752,6 +752,23 @@ int rlg_gru_seq_backward(const float* gates, const float* hn_all, const float* h
                          const unsigned char* dones_or_null, const float* w_hh, const float* d_out,
                          float* d_gx, float* d_gh, int num_seqs, int seq_len, int hidden, void* stream);
 
+/* Layer normalisation behind the recurrent layer (csrc/rnn_layer_norm.hip): `rnn: {layer_norm: True}`,
+ * nn.LayerNorm(rnn_units) over the RNN output [rows, hidden] (network_builder.py:447-500), hidden 16 / 32 / 64 / 128.
+ *   forward:  y = (x - mean) * rstd * gamma + beta, biased variance from the centred values, rstd = 1 / sqrt(var + eps);
+ *             stats_or_null [rows, 2] fp32 receives (mean, rstd) per row for the backward (NULL: inference).
+ *   backward: g = d_y * gamma, xh = (x - mean) * rstd:  d_x = rstd * (g - mean_H(g) - xh * mean_H(g * xh));
+ *             d_gamma_partials / d_beta_partials [num_blocks][hidden] fp64: per-workgroup column sums of d_y * xh and
+ *             d_y, the layout rlg_act_bwd_colsum writes - finished by rlg_colsum_finalize or rlg_mlp_dw_launch's colsums.
+ *             num_blocks: rlg_rnn_layer_norm_num_blocks(rows, hidden) (0 for an unsupported width or rows <= 0).
+ * x, y, d_y, d_x contiguous and 16-byte aligned.  A row's result depends on the row alone (fixed summation order).
+ * Unsupported widths, rows <= 0, NULL or misaligned pointers: hipErrorInvalidValue, nothing is launched. */
+int rlg_rnn_layer_norm_num_blocks(long long rows, int hidden);
+int rlg_rnn_layer_norm_forward(const float* x, const float* gamma, const float* beta, float eps, float* y,
+                               float* stats_or_null, long long rows, int hidden, void* stream);
+int rlg_rnn_layer_norm_backward(const float* d_y, const float* x, const float* stats, const float* gamma, float* d_x,
+                                double* d_gamma_partials, double* d_beta_partials, int num_blocks, long long rows,
+                                int hidden, void* stream);
+
 /* ---- products too narrow for the MFMA kernels (csrc/mlp_narrow.hip; BASELINE config #5: obs 3, act 1) ----------
  * rlg_narrow_dx: dX [rows, in] = dZ [rows, out] W [out, in] for out <= 8 - autograd's grad_output.mm(weight) of the fused
  *   (value | mu) head (rl_games/algos_torch/network_builder.py:295-311, :506-512).

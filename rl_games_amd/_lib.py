@@ -118,6 +118,10 @@ _PROTOTYPES = {
     'rlg_gru_supported': [_c_int],
     'rlg_gru_seq_forward': [_P] * 9 + [_c_int, _c_int, _c_int, _P],
     'rlg_gru_seq_backward': [_P] * 8 + [_c_int, _c_int, _c_int, _P],
+    # rnn_layer_norm.hip
+    'rlg_rnn_layer_norm_num_blocks': [_c_ll, _c_int],
+    'rlg_rnn_layer_norm_forward': [_P, _P, _P, _c_float, _P, _P, _c_ll, _c_int, _P],
+    'rlg_rnn_layer_norm_backward': [_P, _P, _P, _P, _P, _P, _P, _c_int, _c_ll, _c_int, _P],
     'rlg_value_loss': [_P, _P, _P, _P, _P, _P, _P, _c_int, _c_float, _c_int, _P],
     'rlg_ppo_loss_discrete_num_blocks': [_c_int],
     'rlg_ppo_loss_discrete': [_P, _c_ll, _P, _P, _P, _P, _c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _c_int,

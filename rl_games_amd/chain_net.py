@@ -9,7 +9,9 @@ as ONE forward launch, the dX / activation-backward / bias-sum chain as ONE back
 
 Users: the central value network (central_value.py, one value column) and the discrete-action agent (discrete_agent.py:
 [value | logits] behind a shared trunk, or one chain per trunk with `separate: True` as in ppo_cartpole.yaml).  The
-continuous actor has its own engine (mlp_engine.ManualMLP: loss inside the backward launch, LSTM, HIP graphs).  The
+continuous actor has its own engine (mlp_engine.ManualMLP: loss inside the backward launch, LSTM, HIP graphs).
+RecurrentChainNet is the recurrent counterpart for the discrete agent: the trunk + gate-input product as one chain, then
+the sequence-persistent LSTM / GRU kernels, an optional layer norm and the heads.  The
 agents' rollout graphs read these chains too; they hold no pack launch, so the agent brings each chain's weight fragments
 / planes up to date in front of a replay along with its other chains (A2CAgent._forms_before_replay).
 """
@@ -18,19 +20,24 @@ from torch import nn
 
 from . import ops
 
+_DW_MAX_ITEMS = 8          # weight matrices / column-sum jobs of one ops.MlpDwPlan launch (csrc/mlp_dw.hip, kDwMaxLayers)
 _ACT_NAMES = {nn.ELU: 'elu', nn.ReLU: 'relu', nn.Tanh: 'tanh', nn.Identity: 'None'}
 
 
-def arena_layout(params, head_groups):
+def arena_layout(params, head_groups, first_vectors=()):
     """Physical arena order for `FlatArena(layout=...)`: every weight matrix first (parameters() order), then each
     group of head weights (adjacent, in the given order - one GEMM operand per group), then the vectors, then each
     group's biases.  Matrix sizes of the supported shapes are multiples of 4 floats, so the matrices stay 16-byte
-    aligned; the logical (optimiser-state) order is untouched.  head_groups: lists of nn.Linear."""
+    aligned; the logical (optimiser-state) order is untouched.  head_groups: lists of nn.Linear.
+    first_vectors: vectors to put in front of the others (RecurrentChainNet: the trunk's biases directly behind the last
+    matrix, as mlp_engine.ManualMLP.layout places them and explains)."""
     head_w = [m.weight for g in head_groups for m in g]
     head_b = [m.bias for g in head_groups for m in g]
     skip = {id(p) for p in head_w + head_b}
     rest = [p for p in params if id(p) not in skip]
-    return [p for p in rest if p.dim() >= 2] + head_w + [p for p in rest if p.dim() < 2] + head_b
+    first = {id(p) for p in first_vectors}
+    vecs = sorted((p for p in rest if p.dim() < 2), key=lambda p: id(p) not in first)      # (stable)
+    return [p for p in rest if p.dim() >= 2] + head_w + vecs + head_b
 
 
 class ChainNet:
@@ -149,4 +156,241 @@ class ChainNet:
                 ops.colsum_finalize(part, nb, cols, out)
         self.last_dw_path = 'mfma' if plan else 'library'
         for dz, x, g in slow:                               # e.g. a first layer over 9 state features: not a multiple of 4
+            torch.mm(dz.t(), x, out=g)
+
+
+class RecurrentChainNet:
+    """One trunk of a recurrent policy without autograd:
+        obs -> [Linear + act] x L -> W_ih x + b -> LSTM | GRU (one layer, 16 / 32 / 64 / 128 units)
+            -> optional nn.LayerNorm(units) -> heads
+    the RNN branch of mlp_engine.ManualMLP restated for arbitrary head columns (`heads`: nn.Linear modules over the
+    recurrent features, adjacent in `arena` as for ChainNet).  The normaliser, the trunk and the gate-input product are
+    one `ops.MlpChain` launch whose last (linear) layer is W_ih; the sequence-persistent kernels of csrc/lstm*.hip /
+    csrc/gru*.hip, the layer norm of csrc/rnn_layer_norm.hip and the head product follow.  backward() runs the same
+    stations in reverse from `d_heads` and finishes every weight gradient in one `ops.MlpDwPlan` launch.
+    trunk: nn.Sequential of Linear + activation pairs; rnn: the torch.nn.LSTM / GRU module (parameters only);
+    layer_norm: nn.LayerNorm or None.  max_rows: rows of a training minibatch, infer_rows: rows of a rollout step.
+    Raises NotImplementedError for networks outside the kernels' envelope - there is no per-layer fallback."""
+
+    def __init__(self, trunk, rnn, layer_norm, heads, arena, max_rows, infer_rows=0):
+        self.linears = [m for m in trunk if isinstance(m, nn.Linear)]
+        acts = [m for m in trunk if not isinstance(m, nn.Linear)]
+        if not self.linears or len(acts) != len(self.linears):
+            raise NotImplementedError('unexpected MLP structure')
+        name = _ACT_NAMES.get(type(acts[0]))
+        if name in (None, 'None') or any(type(a) is not type(acts[0]) for a in acts):
+            raise NotImplementedError('elu / relu / tanh trunks only')
+        if isinstance(acts[0], nn.ELU) and acts[0].alpha != 1.0:
+            raise NotImplementedError('elu alpha != 1')
+        if any(l.out_features % 4 for l in self.linears):
+            raise NotImplementedError('hidden widths must be multiples of 4')
+        self.lstm = rnn if isinstance(rnn, nn.LSTM) else None
+        self.gru = rnn if isinstance(rnn, nn.GRU) else None
+        if self.lstm is None and self.gru is None:
+            raise NotImplementedError('LSTM or GRU only')
+        H = rnn.hidden_size
+        supported = ops.lstm_supported if self.lstm is not None else ops.gru_supported
+        if (rnn.num_layers != 1 or rnn.bidirectional or not rnn.bias or getattr(rnn, 'proj_size', 0)
+                or not supported(H) or rnn.input_size != self.linears[-1].out_features):
+            raise NotImplementedError('a single-layer LSTM or GRU with 16/32/64/128 units behind the trunk only')
+        if layer_norm is not None and (tuple(layer_norm.normalized_shape) != (H,) or layer_norm.weight is None
+                                       or layer_norm.bias is None):
+            raise NotImplementedError('layer norm over the recurrent features with weight and bias only')
+        self.rnn, self.ln, self.Hr = rnn, layer_norm, H
+        self.Gr = (4 if self.lstm is not None else 3) * H
+        heads = list(heads)
+        if any(h.in_features != H for h in heads):
+            raise NotImplementedError('heads must read the recurrent features')
+        self.head_cols = C = sum(h.out_features for h in heads)
+        if len(heads) == 1:
+            h = heads[0]
+            self.head_w, self.head_w_grad, self.head_b, self.head_b_grad = h.weight, h.weight.grad, h.bias, h.bias.grad
+        else:
+            wp, wg = arena.span_of([h.weight for h in heads])
+            self.head_b, self.head_b_grad = arena.span_of([h.bias for h in heads])
+            self.head_w, self.head_w_grad = wp.view(C, H), wg.view(C, H)
+        dev = self.head_w.device
+        # the bias of the gate-input product.  LSTM: b_ih + b_hh, summed into bias_sum by every forward.  GRU: b_hn is
+        # multiplied by r inside the cell, so only b_ih belongs to the input side; the kernel adds b_hh.
+        if self.lstm is not None:
+            self.gate_bias = self.bias_sum = torch.empty(self.Gr, device=dev)
+        else:
+            self.gate_bias, self.bias_sum = rnn.bias_ih_l0, None
+        layers = [(l.weight, l.bias, name) for l in self.linears] + [(rnn.weight_ih_l0, self.gate_bias, 'None')]
+        self.chain = ops.MlpChain(layers, dev, weights_version=arena.weights_token)
+        self._head_mfma = (C <= 64 and ops.mlp_rowgemm_supported(H, H) and self.head_w.data_ptr() % 16 == 0)
+        rows = max(int(max_rows), int(infer_rows), 1)
+        widths = [l.out_features for l in self.linears]
+        G = self.Gr
+
+        def buf(cols, dtype=torch.float32):
+            return torch.empty(rows, cols, dtype=dtype, device=dev)
+        self.Hs = [buf(w) for w in widths]
+        self.dA = [buf(w) for w in widths]
+        self.xn = buf(self.linears[0].in_features)
+        self.heads, self.d_heads = buf(C), buf(C)
+        self.gates, self.rnn_out, self.d_rnn_out, self.hprev = buf(G), buf(H), buf(H), buf(H)
+        nb = (rows + 15) // 16                              # one partial row per 16-row group at most
+        self.partials = [torch.empty(nb * w, dtype=torch.float64, device=dev) for w in widths]
+        self.gate_partials = torch.empty(ops.act_bwd_blocks(rows, G) * G, dtype=torch.float64, device=dev)
+        if self.lstm is not None:
+            self.d_gates, self.c_all = buf(G), buf(H)
+        else:
+            self.hn_all = buf(H)                            # W_hn h + b_hn, before the gating by r
+            self.d_gx, self.d_gh = buf(G), buf(G)           # gradient of the input side / of the hidden side
+            self.gate_partials_h = torch.empty_like(self.gate_partials)
+        if self.ln is not None:
+            self.ln_out, self.d_ln_out, self.ln_stats = buf(H), buf(H), buf(2)
+            nbl = max(ops.rnn_layer_norm_blocks(rows, H), 1)
+            self.ln_partials = [torch.empty(nbl * H, dtype=torch.float64, device=dev) for _ in range(2)]
+        # final states of the last keep=False forward (LSTM: h and c, GRU: h), ping-pong so that a caller may feed them
+        # back in
+        nstates = 2 if self.lstm is not None else 1
+        self._state_buf = [[torch.empty(1, rows, H, device=dev) for _ in range(nstates)] for _ in range(2)]
+        self.last_states = None
+        self._plans = {}
+        self._rows = 0
+        self._x = self._c0 = self._dones = None
+        self._T = 1
+        self.last_dw_path = None
+
+    @torch.no_grad()
+    def forward(self, x_raw, rms, eps, rnn_states, dones, seq_length, keep):
+        """x_raw [rows, in] RAW inputs, rows ordered (sequence, t) with `seq_length` steps each; rms = (running_mean,
+        running_var) or None - the launch normalises on the way in.  rnn_states = (h0, c0) - GRU: (h0,) - of shape
+        [1, rows / seq_length, H]; dones [rows] u8 resets the state entering a step (or None).  Returns the heads
+        [rows, head_cols].  keep=True retains what backward() reads and leaves the state buffers alone (they hold the
+        live rollout state); keep=False (a rollout step, get_values) keeps nothing and leaves the final states in
+        `last_states`, in whichever buffer pair the inputs do not live in."""
+        rows = x_raw.shape[0]
+        S = rows // seq_length
+        if S * seq_length != rows:
+            raise ValueError(f'rows ({rows}) must be a multiple of seq_length ({seq_length})')
+        if not x_raw.is_contiguous() and (keep or x_raw.stride(-1) != 1):
+            x_raw = x_raw.contiguous()
+        if dones is not None:
+            dones = dones.reshape(-1)
+            if dones.dtype != torch.uint8 or not dones.is_contiguous():
+                dones = dones.to(torch.uint8).contiguous()
+        rnn, H = self.rnn, self.Hr
+        h0 = rnn_states[0][0]
+        c0 = rnn_states[1][0] if self.lstm is not None else None
+        if h0.shape != (S, H) or not h0.is_contiguous() or not (c0 is None or (c0.shape == (S, H) and c0.is_contiguous())):
+            raise ValueError(f'rnn_states must be contiguous [1, {S}, {H}] tensors')
+        if self.lstm is not None:
+            torch.add(rnn.bias_ih_l0, rnn.bias_hh_l0, out=self.bias_sum)
+        gates = self.gates[:rows]
+        if keep:
+            xn = self.xn[:rows] if rms is not None else None
+            self.chain.forward(x_raw, gates, act_out=[h[:rows] for h in self.Hs], rms=rms, eps=eps, xn_out=xn)
+            self._x = xn if rms is not None else x_raw       # what the first layer's weight gradient reads
+        else:
+            self.chain.forward(x_raw, gates, rms=rms, eps=eps)
+        hT = cT = None
+        if not keep:
+            flip = 1 if h0.data_ptr() == self._state_buf[0][0].data_ptr() else 0
+            hT = self._state_buf[flip][0][:, :S]
+            cT = self._state_buf[flip][1][:, :S] if self.lstm is not None else None
+        out = self.rnn_out[:rows]
+        if self.lstm is not None:
+            ops.lstm_seq_forward(gates, rnn.weight_hh_l0, h0, c0, dones, out,
+                                 self.c_all[:rows] if keep else None, self.hprev[:rows] if keep else None,
+                                 None if hT is None else hT[0], None if cT is None else cT[0], seq_len=seq_length)
+            self.last_states = None if hT is None else (hT, cT)
+        else:
+            ops.gru_seq_forward(gates, rnn.weight_hh_l0, rnn.bias_hh_l0, h0, dones, out,
+                                self.hn_all[:rows] if keep else None, self.hprev[:rows] if keep else None,
+                                None if hT is None else hT[0], seq_len=seq_length)
+            self.last_states = None if hT is None else (hT,)
+        feat = out
+        if self.ln is not None:
+            feat = self.ln_out[:rows]
+            ops.rnn_layer_norm_forward(out, self.ln.weight, self.ln.bias, self.ln.eps, feat,
+                                       self.ln_stats[:rows] if keep else None)
+        heads = self.heads[:rows]
+        if self._head_mfma:
+            ops.mlp_linear_act_forward(feat, self.head_w, self.head_b, heads, act_kind=0)
+        else:
+            torch.addmm(self.head_b, feat, self.head_w.t(), out=heads)
+        if keep:
+            self._rows, self._c0, self._dones, self._T = rows, c0, dones, seq_length
+        return heads
+
+    @torch.no_grad()
+    def backward(self):
+        """d loss / d heads in self.d_heads[:rows] -> every gradient of the network in the arena (overwritten)."""
+        rows, L, H, G, rnn = self._rows, len(self.linears), self.Hr, self.Gr, self.rnn
+        d_heads = self.d_heads[:rows]
+        feat = (self.ln_out if self.ln is not None else self.rnn_out)[:rows]
+        d_feat = (self.d_ln_out if self.ln is not None else self.d_rnn_out)[:rows]
+        C = self.head_cols
+        if C <= ops.NARROW_MAX:
+            ops.narrow_dx(d_heads, self.head_w, d_feat)
+        elif ops.mlp_rowgemm_supported(C, C) and d_heads.data_ptr() % 16 == 0:
+            ops.mlp_linear_act_backward(d_heads, self.head_w, None, d_feat, 0)
+        else:
+            torch.mm(d_heads, self.head_w, out=d_feat)
+        colsums = []                                        # (partials, blocks, cols, gradient vector)
+        d_out = self.d_rnn_out[:rows]
+        if self.ln is not None:
+            nbl = ops.rnn_layer_norm_blocks(rows, H)
+            pg, pb = (p[:nbl * H] for p in self.ln_partials)
+            ops.rnn_layer_norm_backward(d_feat, self.rnn_out[:rows], self.ln_stats[:rows], self.ln.weight, d_out, pg, pb,
+                                        nbl)
+            colsums += [(pg, nbl, H, self.ln.weight.grad), (pb, nbl, H, self.ln.bias.grad)]
+        gates = self.gates[:rows]
+        nbg = ops.act_bwd_blocks(rows, G)
+        gpart = self.gate_partials[:nbg * G]
+        if self.lstm is not None:
+            dg = dgh = self.d_gates[:rows]
+            ops.lstm_seq_backward(gates, self.c_all[:rows], self._c0, self._dones, rnn.weight_hh_l0, d_out, dg, self._T)
+            ops.act_bwd_colsum(dg, None, dg, 0, gpart, nbg)                  # identity: column sums only
+            colsums += [(gpart, nbg, G, rnn.bias_ih_l0.grad), (gpart, nbg, G, rnn.bias_hh_l0.grad)]   # d b_hh = d b_ih
+        else:
+            # dg = d_gx: the input side - W_ih, b_ih and the trunk; dgh = d_gh: the hidden side - W_hh, b_hh
+            dg, dgh = self.d_gx[:rows], self.d_gh[:rows]
+            ops.gru_seq_backward(gates, self.hn_all[:rows], self.hprev[:rows], self._dones, rnn.weight_hh_l0, d_out,
+                                 dg, dgh, self._T)
+            gpart_h = self.gate_partials_h[:nbg * G]
+            ops.act_bwd_colsum(dg, None, dg, 0, gpart, nbg)
+            ops.act_bwd_colsum(dgh, None, dgh, 0, gpart_h, nbg)
+            colsums += [(gpart, nbg, G, rnn.bias_ih_l0.grad), (gpart_h, nbg, G, rnn.bias_hh_l0.grad)]
+        # dX chain of the trunk in one launch, from d gates down (the chain's "head" layer is W_ih)
+        acts = [h[:rows] for h in self.Hs]
+        dzs = [d[:rows] for d in self.dA]
+        nblk = self.chain.num_blocks(rows, 1)
+        parts = [p[:nblk * l.out_features] for p, l in zip(self.partials, self.linears)]
+        self.chain.backward(dg, acts, dzs, parts)
+        jobs = [(d_heads, feat, self.head_w_grad), (dgh, self.hprev[:rows], rnn.weight_hh_l0.grad),
+                (dg, acts[-1], rnn.weight_ih_l0.grad)]
+        torch.sum(d_heads, dim=0, out=self.head_b_grad)
+        for l in range(L - 1, -1, -1):
+            lin = self.linears[l]
+            jobs.append((dzs[l], acts[l - 1] if l > 0 else self._x, lin.weight.grad))
+            colsums.append((parts[l], nblk, lin.out_features, lin.bias.grad))
+        fast = [j for j in jobs if j[2].shape[1] % 4 == 0 and all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in j)]
+        slow = [j for j in jobs if not any(j is f for f in fast)]
+        plan = None
+        if len(fast) > _DW_MAX_ITEMS:
+            fast, slow = [], jobs
+        if fast:
+            fast.sort(key=lambda j: -j[2].numel())          # heaviest matrix's blocks first in the launch
+            key = (rows,) + tuple(tuple(g.shape) for _, _, g in fast)
+            plan = self._plans.get(key)
+            if plan is None:
+                try:
+                    plan = ops.MlpDwPlan([tuple(g.shape) for _, _, g in fast], rows, fast[0][2].device)
+                except NotImplementedError:
+                    plan = False
+                self._plans[key] = plan
+        if plan:
+            # (bias / layer-norm gradients finished by the same finalise launch, as many as it takes)
+            plan.launch(fast, colsums[:_DW_MAX_ITEMS])
+            colsums = colsums[_DW_MAX_ITEMS:]
+        else:
+            slow = jobs
+        for part, nb, cols, out in colsums:
+            ops.colsum_finalize(part, nb, cols, out)
+        self.last_dw_path = 'mfma' if plan else 'library'
+        for dz, x, g in slow:                               # e.g. a first layer over 9 observations: not a multiple of 4
             torch.mm(dz.t(), x, out=g)

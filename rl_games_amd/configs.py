@@ -94,5 +94,27 @@ def cartpole_discrete(num_actors=16, **over):
     return {'algo': {'name': 'a2c_discrete'}, 'model': {'name': 'discrete_a2c'}, 'network': net, 'config': cfg}
 
 
+def smac_rnn_discrete(num_actors=8, cell='lstm', units=128, layer_norm=False, actions=14, **over):
+    """The shape of the reference's recurrent SMAC runs (rl_games/configs/smac/v1/runs/MMM2_rnn.yaml, 6h_vs_8z_rnn.yaml;
+    `layer_norm: True` as in 5m_vs_6m_rnn.yaml): discrete PPO, a shared ReLU trunk, one LSTM / GRU layer of `units`
+    behind it, action masks, sequences of 8 steps, normalised observations and values - on the synthetic env (obs 80;
+    `actions`: an int for Discrete, a list for multi-discrete heads).  Hyper-parameters follow MMM2_rnn.yaml."""
+    multi = isinstance(actions, (list, tuple))
+    net = {'name': 'actor_critic', 'separate': False, 'space': {'multi_discrete' if multi else 'discrete': None},
+           'mlp': {'units': [256, 128], 'activation': 'relu', 'initializer': {'name': 'default'}},
+           'rnn': {'name': cell, 'units': units, 'layers': 1, 'layer_norm': bool(layer_norm)}}
+    horizon = over.pop('horizon_length', 32)
+    minibatch = over.pop('minibatch_size', max(num_actors * horizon // 2, 8))
+    cfg = _config('smac_rnn_shaped', num_actors, horizon, minibatch, 4,
+                  {'obs_dim': 80, 'discrete_actions': list(actions) if multi else int(actions), 'action_masks': True},
+                  gamma=0.995, learning_rate=1e-4, lr_schedule=None, kl_threshold=0.05, grad_norm=0.5, entropy_coef=0.005,
+                  clip_value=False, critic_coef=1, value_bootstrap=False, use_action_masks=True, seq_length=8)
+    cfg.pop('bounds_loss_coef')
+    cfg.pop('bound_loss_type')
+    cfg.update(over)
+    return {'algo': {'name': 'a2c_discrete'}, 'model': {'name': 'multi_discrete_a2c' if multi else 'discrete_a2c'},
+            'network': net, 'config': cfg}
+
+
 def clone(params):
     return copy.deepcopy(params)

@@ -13,6 +13,9 @@ Shares the rollout / GAE / dataset-preparation / optimiser path with `A2CAgent`;
     [value | logits] behind a shared trunk, one chain per trunk with `separate: True` (ppo_cartpole.yaml:17) - where the
     network has that form (plain Linear + ELU / ReLU / tanh trunks, widths that are multiples of 4, value_size 1);
     anything else, or `fused_mlp: False`, keeps autograd around the loss kernel (`torch.autograd.backward` on the heads);
+  * recurrent networks of the reference's SMAC shape (one shared trunk, one LSTM / GRU layer of 16 / 32 / 64 / 128 units
+    behind it, optionally a layer norm behind the RNN) run update and rollout on chain_net.RecurrentChainNet
+    (`_rnn_engine`; `manual_lstm: False` keeps them on torch modules);
   * the rollout runs on the same chains (`fused_rollout`, _policy_step_kernels): each chain's inference forward, the
     Exp(1) draws of Categorical.sample(), and one launch of the categorical head (csrc/rollout_categorical.hip) that
     samples, scores and writes the step into the buffer - replayed as one HIP graph per step index like the continuous
@@ -25,8 +28,8 @@ import torch
 from torch import nn
 
 from . import ops
-from .agent import A2CAgent
-from .chain_net import ChainNet, arena_layout
+from .agent import A2CAgent, _ChainForms
+from .chain_net import ChainNet, RecurrentChainNet, arena_layout
 
 
 class DiscreteA2CAgent(A2CAgent):
@@ -64,37 +67,73 @@ class DiscreteA2CAgent(A2CAgent):
         logits = list(net.logits) if net.is_multi_discrete else [net.logits]
         return [logits, [net.value]] if net.is_separate_critic() else [[net.value] + logits]
 
+    def _recurrent_engine_declined(self, config):
+        """Why a recurrent network stays off chain_net.RecurrentChainNet (None: it is eligible): one shared trunk of
+        Linear + activation pairs, one LSTM / GRU layer of a supported width plainly behind it (a layer norm behind the
+        RNN is fine), and `manual_lstm` - recurrent policies through this library's kernels - not switched off."""
+        net = self.model.a2c_network
+        if not config.get('manual_lstm', True):
+            return 'manual_lstm is off'
+        if not getattr(net, 'plain_trunk_rnn_ln', False) or net.is_separate_critic():
+            return 'plain Linear + activation trunks only'
+        supported = {'lstm': ops.lstm_supported, 'gru': ops.gru_supported}.get(net.rnn_name)
+        if supported is None or net.rnn_layers != 1 or not supported(net.rnn_units):
+            return 'a single-layer LSTM or GRU with 16/32/64/128 units only'
+        return None
+
     def _arena_layout(self, config):
         if not config.get('fused_mlp', True):
             return None
         net = self.model.a2c_network
         rest = [p for p in self.model.parameters() if all(p is not q for q in net.parameters())]
-        return arena_layout(list(net.parameters()), self._chain_heads()) + rest
+        first = ()
+        if net.is_rnn() and self._recurrent_engine_declined(config) is None:
+            first = [m.bias for m in net.actor_mlp if isinstance(m, nn.Linear)]      # (RecurrentChainNet's trunk)
+        return arena_layout(list(net.parameters()), self._chain_heads(), first_vectors=first) + rest
 
     def _init_chains(self, config):
+        """Feed-forward networks: `_chains`, one ChainNet per trunk.  Recurrent ones: `_rnn_engine`, a RecurrentChainNet
+        over the shared trunk ([value | logits] heads); `_chains` stays None for them."""
         self._chains = None
+        self._rnn_engine = None
         net = self.model.a2c_network
         if not config.get('fused_mlp', True):
             return
         try:
             if self.value_size != 1 or not isinstance(net.value_act, nn.Identity):
                 raise NotImplementedError('one linear value column only')
-            if not getattr(net, 'plain_trunk', True) or net.is_rnn():
-                raise NotImplementedError('plain Linear + activation trunks only')
             rows = self.minibatch_size
             groups = self._chain_heads()
-            trunks = [net.actor_mlp, net.critic_mlp] if net.is_separate_critic() else [net.actor_mlp]
             roll = self.num_actors * self.num_agents
+            if net.is_rnn():
+                why = self._recurrent_engine_declined(config)
+                if why is not None:
+                    raise NotImplementedError(why)
+                self._rnn_engine = RecurrentChainNet(net.actor_mlp, net.rnn.rnn, net.layer_norm if net.rnn_ln else None,
+                                                     groups[0], self.optimizer, rows, infer_rows=roll)
+                return
+            if not getattr(net, 'plain_trunk', True):
+                raise NotImplementedError('plain Linear + activation trunks only')
+            trunks = [net.actor_mlp, net.critic_mlp] if net.is_separate_critic() else [net.actor_mlp]
             self._chains = [ChainNet(t, g, self.optimizer, rows, infer_rows=roll) for t, g in zip(trunks, groups)]
         except NotImplementedError as e:
             print(f'rl_games_amd: discrete network outside the fused chain kernels ({e}); using autograd')
-            self._chains = None
+            self._chains = self._rnn_engine = None
+
+    def _graph_chains(self):
+        """... and the recurrent engine's trunk chain: a replayed step graph reads its fragments / planes."""
+        forms = super()._graph_chains()
+        if self._rnn_engine is not None:
+            roll = self.num_actors * self.num_agents
+            forms.append(_ChainForms(self._rnn_engine.chain, ((roll, 0),), self.optimizer.flat_params))
+        return forms
 
     # ------------------------------------------------------------------ fused rollout
     def _fused_rollout_network_ok(self):
-        """A feed-forward network on the chains (recurrent policies keep the torch path) of at most
+        """A feed-forward network on the chains or a recurrent one on its engine, of at most
         ops.CATEGORICAL_MAX_BRANCHES action branches."""
-        return self._chains is not None and not self.is_rnn and len(self.branch_sizes) <= ops.CATEGORICAL_MAX_BRANCHES
+        on_kernels = self._rnn_engine is not None if self.is_rnn else self._chains is not None
+        return on_kernels and len(self.branch_sizes) <= ops.CATEGORICAL_MAX_BRANCHES
 
     def init_tensors(self):
         super().init_tensors()
@@ -125,12 +164,17 @@ class DiscreteA2CAgent(A2CAgent):
             self.experience_buffer.store_step(n, {'action_masks': masks.contiguous()})
         return super()._fast_policy_step(n)
 
-    def _chain_heads_of(self, obs, logits_only=False):
+    def _chain_heads_of(self, obs, logits_only=False, rnn_states=None):
         """(logits [N, sum(sizes)], value [N, 1]) of fp32 observations (any row stride): each chain's inference
         forward, the observation normaliser in eval mode inside the launch.  logits_only (a central value network
-        supplies the values): the separate critic trunk does not run, value is None."""
+        supplies the values): the separate critic trunk does not run, value is None.  Recurrent policies: the engine's
+        T = 1 forward on `rnn_states` - the states arrive zeroed where an episode ended (play_steps_rnn), as for the
+        model's eval forward, which takes no done flags (a2c_common.py:590) - leaving the next ones in its last_states."""
         if obs.stride(-1) != 1:
             obs = obs.contiguous()
+        if self._rnn_engine is not None:                         # [value | logits]
+            heads = self._rnn_engine.forward(obs, self._obs_rms(), self._obs_eps(), rnn_states, None, 1, keep=False)
+            return heads[:, 1:], heads[:, :1]
         chains = self._chains[:1] if logits_only else self._chains
         heads = [c.infer(obs, self._obs_rms(), self._obs_eps()) for c in chains]
         if len(self._chains) == 1:                               # [value | logits]
@@ -151,7 +195,7 @@ class DiscreteA2CAgent(A2CAgent):
         the same generator use as get_(masked_)action_values + update_data; no host read, so the step can be captured."""
         buf = self.experience_buffer
         cv = self.has_central_value
-        logits, value = self._chain_heads_of(self._preproc_obs(obs_raw), logits_only=cv)
+        logits, value = self._chain_heads_of(self._preproc_obs(obs_raw), logits_only=cv, rnn_states=rnn_states)
         if cv:
             value = self._critic_infer(states)
         rows = logits.shape[0]
@@ -163,7 +207,10 @@ class DiscreteA2CAgent(A2CAgent):
                                      value_repeat=self.num_agents if cv else 1)
         if store:
             self._store_step_inputs(n, obs_raw, dones, states)
-        return {'actions': self._roll_actions, 'values': self._roll_values.view(rows, 1)}
+        res = {'actions': self._roll_actions, 'values': self._roll_values.view(rows, 1)}
+        if self._rnn_engine is not None:
+            res['rnn_states'] = self._rnn_engine.last_states
+        return res
 
     def _fast_values(self, obs):
         """get_values on the chains: the critic column, de-normalised."""
@@ -175,8 +222,12 @@ class DiscreteA2CAgent(A2CAgent):
         x = self._preproc_obs(x)
         if x.stride(-1) != 1:
             x = x.contiguous()
-        # the critic is column 0 of the last chain's heads ([value | logits], or the critic trunk's [value])
-        v = self._chains[-1].infer(x, self._obs_rms(), self._obs_eps())[:, :1].contiguous()
+        if self._rnn_engine is not None:
+            # the same forward as a rollout step; the states it leaves are dropped
+            v = self._chain_heads_of(x, rnn_states=self.rnn_states)[1].contiguous()
+        else:
+            # the critic is column 0 of the last chain's heads ([value | logits], or the critic trunk's [value])
+            v = self._chains[-1].infer(x, self._obs_rms(), self._obs_eps())[:, :1].contiguous()
         # get_values runs the model's whole eval forward, which samples actions: the same draws keep the generator where
         # the torch path leaves it
         self._draw_exp_noise(x.shape[0])
@@ -230,7 +281,21 @@ class DiscreteA2CAgent(A2CAgent):
         rnn_masks = input_dict.get('rnn_masks', None)
         opt.zero_grad()
         chains = self._chains if obs_batch.dtype == torch.float32 else None
-        if chains is not None:
+        rnn_eng = self._rnn_engine if obs_batch.dtype == torch.float32 else None
+        if rnn_eng is not None:
+            # the same normaliser update, then trunk + gate-input product, the sequence kernel, (layer norm,) heads
+            rms, eps = None, 1e-5
+            if self.normalize_input:
+                m = self.model.running_mean_std
+                if m.training:
+                    m.update(obs_batch)
+                rms, eps = (m.running_mean, m.running_var), m.epsilon
+            mb = obs_batch.shape[0]
+            heads = rnn_eng.forward(obs_batch, rms, eps, input_dict['rnn_states'],
+                                    input_dict['dones'] if self.zero_rnn_on_done else None, self.seq_length, keep=True)
+            logits, values = heads[:, 1:], heads[:, 0]           # [value | logits]
+            d_logits, d_val = rnn_eng.d_heads[:mb, 1:], rnn_eng.d_heads[:mb, 0]
+        elif chains is not None:
             # models.py:54-56 (norm_obs: training mode updates the statistics first), then each trunk + its heads as
             # one launch that normalises on the way in
             rms, eps = None, 1e-5
@@ -274,7 +339,9 @@ class DiscreteA2CAgent(A2CAgent):
                                   mask is not None, self.critic_coef if self.has_value_loss else 0.0,
                                   self.entropy_coef, 0.0, row,
                                   self._no_logstd, opt.kl_slot)
-        if chains is not None:
+        if rnn_eng is not None:
+            rnn_eng.backward()
+        elif chains is not None:
             for c in chains:
                 c.backward()
         else:

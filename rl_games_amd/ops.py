@@ -1411,3 +1411,43 @@ def gru_seq_backward(gates, hn_all, hprev, dones, w_hh, d_out, d_gx, d_gh, seq_l
         _opt(dones, torch.uint8, 'dones'), _need(w_hh, F32, 'w_hh'), _need(d_out, F32, 'd_out'),
         _need(d_gx, F32, 'd_gx'), _need(d_gh, F32, 'd_gh'), S, seq_len, H, _stream(gates)),
         'rlg_gru_seq_backward')
+
+
+# ------------------------------------------------------------------ layer norm behind the recurrent layer
+
+def rnn_layer_norm_blocks(rows, hidden):
+    """Workgroups (= rows of the fp64 column partials) of rnn_layer_norm_backward; 0: width outside 16 / 32 / 64 / 128
+    or no rows."""
+    return _lib.load().rlg_rnn_layer_norm_num_blocks(int(rows), int(hidden))
+
+
+def rnn_layer_norm_forward(x, gamma, beta, eps, y, stats=None):
+    """y = nn.LayerNorm(H)(x) for x [rows, H] behind the RNN (csrc/rnn_layer_norm.hip); stats [rows, 2] receives each
+    row's (mean, rstd) for rnn_layer_norm_backward (None: inference)."""
+    for t, name in ((x, 'x'), (gamma, 'gamma'), (beta, 'beta'), (y, 'y')):
+        _need(t, F32, name)
+    rows, H = x.shape
+    if y.shape != x.shape or gamma.numel() != H or beta.numel() != H or (stats is not None and stats.shape != (rows, 2)):
+        raise ValueError(f'rnn_layer_norm_forward: x / y [rows, H], gamma / beta [H] and stats [rows, 2] do not agree: '
+                         f'{tuple(x.shape)}, {tuple(y.shape)}, {tuple(gamma.shape)}, {tuple(beta.shape)}')
+    _lib.check(_lib.load().rlg_rnn_layer_norm_forward(
+        _need(x, F32, 'x'), _need(gamma, F32, 'gamma'), _need(beta, F32, 'beta'), float(eps), _need(y, F32, 'y'),
+        _opt(stats, F32, 'stats'), rows, H, _stream(x)), 'rlg_rnn_layer_norm_forward')
+
+
+def rnn_layer_norm_backward(d_y, x, stats, gamma, d_x, d_gamma_partials, d_beta_partials, num_blocks):
+    """d_x from d_y, the forward's input x and its stats; d_gamma_partials / d_beta_partials fp64 [num_blocks * H]: the
+    column partials of d gamma = sum d_y * xhat and d beta = sum d_y for colsum_finalize / MlpDwPlan.launch(colsums=)."""
+    for t, name in ((d_y, 'd_y'), (x, 'x'), (stats, 'stats'), (gamma, 'gamma'), (d_x, 'd_x')):
+        _need(t, F32, name)
+    rows, H = x.shape
+    if d_y.shape != x.shape or d_x.shape != x.shape or stats.shape != (rows, 2) or gamma.numel() != H:
+        raise ValueError(f'rnn_layer_norm_backward: d_y / x / d_x [rows, H], stats [rows, 2] and gamma [H] do not agree: '
+                         f'{tuple(d_y.shape)}, {tuple(x.shape)}, {tuple(d_x.shape)}, {tuple(stats.shape)}')
+    if min(d_gamma_partials.numel(), d_beta_partials.numel()) < int(num_blocks) * H:
+        raise ValueError(f'rnn_layer_norm_backward: {int(num_blocks) * H} partials needed per array')
+    _lib.check(_lib.load().rlg_rnn_layer_norm_backward(
+        _need(d_y, F32, 'd_y'), _need(x, F32, 'x'), _need(stats, F32, 'stats'), _need(gamma, F32, 'gamma'),
+        _need(d_x, F32, 'd_x'), _need(d_gamma_partials, F64, 'd_gamma_partials'),
+        _need(d_beta_partials, F64, 'd_beta_partials'), int(num_blocks), rows, H, _stream(x)),
+        'rlg_rnn_layer_norm_backward')

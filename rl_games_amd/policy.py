@@ -261,9 +261,11 @@ class ActorCriticNetwork(nn.Module):
         if self.separate:                                      # network_builder.py:292-293
             self.critic_mlp = build_trunk(mlp_in, self.units, **self._trunk_kw)
         # what the fused engines take (mlp_engine.ManualMLP): Linear + activation pairs, the RNN plainly behind them
-        self.plain_trunk = (not self._trunk_kw['d2rl'] and self._trunk_kw['norm_func_name'] is None and
-                            not (self.rnn_before_mlp or self.rnn_concat_input or self.rnn_concat_output or self.rnn_ln)
-                            and not (self.separate and self.has_rnn))
+        # ... plain but for a layer norm behind the RNN: what chain_net.RecurrentChainNet takes (the discrete agent)
+        self.plain_trunk_rnn_ln = (not self._trunk_kw['d2rl'] and self._trunk_kw['norm_func_name'] is None and
+                                   not (self.rnn_before_mlp or self.rnn_concat_input or self.rnn_concat_output)
+                                   and not (self.separate and self.has_rnn))
+        self.plain_trunk = self.plain_trunk_rnn_ln and not self.rnn_ln
         return out_size
 
     def _init_central_value(self, net_params, input_shape, value_size, num_seqs):
