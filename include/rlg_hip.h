@@ -769,6 +769,29 @@ int rlg_rnn_layer_norm_backward(const float* d_y, const float* x, const float* s
                                 double* d_gamma_partials, double* d_beta_partials, int num_blocks, long long rows,
                                 int hidden, void* stream);
 
+/* Value head + clipped value loss + its backward behind the recurrent layer of a central value critic
+ * (csrc/rnn_value_tail.hip): one value column over the RNN (or layer-normed) features feat [rows, hidden], hidden
+ * 16 / 32 / 64 / 128, as in the reference's recurrent SMAC critics (central_value.py:262-335).
+ *   values[r] = b + sum_k feat[r,k] w[k], products and sum in fp64, rounded to fp32 once; w [hidden], b [1].
+ *   rlg_rnn_value_head: the values alone (a rollout step, get_value) - the same bits as the training form.
+ *   rlg_rnn_value_tail: also the row loss and gradient of rlg_value_loss (the same device function) -> d_values [rows],
+ *     d_feat[r,k] = d_values[r] w[k], and per workgroup in fp64: loss_partials [num_blocks][7] in rlg_value_loss's
+ *     slots (for rlg_ppo_loss_finalize with actions_num 0), d_w_partials [num_blocks][hidden] = sum_r d_values[r]
+ *     feat[r,k] and d_b_partials [num_blocks][1] = sum_r d_values[r], the layout rlg_act_bwd_colsum writes - finished by
+ *     rlg_colsum_finalize or rlg_mlp_dw_launch's colsums.  num_blocks: rlg_rnn_value_tail_num_blocks(rows, hidden)
+ *     (0 for an unsupported width or rows <= 0).
+ * feat, d_feat contiguous and 16-byte aligned.  A row's result depends on the row alone (fixed summation order).
+ * Unsupported widths, rows <= 0, a mask without its sum, NULL or misaligned pointers: hipErrorInvalidValue, nothing is
+ * launched. */
+int rlg_rnn_value_tail_num_blocks(long long rows, int hidden);
+int rlg_rnn_value_head(const float* feat, const float* w, const float* b, float* values, long long rows, int hidden,
+                       void* stream);
+int rlg_rnn_value_tail(const float* feat, const float* w, const float* b, const float* old_values,
+                       const float* returns, const float* mask_or_null, const float* mask_sum_or_null, float* values,
+                       float* d_values, float* d_feat, double* loss_partials, double* d_w_partials,
+                       double* d_b_partials, int num_blocks, long long rows, int hidden, float e_clip, int clip_value,
+                       void* stream);
+
 /* ---- products too narrow for the MFMA kernels (csrc/mlp_narrow.hip; BASELINE config #5: obs 3, act 1) ----------
  * rlg_narrow_dx: dX [rows, in] = dZ [rows, out] W [out, in] for out <= 8 - autograd's grad_output.mm(weight) of the fused
  *   (value | mu) head (rl_games/algos_torch/network_builder.py:295-311, :506-512).

@@ -122,6 +122,10 @@ _PROTOTYPES = {
     'rlg_rnn_layer_norm_num_blocks': [_c_ll, _c_int],
     'rlg_rnn_layer_norm_forward': [_P, _P, _P, _c_float, _P, _P, _c_ll, _c_int, _P],
     'rlg_rnn_layer_norm_backward': [_P, _P, _P, _P, _P, _P, _P, _c_int, _c_ll, _c_int, _P],
+    # rnn_value_tail.hip
+    'rlg_rnn_value_tail_num_blocks': [_c_ll, _c_int],
+    'rlg_rnn_value_head': [_P, _P, _P, _P, _c_ll, _c_int, _P],
+    'rlg_rnn_value_tail': [_P] * 13 + [_c_int, _c_ll, _c_int, _c_float, _c_int, _P],
     'rlg_value_loss': [_P, _P, _P, _P, _P, _P, _P, _c_int, _c_float, _c_int, _P],
     'rlg_ppo_loss_discrete_num_blocks': [_c_int],
     'rlg_ppo_loss_discrete': [_P, _c_ll, _P, _P, _P, _P, _c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _c_int,

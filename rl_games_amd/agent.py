@@ -393,7 +393,12 @@ class A2CAgent:
                 num_actions=self.actions_num, seq_length=self.seq_length, normalize_value=self.normalize_value,
                 network=cv_builder, config=cv_cfg, writter=self.writer, max_epochs=self.max_epochs,
                 multi_gpu=self.multi_gpu, zero_rnn_on_done=self.zero_rnn_on_done)
-        self.use_experimental_cv = config.get('use_experimental_cv', True)
+            if not self.is_rnn:
+                # the reference advances a recurrent critic with the rollout only in play_steps_rnn (a2c_common.py:1085-1086)
+                self.central_value_net.decline_rnn_engine('the actor is not recurrent')
+        # (the reference's defaults: True for the continuous agent, a2c_continuous.py:70; False for the discrete one,
+        #  a2c_discrete.py:72 - its actor trains no value loss next to a central value network unless asked to)
+        self.use_experimental_cv = config.get('use_experimental_cv', not self.is_discrete)
         if self.normalize_value:
             self.value_mean_std = (self.central_value_net.model.value_mean_std if self.has_central_value
                                    else self.model.value_mean_std)
@@ -802,6 +807,8 @@ class A2CAgent:
                     st['rnn'] = [torch.empty_like(s) for s in self.rnn_states]
                 if states is not None:
                     st['states'] = torch.empty_like(states).contiguous()
+                if self._critic_rnn_engine() is not None:
+                    st['cv_rnn'] = [torch.empty_like(s) for s in self.central_value_net.rnn_states]
                 self._rollout_static = st
             st = self._rollout_static
             st['obs'].copy_(obs)
@@ -811,7 +818,10 @@ class A2CAgent:
                     dst.copy_(src)
             if states is not None:
                 st['states'].copy_(states)
-            args = (n, st['obs'], st['dones'], st.get('rnn'), True, st.get('states'))
+            if 'cv_rnn' in st:
+                for dst, src in zip(st['cv_rnn'], self.central_value_net.rnn_states):
+                    dst.copy_(src)
+            args = (n, st['obs'], st['dones'], st.get('rnn'), True, st.get('states'), st.get('cv_rnn'))
         entry = self._rollout_graphs.get((n, direct))
         if entry is None:
             out = []
@@ -824,16 +834,17 @@ class A2CAgent:
         return (self._hip_graphs and self.config.get('rollout_graphs', True) and self._eager_epochs >= 1
                 and not self._graph_failed and isinstance(self.obs['obs'], torch.Tensor))
 
-    def _policy_step_kernels(self, n, obs_raw, dones, rnn_states, store=True, states=None):
+    def _policy_step_kernels(self, n, obs_raw, dones, rnn_states, store=True, states=None, cv_rnn_states=None):
         """obs normalise -> engine GEMMs -> (central value: the critic's chain forward on `states`) -> fused policy-head
         kernel that also writes actions / mus / sigmas / neglogpacs / values of the step into the buffer -> obs + dones
         (+ states) into the buffer -> action clamp/rescale for the env.  Same maths as get_action_values + update_data +
-        preprocess_actions; no autograd, nothing that depends on the host."""
+        preprocess_actions; no autograd, nothing that depends on the host.  cv_rnn_states: the states a recurrent
+        critic's step reads (None: the critic's own `rnn_states`); the ones it leaves go into the result."""
         eng, buf = self._engine, self.experience_buffer
         obs = self._preproc_obs(obs_raw)
         rows = obs.shape[0]
         heads = self._actor_heads(obs, rnn_states)
-        value = self._critic_infer(states) if self.has_central_value else None
+        value = self._critic_infer(states, cv_rnn_states) if self.has_central_value else None
         torch.randn(self._roll_noise.shape, device=self._roll_noise.device, out=self._roll_noise)
         vs, eps = self._rollout_value_stats()
         env_actions = None
@@ -853,6 +864,8 @@ class A2CAgent:
         res['env_actions'] = self._roll_env_actions if self.clip_actions else self._roll_actions
         if self.is_rnn:
             res['rnn_states'] = eng.last_states
+        if self._critic_rnn_engine() is not None:
+            res['cv_rnn_states'] = self._critic_rnn_engine().last_states
         return res
 
     def _actor_heads(self, obs, rnn_states):
@@ -888,10 +901,16 @@ class A2CAgent:
         cv = getattr(self, 'central_value_net', None)
         return None if cv is None else cv._engine
 
-    def _critic_infer(self, states):
+    def _critic_rnn_engine(self):
+        """The recurrent central value network on chain_net.RecurrentChainNet (value-tail mode), or None."""
+        cv = getattr(self, 'central_value_net', None)
+        return None if cv is None else cv._rnn_engine
+
+    def _critic_infer(self, states, cv_rnn_states=None):
         """CentralValueTrain.get_value's forward on the chain (central_value.py:208-222, ModelCentralValue.forward
         models.py:452-458): the states normalised in eval mode inside the launch; raw values [num_actors, 1] (any row
-        stride of `states`)."""
+        stride of `states`).  A recurrent critic: its engine's T = 1 forward from `cv_rnn_states` (None: the critic's own
+        `rnn_states`, which arrive zeroed where an episode ended), the next states left in the engine's `last_states`."""
         cv = self.central_value_net
         if states.stride(-1) != 1:
             states = states.contiguous()
@@ -899,6 +918,9 @@ class A2CAgent:
         if cv.normalize_input:
             m = cv.model.running_mean_std
             rms, eps = (m.running_mean, m.running_var), m.epsilon
+        if cv._rnn_engine is not None:
+            return cv._rnn_engine.forward(states, rms, eps, cv.rnn_states if cv_rnn_states is None else cv_rnn_states,
+                                          None, 1, keep=False)
         return cv._engine.infer(states, rms, eps)
 
     def _rollout_value_stats(self):
@@ -919,8 +941,11 @@ class A2CAgent:
     def _central_fast_values(self, states):
         """get_values with a central value network (a2c_common.py:605-614): the critic's forward only - the actor does
         not run and nothing is drawn from the generator - de-normalised, every agent of an env given the env's value
-        (central_value.py:223-225).  [num_actors * num_agents]."""
+        (central_value.py:223-225).  [num_actors * num_agents].  A recurrent critic's states advance with it, as
+        CentralValueTrain.get_value leaves them (central_value.py:222)."""
         v = self._denorm_values(self._critic_infer(states))
+        if self._critic_rnn_engine() is not None:
+            self.central_value_net.rnn_states = list(self._critic_rnn_engine().last_states)
         return v.expand(-1, self.num_agents).reshape(-1)
 
     def _fast_values(self, obs):
@@ -941,11 +966,14 @@ class A2CAgent:
 
     def _central_value_fused_ok(self):
         """No central value network, or one the fused step can run: a critic on the chain kernels (feed-forward, one
-        value column, `fused_mlp` not off in its config) over fp32 states.  Recurrent critics keep the torch rollout."""
+        value column, `fused_mlp` not off in its config) or - behind a recurrent actor, whose play_steps_rnn is where the
+        reference advances a recurrent critic (a2c_common.py:1085-1086) - a recurrent critic on its engine
+        (CentralValueTrain._rnn_engine), over fp32 states.  Any other recurrent critic keeps the torch rollout."""
         if not self.has_central_value:
             return True
         dtype = getattr(self.state_space, 'dtype', None)
-        return (self._critic_chain() is not None and dtype is not None and np.dtype(dtype) == np.float32)
+        on_kernels = self._critic_chain() is not None or (self._critic_rnn_engine() is not None and self.is_rnn)
+        return on_kernels and dtype is not None and np.dtype(dtype) == np.float32
 
     def _fused_rollout_eligible(self):
         """The rollout on the fused forwards: one value column, no central value network or one the fused step can run,
@@ -1038,6 +1066,8 @@ class A2CAgent:
                 self.central_value_net.pre_step_rnn(n)           # a2c_common.py:1085-1086
             res_dict = self._fast_policy_step(n) if fast else self._torch_action_values()
             self.rnn_states = [s.contiguous() for s in res_dict['rnn_states']]
+            if res_dict.get('cv_rnn_states') is not None:        # (a fused step: get_value's update, central_value.py:222)
+                self.central_value_net.rnn_states = [s.contiguous() for s in res_dict['cv_rnn_states']]
             if mb_valid is not None:
                 prev = self._mark_autoreset_rows(mb_valid, n)
                 if self.zero_rnn_on_done:
@@ -1498,6 +1528,9 @@ class A2CAgent:
         forms += [_ChainForms(c.chain, ((roll, 0),), arena) for c in self._chains or ()]
         if self._critic_chain() is not None:
             forms.append(_ChainForms(self._critic_chain().chain, ((self.num_actors, 0),),
+                                     self.central_value_net.optimizer.flat_params))
+        if self._critic_rnn_engine() is not None:
+            forms.append(_ChainForms(self._critic_rnn_engine().chain, ((self.num_actors, 0),),
                                      self.central_value_net.optimizer.flat_params))
         return forms
 

@@ -16,15 +16,19 @@ tanh trunk, widths that are multiples of 4, one value column); anything else kee
 Multi-agent envs (round 6, central_value.py:153-158,223-234): one state row per env, its value repeated for the env's agents
 in the rollout, the critic trained on agent 0's values and returns.  Recurrent critics (round 6,
 central_value.py:96-107,163-205): the network's RNN advances with the rollout (`pre_step_rnn` keeps the state every sequence
-starts from, `post_step_rnn` / `zero_states_where` zero it where an episode ended) and trains on sequence minibatches as a
-torch module between the loss and optimiser kernels.
+starts from, `post_step_rnn` / `zero_states_where` zero it where an episode ended) and trains on sequence minibatches.  A
+critic of the reference's SMAC shape - plain trunk, one LSTM / GRU layer of 16 / 32 / 64 / 128 units behind it (optionally
+layer-normed), one value column - does so on chain_net.RecurrentChainNet (`_rnn_engine`): trunk + gate-input product as
+one chain launch, the sequence-persistent RNN kernels, and the value head + value loss + its backward as the one launch
+of csrc/rnn_value_tail.hip; `fused_mlp: False` or `manual_lstm: False` in the central-value config, or any other shape,
+keeps the torch module between the loss and optimiser kernels.
 """
 import torch
 from torch import nn
 
 from . import distributed as rdist
 from . import ops
-from .chain_net import ChainNet
+from .chain_net import ChainNet, RecurrentChainNet, arena_layout
 from .flat_optim import FlatAdam
 from .lr_control import IdentityScheduler, LinearScheduler
 from .minibatch import PPODataset
@@ -39,6 +43,23 @@ def _value_chain(net, arena, max_rows):
     if not getattr(net, 'plain_trunk', True) or net.is_rnn():
         raise NotImplementedError('plain Linear + activation trunks only')
     return ChainNet(net.actor_mlp, [net.value], arena, max_rows)
+
+
+def _recurrent_critic_declined(net, config, value_size):
+    """Why a recurrent critic stays off chain_net.RecurrentChainNet (None: it is eligible) - the conditions of
+    DiscreteA2CAgent._recurrent_engine_declined for a value-only network."""
+    if not config.get('fused_mlp', True):
+        return 'fused_mlp is off'
+    if not config.get('manual_lstm', True):
+        return 'manual_lstm is off'
+    if value_size != 1 or not isinstance(net.value_act, nn.Identity) or net.value.out_features != 1:
+        return 'one linear value column only'
+    if not getattr(net, 'plain_trunk_rnn_ln', False):
+        return 'plain Linear + activation trunks only'
+    supported = {'lstm': ops.lstm_supported, 'gru': ops.gru_supported}.get(net.rnn_name)
+    if supported is None or net.rnn_layers != 1 or not supported(net.rnn_units):
+        return 'a single-layer LSTM or GRU with 16/32/64/128 units only'
+    return None
 
 
 class CentralValueTrain(nn.Module):
@@ -77,11 +98,32 @@ class CentralValueTrain(nn.Module):
         self.clip_value = config['clip_value']
         self.writter = writter
         self.weight_decay = config.get('weight_decay', 0.0)
-        self.optimizer = FlatAdam(self.model.parameters(), self.lr, eps=1e-08, weight_decay=self.weight_decay)
-        self._engine = None
-        if config.get('fused_mlp', True) and value_size == 1:
+        net = self.model.a2c_network
+        layout = None
+        rnn_declined = _recurrent_critic_declined(net, config, value_size) if self.is_rnn else None
+        if self.is_rnn and rnn_declined is None:
+            # what RecurrentChainNet asks of the arena: the head behind the matrices, the trunk's biases directly behind
+            # the last matrix (chain_net.arena_layout)
+            rest = [p for p in self.model.parameters() if all(p is not q for q in net.parameters())]
+            first = [m.bias for m in net.actor_mlp if isinstance(m, nn.Linear)]
+            layout = arena_layout(list(net.parameters()), [[net.value]], first_vectors=first) + rest
+        self.optimizer = FlatAdam(self.model.parameters(), self.lr, eps=1e-08, weight_decay=self.weight_decay,
+                                  layout=layout)
+        self._engine = None            # feed-forward critics: chain_net.ChainNet
+        self._rnn_engine = None        # recurrent critics: chain_net.RecurrentChainNet with the value tail
+        if self.is_rnn:
             try:
-                self._engine = _value_chain(self.model.a2c_network, self.optimizer, self.minibatch_size)
+                if rnn_declined is not None:
+                    raise NotImplementedError(rnn_declined)
+                self._rnn_engine = RecurrentChainNet(net.actor_mlp, net.rnn.rnn, net.layer_norm if net.rnn_ln else None,
+                                                     [net.value], self.optimizer, self.minibatch_size,
+                                                     infer_rows=self.num_actors, value_tail=True)
+            except NotImplementedError as e:
+                print(f'rl_games_amd: recurrent central value network outside the sequence-persistent RNN kernels ({e}); '
+                      f'using autograd')
+        elif config.get('fused_mlp', True) and value_size == 1:
+            try:
+                self._engine = _value_chain(net, self.optimizer, self.minibatch_size)
             except NotImplementedError as e:
                 print(f'rl_games_amd: central value network outside the fused chain kernels ({e}); using autograd')
         self.frame = 0
@@ -108,6 +150,13 @@ class CentralValueTrain(nn.Module):
                                  device=ppo_device)
         self._no_logstd = torch.zeros(1, dtype=torch.float32, device=ppo_device)
         self._row_index = 0
+
+    def decline_rnn_engine(self, reason):
+        """Take a recurrent critic off its engine (the agent: conditions that only it knows); it trains with autograd."""
+        if self._rnn_engine is not None:
+            print(f'rl_games_amd: recurrent central value network outside the sequence-persistent RNN kernels ({reason}); '
+                  f'using autograd')
+            self._rnn_engine = None
 
     # ------------------------------------------------------------------ reference API
     def update_lr(self, lr):
@@ -232,6 +281,30 @@ class CentralValueTrain(nn.Module):
         rnn_masks = batch.get('rnn_masks')
         opt.zero_grad()
         eng = self._engine
+        reng = self._rnn_engine if obs_batch.dtype == torch.float32 else None
+        mask = mask_sum = None
+        if rnn_masks is not None:
+            mask = rnn_masks.reshape(-1).float().contiguous()
+            mask_sum = mask.sum().reshape(1)
+        row = self._rows[self._row_index % self._rows.shape[0]]
+        self._row_index += 1
+        if reng is not None:
+            # the same normaliser update, then trunk + gate-input product, the sequence kernel, (layer norm,) and the
+            # value tail: head, loss, d values, the gradient of the recurrent features and the head's gradient partials
+            rms, eps = None, 1e-5
+            if self.normalize_input:
+                m = self.model.running_mean_std
+                if m.training:
+                    m.update(obs_batch)
+                rms, eps = (m.running_mean, m.running_var), m.epsilon
+            mb = obs_batch.shape[0]
+            reng.forward(obs_batch, rms, eps, batch['rnn_states'], batch['dones'], self.seq_length, keep=True,
+                         value_loss=(batch['old_values'].reshape(-1).contiguous(), batch['returns'].reshape(-1).contiguous(),
+                                     mask, mask_sum, self.e_clip, self.clip_value))
+            ops.ppo_loss_finalize(reng.loss_partials, reng.loss_blocks, 0, mb, mask is not None, 2.0, 0.0, 0.0,
+                                  row, self._no_logstd)
+            reng.backward()
+            return self._all_reduce_and_step(row)
         if eng is not None:
             # models.py:54-56 (norm_obs: training mode updates the statistics first), then the whole network in one launch
             rms, eps = None, 1e-5
@@ -247,12 +320,20 @@ class CentralValueTrain(nn.Module):
                 rnn = {'rnn_states': batch['rnn_states'], 'seq_length': self.seq_length, 'dones': batch['dones']}
             values = self.model.forward_values(obs_batch, rnn)              # [mb, V], autograd graph
         mb = values.shape[0]
-        mask = mask_sum = None
-        if rnn_masks is not None:
-            mask = rnn_masks.reshape(-1).float().contiguous()
-            mask_sum = mask.sum().reshape(1)
-        row = self._rows[self._row_index % self._rows.shape[0]]
-        self._row_index += 1
+        if values.shape[1] != 1:
+            # value_size > 1: the loss kernel carries one value column - calc_loss as torch ops (common_losses.py:16-29,
+            # torch_ext.apply_masks: masked, the sum over every column of the valid rows over the number of valid rows)
+            old, ret = batch['old_values'].reshape(values.shape), batch['returns'].reshape(values.shape)
+            if self.clip_value:
+                clipped = old + (values - old).clamp(-self.e_clip, self.e_clip)
+                c = torch.max((values - ret) ** 2, (clipped - ret) ** 2)
+            else:
+                c = (ret - values) ** 2
+            loss = c.mean() if mask is None else (c * mask.view(-1, 1)).sum() / mask_sum.clamp(min=1.0)[0]
+            loss.backward()
+            row.zero_()
+            row[1] = row[5] = loss.detach()
+            return self._all_reduce_and_step(row)
         d_val = self._d_val[:mb] if eng is None else eng.d_heads[:mb].view(-1)
         with torch.no_grad():
             ops.value_loss(values.detach().reshape(-1), batch['old_values'].reshape(-1).contiguous(),
@@ -264,6 +345,10 @@ class CentralValueTrain(nn.Module):
             eng.backward()
         else:
             torch.autograd.backward([values], [d_val.view(mb, 1)])
+        return self._all_reduce_and_step(row)
+
+    def _all_reduce_and_step(self, row):
+        opt = self.optimizer
         if self.multi_gpu:
             rdist.all_reduce_sum(opt.flat_grads)
         scale = 1.0 / self.world_size if self.multi_gpu else 1.0

@@ -170,9 +170,13 @@ class RecurrentChainNet:
     stations in reverse from `d_heads` and finishes every weight gradient in one `ops.MlpDwPlan` launch.
     trunk: nn.Sequential of Linear + activation pairs; rnn: the torch.nn.LSTM / GRU module (parameters only);
     layer_norm: nn.LayerNorm or None.  max_rows: rows of a training minibatch, infer_rows: rows of a rollout step.
+    value_tail (a central value critic: `heads` is one value column): the head, the clipped value loss and the head's
+    backward are one launch of csrc/rnn_value_tail.hip - forward(keep=True, value_loss=...) runs it in place of
+    heads -> loss kernel -> head dX -> bias sum -> 1 x H weight-gradient job and leaves the loss partials in
+    `loss_partials[:loss_blocks]`; backward() then starts at the recurrent features.
     Raises NotImplementedError for networks outside the kernels' envelope - there is no per-layer fallback."""
 
-    def __init__(self, trunk, rnn, layer_norm, heads, arena, max_rows, infer_rows=0):
+    def __init__(self, trunk, rnn, layer_norm, heads, arena, max_rows, infer_rows=0, value_tail=False):
         self.linears = [m for m in trunk if isinstance(m, nn.Linear)]
         acts = [m for m in trunk if not isinstance(m, nn.Linear)]
         if not self.linears or len(acts) != len(self.linears):
@@ -219,6 +223,9 @@ class RecurrentChainNet:
         layers = [(l.weight, l.bias, name) for l in self.linears] + [(rnn.weight_ih_l0, self.gate_bias, 'None')]
         self.chain = ops.MlpChain(layers, dev, weights_version=arena.weights_token)
         self._head_mfma = (C <= 64 and ops.mlp_rowgemm_supported(H, H) and self.head_w.data_ptr() % 16 == 0)
+        self.value_tail = bool(value_tail)
+        if self.value_tail and (len(heads) != 1 or C != 1):
+            raise NotImplementedError('the value tail takes one value column')
         rows = max(int(max_rows), int(infer_rows), 1)
         widths = [l.out_features for l in self.linears]
         G = self.Gr
@@ -243,6 +250,12 @@ class RecurrentChainNet:
             self.ln_out, self.d_ln_out, self.ln_stats = buf(H), buf(H), buf(2)
             nbl = max(ops.rnn_layer_norm_blocks(rows, H), 1)
             self.ln_partials = [torch.empty(nbl * H, dtype=torch.float64, device=dev) for _ in range(2)]
+        if self.value_tail:
+            nbt = max(ops.rnn_value_tail_blocks(rows, H), 1)
+            self.loss_partials = torch.empty(nbt * 7, dtype=torch.float64, device=dev)
+            self.tail_partials = [torch.empty(nbt * H, dtype=torch.float64, device=dev),
+                                  torch.empty(nbt, dtype=torch.float64, device=dev)]
+            self.loss_blocks = 0
         # final states of the last keep=False forward (LSTM: h and c, GRU: h), ping-pong so that a caller may feed them
         # back in
         nstates = 2 if self.lstm is not None else 1
@@ -255,14 +268,22 @@ class RecurrentChainNet:
         self.last_dw_path = None
 
     @torch.no_grad()
-    def forward(self, x_raw, rms, eps, rnn_states, dones, seq_length, keep):
+    def forward(self, x_raw, rms, eps, rnn_states, dones, seq_length, keep, value_loss=None):
         """x_raw [rows, in] RAW inputs, rows ordered (sequence, t) with `seq_length` steps each; rms = (running_mean,
         running_var) or None - the launch normalises on the way in.  rnn_states = (h0, c0) - GRU: (h0,) - of shape
         [1, rows / seq_length, H]; dones [rows] u8 resets the state entering a step (or None).  Returns the heads
         [rows, head_cols].  keep=True retains what backward() reads and leaves the state buffers alone (they hold the
         live rollout state); keep=False (a rollout step, get_values) keeps nothing and leaves the final states in
-        `last_states`, in whichever buffer pair the inputs do not live in."""
+        `last_states`, in whichever buffer pair the inputs do not live in.
+        value_tail engines: value_loss = (old_values [rows], returns [rows], mask [rows] or None, sum(mask) [1] or None,
+        e_clip, clip_value) with keep=True - the launch also writes d_heads and the gradient of the recurrent features,
+        and the loss partials for ops.ppo_loss_finalize; keep=False ends in the value column alone."""
         rows = x_raw.shape[0]
+        if self.value_tail and keep and value_loss is None:
+            raise ValueError('a value-tail engine needs value_loss=(old_values, returns, mask, mask_sum, e_clip, clip_value) '
+                             'for a training forward')
+        if value_loss is not None and not (self.value_tail and keep):
+            raise ValueError('value_loss goes with keep=True on a value-tail engine')
         S = rows // seq_length
         if S * seq_length != rows:
             raise ValueError(f'rows ({rows}) must be a multiple of seq_length ({seq_length})')
@@ -308,7 +329,16 @@ class RecurrentChainNet:
             ops.rnn_layer_norm_forward(out, self.ln.weight, self.ln.bias, self.ln.eps, feat,
                                        self.ln_stats[:rows] if keep else None)
         heads = self.heads[:rows]
-        if self._head_mfma:
+        if self.value_tail and keep:
+            old_values, returns, mask, mask_sum, e_clip, clip_value = value_loss
+            self.loss_blocks = nbt = ops.rnn_value_tail_blocks(rows, H)
+            d_feat = (self.d_ln_out if self.ln is not None else self.d_rnn_out)[:rows]
+            ops.rnn_value_tail(feat, self.head_w.view(-1), self.head_b, old_values, returns, heads.view(-1),
+                               self.d_heads[:rows].view(-1), d_feat, self.loss_partials, self.tail_partials[0],
+                               self.tail_partials[1], nbt, e_clip, clip_value, mask, mask_sum)
+        elif self.value_tail:
+            ops.rnn_value_head(feat, self.head_w.view(-1), self.head_b, heads.view(-1))
+        elif self._head_mfma:
             ops.mlp_linear_act_forward(feat, self.head_w, self.head_b, heads, act_kind=0)
         else:
             torch.addmm(self.head_b, feat, self.head_w.t(), out=heads)
@@ -324,13 +354,19 @@ class RecurrentChainNet:
         feat = (self.ln_out if self.ln is not None else self.rnn_out)[:rows]
         d_feat = (self.d_ln_out if self.ln is not None else self.d_rnn_out)[:rows]
         C = self.head_cols
-        if C <= ops.NARROW_MAX:
+        if self.value_tail:
+            pass                                            # (the tail launch of the forward wrote d_feat)
+        elif C <= ops.NARROW_MAX:
             ops.narrow_dx(d_heads, self.head_w, d_feat)
         elif ops.mlp_rowgemm_supported(C, C) and d_heads.data_ptr() % 16 == 0:
             ops.mlp_linear_act_backward(d_heads, self.head_w, None, d_feat, 0)
         else:
             torch.mm(d_heads, self.head_w, out=d_feat)
         colsums = []                                        # (partials, blocks, cols, gradient vector)
+        if self.value_tail:
+            nbt = self.loss_blocks
+            colsums += [(self.tail_partials[0][:nbt * H], nbt, H, self.head_w_grad.view(-1)),
+                        (self.tail_partials[1][:nbt], nbt, 1, self.head_b_grad)]
         d_out = self.d_rnn_out[:rows]
         if self.ln is not None:
             nbl = ops.rnn_layer_norm_blocks(rows, H)
@@ -361,9 +397,10 @@ class RecurrentChainNet:
         nblk = self.chain.num_blocks(rows, 1)
         parts = [p[:nblk * l.out_features] for p, l in zip(self.partials, self.linears)]
         self.chain.backward(dg, acts, dzs, parts)
-        jobs = [(d_heads, feat, self.head_w_grad), (dgh, self.hprev[:rows], rnn.weight_hh_l0.grad),
-                (dg, acts[-1], rnn.weight_ih_l0.grad)]
-        torch.sum(d_heads, dim=0, out=self.head_b_grad)
+        jobs = [(dgh, self.hprev[:rows], rnn.weight_hh_l0.grad), (dg, acts[-1], rnn.weight_ih_l0.grad)]
+        if not self.value_tail:
+            jobs.insert(0, (d_heads, feat, self.head_w_grad))
+            torch.sum(d_heads, dim=0, out=self.head_b_grad)
         for l in range(L - 1, -1, -1):
             lin = self.linears[l]
             jobs.append((dzs[l], acts[l - 1] if l > 0 else self._x, lin.weight.grad))

@@ -116,5 +116,26 @@ def smac_rnn_discrete(num_actors=8, cell='lstm', units=128, layer_norm=False, ac
             'network': net, 'config': cfg}
 
 
+def smac_rnn_cv_discrete(num_actors=8, agents=5, cell='lstm', units=128, layer_norm=False, state_dim=98, **over):
+    """smac_rnn_discrete with the recurrent central value critic of the reference's `*_rnn_cv` SMAC runs
+    (rl_games/configs/smac/v1/5m_vs_6m_rnn_cv.yaml, 3s_vs_5z_cv_rnn.yaml, 3m_torch_cv_rnn.yaml, runs/6h_vs_8z_rnn.yaml):
+    `agents` agents per env, and over the env's privileged state (`state_dim`) a ReLU trunk [512, 256], one LSTM / GRU
+    layer of `units` (optionally layer-normed) and one value column.  The critic's hyper-parameters follow
+    5m_vs_6m_rnn_cv.yaml; its minibatch is half of the env-steps of a rollout."""
+    cv_over = over.pop('central_value_config', {})
+    params = smac_rnn_discrete(num_actors, cell=cell, units=units, layer_norm=layer_norm, **over)
+    cfg = params['config']
+    cfg['minibatch_size'] = over.get('minibatch_size', max(num_actors * agents * cfg['horizon_length'] // 2, 8))
+    cfg['env_config'].update(state_dim=int(state_dim), agents=int(agents))
+    cfg['central_value_config'] = {
+        'minibatch_size': max(num_actors * cfg['horizon_length'] // 2, 8), 'mini_epochs': 4, 'learning_rate': 5e-4,
+        'clip_value': False, 'normalize_input': True, 'truncate_grads': True, 'grad_norm': 2,
+        'network': {'name': 'actor_critic', 'central_value': True,
+                    'mlp': {'units': [512, 256], 'activation': 'relu', 'initializer': {'name': 'default'}},
+                    'rnn': {'name': cell, 'units': units, 'layers': 1, 'layer_norm': bool(layer_norm)}}}
+    cfg['central_value_config'].update(cv_over)
+    return params
+
+
 def clone(params):
     return copy.deepcopy(params)

@@ -29,6 +29,7 @@
 // of d value (= the head biases' gradients) ride along in the block partials.
 
 #include "ppo_loss_tile.hpp"
+#include "value_loss_row.hpp"
 
 namespace rlg {
 
@@ -273,7 +274,7 @@ __global__ __launch_bounds__(256) void ppo_loss_discrete_kernel(DiscreteLossArgs
 // (rl_games/algos_torch/central_value.py:262-276): common_losses.critic_loss (clipped or plain,
 // common_losses.py:16-29) + torch_ext.apply_masks mean.  Emits d loss / d value per row and the
 // block partials {0, sum c, 0, 0, 0, sum mask, 0} that rlg_ppo_loss_finalize (actions_num 0)
-// reduces; with critic_coef = 2 there its total "loss" slot is exactly mean(c).
+// reduces; with critic_coef = 2 there its total "loss" slot is exactly mean(c).  The row's formula: value_loss_row.hpp.
 // ---------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void value_loss_kernel(
     const float* __restrict__ values, const float* __restrict__ old_values, const float* __restrict__ returns,
@@ -283,26 +284,11 @@ __global__ __launch_bounds__(256) void value_loss_kernel(
   const long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
   double acc[kLossScalars] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   if (i < mb) {
-    const float v = values[i], vo = old_values[i], R = returns[i];
-    float c_loss, g_v;
-    if (clip_value) {
-      const float delta = v - vo;
-      const float vclip = vo + clamp_nan(delta, -e_clip, e_clip);
-      const float d1 = v - R, d2 = vclip - R;
-      const float c1 = d1 * d1, c2 = d2 * d2;
-      c_loss = fmaxf(c1, c2);
-      const float in = (delta >= -e_clip && delta <= e_clip) ? 1.0f : 0.0f;
-      if (c1 > c2) g_v = 2.0f * d1; else if (c2 > c1) g_v = 2.0f * d2 * in;
-      else g_v = 0.5f * (2.0f * d1) + 0.5f * (2.0f * d2 * in);
-    } else {
-      const float d = R - v;
-      c_loss = d * d;
-      g_v = -2.0f * d;
-    }
     const float m = mask ? mask[i] : 1.0f;
     const float denom = mask ? fmaxf(*mask_sum, 1.0f) : static_cast<float>(mb);
-    d_values[i] = g_v * (m / denom);
-    acc[1] = static_cast<double>(c_loss) * m;
+    const ValueLossRow r = value_loss_row(values[i], old_values[i], returns[i], m, denom, e_clip, clip_value);
+    d_values[i] = r.d_value;
+    acc[1] = static_cast<double>(r.c_loss) * m;
     acc[5] = m;
   }
   block_sum<kLossScalars, 256>(acc, red);

@@ -189,7 +189,7 @@ class DiscreteA2CAgent(A2CAgent):
             self._roll_noise[at:at + rows * size].view(rows, size).exponential_()
             at += rows * size
 
-    def _policy_step_kernels(self, n, obs_raw, dones, rnn_states, store=True, states=None):
+    def _policy_step_kernels(self, n, obs_raw, dones, rnn_states, store=True, states=None, cv_rnn_states=None):
         """Chain forward(s) -> (central value: the critic's chain forward on `states`) -> Exp(1) draws -> categorical
         head (actions / neglogpacs / values into the buffer) -> obs + dones (+ states) into the buffer.  Same maths and
         the same generator use as get_(masked_)action_values + update_data; no host read, so the step can be captured."""
@@ -197,7 +197,7 @@ class DiscreteA2CAgent(A2CAgent):
         cv = self.has_central_value
         logits, value = self._chain_heads_of(self._preproc_obs(obs_raw), logits_only=cv, rnn_states=rnn_states)
         if cv:
-            value = self._critic_infer(states)
+            value = self._critic_infer(states, cv_rnn_states)
         rows = logits.shape[0]
         self._draw_exp_noise(rows)
         vs, eps = self._rollout_value_stats()
@@ -210,6 +210,8 @@ class DiscreteA2CAgent(A2CAgent):
         res = {'actions': self._roll_actions, 'values': self._roll_values.view(rows, 1)}
         if self._rnn_engine is not None:
             res['rnn_states'] = self._rnn_engine.last_states
+        if self._critic_rnn_engine() is not None:
+            res['cv_rnn_states'] = self._critic_rnn_engine().last_states
         return res
 
     def _fast_values(self, obs):
@@ -273,7 +275,9 @@ class DiscreteA2CAgent(A2CAgent):
         self._mb_index += 1
         self._forward_loss_backward(input_dict, row)
         self.trancate_gradients_and_step()
-        self.train_result = (row[0], row[1], row[2], row[4], self._host_lr, 1.0)
+        # (a central value network without `use_experimental_cv`: no actor value loss, a2c_discrete.py:164-167)
+        c_loss = row[1] if self.has_value_loss else torch.zeros((), device=row.device)
+        self.train_result = (row[0], c_loss, row[2], row[4], self._host_lr, 1.0)
 
     def _forward_loss_backward(self, input_dict, row):
         opt = self.optimizer

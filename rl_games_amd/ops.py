@@ -1451,3 +1451,51 @@ def rnn_layer_norm_backward(d_y, x, stats, gamma, d_x, d_gamma_partials, d_beta_
         _need(d_x, F32, 'd_x'), _need(d_gamma_partials, F64, 'd_gamma_partials'),
         _need(d_beta_partials, F64, 'd_beta_partials'), int(num_blocks), rows, H, _stream(x)),
         'rlg_rnn_layer_norm_backward')
+
+
+# ------------------------------------------------------------------ value tail behind the recurrent layer of a critic
+
+def rnn_value_tail_blocks(rows, hidden):
+    """Workgroups (= rows of the fp64 partials) of rnn_value_tail; 0: width outside 16 / 32 / 64 / 128 or no rows."""
+    return _lib.load().rlg_rnn_value_tail_num_blocks(int(rows), int(hidden))
+
+
+def rnn_value_head(feat, w, b, values):
+    """values [rows] = feat [rows, H] w [H] + b [1] (csrc/rnn_value_tail.hip, the inference form): fp64 products and
+    sum, one rounding."""
+    for t, name in ((feat, 'feat'), (w, 'w'), (b, 'b'), (values, 'values')):
+        _need(t, F32, name)
+    rows, H = feat.shape
+    if w.numel() != H or b.numel() != 1 or values.numel() != rows:
+        raise ValueError(f'rnn_value_head: feat [rows, H], w [H], b [1] and values [rows] do not agree: '
+                         f'{tuple(feat.shape)}, {tuple(w.shape)}, {tuple(b.shape)}, {tuple(values.shape)}')
+    _lib.check(_lib.load().rlg_rnn_value_head(
+        _need(feat, F32, 'feat'), _need(w, F32, 'w'), _need(b, F32, 'b'), _need(values, F32, 'values'), rows, H,
+        _stream(feat)), 'rlg_rnn_value_head')
+
+
+def rnn_value_tail(feat, w, b, old_values, returns, values, d_values, d_feat, loss_partials, d_w_partials, d_b_partials,
+                   num_blocks, e_clip, clip_value=True, mask=None, mask_sum=None):
+    """The value column over feat [rows, H], the critic loss of value_loss on it and its backward in one launch: values /
+    d_values [rows], d_feat [rows, H]; loss_partials fp64 [num_blocks * 7] for ppo_loss_finalize(actions_num 0),
+    d_w_partials fp64 [num_blocks * H] and d_b_partials fp64 [num_blocks] for colsum_finalize /
+    MlpDwPlan.launch(colsums=).  num_blocks: rnn_value_tail_blocks(rows, H)."""
+    for t, name in ((feat, 'feat'), (w, 'w'), (b, 'b'), (old_values, 'old_values'), (returns, 'returns'),
+                    (values, 'values'), (d_values, 'd_values'), (d_feat, 'd_feat')):
+        _need(t, F32, name)
+    rows, H = feat.shape
+    if (w.numel() != H or b.numel() != 1 or d_feat.shape != feat.shape
+            or any(t.numel() != rows for t in (old_values, returns, values, d_values))
+            or (mask is not None and mask.numel() != rows)):
+        raise ValueError(f'rnn_value_tail: feat / d_feat [rows, H], w [H], b [1] and {rows} rows of old_values / returns '
+                         f'/ values / d_values / mask expected: {tuple(feat.shape)}, {tuple(d_feat.shape)}, {tuple(w.shape)}')
+    nb = int(num_blocks)
+    if loss_partials.numel() < nb * 7 or d_w_partials.numel() < nb * H or d_b_partials.numel() < nb:
+        raise ValueError(f'rnn_value_tail: {nb * 7} / {nb * H} / {nb} partials needed')
+    _lib.check(_lib.load().rlg_rnn_value_tail(
+        _need(feat, F32, 'feat'), _need(w, F32, 'w'), _need(b, F32, 'b'), _need(old_values, F32, 'old_values'),
+        _need(returns, F32, 'returns'), _opt(mask, F32, 'mask'), _opt(mask_sum, F32, 'mask_sum'),
+        _need(values, F32, 'values'), _need(d_values, F32, 'd_values'), _need(d_feat, F32, 'd_feat'),
+        _need(loss_partials, F64, 'loss_partials'), _need(d_w_partials, F64, 'd_w_partials'),
+        _need(d_b_partials, F64, 'd_b_partials'), nb, rows, H, float(np.float32(e_clip)), 1 if clip_value else 0,
+        _stream(feat)), 'rlg_rnn_value_tail')

@@ -9,7 +9,13 @@ and state widths, the per-step rollout time (ms, median and spread over the epoc
 Kernel times come from a separate run under `rocprofv3 --kernel-trace --stats` (--only-fused keeps that trace to the
 fused path).
 
-    python tools/bench_cv_rollout.py [--shapes go1,humanoid,smac] [--epochs 7] [--only-fused]
+--critic-update (recurrent-critic shapes): times CentralValueTrain.train_net() instead - the critic on its engine
+(chain_net.RecurrentChainNet with the value tail of csrc/rnn_value_tail.hip) against `fused_mlp: False` in the critic's
+config (torch modules + autograd) - the same way, and counts the device launches of one critic optimiser step of either
+setting with torch.profiler.
+
+    python tools/bench_cv_rollout.py [--shapes go1,humanoid,smac,smac_rnn_24,smac_rnn] [--epochs 7] [--only-fused]
+                                     [--critic-update]
 """
 import argparse
 import json
@@ -34,6 +40,10 @@ SHAPES = {
     'humanoid': (65536, 32, 1, 108, 128, [400, 200, 100], 'elu'),
     # SMAC-like: 5 agents per env, Discrete(12) with action masks, both nets [256, 128] relu
     'smac': (8192, 16, 5, 56, 120, [256, 128], 'relu'),
+    # configs.smac_rnn_cv_discrete (5m_vs_6m_rnn_cv.yaml): 5 agents, masked Discrete(14), actor and critic [512, 256]
+    # relu + LSTM 128, sequences of 8 - at the config's 24 envs and at 4,096
+    'smac_rnn_24': (24, 16, 5, 80, 98, [512, 256], 'relu'),
+    'smac_rnn': (4096, 16, 5, 80, 98, [512, 256], 'relu'),
 }
 
 
@@ -44,8 +54,16 @@ def _critic(units, act, minibatch):
                         'mlp': {'units': list(units), 'activation': act, 'initializer': {'name': 'default'}}}}
 
 
-def _params(shape, fused):
+def _params(shape, fused, critic_engine=True):
     envs, horizon, agents, obs, states, units, act = SHAPES[shape]
+    if shape.startswith('smac_rnn'):
+        params = configs.smac_rnn_cv_discrete(num_actors=envs, agents=agents, state_dim=states, horizon_length=horizon,
+                                              fused_rollout=fused, mini_epochs=1)
+        params['network']['mlp'].update(units=units)
+        params['config']['central_value_config'].update(mini_epochs=1)
+        if not critic_engine:
+            params['config']['central_value_config']['fused_mlp'] = False
+        return params
     batch = envs * horizon
     mb = min(batch // 4, 32768)                 # (the update only warms up here: BASELINE's minibatch size at most)
     if shape == 'smac':
@@ -68,19 +86,23 @@ def _params(shape, fused):
     return params
 
 
-def _agent(shape, fused):
+def _play(agent):
+    return agent.play_steps_rnn() if agent.is_rnn else agent.play_steps()
+
+
+def _agent(shape, fused, critic_engine=True):
     torch.manual_seed(0)
-    params = _params(shape, fused)
+    params = _params(shape, fused, critic_engine)
     cls = DiscreteA2CAgent if params['algo']['name'] == 'a2c_discrete' else A2CAgent
     agent = cls(f'bench_cv_{shape}', params)
     agent.init_tensors()
     agent.obs = agent.env_reset()
-    assert agent._fast_rollout_ok() == fused
+    assert agent._fast_rollout_ok() == (fused and critic_engine)
     agent.epoch_num += 1
     agent.train_epoch()
     agent.set_eval()
     with torch.no_grad():
-        agent.play_steps()
+        _play(agent)
     torch.cuda.synchronize()
     return agent
 
@@ -90,9 +112,56 @@ def _timed_rollout(agent):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     with torch.no_grad():
-        agent.play_steps()
+        _play(agent)
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / agent.horizon_length * 1e3
+
+
+def _timed_critic_update(agent):
+    cv = agent.central_value_net
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    cv.train_net()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def _launches_per_critic_step(agent):
+    """Device launches (kernels and memory operations) of one CentralValueTrain.train_critic call."""
+    from torch.profiler import ProfilerActivity, profile
+    cv = agent.central_value_net
+    cv.train()
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        cv.train_critic(cv.dataset[0])
+        torch.cuda.synchronize()
+    return sum(e.count for e in prof.key_averages() if e.device_type == torch.autograd.DeviceType.CUDA)
+
+
+def _critic_update(shape, epochs):
+    agents = {e: _agent(shape, True, critic_engine=e) for e in (True, False)}
+    assert agents[True].central_value_net._rnn_engine is not None
+    assert agents[False].central_value_net._rnn_engine is None
+    for a in agents.values():
+        _timed_critic_update(a)
+    times = {e: [] for e in agents}
+    for _ in range(epochs):
+        for e, a in agents.items():
+            times[e].append(_timed_critic_update(a))
+    cv = agents[True].central_value_net
+    steps = cv.mini_epoch * cv.num_minibatches
+    envs, horizon, n_agents, obs, states, units, act = SHAPES[shape]
+    res = {'shape': shape, 'mode': 'critic-update', 'envs': envs, 'horizon': horizon, 'state_dim': states, 'units': units,
+           'critic_minibatch': cv.minibatch_size, 'optimiser_steps_per_train_net': steps, 'epochs': epochs,
+           'dw_path': cv._rnn_engine.last_dw_path}
+    for e, key in ((True, 'engine'), (False, 'autograd')):
+        res[f'{key}_train_net_ms'] = round(statistics.median(times[e]), 4)
+        res[f'{key}_train_net_ms_min_max'] = [round(min(times[e]), 4), round(max(times[e]), 4)]
+        res[f'{key}_launches_per_step'] = _launches_per_critic_step(agents[e])
+    # the tail launch stands for five: padded row-GEMM head, rlg_value_loss, narrow_dx, the bias sum, the 1 x H dW job
+    res['engine_launches_per_step_with_five_launch_tail'] = res['engine_launches_per_step'] + 4
+    res['autograd_over_engine'] = round(res['autograd_train_net_ms'] / res['engine_train_net_ms'], 3)
+    print(json.dumps(res), flush=True)
 
 
 def main():
@@ -100,9 +169,17 @@ def main():
     ap.add_argument('--shapes', default='go1,humanoid,smac')
     ap.add_argument('--epochs', type=int, default=7)
     ap.add_argument('--only-fused', action='store_true')
+    ap.add_argument('--critic-update', action='store_true')
     args = ap.parse_args()
     if args.epochs < 5:
         raise SystemExit('--epochs: at least 5 timed epochs')
+    if args.critic_update:
+        for shape in args.shapes.split(','):
+            if not shape.startswith('smac_rnn'):
+                raise SystemExit('--critic-update: recurrent-critic shapes (smac_rnn_24, smac_rnn) only')
+            _critic_update(shape, args.epochs)
+            torch.cuda.empty_cache()
+        return
     settings = (True,) if args.only_fused else (True, False)
     for shape in args.shapes.split(','):
         agents = {f: _agent(shape, f) for f in settings}
@@ -112,7 +189,7 @@ def main():
                 times[f].append(_timed_rollout(agents[f]))
         a = agents[True]
         envs, horizon, n_agents, obs, states, units, act = SHAPES[shape]
-        chain = a._critic_chain().chain
+        chain = (a._critic_chain() or a._critic_rnn_engine()).chain
         res = {'shape': shape, 'envs': envs, 'horizon': horizon, 'agents': n_agents, 'obs_dim': obs, 'state_dim': states,
                'units': units, 'activation': act, 'actions': getattr(a, 'branch_sizes', a.actions_num),
                'critic_split_planes': chain.split_products(envs, 0), 'critic_lean': chain.lean_used(envs, 0),
