@@ -752,6 +752,44 @@ int rlg_gru_seq_backward(const float* gates, const float* hn_all, const float* h
                          const unsigned char* dones_or_null, const float* w_hh, const float* d_out,
                          float* d_gx, float* d_gh, int num_seqs, int seq_len, int hidden, void* stream);
 
+/* Paired sequence launches: two problems A and B of ONE shape (cell, hidden, num_seqs, seq_len) that do not depend on
+ * each other - the actor's and the critic's recurrence of a `separate: True` network, each with its own RNN
+ * (network_builder.py:272-277, :372-421) - in one launch.  The grid has ceil(S / tile) x 2 workgroups: row 0 runs
+ * problem A, row 1 problem B, each workgroup the code of the single kernel, the tile chosen from ONE problem's
+ * num_seqs exactly as the single entry chooses it.  Every output is therefore bit-identical to what the two single
+ * launches write (csrc/rnn_seq.hpp, "paired launches").
+ * Arguments: the pointer list of the single entry for A (suffix _a), the same list for B (suffix _b), then the shared
+ * num_seqs, seq_len, hidden, stream.  An optional output may be given for one problem and NULL for the other.
+ * hipErrorInvalidValue, before the runtime is asked for anything and with nothing launched: a width other than
+ * 16 / 32 / 64 / 128; num_seqs <= 0 or seq_len <= 0; a NULL pointer without _or_null in either problem; at 128 units a
+ * w_hh of either problem that is not 16-byte aligned (not rlg_lstm_seq_backward_pair, whose single entry has no such
+ * rule either); an output buffer of A - gates, out, c_all / hn_all, hprev, h_final, c_final; d_gates; d_gx, d_gh -
+ * that is also the same-named buffer of B. */
+int rlg_lstm_seq_forward_pair(
+    float* gates_a, const float* w_hh_a, const float* h0_a, const float* c0_a, const unsigned char* dones_a_or_null,
+    float* out_a, float* c_all_a_or_null, float* hprev_a_or_null, float* h_final_a_or_null, float* c_final_a_or_null,
+    float* gates_b, const float* w_hh_b, const float* h0_b, const float* c0_b, const unsigned char* dones_b_or_null,
+    float* out_b, float* c_all_b_or_null, float* hprev_b_or_null, float* h_final_b_or_null, float* c_final_b_or_null,
+    int num_seqs, int seq_len, int hidden, void* stream);
+int rlg_lstm_seq_backward_pair(
+    const float* gates_a, const float* c_all_a, const float* c0_a, const unsigned char* dones_a_or_null,
+    const float* w_hh_a, const float* d_out_a, float* d_gates_a,
+    const float* gates_b, const float* c_all_b, const float* c0_b, const unsigned char* dones_b_or_null,
+    const float* w_hh_b, const float* d_out_b, float* d_gates_b,
+    int num_seqs, int seq_len, int hidden, void* stream);
+int rlg_gru_seq_forward_pair(
+    float* gates_a, const float* w_hh_a, const float* b_hh_a, const float* h0_a, const unsigned char* dones_a_or_null,
+    float* out_a, float* hn_all_a_or_null, float* hprev_a_or_null, float* h_final_a_or_null,
+    float* gates_b, const float* w_hh_b, const float* b_hh_b, const float* h0_b, const unsigned char* dones_b_or_null,
+    float* out_b, float* hn_all_b_or_null, float* hprev_b_or_null, float* h_final_b_or_null,
+    int num_seqs, int seq_len, int hidden, void* stream);
+int rlg_gru_seq_backward_pair(
+    const float* gates_a, const float* hn_all_a, const float* hprev_a, const unsigned char* dones_a_or_null,
+    const float* w_hh_a, const float* d_out_a, float* d_gx_a, float* d_gh_a,
+    const float* gates_b, const float* hn_all_b, const float* hprev_b, const unsigned char* dones_b_or_null,
+    const float* w_hh_b, const float* d_out_b, float* d_gx_b, float* d_gh_b,
+    int num_seqs, int seq_len, int hidden, void* stream);
+
 /* Layer normalisation behind the recurrent layer (csrc/rnn_layer_norm.hip): `rnn: {layer_norm: True}`,
  * nn.LayerNorm(rnn_units) over the RNN output [rows, hidden] (network_builder.py:447-500), hidden 16 / 32 / 64 / 128.
  *   forward:  y = (x - mean) * rstd * gamma + beta, biased variance from the centred values, rstd = 1 / sqrt(var + eps);

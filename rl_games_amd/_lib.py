@@ -115,9 +115,14 @@ _PROTOTYPES = {
     'rlg_lstm_supported': [_c_int],
     'rlg_lstm_seq_forward': [_P] * 10 + [_c_int, _c_int, _c_int, _P],
     'rlg_lstm_seq_backward': [_P] * 7 + [_c_int, _c_int, _c_int, _P],
+    # paired launches: problem A's pointers, problem B's, then the shared shape
+    'rlg_lstm_seq_forward_pair': [_P] * 20 + [_c_int, _c_int, _c_int, _P],
+    'rlg_lstm_seq_backward_pair': [_P] * 14 + [_c_int, _c_int, _c_int, _P],
     'rlg_gru_supported': [_c_int],
     'rlg_gru_seq_forward': [_P] * 9 + [_c_int, _c_int, _c_int, _P],
     'rlg_gru_seq_backward': [_P] * 8 + [_c_int, _c_int, _c_int, _P],
+    'rlg_gru_seq_forward_pair': [_P] * 18 + [_c_int, _c_int, _c_int, _P],
+    'rlg_gru_seq_backward_pair': [_P] * 16 + [_c_int, _c_int, _c_int, _P],
     # rnn_layer_norm.hip
     'rlg_rnn_layer_norm_num_blocks': [_c_ll, _c_int],
     'rlg_rnn_layer_norm_forward': [_P, _P, _P, _c_float, _P, _P, _c_ll, _c_int, _P],

@@ -31,6 +31,7 @@ from typing import NamedTuple
 
 import numpy as np
 import torch
+from torch import nn
 
 from . import distributed as rdist
 from . import ops
@@ -367,6 +368,7 @@ class A2CAgent:
         self.optimizer = FlatAdam(self.model.parameters(), self.last_lr, eps=1e-08,
                                   weight_decay=self.weight_decay, layout=layout)
         self._engine = None
+        self._rnn_pair = None
         if self._use_engine:
             try:
                 self._engine = ManualMLP(self.model.a2c_network, self.optimizer,
@@ -471,14 +473,59 @@ class A2CAgent:
         self.actions_low = torch.from_numpy(np.asarray(action_space.low).copy()).float().to(dev)
         self.actions_high = torch.from_numpy(np.asarray(action_space.high).copy()).float().to(dev)
 
-    def _arena_layout(self, config):
-        """Physical order of the parameters inside the optimiser's arena for agents outside the continuous engine
-        (None: parameters() order)."""
+    def _rnn_pair_declined(self, config):
+        """Why a network stays off chain_net.RecurrentChainPair (None: it is eligible): separate actor / critic trunks
+        of plain Linear + activation pairs, one LSTM / GRU layer of a supported width behind each (a layer norm behind
+        the RNN is fine), a log sigma vector, identity head activations, one value column, and neither `manual_lstm`
+        nor `fused_mlp` switched off."""
+        net = self.model.a2c_network
+        if self.is_discrete or not getattr(net, 'plain_separate_rnn', False):
+            return 'not a continuous policy of separate plain trunks with an RNN each'
+        if not config.get('manual_lstm', True):
+            return 'manual_lstm is off'
+        if not config.get('fused_mlp', True):
+            return 'fused_mlp is off'
+        if self._general_forms:
+            return 'a log sigma vector and one value column only'
+        if not all(isinstance(a, nn.Identity) for a in (net.mu_act, net.value_act, net.sigma_act)):
+            return 'identity head activations only'
+        supported = {'lstm': ops.lstm_supported, 'gru': ops.gru_supported}.get(net.rnn_name)
+        if supported is None or net.rnn_layers != 1 or not supported(net.rnn_units):
+            return 'a single-layer LSTM or GRU with 16/32/64/128 units only'
         return None
 
+    def _arena_layout(self, config):
+        """Physical order of the parameters inside the optimiser's arena for agents outside the continuous engine
+        (None: parameters() order).  Separate recurrent trunks on chain_net.RecurrentChainPair: the matrices first, each
+        trunk's bias vectors directly behind them (where RecurrentChainNet's chains want them), the head biases last."""
+        net = self.model.a2c_network
+        if not net.is_rnn() or self._rnn_pair_declined(config) is not None:
+            return None
+        from .chain_net import arena_layout
+        rest = [p for p in self.model.parameters() if all(p is not q for q in net.parameters())]
+        first = [m.bias for trunk in (net.actor_mlp, net.critic_mlp) for m in trunk if isinstance(m, nn.Linear)]
+        return arena_layout(list(net.parameters()), [[net.mu], [net.value]], first_vectors=first) + rest
+
     def _init_chains(self, config):
-        """Hook behind the optimiser: the discrete agent puts its trunks on the fused chain kernels here (ChainNet list)."""
+        """Hook behind the optimiser: the discrete agent puts its trunks on the fused chain kernels here (ChainNet list).
+        The continuous agent: `_rnn_pair`, separate actor / critic trunks with an RNN each on
+        chain_net.RecurrentChainPair - update and rollout; `_engine` stays None for them."""
         self._chains = None
+        net = self.model.a2c_network
+        if self._engine is not None or not net.is_rnn() or not net.is_separate_critic():
+            return
+        why = self._rnn_pair_declined(config)
+        if why is None:
+            from .chain_net import RecurrentChainPair
+            try:
+                ln = (net.a_layer_norm, net.c_layer_norm) if net.rnn_ln else (None, None)
+                self._rnn_pair = RecurrentChainPair(
+                    net.actor_mlp, net.a_rnn.rnn, ln[0], net.mu, net.critic_mlp, net.c_rnn.rnn, ln[1], net.value,
+                    self.optimizer, self.minibatch_size, infer_rows=self.num_actors * self.num_agents)
+            except NotImplementedError as e:
+                why = str(e)
+        if self._rnn_pair is None:
+            print(f'rl_games_amd: separate recurrent trunks outside the paired RNN engine ({why}); using autograd')
 
     def _alloc_loss_scratch(self, mb, dev):
         A = self.actions_num
@@ -665,7 +712,7 @@ class A2CAgent:
         self._gae_partials = torch.empty(num_moment_partials(rows), 6, dtype=torch.float64, device=dev)
         self.update_list = self._rollout_fields()
         self.tensor_list = self.update_list + ['obses', 'states', 'dones']
-        if self._engine is not None:
+        if self._engine is not None or self._rnn_pair is not None:
             self._roll_obs_norm = torch.empty((rows,) + tuple(self.obs_shape), dtype=torch.float32, device=dev)
             self._roll_noise = torch.empty(rows, self.actions_num, dtype=torch.float32, device=dev)
             self._roll_actions = torch.empty(rows, self.actions_num, dtype=torch.float32, device=dev)
@@ -863,14 +910,21 @@ class A2CAgent:
         res = {'actions': self._roll_actions, 'values': self._roll_values.view(rows, 1)}
         res['env_actions'] = self._roll_env_actions if self.clip_actions else self._roll_actions
         if self.is_rnn:
-            res['rnn_states'] = eng.last_states
+            res['rnn_states'] = (eng if eng is not None else self._rnn_pair).last_states
         if self._critic_rnn_engine() is not None:
             res['cv_rnn_states'] = self._critic_rnn_engine().last_states
         return res
 
     def _actor_heads(self, obs, rnn_states):
         """The actor's inference forward on the engine: heads [rows, ...] of preprocessed observations (any row stride
-        on the fused chain: a buffer slot [:, n, :]), the normaliser in eval mode.  No autograd, no host read."""
+        on the fused chain: a buffer slot [:, n, :]), the normaliser in eval mode.  No autograd, no host read.
+        Separate recurrent trunks: the pair's T = 1 forward on `rnn_states` (the actor's, then the critic's), whose
+        [value | mu] rows are the pair's joint heads and whose next states stay in its `last_states`."""
+        if self._rnn_pair is not None:
+            if obs.stride(-1) != 1:
+                obs = obs.contiguous()
+            self._rnn_pair.forward(obs, self._obs_rms(), self._obs_eps(), rnn_states, None, 1, keep=False)
+            return self._rnn_pair.joint_heads[:obs.shape[0]]
         eng = self._engine
         if not obs.is_contiguous() and (eng.chain is None or obs.stride(-1) != 1):
             obs = obs.contiguous()
@@ -982,7 +1036,11 @@ class A2CAgent:
                 and self._fused_rollout_network_ok())
 
     def _fused_rollout_network_ok(self):
-        """The actor on the manual engine."""
+        """The actor on the manual engine, or on the pair of recurrent engines (fp32 observations: the pair's chains
+        read them raw)."""
+        if self._rnn_pair is not None:
+            dtype = getattr(self.observation_space, 'dtype', None)
+            return dtype is not None and np.dtype(dtype) == np.float32
         return self._engine is not None
 
     def _fast_rollout_ok(self):
@@ -1283,6 +1341,8 @@ class A2CAgent:
         gets captured into a HIP graph per minibatch index."""
         if self._general_forms:
             return self._forward_loss_backward_general(input_dict, row)
+        if self._rnn_pair is not None and input_dict['obs'].dtype == torch.float32:
+            return self._forward_loss_backward_pair(input_dict, row)
         opt = self.optimizer
         net = self.model.a2c_network
         obs_batch = self._preproc_obs(input_dict['obs'])
@@ -1399,6 +1459,41 @@ class A2CAgent:
             torch.autograd.backward([mu, values], [d_mu, d_val.view(mb, 1)])
         # the step's mu is in the dataset now (write_back) and logstd is still the pre-step one (Adam comes behind)
         self._diag_minibatch(input_dict, mu=input_dict['mu'], logstd=logstd.detach(), actions=input_dict['actions'])
+
+    @torch.no_grad()
+    def _forward_loss_backward_pair(self, input_dict, row):
+        """_forward_loss_backward for separate recurrent trunks on chain_net.RecurrentChainPair: the normaliser's
+        statistics first (models.py:54-56), the pair's training forward, the fused loss launch writing d mu / d value
+        into the two engines' d_heads, its finalise launch (log sigma's gradient), the pair's backward.  No autograd,
+        no torch.nn forward."""
+        opt, pair, net = self.optimizer, self._rnn_pair, self.model.a2c_network
+        obs_batch = self._preproc_obs(input_dict['obs'])
+        if not obs_batch.is_contiguous():
+            obs_batch = obs_batch.contiguous()
+        opt.zero_grad()
+        if self.normalize_input and self.model.running_mean_std.training:
+            self.model.running_mean_std.update(obs_batch)
+        mu, values = pair.forward(obs_batch, self._obs_rms(), self._obs_eps(), input_dict['rnn_states'],
+                                  input_dict['dones'] if self.zero_rnn_on_done else None, self.seq_length, keep=True)
+        mb, A = mu.shape
+        rnn_masks = input_dict.get('rnn_masks', None)
+        mask = mask_sum = None
+        if rnn_masks is not None:
+            mask = rnn_masks.reshape(-1).float().contiguous()
+            mask_sum = mask.sum().reshape(1)
+        coef_b = self.bounds_loss_coef if self.bounds_loss_coef is not None else 0.0
+        kind = 0 if self.bounds_loss_coef is None else ops.BOUND_KINDS.get(self.bound_loss_type, 0)
+        coef_c = self.critic_coef if self.has_value_loss else 0.0       # (as _forward_loss_backward)
+        ops.ppo_loss_fused(mu, net.sigma.detach(), values[:, 0], input_dict['actions'], input_dict['old_logp_actions'],
+                           input_dict['advantages'], input_dict['old_values'].reshape(-1),
+                           input_dict['returns'].reshape(-1), input_dict['mu'], input_dict['sigma'],
+                           pair.actor.d_heads[:mb], pair.critic.d_heads[:mb, 0], self._loss_partials, self.e_clip, coef_c,
+                           coef_b, self.clip_value, self.surrogate, kind, True, mask, mask_sum)
+        ops.ppo_loss_finalize(self._loss_partials, ops.ppo_loss_blocks(mb), A, mb, mask is not None, coef_c,
+                              self.entropy_coef, coef_b, row, net.sigma.grad, opt.kl_slot)
+        pair.backward()
+        self._norm_ready = None
+        self._diag_minibatch(input_dict, mu=input_dict['mu'], logstd=net.sigma.detach(), actions=input_dict['actions'])
 
     def _diag_minibatch(self, input_dict, **new_policy):
         """The diagnostics launch of this minibatch (a2c_continuous.py:223-230, a2c_discrete.py:200-207): writes the
@@ -1526,6 +1621,8 @@ class A2CAgent:
         if eng is not None and eng.chain_rnn is not None:
             forms.append(_ChainForms(eng.chain_rnn, actor, arena, True, False))
         forms += [_ChainForms(c.chain, ((roll, 0),), arena) for c in self._chains or ()]
+        if self._rnn_pair is not None:                      # (updates stay eager: the step graphs alone read them)
+            forms += [_ChainForms(c, ((roll, 0),), arena) for c in self._rnn_pair.chains]
         if self._critic_chain() is not None:
             forms.append(_ChainForms(self._critic_chain().chain, ((self.num_actors, 0),),
                                      self.central_value_net.optimizer.flat_params))

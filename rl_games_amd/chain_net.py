@@ -11,7 +11,8 @@ Users: the central value network (central_value.py, one value column) and the di
 [value | logits] behind a shared trunk, or one chain per trunk with `separate: True` as in ppo_cartpole.yaml).  The
 continuous actor has its own engine (mlp_engine.ManualMLP: loss inside the backward launch, LSTM, HIP graphs).
 RecurrentChainNet is the recurrent counterpart for the discrete agent: the trunk + gate-input product as one chain, then
-the sequence-persistent LSTM / GRU kernels, an optional layer norm and the heads.  The
+the sequence-persistent LSTM / GRU kernels, an optional layer norm and the heads.  RecurrentChainPair drives two of them
+- the separate actor / critic trunks of a continuous policy, each with its own RNN - with one paired sequence launch.  The
 agents' rollout graphs read these chains too; they hold no pack launch, so the agent brings each chain's weight fragments
 / planes up to date in front of a replay along with its other chains (A2CAgent._forms_before_replay).
 """
@@ -278,12 +279,23 @@ class RecurrentChainNet:
         value_tail engines: value_loss = (old_values [rows], returns [rows], mask [rows] or None, sum(mask) [1] or None,
         e_clip, clip_value) with keep=True - the launch also writes d_heads and the gradient of the recurrent features,
         and the loss partials for ops.ppo_loss_finalize; keep=False ends in the value column alone."""
-        rows = x_raw.shape[0]
         if self.value_tail and keep and value_loss is None:
             raise ValueError('a value-tail engine needs value_loss=(old_values, returns, mask, mask_sum, e_clip, clip_value) '
                              'for a training forward')
         if value_loss is not None and not (self.value_tail and keep):
             raise ValueError('value_loss goes with keep=True on a value-tail engine')
+        args = self.forward_pre_rnn(x_raw, rms, eps, rnn_states, dones, seq_length, keep)
+        (ops.lstm_seq_forward if self.lstm is not None else ops.gru_seq_forward)(*args, seq_len=seq_length)
+        return self.forward_post_rnn(keep, value_loss)
+
+    # forward() and backward() in three stations each - in front of the sequence kernel, the kernel, behind it - so that
+    # RecurrentChainPair can run two engines' sequence kernels as one paired launch.  forward() / backward() launch
+    # what they always launched, in the same order.
+    @torch.no_grad()
+    def forward_pre_rnn(self, x_raw, rms, eps, rnn_states, dones, seq_length, keep):
+        """Trunk + gate-input product.  Returns the arguments of ops.lstm_seq_forward / gru_seq_forward (without
+        seq_len) for the sequence kernel that has to run next."""
+        rows = x_raw.shape[0]
         S = rows // seq_length
         if S * seq_length != rows:
             raise ValueError(f'rows ({rows}) must be a multiple of seq_length ({seq_length})')
@@ -313,22 +325,29 @@ class RecurrentChainNet:
             hT = self._state_buf[flip][0][:, :S]
             cT = self._state_buf[flip][1][:, :S] if self.lstm is not None else None
         out = self.rnn_out[:rows]
+        self._fwd = (rows, c0, dones, seq_length)
         if self.lstm is not None:
-            ops.lstm_seq_forward(gates, rnn.weight_hh_l0, h0, c0, dones, out,
-                                 self.c_all[:rows] if keep else None, self.hprev[:rows] if keep else None,
-                                 None if hT is None else hT[0], None if cT is None else cT[0], seq_len=seq_length)
             self.last_states = None if hT is None else (hT, cT)
-        else:
-            ops.gru_seq_forward(gates, rnn.weight_hh_l0, rnn.bias_hh_l0, h0, dones, out,
-                                self.hn_all[:rows] if keep else None, self.hprev[:rows] if keep else None,
-                                None if hT is None else hT[0], seq_len=seq_length)
-            self.last_states = None if hT is None else (hT,)
-        feat = out
+            return (gates, rnn.weight_hh_l0, h0, c0, dones, out,
+                    self.c_all[:rows] if keep else None, self.hprev[:rows] if keep else None,
+                    None if hT is None else hT[0], None if cT is None else cT[0])
+        self.last_states = None if hT is None else (hT,)
+        return (gates, rnn.weight_hh_l0, rnn.bias_hh_l0, h0, dones, out,
+                self.hn_all[:rows] if keep else None, self.hprev[:rows] if keep else None,
+                None if hT is None else hT[0])
+
+    @torch.no_grad()
+    def forward_post_rnn(self, keep, value_loss=None, heads_out=None):
+        """Layer norm and head product of the rows forward_pre_rnn saw.  heads_out: a [rows, head_cols] view (unit
+        column stride) to write the heads into in place of the engine's own buffer (plain head mode)."""
+        rows, c0, dones, seq_length = self._fwd
+        H = self.Hr
+        out = feat = self.rnn_out[:rows]
         if self.ln is not None:
             feat = self.ln_out[:rows]
             ops.rnn_layer_norm_forward(out, self.ln.weight, self.ln.bias, self.ln.eps, feat,
                                        self.ln_stats[:rows] if keep else None)
-        heads = self.heads[:rows]
+        heads = self.heads[:rows] if heads_out is None else heads_out
         if self.value_tail and keep:
             old_values, returns, mask, mask_sum, e_clip, clip_value = value_loss
             self.loss_blocks = nbt = ops.rnn_value_tail_blocks(rows, H)
@@ -349,7 +368,15 @@ class RecurrentChainNet:
     @torch.no_grad()
     def backward(self):
         """d loss / d heads in self.d_heads[:rows] -> every gradient of the network in the arena (overwritten)."""
-        rows, L, H, G, rnn = self._rows, len(self.linears), self.Hr, self.Gr, self.rnn
+        args = self.backward_pre_rnn()
+        (ops.lstm_seq_backward if self.lstm is not None else ops.gru_seq_backward)(*args, self._T)
+        self.backward_post_rnn()
+
+    @torch.no_grad()
+    def backward_pre_rnn(self):
+        """Head dX and layer-norm backward.  Returns the arguments of ops.lstm_seq_backward / gru_seq_backward (without
+        seq_len) for the sequence kernel that has to run next."""
+        rows, H, rnn = self._rows, self.Hr, self.rnn
         d_heads = self.d_heads[:rows]
         feat = (self.ln_out if self.ln is not None else self.rnn_out)[:rows]
         d_feat = (self.d_ln_out if self.ln is not None else self.d_rnn_out)[:rows]
@@ -374,19 +401,29 @@ class RecurrentChainNet:
             ops.rnn_layer_norm_backward(d_feat, self.rnn_out[:rows], self.ln_stats[:rows], self.ln.weight, d_out, pg, pb,
                                         nbl)
             colsums += [(pg, nbl, H, self.ln.weight.grad), (pb, nbl, H, self.ln.bias.grad)]
+        self._bwd_colsums = colsums
         gates = self.gates[:rows]
+        if self.lstm is not None:
+            return (gates, self.c_all[:rows], self._c0, self._dones, rnn.weight_hh_l0, d_out, self.d_gates[:rows])
+        return (gates, self.hn_all[:rows], self.hprev[:rows], self._dones, rnn.weight_hh_l0, d_out, self.d_gx[:rows],
+                self.d_gh[:rows])
+
+    @torch.no_grad()
+    def backward_post_rnn(self):
+        """From the gate gradients down: bias column sums, the trunk's dX chain, every weight gradient."""
+        rows, L, H, G, rnn = self._rows, len(self.linears), self.Hr, self.Gr, self.rnn
+        d_heads = self.d_heads[:rows]
+        feat = (self.ln_out if self.ln is not None else self.rnn_out)[:rows]
+        colsums = self._bwd_colsums
         nbg = ops.act_bwd_blocks(rows, G)
         gpart = self.gate_partials[:nbg * G]
         if self.lstm is not None:
             dg = dgh = self.d_gates[:rows]
-            ops.lstm_seq_backward(gates, self.c_all[:rows], self._c0, self._dones, rnn.weight_hh_l0, d_out, dg, self._T)
             ops.act_bwd_colsum(dg, None, dg, 0, gpart, nbg)                  # identity: column sums only
             colsums += [(gpart, nbg, G, rnn.bias_ih_l0.grad), (gpart, nbg, G, rnn.bias_hh_l0.grad)]   # d b_hh = d b_ih
         else:
             # dg = d_gx: the input side - W_ih, b_ih and the trunk; dgh = d_gh: the hidden side - W_hh, b_hh
             dg, dgh = self.d_gx[:rows], self.d_gh[:rows]
-            ops.gru_seq_backward(gates, self.hn_all[:rows], self.hprev[:rows], self._dones, rnn.weight_hh_l0, d_out,
-                                 dg, dgh, self._T)
             gpart_h = self.gate_partials_h[:nbg * G]
             ops.act_bwd_colsum(dg, None, dg, 0, gpart, nbg)
             ops.act_bwd_colsum(dgh, None, dgh, 0, gpart_h, nbg)
@@ -431,3 +468,90 @@ class RecurrentChainNet:
         self.last_dw_path = 'mfma' if plan else 'library'
         for dz, x, g in slow:                               # e.g. a first layer over 9 observations: not a multiple of 4
             torch.mm(dz.t(), x, out=g)
+
+
+def paired_launch_pays(cell, hidden, direction, num_seqs, seq_len):
+    """Is the paired sequence launch at least as fast as the two single launches (profiles/separate_rnn.txt, 1.)?  Every
+    measured shape class but one: the 128-unit LSTM forward at T = 1 once the paired grid holds more workgroups than
+    the chip has CUs (2 * ceil(S / 16) > 256) - 1.08 x the two launches at S = 4,096.  The outputs are the same bits
+    either way."""
+    return not (cell == 'lstm' and hidden == 128 and direction == 'forward' and seq_len == 1
+                and 2 * ((num_seqs + 15) // 16) > 256)
+
+
+class RecurrentChainPair:
+    """Separate actor / critic trunks, each with its own RNN (`separate: True`, network_builder.py:272-277, :372-421):
+    two RecurrentChainNet - the actor's over the `mu` head, the critic's over the `value` head, plain head mode - driven
+    side by side so that their sequence kernels run as ONE paired launch (csrc/rnn_seq.hpp, "paired launches":
+    bit-identical to the two single launches).  Everything else stays the launches of the two engines.
+    paired=False, or two RNNs that differ in cell or width (the reference's builder makes them alike, but the
+    constructor takes modules): two single launches.  So does the one shape class at which the paired launch measured
+    slower (paired_launch_pays).
+    The states travel in the model's order, the actor's in front of the critic's (get_default_rnn_state)."""
+
+    def __init__(self, actor_trunk, actor_rnn, actor_ln, mu, critic_trunk, critic_rnn, critic_ln, value, arena, max_rows,
+                 infer_rows=0, paired=True):
+        self.actor = RecurrentChainNet(actor_trunk, actor_rnn, actor_ln, [mu], arena, max_rows, infer_rows=infer_rows)
+        self.critic = RecurrentChainNet(critic_trunk, critic_rnn, critic_ln, [value], arena, max_rows,
+                                        infer_rows=infer_rows)
+        if self.critic.head_cols != 1:
+            raise NotImplementedError('one value column only')
+        self.lstm = self.actor.lstm is not None
+        same = (type(actor_rnn) is type(critic_rnn) and self.actor.Hr == self.critic.Hr)
+        self.paired = bool(paired) and same
+        self._states_each = 2 if self.lstm else 1
+        if (2 if self.critic.lstm is not None else 1) != self._states_each:
+            raise NotImplementedError('two RNNs of one cell only')
+        # a rollout step's heads side by side, [value | mu]: what ops.rollout_policy_head reads
+        A = self.actor.head_cols
+        self.joint_heads = torch.empty(max(int(infer_rows), 1), 1 + A, device=self.actor.heads.device)
+        self.last_states = None
+        self._T = 1
+
+    @property
+    def chains(self):
+        return [self.actor.chain, self.critic.chain]
+
+    @property
+    def last_dw_path(self):
+        return self.actor.last_dw_path
+
+    def _sequence(self, direction, a_args, b_args, seq_length):
+        cell = 'lstm' if self.lstm else 'gru'
+        if self.paired and paired_launch_pays(cell, self.actor.Hr, direction, a_args[0].shape[0] // seq_length, seq_length):
+            getattr(ops, f'{cell}_seq_{direction}_pair')(a_args, b_args, seq_len=seq_length)
+        else:
+            single = getattr(ops, f'{cell}_seq_{direction}')
+            single(*a_args, seq_len=seq_length)
+            single(*b_args, seq_len=seq_length)
+
+    @torch.no_grad()
+    def forward(self, x_raw, rms, eps, rnn_states, dones, seq_length, keep):
+        """The arguments of RecurrentChainNet.forward, rnn_states being the actor's followed by the critic's.  Returns
+        (mu [rows, A], value [rows, 1]).  keep=True: each engine's own heads buffer, and what backward() reads is kept;
+        keep=False: views of `joint_heads`, and the next states - the actor's, then the critic's - in `last_states`."""
+        n = self._states_each
+        rows = x_raw.shape[0]
+        a_args = self.actor.forward_pre_rnn(x_raw, rms, eps, tuple(rnn_states[:n]), dones, seq_length, keep)
+        b_args = self.critic.forward_pre_rnn(x_raw, rms, eps, tuple(rnn_states[n:]), dones, seq_length, keep)
+        self._sequence('forward', a_args, b_args, seq_length)
+        mu_out = value_out = None
+        if not keep:
+            if self.joint_heads.shape[0] < rows:
+                raise ValueError(f'{rows} rows in a step of a pair built for {self.joint_heads.shape[0]}')
+            mu_out, value_out = self.joint_heads[:rows, 1:], self.joint_heads[:rows, :1]
+        mu = self.actor.forward_post_rnn(keep, heads_out=mu_out)
+        value = self.critic.forward_post_rnn(keep, heads_out=value_out)
+        self.last_states = None if keep else tuple(self.actor.last_states) + tuple(self.critic.last_states)
+        self._T = seq_length
+        return mu, value
+
+    @torch.no_grad()
+    def backward(self):
+        """d loss / d mu in actor.d_heads[:rows], d loss / d value in critic.d_heads[:rows] -> every gradient of the two
+        trunks, RNNs, layer norms and heads in the arena (overwritten)."""
+        a_args = self.actor.backward_pre_rnn()
+        b_args = self.critic.backward_pre_rnn()
+        self._sequence('backward', a_args, b_args, self._T)
+        self.actor.backward_post_rnn()
+        self.critic.backward_post_rnn()

@@ -71,6 +71,24 @@ def pendulum_gru_4096(num_actors=4096, units=64, **over):
     return params
 
 
+def lunar_separate_rnn(num_actors=16, units=64, cell='lstm', layer_norm=False, **over):
+    """The reference's continuous recurrent configurations (rl_games/configs/ppo_lunar_continiuos_torch.yaml and, with
+    `layer_norm=True`, the network of configs/test/test_asymmetric_continuous.yaml): separate actor / critic trunks
+    [64] relu, each with its own LSTM layer of 64 units, LunarLanderContinuous-shaped obs 8 / act 2, 16 actors x 128
+    steps in sequences of 4.  Hyper-parameters follow ppo_lunar_continiuos_torch.yaml."""
+    net = _network([64], rnn={'name': cell, 'units': units, 'layers': 1, 'layer_norm': bool(layer_norm)})
+    net['separate'] = True
+    net['mlp']['activation'] = 'relu'
+    horizon = over.pop('horizon_length', 128)
+    cfg = _config('lunar_separate_rnn', num_actors, horizon, over.pop('minibatch_size', num_actors * horizon // 2), 4,
+                  {'obs_dim': 8, 'act_dim': 2}, normalize_value=False, value_bootstrap=False, tau=0.9,
+                  learning_rate=1e-3, grad_norm=0.5, critic_coef=1, bounds_loss_coef=0, seq_length=4,
+                  reward_shaper={'scale_value': 0.1})
+    cfg.update(over)
+    return {'algo': {'name': 'a2c_continuous'}, 'model': {'name': 'continuous_a2c_logstd'}, 'network': net,
+            'config': cfg}
+
+
 def tiny(num_actors=256, horizon=8, obs_dim=12, act_dim=3, **over):
     """Small config for smoke tests."""
     return {'algo': {'name': 'a2c_continuous'}, 'model': {'name': 'continuous_a2c_logstd'},

@@ -30,8 +30,9 @@
 
 namespace rlg {
 
+// Bodies as functions: the single and the paired kernel run the same code (rnn_seq.hpp, "paired launches").
 template <int H, int SB>
-__global__ __launch_bounds__(kSeqThreads) void gru_seq_fwd_kernel(
+__device__ __forceinline__ void gru_seq_fwd_body(
     float* __restrict__ gates,           // [S*T, 3H]  in: x-part + b_ih, out: activated gates (r, z, n)
     const float* __restrict__ w_hh,      // [3H, H]
     const float* __restrict__ b_hh,      // [3H]
@@ -119,7 +120,7 @@ __global__ __launch_bounds__(kSeqThreads) void gru_seq_fwd_kernel(
 }
 
 template <int H, int SB>
-__global__ __launch_bounds__(kSeqThreads) void gru_seq_bwd_kernel(
+__device__ __forceinline__ void gru_seq_bwd_body(
     const float* __restrict__ gates,     // [S*T, 3H] activated gates of the forward pass
     const float* __restrict__ hn_all,    // [S*T, H]
     const float* __restrict__ hprev,     // [S*T, H]
@@ -189,26 +190,62 @@ __global__ __launch_bounds__(kSeqThreads) void gru_seq_bwd_kernel(
   }
 }
 
+template <int H, int SB>
+__global__ __launch_bounds__(kSeqThreads) void gru_seq_fwd_kernel(
+    float* __restrict__ gates, const float* __restrict__ w_hh, const float* __restrict__ b_hh,
+    const float* __restrict__ h0, const uint8_t* __restrict__ dones, float* __restrict__ out,
+    float* __restrict__ hn_all, float* __restrict__ hprev, float* __restrict__ hT, int S, int T) {
+  gru_seq_fwd_body<H, SB>(gates, w_hh, b_hh, h0, dones, out, hn_all, hprev, hT, S, T);
+}
+
+template <int H, int SB>
+__global__ __launch_bounds__(kSeqThreads) void gru_seq_fwd_pair_kernel(GruFwdArgs a, GruFwdArgs b, int S, int T) {
+  const GruFwdArgs& p = pair_problem(a, b);
+  gru_seq_fwd_body<H, SB>(p.gates, p.w_hh, p.b_hh, p.h0, p.dones, p.out, p.hn_all, p.hprev, p.hT, S, T);
+}
+
+template <int H, int SB>
+__global__ __launch_bounds__(kSeqThreads) void gru_seq_bwd_kernel(
+    const float* __restrict__ gates, const float* __restrict__ hn_all, const float* __restrict__ hprev,
+    const uint8_t* __restrict__ dones, const float* __restrict__ w_hh, const float* __restrict__ d_out,
+    float* __restrict__ d_gx, float* __restrict__ d_gh, int S, int T) {
+  gru_seq_bwd_body<H, SB>(gates, hn_all, hprev, dones, w_hh, d_out, d_gx, d_gh, S, T);
+}
+
+template <int H, int SB>
+__global__ __launch_bounds__(kSeqThreads) void gru_seq_bwd_pair_kernel(GruBwdArgs a, GruBwdArgs b, int S, int T) {
+  const GruBwdArgs& p = pair_problem(a, b);
+  gru_seq_bwd_body<H, SB>(p.gates, p.hn_all, p.hprev, p.dones, p.w_hh, p.d_out, p.d_gx, p.d_gh, S, T);
+}
+
 // 128 units: W_hh (192 KB) does not fit LDS; csrc/gru_wide.hip keeps it in registers as MFMA fragments.
 int launch_gru_fwd_wide(float* gates, const float* w_hh, const float* b_hh, const float* h0, const uint8_t* dones,
                         float* out, float* hn_all, float* hprev, float* hT, int S, int T, hipStream_t st);
 int launch_gru_bwd_wide(const float* gates, const float* hn_all, const float* hprev, const uint8_t* dones,
                         const float* w_hh, const float* d_out, float* d_gx, float* d_gh, int S, int T,
                         hipStream_t st);
+int launch_gru_fwd_wide_pair(GruFwdArgs a, GruFwdArgs b, int S, int T, hipStream_t st);
+int launch_gru_bwd_wide_pair(GruBwdArgs a, GruBwdArgs b, int S, int T, hipStream_t st);
 
 // kernel families for rnn_seq.hpp's launch_seq
 struct GruFwd {
   template <int H, int SB>
   static constexpr auto kernel = gru_seq_fwd_kernel<H, SB>;
+  template <int H, int SB>
+  static constexpr auto pair_kernel = gru_seq_fwd_pair_kernel<H, SB>;
   static constexpr size_t lds_floats(int H, int SB) { return static_cast<size_t>(3) * H * H + 2 * SB * H; }
   static constexpr auto wide = launch_gru_fwd_wide;
+  static constexpr auto wide_pair = launch_gru_fwd_wide_pair;
 };
 
 struct GruBwd {
   template <int H, int SB>
   static constexpr auto kernel = gru_seq_bwd_kernel<H, SB>;
+  template <int H, int SB>
+  static constexpr auto pair_kernel = gru_seq_bwd_pair_kernel<H, SB>;
   static constexpr size_t lds_floats(int H, int SB) { return static_cast<size_t>(3) * H * H + SB * 3 * H; }
   static constexpr auto wide = launch_gru_bwd_wide;
+  static constexpr auto wide_pair = launch_gru_bwd_wide_pair;
 };
 
 }  // namespace rlg
@@ -232,6 +269,30 @@ int rlg_gru_seq_backward(const float* gates, const float* hn_all, const float* h
   if (num_seqs <= 0 || seq_len <= 0) return static_cast<int>(hipErrorInvalidValue);
   return rlg::launch_seq<rlg::GruBwd>(hidden, num_seqs, seq_len, static_cast<hipStream_t>(stream), gates, hn_all,
                                       hprev, dones_or_null, w_hh, d_out, d_gx, d_gh);
+}
+
+int rlg_gru_seq_forward_pair(
+    float* gates_a, const float* w_hh_a, const float* b_hh_a, const float* h0_a, const unsigned char* dones_a_or_null,
+    float* out_a, float* hn_all_a_or_null, float* hprev_a_or_null, float* h_final_a_or_null,
+    float* gates_b, const float* w_hh_b, const float* b_hh_b, const float* h0_b, const unsigned char* dones_b_or_null,
+    float* out_b, float* hn_all_b_or_null, float* hprev_b_or_null, float* h_final_b_or_null,
+    int num_seqs, int seq_len, int hidden, void* stream) {
+  const rlg::GruFwdArgs a{gates_a, w_hh_a, b_hh_a, h0_a, dones_a_or_null, out_a, hn_all_a_or_null, hprev_a_or_null,
+                          h_final_a_or_null};
+  const rlg::GruFwdArgs b{gates_b, w_hh_b, b_hh_b, h0_b, dones_b_or_null, out_b, hn_all_b_or_null, hprev_b_or_null,
+                          h_final_b_or_null};
+  return rlg::launch_seq_pair<rlg::GruFwd>(hidden, num_seqs, seq_len, static_cast<hipStream_t>(stream), a, b);
+}
+
+int rlg_gru_seq_backward_pair(
+    const float* gates_a, const float* hn_all_a, const float* hprev_a, const unsigned char* dones_a_or_null,
+    const float* w_hh_a, const float* d_out_a, float* d_gx_a, float* d_gh_a,
+    const float* gates_b, const float* hn_all_b, const float* hprev_b, const unsigned char* dones_b_or_null,
+    const float* w_hh_b, const float* d_out_b, float* d_gx_b, float* d_gh_b,
+    int num_seqs, int seq_len, int hidden, void* stream) {
+  const rlg::GruBwdArgs a{gates_a, hn_all_a, hprev_a, dones_a_or_null, w_hh_a, d_out_a, d_gx_a, d_gh_a};
+  const rlg::GruBwdArgs b{gates_b, hn_all_b, hprev_b, dones_b_or_null, w_hh_b, d_out_b, d_gx_b, d_gh_b};
+  return rlg::launch_seq_pair<rlg::GruBwd>(hidden, num_seqs, seq_len, static_cast<hipStream_t>(stream), a, b);
 }
 
 }  // extern "C"

@@ -28,7 +28,8 @@ namespace rlg {
 constexpr int kGruWideG = 3 * kWideH;
 constexpr int kGruWideGP = kGruWideG + kWidePad;   // padded row of the [SB][3H] LDS tile
 
-__global__ __launch_bounds__(kWideThreads) void gru_seq_fwd_wide_kernel(
+// Bodies as functions: the single and the paired kernel run the same code (rnn_seq.hpp, "paired launches").
+__device__ __forceinline__ void gru_seq_fwd_wide_body(
     float* __restrict__ gates,           // [S*T, 3H]  in: x-part + b_ih, out: activated gates (r, z, n)
     const float* __restrict__ w_hh,      // [3H, H], 16-byte aligned
     const float* __restrict__ b_hh,      // [3H]
@@ -102,7 +103,7 @@ __global__ __launch_bounds__(kWideThreads) void gru_seq_fwd_wide_kernel(
   }
 }
 
-__global__ __launch_bounds__(kWideThreads) void gru_seq_bwd_wide_kernel(
+__device__ __forceinline__ void gru_seq_bwd_wide_body(
     const float* __restrict__ gates,     // [S*T, 3H] activated gates of the forward pass
     const float* __restrict__ hn_all,    // [S*T, H]
     const float* __restrict__ hprev,     // [S*T, H]
@@ -180,6 +181,32 @@ __global__ __launch_bounds__(kWideThreads) void gru_seq_bwd_wide_kernel(
   }
 }
 
+__global__ __launch_bounds__(kWideThreads) void gru_seq_fwd_wide_kernel(
+    float* __restrict__ gates, const float* __restrict__ w_hh, const float* __restrict__ b_hh,
+    const float* __restrict__ h0, const uint8_t* __restrict__ dones, float* __restrict__ out,
+    float* __restrict__ hn_all, float* __restrict__ hprev, float* __restrict__ hT, int S, int T) {
+  gru_seq_fwd_wide_body(gates, w_hh, b_hh, h0, dones, out, hn_all, hprev, hT, S, T);
+}
+
+__global__ __launch_bounds__(kWideThreads) void gru_seq_fwd_wide_pair_kernel(GruFwdArgs a, GruFwdArgs b, int S,
+                                                                             int T) {
+  const GruFwdArgs& p = pair_problem(a, b);
+  gru_seq_fwd_wide_body(p.gates, p.w_hh, p.b_hh, p.h0, p.dones, p.out, p.hn_all, p.hprev, p.hT, S, T);
+}
+
+__global__ __launch_bounds__(kWideThreads) void gru_seq_bwd_wide_kernel(
+    const float* __restrict__ gates, const float* __restrict__ hn_all, const float* __restrict__ hprev,
+    const uint8_t* __restrict__ dones, const float* __restrict__ w_hh, const float* __restrict__ d_out,
+    float* __restrict__ d_gx, float* __restrict__ d_gh, int S, int T) {
+  gru_seq_bwd_wide_body(gates, hn_all, hprev, dones, w_hh, d_out, d_gx, d_gh, S, T);
+}
+
+__global__ __launch_bounds__(kWideThreads) void gru_seq_bwd_wide_pair_kernel(GruBwdArgs a, GruBwdArgs b, int S,
+                                                                             int T) {
+  const GruBwdArgs& p = pair_problem(a, b);
+  gru_seq_bwd_wide_body(p.gates, p.hn_all, p.hprev, p.dones, p.w_hh, p.d_out, p.d_gx, p.d_gh, S, T);
+}
+
 int launch_gru_fwd_wide(float* gates, const float* w_hh, const float* b_hh, const float* h0, const uint8_t* dones,
                         float* out, float* hn_all, float* hprev, float* hT, int S, int T, hipStream_t st) {
   if ((reinterpret_cast<uintptr_t>(w_hh) & 15u) != 0) return static_cast<int>(hipErrorInvalidValue);
@@ -193,6 +220,16 @@ int launch_gru_bwd_wide(const float* gates, const float* hn_all, const float* hp
   if ((reinterpret_cast<uintptr_t>(w_hh) & 15u) != 0) return static_cast<int>(hipErrorInvalidValue);
   return launch_tile<gru_seq_bwd_wide_kernel>(S, kWideSB, kWideThreads, 0, st, gates, hn_all, hprev, dones, w_hh,
                                               d_out, d_gx, d_gh, S, T);
+}
+
+int launch_gru_fwd_wide_pair(GruFwdArgs a, GruFwdArgs b, int S, int T, hipStream_t st) {
+  if (!wide_pair_aligned(a.w_hh, b.w_hh)) return static_cast<int>(hipErrorInvalidValue);
+  return launch_tile<gru_seq_fwd_wide_pair_kernel, 2>(S, kWideSB, kWideThreads, 0, st, a, b, S, T);
+}
+
+int launch_gru_bwd_wide_pair(GruBwdArgs a, GruBwdArgs b, int S, int T, hipStream_t st) {
+  if (!wide_pair_aligned(a.w_hh, b.w_hh)) return static_cast<int>(hipErrorInvalidValue);
+  return launch_tile<gru_seq_bwd_wide_pair_kernel, 2>(S, kWideSB, kWideThreads, 0, st, a, b, S, T);
 }
 
 }  // namespace rlg

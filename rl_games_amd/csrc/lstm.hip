@@ -27,8 +27,10 @@
 
 namespace rlg {
 
+// The kernels' bodies are functions, so that the single kernel and the paired one (rnn_seq.hpp, "paired launches")
+// run the same code: a body reads its tile from blockIdx.x and nothing else of the grid.
 template <int H, int SB>
-__global__ __launch_bounds__(kSeqThreads) void lstm_seq_fwd_kernel(
+__device__ __forceinline__ void lstm_seq_fwd_body(
     float* __restrict__ gates,           // [S*T, 4H]  in: x-part + biases, out: activated gates
     const float* __restrict__ w_hh,      // [4H, H]
     const float* __restrict__ h0,        // [S, H]
@@ -117,7 +119,7 @@ __global__ __launch_bounds__(kSeqThreads) void lstm_seq_fwd_kernel(
 }
 
 template <int H, int SB>
-__global__ __launch_bounds__(kSeqThreads) void lstm_seq_bwd_kernel(
+__device__ __forceinline__ void lstm_seq_bwd_body(
     const float* __restrict__ gates,     // [S*T, 4H] activated gates of the forward pass
     const float* __restrict__ c_all,     // [S*T, H]
     const float* __restrict__ c0,        // [S, H]
@@ -182,25 +184,62 @@ __global__ __launch_bounds__(kSeqThreads) void lstm_seq_bwd_kernel(
   }
 }
 
+template <int H, int SB>
+__global__ __launch_bounds__(kSeqThreads) void lstm_seq_fwd_kernel(
+    float* __restrict__ gates, const float* __restrict__ w_hh, const float* __restrict__ h0,
+    const float* __restrict__ c0, const uint8_t* __restrict__ dones, float* __restrict__ out,
+    float* __restrict__ c_all, float* __restrict__ hprev, float* __restrict__ hT, float* __restrict__ cT, int S,
+    int T) {
+  lstm_seq_fwd_body<H, SB>(gates, w_hh, h0, c0, dones, out, c_all, hprev, hT, cT, S, T);
+}
+
+template <int H, int SB>
+__global__ __launch_bounds__(kSeqThreads) void lstm_seq_fwd_pair_kernel(LstmFwdArgs a, LstmFwdArgs b, int S, int T) {
+  const LstmFwdArgs& p = pair_problem(a, b);
+  lstm_seq_fwd_body<H, SB>(p.gates, p.w_hh, p.h0, p.c0, p.dones, p.out, p.c_all, p.hprev, p.hT, p.cT, S, T);
+}
+
+template <int H, int SB>
+__global__ __launch_bounds__(kSeqThreads) void lstm_seq_bwd_kernel(
+    const float* __restrict__ gates, const float* __restrict__ c_all, const float* __restrict__ c0,
+    const uint8_t* __restrict__ dones, const float* __restrict__ w_hh, const float* __restrict__ d_out,
+    float* __restrict__ d_gates, int S, int T) {
+  lstm_seq_bwd_body<H, SB>(gates, c_all, c0, dones, w_hh, d_out, d_gates, S, T);
+}
+
+template <int H, int SB>
+__global__ __launch_bounds__(kSeqThreads) void lstm_seq_bwd_pair_kernel(LstmBwdArgs a, LstmBwdArgs b, int S, int T) {
+  const LstmBwdArgs& p = pair_problem(a, b);
+  lstm_seq_bwd_body<H, SB>(p.gates, p.c_all, p.c0, p.dones, p.w_hh, p.d_out, p.d_gates, S, T);
+}
+
 // 128 units: W_hh (256 KB) does not fit LDS; csrc/lstm_wide.hip keeps it in registers as MFMA fragments.
 int launch_lstm_fwd_wide(float* gates, const float* w_hh, const float* h0, const float* c0, const uint8_t* dones,
                          float* out, float* c_all, float* hprev, float* hT, float* cT, int S, int T, hipStream_t st);
 int launch_lstm_bwd_wide(const float* gates, const float* c_all, const float* c0, const uint8_t* dones,
                          const float* w_hh, const float* d_out, float* d_gates, int S, int T, hipStream_t st);
+int launch_lstm_fwd_wide_pair(LstmFwdArgs a, LstmFwdArgs b, int S, int T, hipStream_t st);
+int launch_lstm_bwd_wide_pair(LstmBwdArgs a, LstmBwdArgs b, int S, int T, hipStream_t st);
 
 // kernel families for rnn_seq.hpp's launch_seq
 struct LstmFwd {
   template <int H, int SB>
   static constexpr auto kernel = lstm_seq_fwd_kernel<H, SB>;
+  template <int H, int SB>
+  static constexpr auto pair_kernel = lstm_seq_fwd_pair_kernel<H, SB>;
   static constexpr size_t lds_floats(int H, int SB) { return static_cast<size_t>(4) * H * H + 2 * SB * H; }
   static constexpr auto wide = launch_lstm_fwd_wide;
+  static constexpr auto wide_pair = launch_lstm_fwd_wide_pair;
 };
 
 struct LstmBwd {
   template <int H, int SB>
   static constexpr auto kernel = lstm_seq_bwd_kernel<H, SB>;
+  template <int H, int SB>
+  static constexpr auto pair_kernel = lstm_seq_bwd_pair_kernel<H, SB>;
   static constexpr size_t lds_floats(int H, int SB) { return static_cast<size_t>(4) * H * H + SB * 4 * H; }
   static constexpr auto wide = launch_lstm_bwd_wide;
+  static constexpr auto wide_pair = launch_lstm_bwd_wide_pair;
 };
 
 }  // namespace rlg
@@ -225,6 +264,30 @@ int rlg_lstm_seq_backward(const float* gates, const float* c_all, const float* c
   if (num_seqs <= 0 || seq_len <= 0) return static_cast<int>(hipErrorInvalidValue);
   return rlg::launch_seq<rlg::LstmBwd>(hidden, num_seqs, seq_len, static_cast<hipStream_t>(stream), gates, c_all, c0,
                                        dones_or_null, w_hh, d_out, d_gates);
+}
+
+int rlg_lstm_seq_forward_pair(
+    float* gates_a, const float* w_hh_a, const float* h0_a, const float* c0_a, const unsigned char* dones_a_or_null,
+    float* out_a, float* c_all_a_or_null, float* hprev_a_or_null, float* h_final_a_or_null, float* c_final_a_or_null,
+    float* gates_b, const float* w_hh_b, const float* h0_b, const float* c0_b, const unsigned char* dones_b_or_null,
+    float* out_b, float* c_all_b_or_null, float* hprev_b_or_null, float* h_final_b_or_null, float* c_final_b_or_null,
+    int num_seqs, int seq_len, int hidden, void* stream) {
+  const rlg::LstmFwdArgs a{gates_a, w_hh_a, h0_a, c0_a, dones_a_or_null, out_a, c_all_a_or_null, hprev_a_or_null,
+                           h_final_a_or_null, c_final_a_or_null};
+  const rlg::LstmFwdArgs b{gates_b, w_hh_b, h0_b, c0_b, dones_b_or_null, out_b, c_all_b_or_null, hprev_b_or_null,
+                           h_final_b_or_null, c_final_b_or_null};
+  return rlg::launch_seq_pair<rlg::LstmFwd>(hidden, num_seqs, seq_len, static_cast<hipStream_t>(stream), a, b);
+}
+
+int rlg_lstm_seq_backward_pair(
+    const float* gates_a, const float* c_all_a, const float* c0_a, const unsigned char* dones_a_or_null,
+    const float* w_hh_a, const float* d_out_a, float* d_gates_a,
+    const float* gates_b, const float* c_all_b, const float* c0_b, const unsigned char* dones_b_or_null,
+    const float* w_hh_b, const float* d_out_b, float* d_gates_b,
+    int num_seqs, int seq_len, int hidden, void* stream) {
+  const rlg::LstmBwdArgs a{gates_a, c_all_a, c0_a, dones_a_or_null, w_hh_a, d_out_a, d_gates_a};
+  const rlg::LstmBwdArgs b{gates_b, c_all_b, c0_b, dones_b_or_null, w_hh_b, d_out_b, d_gates_b};
+  return rlg::launch_seq_pair<rlg::LstmBwd>(hidden, num_seqs, seq_len, static_cast<hipStream_t>(stream), a, b);
 }
 
 }  // extern "C"

@@ -26,7 +26,8 @@ namespace rlg {
 constexpr int kWideG = 4 * kWideH;
 constexpr int kWideGP = kWideG + kWidePad;      // padded row of the [SB][4H] LDS tile
 
-__global__ __launch_bounds__(kWideThreads) void lstm_seq_fwd_wide_kernel(
+// Bodies as functions: the single and the paired kernel run the same code (rnn_seq.hpp, "paired launches").
+__device__ __forceinline__ void lstm_seq_fwd_wide_body(
     float* __restrict__ gates,           // [S*T, 4H]  in: x-part + biases, out: activated gates
     const float* __restrict__ w_hh,      // [4H, H], 16-byte aligned
     const float* __restrict__ h0,        // [S, H]
@@ -104,7 +105,7 @@ __global__ __launch_bounds__(kWideThreads) void lstm_seq_fwd_wide_kernel(
   }
 }
 
-__global__ __launch_bounds__(kWideThreads) void lstm_seq_bwd_wide_kernel(
+__device__ __forceinline__ void lstm_seq_bwd_wide_body(
     const float* __restrict__ gates,     // [S*T, 4H] activated gates of the forward pass
     const float* __restrict__ c_all,     // [S*T, H]
     const float* __restrict__ c0,        // [S, H]
@@ -177,6 +178,33 @@ __global__ __launch_bounds__(kWideThreads) void lstm_seq_bwd_wide_kernel(
   }
 }
 
+__global__ __launch_bounds__(kWideThreads) void lstm_seq_fwd_wide_kernel(
+    float* __restrict__ gates, const float* __restrict__ w_hh, const float* __restrict__ h0,
+    const float* __restrict__ c0, const uint8_t* __restrict__ dones, float* __restrict__ out,
+    float* __restrict__ c_all, float* __restrict__ hprev, float* __restrict__ hT, float* __restrict__ cT, int S,
+    int T) {
+  lstm_seq_fwd_wide_body(gates, w_hh, h0, c0, dones, out, c_all, hprev, hT, cT, S, T);
+}
+
+__global__ __launch_bounds__(kWideThreads) void lstm_seq_fwd_wide_pair_kernel(LstmFwdArgs a, LstmFwdArgs b, int S,
+                                                                              int T) {
+  const LstmFwdArgs& p = pair_problem(a, b);
+  lstm_seq_fwd_wide_body(p.gates, p.w_hh, p.h0, p.c0, p.dones, p.out, p.c_all, p.hprev, p.hT, p.cT, S, T);
+}
+
+__global__ __launch_bounds__(kWideThreads) void lstm_seq_bwd_wide_kernel(
+    const float* __restrict__ gates, const float* __restrict__ c_all, const float* __restrict__ c0,
+    const uint8_t* __restrict__ dones, const float* __restrict__ w_hh, const float* __restrict__ d_out,
+    float* __restrict__ d_gates, int S, int T) {
+  lstm_seq_bwd_wide_body(gates, c_all, c0, dones, w_hh, d_out, d_gates, S, T);
+}
+
+__global__ __launch_bounds__(kWideThreads) void lstm_seq_bwd_wide_pair_kernel(LstmBwdArgs a, LstmBwdArgs b, int S,
+                                                                              int T) {
+  const LstmBwdArgs& p = pair_problem(a, b);
+  lstm_seq_bwd_wide_body(p.gates, p.c_all, p.c0, p.dones, p.w_hh, p.d_out, p.d_gates, S, T);
+}
+
 int launch_lstm_fwd_wide(float* gates, const float* w_hh, const float* h0, const float* c0, const uint8_t* dones,
                          float* out, float* c_all, float* hprev, float* hT, float* cT, int S, int T,
                          hipStream_t st) {
@@ -189,6 +217,16 @@ int launch_lstm_bwd_wide(const float* gates, const float* c_all, const float* c0
                          const float* w_hh, const float* d_out, float* d_gates, int S, int T, hipStream_t st) {
   return launch_tile<lstm_seq_bwd_wide_kernel>(S, kWideSB, kWideThreads, 0, st, gates, c_all, c0, dones, w_hh, d_out,
                                                d_gates, S, T);
+}
+
+int launch_lstm_fwd_wide_pair(LstmFwdArgs a, LstmFwdArgs b, int S, int T, hipStream_t st) {
+  if (!wide_pair_aligned(a.w_hh, b.w_hh)) return static_cast<int>(hipErrorInvalidValue);
+  return launch_tile<lstm_seq_fwd_wide_pair_kernel, 2>(S, kWideSB, kWideThreads, 0, st, a, b, S, T);
+}
+
+// (no alignment rule, as launch_lstm_bwd_wide: rnn_seq.hpp's list of asymmetries)
+int launch_lstm_bwd_wide_pair(LstmBwdArgs a, LstmBwdArgs b, int S, int T, hipStream_t st) {
+  return launch_tile<lstm_seq_bwd_wide_pair_kernel, 2>(S, kWideSB, kWideThreads, 0, st, a, b, S, T);
 }
 
 }  // namespace rlg

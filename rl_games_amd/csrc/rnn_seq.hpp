@@ -25,6 +25,14 @@
 //     d h_{-1}); the narrow LSTM backward does neither;
 //   * launch_lstm_bwd_wide does not check that w_hh is 16-byte aligned (its loads are scalar); the other three wide
 //     launchers do, although only the two forwards load 16 bytes at a time.
+//
+// Paired launches.  Separate actor / critic trunks run two recurrences of one shape (cell, H, S, T) that do not depend
+// on each other, each bound by its chain of T dependent steps and, at ceil(S / tile) workgroups, far from filling the
+// chip.  Every kernel therefore has a paired form: the grid gets a second row, blockIdx.y (uniform over the workgroup,
+// so the choice is scalar: selects between kernel-argument words, no lane ever branches on it) picks problem A or B,
+// and the workgroup runs the body of the single kernel on it.  The tile is chosen from ONE problem's S exactly as
+// for a single launch, so a paired launch computes, bit for bit, what the two single launches compute; it inherits
+// the asymmetries above.  The problems' argument sets travel by value as the *Args structs below.
 #pragma once
 
 #include "rlg_device.hpp"
@@ -45,6 +53,76 @@ __device__ __forceinline__ void tile_slot(int s, int S, Index& seq, bool& live) 
 // 0 where step `row` starts a new episode (the state entering it is zeroed), else 1
 __device__ __forceinline__ float step_keep(const uint8_t* dones, long long row) {
   return (dones && dones[row]) ? 0.0f : 1.0f;
+}
+
+// One problem's arguments, in the order of the single kernels' argument lists.  complete(): no required pointer is
+// NULL; shares_output(): a buffer this problem writes is the one the other writes under the same name.
+static inline bool same_buffer(const void* p, const void* q) { return p != nullptr && p == q; }
+
+struct LstmFwdArgs {
+  float* gates;
+  const float* w_hh;
+  const float* h0;
+  const float* c0;
+  const uint8_t* dones;
+  float* out;
+  float* c_all;
+  float* hprev;
+  float* hT;
+  float* cT;
+  bool complete() const { return gates && w_hh && h0 && c0 && out; }
+  bool shares_output(const LstmFwdArgs& o) const {
+    return same_buffer(gates, o.gates) || same_buffer(out, o.out) || same_buffer(c_all, o.c_all) ||
+           same_buffer(hprev, o.hprev) || same_buffer(hT, o.hT) || same_buffer(cT, o.cT);
+  }
+};
+
+struct LstmBwdArgs {
+  const float* gates;
+  const float* c_all;
+  const float* c0;
+  const uint8_t* dones;
+  const float* w_hh;
+  const float* d_out;
+  float* d_gates;
+  bool complete() const { return gates && c_all && c0 && w_hh && d_out && d_gates; }
+  bool shares_output(const LstmBwdArgs& o) const { return same_buffer(d_gates, o.d_gates); }
+};
+
+struct GruFwdArgs {
+  float* gates;
+  const float* w_hh;
+  const float* b_hh;
+  const float* h0;
+  const uint8_t* dones;
+  float* out;
+  float* hn_all;
+  float* hprev;
+  float* hT;
+  bool complete() const { return gates && w_hh && b_hh && h0 && out; }
+  bool shares_output(const GruFwdArgs& o) const {
+    return same_buffer(gates, o.gates) || same_buffer(out, o.out) || same_buffer(hn_all, o.hn_all) ||
+           same_buffer(hprev, o.hprev) || same_buffer(hT, o.hT);
+  }
+};
+
+struct GruBwdArgs {
+  const float* gates;
+  const float* hn_all;
+  const float* hprev;
+  const uint8_t* dones;
+  const float* w_hh;
+  const float* d_out;
+  float* d_gx;
+  float* d_gh;
+  bool complete() const { return gates && hn_all && hprev && w_hh && d_out && d_gx && d_gh; }
+  bool shares_output(const GruBwdArgs& o) const { return same_buffer(d_gx, o.d_gx) || same_buffer(d_gh, o.d_gh); }
+};
+
+// The problem of this workgroup in a paired launch (grid row 0: a, row 1: b)
+template <typename A>
+__device__ __forceinline__ const A& pair_problem(const A& a, const A& b) {
+  return blockIdx.y != 0 ? b : a;
 }
 
 // ------------------------------------------------------------------------------------------- device, narrow scheme
@@ -239,8 +317,9 @@ __device__ __forceinline__ float gru_bwd_point(const float (&g)[3], float hn, fl
 
 // ------------------------------------------------------------------------------------------- host
 
-// Launches Kernel(args...) on ceil(S / sb) workgroups; `shm` bytes of dynamic LDS are allowed once per instantiation.
-template <auto Kernel, typename... Args>
+// Launches Kernel(args...) on ceil(S / sb) workgroups per problem (Problems = 2: a paired kernel, the grid's second
+// row); `shm` bytes of dynamic LDS are allowed once per instantiation.
+template <auto Kernel, int Problems = 1, typename... Args>
 static int launch_tile(int S, int sb, int threads, size_t shm, hipStream_t st, Args... args) {
   static bool attr_set = false;
   if (shm != 0 && !attr_set) {
@@ -249,7 +328,7 @@ static int launch_tile(int S, int sb, int threads, size_t shm, hipStream_t st, A
     if (e != hipSuccess) return static_cast<int>(e);
     attr_set = true;
   }
-  hipLaunchKernelGGL(Kernel, dim3((S + sb - 1) / sb), dim3(threads), shm, st, args...);
+  hipLaunchKernelGGL(Kernel, dim3((S + sb - 1) / sb, Problems), dim3(threads), shm, st, args...);
   RLG_RETURN_LAUNCH_STATUS();
 }
 
@@ -264,37 +343,59 @@ static int seq_per_block(int S, int H) {
 }
 
 // A kernel family F (one cell, one direction) gives: F::kernel<H, SB>, the narrow kernel; F::lds_floats(H, SB), its
-// dynamic LDS; F::wide(args..., S, T, stream), the 128-unit launcher.
-template <typename F, int H, int SB, typename... Args>
+// dynamic LDS; F::wide(args..., S, T, stream), the 128-unit launcher; and for paired launches (Pair: args are the two
+// problems' *Args) F::pair_kernel<H, SB> and F::wide_pair(a, b, S, T, stream).
+template <typename F, int H, int SB, bool Pair, typename... Args>
 static int launch_narrow_sb(int S, int T, hipStream_t st, Args... args) {
   if constexpr (SB < kSeqThreads / H) {
     return static_cast<int>(hipErrorInvalidValue);
+  } else if constexpr (Pair) {
+    return launch_tile<F::template pair_kernel<H, SB>, 2>(S, SB, kSeqThreads, F::lds_floats(H, SB) * sizeof(float), st,
+                                                          args..., S, T);
   } else {
     return launch_tile<F::template kernel<H, SB>>(S, SB, kSeqThreads, F::lds_floats(H, SB) * sizeof(float), st,
                                                   args..., S, T);
   }
 }
 
-template <typename F, int H, typename... Args>
+template <typename F, int H, bool Pair, typename... Args>
 static int launch_narrow(int S, int T, hipStream_t st, Args... args) {
-  switch (seq_per_block(S, H)) {
-    case 16: return launch_narrow_sb<F, H, 16>(S, T, st, args...);
-    case 8: return launch_narrow_sb<F, H, 8>(S, T, st, args...);
-    default: return launch_narrow_sb<F, H, 4>(S, T, st, args...);
+  switch (seq_per_block(S, H)) {                        // S of ONE problem, also for a pair
+    case 16: return launch_narrow_sb<F, H, 16, Pair>(S, T, st, args...);
+    case 8: return launch_narrow_sb<F, H, 8, Pair>(S, T, st, args...);
+    default: return launch_narrow_sb<F, H, 4, Pair>(S, T, st, args...);
   }
+}
+
+// The wide forms' 16-byte rule for w_hh, for both problems of a paired launch
+static bool wide_pair_aligned(const float* w_hh_a, const float* w_hh_b) {
+  return ((reinterpret_cast<uintptr_t>(w_hh_a) | reinterpret_cast<uintptr_t>(w_hh_b)) & 15u) == 0;
 }
 
 static bool seq_hidden_supported(int hidden) { return hidden == 16 || hidden == 32 || hidden == 64 || hidden == 128; }
 
-template <typename F, typename... Args>
+template <typename F, bool Pair = false, typename... Args>
 static int launch_seq(int hidden, int S, int T, hipStream_t st, Args... args) {
   switch (hidden) {
-    case 16: return launch_narrow<F, 16>(S, T, st, args...);
-    case 32: return launch_narrow<F, 32>(S, T, st, args...);
-    case 64: return launch_narrow<F, 64>(S, T, st, args...);
-    case 128: return F::wide(args..., S, T, st);
+    case 16: return launch_narrow<F, 16, Pair>(S, T, st, args...);
+    case 32: return launch_narrow<F, 32, Pair>(S, T, st, args...);
+    case 64: return launch_narrow<F, 64, Pair>(S, T, st, args...);
+    case 128:
+      if constexpr (Pair) {
+        return F::wide_pair(args..., S, T, st);
+      } else {
+        return F::wide(args..., S, T, st);
+      }
     default: return static_cast<int>(hipErrorInvalidValue);
   }
+}
+
+// The paired entry points: everything is checked here, on the host, before the runtime is asked for anything.
+template <typename F, typename A>
+static int launch_seq_pair(int hidden, int S, int T, hipStream_t st, const A& a, const A& b) {
+  if (S <= 0 || T <= 0 || !seq_hidden_supported(hidden)) return static_cast<int>(hipErrorInvalidValue);
+  if (!a.complete() || !b.complete() || a.shares_output(b)) return static_cast<int>(hipErrorInvalidValue);
+  return launch_seq<F, true>(hidden, S, T, st, a, b);
 }
 
 }  // namespace rlg

@@ -1365,6 +1365,57 @@ def lstm_seq_backward(gates, c_all, c0, dones, w_hh, d_out, d_gates, seq_len):
         'rlg_lstm_seq_backward')
 
 
+def _pair_shape(a_gates, b_gates, gates_per_unit, seq_len):
+    """(S, H) of a paired launch: the two problems have one shape."""
+    if a_gates.shape != b_gates.shape:
+        raise ValueError(f'a paired launch needs two problems of one shape: gates {tuple(a_gates.shape)} and '
+                         f'{tuple(b_gates.shape)}')
+    B, G = a_gates.shape
+    if (B // seq_len) * seq_len != B:
+        raise ValueError(f'rows ({B}) must be a multiple of seq_len ({seq_len})')
+    return B // seq_len, G // gates_per_unit
+
+
+def _lstm_forward_pointers(gates, w_hh, h0, c0, dones, out, c_all=None, hprev=None, h_final=None, c_final=None):
+    G = gates.shape[1]
+    H = G // 4
+    if G != 4 * H or tuple(w_hh.shape) != (G, H) or out.shape != (gates.shape[0], H):
+        raise ValueError(f'gates [rows, 4H], w_hh [4H, H] and out [rows, H] do not agree: {tuple(gates.shape)}, '
+                         f'{tuple(w_hh.shape)}, {tuple(out.shape)}')
+    return (_need(gates, F32, 'gates'), _need(w_hh, F32, 'w_hh'), _need(h0, F32, 'h0'), _need(c0, F32, 'c0'),
+            _opt(dones, torch.uint8, 'dones'), _need(out, F32, 'out'), _opt(c_all, F32, 'c_all'),
+            _opt(hprev, F32, 'hprev'), _opt(h_final, F32, 'h_final'), _opt(c_final, F32, 'c_final'))
+
+
+def _lstm_backward_pointers(gates, c_all, c0, dones, w_hh, d_out, d_gates):
+    G = gates.shape[1]
+    H = G // 4
+    if G != 4 * H or tuple(w_hh.shape) != (G, H) or d_gates.shape != gates.shape:
+        raise ValueError(f'gates / d_gates [rows, 4H] and w_hh [4H, H] do not agree: {tuple(gates.shape)}, '
+                         f'{tuple(d_gates.shape)}, {tuple(w_hh.shape)}')
+    return (_need(gates, F32, 'gates'), _need(c_all, F32, 'c_all'), _need(c0, F32, 'c0'),
+            _opt(dones, torch.uint8, 'dones'), _need(w_hh, F32, 'w_hh'), _need(d_out, F32, 'd_out'),
+            _need(d_gates, F32, 'd_gates'))
+
+
+def lstm_seq_forward_pair(a, b, seq_len=1):
+    """Two lstm_seq_forward problems of one shape in ONE launch (twice the workgroups; bit-identical to the two single
+    launches).  a, b: one problem each, the arguments of lstm_seq_forward in its order, without seq_len, as a tuple;
+    dones and the optional outputs may be given for one problem and not for the other.  No output buffer may be shared."""
+    lib = _lib.load()
+    pa, pb = _lstm_forward_pointers(*a), _lstm_forward_pointers(*b)
+    S, H = _pair_shape(a[0], b[0], 4, seq_len)
+    _lib.check(lib.rlg_lstm_seq_forward_pair(*pa, *pb, S, seq_len, H, _stream(a[0])), 'rlg_lstm_seq_forward_pair')
+
+
+def lstm_seq_backward_pair(a, b, seq_len):
+    """Two lstm_seq_backward problems of one shape in one launch; a, b as for lstm_seq_forward_pair."""
+    lib = _lib.load()
+    pa, pb = _lstm_backward_pointers(*a), _lstm_backward_pointers(*b)
+    S, H = _pair_shape(a[0], b[0], 4, seq_len)
+    _lib.check(lib.rlg_lstm_seq_backward_pair(*pa, *pb, S, seq_len, H, _stream(a[0])), 'rlg_lstm_seq_backward_pair')
+
+
 # ------------------------------------------------------------------ recurrent policy (GRU)
 
 def gru_supported(hidden):
@@ -1411,6 +1462,46 @@ def gru_seq_backward(gates, hn_all, hprev, dones, w_hh, d_out, d_gx, d_gh, seq_l
         _opt(dones, torch.uint8, 'dones'), _need(w_hh, F32, 'w_hh'), _need(d_out, F32, 'd_out'),
         _need(d_gx, F32, 'd_gx'), _need(d_gh, F32, 'd_gh'), S, seq_len, H, _stream(gates)),
         'rlg_gru_seq_backward')
+
+
+def _gru_forward_pointers(gates, w_hh, b_hh, h0, dones, out, hn_all=None, hprev=None, h_final=None):
+    G = gates.shape[1]
+    H = G // 3
+    if G != 3 * H or tuple(w_hh.shape) != (G, H) or b_hh.numel() != G:
+        raise ValueError(f'gates [rows, 3H], w_hh [3H, H] and b_hh [3H] do not agree: {tuple(gates.shape)}, '
+                         f'{tuple(w_hh.shape)}, {tuple(b_hh.shape)}')
+    return (_need(gates, F32, 'gates'), _need(w_hh, F32, 'w_hh'), _need(b_hh, F32, 'b_hh'), _need(h0, F32, 'h0'),
+            _opt(dones, torch.uint8, 'dones'), _need(out, F32, 'out'), _opt(hn_all, F32, 'hn_all'),
+            _opt(hprev, F32, 'hprev'), _opt(h_final, F32, 'h_final'))
+
+
+def _gru_backward_pointers(gates, hn_all, hprev, dones, w_hh, d_out, d_gx, d_gh):
+    G = gates.shape[1]
+    H = G // 3
+    if G != 3 * H or tuple(w_hh.shape) != (G, H) or d_gx.shape != gates.shape or d_gh.shape != gates.shape:
+        raise ValueError(f'gates / d_gx / d_gh [rows, 3H] and w_hh [3H, H] do not agree: {tuple(gates.shape)}, '
+                         f'{tuple(d_gx.shape)}, {tuple(d_gh.shape)}, {tuple(w_hh.shape)}')
+    return (_need(gates, F32, 'gates'), _need(hn_all, F32, 'hn_all'), _need(hprev, F32, 'hprev'),
+            _opt(dones, torch.uint8, 'dones'), _need(w_hh, F32, 'w_hh'), _need(d_out, F32, 'd_out'),
+            _need(d_gx, F32, 'd_gx'), _need(d_gh, F32, 'd_gh'))
+
+
+def gru_seq_forward_pair(a, b, seq_len=1):
+    """Two gru_seq_forward problems of one shape in ONE launch (twice the workgroups; bit-identical to the two single
+    launches).  a, b: one problem each, the arguments of gru_seq_forward in its order, without seq_len, as a tuple;
+    dones and the optional outputs may be given for one problem and not for the other.  No output buffer may be shared."""
+    lib = _lib.load()
+    pa, pb = _gru_forward_pointers(*a), _gru_forward_pointers(*b)
+    S, H = _pair_shape(a[0], b[0], 3, seq_len)
+    _lib.check(lib.rlg_gru_seq_forward_pair(*pa, *pb, S, seq_len, H, _stream(a[0])), 'rlg_gru_seq_forward_pair')
+
+
+def gru_seq_backward_pair(a, b, seq_len):
+    """Two gru_seq_backward problems of one shape in one launch; a, b as for gru_seq_forward_pair."""
+    lib = _lib.load()
+    pa, pb = _gru_backward_pointers(*a), _gru_backward_pointers(*b)
+    S, H = _pair_shape(a[0], b[0], 3, seq_len)
+    _lib.check(lib.rlg_gru_seq_backward_pair(*pa, *pb, S, seq_len, H, _stream(a[0])), 'rlg_gru_seq_backward_pair')
 
 
 # ------------------------------------------------------------------ layer norm behind the recurrent layer

@@ -262,10 +262,13 @@ class ActorCriticNetwork(nn.Module):
             self.critic_mlp = build_trunk(mlp_in, self.units, **self._trunk_kw)
         # what the fused engines take (mlp_engine.ManualMLP): Linear + activation pairs, the RNN plainly behind them
         # ... plain but for a layer norm behind the RNN: what chain_net.RecurrentChainNet takes (the discrete agent)
-        self.plain_trunk_rnn_ln = (not self._trunk_kw['d2rl'] and self._trunk_kw['norm_func_name'] is None and
-                                   not (self.rnn_before_mlp or self.rnn_concat_input or self.rnn_concat_output)
-                                   and not (self.separate and self.has_rnn))
+        plain_but_separate = (not self._trunk_kw['d2rl'] and self._trunk_kw['norm_func_name'] is None and
+                              not (self.rnn_before_mlp or self.rnn_concat_input or self.rnn_concat_output))
+        self.plain_trunk_rnn_ln = plain_but_separate and not (self.separate and self.has_rnn)
         self.plain_trunk = self.plain_trunk_rnn_ln and not self.rnn_ln
+        # ... plain but for separate trunks that each have an RNN (and maybe a layer norm) of their own: what
+        # chain_net.RecurrentChainPair takes (the continuous agent)
+        self.plain_separate_rnn = plain_but_separate and self.separate and self.has_rnn
         return out_size
 
     def _init_central_value(self, net_params, input_shape, value_size, num_seqs):
