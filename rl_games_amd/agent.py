@@ -489,10 +489,8 @@ class A2CAgent:
             return 'a log sigma vector and one value column only'
         if not all(isinstance(a, nn.Identity) for a in (net.mu_act, net.value_act, net.sigma_act)):
             return 'identity head activations only'
-        supported = {'lstm': ops.lstm_supported, 'gru': ops.gru_supported}.get(net.rnn_name)
-        if supported is None or net.rnn_layers != 1 or not supported(net.rnn_units):
-            return 'a single-layer LSTM or GRU with 16/32/64/128 units only'
-        return None
+        from .chain_net import rnn_cell_declined
+        return rnn_cell_declined(net.rnn_name, net.rnn_layers, net.rnn_units)
 
     def _arena_layout(self, config):
         """Physical order of the parameters inside the optimiser's arena for agents outside the continuous engine
@@ -1578,7 +1576,7 @@ class A2CAgent:
                   and eng.gradient_elements() == self.optimizer.numel)
             if ok:
                 # one entry per finalise workgroup: ~ one per 64 weights + the bias / loss blocks (MlpDwPlan.
-                # finalize_blocks); a plan that still needs more falls back to grad_sumsq (mlp_engine._weight_grads)
+                # finalize_blocks); a plan that still needs more falls back to grad_sumsq (chain_net.WeightGrads.finish)
                 entries = max(1 << 15, eng.gradient_elements() // 64 + 8192)
                 self._fin_norm_partials = torch.zeros(entries, dtype=torch.float64, device=self.ppo_device)
             self._fin_norm_ok = ok

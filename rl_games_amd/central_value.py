@@ -28,7 +28,7 @@ from torch import nn
 
 from . import distributed as rdist
 from . import ops
-from .chain_net import ChainNet, RecurrentChainNet, arena_layout
+from .chain_net import ChainNet, RecurrentChainNet, arena_layout, rnn_cell_declined
 from .flat_optim import FlatAdam
 from .lr_control import IdentityScheduler, LinearScheduler
 from .minibatch import PPODataset
@@ -56,10 +56,7 @@ def _recurrent_critic_declined(net, config, value_size):
         return 'one linear value column only'
     if not getattr(net, 'plain_trunk_rnn_ln', False):
         return 'plain Linear + activation trunks only'
-    supported = {'lstm': ops.lstm_supported, 'gru': ops.gru_supported}.get(net.rnn_name)
-    if supported is None or net.rnn_layers != 1 or not supported(net.rnn_units):
-        return 'a single-layer LSTM or GRU with 16/32/64/128 units only'
-    return None
+    return rnn_cell_declined(net.rnn_name, net.rnn_layers, net.rnn_units)
 
 
 class CentralValueTrain(nn.Module):

@@ -7,6 +7,11 @@ the weight gradients - as the launches of the continuous actor's hot path: the i
 as ONE forward launch, the dX / activation-backward / bias-sum chain as ONE backward launch (csrc/mlp_chain*.hip,
 `ops.MlpChain`), every weight gradient as the MFMA launch of csrc/mlp_dw.hip (`ops.MlpDwPlan`).
 
+WeightGrads is the one piece of host code between a backward launch and the optimiser, for the engines of this module and
+for mlp_engine.ManualMLP alike: which (dZ, X, grad) products the MFMA launch takes, its plans per shape, the column
+sums and the loss partials its finalise launch finishes, and the library / narrow-kernel products of what is left.
+plain_trunk, head_span and rnn_cell_declined are the shape checks the engines and the agents share.
+
 Users: the central value network (central_value.py, one value column) and the discrete-action agent (discrete_agent.py:
 [value | logits] behind a shared trunk, or one chain per trunk with `separate: True` as in ppo_cartpole.yaml).  The
 continuous actor has its own engine (mlp_engine.ManualMLP: loss inside the backward launch, LSTM, HIP graphs).
@@ -30,8 +35,10 @@ def arena_layout(params, head_groups, first_vectors=()):
     group of head weights (adjacent, in the given order - one GEMM operand per group), then the vectors, then each
     group's biases.  Matrix sizes of the supported shapes are multiples of 4 floats, so the matrices stay 16-byte
     aligned; the logical (optimiser-state) order is untouched.  head_groups: lists of nn.Linear.
-    first_vectors: vectors to put in front of the others (RecurrentChainNet: the trunk's biases directly behind the last
-    matrix, as mlp_engine.ManualMLP.layout places them and explains)."""
+    first_vectors: vectors to put in front of the others - the trunk's biases directly behind the last matrix
+    (RecurrentChainNet, mlp_engine.ManualMLP.layout): the pipelined forward kernels read up to 48 bytes past a matrix
+    whose width is no multiple of 16 and accept that only when the bytes belong to another array of the SAME network
+    (csrc/mlp_chain.hip, chain_pipe_fill) - sigma and the like come after them."""
     head_w = [m.weight for g in head_groups for m in g]
     head_b = [m.bias for g in head_groups for m in g]
     skip = {id(p) for p in head_w + head_b}
@@ -41,35 +48,136 @@ def arena_layout(params, head_groups, first_vectors=()):
     return [p for p in rest if p.dim() >= 2] + head_w + vecs + head_b
 
 
+def plain_trunk(trunk, identity_ok=True):
+    """(linears, activation name) of an nn.Sequential of Linear + activation pairs with one activation kind - what an
+    `ops.MlpChain` takes.  identity_ok=False: in front of an RNN, where a linear trunk is not a supported shape."""
+    linears = [m for m in trunk if isinstance(m, nn.Linear)]
+    acts = [m for m in trunk if not isinstance(m, nn.Linear)]
+    if not linears or len(acts) != len(linears):
+        raise NotImplementedError('unexpected MLP structure')
+    name = _ACT_NAMES.get(type(acts[0]))
+    if name is None or (name == 'None' and not identity_ok) or any(type(a) is not type(acts[0]) for a in acts):
+        raise NotImplementedError('elu / relu / tanh / identity trunks only' if identity_ok else
+                                  'elu / relu / tanh trunks only')
+    if isinstance(acts[0], nn.ELU) and acts[0].alpha != 1.0:
+        raise NotImplementedError('elu alpha != 1')
+    if any(l.out_features % 4 for l in linears):
+        raise NotImplementedError('hidden widths must be multiples of 4')
+    return linears, name
+
+
+def head_span(heads, arena):
+    """(w [columns, K], w_grad, b [columns], b_grad, columns) of nn.Linear heads over the same K features whose weights
+    (and biases) are adjacent in `arena`, in that order: their columns side by side, one GEMM operand."""
+    columns = sum(h.out_features for h in heads)
+    if len(heads) == 1:
+        h = heads[0]
+        return h.weight, h.weight.grad, h.bias, h.bias.grad, columns
+    K = heads[0].in_features
+    wp, wg = arena.span_of([h.weight for h in heads])
+    bp, bg = arena.span_of([h.bias for h in heads])
+    return wp.view(columns, K), wg.view(columns, K), bp, bg, columns
+
+
+RNN_CELLS = 'a single-layer LSTM or GRU with 16/32/64/128 units'
+
+
+def rnn_cell_declined(name, layers, units):
+    """Why the sequence-persistent kernels do not take a recurrent cell ('lstm' / 'gru', layers, units), or None."""
+    supported = {'lstm': ops.lstm_supported, 'gru': ops.gru_supported}.get(name)
+    if supported is None or layers != 1 or not supported(units):
+        return RNN_CELLS + ' only'
+    return None
+
+
+class WeightGrads:
+    """The weight gradients of one backward pass, from the (dZ, X, grad) products the engine lists to finished
+    gradients in the arena.  Everything inside the envelope of the MFMA launch (csrc/mlp_dw.hip: input columns a
+    multiple of 4, contiguous 16-byte aligned operands, at most _DW_MAX_ITEMS matrices) is ONE `ops.MlpDwPlan` launch,
+    the heaviest matrix's blocks first; its finalise launch also finishes up to _DW_MAX_ITEMS bias column sums and the
+    PPO loss partials.  What is left - a first layer over 9 state features, say - is a library product each, or with
+    `narrow` the narrow kernel of csrc/mlp_narrow.hip where it applies (the two give different bits).
+    mfma=False: no MFMA launch at all.  Plans (and the shapes the launch declined) are kept per shape key."""
+
+    def __init__(self, mfma=True, narrow=False):
+        self.mfma, self.narrow = bool(mfma), bool(narrow)
+        self._plans = {}
+        self.last_dw_path = None            # 'mfma' / 'library': whether the last finish() had an MFMA launch
+        self.last_dw_jobs = None            # (jobs, plan, maxima) of the last MFMA launch: bench.py times it after the run
+        self.last_dw_library_jobs = None    # torch.mm products of the last finish()
+
+    def _plan(self, fast, rows):
+        shapes = [tuple(j[2].shape) for j in fast]
+        key = (rows,) + tuple(shapes)
+        plan = self._plans.get(key)
+        if plan is None:
+            try:
+                plan = ops.MlpDwPlan(shapes, rows, fast[0][2].device)
+            except NotImplementedError:
+                plan = False
+            self._plans[key] = plan
+        return plan
+
+    def finish(self, jobs, rows, colsums=(), loss_finalize=None, norm=None, maxima=None):
+        """jobs: (dZ [rows, No], X [rows, Mi], grad [No, Mi][, layer index]); colsums: (partials, blocks, cols, gradient
+        vector).  loss_finalize: ops.loss_finalize_desc(...) - folded into the finalise launch when there is one,
+        launched on its own otherwise.  norm = (partials, grad_scale, step_counter): see ops.MlpDwPlan.launch; returns
+        the number of valid norm partials, or None when the gradient norm was not produced (a gradient of this step did
+        not come out of that launch, or the partials are too few for its finalise grid: the caller's grad_sumsq launch
+        takes over instead of an error in the middle of an epoch).  maxima = (ops.MlpChain.gradient_maxima() of the
+        step, rows per entry) or None: the launch runs its fp16 form when every job in it carries the layer index that
+        names dZ's row of the maxima, else its bf16 form."""
+        fast = [j for j in jobs if self.mfma and j[2].shape[1] % 4 == 0 and j[2].shape[1] >= 4
+                and all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in j[:3])]
+        fast.sort(key=lambda j: -j[2].numel())
+        plan = self._plan(fast, rows) if 0 < len(fast) <= _DW_MAX_ITEMS else None
+        if not plan:
+            fast = []
+        slow = [j for j in jobs if not any(j is f for f in fast)]
+        colsums = list(colsums)
+        norm_blocks = None
+        if plan:
+            launched, colsums = colsums[:_DW_MAX_ITEMS], colsums[_DW_MAX_ITEMS:]
+            # the gradient norm as well when every gradient of the step is written by this launch
+            whole = (norm is not None and not slow and not colsums and loss_finalize is not None
+                     and norm[0].numel() >= plan.finalize_blocks(launched, loss_finalize))
+            mx = None
+            if maxima is not None and all(len(j) == 4 for j in fast):
+                # X is split under the forward's fixed scales: normalised observations (layer 0) / hidden activations
+                mx = (maxima[0], [j[3] for j in fast],
+                      [ops.SPLIT_SCALE_OBS_NORM if j[3] == 0 else ops.SPLIT_SCALE_HIDDEN for j in fast], maxima[1])
+            triples = [j[:3] for j in fast]
+            blocks = plan.launch(triples, launched, loss_finalize, norm if whole else None, maxima=mx)
+            norm_blocks = blocks if whole else None
+            loss_finalize = None
+            self.last_dw_jobs = (triples, plan, mx)
+        if loss_finalize is not None:
+            ops.ppo_loss_finalize_from(loss_finalize, jobs[0][2].device)
+        for part, nb, cols, out in colsums:
+            ops.colsum_finalize(part, nb, cols, out)
+        self.last_dw_path = 'mfma' if plan else 'library'
+        self.last_dw_library_jobs = 0
+        for dz, x, g in (j[:3] for j in slow):
+            if (self.narrow and g.shape[1] <= ops.NARROW_MAX and g.shape[0] <= 256 and dz.stride(1) == 1
+                    and x.stride(1) == 1 and g.is_contiguous()):
+                ops.narrow_dw(dz, x, g)            # a first layer over a few observations (obs 3)
+            else:
+                torch.mm(dz.t(), x, out=g)
+                self.last_dw_library_jobs += 1
+        return norm_blocks
+
+
 class ChainNet:
     """trunk: nn.Sequential of Linear + activation pairs; heads: list of nn.Linear over the trunk's output whose
     weights (and biases) are adjacent in `arena`, in that order (arena_layout) - their columns side by side are the
     chain's last layer.  Raises NotImplementedError for networks outside the kernels' envelope."""
 
     def __init__(self, trunk, heads, arena, max_rows, infer_rows=0):
-        self.linears = [m for m in trunk if isinstance(m, nn.Linear)]
-        acts = [m for m in trunk if not isinstance(m, nn.Linear)]
-        if not self.linears or len(acts) != len(self.linears):
-            raise NotImplementedError('unexpected MLP structure')
-        name = _ACT_NAMES.get(type(acts[0]))
-        if name is None or any(type(a) is not type(acts[0]) for a in acts):
-            raise NotImplementedError('elu / relu / tanh / identity trunks only')
-        if isinstance(acts[0], nn.ELU) and acts[0].alpha != 1.0:
-            raise NotImplementedError('elu alpha != 1')
-        if any(l.out_features % 4 for l in self.linears):
-            raise NotImplementedError('hidden widths must be multiples of 4')
+        self.linears, name = plain_trunk(trunk)
         heads = list(heads)
-        K = self.linears[-1].out_features
-        if any(h.in_features != K for h in heads):
+        if any(h.in_features != self.linears[-1].out_features for h in heads):
             raise NotImplementedError('heads must read the last hidden layer')
-        self.head_cols = sum(h.out_features for h in heads)
-        if len(heads) == 1:
-            h = heads[0]
-            self.head_w, self.head_w_grad, self.head_b, self.head_b_grad = h.weight, h.weight.grad, h.bias, h.bias.grad
-        else:
-            wp, wg = arena.span_of([h.weight for h in heads])
-            self.head_b, self.head_b_grad = arena.span_of([h.bias for h in heads])
-            self.head_w, self.head_w_grad = wp.view(self.head_cols, K), wg.view(self.head_cols, K)
+        self.head_w, self.head_w_grad, self.head_b, self.head_b_grad, self.head_cols = head_span(heads, arena)
         dev = self.head_w.device
         widths = [l.out_features for l in self.linears]
         layers = [(l.weight, l.bias, name) for l in self.linears] + [(self.head_w, self.head_b, 'None')]
@@ -82,10 +190,13 @@ class ChainNet:
         self.infer_heads = torch.empty(infer_rows, self.head_cols, device=dev)
         nb = (max_rows + 15) // 16                          # one partial row per 16-row group at most
         self.partials = [torch.empty(nb * w, dtype=torch.float64, device=dev) for w in widths]
-        self._plans = {}
+        self.weight_grads = WeightGrads()
         self._rows = 0
         self._x = None
-        self.last_dw_path = None
+
+    @property
+    def last_dw_path(self):
+        return self.weight_grads.last_dw_path
 
     @torch.no_grad()
     def forward(self, x, rms, eps):
@@ -137,27 +248,7 @@ class ChainNet:
             lin = self.linears[l]
             jobs.append((dzs[l], acts[l - 1] if l > 0 else self._x, lin.weight.grad))
             colsums.append((parts[l], nblk, lin.out_features, lin.bias.grad))
-        fast = [j for j in jobs if j[2].shape[1] % 4 == 0 and all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in j)]
-        slow = [j for j in jobs if not any(j is f for f in fast)]
-        plan = None
-        if fast:
-            key = (rows,) + tuple(tuple(g.shape) for _, _, g in fast)
-            plan = self._plans.get(key)
-            if plan is None:
-                try:
-                    plan = ops.MlpDwPlan([tuple(g.shape) for _, _, g in fast], rows, fast[0][2].device)
-                except NotImplementedError:
-                    plan = False
-                self._plans[key] = plan
-        if plan:
-            plan.launch(fast, colsums)                      # (bias gradients finished by the same finalise launch)
-        else:
-            slow = jobs
-            for part, nb, cols, out in colsums:
-                ops.colsum_finalize(part, nb, cols, out)
-        self.last_dw_path = 'mfma' if plan else 'library'
-        for dz, x, g in slow:                               # e.g. a first layer over 9 state features: not a multiple of 4
-            torch.mm(dz.t(), x, out=g)
+        self.weight_grads.finish(jobs, rows, colsums)
 
 
 class RecurrentChainNet:
@@ -178,26 +269,15 @@ class RecurrentChainNet:
     Raises NotImplementedError for networks outside the kernels' envelope - there is no per-layer fallback."""
 
     def __init__(self, trunk, rnn, layer_norm, heads, arena, max_rows, infer_rows=0, value_tail=False):
-        self.linears = [m for m in trunk if isinstance(m, nn.Linear)]
-        acts = [m for m in trunk if not isinstance(m, nn.Linear)]
-        if not self.linears or len(acts) != len(self.linears):
-            raise NotImplementedError('unexpected MLP structure')
-        name = _ACT_NAMES.get(type(acts[0]))
-        if name in (None, 'None') or any(type(a) is not type(acts[0]) for a in acts):
-            raise NotImplementedError('elu / relu / tanh trunks only')
-        if isinstance(acts[0], nn.ELU) and acts[0].alpha != 1.0:
-            raise NotImplementedError('elu alpha != 1')
-        if any(l.out_features % 4 for l in self.linears):
-            raise NotImplementedError('hidden widths must be multiples of 4')
+        self.linears, name = plain_trunk(trunk, identity_ok=False)
         self.lstm = rnn if isinstance(rnn, nn.LSTM) else None
         self.gru = rnn if isinstance(rnn, nn.GRU) else None
         if self.lstm is None and self.gru is None:
             raise NotImplementedError('LSTM or GRU only')
         H = rnn.hidden_size
-        supported = ops.lstm_supported if self.lstm is not None else ops.gru_supported
-        if (rnn.num_layers != 1 or rnn.bidirectional or not rnn.bias or getattr(rnn, 'proj_size', 0)
-                or not supported(H) or rnn.input_size != self.linears[-1].out_features):
-            raise NotImplementedError('a single-layer LSTM or GRU with 16/32/64/128 units behind the trunk only')
+        if (rnn_cell_declined('lstm' if self.lstm is not None else 'gru', rnn.num_layers, H) or rnn.bidirectional
+                or not rnn.bias or getattr(rnn, 'proj_size', 0) or rnn.input_size != self.linears[-1].out_features):
+            raise NotImplementedError(RNN_CELLS + ' behind the trunk only')
         if layer_norm is not None and (tuple(layer_norm.normalized_shape) != (H,) or layer_norm.weight is None
                                        or layer_norm.bias is None):
             raise NotImplementedError('layer norm over the recurrent features with weight and bias only')
@@ -206,14 +286,8 @@ class RecurrentChainNet:
         heads = list(heads)
         if any(h.in_features != H for h in heads):
             raise NotImplementedError('heads must read the recurrent features')
-        self.head_cols = C = sum(h.out_features for h in heads)
-        if len(heads) == 1:
-            h = heads[0]
-            self.head_w, self.head_w_grad, self.head_b, self.head_b_grad = h.weight, h.weight.grad, h.bias, h.bias.grad
-        else:
-            wp, wg = arena.span_of([h.weight for h in heads])
-            self.head_b, self.head_b_grad = arena.span_of([h.bias for h in heads])
-            self.head_w, self.head_w_grad = wp.view(C, H), wg.view(C, H)
+        self.head_w, self.head_w_grad, self.head_b, self.head_b_grad, self.head_cols = head_span(heads, arena)
+        C = self.head_cols
         dev = self.head_w.device
         # the bias of the gate-input product.  LSTM: b_ih + b_hh, summed into bias_sum by every forward.  GRU: b_hn is
         # multiplied by r inside the cell, so only b_ih belongs to the input side; the kernel adds b_hh.
@@ -262,11 +336,14 @@ class RecurrentChainNet:
         nstates = 2 if self.lstm is not None else 1
         self._state_buf = [[torch.empty(1, rows, H, device=dev) for _ in range(nstates)] for _ in range(2)]
         self.last_states = None
-        self._plans = {}
+        self.weight_grads = WeightGrads()
         self._rows = 0
         self._x = self._c0 = self._dones = None
         self._T = 1
-        self.last_dw_path = None
+
+    @property
+    def last_dw_path(self):
+        return self.weight_grads.last_dw_path
 
     @torch.no_grad()
     def forward(self, x_raw, rms, eps, rnn_states, dones, seq_length, keep, value_loss=None):
@@ -442,32 +519,8 @@ class RecurrentChainNet:
             lin = self.linears[l]
             jobs.append((dzs[l], acts[l - 1] if l > 0 else self._x, lin.weight.grad))
             colsums.append((parts[l], nblk, lin.out_features, lin.bias.grad))
-        fast = [j for j in jobs if j[2].shape[1] % 4 == 0 and all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in j)]
-        slow = [j for j in jobs if not any(j is f for f in fast)]
-        plan = None
-        if len(fast) > _DW_MAX_ITEMS:
-            fast, slow = [], jobs
-        if fast:
-            fast.sort(key=lambda j: -j[2].numel())          # heaviest matrix's blocks first in the launch
-            key = (rows,) + tuple(tuple(g.shape) for _, _, g in fast)
-            plan = self._plans.get(key)
-            if plan is None:
-                try:
-                    plan = ops.MlpDwPlan([tuple(g.shape) for _, _, g in fast], rows, fast[0][2].device)
-                except NotImplementedError:
-                    plan = False
-                self._plans[key] = plan
-        if plan:
-            # (bias / layer-norm gradients finished by the same finalise launch, as many as it takes)
-            plan.launch(fast, colsums[:_DW_MAX_ITEMS])
-            colsums = colsums[_DW_MAX_ITEMS:]
-        else:
-            slow = jobs
-        for part, nb, cols, out in colsums:
-            ops.colsum_finalize(part, nb, cols, out)
-        self.last_dw_path = 'mfma' if plan else 'library'
-        for dz, x, g in slow:                               # e.g. a first layer over 9 observations: not a multiple of 4
-            torch.mm(dz.t(), x, out=g)
+        # (bias / layer-norm gradients finished by the same finalise launch, as many as it takes)
+        self.weight_grads.finish(jobs, rows, colsums)
 
 
 def paired_launch_pays(cell, hidden, direction, num_seqs, seq_len):

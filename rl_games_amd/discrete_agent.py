@@ -29,7 +29,7 @@ from torch import nn
 
 from . import ops
 from .agent import A2CAgent, _ChainForms
-from .chain_net import ChainNet, RecurrentChainNet, arena_layout
+from .chain_net import ChainNet, RecurrentChainNet, arena_layout, rnn_cell_declined
 
 
 class DiscreteA2CAgent(A2CAgent):
@@ -76,10 +76,7 @@ class DiscreteA2CAgent(A2CAgent):
             return 'manual_lstm is off'
         if not getattr(net, 'plain_trunk_rnn_ln', False) or net.is_separate_critic():
             return 'plain Linear + activation trunks only'
-        supported = {'lstm': ops.lstm_supported, 'gru': ops.gru_supported}.get(net.rnn_name)
-        if supported is None or net.rnn_layers != 1 or not supported(net.rnn_units):
-            return 'a single-layer LSTM or GRU with 16/32/64/128 units only'
-        return None
+        return rnn_cell_declined(net.rnn_name, net.rnn_layers, net.rnn_units)
 
     def _arena_layout(self, config):
         if not config.get('fused_mlp', True):

@@ -72,11 +72,6 @@ class FlatArena:
         calls weights_changed() behind both of its broadcasts)."""
         return (self.weights_version, self.flat_params._version, sum(p._version for p in self.params))
 
-    def span(self, first, last):
-        """(params view, grads view) of the contiguous arena range covering parameters `first`
-        .. `last` (which must be physically adjacent, in that order)."""
-        return self.span_of([first, last])
-
     def span_of(self, params):
         """(params view, grads view) of the contiguous arena range covering `params`, which must follow one another
         physically in that order."""

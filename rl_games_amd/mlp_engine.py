@@ -24,11 +24,15 @@ Numerics: aten's formulas - by default (in-place activations) act' from the laye
 elu_backward(is_result=True): h > 0 ? 1 : h + 1; with `inplace_act=False` from the pre-activation
 (exp(z)); GEMM
 results are the library's, as before.  Parameters keep their reference names and shapes.
+backward() ends in chain_net.WeightGrads.finish - the one finisher of weight gradients, bias column sums and loss
+partials that the chain engines use as well - here with the narrow kernel for left-over products and, on the fused
+chain, the gradient norm and the fp16 form of the MFMA launch.
 """
 import torch
 from torch import nn
 
 from . import ops
+from .chain_net import RNN_CELLS, WeightGrads, arena_layout, head_span, plain_trunk, rnn_cell_declined
 
 
 class ManualMLP:
@@ -41,37 +45,22 @@ class ManualMLP:
         (Measured and rejected: forking the library dW GEMMs onto a second stream - multi-branch
         hipGraphs cost more in cross-branch dependencies than the overlap gains.)"""
         self.net = net
-        self.mfma_dw = mfma_dw
-        self._dw_plans = {}
-        self.last_dw_path = None
-        self.last_dw_jobs = None
+        # a left-over product over a few observations (config #5: obs 3) on the narrow kernel, not the library
+        self.weight_grads = WeightGrads(mfma=mfma_dw, narrow=True)
         self._x_normalised = False
         self.arena = arena
-        self.linears = [m for m in net.actor_mlp if isinstance(m, nn.Linear)]
-        acts = [m for m in net.actor_mlp if not isinstance(m, nn.Linear)]
-        if len(acts) != len(self.linears):
-            raise NotImplementedError('unexpected MLP structure')
-        name = {nn.ELU: 'elu', nn.ReLU: 'relu', nn.Tanh: 'tanh', nn.Identity: 'None'}.get(type(acts[0]))
-        if name is None or any(type(a) is not type(acts[0]) for a in acts):
-            raise NotImplementedError('manual MLP engine supports elu / relu / tanh / identity trunks')
-        if isinstance(acts[0], nn.ELU) and acts[0].alpha != 1.0:
-            raise NotImplementedError('elu alpha != 1')
-        self.act_name = name
-        self.act_kind = ops.ACT_KINDS[name]
-        self.act_module = acts[0]
+        self.linears, self.act_name = plain_trunk(net.actor_mlp)
+        self.act_kind = ops.ACT_KINDS[self.act_name]
         if not isinstance(net.value_act, nn.Identity) or not isinstance(net.mu_act, nn.Identity):
             raise NotImplementedError('head activations are not supported by the manual MLP engine')
-        if any(l.out_features % 4 for l in self.linears):
-            raise NotImplementedError('hidden widths must be multiples of 4')
         self.A = net.mu.out_features
         self.V = net.value.out_features
         K = net.mu.in_features
         self.lstm = self.gru = None      # the recurrent cell's torch module (parameters only), by kind
         self.rnn = None                  # ... whichever of the two it is
         if getattr(net, 'has_rnn', False):
-            supported = {'lstm': ops.lstm_supported, 'gru': ops.gru_supported}.get(net.rnn_name)
-            if supported is None or net.rnn_layers != 1 or not supported(net.rnn_units):
-                raise NotImplementedError('manual engine: only a single-layer LSTM or GRU with 16/32/64/128 units')
+            if rnn_cell_declined(net.rnn_name, net.rnn_layers, net.rnn_units):
+                raise NotImplementedError(f'manual engine: only {RNN_CELLS}')
             self.rnn = net.rnn.rnn
             if net.rnn_name == 'lstm':
                 self.lstm = self.rnn
@@ -79,13 +68,10 @@ class ManualMLP:
                 self.gru = self.rnn
             self.Hr = net.rnn_units
             self.Gr = (4 if self.lstm is not None else 3) * self.Hr      # gate columns
-        wp, wg = arena.span(net.value.weight, net.mu.weight)
-        bp, bg = arena.span(net.value.bias, net.mu.bias)
-        self.head_w, self.head_w_grad = wp.view(self.V + self.A, K), wg.view(self.V + self.A, K)
-        self.head_b, self.head_b_grad = bp, bg
+        self.head_w, self.head_w_grad, self.head_b, self.head_b_grad, _ = head_span([net.value, net.mu], arena)
         self._head_mfma = (mfma_dw and self.V + self.A <= 64 and ops.mlp_rowgemm_supported(K, K)
                            and self.head_w.data_ptr() % 16 == 0)
-        dev = wp.device
+        dev = self.head_w.device
         self.max_rows = max_rows
         widths = [l.out_features for l in self.linears]
         # inplace_act: the activation overwrites the pre-activation (one [rows, width] buffer per
@@ -158,25 +144,21 @@ class ManualMLP:
             self._state_flip = 0
             self.last_states = None
 
+    # what the last backward()'s weight gradients ran on (bench.py and the tests read these)
+    last_dw_path = property(lambda self: self.weight_grads.last_dw_path)
+    last_dw_jobs = property(lambda self: self.weight_grads.last_dw_jobs)
+    last_dw_library_jobs = property(lambda self: self.weight_grads.last_dw_library_jobs)
+
     @staticmethod
     def layout(net):
         """Physical arena order: every weight MATRIX first (parameters() order, the value and mu
         head weights last and adjacent), then the vectors (biases, sigma; value and mu head biases
         last and adjacent).  Matrix sizes are multiples of 4 floats for every supported shape, so
         all weight / weight-gradient views stay 16-byte aligned (vector loads/stores of the MFMA
-        kernels); the logical (optimizer-state) order is untouched."""
-        head_w = [net.value.weight, net.mu.weight]
-        head_b = [net.value.bias, net.mu.bias]
-        skip = {id(p) for p in head_w + head_b}
-        rest = [p for p in net.parameters() if id(p) not in skip]
-        mats = [p for p in rest if p.dim() >= 2]
-        vecs = [p for p in rest if p.dim() < 2]
-        # the layers' bias vectors directly behind the last matrix: the pipelined forward kernels read up to 48 bytes
-        # past a matrix whose width is no multiple of 16 and accept that only when the bytes belong to another array
-        # of the SAME network (csrc/mlp_chain.hip, chain_pipe_fill) - sigma and the like come after them
-        linear_biases = {id(m.bias) for m in net.modules() if isinstance(m, torch.nn.Linear) and m.bias is not None}
-        vecs.sort(key=lambda p: id(p) not in linear_biases)
-        return mats + head_w + vecs + head_b
+        kernels); the logical (optimizer-state) order is untouched.  The layers' bias vectors come directly behind
+        the last matrix (chain_net.arena_layout explains)."""
+        linear_biases = [m.bias for m in net.modules() if isinstance(m, nn.Linear) and m.bias is not None]
+        return arena_layout(list(net.parameters()), [[net.value, net.mu]], first_vectors=linear_biases)
 
     # ------------------------------------------------------------------
     @torch.no_grad()
@@ -356,7 +338,9 @@ class ManualMLP:
             # the fp16 form of the weight-gradient launch splits X under the forward's FIXED scales: hidden activations, and
             # observations that went through the normaliser's clamp (raw observations have no bound: the bf16 form then)
             maxima = self.chain.gradient_maxima(rows) if self._x_normalised else None
-            return self._weight_grads(jobs, rows, colsums, loss_finalize, norm, maxima=maxima)
+            if maxima is not None:
+                maxima = (maxima, self.chain.maxima_rows_per_entry)
+            return self.weight_grads.finish(jobs, rows, colsums, loss_finalize, norm, maxima=maxima)
         jobs = [(d_heads, self._last, self.head_w_grad)]           # (dZ, X, grad) per weight matrix
         colsums = []                                               # (partials, blocks, cols, bias.grad)
         if self.rnn is not None:
@@ -402,7 +386,7 @@ class ManualMLP:
                     lin = self.linears[l]
                     jobs.append((dzs[l], acts[l - 1] if l > 0 else self._x, lin.weight.grad))
                     colsums.append((parts[l], nblk, lin.out_features, lin.bias.grad))
-                return self._weight_grads(jobs, rows, colsums, loss_finalize)
+                return self.weight_grads.finish(jobs, rows, colsums, loss_finalize)
             d = self.dA[L - 1][:rows]
             torch.mm(dg, rnn.weight_ih_l0, out=d)
         else:
@@ -421,66 +405,4 @@ class ManualMLP:
                 d_prev = self.dA[l - 1][:rows]
                 torch.mm(d, lin.weight, out=d_prev)
                 d = d_prev
-        return self._weight_grads(jobs, rows, colsums, loss_finalize)
-
-    def _weight_grads(self, jobs, rows, colsums=(), loss_finalize=None, norm=None, maxima=None):
-        """jobs: (dZ [rows, No], X [rows, Mi], grad [No, Mi][, layer index]).  maxima: ops.MlpChain.gradient_maxima() of the
-        step, or None (then, or when a job carries no layer index, the launch runs its bf16 form).  Everything inside the MFMA kernel's
-        envelope (Mi % 4 == 0, 16-byte aligned contiguous operands) goes into one launch; the rest
-        (e.g. a first layer over 3 observations) uses the library GEMM."""
-        fast, slow = [], []
-        norm_blocks = None
-        if self.mfma_dw:
-            for job in jobs:
-                g = job[2]
-                ok = (g.shape[1] % 4 == 0 and g.shape[1] >= 4
-                      and all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in job[:3]))
-                (fast if ok else slow).append(job)
-        else:
-            slow = list(jobs)
-        if fast:
-            fast.sort(key=lambda job: -job[2].numel())          # heaviest layer's blocks first in the launch
-            key = (rows,) + tuple(tuple(j[2].shape) for j in fast)
-            plan = self._dw_plans.get(key)
-            if plan is None:
-                try:
-                    plan = ops.MlpDwPlan([tuple(j[2].shape) for j in fast], rows, fast[0][2].device)
-                except NotImplementedError:
-                    plan = False
-                self._dw_plans[key] = plan
-            if plan:
-                # bias gradients (and the loss partials) finished in the same finalise launch; the gradient
-                # norm as well when every gradient of the step is written there
-                # (a norm buffer that is too small for this plan's finalise grid: the caller's grad_sumsq
-                #  launch takes over instead of an error in the middle of an epoch)
-                whole = (norm is not None and not slow and loss_finalize is not None
-                         and norm[0].numel() >= plan.finalize_blocks(colsums, loss_finalize))
-                mx = None
-                if maxima is not None and all(len(j) == 4 for j in fast):
-                    mx = (maxima, [j[3] for j in fast],
-                          [ops.SPLIT_SCALE_OBS_NORM if j[3] == 0 else ops.SPLIT_SCALE_HIDDEN for j in fast],
-                          self.chain.maxima_rows_per_entry)
-                triples = [j[:3] for j in fast]
-                norm_blocks = plan.launch(triples, colsums, loss_finalize, norm if whole else None, maxima=mx)
-                if not whole:
-                    norm_blocks = None
-                colsums = ()
-                loss_finalize = None
-                self.last_dw_jobs = (triples, plan, mx)        # bench.py times this launch after the run
-            else:
-                slow = slow + fast
-                fast = []
-        if loss_finalize is not None:
-            ops.ppo_loss_finalize_from(loss_finalize, jobs[0][2].device)
-        for part, nb, cols, out in colsums:
-            ops.colsum_finalize(part, nb, cols, out)
-        self.last_dw_path = 'mfma' if fast else 'library'
-        self.last_dw_library_jobs = 0
-        for dz, x, g in (j[:3] for j in slow):
-            if (g.shape[1] <= ops.NARROW_MAX and g.shape[0] <= 256 and dz.stride(1) == 1 and x.stride(1) == 1
-                    and g.is_contiguous()):
-                ops.narrow_dw(dz, x, g)            # a first layer over a few observations (config #5: obs 3)
-            else:
-                torch.mm(dz.t(), x, out=g)
-                self.last_dw_library_jobs += 1
-        return norm_blocks
+        return self.weight_grads.finish(jobs, rows, colsums, loss_finalize)

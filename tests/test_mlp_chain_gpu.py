@@ -1208,3 +1208,35 @@ def test_split_fp16_range_limits_end_in_non_finite_values_never_in_wrong_ones():
     heavy[1][0][3, 7] = 2000.0
     acts, heads = run(heavy, x, True)
     assert not torch.isfinite(acts[1][:, 3]).any()
+
+
+def test_chain_net_weight_gradients_do_not_depend_on_the_launch_order():
+    """chain_net.WeightGrads launches the matrices heaviest first; ChainNet lists them head, last hidden layer, ...,
+    first.  Every matrix has its own plan and split-K workspace and the launch has no atomics, so the gradients are the
+    bits of a direct launch in ChainNet's own order.  96 rows (no multiple of the 64-row tile), heads of 1 + 3 columns:
+    the head matrix [4 x 32] is the lightest and comes first in ChainNet's list, [32 x 64] is the heaviest."""
+    from rl_games_amd import ops
+    from rl_games_amd.chain_net import ChainNet, arena_layout
+    from rl_games_amd.flat_optim import FlatArena
+    rows = 96
+    torch.manual_seed(41)
+    trunk = torch.nn.Sequential(torch.nn.Linear(12, 64), torch.nn.ELU(), torch.nn.Linear(64, 32), torch.nn.ELU()).to(DEV)
+    heads = [torch.nn.Linear(32, 1).to(DEV), torch.nn.Linear(32, 3).to(DEV)]
+    params = list(trunk.parameters()) + [p for h in heads for p in h.parameters()]
+    arena = FlatArena(params, layout=arena_layout(params, [heads]))
+    net = ChainNet(trunk, heads, arena, rows)
+    x = torch.randn(rows, 12, device=DEV)
+    net.forward(x, None, 1e-5)
+    net.d_heads[:rows] = torch.randn(rows, 4, device=DEV)
+    net.backward()
+    assert net.last_dw_path == 'mfma' and net.weight_grads.last_dw_library_jobs == 0
+    grads = [net.head_w_grad, trunk[2].weight.grad, trunk[0].weight.grad]
+    launched = [j[2] for j in net.weight_grads.last_dw_jobs[0]]
+    assert [g.data_ptr() for g in launched] == [grads[k].data_ptr() for k in (1, 2, 0)]       # heaviest first
+    jobs = [(net.d_heads[:rows], net.Hs[1][:rows], torch.full((4, 32), float('nan'), device=DEV)),
+            (net.dA[1][:rows], net.Hs[0][:rows], torch.full((32, 64), float('nan'), device=DEV)),
+            (net.dA[0][:rows], x, torch.full((64, 12), float('nan'), device=DEV))]
+    ops.MlpDwPlan([tuple(j[2].shape) for j in jobs], rows, DEV).launch(jobs)
+    for (dz, xin, direct), got in zip(jobs, grads):
+        assert torch.equal(got, direct), tuple(got.shape)
+        _close(got, dz.double().t() @ xin.double(), dz.t() @ xin)
