@@ -40,7 +40,7 @@ from .flat_optim import FlatAdam
 from .gae import compute_gae, gae_returns_advantages
 from .lr_control import AdaptiveScheduler, IdentityScheduler, LinearScheduler
 from .minibatch import PPODataset
-from .normalizers import GeneralizedMovingStats
+from .normalizers import GeneralizedMovingStats, launch_stats
 from .policy import PolicyBuilder
 from .rollout_buffer import ExperienceBuffer
 
@@ -966,10 +966,7 @@ class A2CAgent:
         cv = self.central_value_net
         if states.stride(-1) != 1:
             states = states.contiguous()
-        rms, eps = None, 1e-5
-        if cv.normalize_input:
-            m = cv.model.running_mean_std
-            rms, eps = (m.running_mean, m.running_var), m.epsilon
+        rms, eps = launch_stats(cv.model.running_mean_std if cv.normalize_input else None)
         if cv._rnn_engine is not None:
             return cv._rnn_engine.forward(states, rms, eps, cv.rnn_states if cv_rnn_states is None else cv_rnn_states,
                                           None, 1, keep=False)
@@ -1402,10 +1399,7 @@ class A2CAgent:
         else:
             mu, logstd, values, _ = self.model.forward_heads(batch)
         mb, A = mu.shape
-        mask = mask_sum = None
-        if rnn_masks is not None:
-            mask = rnn_masks.reshape(-1).float().contiguous()
-            mask_sum = mask.sum().reshape(1)
+        mask, mask_sum = ops.sequence_mask(rnn_masks)
         coef_b = self.bounds_loss_coef if self.bounds_loss_coef is not None else 0.0
         kind = 0 if self.bounds_loss_coef is None else ops.BOUND_KINDS.get(self.bound_loss_type, 0)
         if eng is not None:
@@ -1469,16 +1463,12 @@ class A2CAgent:
         if not obs_batch.is_contiguous():
             obs_batch = obs_batch.contiguous()
         opt.zero_grad()
-        if self.normalize_input and self.model.running_mean_std.training:
-            self.model.running_mean_std.update(obs_batch)
-        mu, values = pair.forward(obs_batch, self._obs_rms(), self._obs_eps(), input_dict['rnn_states'],
+        rms, eps = launch_stats(self.model.running_mean_std if self.normalize_input else None, obs_batch)
+        mu, values = pair.forward(obs_batch, rms, eps, input_dict['rnn_states'],
                                   input_dict['dones'] if self.zero_rnn_on_done else None, self.seq_length, keep=True)
         mb, A = mu.shape
         rnn_masks = input_dict.get('rnn_masks', None)
-        mask = mask_sum = None
-        if rnn_masks is not None:
-            mask = rnn_masks.reshape(-1).float().contiguous()
-            mask_sum = mask.sum().reshape(1)
+        mask, mask_sum = ops.sequence_mask(rnn_masks)
         coef_b = self.bounds_loss_coef if self.bounds_loss_coef is not None else 0.0
         kind = 0 if self.bounds_loss_coef is None else ops.BOUND_KINDS.get(self.bound_loss_type, 0)
         coef_c = self.critic_coef if self.has_value_loss else 0.0       # (as _forward_loss_backward)

@@ -32,6 +32,7 @@ from .chain_net import ChainNet, RecurrentChainNet, arena_layout, rnn_cell_decli
 from .flat_optim import FlatAdam
 from .lr_control import IdentityScheduler, LinearScheduler
 from .minibatch import PPODataset
+from .normalizers import launch_stats
 
 
 def _value_chain(net, arena, max_rows):
@@ -279,21 +280,13 @@ class CentralValueTrain(nn.Module):
         opt.zero_grad()
         eng = self._engine
         reng = self._rnn_engine if obs_batch.dtype == torch.float32 else None
-        mask = mask_sum = None
-        if rnn_masks is not None:
-            mask = rnn_masks.reshape(-1).float().contiguous()
-            mask_sum = mask.sum().reshape(1)
+        mask, mask_sum = ops.sequence_mask(rnn_masks)
         row = self._rows[self._row_index % self._rows.shape[0]]
         self._row_index += 1
         if reng is not None:
             # the same normaliser update, then trunk + gate-input product, the sequence kernel, (layer norm,) and the
             # value tail: head, loss, d values, the gradient of the recurrent features and the head's gradient partials
-            rms, eps = None, 1e-5
-            if self.normalize_input:
-                m = self.model.running_mean_std
-                if m.training:
-                    m.update(obs_batch)
-                rms, eps = (m.running_mean, m.running_var), m.epsilon
+            rms, eps = launch_stats(self.model.running_mean_std if self.normalize_input else None, obs_batch)
             mb = obs_batch.shape[0]
             reng.forward(obs_batch, rms, eps, batch['rnn_states'], batch['dones'], self.seq_length, keep=True,
                          value_loss=(batch['old_values'].reshape(-1).contiguous(), batch['returns'].reshape(-1).contiguous(),
@@ -304,12 +297,7 @@ class CentralValueTrain(nn.Module):
             return self._all_reduce_and_step(row)
         if eng is not None:
             # models.py:54-56 (norm_obs: training mode updates the statistics first), then the whole network in one launch
-            rms, eps = None, 1e-5
-            if self.normalize_input:
-                m = self.model.running_mean_std
-                if m.training:
-                    m.update(obs_batch)
-                rms, eps = (m.running_mean, m.running_var), m.epsilon
+            rms, eps = launch_stats(self.model.running_mean_std if self.normalize_input else None, obs_batch)
             values = eng.forward(obs_batch, rms, eps)                       # [mb, 1]
         else:
             rnn = None

@@ -10,13 +10,17 @@ as ONE forward launch, the dX / activation-backward / bias-sum chain as ONE back
 WeightGrads is the one piece of host code between a backward launch and the optimiser, for the engines of this module and
 for mlp_engine.ManualMLP alike: which (dZ, X, grad) products the MFMA launch takes, its plans per shape, the column
 sums and the loss partials its finalise launch finishes, and the library / narrow-kernel products of what is left.
-plain_trunk, head_span and rnn_cell_declined are the shape checks the engines and the agents share.
+plain_trunk, head_span and rnn_cell_declined are the shape checks the engines and the agents share; trunk_views and
+trunk_jobs are the one statement of a trunk's weight-gradient list behind a chain backward.  RnnStations is the one copy
+of what lies between the gate-input product and the recurrent features - the LSTM / GRU cell's buffers, gate bias,
+ping-pong states, the sequence kernels' argument tuples, gate-gradient column sums and weight-gradient jobs - for
+RecurrentChainNet and mlp_engine.ManualMLP alike; each engine keeps its own trunk and head stations around it.
 
 Users: the central value network (central_value.py, one value column) and the discrete-action agent (discrete_agent.py:
 [value | logits] behind a shared trunk, or one chain per trunk with `separate: True` as in ppo_cartpole.yaml).  The
-continuous actor has its own engine (mlp_engine.ManualMLP: loss inside the backward launch, LSTM, HIP graphs).
-RecurrentChainNet is the recurrent counterpart for the discrete agent: the trunk + gate-input product as one chain, then
-the sequence-persistent LSTM / GRU kernels, an optional layer norm and the heads.  RecurrentChainPair drives two of them
+continuous actor's engine is mlp_engine.ManualMLP (loss inside the backward launch, a per-layer trunk mode, HIP graphs).
+RecurrentChainNet is the recurrent engine of the discrete agent and the central value critic: the trunk + gate-input
+product as one chain, then RnnStations, an optional layer norm and the heads.  RecurrentChainPair drives two of them
 - the separate actor / critic trunks of a continuous policy, each with its own RNN - with one paired sequence launch.  The
 agents' rollout graphs read these chains too; they hold no pack launch, so the agent brings each chain's weight fragments
 / planes up to date in front of a replay along with its other chains (A2CAgent._forms_before_replay).
@@ -167,6 +171,149 @@ class WeightGrads:
         return norm_blocks
 
 
+def trunk_views(linears, acts, dzs, partials, rows, nblk):
+    """The first `rows` rows of a trunk's activation and dZ buffers, and the `nblk` partial rows per layer a chain
+    backward over them writes (ops.MlpChain.num_blocks) - what ops.MlpChain.backward and trunk_jobs take."""
+    return ([h[:rows] for h in acts], [d[:rows] for d in dzs],
+            [p[:nblk * l.out_features] for p, l in zip(partials, linears)])
+
+
+def trunk_jobs(linears, x, acts, dzs, parts, nblk):
+    """(jobs, colsums) of a trunk for WeightGrads.finish behind a chain backward, last layer first: (dZ, X, W.grad,
+    layer) with X the layer below's activations - `x` under layer 0 - and (partials, blocks, cols, b.grad).  The layer
+    index names dZ's row of the backward's gradient maxima; finish() reads it only when it is given those."""
+    jobs, colsums = [], []
+    for l in range(len(linears) - 1, -1, -1):
+        lin = linears[l]
+        jobs.append((dzs[l], acts[l - 1] if l > 0 else x, lin.weight.grad, l))
+        colsums.append((parts[l], nblk, lin.out_features, lin.bias.grad))
+    return jobs, colsums
+
+
+class RnnStations:
+    """The stations of a single-layer LSTM / GRU between the gate-input product and the features the heads read, for
+    every engine that has one (RecurrentChainNet, mlp_engine.ManualMLP): the cell's buffers, the bias of the gate-input
+    product, the ping-pong final states, the argument tuples of the sequence-persistent kernels (csrc/lstm*.hip,
+    csrc/gru*.hip) and, behind their backward, the bias column sums and the two weight-gradient jobs.  No trunk, no
+    layer norm, no heads and no loss: the engine writes `gates[:rows]`, reads `rnn_out[:rows]`, and hands
+    `d_rnn_out[:rows]` (or a buffer of its own) to backward_args.
+    rnn: the torch.nn.LSTM / GRU module (parameters only); rows: the most rows of a forward."""
+
+    def __init__(self, rnn, rows, device):
+        self.lstm = rnn if isinstance(rnn, nn.LSTM) else None
+        self.gru = rnn if isinstance(rnn, nn.GRU) else None
+        if self.lstm is None and self.gru is None:
+            raise NotImplementedError('LSTM or GRU only')
+        H = rnn.hidden_size
+        if (rnn_cell_declined('lstm' if self.lstm is not None else 'gru', rnn.num_layers, H) or rnn.bidirectional
+                or not rnn.bias or getattr(rnn, 'proj_size', 0)):
+            raise NotImplementedError(RNN_CELLS + ' only')
+        self.rnn, self.Hr = rnn, H
+        self.Gr = G = (4 if self.lstm is not None else 3) * H        # gate columns
+        # the bias of the gate-input product.  LSTM: b_ih + b_hh, summed into bias_sum by every forward.  GRU: b_hn is
+        # multiplied by r inside the cell, so only b_ih belongs to the input side - bias_ih_l0 itself; the kernel adds
+        # b_hh.
+        if self.lstm is not None:
+            self.gate_bias = self.bias_sum = torch.empty(G, device=device)
+        else:
+            self.gate_bias, self.bias_sum = rnn.bias_ih_l0, None
+
+        def buf(cols):
+            return torch.empty(rows, cols, device=device)
+        self.gates, self.rnn_out, self.d_rnn_out, self.hprev = buf(G), buf(H), buf(H), buf(H)
+        self.gate_partials = torch.empty(ops.act_bwd_blocks(rows, G) * G, dtype=torch.float64, device=device)
+        if self.lstm is not None:
+            self.d_gates, self.c_all = buf(G), buf(H)
+        else:
+            self.hn_all = buf(H)                            # W_hn h + b_hn, before the gating by r
+            self.d_gx, self.d_gh = buf(G), buf(G)           # gradient of the input side / of the hidden side
+            self.gate_partials_h = torch.empty_like(self.gate_partials)
+        # final states of the last keep=False forward (LSTM: h and c, GRU: h), ping-pong so that a caller may feed them
+        # back in
+        nstates = 2 if self.lstm is not None else 1
+        self._state_buf = [[torch.empty(1, rows, H, device=device) for _ in range(nstates)] for _ in range(2)]
+        self.last_states = None
+        self._kept = None
+
+    @torch.no_grad()
+    def forward_args(self, rows, rnn_states, dones, seq_length, keep):
+        """Checks the shapes, sums the LSTM's biases (a launch) and returns the arguments of ops.lstm_seq_forward /
+        gru_seq_forward, without seq_len, for `rows` rows ordered (sequence, t) with `seq_length` steps each.
+        rnn_states = (h0, c0) - GRU: (h0,) - contiguous [1, rows / seq_length, H]; dones [rows] resets the state
+        entering a step (or None).  keep=True has the kernel keep what backward_args reads and leaves the state buffers
+        alone (they hold the live rollout state); keep=False (a rollout step, get_values) keeps nothing and puts the
+        final states into whichever buffer pair the inputs do not live in - `last_states`, None after keep=True."""
+        S = rows // seq_length
+        if S * seq_length != rows:
+            raise ValueError(f'rows ({rows}) must be a multiple of seq_length ({seq_length})')
+        if dones is not None:
+            dones = dones.reshape(-1)
+            if dones.dtype != torch.uint8 or not dones.is_contiguous():
+                dones = dones.to(torch.uint8).contiguous()
+        rnn, H = self.rnn, self.Hr
+        h0 = rnn_states[0][0]
+        c0 = rnn_states[1][0] if self.lstm is not None else None
+        if h0.shape != (S, H) or not h0.is_contiguous() or not (c0 is None or (c0.shape == (S, H) and c0.is_contiguous())):
+            raise ValueError(f'rnn_states must be contiguous [1, {S}, {H}] tensors')
+        if self.lstm is not None:
+            torch.add(rnn.bias_ih_l0, rnn.bias_hh_l0, out=self.bias_sum)
+        if keep:
+            self._kept = (rows, c0, dones, seq_length)
+            self.last_states = None
+            kept = ((self.c_all if self.lstm is not None else self.hn_all)[:rows], self.hprev[:rows])
+            finals = (None,) * len(self._state_buf[0])
+        else:
+            pair = self._state_buf[1 if h0.data_ptr() == self._state_buf[0][0].data_ptr() else 0]
+            self.last_states = tuple(t[:, :S] for t in pair)
+            kept = (None, None)
+            finals = tuple(t[0] for t in self.last_states)
+        gates, out = self.gates[:rows], self.rnn_out[:rows]
+        if self.lstm is not None:
+            return (gates, rnn.weight_hh_l0, h0, c0, dones, out) + kept + finals
+        return (gates, rnn.weight_hh_l0, rnn.bias_hh_l0, h0, dones, out) + kept + finals
+
+    def sequence(self, direction, args, seq_length):
+        """The sequence kernel as a launch of its own: direction 'forward' / 'backward', args from forward_args /
+        backward_args."""
+        cell = 'lstm' if self.lstm is not None else 'gru'
+        getattr(ops, f'{cell}_seq_{direction}')(*args, seq_len=seq_length)
+
+    @property
+    def seq_length(self):
+        """Steps per sequence of the last keep=True forward: the backward kernel's seq_len."""
+        return self._kept[3]
+
+    def backward_args(self, d_out):
+        """The arguments of ops.lstm_seq_backward / gru_seq_backward, without seq_len, from d_out [rows, H] and what
+        the last keep=True forward kept."""
+        rows, c0, dones, _ = self._kept
+        gates, w_hh = self.gates[:rows], self.rnn.weight_hh_l0
+        if self.lstm is not None:
+            return (gates, self.c_all[:rows], c0, dones, w_hh, d_out, self.d_gates[:rows])
+        return (gates, self.hn_all[:rows], self.hprev[:rows], dones, w_hh, d_out, self.d_gx[:rows], self.d_gh[:rows])
+
+    def gate_gradients(self, rnn_in):
+        """Behind the backward sequence kernel: the column sums of the gate gradients (one launch, GRU two).  Returns
+        (dg, jobs, colsums): dg, the gradient of the gate-input product that the trunk's backward starts from; the two
+        weight-gradient jobs, W_hh's and - over rnn_in [rows, input], the trunk's features - W_ih's; the two bias
+        gradients' column-sum jobs."""
+        rows, G, rnn = self._kept[0], self.Gr, self.rnn
+        nbg = ops.act_bwd_blocks(rows, G)
+        gpart = gpart_h = self.gate_partials[:nbg * G]
+        if self.lstm is not None:
+            dg = dgh = self.d_gates[:rows]
+            ops.act_bwd_colsum(dg, None, dg, 0, gpart, nbg)                  # identity: column sums only
+        else:
+            # dg = d_gx: the input side - W_ih, b_ih and the trunk; dgh = d_gh: the hidden side - W_hh, b_hh
+            dg, dgh = self.d_gx[:rows], self.d_gh[:rows]
+            gpart_h = self.gate_partials_h[:nbg * G]
+            ops.act_bwd_colsum(dg, None, dg, 0, gpart, nbg)
+            ops.act_bwd_colsum(dgh, None, dgh, 0, gpart_h, nbg)
+        jobs = [(dgh, self.hprev[:rows], rnn.weight_hh_l0.grad), (dg, rnn_in, rnn.weight_ih_l0.grad)]
+        colsums = [(gpart, nbg, G, rnn.bias_ih_l0.grad), (gpart_h, nbg, G, rnn.bias_hh_l0.grad)]   # LSTM: d b_hh = d b_ih
+        return dg, jobs, colsums
+
+
 class ChainNet:
     """trunk: nn.Sequential of Linear + activation pairs; heads: list of nn.Linear over the trunk's output whose
     weights (and biases) are adjacent in `arena`, in that order (arena_layout) - their columns side by side are the
@@ -230,24 +377,18 @@ class ChainNet:
     @torch.no_grad()
     def backward(self):
         """d loss / d heads in self.d_heads[:rows] -> every gradient of the network in the arena."""
-        rows, L = self._rows, len(self.linears)
+        rows = self._rows
         d_heads = self.d_heads[:rows]
-        acts = [h[:rows] for h in self.Hs]
-        dzs = [d[:rows] for d in self.dA]
         nblk = self.chain.num_blocks(rows, 1)
-        parts = [p[:nblk * l.out_features] for p, l in zip(self.partials, self.linears)]
+        acts, dzs, parts = trunk_views(self.linears, self.Hs, self.dA, self.partials, rows, nblk)
         self.chain.backward(d_heads, acts, dzs, parts)
-        jobs, colsums = [], []
+        jobs, colsums = trunk_jobs(self.linears, self._x, acts, dzs, parts, nblk)
         if self.head_cols == 1:
             # one output column - a weighted column sum of the last activations, and the sum of d heads
             torch.mv(acts[-1].t(), d_heads.view(-1), out=self.head_w_grad.view(-1))
         else:
-            jobs.append((d_heads, acts[-1], self.head_w_grad))
+            jobs.insert(0, (d_heads, acts[-1], self.head_w_grad))
         torch.sum(d_heads, dim=0, out=self.head_b_grad)
-        for l in range(L - 1, -1, -1):
-            lin = self.linears[l]
-            jobs.append((dzs[l], acts[l - 1] if l > 0 else self._x, lin.weight.grad))
-            colsums.append((parts[l], nblk, lin.out_features, lin.bias.grad))
         self.weight_grads.finish(jobs, rows, colsums)
 
 
@@ -255,11 +396,12 @@ class RecurrentChainNet:
     """One trunk of a recurrent policy without autograd:
         obs -> [Linear + act] x L -> W_ih x + b -> LSTM | GRU (one layer, 16 / 32 / 64 / 128 units)
             -> optional nn.LayerNorm(units) -> heads
-    the RNN branch of mlp_engine.ManualMLP restated for arbitrary head columns (`heads`: nn.Linear modules over the
-    recurrent features, adjacent in `arena` as for ChainNet).  The normaliser, the trunk and the gate-input product are
-    one `ops.MlpChain` launch whose last (linear) layer is W_ih; the sequence-persistent kernels of csrc/lstm*.hip /
-    csrc/gru*.hip, the layer norm of csrc/rnn_layer_norm.hip and the head product follow.  backward() runs the same
-    stations in reverse from `d_heads` and finishes every weight gradient in one `ops.MlpDwPlan` launch.
+    for arbitrary head columns (`heads`: nn.Linear modules over the recurrent features, adjacent in `arena` as for
+    ChainNet).  The normaliser, the trunk and the gate-input product are one `ops.MlpChain` launch whose last (linear)
+    layer is W_ih; the sequence-persistent kernels of csrc/lstm*.hip / csrc/gru*.hip (`stations`: the RnnStations that
+    mlp_engine.ManualMLP's recurrent branch runs on too), the layer norm of csrc/rnn_layer_norm.hip and the head product
+    follow.  backward() runs the same stations in reverse from `d_heads` and finishes every weight gradient in one
+    `ops.MlpDwPlan` launch.
     trunk: nn.Sequential of Linear + activation pairs; rnn: the torch.nn.LSTM / GRU module (parameters only);
     layer_norm: nn.LayerNorm or None.  max_rows: rows of a training minibatch, infer_rows: rows of a rollout step.
     value_tail (a central value critic: `heads` is one value column): the head, the clipped value loss and the head's
@@ -270,40 +412,29 @@ class RecurrentChainNet:
 
     def __init__(self, trunk, rnn, layer_norm, heads, arena, max_rows, infer_rows=0, value_tail=False):
         self.linears, name = plain_trunk(trunk, identity_ok=False)
-        self.lstm = rnn if isinstance(rnn, nn.LSTM) else None
-        self.gru = rnn if isinstance(rnn, nn.GRU) else None
-        if self.lstm is None and self.gru is None:
-            raise NotImplementedError('LSTM or GRU only')
-        H = rnn.hidden_size
-        if (rnn_cell_declined('lstm' if self.lstm is not None else 'gru', rnn.num_layers, H) or rnn.bidirectional
-                or not rnn.bias or getattr(rnn, 'proj_size', 0) or rnn.input_size != self.linears[-1].out_features):
+        rows = max(int(max_rows), int(infer_rows), 1)
+        self.stations = st = RnnStations(rnn, rows, self.linears[0].weight.device)
+        self.lstm, self.gru, self.rnn, self.Hr, self.Gr = st.lstm, st.gru, st.rnn, st.Hr, st.Gr
+        H = st.Hr
+        if rnn.input_size != self.linears[-1].out_features:
             raise NotImplementedError(RNN_CELLS + ' behind the trunk only')
         if layer_norm is not None and (tuple(layer_norm.normalized_shape) != (H,) or layer_norm.weight is None
                                        or layer_norm.bias is None):
             raise NotImplementedError('layer norm over the recurrent features with weight and bias only')
-        self.rnn, self.ln, self.Hr = rnn, layer_norm, H
-        self.Gr = (4 if self.lstm is not None else 3) * H
+        self.ln = layer_norm
         heads = list(heads)
         if any(h.in_features != H for h in heads):
             raise NotImplementedError('heads must read the recurrent features')
         self.head_w, self.head_w_grad, self.head_b, self.head_b_grad, self.head_cols = head_span(heads, arena)
         C = self.head_cols
         dev = self.head_w.device
-        # the bias of the gate-input product.  LSTM: b_ih + b_hh, summed into bias_sum by every forward.  GRU: b_hn is
-        # multiplied by r inside the cell, so only b_ih belongs to the input side; the kernel adds b_hh.
-        if self.lstm is not None:
-            self.gate_bias = self.bias_sum = torch.empty(self.Gr, device=dev)
-        else:
-            self.gate_bias, self.bias_sum = rnn.bias_ih_l0, None
-        layers = [(l.weight, l.bias, name) for l in self.linears] + [(rnn.weight_ih_l0, self.gate_bias, 'None')]
+        layers = [(l.weight, l.bias, name) for l in self.linears] + [(rnn.weight_ih_l0, st.gate_bias, 'None')]
         self.chain = ops.MlpChain(layers, dev, weights_version=arena.weights_token)
         self._head_mfma = (C <= 64 and ops.mlp_rowgemm_supported(H, H) and self.head_w.data_ptr() % 16 == 0)
         self.value_tail = bool(value_tail)
         if self.value_tail and (len(heads) != 1 or C != 1):
             raise NotImplementedError('the value tail takes one value column')
-        rows = max(int(max_rows), int(infer_rows), 1)
         widths = [l.out_features for l in self.linears]
-        G = self.Gr
 
         def buf(cols, dtype=torch.float32):
             return torch.empty(rows, cols, dtype=dtype, device=dev)
@@ -311,16 +442,8 @@ class RecurrentChainNet:
         self.dA = [buf(w) for w in widths]
         self.xn = buf(self.linears[0].in_features)
         self.heads, self.d_heads = buf(C), buf(C)
-        self.gates, self.rnn_out, self.d_rnn_out, self.hprev = buf(G), buf(H), buf(H), buf(H)
         nb = (rows + 15) // 16                              # one partial row per 16-row group at most
         self.partials = [torch.empty(nb * w, dtype=torch.float64, device=dev) for w in widths]
-        self.gate_partials = torch.empty(ops.act_bwd_blocks(rows, G) * G, dtype=torch.float64, device=dev)
-        if self.lstm is not None:
-            self.d_gates, self.c_all = buf(G), buf(H)
-        else:
-            self.hn_all = buf(H)                            # W_hn h + b_hn, before the gating by r
-            self.d_gx, self.d_gh = buf(G), buf(G)           # gradient of the input side / of the hidden side
-            self.gate_partials_h = torch.empty_like(self.gate_partials)
         if self.ln is not None:
             self.ln_out, self.d_ln_out, self.ln_stats = buf(H), buf(H), buf(2)
             nbl = max(ops.rnn_layer_norm_blocks(rows, H), 1)
@@ -331,19 +454,17 @@ class RecurrentChainNet:
             self.tail_partials = [torch.empty(nbt * H, dtype=torch.float64, device=dev),
                                   torch.empty(nbt, dtype=torch.float64, device=dev)]
             self.loss_blocks = 0
-        # final states of the last keep=False forward (LSTM: h and c, GRU: h), ping-pong so that a caller may feed them
-        # back in
-        nstates = 2 if self.lstm is not None else 1
-        self._state_buf = [[torch.empty(1, rows, H, device=dev) for _ in range(nstates)] for _ in range(2)]
-        self.last_states = None
         self.weight_grads = WeightGrads()
-        self._rows = 0
-        self._x = self._c0 = self._dones = None
-        self._T = 1
+        self._rows = self._fwd_rows = 0
+        self._x = None
 
     @property
     def last_dw_path(self):
         return self.weight_grads.last_dw_path
+
+    @property
+    def last_states(self):
+        return self.stations.last_states
 
     @torch.no_grad()
     def forward(self, x_raw, rms, eps, rnn_states, dones, seq_length, keep, value_loss=None):
@@ -362,7 +483,7 @@ class RecurrentChainNet:
         if value_loss is not None and not (self.value_tail and keep):
             raise ValueError('value_loss goes with keep=True on a value-tail engine')
         args = self.forward_pre_rnn(x_raw, rms, eps, rnn_states, dones, seq_length, keep)
-        (ops.lstm_seq_forward if self.lstm is not None else ops.gru_seq_forward)(*args, seq_len=seq_length)
+        self.stations.sequence('forward', args, seq_length)
         return self.forward_post_rnn(keep, value_loss)
 
     # forward() and backward() in three stations each - in front of the sequence kernel, the kernel, behind it - so that
@@ -373,53 +494,25 @@ class RecurrentChainNet:
         """Trunk + gate-input product.  Returns the arguments of ops.lstm_seq_forward / gru_seq_forward (without
         seq_len) for the sequence kernel that has to run next."""
         rows = x_raw.shape[0]
-        S = rows // seq_length
-        if S * seq_length != rows:
-            raise ValueError(f'rows ({rows}) must be a multiple of seq_length ({seq_length})')
         if not x_raw.is_contiguous() and (keep or x_raw.stride(-1) != 1):
             x_raw = x_raw.contiguous()
-        if dones is not None:
-            dones = dones.reshape(-1)
-            if dones.dtype != torch.uint8 or not dones.is_contiguous():
-                dones = dones.to(torch.uint8).contiguous()
-        rnn, H = self.rnn, self.Hr
-        h0 = rnn_states[0][0]
-        c0 = rnn_states[1][0] if self.lstm is not None else None
-        if h0.shape != (S, H) or not h0.is_contiguous() or not (c0 is None or (c0.shape == (S, H) and c0.is_contiguous())):
-            raise ValueError(f'rnn_states must be contiguous [1, {S}, {H}] tensors')
-        if self.lstm is not None:
-            torch.add(rnn.bias_ih_l0, rnn.bias_hh_l0, out=self.bias_sum)
-        gates = self.gates[:rows]
+        args = self.stations.forward_args(rows, rnn_states, dones, seq_length, keep)
+        gates = args[0]
         if keep:
             xn = self.xn[:rows] if rms is not None else None
             self.chain.forward(x_raw, gates, act_out=[h[:rows] for h in self.Hs], rms=rms, eps=eps, xn_out=xn)
             self._x = xn if rms is not None else x_raw       # what the first layer's weight gradient reads
         else:
             self.chain.forward(x_raw, gates, rms=rms, eps=eps)
-        hT = cT = None
-        if not keep:
-            flip = 1 if h0.data_ptr() == self._state_buf[0][0].data_ptr() else 0
-            hT = self._state_buf[flip][0][:, :S]
-            cT = self._state_buf[flip][1][:, :S] if self.lstm is not None else None
-        out = self.rnn_out[:rows]
-        self._fwd = (rows, c0, dones, seq_length)
-        if self.lstm is not None:
-            self.last_states = None if hT is None else (hT, cT)
-            return (gates, rnn.weight_hh_l0, h0, c0, dones, out,
-                    self.c_all[:rows] if keep else None, self.hprev[:rows] if keep else None,
-                    None if hT is None else hT[0], None if cT is None else cT[0])
-        self.last_states = None if hT is None else (hT,)
-        return (gates, rnn.weight_hh_l0, rnn.bias_hh_l0, h0, dones, out,
-                self.hn_all[:rows] if keep else None, self.hprev[:rows] if keep else None,
-                None if hT is None else hT[0])
+        self._fwd_rows = rows
+        return args
 
     @torch.no_grad()
     def forward_post_rnn(self, keep, value_loss=None, heads_out=None):
         """Layer norm and head product of the rows forward_pre_rnn saw.  heads_out: a [rows, head_cols] view (unit
         column stride) to write the heads into in place of the engine's own buffer (plain head mode)."""
-        rows, c0, dones, seq_length = self._fwd
-        H = self.Hr
-        out = feat = self.rnn_out[:rows]
+        rows, H, st = self._fwd_rows, self.Hr, self.stations
+        out = feat = st.rnn_out[:rows]
         if self.ln is not None:
             feat = self.ln_out[:rows]
             ops.rnn_layer_norm_forward(out, self.ln.weight, self.ln.bias, self.ln.eps, feat,
@@ -428,7 +521,7 @@ class RecurrentChainNet:
         if self.value_tail and keep:
             old_values, returns, mask, mask_sum, e_clip, clip_value = value_loss
             self.loss_blocks = nbt = ops.rnn_value_tail_blocks(rows, H)
-            d_feat = (self.d_ln_out if self.ln is not None else self.d_rnn_out)[:rows]
+            d_feat = (self.d_ln_out if self.ln is not None else st.d_rnn_out)[:rows]
             ops.rnn_value_tail(feat, self.head_w.view(-1), self.head_b, old_values, returns, heads.view(-1),
                                self.d_heads[:rows].view(-1), d_feat, self.loss_partials, self.tail_partials[0],
                                self.tail_partials[1], nbt, e_clip, clip_value, mask, mask_sum)
@@ -439,24 +532,24 @@ class RecurrentChainNet:
         else:
             torch.addmm(self.head_b, feat, self.head_w.t(), out=heads)
         if keep:
-            self._rows, self._c0, self._dones, self._T = rows, c0, dones, seq_length
+            self._rows = rows
         return heads
 
     @torch.no_grad()
     def backward(self):
         """d loss / d heads in self.d_heads[:rows] -> every gradient of the network in the arena (overwritten)."""
         args = self.backward_pre_rnn()
-        (ops.lstm_seq_backward if self.lstm is not None else ops.gru_seq_backward)(*args, self._T)
+        self.stations.sequence('backward', args, self.stations.seq_length)
         self.backward_post_rnn()
 
     @torch.no_grad()
     def backward_pre_rnn(self):
         """Head dX and layer-norm backward.  Returns the arguments of ops.lstm_seq_backward / gru_seq_backward (without
         seq_len) for the sequence kernel that has to run next."""
-        rows, H, rnn = self._rows, self.Hr, self.rnn
+        rows, H, st = self._rows, self.Hr, self.stations
         d_heads = self.d_heads[:rows]
-        feat = (self.ln_out if self.ln is not None else self.rnn_out)[:rows]
-        d_feat = (self.d_ln_out if self.ln is not None else self.d_rnn_out)[:rows]
+        d_out = st.d_rnn_out[:rows]
+        d_feat = self.d_ln_out[:rows] if self.ln is not None else d_out
         C = self.head_cols
         if self.value_tail:
             pass                                            # (the tail launch of the forward wrote d_feat)
@@ -471,56 +564,32 @@ class RecurrentChainNet:
             nbt = self.loss_blocks
             colsums += [(self.tail_partials[0][:nbt * H], nbt, H, self.head_w_grad.view(-1)),
                         (self.tail_partials[1][:nbt], nbt, 1, self.head_b_grad)]
-        d_out = self.d_rnn_out[:rows]
         if self.ln is not None:
             nbl = ops.rnn_layer_norm_blocks(rows, H)
             pg, pb = (p[:nbl * H] for p in self.ln_partials)
-            ops.rnn_layer_norm_backward(d_feat, self.rnn_out[:rows], self.ln_stats[:rows], self.ln.weight, d_out, pg, pb,
+            ops.rnn_layer_norm_backward(d_feat, st.rnn_out[:rows], self.ln_stats[:rows], self.ln.weight, d_out, pg, pb,
                                         nbl)
             colsums += [(pg, nbl, H, self.ln.weight.grad), (pb, nbl, H, self.ln.bias.grad)]
         self._bwd_colsums = colsums
-        gates = self.gates[:rows]
-        if self.lstm is not None:
-            return (gates, self.c_all[:rows], self._c0, self._dones, rnn.weight_hh_l0, d_out, self.d_gates[:rows])
-        return (gates, self.hn_all[:rows], self.hprev[:rows], self._dones, rnn.weight_hh_l0, d_out, self.d_gx[:rows],
-                self.d_gh[:rows])
+        return st.backward_args(d_out)
 
     @torch.no_grad()
     def backward_post_rnn(self):
         """From the gate gradients down: bias column sums, the trunk's dX chain, every weight gradient."""
-        rows, L, H, G, rnn = self._rows, len(self.linears), self.Hr, self.Gr, self.rnn
+        rows, st = self._rows, self.stations
         d_heads = self.d_heads[:rows]
-        feat = (self.ln_out if self.ln is not None else self.rnn_out)[:rows]
-        colsums = self._bwd_colsums
-        nbg = ops.act_bwd_blocks(rows, G)
-        gpart = self.gate_partials[:nbg * G]
-        if self.lstm is not None:
-            dg = dgh = self.d_gates[:rows]
-            ops.act_bwd_colsum(dg, None, dg, 0, gpart, nbg)                  # identity: column sums only
-            colsums += [(gpart, nbg, G, rnn.bias_ih_l0.grad), (gpart, nbg, G, rnn.bias_hh_l0.grad)]   # d b_hh = d b_ih
-        else:
-            # dg = d_gx: the input side - W_ih, b_ih and the trunk; dgh = d_gh: the hidden side - W_hh, b_hh
-            dg, dgh = self.d_gx[:rows], self.d_gh[:rows]
-            gpart_h = self.gate_partials_h[:nbg * G]
-            ops.act_bwd_colsum(dg, None, dg, 0, gpart, nbg)
-            ops.act_bwd_colsum(dgh, None, dgh, 0, gpart_h, nbg)
-            colsums += [(gpart, nbg, G, rnn.bias_ih_l0.grad), (gpart_h, nbg, G, rnn.bias_hh_l0.grad)]
-        # dX chain of the trunk in one launch, from d gates down (the chain's "head" layer is W_ih)
-        acts = [h[:rows] for h in self.Hs]
-        dzs = [d[:rows] for d in self.dA]
+        feat = (self.ln_out if self.ln is not None else st.rnn_out)[:rows]
         nblk = self.chain.num_blocks(rows, 1)
-        parts = [p[:nblk * l.out_features] for p, l in zip(self.partials, self.linears)]
+        acts, dzs, parts = trunk_views(self.linears, self.Hs, self.dA, self.partials, rows, nblk)
+        dg, jobs, gate_colsums = st.gate_gradients(acts[-1])
+        # dX chain of the trunk in one launch, from d gates down (the chain's "head" layer is W_ih)
         self.chain.backward(dg, acts, dzs, parts)
-        jobs = [(dgh, self.hprev[:rows], rnn.weight_hh_l0.grad), (dg, acts[-1], rnn.weight_ih_l0.grad)]
         if not self.value_tail:
             jobs.insert(0, (d_heads, feat, self.head_w_grad))
             torch.sum(d_heads, dim=0, out=self.head_b_grad)
-        for l in range(L - 1, -1, -1):
-            lin = self.linears[l]
-            jobs.append((dzs[l], acts[l - 1] if l > 0 else self._x, lin.weight.grad))
-            colsums.append((parts[l], nblk, lin.out_features, lin.bias.grad))
+        trunk, trunk_colsums = trunk_jobs(self.linears, self._x, acts, dzs, parts, nblk)
         # (bias / layer-norm gradients finished by the same finalise launch, as many as it takes)
-        self.weight_grads.finish(jobs, rows, colsums)
+        self.weight_grads.finish(jobs + trunk, rows, self._bwd_colsums + gate_colsums + trunk_colsums)
 
 
 def paired_launch_pays(cell, hidden, direction, num_seqs, seq_len):
@@ -574,9 +643,8 @@ class RecurrentChainPair:
         if self.paired and paired_launch_pays(cell, self.actor.Hr, direction, a_args[0].shape[0] // seq_length, seq_length):
             getattr(ops, f'{cell}_seq_{direction}_pair')(a_args, b_args, seq_len=seq_length)
         else:
-            single = getattr(ops, f'{cell}_seq_{direction}')
-            single(*a_args, seq_len=seq_length)
-            single(*b_args, seq_len=seq_length)
+            self.actor.stations.sequence(direction, a_args, seq_length)
+            self.critic.stations.sequence(direction, b_args, seq_length)
 
     @torch.no_grad()
     def forward(self, x_raw, rms, eps, rnn_states, dones, seq_length, keep):

@@ -30,6 +30,7 @@ from torch import nn
 from . import ops
 from .agent import A2CAgent, _ChainForms
 from .chain_net import ChainNet, RecurrentChainNet, arena_layout, rnn_cell_declined
+from .normalizers import launch_stats
 
 
 class DiscreteA2CAgent(A2CAgent):
@@ -285,12 +286,7 @@ class DiscreteA2CAgent(A2CAgent):
         rnn_eng = self._rnn_engine if obs_batch.dtype == torch.float32 else None
         if rnn_eng is not None:
             # the same normaliser update, then trunk + gate-input product, the sequence kernel, (layer norm,) heads
-            rms, eps = None, 1e-5
-            if self.normalize_input:
-                m = self.model.running_mean_std
-                if m.training:
-                    m.update(obs_batch)
-                rms, eps = (m.running_mean, m.running_var), m.epsilon
+            rms, eps = launch_stats(self.model.running_mean_std if self.normalize_input else None, obs_batch)
             mb = obs_batch.shape[0]
             heads = rnn_eng.forward(obs_batch, rms, eps, input_dict['rnn_states'],
                                     input_dict['dones'] if self.zero_rnn_on_done else None, self.seq_length, keep=True)
@@ -299,12 +295,7 @@ class DiscreteA2CAgent(A2CAgent):
         elif chains is not None:
             # models.py:54-56 (norm_obs: training mode updates the statistics first), then each trunk + its heads as
             # one launch that normalises on the way in
-            rms, eps = None, 1e-5
-            if self.normalize_input:
-                m = self.model.running_mean_std
-                if m.training:
-                    m.update(obs_batch)
-                rms, eps = (m.running_mean, m.running_var), m.epsilon
+            rms, eps = launch_stats(self.model.running_mean_std if self.normalize_input else None, obs_batch)
             outs = [c.forward(obs_batch, rms, eps) for c in chains]
             mb = obs_batch.shape[0]
             if len(chains) == 1:                                   # [value | logits]
@@ -322,10 +313,7 @@ class DiscreteA2CAgent(A2CAgent):
             logits, values = self.model.forward_heads(batch)
             mb = logits.shape[0]
             d_logits, d_val = self._d_logits[:mb], self._d_val[:mb]
-        mask = mask_sum = None
-        if rnn_masks is not None:
-            mask = rnn_masks.reshape(-1).float().contiguous()
-            mask_sum = mask.sum().reshape(1)
+        mask, mask_sum = ops.sequence_mask(rnn_masks)
         with torch.no_grad():
             lg = logits.detach()
             ops.ppo_loss_discrete(lg if lg.stride(1) == 1 else lg.contiguous(), values.detach().reshape(-1),

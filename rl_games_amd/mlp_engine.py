@@ -24,6 +24,10 @@ Numerics: aten's formulas - by default (in-place activations) act' from the laye
 elu_backward(is_result=True): h > 0 ? 1 : h + 1; with `inplace_act=False` from the pre-activation
 (exp(z)); GEMM
 results are the library's, as before.  Parameters keep their reference names and shapes.
+The recurrent cell's stations - its buffers, gate bias, ping-pong states, the sequence kernels' arguments, the gate
+gradients' column sums and weight-gradient jobs - are chain_net.RnnStations, the same object RecurrentChainNet runs on;
+this engine keeps its two trunk modes in front of it (the fused `chain_rnn`, or per-layer library products) and its own
+head stations behind it.
 backward() ends in chain_net.WeightGrads.finish - the one finisher of weight gradients, bias column sums and loss
 partials that the chain engines use as well - here with the narrow kernel for left-over products and, on the fused
 chain, the gradient norm and the fp16 form of the MFMA launch.
@@ -32,7 +36,7 @@ import torch
 from torch import nn
 
 from . import ops
-from .chain_net import RNN_CELLS, WeightGrads, arena_layout, head_span, plain_trunk, rnn_cell_declined
+from .chain_net import RnnStations, WeightGrads, arena_layout, head_span, plain_trunk, trunk_jobs, trunk_views
 
 
 class ManualMLP:
@@ -56,23 +60,16 @@ class ManualMLP:
         self.A = net.mu.out_features
         self.V = net.value.out_features
         K = net.mu.in_features
-        self.lstm = self.gru = None      # the recurrent cell's torch module (parameters only), by kind
-        self.rnn = None                  # ... whichever of the two it is
-        if getattr(net, 'has_rnn', False):
-            if rnn_cell_declined(net.rnn_name, net.rnn_layers, net.rnn_units):
-                raise NotImplementedError(f'manual engine: only {RNN_CELLS}')
-            self.rnn = net.rnn.rnn
-            if net.rnn_name == 'lstm':
-                self.lstm = self.rnn
-            else:
-                self.gru = self.rnn
-            self.Hr = net.rnn_units
-            self.Gr = (4 if self.lstm is not None else 3) * self.Hr      # gate columns
         self.head_w, self.head_w_grad, self.head_b, self.head_b_grad, _ = head_span([net.value, net.mu], arena)
         self._head_mfma = (mfma_dw and self.V + self.A <= 64 and ops.mlp_rowgemm_supported(K, K)
                            and self.head_w.data_ptr() % 16 == 0)
         dev = self.head_w.device
         self.max_rows = max_rows
+        # the recurrent cell between the trunk and the heads: chain_net.RnnStations, the one RecurrentChainNet runs on
+        self.stations = RnnStations(net.rnn.rnn, max_rows, dev) if getattr(net, 'has_rnn', False) else None
+        st = self.stations
+        # the cell's torch module (parameters only): by kind, and whichever of the two it is
+        self.lstm, self.gru, self.rnn = (st.lstm, st.gru, st.rnn) if st is not None else (None, None, None)
         widths = [l.out_features for l in self.linears]
         # inplace_act: the activation overwrites the pre-activation (one [rows, width] buffer per
         # layer instead of two) and backward takes act' from the output, like torch's in-place ELU
@@ -103,18 +100,10 @@ class ManualMLP:
         # the gate-input product W_ih x + (b_ih + b_hh) as the chain's last (linear) layer - is the same fused
         # forward / backward launch pair; the sequence-persistent LSTM kernels and the head product follow.
         self.chain_rnn = None
-        if self.rnn is not None:
-            # the bias of the gate-input product.  LSTM: b_ih + b_hh, summed into bias_sum by every forward.  GRU: b_hn is
-            # multiplied by r inside the cell, so only b_ih belongs to the input side - bias_ih_l0 itself; the kernel
-            # adds b_hh.
-            if self.lstm is not None:
-                self.gate_bias = self.bias_sum = torch.empty(self.Gr, device=dev)
-            else:
-                self.gate_bias, self.bias_sum = self.rnn.bias_ih_l0, None
         if fused_chain and self.rnn is not None:
             try:
                 layers = [(l.weight, l.bias, self.act_name) for l in self.linears]
-                layers.append((self.rnn.weight_ih_l0, self.gate_bias, 'None'))
+                layers.append((self.rnn.weight_ih_l0, st.gate_bias, 'None'))
                 self.chain_rnn = ops.MlpChain(layers, dev, weights_version=arena.weights_token)
             except NotImplementedError:
                 self.chain_rnn = None
@@ -122,32 +111,13 @@ class ManualMLP:
             self.nb = [(max_rows + 15) // 16 for _ in widths]      # one partial row per 16-row group at most
             self.xn = torch.empty(max_rows, self.linears[0].in_features, device=dev)
         self.partials = [torch.empty(nb * w, dtype=torch.float64, device=dev) for nb, w in zip(self.nb, widths)]
-        if self.rnn is not None:
-            Hr, Gr = self.Hr, self.Gr
-            self.gates = torch.empty(max_rows, Gr, device=dev)
-            d_gates = torch.empty(max_rows, Gr, device=dev)
-            self.rnn_out = torch.empty(max_rows, Hr, device=dev)
-            self.d_rnn_out = torch.empty(max_rows, Hr, device=dev)
-            kept = torch.empty(max_rows, Hr, device=dev)
-            self.hprev = torch.empty(max_rows, Hr, device=dev)
-            self.gate_partials = torch.empty(ops.act_bwd_blocks(max_rows, Gr) * Gr, dtype=torch.float64, device=dev)
-            if self.lstm is not None:
-                self.d_gates, self.c_all = d_gates, kept
-            else:
-                self.hn_all = kept                                       # W_hn h + b_hn, before the gating by r
-                self.d_gx = d_gates                                      # gradient of the input side (dr, dz, dn)
-                self.d_gh = torch.empty(max_rows, Gr, device=dev)        # ... of the hidden side (dr, dz, dn * r)
-                self.gate_partials_h = torch.empty_like(self.gate_partials)
-            # final states of the last forward (LSTM: h and c, GRU: h), ping-pong so that a caller may feed them back in
-            nstates = 2 if self.lstm is not None else 1
-            self._state_buf = [[torch.empty(1, max_rows, Hr, device=dev) for _ in range(nstates)] for _ in range(2)]
-            self._state_flip = 0
-            self.last_states = None
 
     # what the last backward()'s weight gradients ran on (bench.py and the tests read these)
     last_dw_path = property(lambda self: self.weight_grads.last_dw_path)
     last_dw_jobs = property(lambda self: self.weight_grads.last_dw_jobs)
     last_dw_library_jobs = property(lambda self: self.weight_grads.last_dw_library_jobs)
+    # final states of the last keep=False forward of a recurrent policy
+    last_states = property(lambda self: self.stations.last_states)
 
     @staticmethod
     def layout(net):
@@ -194,17 +164,9 @@ class ManualMLP:
                 h = z
             a = h
         if self.rnn is not None:
-            rnn = self.rnn
-            S = rows // seq_length
-            if S * seq_length != rows:
-                raise ValueError(f'rows ({rows}) must be a multiple of seq_length ({seq_length})')
-            h0 = rnn_states[0][0]
-            c0 = rnn_states[1][0] if self.lstm is not None else None
-            if h0.shape[0] != S or not h0.is_contiguous() or not (c0 is None or c0.is_contiguous()):
-                raise ValueError(f'rnn_states must be contiguous [1, {S}, {self.Hr}] tensors')
-            if self.lstm is not None:
-                torch.add(rnn.bias_ih_l0, rnn.bias_hh_l0, out=self.bias_sum)
-            gates = self.gates[:rows]
+            st = self.stations
+            args = st.forward_args(rows, rnn_states, dones, seq_length, keep)
+            gates = args[0]
             if fused_trunk:
                 rms = raw_rms if len(raw_rms) else None
                 if keep:
@@ -217,30 +179,10 @@ class ManualMLP:
                     self.chain_rnn.forward(x, gates, rms=rms, eps=eps)
                     a = None
             else:
-                torch.addmm(self.gate_bias, a, rnn.weight_ih_l0.t(), out=gates)
-            out = self.rnn_out[:rows]
-            # Final states are produced for inference calls only (keep=False: rollout / get_values),
-            # into whichever buffer pair the inputs do NOT live in.  A training forward must not touch
-            # these buffers: they hold the live rollout state that is carried into the next epoch.
-            hT = cT = None
-            if not keep:
-                self._state_flip = 1 if h0.data_ptr() == self._state_buf[0][0].data_ptr() else 0
-                hT = self._state_buf[self._state_flip][0][:, :S]
-                if self.lstm is not None:
-                    cT = self._state_buf[self._state_flip][1][:, :S]
-            if self.lstm is not None:
-                ops.lstm_seq_forward(gates, rnn.weight_hh_l0, h0, c0, dones, out,
-                                     self.c_all[:rows] if keep else None, self.hprev[:rows] if keep else None,
-                                     None if hT is None else hT[0], None if cT is None else cT[0],
-                                     seq_len=seq_length)
-                self.last_states = None if hT is None else (hT, cT)
-            else:
-                ops.gru_seq_forward(gates, rnn.weight_hh_l0, rnn.bias_hh_l0, h0, dones, out,
-                                    self.hn_all[:rows] if keep else None, self.hprev[:rows] if keep else None,
-                                    None if hT is None else hT[0], seq_len=seq_length)
-                self.last_states = None if hT is None else (hT,)
-            self._rnn_in, self._c0, self._dones, self._T = a, c0, dones, seq_length
-            a = out
+                torch.addmm(st.gate_bias, a, self.rnn.weight_ih_l0.t(), out=gates)
+            st.sequence('forward', args, seq_length)
+            self._rnn_in = a
+            a = st.rnn_out[:rows]
         heads = self.heads[:rows]
         if self._head_mfma and a.is_contiguous() and a.data_ptr() % 16 == 0:
             # skinny output (1 + A columns): the LDS-free MFMA kernel beats the library GEMM 2.5x here
@@ -318,9 +260,7 @@ class ManualMLP:
         if self.chain is not None:
             # one launch: dZ of every hidden layer + per-workgroup bias-gradient column sums
             nblk = self.chain.num_blocks(rows, 1)
-            acts = [h[:rows] for h in self.Hs]
-            dzs = [d[:rows] for d in self.dA]
-            parts = [p[:nblk * w.out_features] for p, w in zip(self.partials, self.linears)]
+            acts, dzs, parts = trunk_views(self.linears, self.Hs, self.dA, self.partials, rows, nblk)
             fwd, self._deferred = self._deferred, None
             self.last_step_fused = False
             if fwd is None or not (ppo_loss is not None and self._one_launch_step(fwd, d_heads, dzs, parts, ppo_loss)):
@@ -329,12 +269,8 @@ class ManualMLP:
                                        xn_out=fwd['xn_out'], rms_fold=fwd['rms_fold'])
                 self.chain.backward(d_heads, acts, dzs, parts, ppo_loss=ppo_loss)
             # (dZ, X, grad, layer): the layer index names dZ's row of the backward's gradient maxima (fp16 form)
-            jobs = [(d_heads, acts[-1], self.head_w_grad, L)]
-            colsums = []
-            for l in range(L - 1, -1, -1):
-                lin = self.linears[l]
-                jobs.append((dzs[l], acts[l - 1] if l > 0 else self._x, lin.weight.grad, l))
-                colsums.append((parts[l], nblk, lin.out_features, lin.bias.grad))
+            jobs, colsums = trunk_jobs(self.linears, self._x, acts, dzs, parts, nblk)
+            jobs.insert(0, (d_heads, acts[-1], self.head_w_grad, L))
             # the fp16 form of the weight-gradient launch splits X under the forward's FIXED scales: hidden activations, and
             # observations that went through the normaliser's clamp (raw observations have no bound: the bf16 form then)
             maxima = self.chain.gradient_maxima(rows) if self._x_normalised else None
@@ -344,51 +280,25 @@ class ManualMLP:
         jobs = [(d_heads, self._last, self.head_w_grad)]           # (dZ, X, grad) per weight matrix
         colsums = []                                               # (partials, blocks, cols, bias.grad)
         if self.rnn is not None:
-            rnn = self.rnn
-            d_out = self.d_rnn_out[:rows]
+            st = self.stations
+            d_out = st.d_rnn_out[:rows]
             if self.V + self.A <= ops.NARROW_MAX:
                 ops.narrow_dx(d_heads, self.head_w, d_out)
             else:
                 torch.mm(d_heads, self.head_w, out=d_out)
-            gates = self.gates[:rows]
-            G = self.Gr
-            nbg = ops.act_bwd_blocks(rows, G)
-            gpart = self.gate_partials[:nbg * G]
-            if self.lstm is not None:
-                dg = self.d_gates[:rows]
-                ops.lstm_seq_backward(gates, self.c_all[:rows], self._c0, self._dones, rnn.weight_hh_l0, d_out, dg,
-                                      self._T)
-                dgh = dg
-                ops.act_bwd_colsum(dg, None, dg, 0, gpart, nbg)          # identity: column sums only
-                colsums.append((gpart, nbg, G, rnn.bias_ih_l0.grad))
-                colsums.append((gpart, nbg, G, rnn.bias_hh_l0.grad))     # d b_hh = d b_ih
-            else:
-                # dg = d_gx: the input side - W_ih, b_ih and the trunk; dgh = d_gh: the hidden side - W_hh, b_hh
-                dg, dgh = self.d_gx[:rows], self.d_gh[:rows]
-                ops.gru_seq_backward(gates, self.hn_all[:rows], self.hprev[:rows], self._dones, rnn.weight_hh_l0, d_out,
-                                     dg, dgh, self._T)
-                gpart_h = self.gate_partials_h[:nbg * G]
-                ops.act_bwd_colsum(dg, None, dg, 0, gpart, nbg)
-                ops.act_bwd_colsum(dgh, None, dgh, 0, gpart_h, nbg)
-                colsums.append((gpart, nbg, G, rnn.bias_ih_l0.grad))
-                colsums.append((gpart_h, nbg, G, rnn.bias_hh_l0.grad))
-            jobs.append((dgh, self.hprev[:rows], rnn.weight_hh_l0.grad))
-            jobs.append((dg, self._rnn_in, rnn.weight_ih_l0.grad))
+            st.sequence('backward', st.backward_args(d_out), st.seq_length)
+            dg, gate_jobs, colsums = st.gate_gradients(self._rnn_in)
+            jobs += gate_jobs
             if self._fused_trunk:
                 # dX chain of the trunk in ONE launch, from d gates down: dZ of every hidden layer + the
                 # per-workgroup bias-gradient column sums (the chain's "head" layer is W_ih)
                 nblk = self.chain_rnn.num_blocks(rows, 1)
-                acts = [h[:rows] for h in self.Hs]
-                dzs = [t[:rows] for t in self.dA]
-                parts = [p[:nblk * w.out_features] for p, w in zip(self.partials, self.linears)]
+                acts, dzs, parts = trunk_views(self.linears, self.Hs, self.dA, self.partials, rows, nblk)
                 self.chain_rnn.backward(dg, acts, dzs, parts)
-                for l in range(L - 1, -1, -1):
-                    lin = self.linears[l]
-                    jobs.append((dzs[l], acts[l - 1] if l > 0 else self._x, lin.weight.grad))
-                    colsums.append((parts[l], nblk, lin.out_features, lin.bias.grad))
-                return self.weight_grads.finish(jobs, rows, colsums, loss_finalize)
+                trunk, trunk_colsums = trunk_jobs(self.linears, self._x, acts, dzs, parts, nblk)
+                return self.weight_grads.finish(jobs + trunk, rows, colsums + trunk_colsums, loss_finalize)
             d = self.dA[L - 1][:rows]
-            torch.mm(dg, rnn.weight_ih_l0, out=d)
+            torch.mm(dg, self.rnn.weight_ih_l0, out=d)
         else:
             d = self.dA[L - 1][:rows]
             torch.mm(d_heads, self.head_w, out=d)

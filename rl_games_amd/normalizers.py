@@ -108,6 +108,18 @@ class RunningMeanStd(nn.Module):
         return ops.rms_apply(input, self.running_mean, self.running_var, self.epsilon, mode, out=out)
 
 
+def launch_stats(module, batch=None):
+    """(rms, eps) for a forward launch that normalises its inputs on the way in: ((running_mean, running_var), epsilon)
+    of a RunningMeanStd `module`, (None, 1e-5) for None (normalize_input off).  batch: the inputs of a training forward
+    - a module in training mode folds them into its statistics first (models.py:54-56); None: the statistics as they
+    are (rollout, get_values)."""
+    if module is None:
+        return None, 1e-5
+    if batch is not None and module.training:
+        module.update(batch)
+    return (module.running_mean, module.running_var), module.epsilon
+
+
 class GeneralizedMovingStats(nn.Module):
     """EMA statistics, `impl='mean_std'` only (moving_mean_std.py:24-28,:57-61,:119-122)."""
 

@@ -402,6 +402,15 @@ def prepare_apply(values, returns, advantages, flags, stats, out=None):
 BOUND_KINDS = {None: 0, 'none': 0, 'bound': 1, 'regularisation': 2}
 
 
+def sequence_mask(rnn_masks):
+    """(mask [rows] fp32, sum(mask) [1]) - the `mask` / `mask_sum` arguments of the loss launches - of a recurrent
+    minibatch's `rnn_masks`; (None, None) without one."""
+    if rnn_masks is None:
+        return None, None
+    mask = rnn_masks.reshape(-1).float().contiguous()
+    return mask, mask.sum().reshape(1)
+
+
 def ppo_loss_blocks(minibatch):
     return _lib.load().rlg_ppo_loss_num_blocks(int(minibatch))
 
@@ -1344,11 +1353,8 @@ def lstm_seq_forward(gates, w_hh, h0, c0, dones, out, c_all=None, hprev=None, h_
     S = B // seq_len
     if S * seq_len != B:
         raise ValueError(f'rows ({B}) must be a multiple of seq_len ({seq_len})')
-    _lib.check(lib.rlg_lstm_seq_forward(
-        _need(gates, F32, 'gates'), _need(w_hh, F32, 'w_hh'), _need(h0, F32, 'h0'), _need(c0, F32, 'c0'),
-        _opt(dones, torch.uint8, 'dones'), _need(out, F32, 'out'), _opt(c_all, F32, 'c_all'),
-        _opt(hprev, F32, 'hprev'), _opt(h_final, F32, 'h_final'), _opt(c_final, F32, 'c_final'),
-        S, seq_len, H, _stream(gates)), 'rlg_lstm_seq_forward')
+    ptrs = _lstm_forward_pointers(gates, w_hh, h0, c0, dones, out, c_all, hprev, h_final, c_final)
+    _lib.check(lib.rlg_lstm_seq_forward(*ptrs, S, seq_len, H, _stream(gates)), 'rlg_lstm_seq_forward')
 
 
 def lstm_seq_backward(gates, c_all, c0, dones, w_hh, d_out, d_gates, seq_len):
@@ -1358,11 +1364,8 @@ def lstm_seq_backward(gates, c_all, c0, dones, w_hh, d_out, d_gates, seq_len):
     B, G = gates.shape
     if (B // seq_len) * seq_len != B:
         raise ValueError(f'rows ({B}) must be a multiple of seq_len ({seq_len})')
-    _lib.check(lib.rlg_lstm_seq_backward(
-        _need(gates, F32, 'gates'), _need(c_all, F32, 'c_all'), _need(c0, F32, 'c0'),
-        _opt(dones, torch.uint8, 'dones'), _need(w_hh, F32, 'w_hh'), _need(d_out, F32, 'd_out'),
-        _need(d_gates, F32, 'd_gates'), B // seq_len, seq_len, G // 4, _stream(gates)),
-        'rlg_lstm_seq_backward')
+    ptrs = _lstm_backward_pointers(gates, c_all, c0, dones, w_hh, d_out, d_gates)
+    _lib.check(lib.rlg_lstm_seq_backward(*ptrs, B // seq_len, seq_len, G // 4, _stream(gates)), 'rlg_lstm_seq_backward')
 
 
 def _pair_shape(a_gates, b_gates, gates_per_unit, seq_len):
@@ -1434,14 +1437,8 @@ def gru_seq_forward(gates, w_hh, b_hh, h0, dones, out, hn_all=None, hprev=None, 
     S = B // seq_len
     if S * seq_len != B:
         raise ValueError(f'rows ({B}) must be a multiple of seq_len ({seq_len})')
-    if G != 3 * H or tuple(w_hh.shape) != (G, H) or b_hh.numel() != G:
-        raise ValueError(f'gates [rows, 3H], w_hh [3H, H] and b_hh [3H] do not agree: {tuple(gates.shape)}, '
-                         f'{tuple(w_hh.shape)}, {tuple(b_hh.shape)}')
-    _lib.check(lib.rlg_gru_seq_forward(
-        _need(gates, F32, 'gates'), _need(w_hh, F32, 'w_hh'), _need(b_hh, F32, 'b_hh'), _need(h0, F32, 'h0'),
-        _opt(dones, torch.uint8, 'dones'), _need(out, F32, 'out'), _opt(hn_all, F32, 'hn_all'),
-        _opt(hprev, F32, 'hprev'), _opt(h_final, F32, 'h_final'),
-        S, seq_len, H, _stream(gates)), 'rlg_gru_seq_forward')
+    ptrs = _gru_forward_pointers(gates, w_hh, b_hh, h0, dones, out, hn_all, hprev, h_final)
+    _lib.check(lib.rlg_gru_seq_forward(*ptrs, S, seq_len, H, _stream(gates)), 'rlg_gru_seq_forward')
 
 
 def gru_seq_backward(gates, hn_all, hprev, dones, w_hh, d_out, d_gx, d_gh, seq_len):
@@ -1454,14 +1451,8 @@ def gru_seq_backward(gates, hn_all, hprev, dones, w_hh, d_out, d_gx, d_gh, seq_l
     S = B // seq_len
     if S * seq_len != B:
         raise ValueError(f'rows ({B}) must be a multiple of seq_len ({seq_len})')
-    if G != 3 * H or tuple(w_hh.shape) != (G, H) or d_gx.shape != gates.shape or d_gh.shape != gates.shape:
-        raise ValueError(f'gates / d_gx / d_gh [rows, 3H] and w_hh [3H, H] do not agree: {tuple(gates.shape)}, '
-                         f'{tuple(d_gx.shape)}, {tuple(d_gh.shape)}, {tuple(w_hh.shape)}')
-    _lib.check(lib.rlg_gru_seq_backward(
-        _need(gates, F32, 'gates'), _need(hn_all, F32, 'hn_all'), _need(hprev, F32, 'hprev'),
-        _opt(dones, torch.uint8, 'dones'), _need(w_hh, F32, 'w_hh'), _need(d_out, F32, 'd_out'),
-        _need(d_gx, F32, 'd_gx'), _need(d_gh, F32, 'd_gh'), S, seq_len, H, _stream(gates)),
-        'rlg_gru_seq_backward')
+    ptrs = _gru_backward_pointers(gates, hn_all, hprev, dones, w_hh, d_out, d_gx, d_gh)
+    _lib.check(lib.rlg_gru_seq_backward(*ptrs, S, seq_len, H, _stream(gates)), 'rlg_gru_seq_backward')
 
 
 def _gru_forward_pointers(gates, w_hh, b_hh, h0, dones, out, hn_all=None, hprev=None, h_final=None):
