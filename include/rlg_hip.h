@@ -447,6 +447,46 @@ int rlg_adam_step_pack(float* params, float* grads, float* exp_avg, float* exp_a
                        const int* in_features, const int* out_features, void* planes, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Range guard of the split-fp16 products (csrc/range_guard.hip)
+ *   The split-fp16 launches hold |weight| < 1023 and |hidden activation| < 4094 (csrc/bx_form.hpp); past that a plane
+ *   is Inf and what is computed from it is Inf / NaN.  The guard record is 4 device words (16-byte aligned, zeroed by
+ *   the caller = clear): record[0] = tag of what tripped (0: nothing), record[1] = where; record[2..3] belong to the
+ *   scan.  A set record is sticky: no launch below changes it.
+ *   rlg_range_scan: ONE launch over up to 8 fp32 arrays (arrays[k], counts[k] elements, tags[k] != 0).  On a non-finite
+ *   value: record[0] = the tag of the first array in argument order that holds one, record[1] = the smallest offending
+ *   flat index in that array - whatever the scheduling.  Clean arrays: 16-byte loads and no store, no atomic.  A launch
+ *   that finds the record set leaves it bit for bit.  Capturable; a captured launch must not be replayed over a record
+ *   that an earlier replay of itself set (it would take that record for its own and keep the better of the two hits).
+ *   hipErrorInvalidValue before the runtime is asked for anything: NULL or misaligned record, num_arrays outside
+ *   [0, 8], a negative count or one above 2^32 - 1, a tag of 0, a NULL array with a non-zero count.
+ *   rlg_adam_step_guarded / rlg_adam_pack_guarded: rlg_adam_step / rlg_adam_step_pack with such a record (not NULL) and
+ *   with norm_partials (not NULL, norm_blocks > 0: the guard watches the norm; max_norm = +Inf never clips).
+ *   The launch is skipped exactly as under skip_flag - parameters, moments, planes untouched, the learning rate carried
+ *   over, the step counter as skip_flag leaves it - when the record is set or the total gradient norm (with
+ *   norm_partials) is not finite; in the second case a clear record becomes (RLG_GUARD_TAG_ADAM, low 32 bits of the
+ *   optimiser step).  An infinite norm trips too, where the unguarded launch clips with coefficient 0.  The unguarded
+ *   entries are unchanged: a NaN norm reaches every parameter, as torch.clamp would have it.
+ * ---------------------------------------------------------------------------------- */
+#define RLG_GUARD_TAG_ADAM 0x4144414d   /* 'ADAM' */
+int rlg_range_scan(int num_arrays, const float* const* arrays, const long long* counts, const int* tags,
+                   unsigned* record, void* stream);
+int rlg_adam_step_guarded(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long long n,
+                          const double* norm_partials_or_null, int norm_blocks, float grad_scale,
+                          float max_norm, double* lr_slots, const long long* step_counter, double beta1,
+                          double beta2, double eps, double weight_decay, int schedule_kind,
+                          const float* kl_or_null, float kl_scale, double kl_threshold, double min_lr,
+                          double max_lr, double lr_multiplier, float* stats_out_or_null,
+                          const unsigned* skip_flag_or_null, unsigned* guard_record, void* stream);
+int rlg_adam_pack_guarded(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long long n,
+                          const double* norm_partials_or_null, int norm_blocks, float grad_scale, float max_norm,
+                          double* lr_slots, const long long* step_counter, double beta1, double beta2, double eps,
+                          double weight_decay, int schedule_kind, const float* kl_or_null, float kl_scale,
+                          double kl_threshold, double min_lr, double max_lr, double lr_multiplier,
+                          float* stats_out_or_null, const unsigned* skip_flag_or_null, unsigned* guard_record,
+                          int num_layers, const float* const* weights, const int* in_features, const int* out_features,
+                          void* planes, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Manual MLP backward helpers
  *   replace, per hidden layer of A2CBuilder's MLP (rl_games/algos_torch/network_builder.py:
  *   118-147, forward :498), aten's activation backward + the bias-gradient sum(0) of
@@ -528,6 +568,19 @@ int rlg_mlp_dw_launch(int num_layers, const float* const* dz, const float* const
                        * like rlg_grad_sumsq does. */
                       double* norm_partials_or_null, float grad_scale, long long* step_counter_or_null,
                       int* finalize_blocks_out_or_null, void* stream);
+
+/* rlg_mlp_dw_launch with the product form of THIS launch instead of the process-wide environment switches: form 0 =
+ * exact f32 products (no range limit), 1 = six bf16 plane products, 2 = three fp16 plane products (needs the maxima
+ * of rlg_mlp_dw_gradient_maxima, else hipErrorInvalidValue; |x| * x_scale must stay below 65,504), -1 = the library's
+ * choice, i.e. rlg_mlp_dw_launch (RLG_DW_BF16 / RLG_DW_F16 are the defaults of that choice).  Plans of rlg_mlp_dw_plan
+ * serve every form. */
+int rlg_mlp_dw_launch_form(int form, int num_layers, const float* const* dz, const float* const* x, float* const* partial,
+                           float* const* grad, const int* out_features, const int* in_features,
+                           const int* plans4, int rows, int num_colsums, const double* const* colsum_partials,
+                           const int* colsum_blocks, const int* colsum_cols, float* const* colsum_out,
+                           const rlg_loss_finalize_desc* loss_finalize_or_null, double* norm_partials_or_null,
+                           float grad_scale, long long* step_counter_or_null, int* finalize_blocks_out_or_null,
+                           void* stream);
 
 /* ---- the MLP as one vertically fused chain on f32 MFMA (csrc/mlp_chain.hip) ------------------
  * forward : heads = head(act(... act(norm(x) W_0^T + b_0) ...)) for a row tile, every layer in ONE

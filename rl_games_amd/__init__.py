@@ -3,3 +3,5 @@ clipped-PPO loss, optimiser step) as hand-written gfx950 HIP kernels behind the 
 A2CAgent / Runner API.  MI355X only; there is no CPU fallback."""
 
 __version__ = '0.1.0'
+
+from .range_guard import SplitRangeError  # noqa: E402,F401  (raised by the agents' range guard: split_range 'raise' / 'exact')

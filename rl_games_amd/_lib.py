@@ -80,6 +80,8 @@ _PROTOTYPES = {
     'rlg_mlp_dw_plan': [_c_int, _c_int, _c_int, _c_int, _P],
     'rlg_mlp_dw_launch': [_c_int, _P, _P, _P, _P, _P, _P, _P, _c_int, _c_int, _P, _P, _P, _P, _P, _P, _c_float, _P,
                           _P, _P],
+    'rlg_mlp_dw_launch_form': [_c_int, _c_int, _P, _P, _P, _P, _P, _P, _P, _c_int, _c_int, _P, _P, _P, _P, _P, _P, _c_float,
+                               _P, _P, _P],
     'rlg_narrow_dx': [_P, _c_ll, _P, _P, _c_ll, _c_ll, _c_int, _c_int, _P],
     'rlg_narrow_dw_blocks': [_c_ll],
     'rlg_narrow_dw': [_P, _c_ll, _P, _c_ll, _P, _P, _c_ll, _c_int, _c_int, _P],
@@ -181,6 +183,14 @@ _PROTOTYPES = {
     'rlg_adam_step_pack': [_P, _P, _P, _P, _c_ll, _P, _c_int, _c_float, _c_float, _P, _P,
                            _c_double, _c_double, _c_double, _c_double, _c_int, _P, _c_float, _c_double,
                            _c_double, _c_double, _c_double, _P, _P, _c_int, _P, _P, _P, _P, _P],
+    # range_guard.hip and the guarded optimiser entries (optim.hip, adam_pack.hip)
+    'rlg_range_scan': [_c_int, _P, _P, _P, _P, _P],
+    'rlg_adam_step_guarded': [_P, _P, _P, _P, _c_ll, _P, _c_int, _c_float, _c_float, _P, _P,
+                              _c_double, _c_double, _c_double, _c_double, _c_int, _P, _c_float, _c_double,
+                              _c_double, _c_double, _c_double, _P, _P, _P, _P],
+    'rlg_adam_pack_guarded': [_P, _P, _P, _P, _c_ll, _P, _c_int, _c_float, _c_float, _P, _P,
+                              _c_double, _c_double, _c_double, _c_double, _c_int, _P, _c_float, _c_double,
+                              _c_double, _c_double, _c_double, _P, _P, _P, _c_int, _P, _P, _P, _P, _P],
 }
 
 _lib = None

@@ -34,7 +34,7 @@ import torch
 from torch import nn
 
 from . import distributed as rdist
-from . import ops
+from . import ops, range_guard
 from .diagnostics import DefaultDiagnostics, PpoDiagnostics
 from .flat_optim import FlatAdam
 from .gae import compute_gae, gae_returns_advantages
@@ -174,6 +174,9 @@ class A2CAgent:
         self.multi_gpu_param_check = config.get('multi_gpu_param_check', 'raise')
         if self.multi_gpu_param_check not in ('raise', 'rebroadcast', False, None):
             raise ValueError("multi_gpu_param_check must be 'raise', 'rebroadcast' or False")
+        # range guard of the split-fp16 products (range_guard.py): split_range 'warn' | 'raise' | 'exact', chain_products
+        # 'auto' | 'exact'.  `chain_products` is also the mode the agent is on NOW ('exact' after a trip under 'exact').
+        self.split_range, self.chain_products = range_guard.policy_from_config(config)
         self.local_rank = self.global_rank = 0
         self.world_size = 1
         if self.multi_gpu:
@@ -457,6 +460,7 @@ class A2CAgent:
                                      value_size=self.value_size)
         self._obs_norm_mb = (torch.empty((mb,) + tuple(self.obs_shape), dtype=torch.float32, device=dev)
                              if self.normalize_input else None)
+        self._arm_range_guard()
         self.algo_observer.after_init(self)
 
     def _init_action_space(self, config):
@@ -1096,7 +1100,9 @@ class A2CAgent:
             step_time += time.perf_counter() - t0
             self._rollout_step_tail(n, res_dict, rewards, infos, mb_valid)
         batch_dict = buf.get_transformed_list(swap_and_flatten01, self.tensor_list)
-        return self._finish_rollout(batch_dict, mb_valid, step_time)
+        batch_dict = self._finish_rollout(batch_dict, mb_valid, step_time)
+        self._scan_rollout(batch_dict)
+        return batch_dict
 
     def play_steps_rnn(self):
         """a2c_common.py:1071-1202."""
@@ -1144,6 +1150,7 @@ class A2CAgent:
             self._rollout_step_tail(n, res_dict, rewards, infos, mb_valid)
         batch_dict = buf.get_transformed_list(swap_and_flatten01, self.tensor_list)
         batch_dict = self._finish_rollout(batch_dict, mb_valid, step_time)
+        self._scan_rollout(batch_dict)
         if mb_valid is not None and self.zero_rnn_on_done:
             rnn_dones = buf.tensor_dict['dones'].clone()
             garbage = (mb_valid == 0.0)
@@ -1690,7 +1697,8 @@ class A2CAgent:
         return (ptrs, self.e_clip, self.critic_coef, self.entropy_coef, self.bounds_loss_coef,
                 self.bound_loss_type, self.clip_value, self.surrogate, self.grad_norm,
                 self.truncate_grads, self.schedule_type, self.is_adaptive_lr, sched, self.world_size,
-                self._fold_ready and self.model.running_mean_std._mb_table.data_ptr())
+                self._fold_ready and self.model.running_mean_std._mb_table.data_ptr(),
+                self.chain_products, self._guard is not None)
 
     def _graphs_usable(self):
         return (self._hip_graphs and self._engine is not None and self._eager_epochs >= 1
@@ -1808,6 +1816,12 @@ class A2CAgent:
         update_time_start = time.perf_counter()
         self.set_train()
         self.curr_frames = batch_dict.pop('played_frames')
+        if self._guard is not None and self._range_verdict('rollout'):
+            # policy 'exact': the rollout came off overflowed planes - no prepare_dataset (value_mean_std), no update
+            now = time.perf_counter()
+            nan = [torch.full((), float('nan'), device=self.ppo_device)]
+            return (batch_dict['step_time'], play_time_end - play_time_start, now - update_time_start,
+                    now - play_time_start, nan, list(nan), [], list(nan), list(nan), self._host_lr, 1.0)
         self.prepare_dataset(batch_dict)
         self.algo_observer.after_steps()
         self._prepare_obs_fold()
@@ -1888,6 +1902,9 @@ class A2CAgent:
             self._host_schedule(float(torch.stack(kls).mean().item()))
         self._fold_ready = False
         self.sync_running_stats()
+        # (policy 'exact': every step from the tripped one on was skipped on the device; the next epoch runs on exact
+        #  products, eagerly - it is the warm-up epoch of the new launches, so this epoch does not count as one)
+        switched = self._guard is not None and self._range_verdict('update')
         self._check_ranks_in_sync()
         if self._ipc_comm:
             # one host read per epoch; the verdict is collective, so that every rank raises in the same epoch
@@ -1902,8 +1919,9 @@ class A2CAgent:
                                    f'rank that gave up - parameters may differ between ranks, aborting on all ranks. '
                                    f'Raise native_allreduce_timeout_s / RLG_IPC_TIMEOUT_S for legitimately long rank '
                                    f'skews, or set native_allreduce: False to use RCCL.')
-        self._eager_epochs += 0 if use_graphs else 1
-        self._check_split_range()
+        self._eager_epochs += 0 if (use_graphs or switched) else 1
+        if self._guard is None:
+            self._check_split_range()
         if device_schedule:
             # one host read per epoch: [lr the last minibatch was stepped with, lr for the next one]
             used, nxt = self.optimizer.last_and_next_lr()
@@ -1934,7 +1952,84 @@ class A2CAgent:
             warnings.warn(
                 'rl_games_amd: non-finite losses in this epoch.  If the inputs are finite: the split-fp16 chain kernels hold '
                 '|hidden activation| < 4094 and |weight| < 1023 (fixed operand scales, csrc/bx_form.hpp); a network '
-                'beyond that runs on exact fp32 products with RLG_CHAIN_BX=0 RLG_DW_BF16=0.', RuntimeWarning)
+                "beyond that runs on exact fp32 products with chain_products: 'exact'; split_range: 'raise' / 'exact' "
+                'keeps such an epoch away from parameters and normalisers.', RuntimeWarning)
+
+    # ------------------------------------------------------------------ range guard (range_guard.py)
+    def _range_engines(self):
+        """Every engine of this agent that finishes weight gradients (chain_net.WeightGrads)."""
+        engines = [self._engine, getattr(self, '_rnn_engine', None)] + list(self._chains or ())
+        if self._rnn_pair is not None:
+            engines += [self._rnn_pair.actor, self._rnn_pair.critic]
+        if self.central_value_net is not None:
+            engines += [self.central_value_net._engine, self.central_value_net._rnn_engine]
+        return [e for e in engines if e is not None]
+
+    def _set_chain_products(self, mode):
+        """Every chain of the agent (and of its central value network) on `mode`, the weight-gradient launches on the
+        matching form.  Captured graphs hold the other mode's launches: the update graphs go with the signature, the
+        rollout's step graphs here, and the next epoch runs eagerly like the first."""
+        for f in self._form_chains:
+            f.chain.products = mode
+        for e in self._range_engines():
+            e.weight_grads.form = 'exact' if mode == 'exact' else None
+        if mode != self.chain_products:
+            self._rollout_graphs.clear()
+            self._eager_epochs = 0
+        self.chain_products = mode
+        if self.central_value_net is not None:
+            self.central_value_net.chain_products = mode
+
+    def _arm_range_guard(self):
+        """At the end of construction: the configured product mode on every chain, and - split_range 'raise' / 'exact' -
+        the guard record into this agent's optimiser and its critic's."""
+        self._guard = None
+        self._range_noticed = False
+        if self.central_value_net is not None and self.central_value_net.chain_products == 'exact':
+            self.chain_products = 'exact'                 # (one mode for the agent and its critic)
+        self._set_chain_products(self.chain_products)
+        if self.split_range == 'warn' and (self.central_value_net is None or self.central_value_net.split_range == 'warn'):
+            return
+        if self.split_range == 'warn':
+            self.split_range = self.central_value_net.split_range
+        self._guard = ops.guard_record(self.ppo_device)
+        self.optimizer.guard = self._guard
+        if self.central_value_net is not None:
+            self.central_value_net.share_range_guard(self._guard)
+
+    def _scan_rollout(self, batch_dict):
+        """Armed: ONE launch, behind _finish_rollout, over everything prepare_dataset and the update take from the policy
+        launches - values (a central value critic's, where there is one: they replace the actor's in the buffer),
+        neglogps, for a continuous policy mus (a discrete policy's logits are not kept; its neglogps come from them), and
+        the returns: the bootstrap values of the observation behind the last step are one more launch on the same planes,
+        kept in no buffer, and reach value_mean_std through the returns alone.  No host read."""
+        if self._guard is None:
+            return
+        st = self.experience_buffer.storage
+        arrays = [(st['values'], range_guard.TAG_CRITIC_VALUES if self.has_central_value else range_guard.TAG_VALUES),
+                  (st['neglogpacs'], range_guard.TAG_NEGLOGPS)]
+        if not self.is_discrete:
+            arrays.append((st['mus'], range_guard.TAG_POLICY))
+        returns = batch_dict['returns']
+        arrays.append((returns if returns.is_contiguous() else returns.contiguous(), range_guard.TAG_RETURNS))
+        ops.range_scan(arrays, self._guard)
+
+    def _range_verdict(self, phase):
+        """One host read of the guard record; under multi_gpu the verdict is collective (MAX), so every rank takes the
+        same branch in the same epoch.  Clean: False.  Tripped: SplitRangeError under policy 'raise', or when the
+        products are exact already (then the inputs are not finite); under policy 'exact' one notice, every chain on
+        exact products, the record cleared, True - the caller drops what is left of the epoch."""
+        what = range_guard.verdict(self._guard, phase, self.split_range, self.chain_products, self.multi_gpu,
+                                   self.ppo_device, ops.read_guard)
+        if what is None:
+            return False
+        if not self._range_noticed:
+            self._range_noticed = True
+            print(f'rl_games_amd: {what}.  split_range: exact - the rest of this epoch is dropped, training continues on '
+                  f'exact fp32 products (the actions of this rollout have already gone to the environment).', flush=True)
+        self._set_chain_products('exact')
+        self._guard.zero_()
+        return True
 
     # ================================================================== multi-GPU stats
     def _stats_sync_modules(self):

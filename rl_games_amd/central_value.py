@@ -27,7 +27,7 @@ import torch
 from torch import nn
 
 from . import distributed as rdist
-from . import ops
+from . import ops, range_guard
 from .chain_net import ChainNet, RecurrentChainNet, arena_layout, rnn_cell_declined
 from .flat_optim import FlatAdam
 from .lr_control import IdentityScheduler, LinearScheduler
@@ -72,6 +72,11 @@ class CentralValueTrain(nn.Module):
         self.multi_gpu, self.config = multi_gpu, config
         self.normalize_input = config['normalize_input']
         self.zero_rnn_on_done = zero_rnn_on_done
+        # range guard of the split-fp16 products (range_guard.py).  Inside an agent the agent's keys and its record
+        # take over (share_range_guard); a critic trained on its own arms a record of its own and gives the verdict
+        # at the end of train_net.
+        self.split_range, self.chain_products = range_guard.policy_from_config(config)
+        self._guard, self._guard_shared, self._range_noticed = None, False, False
         self.model = network.build({
             'value_size': value_size, 'input_shape': state_shape, 'actions_num': num_actions,
             'num_agents': num_agents, 'num_seqs': num_actors, 'normalize_input': self.normalize_input,
@@ -124,6 +129,10 @@ class CentralValueTrain(nn.Module):
                 self._engine = _value_chain(net, self.optimizer, self.minibatch_size)
             except NotImplementedError as e:
                 print(f'rl_games_amd: central value network outside the fused chain kernels ({e}); using autograd')
+        self.set_chain_products(self.chain_products)
+        if self.split_range != 'warn':
+            self._guard = ops.guard_record(ppo_device)
+            self.optimizer.guard = self._guard
         self.frame = 0
         self.epoch_num = 0
         self.grad_norm = config.get('grad_norm', 1)
@@ -148,6 +157,32 @@ class CentralValueTrain(nn.Module):
                                  device=ppo_device)
         self._no_logstd = torch.zeros(1, dtype=torch.float32, device=ppo_device)
         self._row_index = 0
+
+    def set_chain_products(self, mode):
+        """'auto' / 'exact' for the critic's chain and its weight-gradient launch (ops.MlpChain.products)."""
+        for eng in (self._engine, self._rnn_engine):
+            if eng is not None:
+                eng.chain.products = mode
+                eng.weight_grads.form = 'exact' if mode == 'exact' else None
+        self.chain_products = mode
+
+    def share_range_guard(self, record):
+        """The agent's guard record: the critic's optimiser steps are guarded by it and the agent gives the verdict."""
+        self._guard, self._guard_shared = record, True
+        self.optimizer.guard = record
+
+    def _range_verdict(self):
+        """A critic with a record of its own: one host read behind its epoch (A2CAgent._range_verdict, phase 'update')."""
+        what = range_guard.verdict(self._guard, 'central value update', self.split_range, self.chain_products,
+                                   self.multi_gpu, self.ppo_device, ops.read_guard)
+        if what is None:
+            return
+        if not self._range_noticed:
+            self._range_noticed = True
+            print(f'rl_games_amd: {what}.  split_range: exact - the optimiser steps from the tripped one on were skipped, '
+                  f'training continues on exact fp32 products.', flush=True)
+        self.set_chain_products('exact')
+        self._guard.zero_()
 
     def decline_rnn_engine(self, reason):
         """Take a recurrent critic off its engine (the agent: conditions that only it knows); it trains with autograd."""
@@ -266,6 +301,8 @@ class CentralValueTrain(nn.Module):
         self.lr, _ = self.scheduler.update(self.lr, 0, self.epoch_num, self.frame, 0)
         self.update_lr(self.lr)
         self.frame += self.batch_size
+        if self._guard is not None and not self._guard_shared:
+            self._range_verdict()
         if self.writter is not None:
             self.writter.add_scalar('losses/cval_loss', avg_loss.item(), self.frame)
             self.writter.add_scalar('info/cval_lr', self.lr, self.frame)

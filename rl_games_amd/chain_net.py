@@ -101,10 +101,13 @@ class WeightGrads:
     the heaviest matrix's blocks first; its finalise launch also finishes up to _DW_MAX_ITEMS bias column sums and the
     PPO loss partials.  What is left - a first layer over 9 state features, say - is a library product each, or with
     `narrow` the narrow kernel of csrc/mlp_narrow.hip where it applies (the two give different bits).
-    mfma=False: no MFMA launch at all.  Plans (and the shapes the launch declined) are kept per shape key."""
+    mfma=False: no MFMA launch at all.  Plans (and the shapes the launch declined) are kept per shape key.
+    form: the product form of the MFMA launch (ops.MlpDwPlan.launch) - None: the library's choice, 'exact': f32 products
+    whatever maxima the step carries (an agent on `chain_products: exact`)."""
 
     def __init__(self, mfma=True, narrow=False):
         self.mfma, self.narrow = bool(mfma), bool(narrow)
+        self.form = None
         self._plans = {}
         self.last_dw_path = None            # 'mfma' / 'library': whether the last finish() had an MFMA launch
         self.last_dw_jobs = None            # (jobs, plan, maxima) of the last MFMA launch: bench.py times it after the run
@@ -146,12 +149,13 @@ class WeightGrads:
             whole = (norm is not None and not slow and not colsums and loss_finalize is not None
                      and norm[0].numel() >= plan.finalize_blocks(launched, loss_finalize))
             mx = None
-            if maxima is not None and all(len(j) == 4 for j in fast):
+            if maxima is not None and self.form != 'exact' and all(len(j) == 4 for j in fast):
                 # X is split under the forward's fixed scales: normalised observations (layer 0) / hidden activations
                 mx = (maxima[0], [j[3] for j in fast],
                       [ops.SPLIT_SCALE_OBS_NORM if j[3] == 0 else ops.SPLIT_SCALE_HIDDEN for j in fast], maxima[1])
             triples = [j[:3] for j in fast]
-            blocks = plan.launch(triples, launched, loss_finalize, norm if whole else None, maxima=mx)
+            form = {} if self.form is None else {'form': self.form}        # (None: the launch as it always was)
+            blocks = plan.launch(triples, launched, loss_finalize, norm if whole else None, maxima=mx, **form)
             norm_blocks = blocks if whole else None
             loss_finalize = None
             self.last_dw_jobs = (triples, plan, mx)

@@ -55,6 +55,7 @@ __global__ __launch_bounds__(256) void adam_pack_kernel(AdamPackArgs ap) {
   const AdamArgs& a = ap.adam;
   __shared__ float sh_clip;
   __shared__ float sh_norm;
+  __shared__ int sh_trip;
   __shared__ double scratch[256 / kWave];
   // ---- everything this thread will need is requested FIRST (the gradient-norm reduction below is a chain of two memory
   //      round trips and two barriers: the loads of the block overlap with it instead of following it)
@@ -83,7 +84,7 @@ __global__ __launch_bounds__(256) void adam_pack_kernel(AdamPackArgs ap) {
       v4[r] = *reinterpret_cast<const f32x4*>(a.exp_avg_sq + idx[r]);
     }
   }
-  const bool skip = a.skip_flag != nullptr && *a.skip_flag != 0u;
+  const bool flagged = (a.skip_flag != nullptr && *a.skip_flag != 0u) || (a.guard != nullptr && a.guard[0] != 0u);
   const long long step = *a.step_counter;
   const int cur = static_cast<int>((step - 1) & 1);
   const double lr = a.lr_slots[cur];
@@ -110,8 +111,12 @@ __global__ __launch_bounds__(256) void adam_pack_kernel(AdamPackArgs ap) {
     }
     sh_clip = coef;
     sh_norm = total_norm;
+    const bool trip = adam_guard_trips(a, total_norm);
+    sh_trip = trip ? 1 : 0;
+    if (trip && blockIdx.x == 0) adam_guard_record(a, step);
   }
   __syncthreads();
+  const bool skip = flagged || sh_trip != 0;
   const float clip = sh_clip;
   const AdamScalars k = adam_scalars(a, step, lr);
 #ifdef RLG_ADAM_TRACE
@@ -227,13 +232,14 @@ extern "C" {
 // uses rlg_adam_step + rlg_mlp_chain_pack_planes): every weight matrix lies inside [params, params + n), 16-byte
 // aligned relative to it, with in_features % 4 == 0; the four arenas are 16-byte aligned; `planes` has been packed in
 // full once (the zero padding).
-int rlg_adam_step_pack(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long long n,
-                       const double* norm_partials_or_null, int norm_blocks, float grad_scale, float max_norm,
-                       double* lr_slots, const long long* step_counter, double beta1, double beta2, double eps,
-                       double weight_decay, int schedule_kind, const float* kl_or_null, float kl_scale,
-                       double kl_threshold, double min_lr, double max_lr, double lr_multiplier, float* stats_out_or_null,
-                       const unsigned* skip_flag_or_null, int num_layers, const float* const* weights,
-                       const int* in_features, const int* out_features, void* planes, void* stream) {
+static int adam_pack_launch(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long long n,
+                            const double* norm_partials_or_null, int norm_blocks, float grad_scale, float max_norm,
+                            double* lr_slots, const long long* step_counter, double beta1, double beta2, double eps,
+                            double weight_decay, int schedule_kind, const float* kl_or_null, float kl_scale,
+                            double kl_threshold, double min_lr, double max_lr, double lr_multiplier,
+                            float* stats_out_or_null, const unsigned* skip_flag_or_null, unsigned* guard_or_null,
+                            int num_layers, const float* const* weights, const int* in_features, const int* out_features,
+                            void* planes, void* stream) {
   using namespace rlg;
   if (n <= 0 || !step_counter || num_layers < 1 || num_layers > kChainMaxLayers || planes == nullptr)
     return static_cast<int>(hipErrorInvalidValue);
@@ -268,6 +274,7 @@ int rlg_adam_step_pack(float* params, float* grads, float* exp_avg, float* exp_a
   a.lr_multiplier = lr_multiplier;
   a.stats_out = stats_out_or_null;
   a.skip_flag = skip_flag_or_null;
+  a.guard = guard_or_null;
   RLG_ADAM_TRACE_FILL(a);
   unsigned foff[kChainMaxLayers], boff[kChainMaxLayers];
   const long long ftotal = chain_bx_plane_offsets(num_layers, in_features, out_features, 0, foff);
@@ -315,6 +322,37 @@ int rlg_adam_step_pack(float* params, float* grads, float* exp_avg, float* exp_a
   const int grid = ap.matrix_blocks + static_cast<int>((flat + 255) / 256);
   hipLaunchKernelGGL(adam_pack_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), ap);
   RLG_RETURN_LAUNCH_STATUS();
+}
+
+int rlg_adam_step_pack(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long long n,
+                       const double* norm_partials_or_null, int norm_blocks, float grad_scale, float max_norm,
+                       double* lr_slots, const long long* step_counter, double beta1, double beta2, double eps,
+                       double weight_decay, int schedule_kind, const float* kl_or_null, float kl_scale,
+                       double kl_threshold, double min_lr, double max_lr, double lr_multiplier, float* stats_out_or_null,
+                       const unsigned* skip_flag_or_null, int num_layers, const float* const* weights,
+                       const int* in_features, const int* out_features, void* planes, void* stream) {
+  return adam_pack_launch(params, grads, exp_avg, exp_avg_sq, n, norm_partials_or_null, norm_blocks, grad_scale, max_norm,
+                          lr_slots, step_counter, beta1, beta2, eps, weight_decay, schedule_kind, kl_or_null, kl_scale,
+                          kl_threshold, min_lr, max_lr, lr_multiplier, stats_out_or_null, skip_flag_or_null, nullptr,
+                          num_layers, weights, in_features, out_features, planes, stream);
+}
+
+// rlg_adam_step_pack under a range-guard record: a skipped launch leaves the planes as they are, too
+int rlg_adam_pack_guarded(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long long n,
+                          const double* norm_partials_or_null, int norm_blocks, float grad_scale, float max_norm,
+                          double* lr_slots, const long long* step_counter, double beta1, double beta2, double eps,
+                          double weight_decay, int schedule_kind, const float* kl_or_null, float kl_scale,
+                          double kl_threshold, double min_lr, double max_lr, double lr_multiplier,
+                          float* stats_out_or_null, const unsigned* skip_flag_or_null, unsigned* guard_record,
+                          int num_layers, const float* const* weights, const int* in_features, const int* out_features,
+                          void* planes, void* stream) {
+  // (the guard watches the gradient norm: without the partials it would watch nothing)
+  if (guard_record == nullptr || norm_partials_or_null == nullptr || norm_blocks <= 0)
+    return static_cast<int>(hipErrorInvalidValue);
+  return adam_pack_launch(params, grads, exp_avg, exp_avg_sq, n, norm_partials_or_null, norm_blocks, grad_scale, max_norm,
+                          lr_slots, step_counter, beta1, beta2, eps, weight_decay, schedule_kind, kl_or_null, kl_scale,
+                          kl_threshold, min_lr, max_lr, lr_multiplier, stats_out_or_null, skip_flag_or_null, guard_record,
+                          num_layers, weights, in_features, out_features, planes, stream);
 }
 
 }  // extern "C"

@@ -856,7 +856,9 @@ long long rlg_mlp_dw_plan(int rows, int out_features, int in_features, int targe
 
 // All layers in one launch.  Arrays are indexed by layer; plans from rlg_mlp_dw_plan.  dz [rows, No]
 // and x [rows, Mi] are contiguous (row stride = width).
-static int dw_launch_impl(int num_layers, const float* const* dz, const float* const* x, float* const* partial,
+// form: kDwExact / kDwBf16 / kDwF16, or -1 = the library's choice (the fp16 form when the launch has its operands' maxima,
+// else what RLG_DW_BF16 says)
+static int dw_launch_impl(int form, int num_layers, const float* const* dz, const float* const* x, float* const* partial,
                           float* const* grad, const int* out_features, const int* in_features,
                           const int* plans4, int rows, int num_colsums, const double* const* colsum_partials,
                           const int* colsum_blocks, const int* colsum_cols, float* const* colsum_out,
@@ -864,7 +866,7 @@ static int dw_launch_impl(int num_layers, const float* const* dz, const float* c
                           long long* step_counter, int* finalize_blocks_out, void* stream) {
   using namespace rlg;
   if (num_layers <= 0 || num_layers > kDwMaxLayers || rows <= 0 || num_colsums < 0 ||
-      num_colsums > kDwMaxLayers)
+      num_colsums > kDwMaxLayers || form < -1 || form > kDwF16)
     return static_cast<int>(hipErrorInvalidValue);
   DwArgs args;
   args.num_layers = num_layers;
@@ -882,7 +884,9 @@ static int dw_launch_impl(int num_layers, const float* const* dz, const float* c
   const char* eb = std::getenv("RLG_DW_F16_AMAX_X");
   const float host_amax_dz = ea ? static_cast<float>(std::atof(ea)) : 0.0f;
   const float host_amax_x = eb ? static_cast<float>(std::atof(eb)) : 0.0f;
-  const bool f16 = dw_f16_products() && (amax != nullptr || (ea != nullptr && eb != nullptr));
+  const bool have_maxima = amax != nullptr || (ea != nullptr && eb != nullptr);
+  if (form == kDwF16 && !have_maxima) return static_cast<int>(hipErrorInvalidValue);   // (that form scales by them)
+  if (form < 0) form = (dw_f16_products() && have_maxima) ? kDwF16 : (dw_split_products() ? kDwBf16 : kDwExact);
   int blocks = 0, fin_blocks = 0;
   for (int l = 0; l < num_layers; ++l) {
     DwLayer& L = args.layer[l];
@@ -930,8 +934,8 @@ static int dw_launch_impl(int num_layers, const float* const* dz, const float* c
   }
   const int total_vb = lf.num_blocks + cs_blocks + fin_blocks;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (f16) hipLaunchKernelGGL(mlp_dw_f16x3_kernel, dim3(blocks), dim3(256), 0, st, args);
-  else if (dw_split_products()) hipLaunchKernelGGL(mlp_dw_bf16x6_kernel, dim3(blocks), dim3(256), 0, st, args);
+  if (form == kDwF16) hipLaunchKernelGGL(mlp_dw_f16x3_kernel, dim3(blocks), dim3(256), 0, st, args);
+  else if (form == kDwBf16) hipLaunchKernelGGL(mlp_dw_bf16x6_kernel, dim3(blocks), dim3(256), 0, st, args);
   else hipLaunchKernelGGL(mlp_dw_kernel, dim3(blocks), dim3(256), 0, st, args);
   if (finalize_blocks_out) *finalize_blocks_out = total_vb;
   NormItem nrm = {norm_partials, norm_partials ? step_counter : nullptr, grad_scale};
@@ -965,7 +969,20 @@ int rlg_mlp_dw_launch(int num_layers, const float* const* dz, const float* const
                       const int* colsum_blocks, const int* colsum_cols, float* const* colsum_out,
                       const rlg_loss_finalize_desc* loss_finalize, double* norm_partials, float grad_scale,
                       long long* step_counter, int* finalize_blocks_out, void* stream) {
-  return dw_launch_impl(num_layers, dz, x, partial, grad, out_features, in_features, plans4, rows, num_colsums,
+  return dw_launch_impl(-1, num_layers, dz, x, partial, grad, out_features, in_features, plans4, rows, num_colsums,
+                        colsum_partials, colsum_blocks, colsum_cols, colsum_out, loss_finalize, norm_partials, grad_scale,
+                        step_counter, finalize_blocks_out, stream);
+}
+
+// rlg_mlp_dw_launch with the product form of THIS launch: 0 exact f32, 1 bf16 planes, 2 fp16 planes (needs the maxima of
+// rlg_mlp_dw_gradient_maxima), -1 the library's choice
+int rlg_mlp_dw_launch_form(int form, int num_layers, const float* const* dz, const float* const* x, float* const* partial,
+                           float* const* grad, const int* out_features, const int* in_features,
+                           const int* plans4, int rows, int num_colsums, const double* const* colsum_partials,
+                           const int* colsum_blocks, const int* colsum_cols, float* const* colsum_out,
+                           const rlg_loss_finalize_desc* loss_finalize, double* norm_partials, float grad_scale,
+                           long long* step_counter, int* finalize_blocks_out, void* stream) {
+  return dw_launch_impl(form, num_layers, dz, x, partial, grad, out_features, in_features, plans4, rows, num_colsums,
                         colsum_partials, colsum_blocks, colsum_cols, colsum_out, loss_finalize, norm_partials, grad_scale,
                         step_counter, finalize_blocks_out, stream);
 }

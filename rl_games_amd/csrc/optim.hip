@@ -52,6 +52,7 @@ __global__ __launch_bounds__(kOptBlock) void grad_sumsq_kernel(const float* __re
 __global__ __launch_bounds__(kOptBlock) void adam_step_kernel(AdamArgs a) {
   __shared__ float sh_clip;
   __shared__ float sh_norm;
+  __shared__ int sh_trip;
   __shared__ double scratch[kOptBlock / kWave];
   const long long n4 = a.n >> 2;
   const long long t = static_cast<long long>(blockIdx.x) * kOptBlock + threadIdx.x;
@@ -70,7 +71,7 @@ __global__ __launch_bounds__(kOptBlock) void adam_step_kernel(AdamArgs a) {
     m4[0] = a.exp_avg[tail];
     v4[0] = a.exp_avg_sq[tail];
   }
-  const bool skip = a.skip_flag != nullptr && *a.skip_flag != 0u;
+  const bool flagged = (a.skip_flag != nullptr && *a.skip_flag != 0u) || (a.guard != nullptr && a.guard[0] != 0u);
   const long long step = *a.step_counter;
   const int cur = static_cast<int>((step - 1) & 1);
   const double lr = a.lr_slots[cur];
@@ -100,8 +101,12 @@ __global__ __launch_bounds__(kOptBlock) void adam_step_kernel(AdamArgs a) {
     }
     sh_clip = coef;
     sh_norm = total_norm;
+    const bool trip = adam_guard_trips(a, total_norm);
+    sh_trip = trip ? 1 : 0;
+    if (trip && blockIdx.x == 0) adam_guard_record(a, step);
   }
   __syncthreads();
+  const bool skip = flagged || sh_trip != 0;
   const float clip = sh_clip;
   const AdamScalars k = adam_scalars(a, step, lr);
 #ifdef RLG_ADAM_TRACE
@@ -184,13 +189,14 @@ int rlg_grad_sumsq(const float* grads, long long n, float grad_scale, double* pa
   RLG_RETURN_LAUNCH_STATUS();
 }
 
-int rlg_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long long n,
-                  const double* norm_partials_or_null, int norm_blocks, float grad_scale,
-                  float max_norm, double* lr_slots, const long long* step_counter, double beta1,
-                  double beta2, double eps, double weight_decay, int schedule_kind,
-                  const float* kl_or_null, float kl_scale, double kl_threshold, double min_lr,
-                  double max_lr, double lr_multiplier, float* stats_out_or_null,
-                  const unsigned* skip_flag_or_null, void* stream) {
+// the launcher of rlg_adam_step and rlg_adam_step_guarded (guard_or_null: AdamArgs::guard)
+static int adam_step_launch(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long long n,
+                            const double* norm_partials_or_null, int norm_blocks, float grad_scale,
+                            float max_norm, double* lr_slots, const long long* step_counter, double beta1,
+                            double beta2, double eps, double weight_decay, int schedule_kind,
+                            const float* kl_or_null, float kl_scale, double kl_threshold, double min_lr,
+                            double max_lr, double lr_multiplier, float* stats_out_or_null,
+                            const unsigned* skip_flag_or_null, unsigned* guard_or_null, void* stream) {
   using namespace rlg;
   if (n <= 0 || !step_counter) return static_cast<int>(hipErrorInvalidValue);
   if (schedule_kind == 1 && !kl_or_null) return static_cast<int>(hipErrorInvalidValue);
@@ -219,6 +225,7 @@ int rlg_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq
   a.lr_multiplier = lr_multiplier;
   a.stats_out = stats_out_or_null;
   a.skip_flag = skip_flag_or_null;
+  a.guard = guard_or_null;
   RLG_ADAM_TRACE_FILL(a);
   // one thread per group of 4 parameters + one per tail element (the arenas are 16-byte aligned: torch allocations)
   if ((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grads) | reinterpret_cast<uintptr_t>(exp_avg) |
@@ -229,6 +236,35 @@ int rlg_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq
   hipLaunchKernelGGL(adam_step_kernel, dim3(static_cast<int>(grid < 1 ? 1 : grid)), dim3(kOptBlock), 0,
                      static_cast<hipStream_t>(stream), a);
   RLG_RETURN_LAUNCH_STATUS();
+}
+
+int rlg_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long long n,
+                  const double* norm_partials_or_null, int norm_blocks, float grad_scale,
+                  float max_norm, double* lr_slots, const long long* step_counter, double beta1,
+                  double beta2, double eps, double weight_decay, int schedule_kind,
+                  const float* kl_or_null, float kl_scale, double kl_threshold, double min_lr,
+                  double max_lr, double lr_multiplier, float* stats_out_or_null,
+                  const unsigned* skip_flag_or_null, void* stream) {
+  return adam_step_launch(params, grads, exp_avg, exp_avg_sq, n, norm_partials_or_null, norm_blocks, grad_scale, max_norm,
+                          lr_slots, step_counter, beta1, beta2, eps, weight_decay, schedule_kind, kl_or_null, kl_scale,
+                          kl_threshold, min_lr, max_lr, lr_multiplier, stats_out_or_null, skip_flag_or_null, nullptr, stream);
+}
+
+// rlg_adam_step under a range-guard record (csrc/range_guard.hip; optim_common.hpp AdamArgs::guard)
+int rlg_adam_step_guarded(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long long n,
+                          const double* norm_partials_or_null, int norm_blocks, float grad_scale,
+                          float max_norm, double* lr_slots, const long long* step_counter, double beta1,
+                          double beta2, double eps, double weight_decay, int schedule_kind,
+                          const float* kl_or_null, float kl_scale, double kl_threshold, double min_lr,
+                          double max_lr, double lr_multiplier, float* stats_out_or_null,
+                          const unsigned* skip_flag_or_null, unsigned* guard_record, void* stream) {
+  // (the guard watches the gradient norm: without the partials it would watch nothing)
+  if (guard_record == nullptr || norm_partials_or_null == nullptr || norm_blocks <= 0)
+    return static_cast<int>(hipErrorInvalidValue);
+  return adam_step_launch(params, grads, exp_avg, exp_avg_sq, n, norm_partials_or_null, norm_blocks, grad_scale, max_norm,
+                          lr_slots, step_counter, beta1, beta2, eps, weight_decay, schedule_kind, kl_or_null, kl_scale,
+                          kl_threshold, min_lr, max_lr, lr_multiplier, stats_out_or_null, skip_flag_or_null, guard_record,
+                          stream);
 }
 
 }  // extern "C"

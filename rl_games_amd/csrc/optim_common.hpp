@@ -3,6 +3,7 @@
 #pragma once
 
 #include "rlg_device.hpp"
+#include "rlg_hip.h"
 
 namespace rlg {
 
@@ -27,6 +28,9 @@ struct AdamArgs {
   float* stats_out;        // [4]: total_norm, clip_coef, lr used, lr next
   const unsigned* skip_flag;  // device word or nullptr; non-zero: the gradients are invalid (a failed in-graph
                               // all-reduce) - nothing is updated, the learning rate is carried over unchanged
+  unsigned* guard;         // range-guard record (csrc/range_guard.hip: [0] tag, 0 = clear, [1] index) or nullptr.  With a
+                           // record the launch is skipped as under skip_flag when the record is set or the total gradient
+                           // norm is not finite, and block 0 then records (RLG_GUARD_TAG_ADAM, step) in a clear record
 #ifdef RLG_ADAM_TRACE
   unsigned long long* trace_rows;   // diagnostic builds only (tools/exp/build_trace_libs.sh): see adam_trace.hpp
   int trace_cap, trace_flags;
@@ -73,6 +77,20 @@ __device__ __forceinline__ void adam_update(const AdamArgs& a, const AdamScalars
 __device__ __forceinline__ float adam_clip_coef(float max_norm, float total_norm) {
   const float coef = fminf(max_norm / (total_norm + 1e-6f), 1.0f);
   return total_norm != total_norm ? total_norm : coef;
+}
+// Guarded launches (AdamArgs::guard).  Every workgroup computes the same norm, so all of them take the same decision; the
+// record is read in front of the norm and written by block 0 only when the norm trips - a workgroup that already sees
+// block 0's word skips, as it would have on the norm.  An infinite norm trips as well: without a record its clip
+// coefficient is 0 and only the infinite gradients turn into NaN; a guarded run drops the whole step instead.
+__device__ __forceinline__ bool adam_guard_trips(const AdamArgs& a, float total_norm) {
+  return a.guard != nullptr && !(fabsf(total_norm) <= 3.4028234663852886e38f);
+}
+__device__ __forceinline__ void adam_guard_record(const AdamArgs& a, long long step) {
+  if (a.guard[0] == 0u) {
+    a.guard[1] = static_cast<unsigned>(step);
+    __threadfence();
+    a.guard[0] = static_cast<unsigned>(RLG_GUARD_TAG_ADAM);
+  }
 }
 // AdaptiveScheduler.update in python-float arithmetic (schedulers.py:27-33) + the statistics row; one thread
 __device__ __forceinline__ void adam_finish(const AdamArgs& a, int cur, double lr, bool skip, float total_norm, float clip) {

@@ -13,6 +13,8 @@ arenas created once, so
 `state_dict()` / `load_state_dict()` use torch.optim.Adam's format, so the 'optimizer' entry
 of a checkpoint (a2c_common.py:829, :862) is interchangeable with the reference's.
 """
+import functools
+
 import torch
 
 from . import ops
@@ -99,6 +101,9 @@ class FlatAdam(FlatArena):
         self.lr_slots = torch.tensor([float(lr), float(lr)], dtype=torch.float64, device=dev)
         self.norm_partials = torch.zeros(ops.grad_norm_blocks(self.numel), dtype=torch.float64, device=dev)
         self.stats = torch.zeros(4, dtype=torch.float32, device=dev)
+        # range-guard record (ops.guard_record) or None: with one, every step is the guarded launch - skipped, and the
+        # record set, when the gradient norm is not finite; skipped while the record is set (csrc/optim_common.hpp)
+        self.guard = None
         self.param_groups = [{'params': self.params, 'lr': float(lr), 'betas': betas, 'eps': eps,
                               'weight_decay': weight_decay}]
 
@@ -139,7 +144,10 @@ class FlatAdam(FlatArena):
         address of the in-graph all-reduce's error word (IpcAllReduce.error_word): a step behind a failed
         collective leaves parameters, moments and learning rate untouched.  pack: an ops.MlpChain whose weights live
         in this arena - the launch also writes the chain's bf16 weight planes for the new weights (one launch instead of
-        Adam + pack; csrc/mlp_chain_bx.hip adam_pack_kernel)."""
+        Adam + pack; csrc/mlp_chain_bx.hip adam_pack_kernel).
+        With `guard` set every step is the guarded launch.  It needs the gradient norm, so with max_norm None the step
+        hands the norm partials over under a threshold of +Inf: the update is the same bits, but `stats` [0] and [1]
+        then hold the norm and 1.0 where an unarmed step without truncation leaves 0 and 1."""
         self.step_count += 1
         self.weights_version += 1
         if norm_ready is None:
@@ -154,12 +162,20 @@ class FlatAdam(FlatArena):
             kind = 1
             kw = dict(kl_threshold=schedule['kl_threshold'], min_lr=schedule['min_lr'],
                       max_lr=schedule['max_lr'], lr_multiplier=schedule['lr_multiplier'])
-        ops.adam_step(self.flat_params, self.grads, self.exp_avg, self.exp_avg_sq, partials,
-                      grad_scale, 0.0 if max_norm is None else max_norm, self.lr_slots,
-                      self.step_counter, betas=self.betas, eps=self.eps,
-                      weight_decay=self.weight_decay, schedule_kind=kind,
-                      kl=self.kl_slot if kind else None, kl_scale=kl_scale, stats_out=self.stats,
-                      skip_flag=skip_flag, pack=None if pack is None else pack.adam_pack_target(), **kw)
+        launch = ops.adam_step
+        if self.guard is not None:
+            launch = functools.partial(ops.adam_step_guarded, self.guard)
+            if max_norm is None:
+                # the guard watches the gradient norm: hand it over under a threshold that never clips (coefficient
+                # min(inf / (norm + 1e-6), 1) = 1, and g * 1 is g)
+                partials = self.norm_partials if norm_ready is None else norm_ready[0][:norm_ready[1]]
+                max_norm = float('inf')
+        launch(self.flat_params, self.grads, self.exp_avg, self.exp_avg_sq, partials,
+               grad_scale, 0.0 if max_norm is None else max_norm, self.lr_slots,
+               self.step_counter, betas=self.betas, eps=self.eps,
+               weight_decay=self.weight_decay, schedule_kind=kind,
+               kl=self.kl_slot if kind else None, kl_scale=kl_scale, stats_out=self.stats,
+               skip_flag=skip_flag, pack=None if pack is None else pack.adam_pack_target(), **kw)
         if pack is not None:
             pack.mark_planes(self.weights_token())
 

@@ -10,7 +10,7 @@ import os
 
 import torch
 
-from . import _lib
+from . import _lib, range_guard
 
 F32 = torch.float32
 F64 = torch.float64
@@ -701,6 +701,28 @@ def adam_step(params, grads, exp_avg, exp_avg_sq, norm_partials, grad_scale, max
     """skip_flag: device address (int) of the in-graph all-reduce's error word, or None.
     pack = MlpChain.adam_pack_target() (n, weights, in, out, planes address): the launch also leaves the chain's
     weight planes for the new weights (rlg_adam_step_pack, csrc/mlp_chain_bx.hip)."""
+    _adam_launch(None, params, grads, exp_avg, exp_avg_sq, norm_partials, grad_scale, max_norm, lr_slots, step_counter,
+                 betas, eps, weight_decay, schedule_kind, kl, kl_scale, kl_threshold, min_lr, max_lr, lr_multiplier,
+                 stats_out, skip_flag, pack)
+
+
+def adam_step_guarded(guard, params, grads, exp_avg, exp_avg_sq, norm_partials, grad_scale, max_norm, lr_slots,
+                      step_counter, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, schedule_kind=0,
+                      kl=None, kl_scale=1.0, kl_threshold=0.008, min_lr=1e-6, max_lr=1e-2,
+                      lr_multiplier=1.5, stats_out=None, skip_flag=None, pack=None):
+    """adam_step under the range-guard record `guard` (guard_record()): the launch is skipped as under skip_flag when the
+    record is set or the total gradient norm is not finite, and a clear record then becomes (GUARD_TAG_ADAM, step) -
+    rlg_adam_step_guarded / rlg_adam_pack_guarded."""
+    if guard is None:
+        raise ValueError('adam_step_guarded needs a guard record (ops.guard_record)')
+    _adam_launch(guard, params, grads, exp_avg, exp_avg_sq, norm_partials, grad_scale, max_norm, lr_slots, step_counter,
+                 betas, eps, weight_decay, schedule_kind, kl, kl_scale, kl_threshold, min_lr, max_lr, lr_multiplier,
+                 stats_out, skip_flag, pack)
+
+
+def _adam_launch(guard, params, grads, exp_avg, exp_avg_sq, norm_partials, grad_scale, max_norm, lr_slots, step_counter,
+                 betas, eps, weight_decay, schedule_kind, kl, kl_scale, kl_threshold, min_lr, max_lr, lr_multiplier,
+                 stats_out, skip_flag, pack):
     lib = _lib.load()
     args = (
         _need(params, F32, 'params'), _need(grads, F32, 'grads'), _need(exp_avg, F32, 'exp_avg'),
@@ -711,11 +733,56 @@ def adam_step(params, grads, exp_avg, exp_avg_sq, norm_partials, grad_scale, max
         float(betas[0]), float(betas[1]), float(eps), float(weight_decay), schedule_kind,
         _opt(kl, F32, 'kl'), float(np.float32(kl_scale)), float(kl_threshold), float(min_lr),
         float(max_lr), float(lr_multiplier), _opt(stats_out, F32, 'stats_out'), skip_flag)
+    if guard is not None:
+        args = args + (_guard_ptr(guard),)
+    names = ('rlg_adam_step', 'rlg_adam_step_pack') if guard is None else ('rlg_adam_step_guarded', 'rlg_adam_pack_guarded')
     if pack is not None:
         n, w, ins, outs, planes = pack
-        _lib.check(lib.rlg_adam_step_pack(*args, n, w, ins, outs, planes, _stream(params)), 'rlg_adam_step_pack')
+        _lib.check(getattr(lib, names[1])(*args, n, w, ins, outs, planes, _stream(params)), names[1])
     else:
-        _lib.check(lib.rlg_adam_step(*args, _stream(params)), 'rlg_adam_step')
+        _lib.check(getattr(lib, names[0])(*args, _stream(params)), names[0])
+
+
+# ------------------------------------------------------------------ range guard of the split-fp16 products
+
+GUARD_TAG_ADAM = range_guard.TAG_ADAM            # RLG_GUARD_TAG_ADAM (include/rlg_hip.h)
+GUARD_MAX_ARRAYS = 8
+
+
+def guard_record(device):
+    """A clear range-guard record: 4 int32 words - [0] tag (0 = clear), [1] index, [2:4] the scan's own."""
+    return torch.zeros(4, dtype=torch.int32, device=device)
+
+
+def _guard_ptr(record):
+    _lib.require_gpu(record, 'guard record')
+    if record.dtype != torch.int32 or record.numel() != 4 or not record.is_contiguous():
+        raise ValueError('guard record: 4 contiguous int32 words expected (ops.guard_record)')
+    return record.data_ptr()
+
+
+def range_scan(arrays, record):
+    """arrays: up to 8 (fp32 tensor, tag != 0) pairs, contiguous, any 4-byte alignment.  One launch; on a non-finite value
+    record[0:2] = (tag of the first array in this order that holds one, smallest offending flat index in it) unless
+    the record is already set (csrc/range_guard.hip).  No host read here: read_guard().
+    Captured into a graph, the launch keeps the nonce of its capture: replayed over a record that an EARLIER REPLAY OF
+    ITSELF set, it takes that record for its own and keeps the better of the two hits instead of leaving it.  Read and
+    clear the record between replays (records set by other launches - other scans, optimiser steps - are safe)."""
+    n = len(arrays)
+    if n > GUARD_MAX_ARRAYS:
+        raise ValueError(f'range_scan: {n} arrays, one launch takes at most {GUARD_MAX_ARRAYS}')
+    P = ctypes.c_void_p * max(n, 1)
+    ptrs = P(*[_need(t, F32, 'scanned array') for t, _ in arrays])
+    counts = (ctypes.c_longlong * max(n, 1))(*[t.numel() for t, _ in arrays])
+    tags = (ctypes.c_int * max(n, 1))(*[int(tag) for _, tag in arrays])
+    _lib.check(_lib.load().rlg_range_scan(n, ptrs, counts, tags, _guard_ptr(record), _lib.stream_handle(record.device)),
+               'rlg_range_scan')
+
+
+def read_guard(record):
+    """(tag, index) of the record - ONE device-to-host copy; tag 0: clear."""
+    w = record[:2].tolist()
+    return int(w[0]) & 0xffffffff, int(w[1]) & 0xffffffff
 
 
 # ------------------------------------------------------------------ MLP forward / dX (MFMA, fused epilogues)
@@ -835,10 +902,17 @@ class MlpChain:
     """The whole MLP (hidden layers + the fused value|mu head as the last layer) as ONE forward and
     ONE backward launch (csrc/mlp_chain.hip).  `layers`: list of (weight [out, in], bias [out], act
     name) - tensors are referenced, not copied, so optimiser updates are seen.  Raises
-    NotImplementedError if the network does not fit the LDS even with one 16-row group."""
+    NotImplementedError if the network does not fit the LDS even with one 16-row group.
+    products: 'auto' - the library's choice per launch: fp16 plane products under fixed operand scales (the 64-row split
+    kernels, the lean 16-row kernels; |weight| < 1023, |hidden activation| < 4094) wherever they apply - or 'exact': every
+    launch of forward / backward / step takes the exact-f32-product kernels that split_products=False selects, which
+    have the full fp32 range.  The attribute may be set at any time; it is part of cache_state()."""
 
-    def __init__(self, layers, device, weights_version=None):
+    PRODUCTS = ('auto', 'exact')
+
+    def __init__(self, layers, device, weights_version=None, products='auto'):
         import ctypes
+        self._products = 'auto'
         self.n = n = len(layers)
         self.layers = layers
         self.device = device
@@ -884,6 +958,20 @@ class MlpChain:
         self._grad_maxima = None
         self._maxima_bwd = None
         self.maxima_rows_per_entry = 64       # 64: left by the 64-row split kernels, 16: by the lean 16-row kernels
+        self.products = products
+
+    @property
+    def products(self):
+        return self._products
+
+    @products.setter
+    def products(self, mode):
+        if mode not in self.PRODUCTS:
+            raise ValueError(f"MlpChain products: 'auto' or 'exact' expected, got {mode!r}")
+        if mode != self._products:
+            self._products = mode
+            self._forms_read = {}            # (answers of lean_used / split_products under the other mode)
+            self._maxima_bwd = None
 
     def _grad_maxima_buffer(self, rows, per=64):
         need = max(1024, -(-int(rows) // per))
@@ -916,24 +1004,26 @@ class MlpChain:
         (HIP-graph capture): taken in front of the capture, put back behind it (restore_cache_state), so that a pack
         launch that was only recorded never counts as done.  The persistent plane / fragment buffers are allocated HERE
         if they are not yet: a tensor first created inside torch.cuda.graph would live in the graph's private pool and
-        dangle behind a capture that fails and is discarded."""
-        if self._lean and self._frags is None and self._frag_bytes[0] >= 0:
+        dangle behind a capture that fails and is discarded.  (Exact products read neither.)"""
+        exact = self._products == 'exact'
+        if not exact and self._lean and self._frags is None and self._frag_bytes[0] >= 0:
             self._frag_buffer()
-        if self._planes is None:
+        if not exact and self._planes is None:
             try:
                 self._plane_buffer()
             except ValueError:
                 pass                      # (a network the split-product kernels do not take: they never ask for planes)
-        return (self._planes_fresh, self._planes_for, self._frags_for, self._planes_packed_once)
+        return (self._planes_fresh, self._planes_for, self._frags_for, self._planes_packed_once, self._products)
 
     def restore_cache_state(self, state):
-        self._planes_fresh, self._planes_for, self._frags_for, self._planes_packed_once = state
+        self._planes_fresh, self._planes_for, self._frags_for, self._planes_packed_once = state[:4]
+        self.products = state[4]
 
     # ---- fragments of the lean 16-row kernels (fp16 planes; the buffer is typed fp32 for its size only)
     def lean_used(self, rows, direction, requested=0):
         """True when the launch of this direction runs the lean 16-row kernel for `rows` rows (16-row workgroups, exact
         products; the backward additionally needs 16-byte aligned H / dZ rows, checked at its launch)."""
-        if not self._lean or (direction == 1 and self._frag_bytes[1] < 0):
+        if not self._lean or self._products == 'exact' or (direction == 1 and self._frag_bytes[1] < 0):
             return False
         return self.groups(rows, direction, requested) == 1 and not self.split_products(rows, direction, requested)
 
@@ -1005,7 +1095,7 @@ class MlpChain:
     def adam_pack_target(self):
         """(n, weights, in, out, planes address) for ops.adam_step(pack=...), or None when this network has no use for
         planes / no version source.  The first call packs the whole buffer once (the fragments' zero padding)."""
-        if self._weights_version is None or self.n < 1:
+        if self._weights_version is None or self.n < 1 or self._products == 'exact':
             return None
         if not self._planes_packed_once:
             self.pack_planes(2, self.layers[0][0])
@@ -1018,7 +1108,9 @@ class MlpChain:
 
     def split_products(self, rows, direction, requested=0):
         """True when the launch of this kind (0 inference forward, 1 backward, 2 training forward) runs the split-product
-        kernel for `rows` rows."""
+        kernel for `rows` rows.  Never under products='exact'."""
+        if self._products == 'exact':
+            return False
         return bool(_lib.load().rlg_mlp_chain_bx_supported(self.n, self._in, self._out, int(rows),
                                                            self.groups(rows, direction, requested), int(direction)))
 
@@ -1109,6 +1201,8 @@ class MlpChain:
         >= 16,384 rows, csrc/mlp_chain_bx_fwd.hip), False = exact f32 products."""
         rows = x.shape[0]
         n = self.n
+        if self._products == 'exact':
+            split_products = False
         outs = list(act_out) if act_out is not None else [None] * (n - 1)
         fwd = self._forward_args(x, outs + [heads], rms, eps, xn_out, rms_fold)
         # A training forward also has the weights split for the backward launch that follows it: by the forward's own
@@ -1191,6 +1285,8 @@ class MlpChain:
         >= 16,384 rows, csrc/mlp_chain_bx.hip), False = exact f32 products."""
         rows = d_heads.shape[0]
         n = self.n
+        if self._products == 'exact':
+            split_products = False
         h = self._P(*([_need(t, F32, 'H', contiguous=False) for t in acts] + [None]))
         hl = self._L(*([t.stride(0) for t in acts] + [0]))
         dz, dl, bp = self._backward_args(dz_out, bias_partials)
@@ -1277,7 +1373,9 @@ class MlpDwPlan:
             n += 1 + (2 * loss_finalize.actions_num + 7) // 8
         return n
 
-    def launch(self, jobs, colsums=(), loss_finalize=None, norm=None, maxima=None):
+    FORMS = {None: -1, 'auto': -1, 'exact': 0, 'bf16': 1, 'fp16': 2}
+
+    def launch(self, jobs, colsums=(), loss_finalize=None, norm=None, maxima=None, form=None):
         """jobs: (dz, x, grad) per planned layer.  maxima = (MlpChain.gradient_maxima() [8, entries], layer of each job's
         dz, fixed scale of each job's x - SPLIT_SCALE_HIDDEN / SPLIT_SCALE_OBS_NORM): the launch runs on three fp16 plane
         products per fp32 product (csrc/split_f16.hpp), dz scaled by the power of two the largest entry over a wave's
@@ -1287,8 +1385,13 @@ class MlpDwPlan:
         norm = (partials fp64 [>= finalise blocks], grad_scale, step_counter int64 [1]): the finalise
         launch also leaves per-block sums of (g * grad_scale)^2 and advances the Adam step counter (what
         grad_sumsq does) - only meaningful when this launch writes every gradient of the arena.
+        form: the product form of THIS launch - None / 'auto' the library's choice as described (the environment's
+        RLG_DW_BF16 / RLG_DW_F16 are the defaults of that choice), 'exact' f32 products (the full fp32 range), 'bf16',
+        'fp16' (needs maxima; |x| times its scale must stay below 65,504) - rlg_mlp_dw_launch_form.
         Returns the number of finalise blocks (= valid entries of the norm partials)."""
         import ctypes
+        if form not in self.FORMS:
+            raise ValueError(f'weight-gradient form {form!r}: one of {sorted(k for k in self.FORMS if k)} or None')
         if len(jobs) != self.n:
             raise ValueError('job count does not match the plan')
         nc = len(colsums)
@@ -1322,15 +1425,17 @@ class MlpDwPlan:
             _lib.check(_lib.load().rlg_mlp_dw_gradient_maxima(
                 _need(entries, F32, 'gradient maxima'), int(entries.shape[1]), per, (ctypes.c_int * self.n)(*[int(v) for v in dzs]),
                 (ctypes.c_float * self.n)(*[float(v) for v in xscales]), self.n), 'rlg_mlp_dw_gradient_maxima')
-        _lib.check(_lib.load().rlg_mlp_dw_launch(self.n, self._dz, self._x, self._ws, self._grad, self._no,
-                                                 self._mi, self._plans, self.rows, nc, cs_part, cs_blocks,
-                                                 cs_cols, cs_out,
-                                                 None if loss_finalize is None else ctypes.addressof(loss_finalize),
-                                                 None if norm is None else _need(norm[0], F64, 'norm partials'),
-                                                 1.0 if norm is None else float(np.float32(norm[1])),
-                                                 None if norm is None else _need(norm[2], torch.int64, 'step_counter'),
-                                                 ctypes.byref(nfin), _lib.stream_handle(self._device)),
-                   'rlg_mlp_dw_launch')
+        args = (self.n, self._dz, self._x, self._ws, self._grad, self._no,
+                self._mi, self._plans, self.rows, nc, cs_part, cs_blocks, cs_cols, cs_out,
+                None if loss_finalize is None else ctypes.addressof(loss_finalize),
+                None if norm is None else _need(norm[0], F64, 'norm partials'),
+                1.0 if norm is None else float(np.float32(norm[1])),
+                None if norm is None else _need(norm[2], torch.int64, 'step_counter'),
+                ctypes.byref(nfin), _lib.stream_handle(self._device))
+        if self.FORMS[form] < 0:
+            _lib.check(_lib.load().rlg_mlp_dw_launch(*args), 'rlg_mlp_dw_launch')
+        else:
+            _lib.check(_lib.load().rlg_mlp_dw_launch_form(self.FORMS[form], *args), 'rlg_mlp_dw_launch_form')
         return nfin.value
 
 
