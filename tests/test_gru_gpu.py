@@ -43,13 +43,40 @@ def _reference(x, gru, h0, dones, T):
 
 
 def _inputs(S, T, I, H, with_dones):
+    """Seeded parameters (a generator of their own, seeded from the shape: a case's weights do not depend on what ran
+    before it), inputs, initial states, dones and d_out.  The dones are a 20 % draw in which sequence S // 2 is then
+    cleared (an episode that outlasts the window) and a reset is SET at t = 0 of sequence 0 and at t = T - 1 of
+    sequence 1: the three places where step_keep and the hprev / h_final stores differ from the middle of a sequence
+    are in every case, and asserted to be."""
     g = torch.Generator().manual_seed(S * 7 + T)
     gru32 = torch.nn.GRU(I, H, 1)
+    gw = torch.Generator().manual_seed(S * 7 + T + 1000 * H)
+    with torch.no_grad():
+        for p in gru32.parameters():            # torch.nn.GRU's own initialisation, from a seeded generator
+            p.uniform_(-H ** -0.5, H ** -0.5, generator=gw)
     x32 = torch.randn(S * T, I, generator=g)
     h0 = (0.5 * torch.randn(S, H, generator=g)).to(DEV)
-    dones = (torch.rand(S * T, generator=g) < 0.2).to(torch.uint8).to(DEV) if with_dones else None
+    dones = None
+    if with_dones:
+        d = (torch.rand(S * T, generator=g) < 0.2).to(torch.uint8).reshape(S, T)
+        d[S // 2] = 0
+        d[0, 0] = 1
+        if T > 1 and S > 1:
+            d[1, T - 1] = 1
+        assert d[:, 0].any() and d[:, T - 1].any() and (d.sum(1) == 0).any() and (d.sum(1) > 0).any()
+        dones = d.reshape(S * T).to(DEV)
     d_out = torch.randn(S * T, H, generator=g).to(DEV)
     return gru32, x32, h0, dones, d_out
+
+
+def _poison(*shape):
+    """An output buffer that starts as NaN: a row the kernel never stores cannot pass on stale memory."""
+    return torch.full(shape, float('nan'), device=DEV)
+
+
+def _no_poison_left(**buffers):
+    for name, b in buffers.items():
+        assert b is None or not torch.isnan(b).any(), f'NaN left in {name}'
 
 
 def _forward(ops, gru32, x, h0, dones, T, train=True):
@@ -57,17 +84,19 @@ def _forward(ops, gru32, x, h0, dones, T, train=True):
     w_ih, w_hh = gru32.weight_ih_l0.detach().to(DEV), gru32.weight_hh_l0.detach().to(DEV).contiguous()
     b_ih, b_hh = gru32.bias_ih_l0.detach().to(DEV), gru32.bias_hh_l0.detach().to(DEV)
     gates = torch.addmm(b_ih, x, w_ih.t())
-    out = torch.empty(S * T, H, device=DEV)
-    hn_all = torch.empty(S * T, H, device=DEV) if train else None
-    hprev = torch.empty(S * T, H, device=DEV) if train else None
-    hT = torch.empty(S, H, device=DEV)
+    out = _poison(S * T, H)
+    hn_all = _poison(S * T, H) if train else None
+    hprev = _poison(S * T, H) if train else None
+    hT = _poison(S, H)
     ops.gru_seq_forward(gates, w_hh, b_hh, h0, dones, out, hn_all, hprev, hT, seq_len=T)
+    _no_poison_left(gates=gates, out=out, hn_all=hn_all, hprev=hprev, hT=hT)
     return dict(gates=gates, out=out, hn_all=hn_all, hprev=hprev, hT=hT, w_ih=w_ih, w_hh=w_hh)
 
 
 def _backward(ops, r, dones, d_out, T):
-    d_gx, d_gh = torch.empty_like(r['gates']), torch.empty_like(r['gates'])
+    d_gx, d_gh = _poison(*r['gates'].shape), _poison(*r['gates'].shape)
     ops.gru_seq_backward(r['gates'], r['hn_all'], r['hprev'], dones, r['w_hh'], d_out, d_gx, d_gh, T)
+    _no_poison_left(d_gx=d_gx, d_gh=d_gh)
     return d_gx, d_gh
 
 
@@ -159,10 +188,11 @@ def test_gru_large_tiles_match_fp64_and_small_tiles(S, T, H):
     assert torch.equal(gx_full[:n * T], gx_part) and torch.equal(gh_full[:n * T], gh_part)
 
 
-@pytest.mark.parametrize('H', [64, 128])
+@pytest.mark.parametrize('H', [16, 32, 64, 128])
 def test_gru_rows_do_not_depend_on_tile_neighbours(H):
     """Sequences 0 - 4 of a 130-sequence launch (full tiles) and the same five alone (a ragged tile): bit-identical
-    rows, forward and backward."""
+    rows, forward and backward - at every width: 16 and 32 units split the tile's sequences over the threads in
+    another way (16 and 8 thread groups of one sequence each) than 64 (4 groups) and the 128-unit MFMA columns."""
     from rl_games_amd import ops
     S, T, I, n = 130, 8, 20, 5
     gru32, x32, h0, dones, d_out = _inputs(S, T, I, H, True)

@@ -63,23 +63,35 @@ def _inputs(S, T, I, H, with_dones):
     return lstm32, x32, h0, c0, dones, d_out
 
 
+def _poison(*shape):
+    """An output buffer that starts as NaN: a row the kernel never stores cannot pass on stale memory."""
+    return torch.full(shape, float('nan'), device=DEV)
+
+
+def _no_poison_left(**buffers):
+    for name, b in buffers.items():
+        assert b is None or not torch.isnan(b).any(), f'NaN left in {name}'
+
+
 def _forward(ops, lstm32, x, h0, c0, dones, T, train=True, finals=True):
     S, H = h0.shape
     w_ih, w_hh = lstm32.weight_ih_l0.detach().to(DEV), lstm32.weight_hh_l0.detach().to(DEV).contiguous()
     bias = (lstm32.bias_ih_l0 + lstm32.bias_hh_l0).detach().to(DEV)
     gates = torch.addmm(bias, x, w_ih.t())
-    out = torch.empty(S * T, H, device=DEV)
-    c_all = torch.empty(S * T, H, device=DEV) if train else None
-    hprev = torch.empty(S * T, H, device=DEV) if train else None
-    hT = torch.empty(S, H, device=DEV) if finals else None
-    cT = torch.empty(S, H, device=DEV) if finals else None
+    out = _poison(S * T, H)
+    c_all = _poison(S * T, H) if train else None
+    hprev = _poison(S * T, H) if train else None
+    hT = _poison(S, H) if finals else None
+    cT = _poison(S, H) if finals else None
     ops.lstm_seq_forward(gates, w_hh, h0, c0, dones, out, c_all, hprev, hT, cT, seq_len=T)
+    _no_poison_left(gates=gates, out=out, c_all=c_all, hprev=hprev, hT=hT, cT=cT)
     return dict(gates=gates, out=out, c_all=c_all, hprev=hprev, hT=hT, cT=cT, w_ih=w_ih, w_hh=w_hh)
 
 
 def _backward(ops, r, c0, dones, d_out, T):
-    d_gates = torch.empty_like(r['gates'])
+    d_gates = _poison(*r['gates'].shape)
     ops.lstm_seq_backward(r['gates'], r['c_all'], c0, dones, r['w_hh'], d_out, d_gates, T)
+    _no_poison_left(d_gates=d_gates)
     return d_gates
 
 

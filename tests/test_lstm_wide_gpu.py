@@ -43,14 +43,41 @@ def _reference(x, lstm, h0, c0, dones, T):
 
 
 def _inputs(S, T, I, with_dones):
+    """Seeded parameters (a generator of their own, seeded from the shape: a case's weights do not depend on what ran
+    before it), inputs, initial states, dones and d_out.  The dones are a 20 % draw in which sequence S // 2 is then
+    cleared (an episode that outlasts the window) and a reset is SET at t = 0 of sequence 0 and at t = T - 1 of
+    sequence 1: the three places where step_keep and the hprev / h_final / c_final stores differ from the middle of a
+    sequence are in every case, and asserted to be."""
     g = torch.Generator().manual_seed(S * 7 + T)
     lstm32 = torch.nn.LSTM(I, H, 1)
+    gw = torch.Generator().manual_seed(S * 7 + T + 1000 * H)
+    with torch.no_grad():
+        for p in lstm32.parameters():           # torch.nn.LSTM's own initialisation, from a seeded generator
+            p.uniform_(-H ** -0.5, H ** -0.5, generator=gw)
     x32 = torch.randn(S * T, I, generator=g)
     h0 = (0.5 * torch.randn(S, H, generator=g)).to(DEV)
     c0 = (0.5 * torch.randn(S, H, generator=g)).to(DEV)
-    dones = (torch.rand(S * T, generator=g) < 0.2).to(torch.uint8).to(DEV) if with_dones else None
+    dones = None
+    if with_dones:
+        d = (torch.rand(S * T, generator=g) < 0.2).to(torch.uint8).reshape(S, T)
+        d[S // 2] = 0
+        d[0, 0] = 1
+        if T > 1 and S > 1:
+            d[1, T - 1] = 1
+        assert d[:, 0].any() and d[:, T - 1].any() and (d.sum(1) == 0).any() and (d.sum(1) > 0).any()
+        dones = d.reshape(S * T).to(DEV)
     d_out = torch.randn(S * T, H, generator=g).to(DEV)
     return lstm32, x32, h0, c0, dones, d_out
+
+
+def _poison(*shape):
+    """An output buffer that starts as NaN: a row the kernel never stores cannot pass on stale memory."""
+    return torch.full(shape, float('nan'), device=DEV)
+
+
+def _no_poison_left(**buffers):
+    for name, b in buffers.items():
+        assert b is None or not torch.isnan(b).any(), f'NaN left in {name}'
 
 
 def _forward(ops, lstm32, x, h0, c0, dones, T, train=True):
@@ -58,12 +85,20 @@ def _forward(ops, lstm32, x, h0, c0, dones, T, train=True):
     w_ih, w_hh = lstm32.weight_ih_l0.detach().to(DEV), lstm32.weight_hh_l0.detach().to(DEV).contiguous()
     bias = (lstm32.bias_ih_l0 + lstm32.bias_hh_l0).detach().to(DEV)
     gates = torch.addmm(bias, x, w_ih.t())
-    out = torch.empty(S * T, H, device=DEV)
-    c_all = torch.empty(S * T, H, device=DEV) if train else None
-    hprev = torch.empty(S * T, H, device=DEV) if train else None
-    hT, cT = torch.empty(S, H, device=DEV), torch.empty(S, H, device=DEV)
+    out = _poison(S * T, H)
+    c_all = _poison(S * T, H) if train else None
+    hprev = _poison(S * T, H) if train else None
+    hT, cT = _poison(S, H), _poison(S, H)
     ops.lstm_seq_forward(gates, w_hh, h0, c0, dones, out, c_all, hprev, hT, cT, seq_len=T)
+    _no_poison_left(gates=gates, out=out, c_all=c_all, hprev=hprev, hT=hT, cT=cT)
     return dict(gates=gates, out=out, c_all=c_all, hprev=hprev, hT=hT, cT=cT, w_ih=w_ih, w_hh=w_hh)
+
+
+def _backward(ops, r, c0, dones, d_out, T):
+    d_gates = _poison(*r['gates'].shape)
+    ops.lstm_seq_backward(r['gates'], r['c_all'], c0, dones, r['w_hh'], d_out, d_gates, T)
+    _no_poison_left(d_gates=d_gates)
+    return d_gates
 
 
 @pytest.mark.parametrize('S,T,I,with_dones', [(64, 16, 64, True), (37, 4, 12, True), (1024, 16, 64, True),
@@ -106,11 +141,8 @@ def test_wide_lstm_forward_backward_match_fp64(S, T, I, with_dones):
     for k in ('out', 'hT', 'cT', 'gates', 'c_all', 'hprev'):
         assert torch.equal(again[k], r[k]), k
 
-    d_gates = torch.empty(S * T, 4 * H, device=DEV)
-    ops.lstm_seq_backward(r['gates'], r['c_all'], c0, dones, r['w_hh'], d_out, d_gates, T)
-    d_gates2 = torch.empty(S * T, 4 * H, device=DEV)
-    ops.lstm_seq_backward(r['gates'], r['c_all'], c0, dones, r['w_hh'], d_out, d_gates2, T)
-    assert torch.equal(d_gates, d_gates2)
+    d_gates = _backward(ops, r, c0, dones, d_out, T)
+    assert torch.equal(d_gates, _backward(ops, r, c0, dones, d_out, T))
     dx = d_gates @ r['w_ih']
     dw_ih = d_gates.t() @ x
     dw_hh = d_gates.t() @ r['hprev']
@@ -142,11 +174,8 @@ def test_wide_lstm_rows_do_not_depend_on_tile_neighbours():
         assert torch.equal(full[k][:n * T], part[k]), k
     for k in ('hT', 'cT'):
         assert torch.equal(full[k][:n], part[k]), k
-    dg_full = torch.empty(S * T, 4 * H, device=DEV)
-    ops.lstm_seq_backward(full['gates'], full['c_all'], c0, dones, full['w_hh'], d_out, dg_full, T)
-    dg_part = torch.empty(n * T, 4 * H, device=DEV)
-    ops.lstm_seq_backward(part['gates'], part['c_all'], c0[:n].contiguous(), dones[:n * T].contiguous(), part['w_hh'],
-                          d_out[:n * T].contiguous(), dg_part, T)
+    dg_full = _backward(ops, full, c0, dones, d_out, T)
+    dg_part = _backward(ops, part, c0[:n].contiguous(), dones[:n * T].contiguous(), d_out[:n * T].contiguous(), T)
     assert torch.equal(dg_full[:n * T], dg_part)
 
 

@@ -136,6 +136,41 @@ def test_paired_backward_equals_two_single_launches(cell, H, S, T):
     assert not torch.equal(pair_a[first], pair_b[first])
 
 
+@pytest.mark.parametrize('H', WIDTHS)
+@pytest.mark.parametrize('cell', ['lstm', 'gru'])
+def test_paired_launch_keeps_a_non_finite_problem_to_itself(cell, H):
+    """Problem A carries a NaN in the whole gate-input row of sequence 3 at t = 2
+    (tests/test_rnn_edges_gpu.py::test_non_finite_sequence_stays_in_its_sequence), problem B is clean: B's outputs are
+    the bits of the single clean launch, forward and backward, and hold no NaN; A's sequence did turn NaN."""
+    from rl_games_amd import ops
+    S, T, bad = 37, 4, 3
+    pa, pb = _problem(cell, S, T, H, 5), _problem(cell, S, T, H, 6)
+    pa = dict(pa, gx=pa['gx'].clone())
+    pa['gx'][bad * T + 2] = float('nan')
+    pair_a, pair_b = _run_forward(ops, cell, pa, pb, S, T, H, ('train', 'train'), paired=True)
+    b_args, alone = _forward_args(cell, pb, S, T, H, 'train')
+    getattr(ops, f'{cell}_seq_forward')(**b_args, seq_len=T)
+    _assert_same(pair_b, alone, 'forward, problem B')
+    assert torch.isnan(pair_a['out'].reshape(S, T, H)[bad, 2:]).all()
+    assert not torch.isnan(pair_a['out'].reshape(S, T, H)[torch.arange(S, device=DEV) != bad]).any()
+
+    def args_of(p, k):
+        if cell == 'lstm':
+            outs = dict(d_gates=_poison(S * T, 4 * H))
+            return dict(outs, gates=k['gates'], c_all=k['c_all'], c0=p['c0'], dones=p['dones'], w_hh=p['w_hh'],
+                        d_out=p['d_out']), outs
+        outs = dict(d_gx=_poison(S * T, 3 * H), d_gh=_poison(S * T, 3 * H))
+        return dict(outs, gates=k['gates'], hn_all=k['hn_all'], hprev=k['hprev'], dones=p['dones'], w_hh=p['w_hh'],
+                    d_out=p['d_out']), outs
+
+    (a, _), (b, back_b) = args_of(pa, pair_a), args_of(pb, pair_b)
+    getattr(ops, f'{cell}_seq_backward_pair')(_positional(cell, 'backward', a), _positional(cell, 'backward', b),
+                                              seq_len=T)
+    b, back_alone = args_of(pb, alone)
+    getattr(ops, f'{cell}_seq_backward')(**b, seq_len=T)
+    _assert_same(back_b, back_alone, 'backward, problem B')
+
+
 def test_paired_wrappers_refuse_two_shapes_and_shared_outputs():
     from rl_games_amd import _lib, ops
     S, T, H = 5, 4, 32
