@@ -140,8 +140,11 @@ template <int B> __device__ __forceinline__ typename DwVec<B>::type dw_zero() { 
 // fp32 rounding: against fp64 the launch is as accurate as with exact f32 products and ~10x more accurate
 // than the library's fp32 GEMM (tools/exp/split_bf16_numerics.py, tools/exp/dw_bf16_check.py,
 // profiles/r2_dw_bf16x6.txt).
-// kSplit = false: exact f32 products (v_mfma_f32_16x16x4_f32).  kSplit = true: split-bf16 products, two
-// register sets of 32 rows.
+// kMode = kDwExact: exact f32 products (v_mfma_f32_16x16x4_f32), three register sets of 16 rows.  kDwBf16: split-bf16
+// products, two register sets of 32 rows.  kDwF16: three fp16 plane products per fp32 product (split_f16.hpp) on the same
+// two sets, dz scaled by the power of two that the largest gradient-maxima entry over the wave's rows asks for, x by
+// the layer's fixed scale, the accumulators un-scaled before the waves combine.
+// (tests/test_dw_schedule_cpu.py mirrors the schedule below on the host - keep it in step with any change here.)
 template <int BO, int BI, int kMode>
 __device__ __forceinline__ void dw_tile(const DwLayer& L, int rows, int o0, int i0, int z, float* lds, int amax_shift) {
   using VA = typename DwVec<BO>::type;
