@@ -27,7 +27,6 @@ import gc
 import os
 import time
 from datetime import datetime
-from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -43,6 +42,7 @@ from .minibatch import PPODataset
 from .normalizers import GeneralizedMovingStats, launch_stats
 from .policy import PolicyBuilder
 from .rollout_buffer import ExperienceBuffer
+from .weight_forms import ChainFormSet, _ChainForms
 
 
 def swap_and_flatten01(arr):
@@ -136,19 +136,6 @@ class DeviceAverageMeter:
         size_sum = old_size + size
         self._sizes[self._slot] = size_sum
         self.mean = (self.mean * old_size + new_mean * size) / size_sum
-
-
-class _ChainForms(NamedTuple):
-    """A fused chain (ops.MlpChain) that this agent's captured graphs read, and what keeps its derived weight forms
-    current.  launches: [(rows, kind), ...] the launches run on it (ops.MlpChain.forms_read); arena: the flat parameters
-    its weights live in.  actor: the actor's chain - the update graphs read it too, and the lean fragments are packed
-    behind every optimiser step.  planes: the split planes are brought up to date in front of a replay; False for the
-    actor's chains unless the Adam launch writes them (`adam_writes_planes`): their graphs pack the planes themselves."""
-    chain: ops.MlpChain
-    launches: tuple
-    arena: torch.Tensor
-    actor: bool = False
-    planes: bool = True
 
 
 class A2CAgent:
@@ -412,7 +399,8 @@ class A2CAgent:
             self.advantage_mean_std = GeneralizedMovingStats((1,), decay=momentum).to(dev)
         self.has_value_loss = self.use_experimental_cv or not self.has_central_value
         self._fused_rollout = self._fused_rollout_eligible()      # (with the critic in place)
-        self._form_chains = self._graph_chains()
+        self._form_chains = forms = ChainFormSet(self._graph_chains())
+        self._lean_chain, self._adam_pack_chain = forms.lean_chain, forms.adam_pack_chain
 
         # device-side episode meters (game_rewards / game_shaped_rewards / game_lengths)
         self._meter_sizes = torch.zeros(3, dtype=torch.int32, device=dev)
@@ -1080,7 +1068,7 @@ class A2CAgent:
         mb_valid = None
         fast = self._fast_rollout_ok()
         if fast:
-            self._forms_before_replay(rollout=True)
+            self._form_chains.before_replay(rollout=True)
         if self.mask_autoreset_rows:
             mb_valid = torch.ones((self.horizon_length, self.num_actors * self.num_agents),
                                   dtype=torch.float32, device=self.ppo_device)
@@ -1114,7 +1102,7 @@ class A2CAgent:
         rows = self.num_actors * self.num_agents
         fast = self._fast_rollout_ok()
         if fast:
-            self._forms_before_replay(rollout=True)
+            self._form_chains.before_replay(rollout=True)
         if self.mask_autoreset_rows:
             mb_valid = torch.ones((self.horizon_length, rows), dtype=torch.float32, device=self.ppo_device)
         for n in range(self.horizon_length):
@@ -1592,16 +1580,11 @@ class A2CAgent:
         # behind the in-graph all-reduce the step takes the collective's error word: a step whose gradients
         # are invalid (a peer never arrived) changes nothing
         skip = self._ipc_comm.error_word if (self.multi_gpu and self._ipc_comm) else None
-        # the lean 16-row kernels read the weights as fragments in each wave's consumption order: one pack launch behind the step writes them - inside
-        # the captured graphs too: no launch of this agent ever packs on demand.  (Round 4 had the Adam launch write them
-        # itself on one GPU, adam_frags_kernel; that kernel family left two ranks that SHARE a GPU one exp_avg_sq update
-        # apart and is gone - profiles/r5_two_rank_sync.txt.)
+        # the Adam launch writes the planes of adam_pack_chain, one pack launch behind it the lean 16-row kernels' fragments
+        # - inside the captured graphs too: no launch of this agent ever packs on demand
         opt.step(norm_ready=self._norm_ready, skip_flag=skip, pack=self._adam_pack_chain(), **self._step_arguments())
         self._norm_ready = None
-        lean = self._lean_chain()
-        if lean is not None:
-            lean.pack_frags(opt.flat_params)
-            lean.mark_frags(opt.weights_token())
+        self._form_chains.after_step(opt)
 
     def _graph_chains(self):
         """The fused chains that this agent's captured graphs read, in the order their forms are brought up to date: the
@@ -1625,36 +1608,6 @@ class A2CAgent:
             forms.append(_ChainForms(self._critic_rnn_engine().chain, ((self.num_actors, 0),),
                                      self.central_value_net.optimizer.flat_params))
         return forms
-
-    def _lean_chain(self):
-        """The actor's chain (the MLP's, or the trunk in front of a recurrent layer: the engine has one of the two) whose
-        launches run the lean 16-row kernels at one of this agent's sizes (csrc/mlp_chain_lean.hip: minibatches /
-        rollouts of < 16,384 rows on exact products) - its fragments are packed behind every optimiser step - or None."""
-        return next((f.chain for f in self._form_chains if f.actor and f.chain.forms_read(f.launches)[0]), None)
-
-    def _adam_pack_chain(self):
-        """The fused chain whose bf16 weight planes the Adam launch writes itself (csrc/mlp_chain_bx.hip,
-        adam_pack_kernel: one launch instead of Adam + pack per optimiser step, no pack in front of the rollout
-        forwards), or None: no fused chain, `adam_writes_planes` off, or none of this agent's launch sizes runs on planes."""
-        return next((f.chain for f in self._form_chains if f.actor and f.planes and f.chain.forms_read(f.launches)[1]),
-                    None)
-
-    def _forms_before_replay(self, rollout=False):
-        """A captured graph contains no pack launch: the derived forms of the chains it reads must belong to the weights
-        as they are (they do behind this agent's optimiser step; not behind a restore / broadcast / set_weights, nor
-        behind the critic's own steps).  The update graphs read the actor's chains, the rollout's step graphs all."""
-        for f in self._form_chains:
-            if rollout or f.actor:
-                f.chain.ensure_forms(f.launches, f.arena, planes=f.planes)
-
-    def _mark_forms_after_replay(self):
-        """Behind a replayed update graph: its last optimiser step left the actor's planes (Adam launch) and fragments
-        (pack launch) those of the weights as they are now."""
-        token = self.optimizer.weights_token()
-        if self._adam_pack_chain() is not None:
-            self._adam_pack_chain().mark_planes(token)
-        if self._lean_chain() is not None:
-            self._lean_chain().mark_frags(token)
 
     # ------------------------------------------------------------------ HIP graphs
     def _with_fold(self, mb_index, fn, *args):
@@ -1706,22 +1659,21 @@ class A2CAgent:
 
     def _capture(self, body):
         """Capture `body` into a HIP graph.  Capturing executes nothing on the device; host mirrors
-        that the body advances (the optimiser's step count) are restored afterwards, also when the
+        that the body advances (the optimiser's step count, the weight forms' stamps) are restored afterwards, also when the
         capture fails (GraphCaptureError: the update then continues on the eager path).  A rollout step
         advances none of them."""
         if self._graph_pool is None:
             self._graph_pool = torch.cuda.graph_pool_handle()
         g = torch.cuda.CUDAGraph()
         count0, version0 = self.optimizer.step_count, self.optimizer.weights_version
-        # ... and what the chains believe their planes / fragments hold: the body's pack launches are recorded, not run
-        cached0 = self._chain_cache_states()
         # No automatic garbage collection while the stream is capturing: a cycle that owns device objects of an
         # earlier graph (torch.cuda.graph collects once on entry, but the body allocates hundreds of Python objects)
         # would be finalised in the middle of the capture, and releasing device resources there aborts the process.
         gc_was_enabled = gc.isenabled()
         gc.disable()
         try:
-            with torch.cuda.graph(g, pool=self._graph_pool, capture_error_mode='thread_local'):
+            with self._form_chains.captured(), \
+                    torch.cuda.graph(g, pool=self._graph_pool, capture_error_mode='thread_local'):
                 body()
         except Exception as e:
             raise GraphCaptureError('HIP graph capture failed') from e
@@ -1729,33 +1681,26 @@ class A2CAgent:
             if gc_was_enabled:
                 gc.enable()
             self.optimizer.step_count, self.optimizer.weights_version = count0, version0
-            self._restore_chain_cache_states(cached0)
         return g
 
-    def _chain_cache_states(self):
-        return [(f.chain, f.chain.cache_state()) for f in self._form_chains]
-
-    @staticmethod
-    def _restore_chain_cache_states(states):
-        for c, state in states:
-            c.restore_cache_state(state)
+    def _drop_stale_graphs(self):
+        sig = self._graph_signature()
+        if sig != self._graph_sig:
+            self._graphs.clear()
+            self._graph_opt = self._graph_epoch = None
+            self._graph_sig = sig
 
     def _graph_minibatch(self, i):
         """Replay (capturing on first use) the forward/loss/backward graph of minibatch i, run the
         gradient all-reduce eagerly, then replay the (norm, Adam, lr) graph."""
-        sig = self._graph_signature()
-        if sig != self._graph_sig:
-            self._graphs.clear()
-            self._graph_opt = None
-            self._graph_epoch = None
-            self._graph_sig = sig
+        self._drop_stale_graphs()
         g = self._graphs.get(i)
         if g is None:
             item = self.dataset[i]
             g = self._graphs[i] = self._capture(lambda: self._with_fold(i, self._forward_loss_backward, item,
                                                                        self._graph_rows[i]))
             self._graph_norm_state = self._norm_ready      # what the captured launches will have produced
-        self._forms_before_replay()
+        self._form_chains.before_replay()
         if self._graph_opt is None:
             # Captured BEFORE anything of this minibatch runs (a failed capture then leaves minibatch i untouched
             # for the eager path), knowing which launch in front of it produces the gradient norm - the
@@ -1771,18 +1716,13 @@ class A2CAgent:
         self._norm_ready = None
         self._graph_opt.replay()
         self.optimizer.step_done()
-        self._mark_forms_after_replay()
+        self._form_chains.after_step(self.optimizer, packed=True)
 
     def _graph_mini_epoch(self, nmb):
         """Single-GPU runs with nothing to do on the host between minibatches (device-side or
         per-epoch lr schedule): ALL minibatches of a mini-epoch - forward, loss, backward, clip, Adam,
         lr update, nmb times - are one HIP graph, replayed once per mini-epoch."""
-        sig = self._graph_signature()
-        if sig != self._graph_sig:
-            self._graphs.clear()
-            self._graph_opt = None
-            self._graph_epoch = None
-            self._graph_sig = sig
+        self._drop_stale_graphs()
         if self._graph_epoch is None:
             def body():
                 for i in range(nmb):
@@ -1793,11 +1733,11 @@ class A2CAgent:
                 if self._fold_ready:
                     self.model.running_mean_std.fold_sync(nmb)
             self._graph_epoch = self._capture(body)
-        self._forms_before_replay()
+        self._form_chains.before_replay()
         self._graph_epoch.replay()
         self.optimizer.step_count += nmb
         self.optimizer.weights_version += nmb
-        self._mark_forms_after_replay()
+        self._form_chains.after_step(self.optimizer, packed=True)
 
     def _host_schedule(self, kl_value):
         lr, self.entropy_coef = self.scheduler.update(self._host_lr, self.entropy_coef, self.epoch_num,
@@ -1969,8 +1909,7 @@ class A2CAgent:
         """Every chain of the agent (and of its central value network) on `mode`, the weight-gradient launches on the
         matching form.  Captured graphs hold the other mode's launches: the update graphs go with the signature, the
         rollout's step graphs here, and the next epoch runs eagerly like the first."""
-        for f in self._form_chains:
-            f.chain.products = mode
+        self._form_chains.set_products(mode)
         for e in self._range_engines():
             e.weight_grads.form = 'exact' if mode == 'exact' else None
         if mode != self.chain_products:

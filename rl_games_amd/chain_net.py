@@ -23,7 +23,7 @@ RecurrentChainNet is the recurrent engine of the discrete agent and the central 
 product as one chain, then RnnStations, an optional layer norm and the heads.  RecurrentChainPair drives two of them
 - the separate actor / critic trunks of a continuous policy, each with its own RNN - with one paired sequence launch.  The
 agents' rollout graphs read these chains too; they hold no pack launch, so the agent brings each chain's weight fragments
-/ planes up to date in front of a replay along with its other chains (A2CAgent._forms_before_replay).
+/ planes up to date in front of a replay along with its other chains (weight_forms.ChainFormSet.before_replay).
 """
 import torch
 from torch import nn

@@ -28,9 +28,10 @@ import torch
 from torch import nn
 
 from . import ops
-from .agent import A2CAgent, _ChainForms
+from .agent import A2CAgent
 from .chain_net import ChainNet, RecurrentChainNet, arena_layout, rnn_cell_declined
 from .normalizers import launch_stats
+from .weight_forms import _ChainForms
 
 
 class DiscreteA2CAgent(A2CAgent):

@@ -34,7 +34,7 @@ class FlatArena:
         if not self.params:
             raise ValueError('no parameters')
         # bumped by everything in this package that changes parameter VALUES (optimiser steps, restores, broadcasts):
-        # derived copies of the weights (ops.MlpChain's bf16 planes) are valid for one value of it
+        # derived copies of the weights (ops.MlpChain's weight forms) are valid for one value of it
         self.weights_version = 0
         physical = list(layout) if layout is not None else self.params
         if sorted(id(p) for p in physical) != sorted(id(p) for p in self.params):
@@ -143,7 +143,7 @@ class FlatAdam(FlatArena):
         the device step counter (ops.MlpDwPlan.launch(norm=...)) - no grad_sumsq launch.  skip_flag: device
         address of the in-graph all-reduce's error word (IpcAllReduce.error_word): a step behind a failed
         collective leaves parameters, moments and learning rate untouched.  pack: an ops.MlpChain whose weights live
-        in this arena - the launch also writes the chain's bf16 weight planes for the new weights (one launch instead of
+        in this arena - the launch also writes the chain's fp16 weight planes for the new weights (one launch instead of
         Adam + pack; csrc/mlp_chain_bx.hip adam_pack_kernel).
         With `guard` set every step is the guarded launch.  It needs the gradient norm, so with max_norm None the step
         hands the norm partials over under a threshold of +Inf: the update is the same bits, but `stats` [0] and [1]
@@ -177,7 +177,7 @@ class FlatAdam(FlatArena):
                kl=self.kl_slot if kind else None, kl_scale=kl_scale, stats_out=self.stats,
                skip_flag=skip_flag, pack=None if pack is None else pack.adam_pack_target(), **kw)
         if pack is not None:
-            pack.mark_planes(self.weights_token())
+            pack.planes.mark(self.weights_token())
 
     def step_done(self):
         """Host mirrors after a replayed graph performed the step (the captured launches advance the device counter)."""

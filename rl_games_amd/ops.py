@@ -10,7 +10,7 @@ import os
 
 import torch
 
-from . import _lib, range_guard
+from . import _lib, range_guard, weight_forms
 
 F32 = torch.float32
 F64 = torch.float64
@@ -906,19 +906,15 @@ class MlpChain:
     products: 'auto' - the library's choice per launch: fp16 plane products under fixed operand scales (the 64-row split
     kernels, the lean 16-row kernels; |weight| < 1023, |hidden activation| < 4094) wherever they apply - or 'exact': every
     launch of forward / backward / step takes the exact-f32-product kernels that split_products=False selects, which
-    have the full fp32 range.  The attribute may be set at any time; it is part of cache_state()."""
+    have the full fp32 range.  The attribute may be set at any time; it is part of cache_state().
+    Derived weight copies (weight_forms.py), both fp16 plane fragments: `planes` (64-row split kernels), `frags` (lean)."""
 
     PRODUCTS = ('auto', 'exact')
 
     def __init__(self, layers, device, weights_version=None, products='auto'):
-        import ctypes
-        self._products = 'auto'
         self.n = n = len(layers)
         self.layers = layers
         self.device = device
-        # callable -> a value that changes whenever the referenced weights change (FlatArena.weights_token):
-        # planes packed by a training forward are re-used by backward() only for the SAME weights
-        self._weights_version = weights_version
         self.ins = [int(w.shape[1]) for w, _, _ in layers]
         self.outs = [int(w.shape[0]) for w, _, _ in layers]
         P, I, L = ctypes.c_void_p * n, ctypes.c_int * n, ctypes.c_longlong * n
@@ -929,7 +925,7 @@ class MlpChain:
         self._act = I(*[ACT_KINDS[a] for _, _, a in layers])
         lib = _lib.load()
         _lib.check(lib.rlg_mlp_chain_prepare(), 'rlg_mlp_chain_prepare')
-        self.max_groups = {}
+        max_groups = {}
         for direction in (0, 1):
             best = 0
             for g in (1, 2, 4):
@@ -937,28 +933,38 @@ class MlpChain:
                     best = g
             if best == 0 and (direction == 0 or n > 1):
                 raise NotImplementedError('MLP does not fit the LDS of the fused chain kernels')
-            self.max_groups[direction] = best
-        # lean 16-row kernels (csrc/mlp_chain_lean.hip, mlp_chain_fwd_lean_kernel / mlp_chain_bwd_lean_kernel): the weights as
-        # plane fragments in each wave's consumption order; RLG_CHAIN_LEAN=0 keeps the pipelined kernels
-        self._lean = os.environ.get('RLG_CHAIN_LEAN', '1') != '0'
-        self._frag_bytes = [int(lib.rlg_mlp_chain_frags_bytes(n, self._in, self._out, 0)),
-                            int(lib.rlg_mlp_chain_frags_bytes(n, self._in, self._out, 1)) if n > 1 else -1]
-        if self._frag_bytes[0] < 0:
-            self._lean = False
-        self._frags = None         # [forward fragments | backward fragments], fp32
-        self._frags_for = None     # weights version the fragments hold
-        self._planes = None        # bf16 plane fragments of the weights, both directions (csrc/mlp_chain_bx.hip)
-        self._bwd_offset = 0
-        self._planes_fresh = None  # (rows, weights version) of the training forward that packed the backward planes
-        self._planes_for = None    # weights version for which BOTH directions' planes are valid (optimiser-written or packed)
-        self._planes_packed_once = False
-        self._forms_read = {}      # forms_read() per launch list
+            max_groups[direction] = best
+        frag_bytes = [int(lib.rlg_mlp_chain_frags_bytes(n, self._in, self._out, 0)),
+                      int(lib.rlg_mlp_chain_frags_bytes(n, self._in, self._out, 1)) if n > 1 else -1]
+        # RLG_CHAIN_LEAN=0 keeps the pipelined kernels where the lean 16-row kernels would run
+        self._set_shape(max_groups, frag_bytes, os.environ.get('RLG_CHAIN_LEAN', '1') != '0', weights_version, products)
+
+    @classmethod
+    def _from_shape(cls, n, max_groups, frag_bytes, weights_version=None, products='auto', lean=True, device=None):
+        """Host-side tests: a chain of `n` layers from the library's answers about its shape.  It can launch nothing."""
+        c = cls.__new__(cls)
+        c.n, c.device, c._in, c._out = n, device, None, None
+        c._set_shape(max_groups, frag_bytes, lean, weights_version, products)
+        return c
+
+    def _set_shape(self, max_groups, frag_bytes, lean, weights_version, products):
+        self.max_groups = max_groups
+        self._frag_bytes = frag_bytes
+        self._lean = lean and frag_bytes[0] >= 0
+        # callable -> a value that changes whenever the weights do (FlatArena.weights_token): the forms' stamp
+        self._weights_version = weights_version
+        self.planes = weight_forms.PlanesForm(self._alloc_planes, self._launch_pack_planes, jobs=2 * self.n - 1)
+        self.frags = weight_forms.WeightForm(self._alloc_frags, self._launch_pack_frags)
         # split-fp16 backward: per 64-row workgroup the largest magnitude of every dZ tensor (csrc/bx_form.hpp), for the
         # weight-gradient launch that follows it; rows of the last backward that left them
-        self._grad_maxima = None
-        self._maxima_bwd = None
+        self._forms_read = {}
+        self._grad_maxima = self._maxima_bwd = None
         self.maxima_rows_per_entry = 64       # 64: left by the 64-row split kernels, 16: by the lean 16-row kernels
+        self._products = 'auto'
         self.products = products
+
+    _planes = property(lambda self: self.planes.buffer)       # (None until a launch has asked for them)
+    _frags = property(lambda self: self.frags.buffer)
 
     @property
     def products(self):
@@ -970,19 +976,15 @@ class MlpChain:
             raise ValueError(f"MlpChain products: 'auto' or 'exact' expected, got {mode!r}")
         if mode != self._products:
             self._products = mode
-            self._forms_read = {}            # (answers of lean_used / split_products under the other mode)
             self._maxima_bwd = None
 
-    def _grad_maxima_buffer(self, rows, per=64):
+    def _request_maxima(self, rows, per):
+        """The next backward / step launch leaves one gradient-maxima entry per `per`-row workgroup (64: split, 16: lean)."""
         need = max(1024, -(-int(rows) // per))
         if self._grad_maxima is None or self._grad_maxima.shape[1] < need:
             self._grad_maxima = torch.zeros(8, need, dtype=F32, device=self.device)
-        return self._grad_maxima
-
-    def _request_lean_maxima(self, rows):
-        """The lean 16-row backward / one-launch step leaves one gradient-maxima entry per 16-row workgroup."""
-        buf = self._grad_maxima_buffer(rows, 16)
-        _lib.load().rlg_mlp_chain_gradient_maxima(buf.data_ptr(), buf.shape[1])
+        self._maxima_bwd = None
+        _lib.load().rlg_mlp_chain_gradient_maxima(self._grad_maxima.data_ptr(), self._grad_maxima.shape[1])
 
     def gradient_maxima(self, rows):
         """[8, entries] fp32: row l = per 64-row workgroup the largest |dZ of layer l| of the backward of this step - when
@@ -992,160 +994,105 @@ class MlpChain:
             return self._grad_maxima
         return None
 
-    def invalidate_planes(self):
-        """The weights changed behind this object's back: backward() re-packs its planes (and the lean kernels'
-        fragments are packed again)."""
-        self._planes_fresh = None
-        self._planes_for = None
-        self._frags_for = None
+    def _route(self, rows, kind, groups=0, split_products=None):
+        """'lean' | 'split' | 'exact': the kernels for a launch of `kind` (0 inference forward, 1 backward, 2 training forward)
+        over `rows` rows - lean 16-row (they read `frags`), else split 64-row (`planes`), else exact f32 products (the
+        weights).  The PREFERENCE: the library may still decline a lean launch when issued (801); the exact one follows."""
+        if self._products == 'exact' or split_products is False:
+            return 'exact'
+        def split(requested):
+            return bool(_lib.load().rlg_mlp_chain_bx_supported(self.n, self._in, self._out, int(rows),
+                                                               self.groups(rows, kind, requested), int(kind)))
+        if (groups in (0, 1) and self._lean and (kind != 1 or self._frag_bytes[1] >= 0) and self.groups(rows, kind) == 1
+                and not split(0)):
+            return 'lean'
+        return 'split' if split(groups) else 'exact'
 
-    def cache_state(self):
-        """Host-side record of what the derived copies hold - for callers that issue launches WITHOUT running them
-        (HIP-graph capture): taken in front of the capture, put back behind it (restore_cache_state), so that a pack
-        launch that was only recorded never counts as done.  The persistent plane / fragment buffers are allocated HERE
-        if they are not yet: a tensor first created inside torch.cuda.graph would live in the graph's private pool and
-        dangle behind a capture that fails and is discarded.  (Exact products read neither.)"""
-        exact = self._products == 'exact'
-        if not exact and self._lean and self._frags is None and self._frag_bytes[0] >= 0:
-            self._frag_buffer()
-        if not exact and self._planes is None:
-            try:
-                self._plane_buffer()
-            except ValueError:
-                pass                      # (a network the split-product kernels do not take: they never ask for planes)
-        return (self._planes_fresh, self._planes_for, self._frags_for, self._planes_packed_once, self._products)
-
-    def restore_cache_state(self, state):
-        self._planes_fresh, self._planes_for, self._frags_for, self._planes_packed_once = state[:4]
-        self.products = state[4]
-
-    # ---- fragments of the lean 16-row kernels (fp16 planes; the buffer is typed fp32 for its size only)
     def lean_used(self, rows, direction, requested=0):
-        """True when the launch of this direction runs the lean 16-row kernel for `rows` rows (16-row workgroups, exact
-        products; the backward additionally needs 16-byte aligned H / dZ rows, checked at its launch)."""
-        if not self._lean or self._products == 'exact' or (direction == 1 and self._frag_bytes[1] < 0):
-            return False
-        return self.groups(rows, direction, requested) == 1 and not self.split_products(rows, direction, requested)
+        """The launch runs the lean 16-row kernel (split-fp16 products on the fragments), row alignment permitting."""
+        return self._route(rows, direction, requested) == 'lean'
 
-    def _frag_buffer(self):
-        if self._frags is None:
-            fb, bb = self._frag_bytes[0], max(self._frag_bytes[1], 0)
-            self._frags = torch.empty((fb + bb) // 4, dtype=F32, device=self.device)
-        return self._frags
-
-    def _frags_ptr(self, direction):
-        return self._frag_buffer().data_ptr() + (self._frag_bytes[0] if direction == 1 else 0)
-
-    def pack_frags(self, stream_of):
-        """Weights (+ biases) -> the fragments of both directions, one launch.  Behind every change of the weights:
-        forward() / backward() do it themselves unless frags_current(); an agent issues it behind its optimiser step."""
-        lib = _lib.load()
-        _lib.check(lib.rlg_mlp_chain_pack_frags_both(self.n, self._w, self._b, self._in, self._out, self._frags_ptr(0),
-                                                     self._frags_ptr(1) if self._frag_bytes[1] >= 0 else None,
-                                                     _stream(stream_of)), 'rlg_mlp_chain_pack_frags_both')
-
-    def frags_current(self):
-        v = self._version()
-        return v is not None and self._frags_for == v
-
-    def mark_frags(self, version):
-        self._frags_for = version
-
-    def ensure_frags(self, stream_of):
-        if not self.frags_current():
-            self.pack_frags(stream_of)
-            self._frags_for = self._version()
-
-    def planes_current(self):
-        """Both directions' planes belong to the weights as they are now (needs a weights-version source)."""
-        v = self._version()
-        return v is not None and self._planes_for == v
-
-    def mark_planes(self, version):
-        """The planes of both directions now hold the weights of `version` (FlatAdam.step(pack=...), or after a
-        graph replay whose last launch was that step)."""
-        self._planes_for = version
-
-    def ensure_planes(self, stream_of):
-        """Eager full pack unless the planes are current (in front of a graph replay that contains no pack launch)."""
-        if not self.planes_current():
-            self.pack_planes(2, stream_of)
-            self._planes_for = self._version()
+    def split_products(self, rows, direction, requested=0):
+        """The launch runs the 64-row split-product kernel.  Never under products='exact'."""
+        return self._route(rows, direction, requested) == 'split'
 
     def forms_read(self, launches):
-        """(fragments, planes): whether any of `launches` [(rows, kind), ...] (kinds as in split_products) runs the lean
-        16-row kernels, which read the fragments, or the split-product kernels, which read the planes."""
-        key = tuple(launches)
-        forms = self._forms_read.get(key)
-        if forms is None:
-            forms = self._forms_read[key] = (any(self.lean_used(r, k) for r, k in key),
-                                             any(self.split_products(r, k) for r, k in key))
-        return forms
+        """(fragments, planes): whether any of `launches` [(rows, kind), ...] reads them; kept per products mode."""
+        key = (self._products, tuple(launches))
+        if key not in self._forms_read:
+            routes = [self._route(r, k) for r, k in key[1]]
+            self._forms_read[key] = ('lean' in routes, 'split' in routes)
+        return self._forms_read[key]
 
-    def ensure_forms(self, launches, stream_of, planes=True):
-        """In front of a graph replay (a captured graph contains no pack launch): pack the derived forms that `launches`
-        read again if the weights changed since they were packed.  planes=False leaves the planes to the caller's
-        launches (they pack them themselves)."""
-        frags, split = self.forms_read(launches)
-        if split and planes:
-            self.ensure_planes(stream_of)
-        if frags:
-            self.ensure_frags(stream_of)
+    def weights_token(self):
+        return None if self._weights_version is None else self._weights_version()
+
+    def cache_state(self):
+        """What the forms hold, for callers that record launches WITHOUT running them (graph capture) and put it back behind
+        (restore_cache_state).  Allocates the buffers (exact products: none): one first made under torch.cuda.graph would
+        live in the graph's private pool and dangle behind a failed capture."""
+        if self._products != 'exact':
+            if self._lean:
+                self.frags.allocate()
+            try:
+                self.planes.allocate()
+            except ValueError:
+                pass                      # (a network the split-product kernels do not take: they never ask for planes)
+        p = self.planes
+        return weight_forms.ChainSnapshot(p.holds, self.frags.holds, p.fresh, p.packed_once, self._products)
+
+    def restore_cache_state(self, state):
+        self.planes.holds, self.planes.fresh, self.planes.packed_once = state.planes, state.fresh, state.packed_once
+        self.frags.holds, self.products = state.frags, state.products
+
+    def _alloc_frags(self):                   # [forward | backward fragments], typed fp32 for its size only
+        return torch.empty((self._frag_bytes[0] + max(self._frag_bytes[1], 0)) // 4, dtype=F32, device=self.device)
+
+    def _frags_ptr(self, direction):
+        return self.frags.allocate().data_ptr() + (self._frag_bytes[0] if direction == 1 else 0)
+
+    def _launch_pack_frags(self, stream_of):
+        bwd = self._frags_ptr(1) if self._frag_bytes[1] >= 0 else None
+        _lib.check(_lib.load().rlg_mlp_chain_pack_frags_both(self.n, self._w, self._b, self._in, self._out, self._frags_ptr(0),
+                                                             bwd, _stream(stream_of)), 'rlg_mlp_chain_pack_frags_both')
+
+    def _alloc_planes(self):
+        """ONE buffer for both directions: forward fragments at 0, backward fragments at _bwd_offset."""
+        lib = _lib.load()
+        nbytes = lib.rlg_mlp_chain_planes_bytes(self.n, self._in, self._out, 2)
+        off = lib.rlg_mlp_chain_planes_offset(self.n, self._in, self._out, 1)
+        if nbytes < 0 or off < 0:
+            raise ValueError('rlg_mlp_chain_planes_bytes: bad network')
+        self._bwd_offset = int(off)
+        self._fwd_bytes, self._bwd_bytes = (int(lib.rlg_mlp_chain_planes_bytes(self.n, self._in, self._out, d)) for d in (0, 1))
+        return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=self.device)
+
+    def _plane_buffer(self):
+        return self.planes.allocate()
+
+    def _planes_ptr(self, direction):
+        return self.planes.allocate().data_ptr() + (self._bwd_offset if direction == 1 else 0)
+
+    def _launch_pack_planes(self, direction, stream_of):
+        buf = self.planes.allocate()
+        view = (buf[:self._fwd_bytes], buf[self._bwd_offset:self._bwd_offset + self._bwd_bytes], buf)[direction]
+        if view.numel() > 0:
+            _lib.check(_lib.load().rlg_mlp_chain_pack_planes(self.n, self._w, self._in, self._out, int(direction),
+                                                             view.data_ptr(), _stream(stream_of)), 'rlg_mlp_chain_pack_planes')
+        return view
+
+    def pack_planes(self, direction, stream_of):
+        """Weights -> fp16 plane fragments (direction 0 forward operand, 1 backward, 2 both); returns that direction's
+        view (2: the whole buffer).  Stamps nothing: forward() / backward() pack for themselves unless planes.current()."""
+        return self.planes.pack(stream_of, direction)
 
     def adam_pack_target(self):
         """(n, weights, in, out, planes address) for ops.adam_step(pack=...), or None when this network has no use for
         planes / no version source.  The first call packs the whole buffer once (the fragments' zero padding)."""
         if self._weights_version is None or self.n < 1 or self._products == 'exact':
             return None
-        if not self._planes_packed_once:
-            self.pack_planes(2, self.layers[0][0])
-            self._planes_packed_once = True
-            self._planes_for = self._version()
-        return self.n, self._w, self._in, self._out, self._plane_buffer().data_ptr()
-
-    def _version(self):
-        return None if self._weights_version is None else self._weights_version()
-
-    def split_products(self, rows, direction, requested=0):
-        """True when the launch of this kind (0 inference forward, 1 backward, 2 training forward) runs the split-product
-        kernel for `rows` rows.  Never under products='exact'."""
-        if self._products == 'exact':
-            return False
-        return bool(_lib.load().rlg_mlp_chain_bx_supported(self.n, self._in, self._out, int(rows),
-                                                           self.groups(rows, direction, requested), int(direction)))
-
-    def pack_planes(self, direction, stream_of):
-        """Weights -> bf16 plane fragments (one launch; direction 0 forward operand, 1 backward, 2 both).  Returns the
-        view of that direction's fragments (direction 2: the whole buffer).  The planes must be re-packed after
-        every change of the weights: forward() / backward() do it themselves, right in front of their launch."""
-        buf = self._plane_buffer()
-        lib = _lib.load()
-        if direction == 2 and 2 * self.n - 1 > 8:                 # more jobs than one launch carries
-            self.pack_planes(0, stream_of)
-            self.pack_planes(1, stream_of)
-            return buf
-        view = (buf[:self._fwd_bytes], buf[self._bwd_offset:self._bwd_offset + self._bwd_bytes], buf)[direction]
-        if view.numel() > 0:
-            _lib.check(lib.rlg_mlp_chain_pack_planes(self.n, self._w, self._in, self._out, int(direction),
-                                                     view.data_ptr(), _stream(stream_of)), 'rlg_mlp_chain_pack_planes')
-        return view
-
-    def _plane_buffer(self):
-        """ONE buffer for both directions: forward fragments at 0, backward fragments at _bwd_offset."""
-        if self._planes is None:
-            lib = _lib.load()
-            nbytes = lib.rlg_mlp_chain_planes_bytes(self.n, self._in, self._out, 2)
-            off = lib.rlg_mlp_chain_planes_offset(self.n, self._in, self._out, 1)
-            if nbytes < 0 or off < 0:
-                raise ValueError('rlg_mlp_chain_planes_bytes: bad network')
-            self._planes = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=self.device)
-            self._bwd_offset = int(off)
-            self._fwd_bytes = int(lib.rlg_mlp_chain_planes_bytes(self.n, self._in, self._out, 0))
-            self._bwd_bytes = int(lib.rlg_mlp_chain_planes_bytes(self.n, self._in, self._out, 1))
-        return self._planes
-
-    def _planes_ptr(self, direction):
-        return self._plane_buffer().data_ptr() + (self._bwd_offset if direction == 1 else 0)
+        self.planes.pack_once(self.weights_token(), self.layers[0][0])
+        return self.n, self._w, self._in, self._out, self.planes.allocate().data_ptr()
 
     def groups(self, rows, direction, requested=0):
         """direction names the launch kind: 0 inference forward, 1 backward, 2 training forward (csrc/mlp_chain.hip
@@ -1197,47 +1144,40 @@ class MlpChain:
         (moments_row [2*in0+1] fp64, count int64, mean_out, var_out, count_out): training-mode
         RunningMeanStd - the minibatch's moments are folded into the state first, the new state is
         written to the *_out tensors (a second buffer set).
-        split_products: None = the library's choice (split-bf16 products on 64-row tiles for minibatches of
-        >= 16,384 rows, csrc/mlp_chain_bx_fwd.hip), False = exact f32 products."""
+        split_products: None = the library's choice (_route), False = exact f32 products."""
         rows = x.shape[0]
         n = self.n
-        if self._products == 'exact':
-            split_products = False
         outs = list(act_out) if act_out is not None else [None] * (n - 1)
         fwd = self._forward_args(x, outs + [heads], rms, eps, xn_out, rms_fold)
-        # A training forward also has the weights split for the backward launch that follows it: by the forward's own
-        # pack launch when the forward runs on planes as well (one launch, both directions), else in extra workgroups
-        # of the exact-product forward launch.  backward() uses those planes once; any other caller packs for itself.
+        # A training forward also leaves the planes of the backward that follows it: its own pack launch takes both
+        # directions, an exact-product forward splits them in extra workgroups.  That backward alone uses them (fresh).
         kind = 2 if (act_out is not None and self.n > 1 and any(t is not None for t in act_out)) else 0
-        if split_products is not False and groups in (0, 1) and self.lean_used(rows, kind):
-            self._planes_fresh = None
-            self.ensure_frags(x)
+        route = self._route(rows, kind, groups, split_products)
+        token = self.weights_token()
+        self.planes.drop_fresh()
+        if route == 'lean':
+            self.frags.ensure(token, x)
             err = _timed_chain_call('fwd_train' if act_out is not None else 'fwd_infer', _lib.load().rlg_mlp_chain_forward_lean,
                                     n, self._b, self._in, self._out, self._act, *fwd, rows, self._frags_ptr(0), _stream(x))
             if err != 801:                              # (hipErrorNotSupported: the pipelined / unit-structured launch)
                 _lib.check(err, 'rlg_mlp_chain_forward_lean')
                 return
-        train = act_out is not None and self.n > 1
-        bwd_split = train and self.split_products(rows, 1)
+        bwd_split = act_out is not None and n > 1 and self._route(rows, 1) == 'split'
         planes = fwd_planes = None
-        self._planes_fresh = None
-        packed_both = False
-        if split_products is not False and self.split_products(rows, kind, groups):
-            if not self.planes_current():
-                self.pack_planes(2 if bwd_split else 0, x)
-                packed_both = bwd_split
+        if route == 'split':
+            if not self.planes.current(token):
+                self.planes.pack(x, 2 if bwd_split else 0)
+                if bwd_split:
+                    self.planes.mark(token)
             fwd_planes = self._planes_ptr(0)
-        elif bwd_split and not self.planes_current():
+        elif bwd_split and not self.planes.current(token):
             planes = self._planes_ptr(1)
         _time_chain_launch('fwd_train' if act_out is not None else 'fwd_infer')
         _lib.check(_lib.load().rlg_mlp_chain_forward(
             n, self._w, self._b, self._in, self._out, self._act, *fwd, rows,
             self.groups(rows, kind, groups), planes, fwd_planes, _stream(x)), 'rlg_mlp_chain_forward')
-        if bwd_split:
-            # only behind a launch that succeeded, and only for the weights as they are now
-            self._planes_fresh = (rows, self._version())
-        if packed_both and self._weights_version is not None:
-            self._planes_for = self._version()
+        if bwd_split:                                   # (behind a launch that succeeded, for the weights as they are)
+            self.planes.fresh = (rows, token)
 
     def step(self, x, heads, act_out, d_heads, dz_out, bias_partials, ppo_loss, rms=None, eps=1e-5, xn_out=None,
              rms_fold=None):
@@ -1248,32 +1188,28 @@ class MlpChain:
         n = self.n
         if act_out is None or any(t is None for t in act_out) or ppo_loss is None or n < 2:
             return False
-        if self.split_products(rows, 2) or self.split_products(rows, 1) or self.groups(rows, 2) != 1 or self.groups(rows, 1) != 1:
+        routes = (self._route(rows, 2), self._route(rows, 1))
+        if 'split' in routes or self.groups(rows, 2) != 1 or self.groups(rows, 1) != 1:
             return False
-        lean = self.lean_used(rows, 2) and self.lean_used(rows, 1)
+        lean = routes == ('lean', 'lean')
         fwd = self._forward_args(x, list(act_out) + [heads], rms, eps, xn_out, rms_fold)
         bwd = (_need(d_heads, F32, 'd_heads', contiguous=False), d_heads.stride(0), *self._backward_args(dz_out, bias_partials),
                ctypes.addressof(ppo_loss), rows)
         if lean:
-            # the lean form of the same launch (fp32 weight fragments); outside its envelope: the lean forward and the lean
-            # backward as two launches (the caller's fallback), which beat the pipelined one-launch step
-            self.ensure_frags(x)
-            self._maxima_bwd = None
-            self._request_lean_maxima(rows)
+            # (outside the lean step's envelope the caller's two lean launches beat the pipelined one-launch step)
+            self.frags.ensure(self.weights_token(), x)
+            self._request_maxima(rows, 16)
             err = _timed_chain_call('step16', _lib.load().rlg_mlp_chain_step_lean, n, self._b, self._in, self._out, self._act,
                                     *fwd, *bwd, self._frags_ptr(0), self._frags_ptr(1), _stream(x))
-            if err == 801:
-                return False
-            _lib.check(err, 'rlg_mlp_chain_step_lean')
-            self._planes_fresh = None
-            self._maxima_bwd, self.maxima_rows_per_entry = rows, 16
-            return True
-        err = _timed_chain_call('step16', _lib.load().rlg_mlp_chain_step, n, self._w, self._b, self._in, self._out, self._act,
-                                *fwd, *bwd, _stream(x))
+        else:
+            err = _timed_chain_call('step16', _lib.load().rlg_mlp_chain_step, n, self._w, self._b, self._in, self._out,
+                                    self._act, *fwd, *bwd, _stream(x))
         if err == 801:                                  # hipErrorNotSupported: outside the fused kernel's envelope
             return False
-        _lib.check(err, 'rlg_mlp_chain_step')
-        self._planes_fresh = None
+        _lib.check(err, 'rlg_mlp_chain_step_lean' if lean else 'rlg_mlp_chain_step')
+        self.planes.drop_fresh()
+        if lean:
+            self._maxima_bwd, self.maxima_rows_per_entry = rows, 16
         return True
 
     def backward(self, d_heads, acts, dz_out, bias_partials=None, groups=0, ppo_loss=None, split_products=None):
@@ -1281,21 +1217,19 @@ class MlpChain:
         dZ_l output; bias_partials: per hidden layer fp64 [num_blocks(rows, 1), out_l] or None.
         ppo_loss = ops.ppo_loss_desc(...): the launch first evaluates the PPO loss of its row tiles, i.e.
         it produces d_heads itself (and the loss partials, the mu/sigma write-back).
-        split_products: None = the library's choice (split-bf16 products on 64-row tiles for minibatches of
-        >= 16,384 rows, csrc/mlp_chain_bx.hip), False = exact f32 products."""
+        split_products: None = the library's choice (_route), False = exact f32 products."""
         rows = d_heads.shape[0]
         n = self.n
-        if self._products == 'exact':
-            split_products = False
         h = self._P(*([_need(t, F32, 'H', contiguous=False) for t in acts] + [None]))
         hl = self._L(*([t.stride(0) for t in acts] + [0]))
         dz, dl, bp = self._backward_args(dz_out, bias_partials)
         _lib.require_gpu(d_heads, 'd_heads')
-        if split_products is not False and groups in (0, 1) and self.lean_used(rows, 1):
-            self._planes_fresh = None
-            self._maxima_bwd = None
-            self.ensure_frags(d_heads)
-            self._request_lean_maxima(rows)
+        route = self._route(rows, 1, groups, split_products)
+        token = self.weights_token()
+        fresh = self.planes.take_fresh(rows, token)             # (packed with the forward launch of this step)
+        if route == 'lean':
+            self.frags.ensure(token, d_heads)
+            self._request_maxima(rows, 16)
             err = _timed_chain_call(
                 'bwd_loss' if ppo_loss is not None else 'bwd', _lib.load().rlg_mlp_chain_backward_lean,
                 n, self._in, self._out, self._act, h, hl, d_heads.data_ptr(), d_heads.stride(0), dz, dl, bp,
@@ -1305,22 +1239,17 @@ class MlpChain:
                 self._maxima_bwd, self.maxima_rows_per_entry = rows, 16
                 return
         planes = None
-        if split_products is not False and self.split_products(rows, 1, groups):
-            if not self.planes_current() and (self._planes_fresh is None or self._planes_fresh != (rows, self._version())):
-                self.pack_planes(1, d_heads)                    # (else: packed with the forward launch of this step)
+        if route == 'split':
+            if not self.planes.current(token) and not fresh:
+                self.planes.pack(d_heads, 1)
             planes = self._planes_ptr(1)
         # the split-fp16 launch leaves the gradient maxima the weight-gradient launch scales by - claimed only where the
         # library is sure to take that launch (chain_bx_bwd_eligible: 16-byte aligned H / dZ rows of 4-float groups)
-        left_maxima = False
+        self._maxima_bwd = None
         if planes is not None and all(
                 t.data_ptr() % 16 == 0 and t.stride(0) % 4 == 0 and t.shape[1] % 4 == 0 for t in list(acts) + list(dz_out)):
-            buf = self._grad_maxima_buffer(rows)
-            _lib.load().rlg_mlp_chain_gradient_maxima(buf.data_ptr(), buf.shape[1])
-            left_maxima = True
-        self._maxima_bwd = rows if left_maxima else None
-        if left_maxima:
-            self.maxima_rows_per_entry = 64
-        self._planes_fresh = None
+            self._request_maxima(rows, 64)
+            self._maxima_bwd, self.maxima_rows_per_entry = rows, 64
         _time_chain_launch('bwd_loss' if ppo_loss is not None else 'bwd')
         _lib.check(_lib.load().rlg_mlp_chain_backward(
             n, self._w, self._in, self._out, self._act, h, hl, d_heads.data_ptr(), d_heads.stride(0), dz, dl,

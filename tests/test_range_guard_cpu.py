@@ -211,17 +211,8 @@ class _Lib:
 def _chain(monkeypatch, products):
     from rl_games_amd import _lib, ops
     monkeypatch.setattr(_lib, 'load', lambda: _Lib())
-    c = ops.MlpChain.__new__(ops.MlpChain)
-    c.n, c._in, c._out = 3, None, None
-    c.max_groups = {0: 4, 1: 4}
-    c._lean, c._frag_bytes = True, [1024, 1024]
-    c._forms_read, c._maxima_bwd = {}, None
-    c._weights_version = lambda: 0
-    c._planes_fresh = c._planes_for = c._frags_for = None
-    c._planes_packed_once = False
-    c._frags = c._planes = None
-    c._products = 'auto'
-    c.products = products
+    c = ops.MlpChain._from_shape(3, max_groups={0: 4, 1: 4}, frag_bytes=[1024, 1024], weights_version=lambda: 0,
+                                 products=products)
     return c
 
 
@@ -242,14 +233,15 @@ def test_exact_products_take_neither_the_lean_nor_the_split_kernels(monkeypatch,
             raise AssertionError(f'products=exact asked for {name}')
     from rl_games_amd import _lib
     monkeypatch.setattr(_lib, 'load', lambda: _NoLaunch())
-    exact.ensure_forms(launches, None)                      # no pack launch
+    from rl_games_amd.weight_forms import ChainFormSet, _ChainForms
+    ChainFormSet([_ChainForms(exact, launches, None)]).before_replay(rollout=True)          # no pack launch
     state = exact.cache_state()                             # no buffer allocated for planes / fragments
-    assert exact._frags is None and exact._planes is None and state[-1] == 'exact'
+    assert exact.frags.buffer is None and exact.planes.buffer is None and state.products == 'exact'
 
 
 def test_the_products_mode_travels_with_the_cache_state_and_is_validated(monkeypatch):
     c = _chain(monkeypatch, 'auto')
-    c._frags = c._planes = object()                         # (allocated: cache_state has nothing to do)
+    c.frags.buffer = c.planes.buffer = object()             # (allocated: cache_state has nothing to do)
     before = c.cache_state()
     assert c.forms_read(((4096, 1),)) == (True, False)
     c.products = 'exact'
