@@ -34,15 +34,16 @@ from torch import nn
 
 from . import distributed as rdist
 from . import ops, range_guard
+from .actor_paths import AutogradPath, Plan
 from .diagnostics import DefaultDiagnostics, PpoDiagnostics
 from .flat_optim import FlatAdam
 from .gae import compute_gae, gae_returns_advantages
 from .lr_control import AdaptiveScheduler, IdentityScheduler, LinearScheduler
 from .minibatch import PPODataset
-from .normalizers import GeneralizedMovingStats, launch_stats
+from .normalizers import GeneralizedMovingStats
 from .policy import PolicyBuilder
 from .rollout_buffer import ExperienceBuffer
-from .weight_forms import ChainFormSet, _ChainForms
+from .weight_forms import ChainFormSet
 
 
 def swap_and_flatten01(arr):
@@ -332,45 +333,14 @@ class A2CAgent:
         self.states = None
         self.is_rnn = self.model.is_rnn()
         self.bound_loss_type = config.get('bound_loss_type', 'bound')
-        layout = None
-        self._grads_overwritten = False
-        # (value_size > 1: the fused loss kernels carry one value column - that agent takes autograd through
-        #  rl_games_amd/torch_fallback.py instead, SURVEY 8a'-13)
-        # (... and so does a state-dependent sigma head, fixed_sigma False: the kernels carry log sigma as a parameter vector)
-        # (... and a sigma that is not exp of an unbounded log sigma: logstd_bounds, min_sigma, softplus / linear forms)
-        self._general_forms = (not self.is_discrete) and (self.value_size != 1
-                                                          or not getattr(self.model.a2c_network, 'fixed_sigma', True)
-                                                          or not getattr(self.model.a2c_network, 'plain_sigma', True))
-        self._use_engine = ((not self.is_discrete) and config.get('manual_mlp', True) and not self._general_forms
-                            and getattr(self.model.a2c_network, 'plain_trunk', True)
-                            and not self.model.a2c_network.is_separate_critic()
-                            and (not self.is_rnn or config.get('manual_lstm', True)))
-        if self._use_engine:
-            from .mlp_engine import ManualMLP
-            net = self.model.a2c_network
-            rest = [p for p in self.model.parameters() if all(p is not q for q in net.parameters())]
-            layout = ManualMLP.layout(net) + rest
-            # with the engine every gradient slot is overwritten (GEMM out=, column-sum and loss
-            # finalise kernels), so the per-step zero fill of the arena is skipped
-            self._grads_overwritten = len(rest) == 0
-        else:
-            layout = self._arena_layout(config)
+        # which engine runs the network (actor_paths.py): planned in front of the optimiser, whose arena
+        # takes the path's layout, built behind it
+        plan = Plan(self, config)
         self.optimizer = FlatAdam(self.model.parameters(), self.last_lr, eps=1e-08,
-                                  weight_decay=self.weight_decay, layout=layout)
-        self._engine = None
-        self._rnn_pair = None
-        if self._use_engine:
-            try:
-                self._engine = ManualMLP(self.model.a2c_network, self.optimizer,
-                                         max(self.minibatch_size, self.num_actors * self.num_agents),
-                                         mfma_dw=bool(config.get('mfma_dw', True)),
-                                         inplace_act=bool(config.get('inplace_act', True)),
-                                         fused_chain=bool(config.get('fused_mlp', True)))
-            except NotImplementedError as e:
-                print(f'rl_games_amd: manual MLP engine unavailable ({e}); using autograd')
-                self._engine = None
-                self._grads_overwritten = False
-        self._init_chains(config)
+                                  weight_decay=self.weight_decay, layout=plan.layout)
+        self._path = plan.build(self)
+        # where a step or a minibatch goes whose observations the path does not take (takes())
+        self._autograd = self._path if type(self._path) is AutogradPath else AutogradPath(self)
         self.dataset = PPODataset(self.batch_size, self.minibatch_size, self.is_discrete, self.is_rnn,
                                   dev, self.seq_length)
         self.central_value_net = None
@@ -418,7 +388,6 @@ class A2CAgent:
                                        dtype=torch.float32, device=dev)
         self._mb_index = 0
         self._prep_stats = ops.prepare_stats_buffer(dev)
-        self._obs_norm = None
         self._host_lr = self.last_lr
         self.train_result = None
         self.kernel_timers = None
@@ -431,8 +400,6 @@ class A2CAgent:
         self.last_allreduce = None    # 'ipc' | 'rccl' once a multi-GPU step has run (bench.py reports it)
         self._graph_failed = False
         self._fold_ready = False      # this epoch's minibatch observation moments are precomputed
-        self._fin_norm_ok = None      # decided on first use (_norm_in_finalize)
-        self._fin_norm_partials = None
         self._norm_ready = None       # (partials, count) when the finalise / all-reduce launch produced the gradient norm
         self._roll_env_actions = None
         self._ar_norm_partials = None
@@ -465,61 +432,16 @@ class A2CAgent:
         self.actions_low = torch.from_numpy(np.asarray(action_space.low).copy()).float().to(dev)
         self.actions_high = torch.from_numpy(np.asarray(action_space.high).copy()).float().to(dev)
 
-    def _rnn_pair_declined(self, config):
-        """Why a network stays off chain_net.RecurrentChainPair (None: it is eligible): separate actor / critic trunks
-        of plain Linear + activation pairs, one LSTM / GRU layer of a supported width behind each (a layer norm behind
-        the RNN is fine), a log sigma vector, identity head activations, one value column, and neither `manual_lstm`
-        nor `fused_mlp` switched off."""
-        net = self.model.a2c_network
-        if self.is_discrete or not getattr(net, 'plain_separate_rnn', False):
-            return 'not a continuous policy of separate plain trunks with an RNN each'
-        if not config.get('manual_lstm', True):
-            return 'manual_lstm is off'
-        if not config.get('fused_mlp', True):
-            return 'fused_mlp is off'
-        if self._general_forms:
-            return 'a log sigma vector and one value column only'
-        if not all(isinstance(a, nn.Identity) for a in (net.mu_act, net.value_act, net.sigma_act)):
-            return 'identity head activations only'
-        from .chain_net import rnn_cell_declined
-        return rnn_cell_declined(net.rnn_name, net.rnn_layers, net.rnn_units)
-
-    def _arena_layout(self, config):
-        """Physical order of the parameters inside the optimiser's arena for agents outside the continuous engine
-        (None: parameters() order).  Separate recurrent trunks on chain_net.RecurrentChainPair: the matrices first, each
-        trunk's bias vectors directly behind them (where RecurrentChainNet's chains want them), the head biases last."""
-        net = self.model.a2c_network
-        if not net.is_rnn() or self._rnn_pair_declined(config) is not None:
-            return None
-        from .chain_net import arena_layout
-        rest = [p for p in self.model.parameters() if all(p is not q for q in net.parameters())]
-        first = [m.bias for trunk in (net.actor_mlp, net.critic_mlp) for m in trunk if isinstance(m, nn.Linear)]
-        return arena_layout(list(net.parameters()), [[net.mu], [net.value]], first_vectors=first) + rest
-
-    def _init_chains(self, config):
-        """Hook behind the optimiser: the discrete agent puts its trunks on the fused chain kernels here (ChainNet list).
-        The continuous agent: `_rnn_pair`, separate actor / critic trunks with an RNN each on
-        chain_net.RecurrentChainPair - update and rollout; `_engine` stays None for them."""
-        self._chains = None
-        net = self.model.a2c_network
-        if self._engine is not None or not net.is_rnn() or not net.is_separate_critic():
-            return
-        why = self._rnn_pair_declined(config)
-        if why is None:
-            from .chain_net import RecurrentChainPair
-            try:
-                ln = (net.a_layer_norm, net.c_layer_norm) if net.rnn_ln else (None, None)
-                self._rnn_pair = RecurrentChainPair(
-                    net.actor_mlp, net.a_rnn.rnn, ln[0], net.mu, net.critic_mlp, net.c_rnn.rnn, ln[1], net.value,
-                    self.optimizer, self.minibatch_size, infer_rows=self.num_actors * self.num_agents)
-            except NotImplementedError as e:
-                why = str(e)
-        if self._rnn_pair is None:
-            print(f'rl_games_amd: separate recurrent trunks outside the paired RNN engine ({why}); using autograd')
+    # the engines of the chosen path under the names tests, tools and bench.py read (None where the path is another one)
+    _engine = property(lambda self: self._path.engine)
+    _rnn_pair = property(lambda self: self._path.pair)
+    _chains = property(lambda self: self._path.chains)
+    _rnn_engine = property(lambda self: self._path.recurrent)
+    _fin_norm_ok = property(lambda self: self._path.norm_ok)
 
     def _alloc_loss_scratch(self, mb, dev):
         A = self.actions_num
-        self._d_mu = torch.empty(mb, A, dtype=torch.float32, device=dev)
+        self._d_policy = torch.empty(mb, A, dtype=torch.float32, device=dev)
         self._d_val = torch.empty(mb, dtype=torch.float32, device=dev)
         self._loss_blocks = ops.ppo_loss_blocks(mb)
         # (a fused backward launch leaves one row per 16 / 32 / 64-row workgroup)
@@ -591,13 +513,14 @@ class A2CAgent:
             obs_batch = obs_batch.float() / 255.0
         return obs_batch
 
+    def _eval_batch(self, obs, **more):
+        """The input of the model's eval forward on the current RNN states."""
+        return dict(is_train=False, prev_actions=None, obs=self._preproc_obs(obs['obs']), rnn_states=self.rnn_states, **more)
+
     def get_action_values(self, obs):
-        processed_obs = self._preproc_obs(obs['obs'])
         self.model.eval()
-        input_dict = {'is_train': False, 'prev_actions': None, 'obs': processed_obs,
-                      'rnn_states': self.rnn_states}
         with torch.no_grad():
-            res_dict = self.model(input_dict)
+            res_dict = self.model(self._eval_batch(obs))
             if self.has_central_value:                               # a2c_common.py:593-600
                 res_dict['values'] = self.get_central_value({'is_train': False, 'states': obs['states']})
         return res_dict
@@ -615,10 +538,7 @@ class A2CAgent:
                 return self.get_central_value({'is_train': False, 'states': obs['states'], 'actions': None,
                                                'is_done': self.dones})
             self.model.eval()
-            processed_obs = self._preproc_obs(obs['obs'])
-            input_dict = {'is_train': False, 'prev_actions': None, 'obs': processed_obs,
-                          'rnn_states': self.rnn_states}
-            return self.model(input_dict)['values']
+            return self.model(self._eval_batch(obs))['values']
 
     def get_masked_action_values(self, obs, action_masks):
         raise NotImplementedError('Masked action values are not implemented for continuous actions')
@@ -702,14 +622,10 @@ class A2CAgent:
         self._gae_partials = torch.empty(num_moment_partials(rows), 6, dtype=torch.float64, device=dev)
         self.update_list = self._rollout_fields()
         self.tensor_list = self.update_list + ['obses', 'states', 'dones']
-        if self._engine is not None or self._rnn_pair is not None:
-            self._roll_obs_norm = torch.empty((rows,) + tuple(self.obs_shape), dtype=torch.float32, device=dev)
-            self._roll_noise = torch.empty(rows, self.actions_num, dtype=torch.float32, device=dev)
-            self._roll_actions = torch.empty(rows, self.actions_num, dtype=torch.float32, device=dev)
-            self._roll_values = torch.empty(rows, dtype=torch.float32, device=dev)
-        if self._critic_chain() is not None and self._fast_rollout_ok():
-            # the critic's rollout heads [num_actors, 1]: allocated here, not inside the first step's capture
-            self._critic_chain().reserve_infer(self.num_actors)
+        if self._fast_rollout_ok():
+            self._alloc_rollout_scratch(rows, dev)
+            if self.has_central_value:
+                self.central_value_net.reserve_rollout()
         if self.is_rnn:
             self.rnn_states = [s.to(dev) for s in self.model.get_default_rnn_state()]
             num_seqs = self.horizon_length // self.seq_length
@@ -719,6 +635,12 @@ class A2CAgent:
                                  f'length ({self.seq_length})')
             self.mb_rnn_states = [torch.zeros((num_seqs, s.size()[0], rows, s.size()[2]),
                                               dtype=torch.float32, device=dev) for s in self.rnn_states]
+
+    def _alloc_rollout_scratch(self, rows, dev):
+        self._roll_obs_norm = torch.empty((rows,) + tuple(self.obs_shape), dtype=torch.float32, device=dev)
+        self._roll_noise = torch.empty(rows, self.actions_num, dtype=torch.float32, device=dev)
+        self._roll_actions = torch.empty(rows, self.actions_num, dtype=torch.float32, device=dev)
+        self._roll_values = torch.empty(rows, dtype=torch.float32, device=dev)
 
     def init_current_rewards(self, batch_size, current_rewards_shape):
         dev = self.ppo_device
@@ -844,7 +766,7 @@ class A2CAgent:
                     st['rnn'] = [torch.empty_like(s) for s in self.rnn_states]
                 if states is not None:
                     st['states'] = torch.empty_like(states).contiguous()
-                if self._critic_rnn_engine() is not None:
+                if self._critic_steps_rnn():
                     st['cv_rnn'] = [torch.empty_like(s) for s in self.central_value_net.rnn_states]
                 self._rollout_static = st
             st = self._rollout_static
@@ -872,65 +794,45 @@ class A2CAgent:
                 and not self._graph_failed and isinstance(self.obs['obs'], torch.Tensor))
 
     def _policy_step_kernels(self, n, obs_raw, dones, rnn_states, store=True, states=None, cv_rnn_states=None):
-        """obs normalise -> engine GEMMs -> (central value: the critic's chain forward on `states`) -> fused policy-head
-        kernel that also writes actions / mus / sigmas / neglogpacs / values of the step into the buffer -> obs + dones
-        (+ states) into the buffer -> action clamp/rescale for the env.  Same maths as get_action_values + update_data +
-        preprocess_actions; no autograd, nothing that depends on the host.  cv_rnn_states: the states a recurrent
-        critic's step reads (None: the critic's own `rnn_states`); the ones it leaves go into the result."""
-        eng, buf = self._engine, self.experience_buffer
+        """obs normalise -> the path's inference forward -> (central value: the critic's forward on `states`) -> the
+        draws and the fused policy-head kernel that also writes actions / neglogpacs / values (/ mus / sigmas) of the step
+        into the buffer (_sample_step) -> obs + dones (+ states) into the buffer.  Same maths and the same generator use
+        as get_(masked_)action_values + update_data + preprocess_actions; no autograd, nothing that depends on the host,
+        so the step can be captured.  cv_rnn_states: the states a recurrent critic's step reads (None: the critic's own
+        `rnn_states`); the ones it leaves go into the result."""
+        cv = self.central_value_net
         obs = self._preproc_obs(obs_raw)
-        rows = obs.shape[0]
-        heads = self._actor_heads(obs, rnn_states)
-        value = self._critic_infer(states, cv_rnn_states) if self.has_central_value else None
-        torch.randn(self._roll_noise.shape, device=self._roll_noise.device, out=self._roll_noise)
-        vs, eps = self._rollout_value_stats()
-        env_actions = None
-        if self.clip_actions:
-            # clamp + rescale for the env ride along in the same launch (3 element-wise launches less per step)
-            if self._roll_env_actions is None or self._roll_env_actions.shape != self._roll_actions.shape:
-                self._roll_env_actions = torch.empty_like(self._roll_actions)
-            env_actions = (self._roll_env_actions, self.actions_low, self.actions_high)
-        ops.rollout_policy_head(heads, self.model.a2c_network.sigma.data, self._roll_noise, vs, eps,
-                                self._roll_actions, self._roll_values, buf.storage, self.horizon_length, n,
-                                env_actions=env_actions, value=value, value_repeat=self.num_agents if value is not None else 1)
+        heads = self._path.infer(obs, rnn_states, logits_only=self.has_central_value)
+        value = cv.infer(states, cv_rnn_states) if self.has_central_value else None
+        env_actions = self._sample_step(n, heads, value)
         # the buffer keeps the observation as the env delivered it (a2c_common.py:1000), not the
         # /255-preprocessed copy
         if store:
             self._store_step_inputs(n, obs_raw, dones, states)
-        res = {'actions': self._roll_actions, 'values': self._roll_values.view(rows, 1)}
-        res['env_actions'] = self._roll_env_actions if self.clip_actions else self._roll_actions
+        res = {'actions': self._roll_actions, 'values': self._roll_values.view(obs.shape[0], 1)}
+        if env_actions is not None:
+            res['env_actions'] = env_actions
         if self.is_rnn:
-            res['rnn_states'] = (eng if eng is not None else self._rnn_pair).last_states
-        if self._critic_rnn_engine() is not None:
-            res['cv_rnn_states'] = self._critic_rnn_engine().last_states
+            res['rnn_states'] = self._path.last_states
+        if self._critic_steps_rnn():
+            res['cv_rnn_states'] = cv.last_states
         return res
 
-    def _actor_heads(self, obs, rnn_states):
-        """The actor's inference forward on the engine: heads [rows, ...] of preprocessed observations (any row stride
-        on the fused chain: a buffer slot [:, n, :]), the normaliser in eval mode.  No autograd, no host read.
-        Separate recurrent trunks: the pair's T = 1 forward on `rnn_states` (the actor's, then the critic's), whose
-        [value | mu] rows are the pair's joint heads and whose next states stay in its `last_states`."""
-        if self._rnn_pair is not None:
-            if obs.stride(-1) != 1:
-                obs = obs.contiguous()
-            self._rnn_pair.forward(obs, self._obs_rms(), self._obs_eps(), rnn_states, None, 1, keep=False)
-            return self._rnn_pair.joint_heads[:obs.shape[0]]
-        eng = self._engine
-        if not obs.is_contiguous() and (eng.chain is None or obs.stride(-1) != 1):
-            obs = obs.contiguous()
-        if eng.chain is not None:
-            # normaliser + every layer + heads in one launch; nothing but the heads is written
-            return eng.forward_obs(obs, self._obs_rms(), self._obs_eps(), keep=False)
-        if self.is_rnn and eng.chain_rnn is not None and obs.dtype == torch.float32:
-            # recurrent policy: normaliser + trunk + gate-input product in one launch, then the LSTM step + heads
-            return eng.forward(obs, keep=False, rnn_states=rnn_states, seq_length=1,
-                               raw_rms=self._obs_rms() or (), eps=self._obs_eps())
-        if self.normalize_input:
-            m = self.model.running_mean_std
-            obs = ops.rms_apply(obs, m.running_mean, m.running_var, m.epsilon, 0, out=self._roll_obs_norm)
-        if self.is_rnn:
-            return eng.forward(obs, keep=False, rnn_states=rnn_states, seq_length=1)
-        return eng.forward(obs, keep=False)
+    def _sample_step(self, n, heads, value):
+        """Gaussian noise, then one launch: sample, score, write the step into the buffer - and clamp + rescale for the env
+        in the same launch (3 element-wise launches less per step).  Returns the actions the env takes."""
+        torch.randn(self._roll_noise.shape, device=self._roll_noise.device, out=self._roll_noise)
+        vs, eps = self._rollout_value_stats()
+        env_actions = None
+        if self.clip_actions:
+            if self._roll_env_actions is None or self._roll_env_actions.shape != self._roll_actions.shape:
+                self._roll_env_actions = torch.empty_like(self._roll_actions)
+            env_actions = (self._roll_env_actions, self.actions_low, self.actions_high)
+        ops.rollout_policy_head(heads, self.model.a2c_network.sigma.data, self._roll_noise, vs, eps,
+                                self._roll_actions, self._roll_values, self.experience_buffer.storage, self.horizon_length,
+                                n, env_actions=env_actions, value=value,
+                                value_repeat=self.num_agents if value is not None else 1)
+        return self._roll_env_actions if self.clip_actions else self._roll_actions
 
     def _store_step_inputs(self, n, obs_raw, dones, states):
         """update_data('obses' / 'dones' (/ 'states'), n) of a fused step (a2c_common.py:1000-1011): one launch per row
@@ -941,28 +843,12 @@ class A2CAgent:
         self.experience_buffer.store_step(n, fields)
 
     def _critic_chain(self):
-        """The central value network on the fused chain kernels (chain_net.ChainNet), or None."""
-        cv = getattr(self, 'central_value_net', None)
-        return None if cv is None else cv._engine
+        """The central value network's chain_net.ChainNet, or None (a name the tests read, like `_engine`)."""
+        return self.central_value_net._engine if self.has_central_value else None
 
-    def _critic_rnn_engine(self):
-        """The recurrent central value network on chain_net.RecurrentChainNet (value-tail mode), or None."""
-        cv = getattr(self, 'central_value_net', None)
-        return None if cv is None else cv._rnn_engine
-
-    def _critic_infer(self, states, cv_rnn_states=None):
-        """CentralValueTrain.get_value's forward on the chain (central_value.py:208-222, ModelCentralValue.forward
-        models.py:452-458): the states normalised in eval mode inside the launch; raw values [num_actors, 1] (any row
-        stride of `states`).  A recurrent critic: its engine's T = 1 forward from `cv_rnn_states` (None: the critic's own
-        `rnn_states`, which arrive zeroed where an episode ended), the next states left in the engine's `last_states`."""
-        cv = self.central_value_net
-        if states.stride(-1) != 1:
-            states = states.contiguous()
-        rms, eps = launch_stats(cv.model.running_mean_std if cv.normalize_input else None)
-        if cv._rnn_engine is not None:
-            return cv._rnn_engine.forward(states, rms, eps, cv.rnn_states if cv_rnn_states is None else cv_rnn_states,
-                                          None, 1, keep=False)
-        return cv._engine.infer(states, rms, eps)
+    def _critic_steps_rnn(self):
+        """A recurrent critic on its engine: the fused step carries its states."""
+        return self.has_central_value and self.central_value_net.rnn_on_engine
 
     def _rollout_value_stats(self):
         """(mean, var) and epsilon of the value de-normaliser of the rollout: the critic's with a central value network
@@ -979,22 +865,25 @@ class A2CAgent:
             return v
         return ops.rms_apply(v.contiguous(), vs[0], vs[1], eps, 1)
 
-    def _central_fast_values(self, states):
-        """get_values with a central value network (a2c_common.py:605-614): the critic's forward only - the actor does
-        not run and nothing is drawn from the generator - de-normalised, every agent of an env given the env's value
-        (central_value.py:223-225).  [num_actors * num_agents].  A recurrent critic's states advance with it, as
-        CentralValueTrain.get_value leaves them (central_value.py:222)."""
-        v = self._denorm_values(self._critic_infer(states))
-        if self._critic_rnn_engine() is not None:
-            self.central_value_net.rnn_states = list(self._critic_rnn_engine().last_states)
-        return v.expand(-1, self.num_agents).reshape(-1)
-
     def _fast_values(self, obs):
-        """get_values on the engine: de-normalised critic values [N] of `obs`."""
+        """get_values on the path's engine: de-normalised critic values [N] of `obs`.  With a central value network
+        (a2c_common.py:605-614) the critic's forward only - the actor does not run and nothing is drawn from the
+        generator - every agent of an env given the env's value (central_value.py:223-225); a recurrent critic's
+        states advance with it, as CentralValueTrain.get_value leaves them (central_value.py:222)."""
         if self.has_central_value:
-            return self._central_fast_values(obs['states'])
-        heads = self._actor_heads(self._preproc_obs(obs['obs']).contiguous(), self.rnn_states)
-        return self._denorm_values(heads[:, 0].contiguous().view(-1, 1)).view(-1)
+            cv = self.central_value_net
+            v = self._denorm_values(cv.infer(obs['states']))
+            if self._critic_steps_rnn():
+                cv.rnn_states = list(cv.last_states)
+            return v.expand(-1, self.num_agents).reshape(-1)
+        if not self._path.takes(obs['obs']):
+            return self.get_values(obs)
+        v = self._path.values(self._preproc_obs(obs['obs']), self.rnn_states)
+        self._draw_value_noise(v.shape[0])
+        return self._denorm_values(v).view(-1)
+
+    def _draw_value_noise(self, rows):
+        """What get_values' eval forward draws from the generator next to the values: nothing for a Gaussian policy."""
 
     def _obs_rms(self):
         if not self.normalize_input:
@@ -1005,30 +894,12 @@ class A2CAgent:
     def _obs_eps(self):
         return self.model.running_mean_std.epsilon if self.normalize_input else 1e-5
 
-    def _central_value_fused_ok(self):
-        """No central value network, or one the fused step can run: a critic on the chain kernels (feed-forward, one
-        value column, `fused_mlp` not off in its config) or - behind a recurrent actor, whose play_steps_rnn is where the
-        reference advances a recurrent critic (a2c_common.py:1085-1086) - a recurrent critic on its engine
-        (CentralValueTrain._rnn_engine), over fp32 states.  Any other recurrent critic keeps the torch rollout."""
-        if not self.has_central_value:
-            return True
-        dtype = getattr(self.state_space, 'dtype', None)
-        on_kernels = self._critic_chain() is not None or (self._critic_rnn_engine() is not None and self.is_rnn)
-        return on_kernels and dtype is not None and np.dtype(dtype) == np.float32
-
     def _fused_rollout_eligible(self):
-        """The rollout on the fused forwards: one value column, no central value network or one the fused step can run,
-        `fused_rollout` on, and the agent's own conditions (_fused_rollout_network_ok)."""
-        return (self.value_size == 1 and self._central_value_fused_ok() and self.config.get('fused_rollout', True)
-                and self._fused_rollout_network_ok())
-
-    def _fused_rollout_network_ok(self):
-        """The actor on the manual engine, or on the pair of recurrent engines (fp32 observations: the pair's chains
-        read them raw)."""
-        if self._rnn_pair is not None:
-            dtype = getattr(self.observation_space, 'dtype', None)
-            return dtype is not None and np.dtype(dtype) == np.float32
-        return self._engine is not None
+        """The rollout on the fused forwards: one value column, no central value network or one the fused step can run
+        (behind a recurrent actor, whose play_steps_rnn is where the reference advances a recurrent critic), `fused_rollout`
+        on, and the path's own conditions (rollout_ok)."""
+        cv_ok = not self.has_central_value or self.central_value_net.rollout_ok(self.state_space, self.is_rnn)
+        return self.value_size == 1 and cv_ok and self.config.get('fused_rollout', True) and self._path.rollout_ok
 
     def _fast_rollout_ok(self):
         """Does the rollout run fused (decided when the agent was built)."""
@@ -1061,6 +932,16 @@ class A2CAgent:
 
     def play_steps(self):
         """a2c_common.py:985-1069."""
+        return self._play_steps(recurrent=False)
+
+    def play_steps_rnn(self):
+        """a2c_common.py:1071-1202."""
+        return self._play_steps(recurrent=True)
+
+    def _play_steps(self, recurrent):
+        """The rollout loop of both entry points.  What play_steps_rnn adds is marked `recurrent`: the state every sequence
+        starts from, the new states behind the forward, their zeroing where an episode ended, and behind the loop the
+        done flags of filler rows and the kept states for the dataset."""
         buf = self.experience_buffer
         self._shaper = self._shaper_params()
         self._observer_needs_infos = self._uses_observer_infos()
@@ -1073,56 +954,24 @@ class A2CAgent:
             mb_valid = torch.ones((self.horizon_length, self.num_actors * self.num_agents),
                                   dtype=torch.float32, device=self.ppo_device)
         for n in range(self.horizon_length):
-            if fast:
-                res_dict = self._fast_policy_step(n)
-            else:
-                res_dict = self._torch_action_values()
-                self._store_torch_step(n, res_dict)
-            if mb_valid is not None:
-                self._mark_autoreset_rows(mb_valid, n)
-            t0 = time.perf_counter()
-            self.obs, rewards, dones, infos = self.env_step(res_dict['actions'], res_dict.get('env_actions'))
-            self.dones = self._as_u8(dones)
-            if self.mask_autoreset_rows:
-                self._autoreset_prev_dones = self.dones.clone()
-            step_time += time.perf_counter() - t0
-            self._rollout_step_tail(n, res_dict, rewards, infos, mb_valid)
-        batch_dict = buf.get_transformed_list(swap_and_flatten01, self.tensor_list)
-        batch_dict = self._finish_rollout(batch_dict, mb_valid, step_time)
-        self._scan_rollout(batch_dict)
-        return batch_dict
-
-    def play_steps_rnn(self):
-        """a2c_common.py:1071-1202."""
-        buf = self.experience_buffer
-        self._shaper = self._shaper_params()
-        self._observer_needs_infos = self._uses_observer_infos()
-        step_time = 0.0
-        mb_valid = None
-        rows = self.num_actors * self.num_agents
-        fast = self._fast_rollout_ok()
-        if fast:
-            self._form_chains.before_replay(rollout=True)
-        if self.mask_autoreset_rows:
-            mb_valid = torch.ones((self.horizon_length, rows), dtype=torch.float32, device=self.ppo_device)
-        for n in range(self.horizon_length):
-            if n % self.seq_length == 0:
-                for s, mb_s in zip(self.rnn_states, self.mb_rnn_states):
-                    mb_s[n // self.seq_length, :, :, :] = s
-            if self.has_central_value:
-                self.central_value_net.pre_step_rnn(n)           # a2c_common.py:1085-1086
+            if recurrent:
+                if n % self.seq_length == 0:
+                    for s, mb_s in zip(self.rnn_states, self.mb_rnn_states):
+                        mb_s[n // self.seq_length, :, :, :] = s
+                if self.has_central_value:
+                    self.central_value_net.pre_step_rnn(n)       # a2c_common.py:1085-1086
             res_dict = self._fast_policy_step(n) if fast else self._torch_action_values()
-            self.rnn_states = [s.contiguous() for s in res_dict['rnn_states']]
-            if res_dict.get('cv_rnn_states') is not None:        # (a fused step: get_value's update, central_value.py:222)
-                self.central_value_net.rnn_states = [s.contiguous() for s in res_dict['cv_rnn_states']]
+            if recurrent:
+                self.rnn_states = [s.contiguous() for s in res_dict['rnn_states']]
+                if res_dict.get('cv_rnn_states') is not None:    # (a fused step: get_value's update, central_value.py:222)
+                    self.central_value_net.rnn_states = [s.contiguous() for s in res_dict['cv_rnn_states']]
+            elif not fast:
+                self._store_torch_step(n, res_dict)
             if mb_valid is not None:
                 prev = self._mark_autoreset_rows(mb_valid, n)
-                if self.zero_rnn_on_done:
-                    for s in self.rnn_states:
-                        ops.rnn_zero_done_states(s, prev)
-                    if self.has_central_value:                   # (the critic absorbed the same filler row: :1112-1115)
-                        self.central_value_net.zero_states_where(prev)
-            if not fast:
+                if recurrent:                                    # (the critic absorbed the same filler row: :1112-1115)
+                    self._zero_rnn_states(prev)
+            if recurrent and not fast:                           # (a recurrent step is stored behind its state upkeep)
                 self._store_torch_step(n, res_dict)
             t0 = time.perf_counter()
             self.obs, rewards, dones, infos = self.env_step(res_dict['actions'], res_dict.get('env_actions'))
@@ -1130,15 +979,14 @@ class A2CAgent:
             if self.mask_autoreset_rows:
                 self._autoreset_prev_dones = self.dones.clone()
             step_time += time.perf_counter() - t0
-            if self.zero_rnn_on_done:
-                for s in self.rnn_states:
-                    ops.rnn_zero_done_states(s, self.dones)
-            if self.has_central_value:                           # a2c_common.py:1151-1152
-                self.central_value_net.zero_states_where(self.dones)
+            if recurrent:                                        # a2c_common.py:1151-1152
+                self._zero_rnn_states(self.dones)
             self._rollout_step_tail(n, res_dict, rewards, infos, mb_valid)
         batch_dict = buf.get_transformed_list(swap_and_flatten01, self.tensor_list)
         batch_dict = self._finish_rollout(batch_dict, mb_valid, step_time)
         self._scan_rollout(batch_dict)
+        if not recurrent:
+            return batch_dict
         if mb_valid is not None and self.zero_rnn_on_done:
             rnn_dones = buf.tensor_dict['dones'].clone()
             garbage = (mb_valid == 0.0)
@@ -1155,6 +1003,14 @@ class A2CAgent:
             states.append(self._rnn_state_store[k])
         batch_dict['rnn_states'] = states
         return batch_dict
+
+    def _zero_rnn_states(self, ended):
+        """`zero_rnn_on_done`: the actor's states - and a recurrent critic's - start from zero where `ended` is set."""
+        if self.zero_rnn_on_done:
+            for s in self.rnn_states:
+                ops.rnn_zero_done_states(s, ended)
+        if self.has_central_value:
+            self.central_value_net.zero_states_where(ended)
 
     # ================================================================== dataset
     def prepare_dataset(self, batch_dict):
@@ -1207,10 +1063,13 @@ class A2CAgent:
                           out=(nv.view(-1), nr.view(-1), na))
         if self.normalize_value:
             self.value_mean_std.eval()
+        self._update_datasets(batch_dict, nv, nr, na, rnn_masks)
 
+    def _update_datasets(self, batch_dict, values, returns, advantages, rnn_masks):
+        """The actor's dataset and (a2c_common.py:1651-1660) the central value network's, of the prepared tensors."""
         dataset_dict = {
-            'old_values': nv, 'old_logp_actions': batch_dict['neglogpacs'], 'advantages': na,
-            'returns': nr, 'actions': batch_dict['actions'], 'obs': batch_dict['obses'],
+            'old_values': values, 'old_logp_actions': batch_dict['neglogpacs'], 'advantages': advantages,
+            'returns': returns, 'actions': batch_dict['actions'], 'obs': batch_dict['obses'],
             'dones': batch_dict['dones'], 'rnn_states': batch_dict.get('rnn_states', None),
             'rnn_masks': rnn_masks,
         }
@@ -1219,9 +1078,9 @@ class A2CAgent:
         if self.use_action_masks:                                    # a2c_common.py:1346-1347
             dataset_dict['action_masks'] = batch_dict['action_masks']
         self.dataset.update_values_dict(dataset_dict)
-        if self.has_central_value:                                   # a2c_common.py:1651-1660
+        if self.has_central_value:
             self.central_value_net.update_dataset({
-                'old_values': nv, 'advantages': na, 'returns': nr, 'actions': batch_dict['actions'],
+                'old_values': values, 'advantages': advantages, 'returns': returns, 'actions': batch_dict['actions'],
                 'obs': batch_dict['states'], 'dones': batch_dict['dones'], 'rnn_masks': rnn_masks,
             })
 
@@ -1256,57 +1115,7 @@ class A2CAgent:
                 advantages = self.advantage_mean_std(advantages, mask=rnn_masks)
             else:
                 advantages = tf.normalize_advantages(advantages, rnn_masks)
-        dataset_dict = {
-            'old_values': values, 'old_logp_actions': batch_dict['neglogpacs'], 'advantages': advantages,
-            'returns': returns, 'actions': batch_dict['actions'], 'obs': batch_dict['obses'],
-            'dones': batch_dict['dones'], 'rnn_states': batch_dict.get('rnn_states', None), 'rnn_masks': rnn_masks,
-            'mu': batch_dict['mus'], 'sigma': batch_dict['sigmas'],
-        }
-        self.dataset.update_values_dict(dataset_dict)
-        if self.has_central_value:
-            self.central_value_net.update_dataset({
-                'old_values': values, 'advantages': advantages, 'returns': returns, 'actions': batch_dict['actions'],
-                'obs': batch_dict['states'], 'dones': batch_dict['dones'], 'rnn_masks': rnn_masks,
-            })
-
-    def _forward_loss_backward_general(self, input_dict, row):
-        """calc_gradients up to the gradients in the arena for value_size > 1: forward with autograd, the losses as torch
-        ops (rl_games_amd/torch_fallback.py: a2c_continuous.py:97-134, :173-221), loss.backward() into the arena views.
-        Leaves the same things behind as the fused path: the five scalars in `row`, the KL in the arena's tail slot (the
-        device-side lr rule and the multi-GPU average read it there), mu / sigma written back into the dataset."""
-        from . import torch_fallback as tf
-        opt = self.optimizer
-        batch = {'is_train': True, 'prev_actions': input_dict['actions'], 'obs': self._preproc_obs(input_dict['obs'])}
-        if self.is_rnn:
-            batch['rnn_states'] = input_dict['rnn_states']
-            batch['seq_length'] = self.seq_length
-            if self.zero_rnn_on_done:
-                batch['dones'] = input_dict['dones']
-        rnn_masks = input_dict.get('rnn_masks', None)
-        mask = None if rnn_masks is None else rnn_masks.reshape(-1).float()
-        opt.zero_grad()
-        mu, logstd, values, _ = self.model.forward_heads(batch)
-        mb = mu.shape[0]
-        net = self.model.a2c_network
-        kind = 0 if self.bounds_loss_coef is None else ops.BOUND_KINDS.get(self.bound_loss_type, 0)
-        loss, scalars, sigma = tf.ppo_loss(
-            mu, logstd, values.reshape(mb, -1), input_dict['actions'], input_dict['old_logp_actions'], input_dict['advantages'],
-            input_dict['old_values'].reshape(mb, -1), input_dict['returns'].reshape(mb, -1), e_clip=self.e_clip,
-            critic_coef=self.critic_coef if self.has_value_loss else 0.0, entropy_coef=self.entropy_coef,
-            bounds_coef=self.bounds_loss_coef if self.bounds_loss_coef is not None else 0.0, bound_kind=kind,
-            clip_value=self.clip_value, smooth=self.surrogate, mask=mask,
-            sigma_fn=None if net.plain_sigma else net.sigma_and_logstd)
-        loss.backward()
-        with torch.no_grad():
-            sig = sigma.detach().expand_as(mu)
-            kl = tf.policy_kl(mu.detach(), sig, input_dict['mu'], input_dict['sigma'], mask)
-            row[0], row[1], row[2], row[3], row[4] = (scalars['a_loss'], scalars['c_loss'], scalars['entropy'],
-                                                      scalars['b_loss'], kl)
-            opt.kl_slot.copy_(kl.reshape(1))
-            input_dict['mu'].copy_(mu.detach())                                         # datasets.py:33-43
-            input_dict['sigma'].copy_(sig)
-            self._diag_minibatch(input_dict, new_neglogp=scalars['neglogp'])
-        self._norm_ready = None
+        self._update_datasets(batch_dict, values, returns, advantages, rnn_masks)
 
     # ================================================================== update
     def train_actor_critic(self, input_dict):
@@ -1315,168 +1124,67 @@ class A2CAgent:
         return self.train_result
 
     def calc_gradients(self, input_dict):
-        """a2c_continuous.py:136-234 - forward, fused loss + analytic backward + KL, optimiser."""
+        """a2c_continuous.py:136-234, a2c_discrete.py:121-209 - forward, fused loss + analytic backward + KL, optimiser."""
         row = self._mb_scalars[self._mb_index % self._mb_scalars.shape[0]]
         self._mb_index += 1
         self._forward_loss_backward(input_dict, row)
         self.trancate_gradients_and_step()
-        # dataset.update_mu_sigma happened inside the loss kernel (write_back)
+        # (a central value network without `use_experimental_cv`: no actor value loss, a2c_discrete.py:164-167)
         c_loss = row[1] if self.has_value_loss else torch.zeros((), device=row.device)
-        self.train_result = (row[0], c_loss, row[2], row[4], self._host_lr, 1.0,
-                             input_dict['mu'], input_dict['sigma'], row[3])
+        self.train_result = (row[0], c_loss, row[2], row[4], self._host_lr, 1.0)
+        if not self.is_discrete:        # dataset.update_mu_sigma happened inside the loss kernel (write_back)
+            self.train_result += (input_dict['mu'], input_dict['sigma'], row[3])
 
     def _forward_loss_backward(self, input_dict, row):
-        """Everything of calc_gradients up to (and including) the gradients in the arena.  No
-        host-side scalars change between calls for a given minibatch slice, so this body is what
-        gets captured into a HIP graph per minibatch index."""
-        if self._general_forms:
-            return self._forward_loss_backward_general(input_dict, row)
-        if self._rnn_pair is not None and input_dict['obs'].dtype == torch.float32:
-            return self._forward_loss_backward_pair(input_dict, row)
-        opt = self.optimizer
-        net = self.model.a2c_network
-        obs_batch = self._preproc_obs(input_dict['obs'])
-        rnn_masks = input_dict.get('rnn_masks', None)
-        batch = {'is_train': True, 'prev_actions': input_dict['actions'], 'obs': obs_batch}
+        """Everything of calc_gradients up to (and including) the gradients in the arena: the update of the chosen path,
+        or the autograd path's where the path does not take the minibatch's observations."""
+        path = self._path if self._path.takes(input_dict['obs']) else self._autograd
+        path.update(input_dict, row)
+
+    def _torch_batch(self, input_dict, obs):
+        """The training input of the torch model's forward (a2c_continuous.py:141-153, a2c_discrete.py:131-144)."""
+        batch = {'is_train': True, 'prev_actions': input_dict['actions'], 'obs': obs}
         if self.is_rnn:
             batch['rnn_states'] = input_dict['rnn_states']
             batch['seq_length'] = self.seq_length
             if self.zero_rnn_on_done:
                 batch['dones'] = input_dict['dones']
+        return batch
 
-        eng = self._engine
-        if eng is None or not self._grads_overwritten:
-            opt.zero_grad()
-        if eng is not None:
-            with torch.no_grad():
-                if eng.chain is not None:
-                    if not obs_batch.is_contiguous():
-                        obs_batch = obs_batch.contiguous()
-                    rms, fold = self._obs_rms(), None
-                    if self.normalize_input and self.model.running_mean_std.training:
-                        if self._fold_index is not None:
-                            # statistics first (models.py:54-56), in the launch's prologue, from the
-                            # epoch's precomputed minibatch moments
-                            rms, fold = self.model.running_mean_std.fold_buffers(self._fold_index)
-                        else:
-                            self.model.running_mean_std.update(obs_batch)
-                    # forward + loss + backward as ONE launch where the chain has that form (minibatches < 16,384 rows,
-                    # the loss evaluated by the backward launch): the forward is handed to eng.backward() below
-                    defer = (self.config.get('fused_step16', True) and self.config.get('fold_loss_finalize', True)
-                             and self.config.get('loss_in_backward', True)
-                             and not eng.chain.split_products(obs_batch.shape[0], 2))
-                    heads = eng.forward_obs(obs_batch, rms, self._obs_eps(), rms_fold=fold, defer=defer)
-                    obs_n = None
-                elif self.is_rnn and eng.chain_rnn is not None and obs_batch.dtype == torch.float32:
-                    # recurrent policy on the fused trunk: the statistics update stays its own (two) launches, the
-                    # normalisation happens inside the trunk launch
-                    if not obs_batch.is_contiguous():
-                        obs_batch = obs_batch.contiguous()
-                    if self.normalize_input and self.model.running_mean_std.training:
-                        self.model.running_mean_std.update(obs_batch)
-                    heads = eng.forward(obs_batch, rnn_states=batch['rnn_states'], dones=batch.get('dones'),
-                                        seq_length=self.seq_length, raw_rms=self._obs_rms() or (), eps=self._obs_eps())
-                    obs_n = None
-                elif self.normalize_input:                              # updates the obs statistics
-                    out = self._obs_norm_mb[:obs_batch.shape[0]] if self._obs_norm_mb is not None else None
-                    obs_n = self.model.running_mean_std(obs_batch, out=out)
-                else:
-                    obs_n = obs_batch
-                if eng.chain is not None or obs_n is None:
-                    pass
-                elif self.is_rnn:
-                    heads = eng.forward(obs_n, rnn_states=batch['rnn_states'], dones=batch.get('dones'),
-                                        seq_length=self.seq_length)
-                else:
-                    heads = eng.forward(obs_n)
-            mu, values = eng.mu_view(heads), eng.values_view(heads)
-            logstd = net.sigma
-        else:
-            mu, logstd, values, _ = self.model.forward_heads(batch)
-        mb, A = mu.shape
-        mask, mask_sum = ops.sequence_mask(rnn_masks)
+    def _loss_scalars(self):
+        """(coef_c, coef_b, bound kind) of the loss.  Central value without `use_experimental_cv`: the actor's own value
+        head is not trained (c_loss = zeros, a2c_continuous.py:112-115) - a zero coefficient removes it from loss and grads."""
         coef_b = self.bounds_loss_coef if self.bounds_loss_coef is not None else 0.0
         kind = 0 if self.bounds_loss_coef is None else ops.BOUND_KINDS.get(self.bound_loss_type, 0)
-        if eng is not None:
-            d_heads = eng.d_heads[:mb]
-            d_mu, d_val = eng.mu_view(d_heads), eng.values_view(d_heads)
-            mu_bias_grad, value_bias_grad = eng.net.mu.bias.grad, eng.net.value.bias.grad
-        else:
-            d_mu, d_val = self._d_mu[:mb], self._d_val[:mb]
-            mu_bias_grad = value_bias_grad = None
-        # central value without `use_experimental_cv`: the actor's own value head is not trained
-        # (c_loss = zeros, a2c_continuous.py:112-115) - a zero coefficient removes it from loss and grads
-        coef_c = self.critic_coef if self.has_value_loss else 0.0
-        with torch.no_grad():
-            loss_args = (mu.detach(), logstd.detach(),
-                         values.detach().reshape(mb, -1)[:, 0] if eng is not None else values.detach().reshape(-1),
-                         input_dict['actions'], input_dict['old_logp_actions'], input_dict['advantages'],
-                         input_dict['old_values'].reshape(-1), input_dict['returns'].reshape(-1),
-                         input_dict['mu'], input_dict['sigma'], d_mu, d_val[:, 0] if eng is not None else d_val,
-                         self._loss_partials, self.e_clip, coef_c, coef_b, self.clip_value,
-                         self.surrogate, kind, True, mask, mask_sum)
-            fold = eng is not None and self.config.get('fold_loss_finalize', True)
-            # On the fused chain the backward launch evaluates the loss of its own row tiles first (no loss
-            # launch; one partial row per backward workgroup).
-            in_backward = fold and eng.chain is not None and self.config.get('loss_in_backward', True)
-            if in_backward:
-                loss_blocks = eng.chain.num_blocks(mb, 1)
-                ppo = ops.ppo_loss_desc(*loss_args)
-            else:
-                loss_blocks = ops.ppo_loss_blocks(mb)
-                ppo = None
-                ops.ppo_loss_fused(*loss_args)
-            fin = (self._loss_partials, loss_blocks, A, mb, mask is not None,
-                   coef_c, self.entropy_coef, coef_b, row, net.sigma.grad,
-                   opt.kl_slot, mu_bias_grad, value_bias_grad)
-            if fold:
-                # the loss partials are folded by the weight-gradient finalise launch (one launch less),
-                # and - single GPU, every gradient of the arena written by that launch - the sums of
-                # squares for clip_grad_norm_ with them (another one)
-                norm = None
-                if self._norm_in_finalize():
-                    norm = (self._fin_norm_partials, 1.0, opt.step_counter)
-                nb = eng.backward(d_heads, loss_finalize=ops.loss_finalize_desc(*fin), norm=norm, ppo_loss=ppo)
-                self._norm_ready = (self._fin_norm_partials, nb) if nb else None
-            else:
-                ops.ppo_loss_finalize(*fin)
-                if eng is not None:
-                    eng.backward(d_heads)
-        if eng is None:
-            torch.autograd.backward([mu, values], [d_mu, d_val.view(mb, 1)])
-        # the step's mu is in the dataset now (write_back) and logstd is still the pre-step one (Adam comes behind)
-        self._diag_minibatch(input_dict, mu=input_dict['mu'], logstd=logstd.detach(), actions=input_dict['actions'])
+        return self.critic_coef if self.has_value_loss else 0.0, coef_b, kind
+
+    def _ppo_loss_setup(self, input_dict, mu, logstd, values, d_mu, d_values):
+        """The loss of one minibatch, set up once for every path: (args, fin) - `args` the arguments of ops.ppo_loss_fused
+        / ppo_loss_desc, fin(blocks, row, *bias_grads) those of ops.ppo_loss_finalize / loss_finalize_desc."""
+        mask, mask_sum = ops.sequence_mask(input_dict.get('rnn_masks', None))
+        coef_c, coef_b, kind = self._loss_scalars()
+        (mb, A), sigma_grad = mu.shape, self.model.a2c_network.sigma.grad
+        args = (mu.detach(), logstd.detach(), values, input_dict['actions'], input_dict['old_logp_actions'],
+                input_dict['advantages'], input_dict['old_values'].reshape(-1), input_dict['returns'].reshape(-1),
+                input_dict['mu'], input_dict['sigma'], d_mu, d_values, self._loss_partials, self.e_clip, coef_c, coef_b,
+                self.clip_value, self.surrogate, kind, True, mask, mask_sum)
+
+        def fin(blocks, row, *bias_grads):
+            return (self._loss_partials, blocks, A, mb, mask is not None, coef_c, self.entropy_coef, coef_b, row,
+                    sigma_grad, self.optimizer.kl_slot) + bias_grads
+        return args, fin
 
     @torch.no_grad()
-    def _forward_loss_backward_pair(self, input_dict, row):
-        """_forward_loss_backward for separate recurrent trunks on chain_net.RecurrentChainPair: the normaliser's
-        statistics first (models.py:54-56), the pair's training forward, the fused loss launch writing d mu / d value
-        into the two engines' d_heads, its finalise launch (log sigma's gradient), the pair's backward.  No autograd,
-        no torch.nn forward."""
-        opt, pair, net = self.optimizer, self._rnn_pair, self.model.a2c_network
-        obs_batch = self._preproc_obs(input_dict['obs'])
-        if not obs_batch.is_contiguous():
-            obs_batch = obs_batch.contiguous()
-        opt.zero_grad()
-        rms, eps = launch_stats(self.model.running_mean_std if self.normalize_input else None, obs_batch)
-        mu, values = pair.forward(obs_batch, rms, eps, input_dict['rnn_states'],
-                                  input_dict['dones'] if self.zero_rnn_on_done else None, self.seq_length, keep=True)
-        mb, A = mu.shape
-        rnn_masks = input_dict.get('rnn_masks', None)
-        mask, mask_sum = ops.sequence_mask(rnn_masks)
-        coef_b = self.bounds_loss_coef if self.bounds_loss_coef is not None else 0.0
-        kind = 0 if self.bounds_loss_coef is None else ops.BOUND_KINDS.get(self.bound_loss_type, 0)
-        coef_c = self.critic_coef if self.has_value_loss else 0.0       # (as _forward_loss_backward)
-        ops.ppo_loss_fused(mu, net.sigma.detach(), values[:, 0], input_dict['actions'], input_dict['old_logp_actions'],
-                           input_dict['advantages'], input_dict['old_values'].reshape(-1),
-                           input_dict['returns'].reshape(-1), input_dict['mu'], input_dict['sigma'],
-                           pair.actor.d_heads[:mb], pair.critic.d_heads[:mb, 0], self._loss_partials, self.e_clip, coef_c,
-                           coef_b, self.clip_value, self.surrogate, kind, True, mask, mask_sum)
-        ops.ppo_loss_finalize(self._loss_partials, ops.ppo_loss_blocks(mb), A, mb, mask is not None, coef_c,
-                              self.entropy_coef, coef_b, row, net.sigma.grad, opt.kl_slot)
-        pair.backward()
-        self._norm_ready = None
-        self._diag_minibatch(input_dict, mu=input_dict['mu'], logstd=net.sigma.detach(), actions=input_dict['actions'])
+    def _loss_launches(self, input_dict, row, policy, values, d_mu, d_values):
+        """The fused loss launch (d mu / d value, per-block partials, mu / sigma written back into the dataset) and its
+        finalise launch (the scalars in `row`, log sigma's gradient, the KL)."""
+        args, fin = self._ppo_loss_setup(input_dict, *policy, values, d_mu, d_values)
+        ops.ppo_loss_fused(*args)
+        ops.ppo_loss_finalize(*fin(ops.ppo_loss_blocks(d_mu.shape[0]), row))
+
+    def _diag_update(self, input_dict, policy):
+        """Behind the backward: the step's mu is in the dataset (write_back), log sigma still the pre-step one."""
+        self._diag_minibatch(input_dict, mu=input_dict['mu'], logstd=policy[1].detach(), actions=input_dict['actions'])
 
     def _diag_minibatch(self, input_dict, **new_policy):
         """The diagnostics launch of this minibatch (a2c_continuous.py:223-230, a2c_discrete.py:200-207): writes the
@@ -1550,23 +1258,6 @@ class A2CAgent:
             self._all_reduce_grads()
         self._optimizer_kernels()
 
-    def _norm_in_finalize(self):
-        """The weight-gradient finalise launch may leave the gradient-norm partials (and advance the Adam
-        step counter) when it writes EVERY gradient of the arena and nothing touches them before Adam."""
-        ok = self._fin_norm_ok
-        if ok is None:
-            eng = self._engine
-            ok = (not self.multi_gpu and eng is not None and eng.chain is not None and not self.is_rnn
-                  and self.config.get('norm_in_finalize', True)
-                  and eng.gradient_elements() == self.optimizer.numel)
-            if ok:
-                # one entry per finalise workgroup: ~ one per 64 weights + the bias / loss blocks (MlpDwPlan.
-                # finalize_blocks); a plan that still needs more falls back to grad_sumsq (chain_net.WeightGrads.finish)
-                entries = max(1 << 15, eng.gradient_elements() // 64 + 8192)
-                self._fin_norm_partials = torch.zeros(entries, dtype=torch.float64, device=self.ppo_device)
-            self._fin_norm_ok = ok
-        return ok
-
     def _step_arguments(self):
         scale = 1.0 / self.world_size if self.multi_gpu else 1.0
         schedule = None
@@ -1588,26 +1279,12 @@ class A2CAgent:
 
     def _graph_chains(self):
         """The fused chains that this agent's captured graphs read, in the order their forms are brought up to date: the
-        actor engine's, the discrete agent's, the critic's (_ChainForms)."""
-        roll, eng = self.num_actors * self.num_agents, self._engine
-        arena = self.optimizer.flat_params
-        # the update's training forward (2) and backward (1), the rollout's inference forward (0)
-        actor = ((self.minibatch_size, 2), (self.minibatch_size, 1), (roll, 0))
-        forms = []
-        if eng is not None and eng.chain is not None:
-            forms.append(_ChainForms(eng.chain, actor, arena, True, bool(self.config.get('adam_writes_planes', True))))
-        if eng is not None and eng.chain_rnn is not None:
-            forms.append(_ChainForms(eng.chain_rnn, actor, arena, True, False))
-        forms += [_ChainForms(c.chain, ((roll, 0),), arena) for c in self._chains or ()]
-        if self._rnn_pair is not None:                      # (updates stay eager: the step graphs alone read them)
-            forms += [_ChainForms(c, ((roll, 0),), arena) for c in self._rnn_pair.chains]
-        if self._critic_chain() is not None:
-            forms.append(_ChainForms(self._critic_chain().chain, ((self.num_actors, 0),),
-                                     self.central_value_net.optimizer.flat_params))
-        if self._critic_rnn_engine() is not None:
-            forms.append(_ChainForms(self._critic_rnn_engine().chain, ((self.num_actors, 0),),
-                                     self.central_value_net.optimizer.flat_params))
-        return forms
+        actor path's, then the critic's (_ChainForms)."""
+        actor = self._path.chain_forms()
+        critic = self.central_value_net.chain_forms() if self.has_central_value else []
+        # (the discrete recurrent engine's chain has always come behind the critic's; the order is the order of the pack
+        #  launches in front of a replayed rollout, so it stays)
+        return critic + actor if self._path.kind == 'recurrent' else actor + critic
 
     # ------------------------------------------------------------------ HIP graphs
     def _with_fold(self, mb_index, fn, *args):
@@ -1624,8 +1301,7 @@ class A2CAgent:
         """Once per epoch, after prepare_dataset: column moments of every minibatch's observations in
         two launches (instead of a moments + a merge launch in each of the epoch's optimiser steps)."""
         self._fold_ready = False
-        eng = self._engine
-        if (eng is None or eng.chain is None or not self.normalize_input or self.is_rnn
+        if (self._path.fused_chain is None or not self.normalize_input or self.is_rnn
                 or not self.config.get('fold_obs_stats', True)):
             return
         obs = self.dataset.values_dict.get('obs')
@@ -1654,7 +1330,7 @@ class A2CAgent:
                 self.chain_products, self._guard is not None)
 
     def _graphs_usable(self):
-        return (self._hip_graphs and self._engine is not None and self._eager_epochs >= 1
+        return (self._hip_graphs and self._path.graphs and self._eager_epochs >= 1
                 and self.dataset.values_dict.get('rnn_masks') is None and not self._graph_failed)
 
     def _capture(self, body):
@@ -1881,8 +1557,7 @@ class A2CAgent:
         hidden activation of 4,094 or a weight of 1,023 and more becomes Inf in its plane and NaN in everything computed
         from it - never a finite wrong value, but the reason deserves a sentence (a warning, once: the reference would train on
         with NaNs as well).  One host read per epoch."""
-        chain = getattr(self._engine, 'chain', None) if self._engine is not None else None
-        if chain is None or self._mb_index == 0:
+        if self._path.fused_chain is None or self._mb_index == 0:
             return
         n = min(self._mb_index, self._mb_scalars.shape[0])
         if not getattr(self, '_split_range_warned', False) and \
@@ -1898,12 +1573,7 @@ class A2CAgent:
     # ------------------------------------------------------------------ range guard (range_guard.py)
     def _range_engines(self):
         """Every engine of this agent that finishes weight gradients (chain_net.WeightGrads)."""
-        engines = [self._engine, getattr(self, '_rnn_engine', None)] + list(self._chains or ())
-        if self._rnn_pair is not None:
-            engines += [self._rnn_pair.actor, self._rnn_pair.critic]
-        if self.central_value_net is not None:
-            engines += [self.central_value_net._engine, self.central_value_net._rnn_engine]
-        return [e for e in engines if e is not None]
+        return list(self._path.engines) + (self.central_value_net.engines() if self.has_central_value else [])
 
     def _set_chain_products(self, mode):
         """Every chain of the agent (and of its central value network) on `mode`, the weight-gradient launches on the

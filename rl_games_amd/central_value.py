@@ -6,33 +6,28 @@ the rollout (a2c_common.py:593-615) and therefore in GAE.
 Same kernels as the actor path: the state normaliser and value de-normaliser are `RunningMeanStd`
 (csrc/running_stats.hip), the clipped value loss + its gradient + masked mean is one fused kernel
 (`rlg_value_loss`) reduced by `rlg_ppo_loss_finalize`, clipping + Adam run on a flat parameter arena
-(`FlatAdam`, csrc/optim.hip) with one in-place all-reduce per step in multi-GPU runs.  Round 5: the MLP itself runs on
-the actor path's fused chain kernels - state normaliser + hidden layers + value head as ONE forward launch, the dX /
-activation-backward / bias-sum chain as ONE backward launch (csrc/mlp_chain*.hip), the hidden layers' weight gradients as
-the MFMA launch of csrc/mlp_dw.hip (chain_net.ChainNet) - where the network has that form (plain Linear + ELU / ReLU /
-tanh trunk, widths that are multiples of 4, one value column); anything else keeps autograd around the loss kernel
-(`fused_mlp: False` in the central-value config forces that path).
+(`FlatAdam`, csrc/optim.hip) with one in-place all-reduce per step in multi-GPU runs.  The network itself runs on the
+actor paths' engines where it has their form - feed-forward critics on chain_net.ChainNet (`_engine`), recurrent ones on
+chain_net.RecurrentChainNet with the value tail of csrc/rnn_value_tail.hip (`_rnn_engine`) - and keeps the torch module
+between the loss and optimiser kernels otherwise (the conditions: DESIGN.md 4.1a).
 
 Multi-agent envs (round 6, central_value.py:153-158,223-234): one state row per env, its value repeated for the env's agents
 in the rollout, the critic trained on agent 0's values and returns.  Recurrent critics (round 6,
 central_value.py:96-107,163-205): the network's RNN advances with the rollout (`pre_step_rnn` keeps the state every sequence
-starts from, `post_step_rnn` / `zero_states_where` zero it where an episode ended) and trains on sequence minibatches.  A
-critic of the reference's SMAC shape - plain trunk, one LSTM / GRU layer of 16 / 32 / 64 / 128 units behind it (optionally
-layer-normed), one value column - does so on chain_net.RecurrentChainNet (`_rnn_engine`): trunk + gate-input product as
-one chain launch, the sequence-persistent RNN kernels, and the value head + value loss + its backward as the one launch
-of csrc/rnn_value_tail.hip; `fused_mlp: False` or `manual_lstm: False` in the central-value config, or any other shape,
-keeps the torch module between the loss and optimiser kernels.
+starts from, `post_step_rnn` / `zero_states_where` zero it where an episode ended) and trains on sequence minibatches.
 """
 import torch
 from torch import nn
 
 from . import distributed as rdist
 from . import ops, range_guard
+from .actor_paths import fp32_space, train_forward
 from .chain_net import ChainNet, RecurrentChainNet, arena_layout, rnn_cell_declined
 from .flat_optim import FlatAdam
 from .lr_control import IdentityScheduler, LinearScheduler
 from .minibatch import PPODataset
 from .normalizers import launch_stats
+from .weight_forms import _ChainForms
 
 
 def _value_chain(net, arena, max_rows):
@@ -48,7 +43,7 @@ def _value_chain(net, arena, max_rows):
 
 def _recurrent_critic_declined(net, config, value_size):
     """Why a recurrent critic stays off chain_net.RecurrentChainNet (None: it is eligible) - the conditions of
-    DiscreteA2CAgent._recurrent_engine_declined for a value-only network."""
+    actor_paths.RecurrentPath.declined for a value-only network."""
     if not config.get('fused_mlp', True):
         return 'fused_mlp is off'
     if not config.get('manual_lstm', True):
@@ -160,11 +155,48 @@ class CentralValueTrain(nn.Module):
 
     def set_chain_products(self, mode):
         """'auto' / 'exact' for the critic's chain and its weight-gradient launch (ops.MlpChain.products)."""
-        for eng in (self._engine, self._rnn_engine):
-            if eng is not None:
-                eng.chain.products = mode
-                eng.weight_grads.form = 'exact' if mode == 'exact' else None
+        for eng in self.engines():
+            eng.chain.products = mode
+            eng.weight_grads.form = 'exact' if mode == 'exact' else None
         self.chain_products = mode
+
+    # ------------------------------------------------------------------ what the agent asks of its critic
+    rnn_on_engine = property(lambda self: self._rnn_engine is not None)
+    last_states = property(lambda self: self._rnn_engine.last_states)       # behind infer() of a recurrent critic
+
+    def engines(self):
+        """The critic's engines that finish weight gradients (chain_net.WeightGrads): one at most."""
+        return [e for e in (self._engine, self._rnn_engine) if e is not None]
+
+    def chain_forms(self):
+        """The chains an agent's step graphs read: the rollout's inference forward of `num_actors` rows."""
+        return [_ChainForms(e.chain, ((self.num_actors, 0),), self.optimizer.flat_params) for e in self.engines()]
+
+    def rollout_ok(self, state_space, recurrent_actor):
+        """Can the agent's fused rollout step run this critic: on the chain kernels (feed-forward, one value column,
+        `fused_mlp` not off in its config) or - behind a recurrent actor, whose play_steps_rnn is where the reference
+        advances a recurrent critic (a2c_common.py:1085-1086) - on its recurrent engine, over fp32 states.  Any other
+        critic keeps the torch rollout."""
+        on_kernels = self._engine is not None or (self.rnn_on_engine and recurrent_actor)
+        return on_kernels and fp32_space(state_space)
+
+    def reserve_rollout(self):
+        """The rollout heads [num_actors, 1]: allocated now, not inside the first step's capture."""
+        if self._engine is not None:
+            self._engine.reserve_infer(self.num_actors)
+
+    def infer(self, states, rnn_states=None):
+        """get_value's forward on the engine (central_value.py:208-222, ModelCentralValue.forward models.py:452-458): the
+        states normalised in eval mode inside the launch; raw values [num_actors, 1] (any row stride of `states`).  A
+        recurrent critic: its engine's T = 1 forward from `rnn_states` (None: the critic's own, which arrive zeroed
+        where an episode ended), the next states left in `last_states`."""
+        if states.stride(-1) != 1:
+            states = states.contiguous()
+        rms, eps = launch_stats(self.model.running_mean_std if self.normalize_input else None)
+        if self.rnn_on_engine:
+            return self._rnn_engine.forward(states, rms, eps, self.rnn_states if rnn_states is None else rnn_states,
+                                            None, 1, keep=False)
+        return self._engine.infer(states, rms, eps)
 
     def share_range_guard(self, record):
         """The agent's guard record: the critic's optimiser steps are guarded by it and the agent gives the verdict."""
@@ -323,11 +355,11 @@ class CentralValueTrain(nn.Module):
         if reng is not None:
             # the same normaliser update, then trunk + gate-input product, the sequence kernel, (layer norm,) and the
             # value tail: head, loss, d values, the gradient of the recurrent features and the head's gradient partials
-            rms, eps = launch_stats(self.model.running_mean_std if self.normalize_input else None, obs_batch)
             mb = obs_batch.shape[0]
-            reng.forward(obs_batch, rms, eps, batch['rnn_states'], batch['dones'], self.seq_length, keep=True,
-                         value_loss=(batch['old_values'].reshape(-1).contiguous(), batch['returns'].reshape(-1).contiguous(),
-                                     mask, mask_sum, self.e_clip, self.clip_value))
+            train_forward(reng, self.model.running_mean_std if self.normalize_input else None, obs_batch,
+                          batch['rnn_states'], batch['dones'], self.seq_length,
+                          value_loss=(batch['old_values'].reshape(-1).contiguous(), batch['returns'].reshape(-1).contiguous(),
+                                      mask, mask_sum, self.e_clip, self.clip_value))
             ops.ppo_loss_finalize(reng.loss_partials, reng.loss_blocks, 0, mb, mask is not None, 2.0, 0.0, 0.0,
                                   row, self._no_logstd)
             reng.backward()

@@ -173,7 +173,7 @@ class ActorCriticNetwork(nn.Module):
         # fixed_sigma False (round 6): a Linear sigma head over the trunk's features (network_builder.py:341-344, :508-511).
         # The fused kernels carry log sigma as a parameter vector, so such a policy runs the reference's operation sequence
         # as torch ops with autograd around this library's rollout, GAE, dataset and optimiser kernels
-        # (agent._forward_loss_backward_general, torch_fallback.py; pinned to the reference on the CPU).
+        # (actor_paths.GeneralPath, torch_fallback.py; pinned to the reference on the CPU).
         self.fixed_sigma = bool(self.space_config['fixed_sigma'])
         # how the sigma head's raw output becomes sigma (network_builder.py:311-322, models.py:272-301): the fused kernels
         # know `exp` of an unbounded log sigma; a floor, bounds or the softplus / linear forms run as torch ops like a

@@ -189,7 +189,7 @@ def main():
                 times[f].append(_timed_rollout(agents[f]))
         a = agents[True]
         envs, horizon, n_agents, obs, states, units, act = SHAPES[shape]
-        chain = (a._critic_chain() or a._critic_rnn_engine()).chain
+        chain = a.central_value_net.engines()[0].chain
         res = {'shape': shape, 'envs': envs, 'horizon': horizon, 'agents': n_agents, 'obs_dim': obs, 'state_dim': states,
                'units': units, 'activation': act, 'actions': getattr(a, 'branch_sizes', a.actions_num),
                'critic_split_planes': chain.split_products(envs, 0), 'critic_lean': chain.lean_used(envs, 0),
