@@ -199,6 +199,47 @@ int rlg_rnn_zero_done_states(float* states, const uint8_t* dones, int layers, in
                              int units, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Players (csrc/play.hip): what runs behind the policy's heads when a checkpoint is played
+ *   rl_games/algos_torch/players.py:60-83, :117-160 (get_action / get_masked_action);
+ *   rl_games/common/player.py:242-330 (run: the episode accounting).
+ * Common contract: launch-only (no allocation, no synchronise, capturable), no atomics, every clamp propagates NaN,
+ * rows == 0 returns 0 without a launch.  Before the runtime is asked for anything: a NULL required pointer, rows < 0,
+ * actions_num <= 0, a leading dimension < 1 (or smaller than the columns read), act_low without act_high (or the other
+ * way round), a branch size <= 0: hipErrorInvalidValue; more than 16 branches: hipErrorNotSupported.
+ * ---------------------------------------------------------------------------------- */
+
+/* The action of a Gaussian policy.  heads [rows, ld_heads], the means in columns mu_col .. mu_col + actions_num - 1;
+ * noise [rows, actions_num] contiguous or NULL; actions_out [rows, actions_num] contiguous.
+ *   noise == NULL:  a = mu (logstd is not read and may be NULL);   else  a = mu + expf(logstd) * noise
+ *   bounds given:   out = clamp(a, -1, 1) * ((hi - lo) / 2) + ((hi + lo) / 2), each op rounded on its own;  else out = a
+ * Numeric contract: on the same heads, logstd and noise the output equals env_actions_out (bounds) / actions_out (none)
+ * of rlg_rollout_policy_head bit for bit. */
+int rlg_play_policy_head(const float* heads, int ld_heads, int mu_col, const float* logstd, const float* noise_or_null,
+                         const float* act_low_or_null, const float* act_high_or_null, float* actions_out, int rows,
+                         int actions_num, void* stream);
+
+/* The action of a (multi-)categorical policy, actions_out int64 [rows, num_branches] contiguous.  Masked logits are set
+ * to exactly -1e8.  exp_noise == NULL: per branch the arg-max by torch.argmax's rule on the CPU - lowest index on ties,
+ * the first NaN wins, an all-masked branch gives 0.  Else the sample of rlg_rollout_categorical_head: the same op
+ * sequence on the same branch-major Exp(1) draws, actions_out bit-identical to that entry's. */
+int rlg_play_categorical_head(const float* logits, int ld_logits, const int* branch_sizes, int num_branches,
+                              const float* exp_noise_or_null, const uint8_t* masks_or_null, int ld_masks,
+                              int64_t* actions_out, int rows, void* stream);
+
+/* Episode accounting of one step.  cur_rewards[i] += rewards[i * ld_rewards] (fp32), cur_lengths[i] += 1; where
+ * dones[i], (cur_rewards[i], cur_lengths[i], 1) go into the workgroup's fp64 sums - fixed order - and both are zeroed.
+ * partials_slot: fp64 [rlg_play_post_step_num_blocks(rows)][3], written whole (zeros where nothing finished). */
+int rlg_play_post_step_num_blocks(int rows);
+int rlg_play_post_step(const float* rewards, int ld_rewards, const uint8_t* dones, float* cur_rewards,
+                       float* cur_lengths, double* partials_slot, int rows, void* stream);
+
+/* One workgroup folds partials fp64 [slots][blocks][3] into totals (24 bytes: fp64 reward sum, fp64 length sum, int64
+ * games): the slots in order, a slot's blocks in a fixed order, a slot only while games < games_limit at its start -
+ * the host loop's "add the step, then break once games >= games_num".  The totals are the same bits however the slots
+ * are spread over calls.  slots == 0 returns 0; slots < 0 or blocks < 1: hipErrorInvalidValue. */
+int rlg_play_fold(const double* partials, int slots, int blocks, long long games_limit, double* totals, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * RunningMeanStd / advantage normalisation
  *   replaces rl_games/algos_torch/running_mean_std.py: RunningMeanStd.forward :69-114,
  *   _update_mean_var_count_from_moments :55-67; rl_games/algos_torch/torch_ext.py:

@@ -54,6 +54,12 @@ _PROTOTYPES = {
                                      _c_float, _P, _P, _P, _P, _P, _c_int, _c_int, _c_int, _P],
     'rlg_rollout_categorical_head_cv': [_P, _c_int, _P, _c_int, _c_int, ctypes.POINTER(_c_int), _c_int, _P, _P, _c_int,
                                         _P, _P, _c_float, _P, _P, _P, _P, _P, _c_int, _c_int, _c_int, _P],
+    # play.hip
+    'rlg_play_policy_head': [_P, _c_int, _c_int, _P, _P, _P, _P, _P, _c_int, _c_int, _P],
+    'rlg_play_categorical_head': [_P, _c_int, ctypes.POINTER(_c_int), _c_int, _P, _P, _c_int, _P, _c_int, _P],
+    'rlg_play_post_step_num_blocks': [_c_int],
+    'rlg_play_post_step': [_P, _c_int, _P, _P, _P, _P, _c_int, _P],
+    'rlg_play_fold': [_P, _c_int, _c_int, _c_ll, _P, _P],
     # running_stats.hip
     'rlg_column_moments_num_blocks': [_c_ll, _c_int],
     'rlg_column_moments': [_P, _P, _c_ll, _c_int, _P, _c_int, _P],

@@ -208,6 +208,74 @@ def rnn_zero_done_states(states, dones):
                                             L, N, U, _stream(states)), 'rlg_rnn_zero_done_states')
 
 
+# ------------------------------------------------------------------ players (csrc/play.hip)
+
+def play_policy_head(mu, logstd, noise, actions_out, bounds=None):
+    """mu: the [rows, A] mean columns of the heads (a view, any row stride); noise [rows, A] or None (deterministic: a =
+    mu, logstd is not read); bounds = (low [A], high [A]) or None: clamp + rescale for the env.  actions_out [rows, A]."""
+    rows, A = mu.shape
+    mp, ld = _row_view(mu, F32, rows, A, 'mu')
+    if tuple(actions_out.shape) != (rows, A) or (noise is not None and tuple(noise.shape) != (rows, A)):
+        raise ValueError(f'noise / actions_out: [{rows}, {A}] expected')
+    lo, hi = (None, None) if bounds is None else (_need(bounds[0], F32, 'actions low'), _need(bounds[1], F32, 'actions high'))
+    _lib.check(_lib.load().rlg_play_policy_head(
+        mp, ld, 0, _opt(logstd, F32, 'logstd'), _opt(noise, F32, 'noise'), lo, hi,
+        _need(actions_out, F32, 'actions_out'), rows, A, _stream(mu)), 'rlg_play_policy_head')
+
+
+def play_categorical_head(logits, branch_sizes, noise, masks, actions_out):
+    """logits [N, sum(sizes)] (a view, any row stride); noise: the Exp(1) draws of rollout_categorical_head or None
+    (arg-max); masks: bool / uint8 [N, sum(sizes)] view or None; actions_out int64 [N] / [N, B]."""
+    sizes = [int(s) for s in branch_sizes]
+    N, S, B = logits.shape[0], sum(sizes), len(sizes)
+    lg, ld_lg = _row_view(logits, F32, N, S, 'logits')
+    if noise is not None:
+        _need(noise, F32, 'noise')
+        if noise.numel() < N * S:
+            raise ValueError(f'noise: {noise.numel()} draws for {N} x {S}')
+    mp, ld_m = None, 0
+    if masks is not None:
+        mp, ld_m = _row_view(masks.view(U8) if masks.dtype == torch.bool else masks, U8, N, S, 'masks')
+    if actions_out.numel() != N * B:
+        raise ValueError('actions_out [N, B] expected')
+    _lib.check(_lib.load().rlg_play_categorical_head(
+        lg, ld_lg, (ctypes.c_int * B)(*sizes), B, None if noise is None else noise.data_ptr(), mp, ld_m,
+        _need(actions_out, torch.int64, 'actions_out'), N, _stream(logits)), 'rlg_play_categorical_head')
+
+
+def play_post_step_blocks(rows):
+    return _lib.load().rlg_play_post_step_num_blocks(int(rows))
+
+
+def play_post_step(rewards, dones, cur_rewards, cur_lengths, partials_slot):
+    """rewards: fp32 [rows] or column 0 of [rows, V]; dones: bool / uint8 [rows]; partials_slot: fp64 [blocks, 3]."""
+    rows = cur_rewards.shape[0]
+    if rewards.dim() == 1:
+        rewards = rewards.unsqueeze(1)
+    rp, ld = _row_view(rewards[:, :1], F32, rows, 1, 'rewards')
+    if dones.numel() != rows or cur_lengths.numel() != rows or partials_slot.numel() != 3 * play_post_step_blocks(rows):
+        raise ValueError('dones / cur_lengths [rows] and partials_slot [blocks, 3] expected')
+    _lib.check(_lib.load().rlg_play_post_step(
+        rp, ld, _need(dones.view(U8) if dones.dtype == torch.bool else dones, U8, 'dones'),
+        _need(cur_rewards, F32, 'cur_rewards'), _need(cur_lengths, F32, 'cur_lengths'),
+        _need(partials_slot, F64, 'partials_slot'), rows, _stream(cur_rewards)), 'rlg_play_post_step')
+
+
+def play_totals(device):
+    """(totals, games): 24 bytes as fp64 [3] - reward sum, length sum - and the same storage's third word as int64."""
+    totals = torch.zeros(3, dtype=F64, device=device)
+    return totals, totals.view(torch.int64)[2:]
+
+
+def play_fold(partials, slots, games_limit, totals):
+    """partials fp64 [>= slots, blocks, 3]: folds the first `slots` slots into totals while games < games_limit."""
+    if partials.dim() != 3 or partials.shape[2] != 3 or partials.shape[0] < slots or totals.numel() != 3:
+        raise ValueError('partials [slots, blocks, 3] and totals [3] expected')
+    _lib.check(_lib.load().rlg_play_fold(
+        _need(partials, F64, 'partials'), int(slots), partials.shape[1], min(int(games_limit), 2 ** 62),
+        _need(totals, F64, 'totals'), _stream(partials)), 'rlg_play_fold')
+
+
 # ------------------------------------------------------------------ running statistics
 
 def column_moments_blocks(rows, cols):

@@ -5,12 +5,21 @@ reference agents (same `.pth` format): host mirror of `PpoPlayerContinuous` / `P
 `reset()`, `run()`.  The policy is the same module the agents train (`policy.PolicyBuilder`), on
 the GPU; observation normalisation runs through the `RunningMeanStd` HIP kernels in eval mode.
 Not mirrored: the evaluation-worker checkpoint watcher, rendering, self-play hooks.
+`config['player']['fused'] = True` (default False) takes the step off the torch modules: the engine the agents roll the
+network out through, one head launch of csrc/play.hip, a HIP graph from the second call on, and in run() the episode
+accounting on the device with one host read every `fused_poll_steps` steps (play_engine.py).  A network outside the
+engines prints a notice and plays on its torch modules.
 """
 import numpy as np
 import torch
 
 from .agent import rescale_actions
 from .policy import PolicyBuilder
+
+
+def _require_hip(device):
+    if device.type != 'cuda':
+        raise RuntimeError('rl_games_amd players run on an MI355X HIP device only')
 
 
 class _BasePlayer:
@@ -37,8 +46,7 @@ class _BasePlayer:
             raise NotImplementedError('dict observations are not implemented on the MI355X path')
         self.obs_shape = self.observation_space.shape
         self.device = torch.device(config.get('device', config.get('device_name', 'cuda:0')))
-        if self.device.type != 'cuda':
-            raise RuntimeError('rl_games_amd players run on an MI355X HIP device only')
+        _require_hip(self.device)
         self.states = None
         self.batch_size = 1
         self.has_batch_dimension = False
@@ -57,6 +65,11 @@ class _BasePlayer:
             'normalize_input': self.normalize_input}).to(self.device)
         self.model.eval()
         self.is_rnn = self.model.is_rnn()
+        self._fused = None
+        if self.player_config.get('fused', False):
+            from .play_engine import FusedPlay
+            fused = FusedPlay(self, max(1, int(self.config.get('num_actors', 1)) * self.num_agents))
+            self._fused = fused if fused.declined is None else None
 
     # ------------------------------------------------------------------ reference API
     def restore(self, fn):
@@ -99,6 +112,17 @@ class _BasePlayer:
             obs = obs.float()
         return obs
 
+    def _fused_action(self, obs, action_masks, is_deterministic):
+        """The step on the fused play path: the actions (the engine's buffer - the next step overwrites it), with
+        `self.states` advanced; None where this observation tensor is not taken (the torch modules run then)."""
+        obs = self._to_device(obs)
+        if not self.has_batch_dimension and obs.dim() == len(self.obs_shape):
+            obs = obs.unsqueeze(0)
+        if not self._fused.takes(obs):
+            return None
+        action = self._fused.step(obs, action_masks, is_deterministic)
+        return action if self.has_batch_dimension else torch.squeeze(action)
+
     def _forward(self, obs, action_masks=None):
         obs = self._to_device(obs)
         if not self.has_batch_dimension and obs.dim() == len(self.obs_shape):
@@ -113,7 +137,9 @@ class _BasePlayer:
 
     def run(self):
         """Plays `games_num` episodes (counted over all envs of the vec-env) and returns
-        (mean reward, mean episode length)."""
+        (mean reward, mean episode length).  On the fused play path with an env that returns device tensors the episode
+        accounting stays on the device: the totals are read every `fused_poll_steps` (K, default 16) steps, so the env may
+        be stepped up to K - 1 times past the step that finished the last game - the totals are the same."""
         obs = self.env.reset()
         first = self._to_device(obs)
         self.batch_size = first.shape[0] if first.dim() > len(self.obs_shape) else 1
@@ -125,6 +151,7 @@ class _BasePlayer:
         games = 0
         mask_fn = getattr(self.env, 'has_action_mask', None)       # the reference's player-side name (player.py:284-294)
         has_masks = bool(mask_fn()) if mask_fn is not None else False
+        on_device, unread = None, False      # episode totals on the device (None: not decided yet); slots not folded yet
         for _ in range(self.max_steps):
             if has_masks:
                 action = self.get_masked_action(obs, self.env.get_action_mask(), self.is_deterministic)
@@ -133,6 +160,19 @@ class _BasePlayer:
             if not self.is_tensor_obses:
                 action = action.cpu().numpy()
             obs, rewards, dones, _ = self.env.step(action)
+            if on_device is None:
+                on_device = (self._fused is not None and self.is_tensor_obses and torch.is_tensor(rewards)
+                             and rewards.is_cuda and torch.is_tensor(dones) and dones.is_cuda)
+                if on_device:
+                    self._fused.start_run(self.batch_size, self.player_config.get('fused_poll_steps', 16))
+            if on_device:
+                unread = not self._fused.post_step(rewards, dones)        # (False: the K slots are full)
+                if not unread:
+                    self._fused.fold(self.games_num)
+                    sum_r, sum_n, games = self._fused.read_totals()
+                    if games >= self.games_num:
+                        break
+                continue
             rewards = torch.as_tensor(rewards, device=self.device, dtype=torch.float32).reshape(self.batch_size, -1)[:, 0]
             dones = torch.as_tensor(dones, device=self.device).reshape(-1).bool()
             cur_r += rewards
@@ -149,6 +189,9 @@ class _BasePlayer:
                 cur_n[dones] = 0
                 if games >= self.games_num:
                     break
+        if on_device and unread:
+            self._fused.fold(self.games_num)
+            sum_r, sum_n, games = self._fused.read_totals()
         if self.print_stats and games:
             print(f'av reward: {sum_r / games:.4f} av steps: {sum_n / games:.2f} games: {games}')
         return (sum_r / max(games, 1), sum_n / max(games, 1))
@@ -163,6 +206,10 @@ class PpoPlayerContinuous(_BasePlayer):
         self._build_model(self.actions_num)
 
     def get_action(self, obs, is_deterministic=False):
+        if self._fused is not None:
+            action = self._fused_action(obs, None, is_deterministic)      # (clamped and rescaled by the head launch)
+            if action is not None:
+                return action
         res = self._forward(obs)
         current = res['mus'] if is_deterministic else res['actions']
         if not self.has_batch_dimension:
@@ -200,6 +247,10 @@ class PpoPlayerDiscrete(_BasePlayer):
         return action if self.has_batch_dimension else torch.squeeze(action.detach())
 
     def get_action(self, obs, is_deterministic=True):
+        if self._fused is not None:
+            action = self._fused_action(obs, None, is_deterministic)
+            if action is not None:
+                return action
         return self._pick(self._forward(obs), is_deterministic)
 
     def get_masked_action(self, obs, action_masks, is_deterministic=True):
@@ -207,4 +258,8 @@ class PpoPlayerDiscrete(_BasePlayer):
         masks = torch.as_tensor(action_masks).to(self.device).bool()
         if not self.has_batch_dimension and masks.dim() == 1:
             masks = masks.unsqueeze(0)
+        if self._fused is not None:
+            action = self._fused_action(obs, masks, is_deterministic)
+            if action is not None:
+                return action
         return self._pick(self._forward(obs, action_masks=masks), is_deterministic)
