@@ -24,8 +24,12 @@
 
 #include <stdint.h>
 
+/* sizeof of a descriptor struct is part of the ABI (the ctypes classes of _lib.py mirror the layouts) */
 #ifdef __cplusplus
+#define RLG_ABI_SIZE(type, bytes) static_assert(sizeof(type) == (bytes), #type ": layout is part of the C ABI")
 extern "C" {
+#else
+#define RLG_ABI_SIZE(type, bytes) _Static_assert(sizeof(type) == (bytes), #type ": layout is part of the C ABI")
 #endif
 
 /* ------------------------------------------------------------------------------------
@@ -350,15 +354,34 @@ int rlg_ppo_loss_partials_per_block(int actions);
  * [mb, 1+A] head buffer.  bound_kind 0 none / 1 'bound' / 2 'regularisation'.
  * use_smooth_clamp selects the actor loss of rl_games/common/common_losses.py:39-82: 0 = actor_loss (clipped PPO),
  * 1 = smoothed_actor_loss (`use_smooth_clamp: True`), 2 = `ppo: False` (a_loss = neglogp * advantage, either function's
- * else branch; round 6) - here and in every entry point / descriptor that carries the flag. */
-int rlg_ppo_loss_fused(const float* mu, const float* logstd, const float* values,
-                       const float* actions, const float* old_neglogp, const float* advantages,
-                       const float* old_values, const float* returns, float* old_mu,
-                       float* old_sigma, const float* mask_or_null, const float* mask_sum_or_null,
-                       float* d_mu, float* d_values, double* partials, int minibatch, int actions_num,
-                       int ld_mu, int ld_values, int ld_d_mu, int ld_d_values, float e_clip,
-                       float critic_coef, float bounds_coef, int clip_value, int use_smooth_clamp,
-                       int bound_kind, int write_back, void* stream);
+ * else branch; round 6) - here and in every entry point / descriptor that carries the flag.
+ * The arguments travel as a descriptor, which the chain's backward launches take as well (rlg_mlp_chain_backward, _step,
+ * _backward_lean, _backward_bx).  Like every descriptor of this header it is read before the entry returns and may be
+ * freed or reused then (rlg_mlp_dw_launch does the same with its own); NULL: hipErrorInvalidValue. */
+typedef struct rlg_ppo_loss_desc {
+  const float* mu;            /* [rows, A] view, row stride ld_mu */
+  const float* logstd;        /* [A] */
+  const float* values;        /* [rows] view, stride ld_values */
+  const float* actions;       /* [rows, A] */
+  const float* old_neglogp;   /* [rows] */
+  const float* advantages;
+  const float* old_values;
+  const float* returns;
+  float* old_mu;              /* [rows, A] read, then overwritten when write_back */
+  float* old_sigma;
+  const float* mask_or_null;
+  const float* mask_sum_or_null;
+  float* d_mu;                /* [rows, A] view, row stride ld_d_mu */
+  float* d_values;            /* [rows] view, stride ld_d_values */
+  double* partials;
+  int minibatch, actions_num;
+  int ld_mu, ld_values, ld_d_mu, ld_d_values;
+  float e_clip, critic_coef, bounds_coef;
+  int clip_value, use_smooth_clamp, bound_kind, write_back;
+} rlg_ppo_loss_desc;
+RLG_ABI_SIZE(rlg_ppo_loss_desc, 176);
+
+int rlg_ppo_loss_fused(const rlg_ppo_loss_desc* desc, void* stream);
 
 /* Value-only loss of the central value network - replaces CentralValueTrain.calc_loss
  * (rl_games/algos_torch/central_value.py:262-276: common_losses.critic_loss + apply_masks).
@@ -374,28 +397,12 @@ int rlg_value_loss(const float* values, const float* old_values, const float* re
  * logits [mb, n] (row stride ld), n = sum(branch_sizes); actions int64 [mb, num_branches];
  * action_masks bool [mb, n] or NULL.  Emits d_logits [mb, n] (actor + entropy terms, scaled) and
  * d_values [mb]; partials [blocks][7] feed rlg_ppo_loss_finalize with actions_num = 0
- * (kl = 0.5 (old_nlp - nlp)^2, :192-198). */
+ * (kl = 0.5 (old_nlp - nlp)^2, :192-198).
+ * The heads may live inside wider rows (the fused chain's [value | logits] head matrix and its gradient): values /
+ * d_values take an element stride, d_logits a row stride; separate contiguous tensors are ld_values = ld_d_values = 1,
+ * ld_d_logits = n.  Each row's neglogp (the sum over the branches, as the loss used it) is also stored into
+ * new_neglogp_or_null [mb] - the per-minibatch diagnostics read it (rlg_ppo_diag).  NULL: no store. */
 int rlg_ppo_loss_discrete_num_blocks(int minibatch);
-int rlg_ppo_loss_discrete(const float* logits, long long ld_logits, const float* values,
-                          const long long* actions, const unsigned char* action_masks_or_null,
-                          const int* branch_sizes, int num_branches, const float* old_neglogp,
-                          const float* advantages, const float* old_values, const float* returns,
-                          const float* mask_or_null, const float* mask_sum_or_null, float* d_logits,
-                          float* d_values, double* partials, int minibatch, float e_clip, float critic_coef,
-                          float entropy_coef, int clip_value, int use_smooth_clamp, void* stream);
-/* The same launch over heads that live inside wider rows (the fused chain's [value | logits] head matrix and its
- * gradient): values / d_values with an element stride, d_logits with a row stride.  rlg_ppo_loss_discrete is this with
- * ld_values = ld_d_values = 1, ld_d_logits = n. */
-int rlg_ppo_loss_discrete_strided(const float* logits, long long ld_logits, const float* values, long long ld_values,
-                                  const long long* actions, const unsigned char* action_masks_or_null,
-                                  const int* branch_sizes, int num_branches, const float* old_neglogp,
-                                  const float* advantages, const float* old_values, const float* returns,
-                                  const float* mask_or_null, const float* mask_sum_or_null, float* d_logits,
-                                  long long ld_d_logits, float* d_values, long long ld_d_values, double* partials,
-                                  int minibatch, float e_clip, float critic_coef, float entropy_coef, int clip_value,
-                                  int use_smooth_clamp, void* stream);
-/* rlg_ppo_loss_discrete_strided that also stores each row's neglogp (the sum over the branches, as the loss used it)
- * into new_neglogp_or_null [mb] - the per-minibatch diagnostics read it (rlg_ppo_diag).  NULL: no store. */
 int rlg_ppo_loss_discrete_nlp(const float* logits, long long ld_logits, const float* values, long long ld_values,
                               const long long* actions, const unsigned char* action_masks_or_null,
                               const int* branch_sizes, int num_branches, const float* old_neglogp,
@@ -437,11 +444,23 @@ int rlg_ppo_diag_moments(const float* values, const float* returns, const float*
 /* scalars8 = {a_loss, c_loss, entropy, b_loss, kl, loss, sum(mask), 0}; d_logstd [A];
  * kl_slot_or_null receives the KL as well (e.g. the tail slot of the flat gradient arena);
  * d_mu_bias_or_null [A] / d_value_bias_or_null [1] receive sum_rows d_mu / d_values, i.e. the
- * bias gradients of the mu and value heads (what nn.Linear's backward computes with sum(0)). */
-int rlg_ppo_loss_finalize(const double* partials, int num_blocks, int actions_num, int minibatch,
-                          int masked, float critic_coef, float entropy_coef, float bounds_coef,
-                          float* scalars8, float* d_logstd, float* kl_slot_or_null,
-                          float* d_mu_bias_or_null, float* d_value_bias_or_null, void* stream);
+ * bias gradients of the mu and value heads (what nn.Linear's backward computes with sum(0)).
+ * rlg_mlp_dw_launch takes the same descriptor and folds the loss partials in its finalise launch (a few extra
+ * workgroups next to the weight-gradient ones) instead of a launch of its own - the head-bias / logstd gradients, the
+ * loss scalars and the KL are then ready when the weight gradients are.  NULL here: hipErrorInvalidValue. */
+typedef struct rlg_loss_finalize_desc {
+  const double* partials;
+  int num_blocks, actions_num, minibatch, masked;
+  float critic_coef, entropy_coef, bounds_coef;
+  float* scalars8;
+  float* d_logstd;
+  float* kl_slot_or_null;
+  float* d_mu_bias_or_null;
+  float* d_value_bias_or_null;
+} rlg_loss_finalize_desc;
+RLG_ABI_SIZE(rlg_loss_finalize_desc, 80);
+
+int rlg_ppo_loss_finalize(const rlg_loss_finalize_desc* desc, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Gradient truncation + Adam + adaptive learning rate on a flat arena
@@ -455,21 +474,37 @@ int rlg_grad_norm_num_blocks(long long n);
 int rlg_grad_sumsq(const float* grads, long long n, float grad_scale, double* partials,
                    int num_blocks, long long* step_counter_or_null, void* stream);
 
-/* One optimiser step over n contiguous parameters.  grads are first scaled by grad_scale
- * (1/world_size) and by the clip coefficient min(1, max_norm/(norm+1e-6)) when
- * norm_partials is given.  step = *step_counter is the 1-based Adam step (device word, advanced
- * by rlg_grad_sumsq); lr_slots[(step-1)&1] is the lr of this step, the other slot receives the next
- * lr (schedule_kind 1: KL-adaptive on *kl * kl_scale).  stats_out[4] = {total_norm, clip_coef,
- * lr_used, lr_next}.  No per-call host scalars: the pair replays from a captured HIP graph.
- * skip_flag_or_null: device word (rlg_ipc_comm_error_word); non-zero = the gradients are invalid
- * (a failed in-graph all-reduce): parameters and moments stay untouched, the lr is carried over. */
-int rlg_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long long n,
-                  const double* norm_partials_or_null, int norm_blocks, float grad_scale,
-                  float max_norm, double* lr_slots, const long long* step_counter, double beta1,
-                  double beta2, double eps, double weight_decay, int schedule_kind,
-                  const float* kl_or_null, float kl_scale, double kl_threshold, double min_lr,
-                  double max_lr, double lr_multiplier, float* stats_out_or_null,
-                  const unsigned* skip_flag_or_null, void* stream);
+/* One optimiser step over n contiguous parameters: the arguments of the four rlg_adam_* entries.  No per-call host
+ * scalars - step and learning rate are device words - so a (norm, Adam) launch pair replays from a captured HIP graph.
+ * The entries read the descriptor before they return; it may be freed or reused then.  hipErrorInvalidValue: a NULL
+ * descriptor, n <= 0, no step_counter, schedule_kind 1 without kl_or_null, an arena that is not 16-byte aligned. */
+typedef struct rlg_adam_desc {
+  float* params;
+  float* grads;                 /* overwritten with the scaled / clipped gradient (like clip_grad_norm_) */
+  float* exp_avg;
+  float* exp_avg_sq;            /* the four arenas: [n] fp32, 16-byte aligned */
+  long long n;
+  const double* norm_partials_or_null;  /* [norm_blocks] sums of (grad * grad_scale)^2 (rlg_grad_sumsq, rlg_mlp_dw_launch):
+                                         * grads are also scaled by the clip coefficient min(1, max_norm / (norm + 1e-6));
+                                         * NULL: no truncation */
+  int norm_blocks;
+  float grad_scale;             /* 1 / world_size (multi-GPU average), 1 otherwise */
+  float max_norm;               /* grad_norm */
+  double* lr_slots;             /* [2] fp64; slot (step - 1) & 1 is the lr of this step, the other receives the next lr */
+  const long long* step_counter;  /* device word: the 1-based Adam step of THIS update (advanced by rlg_grad_sumsq) */
+  double beta1, beta2, eps, weight_decay;
+  int schedule_kind;            /* 0 keep the lr, 1 KL-adaptive on *kl_or_null * kl_scale (the KL of THIS minibatch) */
+  const float* kl_or_null;      /* device scalar */
+  float kl_scale;               /* 1 / world_size when *kl_or_null holds a cross-rank SUM */
+  double kl_threshold, min_lr, max_lr, lr_multiplier;
+  float* stats_out_or_null;     /* [4] = {total_norm, clip_coef, lr_used, lr_next} */
+  const unsigned* skip_flag_or_null;  /* device word (rlg_ipc_comm_error_word); non-zero = the gradients are invalid (a
+                                       * failed in-graph all-reduce): parameters and moments stay untouched, the lr is
+                                       * carried over unchanged */
+} rlg_adam_desc;
+RLG_ABI_SIZE(rlg_adam_desc, 184);
+
+int rlg_adam_step(const rlg_adam_desc* desc, void* stream);
 
 /* rlg_adam_step that also leaves the fused chain's weight planes (both directions, the layout and buffer of
  * rlg_mlp_chain_pack_planes direction 2) for the NEW weights: the thread that updates a 4 x 4 block of a weight
@@ -479,13 +514,8 @@ int rlg_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq
  * two launches) unless the four arenas are 16-byte aligned (as for rlg_adam_step) and every weights[l] lies inside
  * [params, params + n) at a multiple of 4 floats with in_features[l] % 4 == 0; `planes` must have been packed in full
  * once (the zero padding of the fragments). */
-int rlg_adam_step_pack(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long long n,
-                       const double* norm_partials_or_null, int norm_blocks, float grad_scale, float max_norm,
-                       double* lr_slots, const long long* step_counter, double beta1, double beta2, double eps,
-                       double weight_decay, int schedule_kind, const float* kl_or_null, float kl_scale,
-                       double kl_threshold, double min_lr, double max_lr, double lr_multiplier, float* stats_out_or_null,
-                       const unsigned* skip_flag_or_null, int num_layers, const float* const* weights,
-                       const int* in_features, const int* out_features, void* planes, void* stream);
+int rlg_adam_step_pack(const rlg_adam_desc* desc, int num_layers, const float* const* weights, const int* in_features,
+                       const int* out_features, void* planes, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Range guard of the split-fp16 products (csrc/range_guard.hip)
@@ -511,21 +541,9 @@ int rlg_adam_step_pack(float* params, float* grads, float* exp_avg, float* exp_a
 #define RLG_GUARD_TAG_ADAM 0x4144414d   /* 'ADAM' */
 int rlg_range_scan(int num_arrays, const float* const* arrays, const long long* counts, const int* tags,
                    unsigned* record, void* stream);
-int rlg_adam_step_guarded(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long long n,
-                          const double* norm_partials_or_null, int norm_blocks, float grad_scale,
-                          float max_norm, double* lr_slots, const long long* step_counter, double beta1,
-                          double beta2, double eps, double weight_decay, int schedule_kind,
-                          const float* kl_or_null, float kl_scale, double kl_threshold, double min_lr,
-                          double max_lr, double lr_multiplier, float* stats_out_or_null,
-                          const unsigned* skip_flag_or_null, unsigned* guard_record, void* stream);
-int rlg_adam_pack_guarded(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long long n,
-                          const double* norm_partials_or_null, int norm_blocks, float grad_scale, float max_norm,
-                          double* lr_slots, const long long* step_counter, double beta1, double beta2, double eps,
-                          double weight_decay, int schedule_kind, const float* kl_or_null, float kl_scale,
-                          double kl_threshold, double min_lr, double max_lr, double lr_multiplier,
-                          float* stats_out_or_null, const unsigned* skip_flag_or_null, unsigned* guard_record,
-                          int num_layers, const float* const* weights, const int* in_features, const int* out_features,
-                          void* planes, void* stream);
+int rlg_adam_step_guarded(const rlg_adam_desc* desc, unsigned* guard_record, void* stream);
+int rlg_adam_pack_guarded(const rlg_adam_desc* desc, unsigned* guard_record, int num_layers, const float* const* weights,
+                          const int* in_features, const int* out_features, void* planes, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Manual MLP backward helpers
@@ -581,22 +599,8 @@ int rlg_mlp_linear_act_backward(const float* dz, long long lddz, const float* w,
  * default workgroup count. */
 long long rlg_mlp_dw_plan(int rows, int out_features, int in_features, int target_blocks, int* plan4);
 /* colsum_* (num_colsums may be 0): bias gradients `grad_output.sum(0)` finished in the same finalise
- * launch from the per-block fp64 column sums of rlg_act_bwd_colsum (partials [blocks][cols]). */
-/* The arguments of rlg_ppo_loss_finalize as a struct: rlg_mlp_dw_launch can fold the loss partials in
- * its finalise launch (a few extra workgroups next to the weight-gradient ones) instead of a launch of
- * its own - the head-bias / logstd gradients, the loss scalars and the KL are then ready when the
- * weight gradients are. */
-typedef struct rlg_loss_finalize_desc {
-  const double* partials;
-  int num_blocks, actions_num, minibatch, masked;
-  float critic_coef, entropy_coef, bounds_coef;
-  float* scalars8;
-  float* d_logstd;
-  float* kl_slot_or_null;
-  float* d_mu_bias_or_null;
-  float* d_value_bias_or_null;
-} rlg_loss_finalize_desc;
-
+ * launch from the per-block fp64 column sums of rlg_act_bwd_colsum (partials [blocks][cols]).
+ * loss_finalize_or_null: the descriptor of rlg_ppo_loss_finalize, whose work then rides in that finalise launch. */
 int rlg_mlp_dw_launch(int num_layers, const float* const* dz, const float* const* x, float* const* partial,
                       float* const* grad, const int* out_features, const int* in_features,
                       const int* plans4, int rows, int num_colsums, const double* const* colsum_partials,
@@ -684,34 +688,11 @@ int rlg_mlp_chain_forward(int num_layers, const float* const* weights, const flo
                           double* rms_mean_out, double* rms_var_out, long long* rms_count_out,
                           long long rows, int groups, void* pack_backward_planes_or_null,
                           const void* weight_planes_or_null, void* stream);
-/* Arguments of the clipped-PPO loss (the parameter list of rlg_ppo_loss_fused as a struct): with a
- * non-NULL descriptor the BACKWARD launch evaluates the loss of its own row tile in front of its
- * prologue - no separate loss launch - i.e. it first writes d mu / d values (which must be views of the
- * d_out buffer this launch then reads), the mu/sigma write-back and one row of partials per workgroup
- * (rlg_mlp_chain_num_blocks(rows, resolved backward groups) rows of rlg_ppo_loss_partials_per_block
- * doubles).  minibatch must equal rows. */
-typedef struct rlg_ppo_loss_desc {
-  const float* mu;            /* [rows, A] view, row stride ld_mu */
-  const float* logstd;        /* [A] */
-  const float* values;        /* [rows] view, stride ld_values */
-  const float* actions;       /* [rows, A] */
-  const float* old_neglogp;   /* [rows] */
-  const float* advantages;
-  const float* old_values;
-  const float* returns;
-  float* old_mu;              /* [rows, A] read, then overwritten when write_back */
-  float* old_sigma;
-  const float* mask_or_null;
-  const float* mask_sum_or_null;
-  float* d_mu;                /* [rows, A] view, row stride ld_d_mu */
-  float* d_values;            /* [rows] view, stride ld_d_values */
-  double* partials;
-  int minibatch, actions_num;
-  int ld_mu, ld_values, ld_d_mu, ld_d_values;
-  float e_clip, critic_coef, bounds_coef;
-  int clip_value, use_smooth_clamp, bound_kind, write_back;
-} rlg_ppo_loss_desc;
-
+/* With a non-NULL rlg_ppo_loss_desc (the descriptor of rlg_ppo_loss_fused) the BACKWARD launch evaluates the
+ * loss of its own row tile in front of its prologue - no separate loss launch - i.e. it first writes
+ * d mu / d values (which must be views of the d_out buffer this launch then reads), the mu/sigma
+ * write-back and one row of partials per workgroup (rlg_mlp_chain_num_blocks(rows, resolved backward
+ * groups) rows of rlg_ppo_loss_partials_per_block doubles).  minibatch must equal rows. */
 int rlg_mlp_chain_backward(int num_layers, const float* const* weights, const int* in_features,
                            const int* out_features, const int* acts, const float* const* act_in,
                            const long long* act_ld, const float* d_out, long long ld_dout,

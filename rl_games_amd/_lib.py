@@ -78,8 +78,7 @@ _PROTOTYPES = {
     # ppo_loss.hip
     'rlg_ppo_loss_num_blocks': [_c_int],
     'rlg_ppo_loss_partials_per_block': [_c_int],
-    'rlg_ppo_loss_fused': [_P] * 15 + [_c_int] * 6 + [_c_float, _c_float, _c_float, _c_int, _c_int,
-                                                      _c_int, _c_int, _P],
+    'rlg_ppo_loss_fused': [_P, _P],                  # (PpoLossDesc, stream)
     'rlg_mlp_rowgemm_supported': [_c_int, _c_ll],
     'rlg_mlp_linear_act_forward': [_P, _c_ll, _P, _P, _P, _P, _c_ll, _c_int, _c_int, _c_int, _c_int, _P],
     'rlg_mlp_linear_act_backward': [_P, _c_ll, _P, _P, _P, _c_ll, _c_int, _c_int, _c_int, _c_int, _P],
@@ -141,10 +140,6 @@ _PROTOTYPES = {
     'rlg_rnn_value_tail': [_P] * 13 + [_c_int, _c_ll, _c_int, _c_float, _c_int, _P],
     'rlg_value_loss': [_P, _P, _P, _P, _P, _P, _P, _c_int, _c_float, _c_int, _P],
     'rlg_ppo_loss_discrete_num_blocks': [_c_int],
-    'rlg_ppo_loss_discrete': [_P, _c_ll, _P, _P, _P, _P, _c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _c_int,
-                              _c_float, _c_float, _c_float, _c_int, _c_int, _P],
-    'rlg_ppo_loss_discrete_strided': [_P, _c_ll, _P, _c_ll, _P, _P, _P, _c_int, _P, _P, _P, _P, _P, _P, _P, _c_ll, _P,
-                                      _c_ll, _P, _c_int, _c_float, _c_float, _c_float, _c_int, _c_int, _P],
     'rlg_ppo_loss_discrete_nlp': [_P, _c_ll, _P, _c_ll, _P, _P, _P, _c_int, _P, _P, _P, _P, _P, _P, _P, _c_ll, _P,
                                   _c_ll, _P, _c_int, _c_float, _c_float, _c_float, _c_int, _c_int, _P, _P],
     # ppo_diag.hip
@@ -153,8 +148,7 @@ _PROTOTYPES = {
     'rlg_ppo_diag': [_P, _c_ll, _P, _P, _c_ll, _P, _P, _P, _c_int, _c_int, _c_float, _c_float, _P, _P, _P, _P, _P],
     'rlg_ppo_diag_moments_num_blocks': [_c_int, _c_int],
     'rlg_ppo_diag_moments': [_P, _P, _P, _c_int, _c_int, _c_int, _P, _P, _P, _c_ll, _P],
-    'rlg_ppo_loss_finalize': [_P, _c_int, _c_int, _c_int, _c_int, _c_float, _c_float, _c_float, _P,
-                              _P, _P, _P, _P, _P],
+    'rlg_ppo_loss_finalize': [_P, _P],               # (LossFinalizeDesc, stream)
     # mlp_fused.hip
     'rlg_act_bwd_num_blocks': [_c_ll, _c_int],
     'rlg_act_bwd_colsum': [_P, _P, _P, _c_ll, _c_int, _c_ll, _c_int, _P, _c_int, _P],
@@ -176,9 +170,7 @@ _PROTOTYPES = {
     # optim.hip
     'rlg_grad_norm_num_blocks': [_c_ll],
     'rlg_grad_sumsq': [_P, _c_ll, _c_float, _P, _c_int, _P, _P],
-    'rlg_adam_step': [_P, _P, _P, _P, _c_ll, _P, _c_int, _c_float, _c_float, _P, _P,
-                      _c_double, _c_double, _c_double, _c_double, _c_int, _P, _c_float, _c_double,
-                      _c_double, _c_double, _c_double, _P, _P, _P],
+    'rlg_adam_step': [_P, _P],                       # (AdamDesc, stream)
     'rlg_rccl_available': [],
     'rlg_rccl_unique_id_bytes': [],
     'rlg_rccl_get_unique_id': [ctypes.c_char_p],
@@ -186,17 +178,11 @@ _PROTOTYPES = {
     'rlg_rccl_allreduce_sum': [_P, _P, _c_ll, _P],
     'rlg_rccl_allreduce_sum_f64': [_P, _P, _c_ll, _P],
     'rlg_rccl_comm_destroy': [_P],
-    'rlg_adam_step_pack': [_P, _P, _P, _P, _c_ll, _P, _c_int, _c_float, _c_float, _P, _P,
-                           _c_double, _c_double, _c_double, _c_double, _c_int, _P, _c_float, _c_double,
-                           _c_double, _c_double, _c_double, _P, _P, _c_int, _P, _P, _P, _P, _P],
+    'rlg_adam_step_pack': [_P, _c_int, _P, _P, _P, _P, _P],
     # range_guard.hip and the guarded optimiser entries (optim.hip, adam_pack.hip)
     'rlg_range_scan': [_c_int, _P, _P, _P, _P, _P],
-    'rlg_adam_step_guarded': [_P, _P, _P, _P, _c_ll, _P, _c_int, _c_float, _c_float, _P, _P,
-                              _c_double, _c_double, _c_double, _c_double, _c_int, _P, _c_float, _c_double,
-                              _c_double, _c_double, _c_double, _P, _P, _P, _P],
-    'rlg_adam_pack_guarded': [_P, _P, _P, _P, _c_ll, _P, _c_int, _c_float, _c_float, _P, _P,
-                              _c_double, _c_double, _c_double, _c_double, _c_int, _P, _c_float, _c_double,
-                              _c_double, _c_double, _c_double, _P, _P, _P, _c_int, _P, _P, _P, _P, _P],
+    'rlg_adam_step_guarded': [_P, _P, _P],           # (AdamDesc, guard record, stream)
+    'rlg_adam_pack_guarded': [_P, _P, _c_int, _P, _P, _P, _P, _P],
 }
 
 _lib = None
@@ -239,7 +225,7 @@ def load():
 
 
 class PpoLossDesc(ctypes.Structure):
-    """rlg_ppo_loss_desc (include/rlg_hip.h): the PPO-loss arguments of a fused backward launch."""
+    """rlg_ppo_loss_desc (include/rlg_hip.h): the arguments of rlg_ppo_loss_fused and of a fused backward launch."""
     _fields_ = ([(n, ctypes.c_void_p) for n in (
         'mu', 'logstd', 'values', 'actions', 'old_neglogp', 'advantages', 'old_values', 'returns', 'old_mu',
         'old_sigma', 'mask_or_null', 'mask_sum_or_null', 'd_mu', 'd_values', 'partials')]
@@ -256,6 +242,18 @@ class LossFinalizeDesc(ctypes.Structure):
                 ('entropy_coef', ctypes.c_float), ('bounds_coef', ctypes.c_float), ('scalars8', ctypes.c_void_p),
                 ('d_logstd', ctypes.c_void_p), ('kl_slot_or_null', ctypes.c_void_p),
                 ('d_mu_bias_or_null', ctypes.c_void_p), ('d_value_bias_or_null', ctypes.c_void_p)]
+
+
+class AdamDesc(ctypes.Structure):
+    """rlg_adam_desc (include/rlg_hip.h): the optimiser step of the four rlg_adam_* entries."""
+    _fields_ = ([(n, ctypes.c_void_p) for n in ('params', 'grads', 'exp_avg', 'exp_avg_sq')]
+                + [('n', _c_ll), ('norm_partials_or_null', ctypes.c_void_p), ('norm_blocks', _c_int),
+                   ('grad_scale', _c_float), ('max_norm', _c_float), ('lr_slots', ctypes.c_void_p),
+                   ('step_counter', ctypes.c_void_p)]
+                + [(n, _c_double) for n in ('beta1', 'beta2', 'eps', 'weight_decay')]
+                + [('schedule_kind', _c_int), ('kl_or_null', ctypes.c_void_p), ('kl_scale', _c_float)]
+                + [(n, _c_double) for n in ('kl_threshold', 'min_lr', 'max_lr', 'lr_multiplier')]
+                + [('stats_out_or_null', ctypes.c_void_p), ('skip_flag_or_null', ctypes.c_void_p)])
 
 
 def check(err, what):

@@ -232,50 +232,15 @@ extern "C" {
 // uses rlg_adam_step + rlg_mlp_chain_pack_planes): every weight matrix lies inside [params, params + n), 16-byte
 // aligned relative to it, with in_features % 4 == 0; the four arenas are 16-byte aligned; `planes` has been packed in
 // full once (the zero padding).
-static int adam_pack_launch(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long long n,
-                            const double* norm_partials_or_null, int norm_blocks, float grad_scale, float max_norm,
-                            double* lr_slots, const long long* step_counter, double beta1, double beta2, double eps,
-                            double weight_decay, int schedule_kind, const float* kl_or_null, float kl_scale,
-                            double kl_threshold, double min_lr, double max_lr, double lr_multiplier,
-                            float* stats_out_or_null, const unsigned* skip_flag_or_null, unsigned* guard_or_null,
-                            int num_layers, const float* const* weights, const int* in_features, const int* out_features,
+static int adam_pack_launch(const rlg_adam_desc* desc, unsigned* guard_or_null, int num_layers,
+                            const float* const* weights, const int* in_features, const int* out_features,
                             void* planes, void* stream) {
   using namespace rlg;
-  if (n <= 0 || !step_counter || num_layers < 1 || num_layers > kChainMaxLayers || planes == nullptr)
-    return static_cast<int>(hipErrorInvalidValue);
-  if (schedule_kind == 1 && !kl_or_null) return static_cast<int>(hipErrorInvalidValue);
-  // (16-byte loads relative to the arenas, like rlg_adam_step)
-  if ((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grads) | reinterpret_cast<uintptr_t>(exp_avg) |
-       reinterpret_cast<uintptr_t>(exp_avg_sq)) % 16 != 0)
-    return static_cast<int>(hipErrorInvalidValue);
+  if (num_layers < 1 || num_layers > kChainMaxLayers || planes == nullptr) return static_cast<int>(hipErrorInvalidValue);
   AdamPackArgs ap;
-  AdamArgs& a = ap.adam;
-  a.params = params;
-  a.grads = grads;
-  a.exp_avg = exp_avg;
-  a.exp_avg_sq = exp_avg_sq;
-  a.n = n;
-  a.norm_partials = norm_partials_or_null;
-  a.norm_blocks = norm_blocks;
-  a.grad_scale = grad_scale;
-  a.max_norm = max_norm;
-  a.lr_slots = lr_slots;
-  a.step_counter = step_counter;
-  a.beta1 = beta1;
-  a.beta2 = beta2;
-  a.eps = eps;
-  a.weight_decay = weight_decay;
-  a.schedule_kind = schedule_kind;
-  a.kl = kl_or_null;
-  a.kl_scale = kl_scale;
-  a.kl_threshold = kl_threshold;
-  a.min_lr = min_lr;
-  a.max_lr = max_lr;
-  a.lr_multiplier = lr_multiplier;
-  a.stats_out = stats_out_or_null;
-  a.skip_flag = skip_flag_or_null;
-  a.guard = guard_or_null;
-  RLG_ADAM_TRACE_FILL(a);
+  if (const int err = adam_args_from_desc(desc, guard_or_null, ap.adam)) return err;
+  const float* params = ap.adam.params;
+  const long long n = ap.adam.n;
   unsigned foff[kChainMaxLayers], boff[kChainMaxLayers];
   const long long ftotal = chain_bx_plane_offsets(num_layers, in_features, out_features, 0, foff);
   const long long btotal = chain_bx_plane_offsets(num_layers, in_features, out_features, 1, boff);
@@ -324,35 +289,16 @@ static int adam_pack_launch(float* params, float* grads, float* exp_avg, float* 
   RLG_RETURN_LAUNCH_STATUS();
 }
 
-int rlg_adam_step_pack(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long long n,
-                       const double* norm_partials_or_null, int norm_blocks, float grad_scale, float max_norm,
-                       double* lr_slots, const long long* step_counter, double beta1, double beta2, double eps,
-                       double weight_decay, int schedule_kind, const float* kl_or_null, float kl_scale,
-                       double kl_threshold, double min_lr, double max_lr, double lr_multiplier, float* stats_out_or_null,
-                       const unsigned* skip_flag_or_null, int num_layers, const float* const* weights,
-                       const int* in_features, const int* out_features, void* planes, void* stream) {
-  return adam_pack_launch(params, grads, exp_avg, exp_avg_sq, n, norm_partials_or_null, norm_blocks, grad_scale, max_norm,
-                          lr_slots, step_counter, beta1, beta2, eps, weight_decay, schedule_kind, kl_or_null, kl_scale,
-                          kl_threshold, min_lr, max_lr, lr_multiplier, stats_out_or_null, skip_flag_or_null, nullptr,
-                          num_layers, weights, in_features, out_features, planes, stream);
+int rlg_adam_step_pack(const rlg_adam_desc* desc, int num_layers, const float* const* weights, const int* in_features,
+                       const int* out_features, void* planes, void* stream) {
+  return adam_pack_launch(desc, nullptr, num_layers, weights, in_features, out_features, planes, stream);
 }
 
 // rlg_adam_step_pack under a range-guard record: a skipped launch leaves the planes as they are, too
-int rlg_adam_pack_guarded(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long long n,
-                          const double* norm_partials_or_null, int norm_blocks, float grad_scale, float max_norm,
-                          double* lr_slots, const long long* step_counter, double beta1, double beta2, double eps,
-                          double weight_decay, int schedule_kind, const float* kl_or_null, float kl_scale,
-                          double kl_threshold, double min_lr, double max_lr, double lr_multiplier,
-                          float* stats_out_or_null, const unsigned* skip_flag_or_null, unsigned* guard_record,
-                          int num_layers, const float* const* weights, const int* in_features, const int* out_features,
-                          void* planes, void* stream) {
-  // (the guard watches the gradient norm: without the partials it would watch nothing)
-  if (guard_record == nullptr || norm_partials_or_null == nullptr || norm_blocks <= 0)
-    return static_cast<int>(hipErrorInvalidValue);
-  return adam_pack_launch(params, grads, exp_avg, exp_avg_sq, n, norm_partials_or_null, norm_blocks, grad_scale, max_norm,
-                          lr_slots, step_counter, beta1, beta2, eps, weight_decay, schedule_kind, kl_or_null, kl_scale,
-                          kl_threshold, min_lr, max_lr, lr_multiplier, stats_out_or_null, skip_flag_or_null, guard_record,
-                          num_layers, weights, in_features, out_features, planes, stream);
+int rlg_adam_pack_guarded(const rlg_adam_desc* desc, unsigned* guard_record, int num_layers, const float* const* weights,
+                          const int* in_features, const int* out_features, void* planes, void* stream) {
+  if (!rlg::adam_guard_args_ok(desc, guard_record)) return static_cast<int>(hipErrorInvalidValue);
+  return adam_pack_launch(desc, guard_record, num_layers, weights, in_features, out_features, planes, stream);
 }
 
 }  // extern "C"

@@ -1465,34 +1465,7 @@ int chain_loss_args(LossArgs& loss, const rlg_ppo_loss_desc& d, long long rows) 
   if (d.minibatch != rows || d.actions_num <= 0 || (d.mask_or_null && !d.mask_sum_or_null) || !d.partials ||
       !d.mu || !d.values || !d.d_mu || !d.d_values)
     return static_cast<int>(hipErrorInvalidValue);
-  loss.mu = d.mu;
-  loss.logstd = d.logstd;
-  loss.values = d.values;
-  loss.actions = d.actions;
-  loss.old_neglogp = d.old_neglogp;
-  loss.advantages = d.advantages;
-  loss.old_values = d.old_values;
-  loss.returns = d.returns;
-  loss.old_mu = d.old_mu;
-  loss.old_sigma = d.old_sigma;
-  loss.mask = d.mask_or_null;
-  loss.mask_sum = d.mask_sum_or_null;
-  loss.d_mu = d.d_mu;
-  loss.d_values = d.d_values;
-  loss.partials = d.partials;
-  loss.mb = d.minibatch;
-  loss.A = d.actions_num;
-  loss.ld_mu = d.ld_mu;
-  loss.ld_val = d.ld_values;
-  loss.ld_dmu = d.ld_d_mu;
-  loss.ld_dval = d.ld_d_values;
-  loss.e_clip = d.e_clip;
-  loss.critic_coef = d.critic_coef;
-  loss.bounds_coef = d.bounds_coef;
-  loss.clip_value = d.clip_value;
-  loss.smooth = d.use_smooth_clamp;
-  loss.bound_kind = d.bound_kind;
-  loss.write_back = d.write_back;
+  loss_args_from_desc(loss, d);
   return 0;
 }
 

@@ -189,82 +189,25 @@ int rlg_grad_sumsq(const float* grads, long long n, float grad_scale, double* pa
   RLG_RETURN_LAUNCH_STATUS();
 }
 
-// the launcher of rlg_adam_step and rlg_adam_step_guarded (guard_or_null: AdamArgs::guard)
-static int adam_step_launch(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long long n,
-                            const double* norm_partials_or_null, int norm_blocks, float grad_scale,
-                            float max_norm, double* lr_slots, const long long* step_counter, double beta1,
-                            double beta2, double eps, double weight_decay, int schedule_kind,
-                            const float* kl_or_null, float kl_scale, double kl_threshold, double min_lr,
-                            double max_lr, double lr_multiplier, float* stats_out_or_null,
-                            const unsigned* skip_flag_or_null, unsigned* guard_or_null, void* stream) {
+// the launcher of rlg_adam_step and rlg_adam_step_guarded
+static int adam_step_launch(const rlg_adam_desc* desc, unsigned* guard_or_null, void* stream) {
   using namespace rlg;
-  if (n <= 0 || !step_counter) return static_cast<int>(hipErrorInvalidValue);
-  if (schedule_kind == 1 && !kl_or_null) return static_cast<int>(hipErrorInvalidValue);
   AdamArgs a;
-  a.params = params;
-  a.grads = grads;
-  a.exp_avg = exp_avg;
-  a.exp_avg_sq = exp_avg_sq;
-  a.n = n;
-  a.norm_partials = norm_partials_or_null;
-  a.norm_blocks = norm_blocks;
-  a.grad_scale = grad_scale;
-  a.max_norm = max_norm;
-  a.lr_slots = lr_slots;
-  a.step_counter = step_counter;
-  a.beta1 = beta1;
-  a.beta2 = beta2;
-  a.eps = eps;
-  a.weight_decay = weight_decay;
-  a.schedule_kind = schedule_kind;
-  a.kl = kl_or_null;
-  a.kl_scale = kl_scale;
-  a.kl_threshold = kl_threshold;
-  a.min_lr = min_lr;
-  a.max_lr = max_lr;
-  a.lr_multiplier = lr_multiplier;
-  a.stats_out = stats_out_or_null;
-  a.skip_flag = skip_flag_or_null;
-  a.guard = guard_or_null;
-  RLG_ADAM_TRACE_FILL(a);
-  // one thread per group of 4 parameters + one per tail element (the arenas are 16-byte aligned: torch allocations)
-  if ((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grads) | reinterpret_cast<uintptr_t>(exp_avg) |
-       reinterpret_cast<uintptr_t>(exp_avg_sq)) % 16 != 0)
-    return static_cast<int>(hipErrorInvalidValue);
-  const long long threads = (n >> 2) + (n & 3);
+  if (const int err = adam_args_from_desc(desc, guard_or_null, a)) return err;
+  // one thread per group of 4 parameters + one per tail element
+  const long long threads = (a.n >> 2) + (a.n & 3);
   const long long grid = (threads + kOptBlock - 1) / kOptBlock;
   hipLaunchKernelGGL(adam_step_kernel, dim3(static_cast<int>(grid < 1 ? 1 : grid)), dim3(kOptBlock), 0,
                      static_cast<hipStream_t>(stream), a);
   RLG_RETURN_LAUNCH_STATUS();
 }
 
-int rlg_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long long n,
-                  const double* norm_partials_or_null, int norm_blocks, float grad_scale,
-                  float max_norm, double* lr_slots, const long long* step_counter, double beta1,
-                  double beta2, double eps, double weight_decay, int schedule_kind,
-                  const float* kl_or_null, float kl_scale, double kl_threshold, double min_lr,
-                  double max_lr, double lr_multiplier, float* stats_out_or_null,
-                  const unsigned* skip_flag_or_null, void* stream) {
-  return adam_step_launch(params, grads, exp_avg, exp_avg_sq, n, norm_partials_or_null, norm_blocks, grad_scale, max_norm,
-                          lr_slots, step_counter, beta1, beta2, eps, weight_decay, schedule_kind, kl_or_null, kl_scale,
-                          kl_threshold, min_lr, max_lr, lr_multiplier, stats_out_or_null, skip_flag_or_null, nullptr, stream);
-}
+int rlg_adam_step(const rlg_adam_desc* desc, void* stream) { return adam_step_launch(desc, nullptr, stream); }
 
 // rlg_adam_step under a range-guard record (csrc/range_guard.hip; optim_common.hpp AdamArgs::guard)
-int rlg_adam_step_guarded(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long long n,
-                          const double* norm_partials_or_null, int norm_blocks, float grad_scale,
-                          float max_norm, double* lr_slots, const long long* step_counter, double beta1,
-                          double beta2, double eps, double weight_decay, int schedule_kind,
-                          const float* kl_or_null, float kl_scale, double kl_threshold, double min_lr,
-                          double max_lr, double lr_multiplier, float* stats_out_or_null,
-                          const unsigned* skip_flag_or_null, unsigned* guard_record, void* stream) {
-  // (the guard watches the gradient norm: without the partials it would watch nothing)
-  if (guard_record == nullptr || norm_partials_or_null == nullptr || norm_blocks <= 0)
-    return static_cast<int>(hipErrorInvalidValue);
-  return adam_step_launch(params, grads, exp_avg, exp_avg_sq, n, norm_partials_or_null, norm_blocks, grad_scale, max_norm,
-                          lr_slots, step_counter, beta1, beta2, eps, weight_decay, schedule_kind, kl_or_null, kl_scale,
-                          kl_threshold, min_lr, max_lr, lr_multiplier, stats_out_or_null, skip_flag_or_null, guard_record,
-                          stream);
+int rlg_adam_step_guarded(const rlg_adam_desc* desc, unsigned* guard_record, void* stream) {
+  if (!rlg::adam_guard_args_ok(desc, guard_record)) return static_cast<int>(hipErrorInvalidValue);
+  return adam_step_launch(desc, guard_record, stream);
 }
 
 }  // extern "C"

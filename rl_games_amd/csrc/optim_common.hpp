@@ -7,27 +7,26 @@
 
 namespace rlg {
 
+// The kernels' argument: the fields of rlg_adam_desc (include/rlg_hip.h documents each of them) and the guard record.
 struct AdamArgs {
   float* params;
-  float* grads;            // overwritten with the scaled/clipped gradient (like clip_grad_norm_)
+  float* grads;
   float* exp_avg;
   float* exp_avg_sq;
   long long n;
-  const double* norm_partials;  // [norm_blocks] from grad_sumsq_kernel, or nullptr (no truncation)
+  const double* norm_partials;
   int norm_blocks;
-  float grad_scale;        // 1/world_size (multi-GPU average), 1 otherwise
-  float max_norm;          // grad_norm
-  double* lr_slots;        // [2] fp64; slot (step-1)&1 is read, the other receives the next lr
-  const long long* step_counter;  // device: Adam step count AFTER this update (1-based)
+  float grad_scale;
+  float max_norm;
+  double* lr_slots;
+  const long long* step_counter;
   double beta1, beta2, eps, weight_decay;
-  // adaptive schedule (schedule_kind 1) driven by the KL of THIS minibatch
-  int schedule_kind;       // 0 keep lr, 1 adaptive on *kl
-  const float* kl;         // device scalar (already averaged over ranks)
-  float kl_scale;          // 1/world_size when kl holds a cross-rank SUM
+  int schedule_kind;
+  const float* kl;
+  float kl_scale;
   double kl_threshold, min_lr, max_lr, lr_multiplier;
-  float* stats_out;        // [4]: total_norm, clip_coef, lr used, lr next
-  const unsigned* skip_flag;  // device word or nullptr; non-zero: the gradients are invalid (a failed in-graph
-                              // all-reduce) - nothing is updated, the learning rate is carried over unchanged
+  float* stats_out;
+  const unsigned* skip_flag;
   unsigned* guard;         // range-guard record (csrc/range_guard.hip: [0] tag, 0 = clear, [1] index) or nullptr.  With a
                            // record the launch is skipped as under skip_flag when the record is set or the total gradient
                            // norm is not finite, and block 0 then records (RLG_GUARD_TAG_ADAM, step) in a clear record
@@ -112,3 +111,49 @@ __device__ __forceinline__ void adam_finish(const AdamArgs& a, int cur, double l
 }  // namespace rlg
 
 #include "adam_trace.hpp"
+
+namespace rlg {
+
+// Host: what every rlg_adam_* entry does with its descriptor - reject what no launch may see, then fill the kernels'
+// argument (guard_or_null: AdamArgs::guard).  0 or hipErrorInvalidValue.
+inline int adam_args_from_desc(const rlg_adam_desc* d, unsigned* guard_or_null, AdamArgs& a) {
+  if (d == nullptr || d->n <= 0 || !d->step_counter) return static_cast<int>(hipErrorInvalidValue);
+  if (d->schedule_kind == 1 && !d->kl_or_null) return static_cast<int>(hipErrorInvalidValue);
+  // (one thread per group of 4 parameters, 16-byte loads: torch allocations are aligned)
+  if ((reinterpret_cast<uintptr_t>(d->params) | reinterpret_cast<uintptr_t>(d->grads) |
+       reinterpret_cast<uintptr_t>(d->exp_avg) | reinterpret_cast<uintptr_t>(d->exp_avg_sq)) % 16 != 0)
+    return static_cast<int>(hipErrorInvalidValue);
+  a.params = d->params;
+  a.grads = d->grads;
+  a.exp_avg = d->exp_avg;
+  a.exp_avg_sq = d->exp_avg_sq;
+  a.n = d->n;
+  a.norm_partials = d->norm_partials_or_null;
+  a.norm_blocks = d->norm_blocks;
+  a.grad_scale = d->grad_scale;
+  a.max_norm = d->max_norm;
+  a.lr_slots = d->lr_slots;
+  a.step_counter = d->step_counter;
+  a.beta1 = d->beta1;
+  a.beta2 = d->beta2;
+  a.eps = d->eps;
+  a.weight_decay = d->weight_decay;
+  a.schedule_kind = d->schedule_kind;
+  a.kl = d->kl_or_null;
+  a.kl_scale = d->kl_scale;
+  a.kl_threshold = d->kl_threshold;
+  a.min_lr = d->min_lr;
+  a.max_lr = d->max_lr;
+  a.lr_multiplier = d->lr_multiplier;
+  a.stats_out = d->stats_out_or_null;
+  a.skip_flag = d->skip_flag_or_null;
+  a.guard = guard_or_null;
+  RLG_ADAM_TRACE_FILL(a);
+  return 0;
+}
+// the guarded entries' own condition: a record, and the norm partials it watches (without them it would watch nothing)
+inline bool adam_guard_args_ok(const rlg_adam_desc* d, const unsigned* guard_record) {
+  return guard_record != nullptr && d != nullptr && d->norm_partials_or_null != nullptr && d->norm_blocks > 0;
+}
+
+}  // namespace rlg

@@ -310,46 +310,13 @@ int rlg_ppo_loss_num_blocks(int minibatch) {
 
 int rlg_ppo_loss_partials_per_block(int actions) { return rlg::kLossScalars + 2 * actions; }
 
-int rlg_ppo_loss_fused(const float* mu, const float* logstd, const float* values,
-                       const float* actions, const float* old_neglogp, const float* advantages,
-                       const float* old_values, const float* returns, float* old_mu,
-                       float* old_sigma, const float* mask_or_null, const float* mask_sum_or_null,
-                       float* d_mu, float* d_values, double* partials, int minibatch, int actions_num,
-                       int ld_mu, int ld_values, int ld_d_mu, int ld_d_values, float e_clip,
-                       float critic_coef, float bounds_coef, int clip_value, int use_smooth_clamp,
-                       int bound_kind, int write_back, void* stream) {
+int rlg_ppo_loss_fused(const rlg_ppo_loss_desc* desc, void* stream) {
   using namespace rlg;
-  if (minibatch <= 0 || actions_num <= 0) return static_cast<int>(hipErrorInvalidValue);
-  if (mask_or_null && !mask_sum_or_null) return static_cast<int>(hipErrorInvalidValue);
+  if (desc == nullptr || desc->minibatch <= 0 || desc->actions_num <= 0) return static_cast<int>(hipErrorInvalidValue);
+  if (desc->mask_or_null && !desc->mask_sum_or_null) return static_cast<int>(hipErrorInvalidValue);
   LossArgs p;
-  p.mu = mu;
-  p.logstd = logstd;
-  p.values = values;
-  p.actions = actions;
-  p.old_neglogp = old_neglogp;
-  p.advantages = advantages;
-  p.old_values = old_values;
-  p.returns = returns;
-  p.old_mu = old_mu;
-  p.old_sigma = old_sigma;
-  p.mask = mask_or_null;
-  p.mask_sum = mask_sum_or_null;
-  p.d_mu = d_mu;
-  p.d_values = d_values;
-  p.partials = partials;
-  p.mb = minibatch;
-  p.A = actions_num;
-  p.ld_mu = ld_mu;
-  p.ld_val = ld_values;
-  p.ld_dmu = ld_d_mu;
-  p.ld_dval = ld_d_values;
-  p.e_clip = e_clip;
-  p.critic_coef = critic_coef;
-  p.bounds_coef = bounds_coef;
-  p.clip_value = clip_value;
-  p.smooth = use_smooth_clamp;
-  p.bound_kind = bound_kind;
-  p.write_back = write_back;
+  loss_args_from_desc(p, *desc);
+  const int minibatch = p.mb, actions_num = p.A;
   const int tile_rows = loss_tile_rows(minibatch);
   const size_t shm = ppo_loss_lds_bytes(tile_rows, actions_num);
   if (shm > 160 * 1024) return static_cast<int>(hipErrorInvalidValue);
@@ -428,43 +395,12 @@ int rlg_ppo_loss_discrete_nlp(const float* logits, long long ld_logits, const fl
   RLG_RETURN_LAUNCH_STATUS();
 }
 
-int rlg_ppo_loss_discrete_strided(const float* logits, long long ld_logits, const float* values, long long ld_values,
-                                  const long long* actions, const unsigned char* action_masks_or_null,
-                                  const int* branch_sizes, int num_branches, const float* old_neglogp,
-                                  const float* advantages, const float* old_values, const float* returns,
-                                  const float* mask_or_null, const float* mask_sum_or_null, float* d_logits,
-                                  long long ld_d_logits, float* d_values, long long ld_d_values, double* partials,
-                                  int minibatch, float e_clip, float critic_coef, float entropy_coef, int clip_value,
-                                  int use_smooth_clamp, void* stream) {
-  return rlg_ppo_loss_discrete_nlp(logits, ld_logits, values, ld_values, actions, action_masks_or_null, branch_sizes,
-                                   num_branches, old_neglogp, advantages, old_values, returns, mask_or_null,
-                                   mask_sum_or_null, d_logits, ld_d_logits, d_values, ld_d_values, partials, minibatch,
-                                   e_clip, critic_coef, entropy_coef, clip_value, use_smooth_clamp, nullptr, stream);
-}
-
-int rlg_ppo_loss_discrete(const float* logits, long long ld_logits, const float* values,
-                          const long long* actions, const unsigned char* action_masks_or_null,
-                          const int* branch_sizes, int num_branches, const float* old_neglogp,
-                          const float* advantages, const float* old_values, const float* returns,
-                          const float* mask_or_null, const float* mask_sum_or_null, float* d_logits,
-                          float* d_values, double* partials, int minibatch, float e_clip, float critic_coef,
-                          float entropy_coef, int clip_value, int use_smooth_clamp, void* stream) {
-  long long n = 0;
-  for (int b = 0; b < num_branches && b < rlg::kMaxBranches; ++b) n += branch_sizes[b];
-  return rlg_ppo_loss_discrete_strided(logits, ld_logits, values, 1, actions, action_masks_or_null, branch_sizes,
-                                       num_branches, old_neglogp, advantages, old_values, returns, mask_or_null,
-                                       mask_sum_or_null, d_logits, n, d_values, 1, partials, minibatch, e_clip,
-                                       critic_coef, entropy_coef, clip_value, use_smooth_clamp, stream);
-}
-
-int rlg_ppo_loss_finalize(const double* partials, int num_blocks, int actions_num, int minibatch,
-                          int masked, float critic_coef, float entropy_coef, float bounds_coef,
-                          float* scalars8, float* d_logstd, float* kl_slot_or_null,
-                          float* d_mu_bias_or_null, float* d_value_bias_or_null, void* stream) {
-  hipLaunchKernelGGL(rlg::ppo_loss_finalize_kernel, dim3(1), dim3(1024), 0,
-                     static_cast<hipStream_t>(stream), partials, num_blocks, actions_num, minibatch,
-                     masked, critic_coef, entropy_coef, bounds_coef, scalars8, d_logstd,
-                     kl_slot_or_null, d_mu_bias_or_null, d_value_bias_or_null);
+int rlg_ppo_loss_finalize(const rlg_loss_finalize_desc* desc, void* stream) {
+  if (desc == nullptr) return static_cast<int>(hipErrorInvalidValue);
+  hipLaunchKernelGGL(rlg::ppo_loss_finalize_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream),
+                     desc->partials, desc->num_blocks, desc->actions_num, desc->minibatch, desc->masked,
+                     desc->critic_coef, desc->entropy_coef, desc->bounds_coef, desc->scalars8, desc->d_logstd,
+                     desc->kl_slot_or_null, desc->d_mu_bias_or_null, desc->d_value_bias_or_null);
   RLG_RETURN_LAUNCH_STATUS();
 }
 

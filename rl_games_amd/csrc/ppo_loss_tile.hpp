@@ -3,6 +3,7 @@
 #pragma once
 
 #include "rlg_device.hpp"
+#include "rlg_hip.h"
 
 namespace rlg {
 
@@ -51,6 +52,39 @@ struct LossArgs {
   int bound_kind;          // 0 none (coef None), 1 'bound', 2 'regularisation'
   int write_back;          // overwrite old_mu/old_sigma with the new policy's
 };
+
+// Host: the kernels' argument from the C ABI's descriptor.  What a launch rejects is its caller's business
+// (rlg_ppo_loss_fused, chain_loss_args).
+inline void loss_args_from_desc(LossArgs& loss, const rlg_ppo_loss_desc& d) {
+  loss.mu = d.mu;
+  loss.logstd = d.logstd;
+  loss.values = d.values;
+  loss.actions = d.actions;
+  loss.old_neglogp = d.old_neglogp;
+  loss.advantages = d.advantages;
+  loss.old_values = d.old_values;
+  loss.returns = d.returns;
+  loss.old_mu = d.old_mu;
+  loss.old_sigma = d.old_sigma;
+  loss.mask = d.mask_or_null;
+  loss.mask_sum = d.mask_sum_or_null;
+  loss.d_mu = d.d_mu;
+  loss.d_values = d.d_values;
+  loss.partials = d.partials;
+  loss.mb = d.minibatch;
+  loss.A = d.actions_num;
+  loss.ld_mu = d.ld_mu;
+  loss.ld_val = d.ld_values;
+  loss.ld_dmu = d.ld_d_mu;
+  loss.ld_dval = d.ld_d_values;
+  loss.e_clip = d.e_clip;
+  loss.critic_coef = d.critic_coef;
+  loss.bounds_coef = d.bounds_coef;
+  loss.clip_value = d.clip_value;
+  loss.smooth = d.use_smooth_clamp;
+  loss.bound_kind = d.bound_kind;
+  loss.write_back = d.write_back;
+}
 
 __device__ __forceinline__ float smooth_clamp_f(float x, float mi, float mx) {
   // 1/(1 + exp((-(x-mi)/(mx-mi)+0.5)*4)) * (mx-mi) + mi          common_losses.py:32-36

@@ -519,30 +519,20 @@ def ppo_loss_fused(mu, logstd, values, actions, old_neglogp, advantages, old_val
                    mask_sum=None):
     """mu/d_mu [mb, A] and values/d_values [mb] may be strided row views (fused head buffer)."""
     lib = _lib.load()
-    mb, A = mu.shape
-    mu_p, ld_mu = _rows_view(mu, 'mu')
-    val_p, ld_val = _rows_view(values, 'values')
-    dmu_p, ld_dmu = _rows_view(d_mu, 'd_mu')
-    dval_p, ld_dval = _rows_view(d_values, 'd_values')
-    _lib.check(lib.rlg_ppo_loss_fused(
-        mu_p, _need(logstd, F32, 'logstd'), val_p,
-        _need(actions, F32, 'actions'), _need(old_neglogp, F32, 'old_neglogp'),
-        _need(advantages, F32, 'advantages'), _need(old_values, F32, 'old_values'),
-        _need(returns, F32, 'returns'), _need(old_mu, F32, 'old_mu'), _need(old_sigma, F32, 'old_sigma'),
-        _opt(mask, F32, 'mask'), _opt(mask_sum, F32, 'mask_sum'), dmu_p,
-        dval_p, _need(partials, F64, 'partials'), mb, A, ld_mu, ld_val, ld_dmu, ld_dval,
-        float(np.float32(e_clip)), float(np.float32(critic_coef)), float(np.float32(bounds_coef)),
-        1 if clip_value else 0, _surrogate_kind(smooth), bound_kind, 1 if write_back else 0, _stream(mu)),
-        'rlg_ppo_loss_fused')
+    desc = ppo_loss_desc(mu, logstd, values, actions, old_neglogp, advantages, old_values, returns, old_mu, old_sigma,
+                         d_mu, d_values, partials, e_clip, critic_coef, bounds_coef, clip_value, smooth, bound_kind,
+                         write_back, mask, mask_sum)
+    _lib.check(lib.rlg_ppo_loss_fused(ctypes.addressof(desc), _stream(mu)), 'rlg_ppo_loss_fused')
 
 
 def ppo_loss_desc(mu, logstd, values, actions, old_neglogp, advantages, old_values, returns,
                   old_mu, old_sigma, d_mu, d_values, partials, e_clip, critic_coef, bounds_coef,
                   clip_value=True, smooth=False, bound_kind=1, write_back=True, mask=None, mask_sum=None):
-    """The arguments of ppo_loss_fused as an rlg_ppo_loss_desc for MlpChain.backward(ppo_loss=...): the
-    backward launch evaluates the loss of each row tile in front of its own work.  d_mu / d_values must be
-    views of the d_heads tensor that backward then reads; partials needs MlpChain.num_blocks(rows, 1)
-    rows.  The descriptor keeps no tensor alive - the caller does (they are the step's static buffers)."""
+    """The arguments of the loss as an rlg_ppo_loss_desc: what ppo_loss_fused launches, and for
+    MlpChain.backward(ppo_loss=...) the loss the backward launch evaluates for each row tile in front of its own
+    work.  There d_mu / d_values must be views of the d_heads tensor that backward then reads, and partials needs
+    MlpChain.num_blocks(rows, 1) rows.  The descriptor keeps no tensor alive - the caller does (they are the step's
+    static buffers)."""
     mb, A = mu.shape
     mu_p, ld_mu = _rows_view(mu, 'mu')
     val_p, ld_val = _rows_view(values, 'values')
@@ -694,13 +684,9 @@ def ppo_diag_moments(table, values, returns, slices, rows, partials, tickets, ma
 def ppo_loss_finalize(partials, num_blocks, actions_num, minibatch, masked, critic_coef,
                       entropy_coef, bounds_coef, scalars, d_logstd, kl_slot=None, d_mu_bias=None,
                       d_value_bias=None):
-    lib = _lib.load()
-    _lib.check(lib.rlg_ppo_loss_finalize(
-        _need(partials, F64, 'partials'), num_blocks, actions_num, minibatch, 1 if masked else 0,
-        float(np.float32(critic_coef)), float(np.float32(entropy_coef)), float(np.float32(bounds_coef)),
-        _need(scalars, F32, 'scalars'), _need(d_logstd, F32, 'd_logstd'),
-        _opt(kl_slot, F32, 'kl_slot'), _opt(d_mu_bias, F32, 'd_mu_bias'),
-        _opt(d_value_bias, F32, 'd_value_bias'), _stream(partials)), 'rlg_ppo_loss_finalize')
+    ppo_loss_finalize_from(loss_finalize_desc(partials, num_blocks, actions_num, minibatch, masked, critic_coef,
+                                              entropy_coef, bounds_coef, scalars, d_logstd, kl_slot, d_mu_bias,
+                                              d_value_bias), partials.device)
 
 
 def loss_finalize_desc(partials, num_blocks, actions_num, minibatch, masked, critic_coef, entropy_coef,
@@ -715,10 +701,8 @@ def loss_finalize_desc(partials, num_blocks, actions_num, minibatch, masked, cri
 
 
 def ppo_loss_finalize_from(desc, device):
-    _lib.check(_lib.load().rlg_ppo_loss_finalize(
-        desc.partials, desc.num_blocks, desc.actions_num, desc.minibatch, desc.masked, desc.critic_coef,
-        desc.entropy_coef, desc.bounds_coef, desc.scalars8, desc.d_logstd, desc.kl_slot_or_null,
-        desc.d_mu_bias_or_null, desc.d_value_bias_or_null, _lib.stream_handle(device)), 'rlg_ppo_loss_finalize')
+    _lib.check(_lib.load().rlg_ppo_loss_finalize(ctypes.addressof(desc), _lib.stream_handle(device)),
+               'rlg_ppo_loss_finalize')
 
 
 # ------------------------------------------------------------------ manual MLP backward
@@ -792,7 +776,7 @@ def _adam_launch(guard, params, grads, exp_avg, exp_avg_sq, norm_partials, grad_
                  betas, eps, weight_decay, schedule_kind, kl, kl_scale, kl_threshold, min_lr, max_lr, lr_multiplier,
                  stats_out, skip_flag, pack):
     lib = _lib.load()
-    args = (
+    desc = _lib.AdamDesc(
         _need(params, F32, 'params'), _need(grads, F32, 'grads'), _need(exp_avg, F32, 'exp_avg'),
         _need(exp_avg_sq, F32, 'exp_avg_sq'), params.numel(), _opt(norm_partials, F64, 'norm_partials'),
         0 if norm_partials is None else norm_partials.numel(), float(np.float32(grad_scale)),
@@ -801,8 +785,7 @@ def _adam_launch(guard, params, grads, exp_avg, exp_avg_sq, norm_partials, grad_
         float(betas[0]), float(betas[1]), float(eps), float(weight_decay), schedule_kind,
         _opt(kl, F32, 'kl'), float(np.float32(kl_scale)), float(kl_threshold), float(min_lr),
         float(max_lr), float(lr_multiplier), _opt(stats_out, F32, 'stats_out'), skip_flag)
-    if guard is not None:
-        args = args + (_guard_ptr(guard),)
+    args = (ctypes.addressof(desc),) if guard is None else (ctypes.addressof(desc), _guard_ptr(guard))
     names = ('rlg_adam_step', 'rlg_adam_step_pack') if guard is None else ('rlg_adam_step_guarded', 'rlg_adam_pack_guarded')
     if pack is not None:
         n, w, ins, outs, planes = pack

@@ -33,6 +33,19 @@ def test_binding_table_matches_header():
     assert sorted(_lib.exported_prototypes()) == _declared_symbols()
 
 
+def test_descriptor_classes_have_the_sizes_the_header_asserts():
+    """RLG_ABI_SIZE(struct, bytes) in include/rlg_hip.h is a static assertion of every build; the ctypes mirror of each
+    descriptor must be as large, or a field is missing, misplaced or of another type."""
+    import ctypes
+    from rl_games_amd import _lib
+    text = open(os.path.join(ROOT, 'include', 'rlg_hip.h')).read()
+    sizes = {name: int(n) for name, n in re.findall(r'^RLG_ABI_SIZE\((\w+), (\d+)\);', text, flags=re.M)}
+    assert sizes == {'rlg_adam_desc': 184, 'rlg_ppo_loss_desc': 176, 'rlg_loss_finalize_desc': 80}
+    assert ctypes.sizeof(_lib.AdamDesc) == sizes['rlg_adam_desc']
+    assert ctypes.sizeof(_lib.PpoLossDesc) == sizes['rlg_ppo_loss_desc']
+    assert ctypes.sizeof(_lib.LossFinalizeDesc) == sizes['rlg_loss_finalize_desc']
+
+
 def test_host_queries_without_gpu():
     from rl_games_amd import _lib
     lib = _lib.load()

@@ -12,6 +12,9 @@ instead of handing fake addresses to a device.  `python tests/test_chain_entry_e
 library that RLG_HIP_LIB selects (one JSON object), which is how two builds are compared.
 
 The expected values are the answers of the library before the entry points shared their argument setup.
+
+The two stand-alone loss entries take the same kind of descriptor (rlg_ppo_loss_fused the chain's own) and are asked
+beside them, in the same child: no descriptor, and what rlg_ppo_loss_fused itself rejects.
 """
 import ctypes
 import json
@@ -123,7 +126,13 @@ _ENTRIES = {
 }
 
 
+_LOSS_ENTRIES = ('ppo_loss_fused', 'ppo_loss_finalize')      # (descriptor, stream)
+
+
 def _call(lib, entry, **over):
+    if entry in _LOSS_ENTRIES:
+        desc = over['desc']
+        return getattr(lib, 'rlg_' + entry)(None if desc is None else ctypes.byref(desc), None)
     order, base = _ENTRIES[entry]
     kw = base()
     unknown = set(over) - set(kw)
@@ -212,6 +221,14 @@ def _rows():
     row('step: a minibatch of the 64-row kernels', NOT_SUPPORTED, 'step', rows=16384, ppo_loss=_desc(minibatch=16384))
     row('step_lean: no forward fragments', NOT_SUPPORTED, 'step_lean', frags_fwd=None)
     row('step_lean: no backward fragments', NOT_SUPPORTED, 'step_lean', frags_bwd=None)
+    # ---- the stand-alone loss launches
+    for e in _LOSS_ENTRIES:
+        row(f'{e}: NULL descriptor', INVALID, e, desc=None)
+    row('ppo_loss_fused: minibatch 0', INVALID, 'ppo_loss_fused', desc=_desc(minibatch=0))
+    row('ppo_loss_fused: descriptor without actions', INVALID, 'ppo_loss_fused', desc=_desc(actions_num=0))
+    row('ppo_loss_fused: descriptor with a mask and no mask sum', INVALID, 'ppo_loss_fused',
+        desc=_desc(mask_or_null=_addr(250)))
+    row('ppo_loss_fused: a loss tile beyond LDS', INVALID, 'ppo_loss_fused', desc=_desc(**_BIG_LOSS))
     # ---- the one-shot request for gradient maxima (rlg_mlp_chain_gradient_maxima): rlg_mlp_chain_backward takes it at
     # its very top, the lean backward late - a request that a declined lean call left pending is still there for the next
     # call, and rlg_mlp_chain_backward clears it whatever else it does.  A taken request with too few entries per

@@ -1,9 +1,10 @@
 """CPU: what rlg_adam_step and rlg_adam_step_pack answer to malformed calls.
 
-Both validate their arguments on the host and return hipErrorInvalidValue (1) before they ask the HIP runtime for
-anything, so the answers do not depend on a device being there.  Every row below differs from a well-formed call in one
-argument.  The pointers are small fake aligned addresses - the host code dereferences none of them (the pack form reads
-the `weights`, `in_features` and `out_features` tables, which are real host arrays).
+Both take the step as an rlg_adam_desc, validate it and their own arguments on the host and return hipErrorInvalidValue
+(1) before they ask the HIP runtime for anything, so the answers do not depend on a device being there.  Every row below
+differs from a well-formed call in one argument or descriptor field, or passes no descriptor at all.  The pointers are
+small fake aligned addresses - the host code dereferences none of them (the pack form reads the `weights`, `in_features`
+and `out_features` tables, which are real host arrays).
 
 As in tests/test_chain_entry_errors_cpu.py the table runs in a child process that sees no GPU: should a row ever get
 past validation, its launch fails there instead of handing fake addresses to a device.
@@ -31,8 +32,12 @@ def _base():
                 stats_out=ARENA + 0x500300, skip_flag=None)
 
 
-_ORDER = ('params grads exp_avg exp_avg_sq n norm_partials norm_blocks grad_scale max_norm lr_slots step_counter beta1 '
-          'beta2 eps weight_decay schedule_kind kl kl_scale kl_threshold min_lr max_lr lr_multiplier stats_out skip_flag')
+def adam_desc(kw):
+    """_lib.AdamDesc from a dict keyed like _base() (the `_or_null` of a field name left off)"""
+    from rl_games_amd import _lib
+    fields = [f for f, _ in _lib.AdamDesc._fields_]
+    assert {f.replace('_or_null', '') for f in fields} == set(kw), sorted(kw)
+    return _lib.AdamDesc(**{f: kw[f.replace('_or_null', '')] for f in fields})
 
 
 def _offsets(ins=IN, outs=OUT):
@@ -54,9 +59,10 @@ def _pack_side(ins=IN, outs=OUT, offsets=None, num_layers=None, planes=ARENA + 0
 
 
 def _rows():
-    """(id, entry, overrides of the adam arguments, overrides of the pack arguments)"""
+    """(id, entry, overrides of the descriptor's fields - None: no descriptor -, overrides of the pack arguments)"""
     t = []
     for entry in ('adam_step', 'adam_step_pack'):
+        t.append((f'{entry}: NULL descriptor', entry, None, {}))
         t.append((f'{entry}: n 0', entry, dict(n=0), {}))
         t.append((f'{entry}: n negative', entry, dict(n=-N), {}))
         t.append((f'{entry}: no step counter', entry, dict(step_counter=None), {}))
@@ -85,10 +91,13 @@ def run_table():
     codes = {}
     for name, entry, over, pack_over in _rows():
         assert name not in codes, name
-        kw = _base()
-        assert not set(over) - set(kw)
-        kw.update(over)
-        args = [kw[k] for k in _ORDER.split()]
+        desc = None
+        if over is not None:
+            kw = _base()
+            assert not set(over) - set(kw)
+            kw.update(over)
+            desc = adam_desc(kw)
+        args = [None if desc is None else ctypes.addressof(desc)]
         if entry == 'adam_step_pack':
             side = _pack_side(**pack_over)
             args += [side[k] for k in ('num_layers', 'weights', 'in_features', 'out_features', 'planes')]
@@ -104,7 +113,7 @@ def test_malformed_optimiser_calls_are_rejected_before_any_launch():
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     codes = json.loads(out.stdout.strip().splitlines()[-1])
     names = [name for name, _, _, _ in _rows()]
-    assert len(names) == 24 and set(codes) == set(names)
+    assert len(names) == 26 and set(codes) == set(names)
     wrong = {name: codes[name] for name in names if codes[name] != INVALID}
     assert not wrong, f'rows that were not answered with hipErrorInvalidValue: {wrong}'
 

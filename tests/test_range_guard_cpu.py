@@ -25,7 +25,8 @@ A = 0x10000000                    # fake 16-byte aligned device addresses at 1 M
 N = 12 * 64 + 64 + 64 * 32 + 32   # the [12 -> 64 -> 32] net of the pack rows, every matrix followed by its bias
 
 
-def _adam_args(**over):
+def _adam_args(desc=True, **over):
+    """[address of an rlg_adam_desc (desc=False: NULL), guard record]"""
     kw = dict(params=A, grads=A + 0x100000, exp_avg=A + 0x200000, exp_avg_sq=A + 0x300000, n=N,
               norm_partials=A + 0x400000, norm_blocks=4, grad_scale=1.0, max_norm=1.0, lr_slots=A + 0x500000,
               step_counter=A + 0x500100, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, schedule_kind=1,
@@ -33,7 +34,16 @@ def _adam_args(**over):
               stats_out=A + 0x500300, skip_flag=None, guard=A + 0x500400)
     assert not set(over) - set(kw)
     kw.update(over)
-    return list(kw.values())
+    guard = kw.pop('guard')
+    if not desc:
+        return [None, guard]
+    from test_optim_entry_errors_cpu import adam_desc
+    d = adam_desc(kw)
+    _KEEP.append(d)
+    return [ctypes.addressof(d), guard]
+
+
+_KEEP = []                        # the descriptors of the rows stay alive until the table has run
 
 
 def _pack_side(planes=A + 0x600000, num_layers=2):
@@ -70,6 +80,7 @@ def _rows():
          ('range_scan: an array that is not 4-byte aligned', 'range_scan', _scan_args(arrays=(A + 2, A + 0x100000))),
          ('range_scan: arrays without their tables', 'range_scan', _scan_args(tables=False))]
     for entry, tail in (('adam_step_guarded', []), ('adam_pack_guarded', _pack_side())):
+        t.append((f'{entry}: NULL descriptor', entry, _adam_args(desc=False) + tail))
         t.append((f'{entry}: no guard record', entry, _adam_args(guard=None) + tail))
         t.append((f'{entry}: no norm partials (nothing to watch)', entry, _adam_args(norm_partials=None, norm_blocks=0) + tail))
         t.append((f'{entry}: n 0', entry, _adam_args(n=0) + tail))
@@ -107,7 +118,7 @@ def test_malformed_guard_calls_are_rejected_before_any_launch():
     codes = json.loads(out.stdout.strip().splitlines()[-1])
     assert codes.pop('range_scan: zero arrays') == 0
     names = [name for name, _, _ in _rows()]
-    assert len(names) == 27 and set(codes) == set(names)
+    assert len(names) == 29 and set(codes) == set(names)
     wrong = {name: codes[name] for name in names if codes[name] != INVALID}
     assert not wrong, f'rows that were not answered with hipErrorInvalidValue: {wrong}'
 
