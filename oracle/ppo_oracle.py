@@ -328,7 +328,9 @@ def distribution_loss_and_grads(mu, logstd, values, batch, hp, mask=None):
     """Forward + autograd backward of the model epilogue + calc_losses, from the network
     outputs (mu [mb,A], logstd [A] fixed-sigma parameter, values [mb,1]) down to scalars.
     models.py:329-347 + a2c_continuous.py:97-134,215-221.  Returns dict of scalars and
-    d loss / d{mu, logstd, values}."""
+    d loss / d{mu, logstd, values}.  'rows': the per-row terms whose (masked) means the scalars are - a (actor), c (critic),
+    entropy, b (bound), kl, each [mb] - and 'd_neglogp' [mb] = d loss / d neglogp of every row (the kernels' row
+    coefficient: d loss / d logstd_a = sum_i d_neglogp_i (1 - z_ia^2) - entropy_coef * sum_i w_i)."""
     mu = mu.detach().clone().requires_grad_(True)
     logstd = logstd.detach().clone().requires_grad_(True)
     values = values.detach().clone().requires_grad_(True)
@@ -336,6 +338,7 @@ def distribution_loss_and_grads(mu, logstd, values, batch, hp, mask=None):
     sigma = mu * 0 + sigma_row                                   # network_builder.py:512
     ent = normal_entropy(mu, sigma)
     nlp = torch.squeeze(neglogp(batch['actions'], mu, sigma, mu * 0 + logstd))
+    nlp.retain_grad()
     loss, a, c, e, b = ppo_losses(
         batch['old_logp_actions'], nlp, batch['advantages'], batch['old_values'], values,
         batch['returns'], mu, ent, hp['e_clip'], hp['critic_coef'], hp['entropy_coef'],
@@ -344,10 +347,25 @@ def distribution_loss_and_grads(mu, logstd, values, batch, hp, mask=None):
     loss.backward()
     with torch.no_grad():
         kl = policy_kl(mu.detach(), sigma.detach(), batch['mu'], batch['sigma'], mask)
+        mb = mu.shape[0]
+        coef_b = hp.get('bounds_loss_coef')
+        rows = {
+            'a': actor_loss(batch['old_logp_actions'], nlp, batch['advantages'], hp['e_clip'], hp.get('ppo', True),
+                            hp.get('use_smooth_clamp', False)).reshape(mb),
+            'c': critic_loss(batch['old_values'], values, hp['e_clip'], batch['returns'],
+                             hp.get('clip_value', True)).reshape(mb),
+            'entropy': ent.reshape(mb),
+            'b': torch.zeros_like(ent).reshape(mb) if coef_b is None
+            else bound_loss(mu, hp.get('bound_loss_type', 'bound')).reshape(mb),
+            'kl': (torch.log(batch['sigma'] / sigma + 1e-5)
+                   + (sigma ** 2 + (batch['mu'] - mu) ** 2) / (2.0 * (batch['sigma'] ** 2 + 1e-5))
+                   + (-1.0 / 2.0)).sum(dim=-1).reshape(mb),
+        }
+        rows = {k: v.detach().clone() for k, v in rows.items()}
     return {'loss': loss.detach(), 'a_loss': a.detach(), 'c_loss': c.detach(),
             'entropy': e.detach(), 'b_loss': b.detach(), 'kl': kl, 'neglogp': nlp.detach(),
             'sigma': sigma.detach(), 'd_mu': mu.grad, 'd_logstd': logstd.grad,
-            'd_values': values.grad}
+            'd_values': values.grad, 'rows': rows, 'd_neglogp': nlp.grad.reshape(mb)}
 
 
 def masked_categorical(logits, masks=None):

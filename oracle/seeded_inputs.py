@@ -16,6 +16,46 @@ def gae_inputs(horizon, num_envs, value_size, seed=0, p_done=0.15):
     return rewards, values, dones, last_values, last_dones
 
 
+# ------------------------------------------------------------------ PPO loss
+def loss_inputs(mb, A, seed, mu=None, values=None):
+    """SURVEY 8d kernel-level inputs of the continuous PPO loss: (mu [mb, A], logstd [A], values [mb, 1], batch) with the
+    batch keys of the oracle (ppo_oracle.distribution_loss_and_grads).  Both clip sides fire (old neglogp = new neglogp +
+    0.2 N(0, 1): ratios on both sides of [1 - e, 1 + e] and inside it) and the bound loss is active (|mu| > 1.1 in places).
+    mu / values given (a network's outputs): the same draws in the same order, the OLD policy and the old values are then
+    placed around them instead of the new ones around the old."""
+    from oracle import ppo_oracle as O
+    gen = torch.Generator().manual_seed(seed)
+    old_nlp = torch.randn(mb, generator=gen)
+    batch = {
+        'old_logp_actions': old_nlp,
+        'advantages': torch.randn(mb, generator=gen),
+        'old_values': torch.randn(mb, 1, generator=gen),
+        'returns': torch.randn(mb, 1, generator=gen),
+        'actions': torch.randn(mb, A, generator=gen),
+        'mu': 1.2 * torch.randn(mb, A, generator=gen),
+        'sigma': torch.exp(0.1 * torch.randn(mb, A, generator=gen)),
+    }
+    d_mu = 0.1 * torch.randn(mb, A, generator=gen)
+    logstd = 0.1 * torch.randn(A, generator=gen)
+    d_values = 0.3 * torch.randn(mb, 1, generator=gen)
+    if mu is None:
+        mu = batch['mu'] + d_mu
+    else:
+        mu = mu.detach().clone().reshape(mb, A)
+        batch['mu'] = mu - d_mu
+    if values is None:
+        values = batch['old_values'] + d_values
+    else:
+        values = values.detach().clone().reshape(mb, 1)
+        batch['old_values'] = values - d_values
+    # make neglogp land near old_neglogp so that ratios straddle the clip range
+    with torch.no_grad():
+        sigma = torch.exp(logstd)
+        nlp = O.neglogp(batch['actions'], mu, mu * 0 + sigma, mu * 0 + logstd)
+        batch['old_logp_actions'] = nlp + 0.2 * torch.randn(mb, generator=gen)
+    return mu, logstd, values, batch
+
+
 # ------------------------------------------------------------------ optimiser step
 # (length, truncation, weight_decay, grad_scale, betas, eps, step counter before the first step): a covering set - every
 # value of every option appears with at least two lengths, one of them with a tail (length % 4 != 0).

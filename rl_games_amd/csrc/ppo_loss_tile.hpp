@@ -101,6 +101,11 @@ __device__ __forceinline__ float smooth_clamp_grad(float x, float mi, float mx) 
   return (4.0f * e) * (s * s);
 }
 
+// torch.clamp_min / clamp_max of bound_loss (a2c_continuous.py:248-253): a NaN mu stays NaN.  fmaxf / fminf return the
+// other operand (see clamp_nan, rlg_device.hpp) - the bound loss of a row with a NaN mu was finite where the reference's is NaN.
+__device__ __forceinline__ float clamp_min_nan(float x, float lo) { return x != x ? x : fmaxf(x, lo); }
+__device__ __forceinline__ float clamp_max_nan(float x, float hi) { return x != x ? x : fminf(x, hi); }
+
 // The row-level part of the loss: from a row's five sums over the actions (z^2, KL terms, bound terms, log sigma, entropy
 // terms) and its scalars to  g = d loss / d neglogp x weight,  w = mask / count,  dv = d loss / d value,  and the row's
 // seven contributions to the tile's partial sums.  One definition for both tile forms below.
@@ -279,8 +284,8 @@ __device__ __forceinline__ void ppo_loss_tile_rows(const LossArgs& p, float* lds
       t_kl[r * AP + a] = (c1 + c2) + (-0.5f);
       float b = 0.0f;
       if (p.bound_kind == 1) {                                                // a2c_continuous.py:248-253
-        const float hi_t = fmaxf(mu - 1.1f, 0.0f);
-        const float lo_t = fminf(mu + 1.1f, 0.0f);
+        const float hi_t = clamp_min_nan(mu - 1.1f, 0.0f);
+        const float lo_t = clamp_max_nan(mu + 1.1f, 0.0f);
         b = lo_t * lo_t + hi_t * hi_t;
       } else if (p.bound_kind == 2) {                                         // :241-246
         b = mu * mu;
@@ -321,9 +326,12 @@ __device__ __forceinline__ void ppo_loss_tile_rows(const LossArgs& p, float* lds
     const int rr = prow < rows ? prow : 0;
     row_acc_t mine = 0, mine2 = 0;
     if (ppart == 3) {
+      // (+ mu * 0: the reference's sigma is mu * 0 + exp(logstd), network_builder.py:512 - a non-finite mu makes the
+      //  element's sigma and with it the row's entropy NaN; a finite one adds a zero)
+      const float* mu_row = p.mu + (row0 + rr) * p.ld_mu;
       for (int a = 0; a < A; ++a) {
         mine += static_cast<row_acc_t>(col_logstd[a]);
-        mine2 += static_cast<row_acc_t>(col_ent[a]);
+        mine2 += static_cast<row_acc_t>(col_ent[a] + mu_row[a] * 0.0f);
       }
     } else {
       const float* tile = ppart == 0 ? t_z2 : (ppart == 1 ? t_kl : t_b);
@@ -338,12 +346,13 @@ __device__ __forceinline__ void ppo_loss_tile_rows(const LossArgs& p, float* lds
     s_ent = __shfl(mine2_f, quad + 3, kWave);
   } else if (prow < rows) {
     row_acc_t d_z2 = 0, d_kl = 0, d_b = 0, d_ls = 0, d_ent = 0;
+    const float* mu_row = p.mu + (row0 + prow) * p.ld_mu;
     for (int a = 0; a < A; ++a) {
       d_z2 += static_cast<row_acc_t>(t_z2[prow * AP + a]);
       d_kl += static_cast<row_acc_t>(t_kl[prow * AP + a]);
       d_b += static_cast<row_acc_t>(t_b[prow * AP + a]);
       d_ls += static_cast<row_acc_t>(col_logstd[a]);
-      d_ent += static_cast<row_acc_t>(col_ent[a]);
+      d_ent += static_cast<row_acc_t>(col_ent[a] + mu_row[a] * 0.0f);
     }
     s_z2 = static_cast<float>(d_z2);
     s_kl = static_cast<float>(d_kl);
@@ -537,7 +546,9 @@ __device__ __forceinline__ void ppo_loss_quad_run(const LossArgs& p, float* lds,
       const float sg = expf(ls);                                              // models.py:296
       e_sg[k] = sg;
       s_ls += static_cast<row_acc_t>(ls);
-      s_ent += static_cast<row_acc_t>(1.4189385332046727f + logf(sg));      // Normal.entropy(): 0.5 + 0.5*log(2*pi) + log(scale)
+      // Normal.entropy(): 0.5 + 0.5*log(2*pi) + log(scale); + mu * 0: the reference's sigma is mu * 0 + exp(logstd)
+      // (network_builder.py:512) - a non-finite mu makes the row's entropy NaN, a finite one (0 without a row) adds a zero
+      s_ent += static_cast<row_acc_t>((1.4189385332046727f + logf(sg)) + e_mu[k] * 0.0f);
       if (row_ok) {
         const float mu = e_mu[k], x = e_x[k], omu = e_omu[k], osg = e_osg[k];
         const float z = (x - mu) / sg;                                        // models.py:362
@@ -549,8 +560,8 @@ __device__ __forceinline__ void ppo_loss_quad_run(const LossArgs& p, float* lds,
         const float c2 = (sg * sg + dm * dm) / (2.0f * (osg * osg + 1e-5f));
         s_kl += static_cast<row_acc_t>((c1 + c2) + (-0.5f));
         if (p.bound_kind == 1) {                                              // a2c_continuous.py:248-253
-          const float hi_t = fmaxf(mu - 1.1f, 0.0f);
-          const float lo_t = fminf(mu + 1.1f, 0.0f);
+          const float hi_t = clamp_min_nan(mu - 1.1f, 0.0f);
+          const float lo_t = clamp_max_nan(mu + 1.1f, 0.0f);
           s_b += static_cast<row_acc_t>(lo_t * lo_t + hi_t * hi_t);
         } else if (p.bound_kind == 2) {                                       // :241-246
           s_b += static_cast<row_acc_t>(mu * mu);

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from oracle import ppo_oracle as O
+from oracle.seeded_inputs import loss_inputs as _loss_inputs
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -231,30 +232,6 @@ def test_prepare_dataset_from_gae_moments(N, H, ema):
 
 
 # ----------------------------------------------------------------------------- PPO loss
-
-def _loss_inputs(mb, A, seed):
-    """SURVEY 8d kernel-level inputs: both clip sides fire, bound loss active."""
-    gen = g(seed)
-    old_nlp = torch.randn(mb, generator=gen)
-    batch = {
-        'old_logp_actions': old_nlp,
-        'advantages': torch.randn(mb, generator=gen),
-        'old_values': torch.randn(mb, 1, generator=gen),
-        'returns': torch.randn(mb, 1, generator=gen),
-        'actions': torch.randn(mb, A, generator=gen),
-        'mu': 1.2 * torch.randn(mb, A, generator=gen),
-        'sigma': torch.exp(0.1 * torch.randn(mb, A, generator=gen)),
-    }
-    mu = batch['mu'] + 0.1 * torch.randn(mb, A, generator=gen)
-    logstd = 0.1 * torch.randn(A, generator=gen)
-    values = batch['old_values'] + 0.3 * torch.randn(mb, 1, generator=gen)
-    # make neglogp land near old_neglogp so that ratios straddle the clip range
-    with torch.no_grad():
-        sigma = torch.exp(logstd)
-        nlp = O.neglogp(batch['actions'], mu, mu * 0 + sigma, mu * 0 + logstd)
-        batch['old_logp_actions'] = nlp + 0.2 * torch.randn(mb, generator=gen)
-    return mu, logstd, values, batch
-
 
 @pytest.mark.parametrize('mb,A', [(4096, 21), (1000, 8), (300, 1), (257, 33), (32768, 21)])
 @pytest.mark.parametrize('variant', ['bound', 'smooth_reg', 'noclip_nobound', 'masked', 'ppo_false'])
