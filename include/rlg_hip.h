@@ -598,34 +598,59 @@ int rlg_mlp_linear_act_backward(const float* dz, long long lddz, const float* w,
  * workspace size in floats (-1: shape unsupported, use the library GEMM); target_blocks <= 0: the
  * default workgroup count. */
 long long rlg_mlp_dw_plan(int rows, int out_features, int in_features, int target_blocks, int* plan4);
-/* colsum_* (num_colsums may be 0): bias gradients `grad_output.sum(0)` finished in the same finalise
- * launch from the per-block fp64 column sums of rlg_act_bwd_colsum (partials [blocks][cols]).
- * loss_finalize_or_null: the descriptor of rlg_ppo_loss_finalize, whose work then rides in that finalise launch. */
-int rlg_mlp_dw_launch(int num_layers, const float* const* dz, const float* const* x, float* const* partial,
-                      float* const* grad, const int* out_features, const int* in_features,
-                      const int* plans4, int rows, int num_colsums, const double* const* colsum_partials,
-                      const int* colsum_blocks, const int* colsum_cols, float* const* colsum_out,
-                      const rlg_loss_finalize_desc* loss_finalize_or_null,
-                      /* optional by-product: norm_partials[b] = sum (g * grad_scale)^2 over the gradient
-                       * elements finalise block b wrote (*finalize_blocks_out blocks, host int) - the input of
-                       * rlg_adam_step's clipping when THIS launch produces every gradient of the arena and
-                       * nothing touches them before Adam (single GPU); it then also advances step_counter
-                       * like rlg_grad_sumsq does. */
-                      double* norm_partials_or_null, float grad_scale, long long* step_counter_or_null,
-                      int* finalize_blocks_out_or_null, void* stream);
+/* One weight-gradient launch: rlg_mlp_dw_launch / rlg_mlp_dw_launch_form.  Arrays are indexed by job (= layer); the
+ * descriptor is read before the entry returns.  hipErrorInvalidValue: a NULL descriptor, num_layers outside [1, 8], rows
+ * <= 0, num_colsums outside [0, 8], a bad plan / misaligned workspace or gradient, a bad maxima field (below). */
+typedef struct rlg_mlp_dw_desc {
+  int num_layers;
+  int rows;
+  const float* const* dz;          /* [rows, out_features[l]] contiguous */
+  const float* const* x;           /* [rows, in_features[l]] contiguous */
+  float* const* partial;           /* split-K workspace of rlg_mlp_dw_plan's size, 16-byte aligned */
+  float* const* grad;              /* [out_features[l], in_features[l]], 16-byte aligned */
+  const int* out_features;
+  const int* in_features;
+  const int* plans4;               /* [4 * num_layers] from rlg_mlp_dw_plan */
+  /* bias gradients `grad_output.sum(0)` finished in the same finalise launch from the per-block fp64 column sums of
+   * rlg_act_bwd_colsum / the chain's backward (partials [blocks][cols]); num_colsums may be 0 */
+  int num_colsums;
+  const double* const* colsum_partials;
+  const int* colsum_blocks;
+  const int* colsum_cols;
+  float* const* colsum_out;
+  const rlg_loss_finalize_desc* loss_finalize_or_null;  /* rlg_ppo_loss_finalize's work rides in the finalise launch */
+  /* optional by-product: norm_partials[b] = sum (g * grad_scale)^2 over the gradient elements finalise block b wrote
+   * (*finalize_blocks_out blocks, host int) - the input of rlg_adam_step's clipping when THIS launch produces every
+   * gradient of the arena and nothing touches them before Adam (single GPU); it then also advances step_counter like
+   * rlg_grad_sumsq does. */
+  double* norm_partials_or_null;
+  float grad_scale;
+  long long* step_counter_or_null;
+  int* finalize_blocks_out_or_null;
+  /* Split-fp16 form.  The launch sums over the batch rows, so it scales an operand by ONE power of two per K-slice of
+   * rows: dz of job k by what the largest entry over a wave's rows asks for, maxima[dz_slot[k] * maxima_stride + e] = the
+   * largest |dZ| of rows [e * maxima_rows_per_entry, ...) as the chain's backward launch left them (rlg_chain_bwd), x of
+   * job k by x_scale[k], the fixed power of two the forward splits the same tensor with (16 for hidden activations,
+   * 4096 for normalised observations).  NULL maxima: the other fields are not read, the launch runs the bf16 form.  With
+   * maxima: maxima_stride <= 0, maxima_rows_per_entry other than 16 / 64, a dz_slot outside [0, 7] or an x_scale that is
+   * not > 0 is hipErrorInvalidValue; a stride below ceil(rows / maxima_rows_per_entry) counts as no maxima. */
+  const float* maxima_or_null;
+  int maxima_stride;
+  int maxima_rows_per_entry;
+  const int* dz_slot;
+  const float* x_scale;
+} rlg_mlp_dw_desc;
+RLG_ABI_SIZE(rlg_mlp_dw_desc, 176);
+
+/* The product form is the library's choice: three fp16 plane products with maxima, else six bf16 plane products
+ * (RLG_DW_BF16 / RLG_DW_F16 in the environment are the defaults of that choice). */
+int rlg_mlp_dw_launch(const rlg_mlp_dw_desc* desc, void* stream);
 
 /* rlg_mlp_dw_launch with the product form of THIS launch instead of the process-wide environment switches: form 0 =
- * exact f32 products (no range limit), 1 = six bf16 plane products, 2 = three fp16 plane products (needs the maxima
- * of rlg_mlp_dw_gradient_maxima, else hipErrorInvalidValue; |x| * x_scale must stay below 65,504), -1 = the library's
- * choice, i.e. rlg_mlp_dw_launch (RLG_DW_BF16 / RLG_DW_F16 are the defaults of that choice).  Plans of rlg_mlp_dw_plan
- * serve every form. */
-int rlg_mlp_dw_launch_form(int form, int num_layers, const float* const* dz, const float* const* x, float* const* partial,
-                           float* const* grad, const int* out_features, const int* in_features,
-                           const int* plans4, int rows, int num_colsums, const double* const* colsum_partials,
-                           const int* colsum_blocks, const int* colsum_cols, float* const* colsum_out,
-                           const rlg_loss_finalize_desc* loss_finalize_or_null, double* norm_partials_or_null,
-                           float grad_scale, long long* step_counter_or_null, int* finalize_blocks_out_or_null,
-                           void* stream);
+ * exact f32 products (no range limit), 1 = six bf16 plane products, 2 = three fp16 plane products (needs the
+ * descriptor's maxima, else hipErrorInvalidValue; |x| * x_scale must stay below 65,504), -1 = the library's choice, i.e.
+ * rlg_mlp_dw_launch.  Plans of rlg_mlp_dw_plan serve every form. */
+int rlg_mlp_dw_launch_form(int form, const rlg_mlp_dw_desc* desc, void* stream);
 
 /* ---- the MLP as one vertically fused chain on f32 MFMA (csrc/mlp_chain.hip) ------------------
  * forward : heads = head(act(... act(norm(x) W_0^T + b_0) ...)) for a row tile, every layer in ONE
@@ -655,67 +680,96 @@ int rlg_mlp_chain_lds_bytes(int num_layers, const int* in_features, const int* o
 /* tools only: the following forward launches record shader-clock stamps per phase into
  * buffer [blocks][4 waves][32] (int64); NULL switches it off. */
 int rlg_mlp_chain_debug_stamps(long long* buffer);
-/* HIP events (rlg_event_create) bound to the NEXT chain dispatch (forward or backward), one-shot; not for
- * launches inside a graph capture.  bench.py's roofline_fwd / roofline_bwd. */
-/* Split-fp16 launches (round 6).  The weight-gradient launch sums over the batch rows, so it scales an operand by ONE power
- * of two per K-slice of rows.  rlg_mlp_chain_gradient_maxima: the next rlg_mlp_chain_backward launch, if it runs the
- * split-fp16 kernel, leaves per 64-row workgroup the largest magnitude of dZ of layer l (the last layer: of the d heads it
- * read) in entries[l * stride + workgroup] (plain stores; stride >= ceil(rows / 64)); one-shot.  The lean 16-row launches
- * (rlg_mlp_chain_backward_lean / _step_lean) take the same setter and leave one entry per 16-row workgroup (stride >=
- * ceil(rows / 16)); rows_per_entry of rlg_mlp_dw_gradient_maxima says which (64 or 16).
- * rlg_mlp_dw_gradient_maxima hands them to the NEXT rlg_mlp_dw_launch: dz_slot[k] = the layer of job k's dz, x_scale[k] = the
- * fixed power of two job k's x is split under (the forward's: 16 for hidden activations, 4096 for normalised
- * observations); every wave takes the largest entry over its own rows.  Without them the launch runs the bf16 form. */
-int rlg_mlp_chain_gradient_maxima(float* entries, int stride);
-int rlg_mlp_dw_gradient_maxima(const float* entries, int stride, int rows_per_entry, const int* dz_slot, const float* x_scale,
-                               int num_layers);
 /* plane products per fp32 product of the split-product chain kernels: 3 (two fp16 planes per operand) */
 int rlg_mlp_chain_split_products(void);
-int rlg_mlp_chain_time_next(void* ev_start, void* ev_stop);
 
-int rlg_mlp_chain_forward(int num_layers, const float* const* weights, const float* const* biases,
-                          const int* in_features, const int* out_features, const int* acts,
-                          float* const* act_out, const long long* act_ld, const float* x, long long ldx,
-                          const double* rms_mean_or_null, const double* rms_var, float rms_eps,
-                          float* xn_out_or_null,
-                          /* training-mode RunningMeanStd.forward (rl_games/algos_torch/running_mean_std.py:
-                           * 69-84, called from models.py:54-56): fold this minibatch's column moments
-                           * rms_batch = {sum[in], sumsq[in], rows} (rlg_column_moments_segments) into the
-                           * state BEFORE normalising; the new state goes to the *_out buffers, which must
-                           * differ from the inputs (every workgroup folds from the old state).  NULL
-                           * rms_batch: normalise with the state as it is. */
-                          const double* rms_batch_or_null, const long long* rms_count,
-                          double* rms_mean_out, double* rms_var_out, long long* rms_count_out,
-                          long long rows, int groups, void* pack_backward_planes_or_null,
-                          const void* weight_planes_or_null, void* stream);
-/* With a non-NULL rlg_ppo_loss_desc (the descriptor of rlg_ppo_loss_fused) the BACKWARD launch evaluates the
- * loss of its own row tile in front of its prologue - no separate loss launch - i.e. it first writes
- * d mu / d values (which must be views of the d_out buffer this launch then reads), the mu/sigma
- * write-back and one row of partials per workgroup (rlg_mlp_chain_num_blocks(rows, resolved backward
- * groups) rows of rlg_ppo_loss_partials_per_block doubles).  minibatch must equal rows. */
-int rlg_mlp_chain_backward(int num_layers, const float* const* weights, const int* in_features,
-                           const int* out_features, const int* acts, const float* const* act_in,
-                           const long long* act_ld, const float* d_out, long long ld_dout,
-                           float* const* dz_out, const long long* dz_ld, double* const* bias_partials_or_null,
-                           const rlg_ppo_loss_desc* ppo_loss_or_null, long long rows, int groups,
-                           const void* weight_planes_or_null, void* stream);
+/* The six launching entries (rlg_mlp_chain_forward / _backward / _step and their _lean forms) take their arguments as
+ * descriptors: the network, the forward half, the backward half, the launch.  Like every descriptor of this header they
+ * are read before the entry returns; a NULL one is hipErrorInvalidValue, answered first. */
+typedef struct rlg_chain_net {
+  int num_layers;
+  const float* const* weights;      /* [out, in] fp32 per layer; the lean entries read fragments instead: may be NULL there */
+  const float* const* biases;       /* NULL: no biases (the backward entries do not read it) */
+  const int* in_features;
+  const int* out_features;
+  const int* acts;                  /* 0 identity, 1 elu, 2 relu, 3 tanh */
+} rlg_chain_net;
+RLG_ABI_SIZE(rlg_chain_net, 48);
+
+typedef struct rlg_chain_fwd {
+  float* const* act_out;            /* layer l's output: required for the last layer (the heads), optional for the hidden */
+  const long long* act_ld;          /*   ones (training: what backward needs; the step entries need all); row strides */
+  const float* x;                   /* observations [rows, in_0], row stride ldx */
+  long long ldx;
+  const double* rms_mean_or_null;   /* RunningMeanStd state: normalise x on the way in; NULL: x as it is */
+  const double* rms_var;
+  float rms_eps;
+  float* xn_out_or_null;            /* receives the normalised observations [rows, in_0] */
+  /* training-mode RunningMeanStd.forward (rl_games/algos_torch/running_mean_std.py:69-84, called from models.py:54-56):
+   * fold this minibatch's column moments rms_batch = {sum[in], sumsq[in], rows} (rlg_column_moments_segments) into the
+   * state BEFORE normalising; the new state goes to the *_out buffers, which must differ from the inputs (every
+   * workgroup folds from the old state).  NULL rms_batch: normalise with the state as it is. */
+  const double* rms_batch_or_null;
+  const long long* rms_count;
+  double* rms_mean_out;
+  double* rms_var_out;
+  long long* rms_count_out;
+  const void* weight_form_or_null;  /* rlg_mlp_chain_forward: forward planes (the 64-row split kernel runs when it applies);
+                                     * the lean entries: forward fragments, required */
+  void* pack_backward_planes_or_null;  /* rlg_mlp_chain_forward only: split the weights for the backward launch that
+                                        * follows, in extra workgroups at the end of the grid */
+} rlg_chain_fwd;
+RLG_ABI_SIZE(rlg_chain_fwd, 120);
+
+typedef struct rlg_chain_bwd {
+  const float* const* act_in;       /* H_l of the hidden layers (the forward's act_out) and their row strides; the step */
+  const long long* act_ld;          /*   entries do not read the two: H is their forward half's act_out */
+  float* d_out;                     /* d loss / d heads [rows, out_last], row stride ld_dout; read, and with a loss */
+  long long ld_dout;                /*   descriptor written first by the launch's own loss tile */
+  float* const* dz_out;             /* dZ_l of the hidden layers and their row strides */
+  const long long* dz_ld;
+  double* const* bias_partials_or_null;  /* [num_blocks, out_l] fp64 per-workgroup column sums of dZ_l (finished by
+                                          * rlg_mlp_dw_launch's colsum items) */
+  /* With a descriptor of rlg_ppo_loss_fused the launch evaluates the loss of its own row tile in front of its prologue -
+   * no separate loss launch - i.e. it first writes d mu / d values (which must be views of d_out), the mu/sigma
+   * write-back and one row of partials per workgroup (rlg_mlp_chain_num_blocks(rows, resolved backward groups) rows of
+   * rlg_ppo_loss_partials_per_block doubles).  minibatch must equal rows.  The step entries require it. */
+  const rlg_ppo_loss_desc* ppo_loss_or_null;
+  const void* weight_form_or_null;  /* rlg_mlp_chain_backward: backward planes (the 64-row split kernel runs when it applies
+                                     * and H / dZ are 16-byte aligned); the lean entries: backward fragments, required */
+  /* Gradient maxima for the weight-gradient launch (rlg_mlp_dw_desc): a split-fp16 launch leaves per workgroup the
+   * largest magnitude of dZ of layer l (the last layer: of the d heads it read) in maxima[l * maxima_stride + workgroup],
+   * plain stores.  The 64-row split kernel of rlg_mlp_chain_backward: one entry per 64 rows, maxima it cannot use (another
+   * kernel runs, stride < ceil(rows / 64)) are ignored.  The lean entries: one entry per 16 rows, stride < ceil(rows / 16)
+   * is hipErrorInvalidValue.  rlg_mlp_chain_step leaves none. */
+  float* maxima_or_null;
+  int maxima_stride;
+  int* maxima_rows_out_or_null;     /* host int: the rows one entry covers, 64 or 16; 0 = this launch leaves no maxima */
+} rlg_chain_bwd;
+RLG_ABI_SIZE(rlg_chain_bwd, 96);
+
+typedef struct rlg_chain_launch {
+  long long rows;                   /* <= 0: nothing to do, 0 */
+  int groups;                       /* rlg_mlp_chain_forward / _backward: 16-row groups per workgroup, 1 / 2 / 4, 0 = chosen
+                                     * from rows and direction (rlg_mlp_chain_groups); the other entries run 16-row workgroups */
+  void* ev_start_or_null;           /* HIP events (rlg_event_create) on THIS dispatch; not for launches inside a graph */
+  void* ev_stop_or_null;            /*   capture.  bench.py's roofline_fwd / roofline_bwd */
+} rlg_chain_launch;
+RLG_ABI_SIZE(rlg_chain_launch, 32);
+
+int rlg_mlp_chain_forward(const rlg_chain_net* net, const rlg_chain_fwd* fwd, const rlg_chain_launch* launch, void* stream);
+int rlg_mlp_chain_backward(const rlg_chain_net* net, const rlg_chain_bwd* bwd, const rlg_chain_launch* launch, void* stream);
 
 /* Forward + PPO loss + backward of one minibatch as ONE launch (round 4; csrc/mlp_chain.hip,
- * mlp_chain_step_pipe_kernel): the arguments of rlg_mlp_chain_forward in its training form (every act_out given) and of
+ * mlp_chain_step_pipe_kernel): rlg_mlp_chain_forward in its training form (every act_out given) and
  * rlg_mlp_chain_backward with a loss descriptor whose mu / values are the forward's heads and whose d_mu / d_values are
  * `d_out`.  For minibatches below 16,384 rows (a data-parallel rank's 4,096 - 8,192): the loss tile's inputs are
  * requested before the forward and arrive during it, and the launch boundary between the two halves is gone
  * (a2c_continuous.py:136-234: model forward, calc_losses, loss.backward() up to the weight-gradient GEMMs).  Same device
  * code as the two launches, same results.  Returns hipErrorNotSupported (801) when the shape is outside the kernel's
  * envelope - the caller then issues rlg_mlp_chain_forward and rlg_mlp_chain_backward. */
-int rlg_mlp_chain_step(int num_layers, const float* const* weights, const float* const* biases,
-                       const int* in_features, const int* out_features, const int* acts,
-                       float* const* act_out, const long long* act_ld, const float* x, long long ldx,
-                       const double* rms_mean, const double* rms_var, float rms_eps, float* xn_out,
-                       const double* rms_batch, const long long* rms_count, double* rms_mean_out,
-                       double* rms_var_out, long long* rms_count_out, float* d_out, long long ld_dout,
-                       float* const* dz_out, const long long* dz_ld, double* const* bias_partials_or_null,
-                       const rlg_ppo_loss_desc* ppo_loss, long long rows, void* stream);
+int rlg_mlp_chain_step(const rlg_chain_net* net, const rlg_chain_fwd* fwd, const rlg_chain_bwd* bwd,
+                       const rlg_chain_launch* launch, void* stream);
 
 /* The 16-row launches of a data-parallel rank's minibatches (< 16,384 rows; rollouts of that size) in their LEAN form
  * (round 4; csrc/mlp_chain_lean.hip, mlp_chain_fwd_lean_kernel / mlp_chain_bwd_lean_kernel): the weights as FRAGMENTS (round 6: two fp16 planes of 64 w per group of 32 k values where rounds 4 - 5 had two fp32 chunks - the same bytes; csrc/split_f16.hpp) in
@@ -728,8 +782,8 @@ int rlg_mlp_chain_step(int num_layers, const float* const* weights, const float*
  *     outside the format.
  *   rlg_mlp_chain_pack_frags / _both: weights -> fragments, one launch (the bias pointers are not read); to be repeated behind every change of
  *     the weights (an agent issues it behind its optimiser step).
- *   rlg_mlp_chain_forward_lean / rlg_mlp_chain_backward_lean: the launches; arguments as their namesakes without the
- *     weight pointers.  hipErrorNotSupported (801): shape outside the kernels' envelope (LDS, unaligned H / dZ
+ *   rlg_mlp_chain_forward_lean / rlg_mlp_chain_backward_lean: the launches; the descriptors of their namesakes, the
+ *     weights read from weight_form.  hipErrorNotSupported (801): shape outside the kernels' envelope (LDS, unaligned H / dZ
  *     rows) - the caller then uses rlg_mlp_chain_forward / rlg_mlp_chain_backward. */
 long long rlg_mlp_chain_frags_bytes(int num_layers, const int* in_features, const int* out_features, int direction);
 int rlg_mlp_chain_pack_frags(int num_layers, const float* const* weights, const float* const* biases_or_null,
@@ -737,35 +791,21 @@ int rlg_mlp_chain_pack_frags(int num_layers, const float* const* weights, const 
 int rlg_mlp_chain_pack_frags_both(int num_layers, const float* const* weights, const float* const* biases,
                                   const int* in_features, const int* out_features, void* frags_fwd, void* frags_bwd_or_null,
                                   void* stream);
-int rlg_mlp_chain_forward_lean(int num_layers, const float* const* biases, const int* in_features, const int* out_features,
-                               const int* acts, float* const* act_out, const long long* act_ld, const float* x, long long ldx,
-                               const double* rms_mean, const double* rms_var, float rms_eps, float* xn_out,
-                               const double* rms_batch, const long long* rms_count, double* rms_mean_out,
-                               double* rms_var_out, long long* rms_count_out, long long rows, const void* frags,
-                               void* stream);
-/* forward + PPO loss + backward in ONE lean launch (the arguments of rlg_mlp_chain_step without the weight pointers;
- * minibatches of at most 16 rows x CUs; 801 otherwise) */
-int rlg_mlp_chain_step_lean(int num_layers, const float* const* biases, const int* in_features, const int* out_features,
-                            const int* acts, float* const* act_out, const long long* act_ld, const float* x, long long ldx,
-                            const double* rms_mean, const double* rms_var, float rms_eps, float* xn_out,
-                            const double* rms_batch, const long long* rms_count, double* rms_mean_out,
-                            double* rms_var_out, long long* rms_count_out, float* d_out, long long ld_dout,
-                            float* const* dz_out, const long long* dz_ld, double* const* bias_partials,
-                            const rlg_ppo_loss_desc* ppo_loss, long long rows, const void* frags_fwd, const void* frags_bwd,
-                            void* stream);
-int rlg_mlp_chain_backward_lean(int num_layers, const int* in_features, const int* out_features, const int* acts,
-                                const float* const* act_in, const long long* act_ld, const float* d_out, long long ld_dout,
-                                float* const* dz_out, const long long* dz_ld, double* const* bias_partials,
-                                const rlg_ppo_loss_desc* ppo_loss, long long rows, const void* frags, void* stream);
+int rlg_mlp_chain_forward_lean(const rlg_chain_net* net, const rlg_chain_fwd* fwd, const rlg_chain_launch* launch, void* stream);
+/* forward + PPO loss + backward in ONE lean launch (rlg_mlp_chain_step on the fragments; minibatches of at most
+ * 16 rows x CUs; 801 otherwise) */
+int rlg_mlp_chain_step_lean(const rlg_chain_net* net, const rlg_chain_fwd* fwd, const rlg_chain_bwd* bwd,
+                            const rlg_chain_launch* launch, void* stream);
+int rlg_mlp_chain_backward_lean(const rlg_chain_net* net, const rlg_chain_bwd* bwd, const rlg_chain_launch* launch, void* stream);
 
 /* Split-product form of the chain (csrc/mlp_chain_bx.hip): every fp32 product as three exact fp16 plane products on
  * v_mfma_f32_16x16x32_f16 (round 6, csrc/split_f16.hpp: results within 3 * 2^-22 |x||w| per product of the exact-product
  * kernels in the worst case, ~2^-24 rms).  The weights
- * are split ONCE per optimizer step into plane fragments; the launch that is given them (weight_planes_or_null of
+ * are split ONCE per optimizer step into plane fragments; the launch that is given them (weight_form_or_null of
  * rlg_mlp_chain_backward, direction 1) uses the split kernel when rlg_mlp_chain_bx_supported says so and the
  * activation arrays are 16-byte aligned, else the exact-product kernel.  Same autograd nodes as above
  * (rl_games/algos_torch/network_builder.py:447-512).
- * pack_backward_planes_or_null of rlg_mlp_chain_forward: the forward launch of a training step splits the weights
+ * pack_backward_planes_or_null of rlg_chain_fwd: the forward launch of a training step splits the weights
  * for the backward launch that follows it (same weights) in extra workgroups at the end of its grid - no launch of its own.
  *   rlg_mlp_chain_planes_bytes : size of the fragment buffer for one direction (0 forward products, 1 backward) or,
  *                                direction 2, of ONE buffer with both (the backward fragments at

@@ -83,10 +83,8 @@ _PROTOTYPES = {
     'rlg_mlp_linear_act_forward': [_P, _c_ll, _P, _P, _P, _P, _c_ll, _c_int, _c_int, _c_int, _c_int, _P],
     'rlg_mlp_linear_act_backward': [_P, _c_ll, _P, _P, _P, _c_ll, _c_int, _c_int, _c_int, _c_int, _P],
     'rlg_mlp_dw_plan': [_c_int, _c_int, _c_int, _c_int, _P],
-    'rlg_mlp_dw_launch': [_c_int, _P, _P, _P, _P, _P, _P, _P, _c_int, _c_int, _P, _P, _P, _P, _P, _P, _c_float, _P,
-                          _P, _P],
-    'rlg_mlp_dw_launch_form': [_c_int, _c_int, _P, _P, _P, _P, _P, _P, _P, _c_int, _c_int, _P, _P, _P, _P, _P, _P, _c_float,
-                               _P, _P, _P],
+    'rlg_mlp_dw_launch': [_P, _P],                   # (MlpDwDesc, stream)
+    'rlg_mlp_dw_launch_form': [_c_int, _P, _P],      # (form, MlpDwDesc, stream)
     'rlg_narrow_dx': [_P, _c_ll, _P, _P, _c_ll, _c_ll, _c_int, _c_int, _P],
     'rlg_narrow_dw_blocks': [_c_ll],
     'rlg_narrow_dw': [_P, _c_ll, _P, _c_ll, _P, _P, _c_ll, _c_int, _c_int, _P],
@@ -96,24 +94,17 @@ _PROTOTYPES = {
     'rlg_mlp_chain_num_blocks': [_c_ll, _c_int],
     'rlg_mlp_chain_lds_bytes': [_c_int, _P, _P, _c_int, _c_int],
     'rlg_mlp_chain_debug_stamps': [_P],
-    'rlg_mlp_chain_time_next': [_P, _P],
-    'rlg_mlp_chain_gradient_maxima': [_P, _c_int],
     'rlg_mlp_chain_split_products': [],
-    'rlg_mlp_dw_gradient_maxima': [_P, _c_int, _c_int, _P, _P, _c_int],
-    'rlg_mlp_chain_forward': [_c_int, _P, _P, _P, _P, _P, _P, _P, _P, _c_ll, _P, _P, _c_float, _P,
-                              _P, _P, _P, _P, _P, _c_ll, _c_int, _P, _P, _P],
-    'rlg_mlp_chain_step': [_c_int, _P, _P, _P, _P, _P, _P, _P, _P, _c_ll, _P, _P, _c_float, _P,
-                           _P, _P, _P, _P, _P, _P, _c_ll, _P, _P, _P, _P, _c_ll, _P],
-    'rlg_mlp_chain_backward': [_c_int, _P, _P, _P, _P, _P, _P, _P, _c_ll, _P, _P, _P, _P, _c_ll, _c_int, _P, _P],
+    'rlg_mlp_chain_forward': [_P, _P, _P, _P],       # (ChainNet, ChainFwd, ChainLaunch, stream)
+    'rlg_mlp_chain_step': [_P, _P, _P, _P, _P],      # (ChainNet, ChainFwd, ChainBwd, ChainLaunch, stream)
+    'rlg_mlp_chain_backward': [_P, _P, _P, _P],      # (ChainNet, ChainBwd, ChainLaunch, stream)
     # lean 16-row forward (csrc/mlp_chain_lean.hip, mlp_chain_fwd_lean_kernel)
     'rlg_mlp_chain_frags_bytes': [_c_int, _P, _P, _c_int],
     'rlg_mlp_chain_pack_frags': [_c_int, _P, _P, _P, _P, _c_int, _P, _P],
     'rlg_mlp_chain_pack_frags_both': [_c_int, _P, _P, _P, _P, _P, _P, _P],
-    'rlg_mlp_chain_step_lean': [_c_int, _P, _P, _P, _P, _P, _P, _P, _c_ll, _P, _P, _c_float, _P,
-                                _P, _P, _P, _P, _P, _P, _c_ll, _P, _P, _P, _P, _c_ll, _P, _P, _P],
-    'rlg_mlp_chain_backward_lean': [_c_int, _P, _P, _P, _P, _P, _P, _c_ll, _P, _P, _P, _P, _c_ll, _P, _P],
-    'rlg_mlp_chain_forward_lean': [_c_int, _P, _P, _P, _P, _P, _P, _P, _c_ll, _P, _P, _c_float, _P,
-                                   _P, _P, _P, _P, _P, _c_ll, _P, _P],
+    'rlg_mlp_chain_step_lean': [_P, _P, _P, _P, _P],      # as rlg_mlp_chain_step
+    'rlg_mlp_chain_backward_lean': [_P, _P, _P, _P],      # as rlg_mlp_chain_backward
+    'rlg_mlp_chain_forward_lean': [_P, _P, _P, _P],       # as rlg_mlp_chain_forward
     # mlp_chain_bx.hip
     'rlg_mlp_chain_planes_bytes': [_c_int, _P, _P, _c_int],
     'rlg_mlp_chain_planes_offset': [_c_int, _P, _P, _c_int],
@@ -254,6 +245,45 @@ class AdamDesc(ctypes.Structure):
                 + [('schedule_kind', _c_int), ('kl_or_null', ctypes.c_void_p), ('kl_scale', _c_float)]
                 + [(n, _c_double) for n in ('kl_threshold', 'min_lr', 'max_lr', 'lr_multiplier')]
                 + [('stats_out_or_null', ctypes.c_void_p), ('skip_flag_or_null', ctypes.c_void_p)])
+
+
+# Every pointer field of the descriptors below is a plain address (ctypes.addressof for host arrays and descriptors):
+# whoever fills one keeps what it points at alive until the entry has returned.
+class ChainNet(ctypes.Structure):
+    """rlg_chain_net (include/rlg_hip.h): the network of the six launching chain entries, stated once per chain."""
+    _fields_ = [('num_layers', _c_int)] + [(n, _P) for n in ('weights', 'biases', 'in_features', 'out_features', 'acts')]
+
+
+class ChainFwd(ctypes.Structure):
+    """rlg_chain_fwd: the forward half of a chain launch."""
+    _fields_ = ([('act_out', _P), ('act_ld', _P), ('x', _P), ('ldx', _c_ll), ('rms_mean_or_null', _P), ('rms_var', _P),
+                 ('rms_eps', _c_float), ('xn_out_or_null', _P)]
+                + [(n, _P) for n in ('rms_batch_or_null', 'rms_count', 'rms_mean_out', 'rms_var_out', 'rms_count_out',
+                                     'weight_form_or_null', 'pack_backward_planes_or_null')])
+
+
+class ChainBwd(ctypes.Structure):
+    """rlg_chain_bwd: the backward half of a chain launch."""
+    _fields_ = [('act_in', _P), ('act_ld', _P), ('d_out', _P), ('ld_dout', _c_ll), ('dz_out', _P), ('dz_ld', _P),
+                ('bias_partials_or_null', _P), ('ppo_loss_or_null', _P), ('weight_form_or_null', _P),
+                ('maxima_or_null', _P), ('maxima_stride', _c_int), ('maxima_rows_out_or_null', _P)]
+
+
+class ChainLaunch(ctypes.Structure):
+    """rlg_chain_launch: rows, groups and the HIP events on this dispatch."""
+    _fields_ = [('rows', _c_ll), ('groups', _c_int), ('ev_start_or_null', _P), ('ev_stop_or_null', _P)]
+
+
+class MlpDwDesc(ctypes.Structure):
+    """rlg_mlp_dw_desc: one weight-gradient launch (rlg_mlp_dw_launch / rlg_mlp_dw_launch_form)."""
+    _fields_ = ([('num_layers', _c_int), ('rows', _c_int)]
+                + [(n, _P) for n in ('dz', 'x', 'partial', 'grad', 'out_features', 'in_features', 'plans4')]
+                + [('num_colsums', _c_int)]
+                + [(n, _P) for n in ('colsum_partials', 'colsum_blocks', 'colsum_cols', 'colsum_out',
+                                     'loss_finalize_or_null', 'norm_partials_or_null')]
+                + [('grad_scale', _c_float), ('step_counter_or_null', _P), ('finalize_blocks_out_or_null', _P),
+                   ('maxima_or_null', _P), ('maxima_stride', _c_int), ('maxima_rows_per_entry', _c_int),
+                   ('dz_slot', _P), ('x_scale', _P)])
 
 
 def check(err, what):

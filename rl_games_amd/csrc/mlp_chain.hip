@@ -1361,14 +1361,16 @@ static int chain_lds(int num_layers, const int* in_features, const int* out_feat
   return bytes <= 160 * 1024 ? static_cast<int>(bytes) : -1;
 }
 
-int chain_fill_shape(ChainArgs& args, int num_layers, const int* in_features, const int* out_features, const int* acts) {
+int chain_fill_shape(ChainArgs& args, const rlg_chain_net& net) {
+  const int num_layers = net.num_layers;
+  const int* const out_features = net.out_features;
   if (num_layers < 1 || num_layers > kChainMaxLayers) return 1;
   for (int L = 0; L < num_layers; ++L) {
     ChainLayer& ly = args.layer[L];
     ly.w = nullptr;
-    ly.in = in_features[L];
+    ly.in = net.in_features[L];
     ly.out = out_features[L];
-    ly.act = acts[L];
+    ly.act = net.acts[L];
     ly.bias = nullptr;
     ly.h = nullptr;
     ly.dz = nullptr;
@@ -1384,61 +1386,59 @@ int chain_fill_shape(ChainArgs& args, int num_layers, const int* in_features, co
   args.pack.njobs = args.pack.total_pairs = 0;
   args.pack.dst = nullptr;
   args.planes = nullptr;
+  args.amax = nullptr;
+  args.amax_stride = 0;
   return 0;
 }
 
-int chain_fill(ChainArgs& args, int num_layers, const float* const* weights, const int* in_features,
-               const int* out_features, const int* acts) {
-  if (chain_fill_shape(args, num_layers, in_features, out_features, acts)) return 1;
-  for (int L = 0; L < num_layers; ++L) {
-    args.layer[L].w = weights[L];
-    if (reinterpret_cast<uintptr_t>(weights[L]) % 4 != 0) return 1;
+int chain_fill(ChainArgs& args, const rlg_chain_net& net) {
+  if (chain_fill_shape(args, net) || net.weights == nullptr) return 1;
+  for (int L = 0; L < net.num_layers; ++L) {
+    args.layer[L].w = net.weights[L];
+    if (reinterpret_cast<uintptr_t>(net.weights[L]) % 4 != 0) return 1;
   }
   return 0;
 }
 
-int chain_fill_forward(ChainArgs& args, const float* const* biases_or_null, float* const* act_out, const long long* act_ld,
-                       const float* x, long long ldx, const double* rms_mean, const double* rms_var, float rms_eps,
-                       float* xn_out, const double* rms_batch, const long long* rms_count, double* rms_mean_out,
-                       double* rms_var_out, long long* rms_count_out, long long rows) {
+int chain_fill_forward(ChainArgs& args, const rlg_chain_net& net, const rlg_chain_fwd& fwd, long long rows) {
   for (int L = 0; L < args.num_layers; ++L) {
-    args.layer[L].bias = biases_or_null ? biases_or_null[L] : nullptr;
-    args.layer[L].h = act_out[L];
-    args.layer[L].ldh = act_ld[L];
+    args.layer[L].bias = net.biases ? net.biases[L] : nullptr;
+    args.layer[L].h = fwd.act_out[L];
+    args.layer[L].ldh = fwd.act_ld[L];
   }
-  args.x = x;
-  args.ldx = ldx;
+  const double* const rms_mean = fwd.rms_mean_or_null;
+  args.x = fwd.x;
+  args.ldx = fwd.ldx;
   args.rms_mean = rms_mean;
-  args.rms_var = rms_mean ? rms_var : nullptr;
-  args.rms_eps = rms_eps;
-  args.rms_batch = rms_mean ? rms_batch : nullptr;
+  args.rms_var = rms_mean ? fwd.rms_var : nullptr;
+  args.rms_eps = fwd.rms_eps;
+  args.rms_batch = rms_mean ? fwd.rms_batch_or_null : nullptr;
   if (args.rms_batch) {
-    if (!rms_count || !rms_mean_out || !rms_var_out || !rms_count_out || rms_mean_out == rms_mean ||
-        rms_var_out == rms_var || rms_count_out == rms_count)
+    if (!fwd.rms_count || !fwd.rms_mean_out || !fwd.rms_var_out || !fwd.rms_count_out || fwd.rms_mean_out == rms_mean ||
+        fwd.rms_var_out == fwd.rms_var || fwd.rms_count_out == fwd.rms_count)
       return static_cast<int>(hipErrorInvalidValue);      // the fold publishes into a second buffer set
   }
-  args.rms_count = rms_count;
-  args.rms_mean_out = rms_mean_out;
-  args.rms_var_out = rms_var_out;
-  args.rms_count_out = rms_count_out;
-  args.xn = xn_out;
+  args.rms_count = fwd.rms_count;
+  args.rms_mean_out = fwd.rms_mean_out;
+  args.rms_var_out = fwd.rms_var_out;
+  args.rms_count_out = fwd.rms_count_out;
+  args.xn = fwd.xn_out_or_null;
   args.rows = rows;
   return 0;
 }
 
-void chain_fill_backward(ChainArgs& args, const float* const* act_in, const long long* act_ld, const float* d_out,
-                         long long ld_dout, float* const* dz_out, const long long* dz_ld, double* const* bias_partials_or_null,
+void chain_fill_backward(ChainArgs& args, const float* const* act_in, const long long* act_ld, const rlg_chain_bwd& bwd,
                          long long rows) {
   for (int L = 0; L + 1 < args.num_layers; ++L) {
     ChainLayer& ly = args.layer[L];
     ly.h = const_cast<float*>(act_in[L]);
     ly.ldh = act_ld[L];
-    ly.dz = dz_out[L];
-    ly.lddz = dz_ld[L];
-    ly.bias_partials = bias_partials_or_null ? bias_partials_or_null[L] : nullptr;
+    ly.dz = bwd.dz_out[L];
+    ly.lddz = bwd.dz_ld[L];
+    ly.bias_partials = bwd.bias_partials_or_null ? bwd.bias_partials_or_null[L] : nullptr;
   }
-  args.x = d_out;
-  args.ldx = ld_dout;
+  args.x = bwd.d_out;
+  args.ldx = bwd.ld_dout;
   args.rms_mean = args.rms_var = nullptr;
   args.rms_eps = 0.0f;
   args.rms_batch = nullptr;
@@ -1477,12 +1477,9 @@ bool chain_elu_only(const ChainArgs& args) {
 }
 
 static bool g_chain_prepared = false;     // rlg_mlp_chain_prepare raised the LDS limit of every kernel
-// rlg_mlp_chain_time_next: HIP events bound to the NEXT chain dispatch (its begin / end timestamps, what
-// rocprofv3 --kernel-trace reports); one-shot, bench.py's roofline_fwd / roofline_bwd
-static hipEvent_t g_chain_ev_start = nullptr, g_chain_ev_stop = nullptr;
 
 template <int G, bool kBackward, int HACT, int W>
-static int chain_launch_as(const ChainArgs& args_in, int lds_bytes, hipStream_t st, const LossArgs* loss) {
+static int chain_launch_as(const ChainArgs& args_in, int lds_bytes, const ChainQueue& q, const LossArgs* loss) {
   ChainArgs args = args_in;
   int grid = static_cast<int>((args.rows + 16 * G - 1) / (16 * G));
   args.fwd_blocks = grid;
@@ -1499,9 +1496,9 @@ static int chain_launch_as(const ChainArgs& args_in, int lds_bytes, hipStream_t 
     }
   }
   if constexpr (kBackward)
-    return chain_launch_kernel(mlp_chain_bwd_kernel<G, W>, grid, 64 * W, lds_bytes, st, args, loss ? *loss : LossArgs{});
+    return chain_launch_kernel(mlp_chain_bwd_kernel<G, W>, grid, 64 * W, lds_bytes, q, args, loss ? *loss : LossArgs{});
   else
-    return chain_launch_kernel(mlp_chain_fwd_kernel<G, HACT, W>, grid, 64 * W, lds_bytes, st, args);
+    return chain_launch_kernel(mlp_chain_fwd_kernel<G, HACT, W>, grid, 64 * W, lds_bytes, q, args);
 }
 
 // The pipelined kernels address every weight matrix and bias vector through ONE buffer resource: fills w_base /
@@ -1569,12 +1566,12 @@ static bool chain_pipe_fill(ChainArgs& args, bool with_bias) {
   return true;
 }
 template <int G, int HACT, int W = 4>
-static int chain_launch_fwd_pipe(const ChainArgs& args_in, int lds_bytes, hipStream_t st) {
+static int chain_launch_fwd_pipe(const ChainArgs& args_in, int lds_bytes, const ChainQueue& q) {
   ChainArgs args = args_in;
   int grid = static_cast<int>((args.rows + 16 * G - 1) / (16 * G));
   args.fwd_blocks = grid;
   if (args.pack.total_pairs > 0) grid += chain_bx_pack_blocks(args.pack);
-  return chain_launch_kernel(mlp_chain_fwd_pipe_kernel<G, HACT, W>, grid, 64 * W, lds_bytes, st, args);
+  return chain_launch_kernel(mlp_chain_fwd_pipe_kernel<G, HACT, W>, grid, 64 * W, lds_bytes, q, args);
 }
 // 16-row pipelined kernels: 8 waves per workgroup, two per SIMD - at one wave the four-chunk look-ahead of the weight stream
 // (512 MFMA cycles at one 16-row group) is shorter than the loaded L2 latency (~900 cycles) and every chunk waits; 16 waves
@@ -1592,19 +1589,19 @@ static int chain_waves(int G, long long rows) {
 }
 
 template <int G, bool kBackward, int W>
-static int chain_launch_w(const ChainArgs& args, int lds_bytes, hipStream_t st, const LossArgs* loss) {
+static int chain_launch_w(const ChainArgs& args, int lds_bytes, const ChainQueue& q, const LossArgs* loss) {
   if constexpr (!kBackward) {
-    if (chain_elu_only(args)) return chain_launch_as<G, false, kChElu, W>(args, lds_bytes, st, loss);
+    if (chain_elu_only(args)) return chain_launch_as<G, false, kChElu, W>(args, lds_bytes, q, loss);
   }
-  return chain_launch_as<G, kBackward, kChAny, W>(args, lds_bytes, st, loss);
+  return chain_launch_as<G, kBackward, kChAny, W>(args, lds_bytes, q, loss);
 }
 
 template <int G, bool kBackward>
-static int chain_launch(const ChainArgs& args, int lds_bytes, hipStream_t st, const LossArgs* loss = nullptr) {
+static int chain_launch(const ChainArgs& args, int lds_bytes, const ChainQueue& q, const LossArgs* loss = nullptr) {
   if constexpr (G == 1) {
-    if (chain_waves(1, args.rows) == 8) return chain_launch_w<1, kBackward, 8>(args, lds_bytes, st, loss);
+    if (chain_waves(1, args.rows) == 8) return chain_launch_w<1, kBackward, 8>(args, lds_bytes, q, loss);
   }
-  return chain_launch_w<G, kBackward, 4>(args, lds_bytes, st, loss);
+  return chain_launch_w<G, kBackward, 4>(args, lds_bytes, q, loss);
 }
 
 
@@ -1682,25 +1679,6 @@ int rlg_mlp_chain_lds_bytes(int num_layers, const int* in_features, const int* o
   return rlg::chain_lds(num_layers, in_features, out_features, groups, direction, &b);
 }
 
-// The next rlg_mlp_chain_forward / _backward launch (not inside a graph capture) is bracketed by these two HIP
-// events (rlg_event_create); one-shot.  bench.py: in-epoch launch durations of the two dominant kernels.
-int rlg_mlp_chain_time_next(void* ev_start, void* ev_stop) {
-  rlg::g_chain_ev_start = static_cast<hipEvent_t>(ev_start);
-  rlg::g_chain_ev_stop = static_cast<hipEvent_t>(ev_stop);
-  return 0;
-}
-
-// The next rlg_mlp_chain_backward launch, if it runs the split-fp16 kernel, leaves per 64-row workgroup the largest magnitude
-// of every dZ tensor it produces (and of the d heads it reads) in entries[(layer) * stride + workgroup] (csrc/bx_form.hpp) -
-// what rlg_mlp_dw_gradient_maxima hands to the weight-gradient launch.  One-shot, like the timing events.
-static float* g_chain_amax = nullptr;
-static int g_chain_amax_stride = 0;
-int rlg_mlp_chain_gradient_maxima(float* entries, int stride) {
-  g_chain_amax = entries;
-  g_chain_amax_stride = stride;
-  return 0;
-}
-
 static long long* g_chain_dbg = nullptr;
 // tools only: phase stamps of the next forward launches ([blocks][4][32] int64), nullptr to stop
 int rlg_mlp_chain_debug_stamps(long long* buffer) {
@@ -1708,32 +1686,29 @@ int rlg_mlp_chain_debug_stamps(long long* buffer) {
   return 0;
 }
 
-int rlg_mlp_chain_forward(int num_layers, const float* const* weights, const float* const* biases,
-                          const int* in_features, const int* out_features, const int* acts,
-                          float* const* act_out, const long long* act_ld, const float* x, long long ldx,
-                          const double* rms_mean, const double* rms_var, float rms_eps, float* xn_out,
-                          const double* rms_batch, const long long* rms_count, double* rms_mean_out,
-                          double* rms_var_out, long long* rms_count_out,
-                          long long rows, int groups, void* pack_backward_planes_or_null,
-                          const void* weight_planes_or_null, void* stream) {
+int rlg_mlp_chain_forward(const rlg_chain_net* net, const rlg_chain_fwd* fwd, const rlg_chain_launch* launch, void* stream) {
   using namespace rlg;
+  if (net == nullptr || fwd == nullptr || launch == nullptr) return static_cast<int>(hipErrorInvalidValue);
+  const long long rows = launch->rows;
+  const int groups = launch->groups;
   if (rows <= 0) return 0;
   ChainArgs args;
-  if (chain_fill(args, num_layers, weights, in_features, out_features, acts)) return static_cast<int>(hipErrorInvalidValue);
-  args.amax = nullptr;
-  args.amax_stride = 0;
+  if (chain_fill(args, *net)) return static_cast<int>(hipErrorInvalidValue);
+  const int num_layers = net->num_layers;
+  const int* const in_features = net->in_features;
+  const int* const out_features = net->out_features;
+  float* const* const act_out = fwd->act_out;
+  const ChainQueue q = chain_queue(*launch, stream);
   // the backward launch's weight planes ride along as extra workgroups (with the tools' phase stamps, which index
   // their buffer by workgroup, as a launch of their own)
-  if (pack_backward_planes_or_null != nullptr &&
-      chain_bx_fill_pack(args.pack, num_layers, weights, in_features, out_features, 1, pack_backward_planes_or_null) &&
+  if (fwd->pack_backward_planes_or_null != nullptr &&
+      chain_bx_fill_pack(args.pack, num_layers, net->weights, in_features, out_features, 1, fwd->pack_backward_planes_or_null) &&
       g_chain_dbg != nullptr) {
-    if (const int e = chain_bx_pack_launch(args.pack, static_cast<hipStream_t>(stream))) return e;
+    if (const int e = chain_bx_pack_launch(args.pack, q.st)) return e;
     args.pack.total_pairs = 0;
   }
   if (act_out[num_layers - 1] == nullptr) return static_cast<int>(hipErrorInvalidValue);
-  if (const int e = chain_fill_forward(args, biases, act_out, act_ld, x, ldx, rms_mean, rms_var, rms_eps, xn_out, rms_batch,
-                                       rms_count, rms_mean_out, rms_var_out, rms_count_out, rows))
-    return e;
+  if (const int e = chain_fill_forward(args, *net, *fwd, rows)) return e;
   args.dbg = g_chain_dbg;
   bool training = false;
   for (int L = 0; L + 1 < num_layers; ++L) training = training || act_out[L] != nullptr;
@@ -1744,19 +1719,14 @@ int rlg_mlp_chain_forward(int num_layers, const float* const* weights, const flo
   args.lds_b_floats = b_floats;
   args.lds_split_floats = lds_bytes / 4 - chain_split_floats(G);
   args.no_ksplit = 0;
-  hipStream_t st = static_cast<hipStream_t>(stream);
   // split-bf16 products on pre-split weight planes (mlp_chain_bx_fwd.hip): 64-row workgroups
-  if (weight_planes_or_null != nullptr && chain_bx_fwd_wanted(rows, groups, training)) {
+  if (fwd->weight_form_or_null != nullptr && chain_bx_fwd_wanted(rows, groups, training)) {
     ChainArgs bx = args;
     const long long total = chain_bx_plane_offsets(num_layers, in_features, out_features, 0, bx.p_off);
-    bx.planes = weight_planes_or_null;
+    bx.planes = fwd->weight_form_or_null;
     bx.planes_bytes = static_cast<unsigned>(total);
     const int bx_lds = chain_bx_fwd_plan(bx);
-    if (bx_lds >= 0 && total < static_cast<long long>(kOob) && chain_bx_fwd_eligible(bx)) {
-      hipEvent_t ev0 = nullptr, ev1 = nullptr;
-      chain_take_events(&ev0, &ev1);
-      return chain_bx_launch_fwd(bx, bx_lds, st, ev0, ev1);
-    }
+    if (bx_lds >= 0 && total < static_cast<long long>(kOob) && chain_bx_fwd_eligible(bx)) return chain_bx_launch_fwd(bx, bx_lds, q);
   }
   // (round 4: the pipelined forward for 16-row workgroups as well - minibatches < 16,384 rows, a data-parallel rank's shapes:
   //  the unit-structured kernel pays a cold weight fetch at the head of each of its 8 chain_units calls there,
@@ -1764,34 +1734,32 @@ int rlg_mlp_chain_forward(int num_layers, const float* const* weights, const flo
   if (chain_pipe_fill(args, true)) {
     const bool elu_only = chain_elu_only(args);
     if (G == 1)
-      return elu_only ? chain_launch_fwd_pipe<1, kChElu, kPipe1Waves>(args, lds_bytes, st) : chain_launch_fwd_pipe<1, kChAny, kPipe1Waves>(args, lds_bytes, st);
-    if (G == 4) return elu_only ? chain_launch_fwd_pipe<4, kChElu>(args, lds_bytes, st) : chain_launch_fwd_pipe<4, kChAny>(args, lds_bytes, st);
-    return elu_only ? chain_launch_fwd_pipe<2, kChElu>(args, lds_bytes, st) : chain_launch_fwd_pipe<2, kChAny>(args, lds_bytes, st);
+      return elu_only ? chain_launch_fwd_pipe<1, kChElu, kPipe1Waves>(args, lds_bytes, q) : chain_launch_fwd_pipe<1, kChAny, kPipe1Waves>(args, lds_bytes, q);
+    if (G == 4) return elu_only ? chain_launch_fwd_pipe<4, kChElu>(args, lds_bytes, q) : chain_launch_fwd_pipe<4, kChAny>(args, lds_bytes, q);
+    return elu_only ? chain_launch_fwd_pipe<2, kChElu>(args, lds_bytes, q) : chain_launch_fwd_pipe<2, kChAny>(args, lds_bytes, q);
   }
-  if (G == 4) return chain_launch<4, false>(args, lds_bytes, st);
-  if (G == 2) return chain_launch<2, false>(args, lds_bytes, st);
-  return chain_launch<1, false>(args, lds_bytes, st);
+  if (G == 4) return chain_launch<4, false>(args, lds_bytes, q);
+  if (G == 2) return chain_launch<2, false>(args, lds_bytes, q);
+  return chain_launch<1, false>(args, lds_bytes, q);
 }
 
-int rlg_mlp_chain_backward(int num_layers, const float* const* weights, const int* in_features,
-                           const int* out_features, const int* acts, const float* const* act_in,
-                           const long long* act_ld, const float* d_out, long long ld_dout,
-                           float* const* dz_out, const long long* dz_ld, double* const* bias_partials,
-                           const rlg_ppo_loss_desc* ppo_loss, long long rows, int groups,
-                           const void* weight_planes_or_null, void* stream) {
+int rlg_mlp_chain_backward(const rlg_chain_net* net, const rlg_chain_bwd* bwd, const rlg_chain_launch* launch, void* stream) {
   using namespace rlg;
-  float* const amax = g_chain_amax;
-  const int amax_stride = g_chain_amax_stride;
-  g_chain_amax = nullptr;
+  if (net == nullptr || bwd == nullptr || launch == nullptr) return static_cast<int>(hipErrorInvalidValue);
+  if (bwd->maxima_rows_out_or_null) *bwd->maxima_rows_out_or_null = 0;
+  const long long rows = launch->rows;
+  const int groups = launch->groups;
   if (rows <= 0) return 0;
+  const int num_layers = net->num_layers;
   if (num_layers < 2) return static_cast<int>(hipErrorInvalidValue);
   ChainArgs args;
-  if (chain_fill(args, num_layers, weights, in_features, out_features, acts)) return static_cast<int>(hipErrorInvalidValue);
-  args.amax = nullptr;
-  args.amax_stride = 0;
-  chain_fill_backward(args, act_in, act_ld, d_out, ld_dout, dz_out, dz_ld, bias_partials, rows);
+  if (chain_fill(args, *net)) return static_cast<int>(hipErrorInvalidValue);
+  const int* const in_features = net->in_features;
+  const int* const out_features = net->out_features;
+  const rlg_ppo_loss_desc* const ppo_loss = bwd->ppo_loss_or_null;
+  chain_fill_backward(args, bwd->act_in, bwd->act_ld, *bwd, rows);
   for (int L = 0; L + 1 < num_layers; ++L) {
-    if (act_in[L] == nullptr || dz_out[L] == nullptr) return static_cast<int>(hipErrorInvalidValue);
+    if (bwd->act_in[L] == nullptr || bwd->dz_out[L] == nullptr) return static_cast<int>(hipErrorInvalidValue);
   }
   const int G = pick_groups(rows, groups, 1);
   int b_floats = 0;
@@ -1806,19 +1774,18 @@ int rlg_mlp_chain_backward(int num_layers, const float* const* weights, const in
     if (need > 160 * 1024) return static_cast<int>(hipErrorInvalidValue);
     if (need > lds_bytes) lds_bytes = need;
   }
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  const ChainQueue q = chain_queue(*launch, stream);
   const LossArgs* lp = ppo_loss ? &loss : nullptr;
   // split-bf16 products on pre-split weight planes (mlp_chain_bx.hip): 64-row workgroups, aligned activations
-  args.planes = nullptr;
-  if (weight_planes_or_null != nullptr && G == 4 && chain_bx_enabled()) {
+  if (bwd->weight_form_or_null != nullptr && G == 4 && chain_bx_enabled()) {
     const long long total = chain_bx_plane_offsets(num_layers, in_features, out_features, 1, args.p_off);
     ChainArgs bx = args;
     bx.dbg = g_chain_dbg;
-    bx.planes = weight_planes_or_null;
+    bx.planes = bwd->weight_form_or_null;
     bx.planes_bytes = static_cast<unsigned>(total);
-    if (amax != nullptr && amax_stride >= (rows + 16 * G - 1) / (16 * G)) {
-      bx.amax = amax;
-      bx.amax_stride = amax_stride;
+    if (bwd->maxima_or_null != nullptr && bwd->maxima_stride >= (rows + 16 * G - 1) / (16 * G)) {
+      bx.amax = bwd->maxima_or_null;
+      bx.amax_stride = bwd->maxima_stride;
     }
     int bx_lds = chain_bx_bwd_lds(bx, G);
     if (bx_lds >= 0 && total < static_cast<long long>(kOob) && chain_bx_bwd_eligible(bx)) {
@@ -1833,8 +1800,8 @@ int rlg_mlp_chain_backward(int num_layers, const float* const* weights, const in
         const int w = out_features[num_layers - 1];
         const int hld = (w + 1) | 1;
         const int hbytes = 16 * G * hld * 4;
-        if (w == 1 + d.actions_num && d.d_values == d_out && d.d_mu == d_out + 1 && d.ld_d_values == ld_dout &&
-            d.ld_d_mu == ld_dout && d.actions_num <= 32 && bx_lds + hbytes + kBxBwdScratch <= 160 * 1024) {
+        if (w == 1 + d.actions_num && d.d_values == bwd->d_out && d.d_mu == bwd->d_out + 1 && d.ld_d_values == bwd->ld_dout &&
+            d.ld_d_mu == bwd->ld_dout && d.actions_num <= 32 && bx_lds + hbytes + kBxBwdScratch <= 160 * 1024) {
           bx.bx_handoff_off = (bx_lds + 15) & ~15;
           bx.bx_handoff_ld = hld;
           bx_lds = bx.bx_handoff_off + hbytes;
@@ -1842,20 +1809,19 @@ int rlg_mlp_chain_backward(int num_layers, const float* const* weights, const in
       }
       bx.bx_scales_off = (bx_lds + 15) & ~15;                  // (row scales of the d heads tile, fp16 form)
       bx_lds = bx.bx_scales_off + 16 * G * 4 + kChainMaxLayers * 4 * 4;      // (+ the waves' gradient maxima of every layer)
-      hipEvent_t ev0 = g_chain_ev_start, ev1 = g_chain_ev_stop;
-      g_chain_ev_start = g_chain_ev_stop = nullptr;
-      if (bx_lds <= 160 * 1024) return chain_bx_launch_bwd(bx, G, bx_lds, st, lp, ev0, ev1);
-      g_chain_ev_start = ev0;
-      g_chain_ev_stop = ev1;
+      if (bx_lds <= 160 * 1024) {
+        if (bx.amax != nullptr && bwd->maxima_rows_out_or_null) *bwd->maxima_rows_out_or_null = 16 * G;
+        return chain_bx_launch_bwd(bx, G, bx_lds, q, lp);
+      }
     }
   }
-  if (G == 4) return chain_launch<4, true>(args, lds_bytes, st, lp);
-  if (G == 2) return chain_launch<2, true>(args, lds_bytes, st, lp);
+  if (G == 4) return chain_launch<4, true>(args, lds_bytes, q, lp);
+  if (G == 2) return chain_launch<2, true>(args, lds_bytes, q, lp);
   // 16-row workgroups: the pipelined kernel when every H / dZ array takes 16-byte row accesses
   if (g_chain_dbg == nullptr && chain_rows16_status(args) == 0)
-    return chain_launch_kernel(mlp_chain_bwd_pipe_kernel<kPipe1Waves>, static_cast<int>((rows + 15) / 16), 64 * kPipe1Waves, lds_bytes, st,
+    return chain_launch_kernel(mlp_chain_bwd_pipe_kernel<kPipe1Waves>, static_cast<int>((rows + 15) / 16), 64 * kPipe1Waves, lds_bytes, q,
                                args, lp ? *lp : LossArgs{});
-  return chain_launch<1, true>(args, lds_bytes, st, lp);
+  return chain_launch<1, true>(args, lds_bytes, q, lp);
 }
 
 
@@ -1864,16 +1830,18 @@ int rlg_mlp_chain_backward(int num_layers, const float* const* weights, const in
 // hipErrorNotSupported when the shape is outside the kernel's envelope (the caller then issues the two launches):
 // minibatches of >= 16,384 rows (they run the split-bf16 kernels), weights not in one arena, H / dZ rows not 16-byte
 // aligned, more than 32 actions.
-int rlg_mlp_chain_step(int num_layers, const float* const* weights, const float* const* biases,
-                       const int* in_features, const int* out_features, const int* acts,
-                       float* const* act_out, const long long* act_ld, const float* x, long long ldx,
-                       const double* rms_mean, const double* rms_var, float rms_eps, float* xn_out,
-                       const double* rms_batch, const long long* rms_count, double* rms_mean_out,
-                       double* rms_var_out, long long* rms_count_out, float* d_out, long long ld_dout,
-                       float* const* dz_out, const long long* dz_ld, double* const* bias_partials,
-                       const rlg_ppo_loss_desc* ppo_loss, long long rows, void* stream) {
+int rlg_mlp_chain_step(const rlg_chain_net* net, const rlg_chain_fwd* fwd, const rlg_chain_bwd* bwd,
+                       const rlg_chain_launch* launch, void* stream) {
   using namespace rlg;
+  if (net == nullptr || fwd == nullptr || bwd == nullptr || launch == nullptr) return static_cast<int>(hipErrorInvalidValue);
+  if (bwd->maxima_rows_out_or_null) *bwd->maxima_rows_out_or_null = 0;     // (this kernel leaves none)
+  const long long rows = launch->rows;
   if (rows <= 0) return 0;
+  const int num_layers = net->num_layers;
+  const int* const in_features = net->in_features;
+  const int* const out_features = net->out_features;
+  float* const* const act_out = fwd->act_out;
+  const rlg_ppo_loss_desc* const ppo_loss = bwd->ppo_loss_or_null;
   if (g_chain_dbg != nullptr || num_layers < 2 || ppo_loss == nullptr || pick_groups(rows, 0, 2) != 1 || pick_groups(rows, 0, 1) != 1)
     return static_cast<int>(hipErrorNotSupported);
   // one 8-wave workgroup per CU (200 registers per wave): beyond one round of workgroups the two separate launches,
@@ -1886,13 +1854,11 @@ int rlg_mlp_chain_step(int num_layers, const float* const* weights, const float*
   }
   // ---- forward arguments (as rlg_mlp_chain_forward)
   ChainArgs fa;
-  if (chain_fill(fa, num_layers, weights, in_features, out_features, acts)) return static_cast<int>(hipErrorInvalidValue);
+  if (chain_fill(fa, *net)) return static_cast<int>(hipErrorInvalidValue);
   for (int L = 0; L < num_layers; ++L) {
     if (act_out[L] == nullptr) return static_cast<int>(hipErrorNotSupported);       // training form only
   }
-  if (const int e = chain_fill_forward(fa, biases, act_out, act_ld, x, ldx, rms_mean, rms_var, rms_eps, xn_out, rms_batch,
-                                       rms_count, rms_mean_out, rms_var_out, rms_count_out, rows))
-    return e;
+  if (const int e = chain_fill_forward(fa, *net, *fwd, rows)) return e;
   fa.dbg = nullptr;
   int fb = 0;
   const int fwd_lds = chain_lds(num_layers, in_features, out_features, 1, 0, &fb);
@@ -1903,8 +1869,8 @@ int rlg_mlp_chain_step(int num_layers, const float* const* weights, const float*
   if (!chain_pipe_fill(fa, true)) return static_cast<int>(hipErrorNotSupported);
   // ---- backward arguments (as rlg_mlp_chain_backward); H of the hidden layers = what the forward half writes
   ChainArgs ba;
-  if (chain_fill(ba, num_layers, weights, in_features, out_features, acts)) return static_cast<int>(hipErrorInvalidValue);
-  chain_fill_backward(ba, act_out, act_ld, d_out, ld_dout, dz_out, dz_ld, bias_partials, rows);
+  if (chain_fill(ba, *net)) return static_cast<int>(hipErrorInvalidValue);
+  chain_fill_backward(ba, act_out, fwd->act_ld, *bwd, rows);
   if (const int e = chain_rows16_status(ba)) return e;
   ba.with_loss = 1;
   int bb = 0;
@@ -1920,7 +1886,7 @@ int rlg_mlp_chain_step(int num_layers, const float* const* weights, const float*
   if (need > lds_bytes) lds_bytes = need;
   if (lds_bytes > 160 * 1024) return static_cast<int>(hipErrorNotSupported);
   const auto kern = chain_elu_only(fa) ? mlp_chain_step_pipe_kernel<kChElu, kPipe1Waves> : mlp_chain_step_pipe_kernel<kChAny, kPipe1Waves>;
-  return chain_launch_kernel(kern, static_cast<int>((rows + 15) / 16), 64 * kPipe1Waves, lds_bytes, static_cast<hipStream_t>(stream), fa, ba, loss);
+  return chain_launch_kernel(kern, static_cast<int>((rows + 15) / 16), 64 * kPipe1Waves, lds_bytes, chain_queue(*launch, stream), fa, ba, loss);
 }
 
 
@@ -1929,14 +1895,4 @@ int rlg_mlp_chain_step(int num_layers, const float* const* weights, const float*
 // ---- what mlp_chain_lean.hip needs of this file's launch state (mlp_chain_shared.hpp)
 namespace rlg {
 long long* chain_debug_stamps() { return g_chain_dbg; }
-void chain_take_events(hipEvent_t* ev_start, hipEvent_t* ev_stop) {
-  *ev_start = g_chain_ev_start;
-  *ev_stop = g_chain_ev_stop;
-  g_chain_ev_start = g_chain_ev_stop = nullptr;
-}
-void chain_take_gradient_maxima(float** entries, int* stride) {
-  *entries = ::g_chain_amax;
-  *stride = ::g_chain_amax_stride;
-  ::g_chain_amax = nullptr;
-}
 }  // namespace rlg

@@ -401,10 +401,9 @@ bool chain_bx_bwd_eligible(const ChainArgs& args) {
 }
 
 template <int G, int PACT>
-static int chain_bx_launch_bwd_as(const ChainArgs& args, int lds_bytes, hipStream_t st, const LossArgs* loss, hipEvent_t ev0,
-                                  hipEvent_t ev1) {
+static int chain_bx_launch_bwd_as(const ChainArgs& args, int lds_bytes, const ChainQueue& q, const LossArgs* loss) {
   const int grid = static_cast<int>((args.rows + 16 * G - 1) / (16 * G));
-  return chain_launch_timed(mlp_chain_bwd_bx_kernel<G, PACT>, grid, 64 * kBwW, lds_bytes, st, ev0, ev1, args, loss ? *loss : LossArgs{});
+  return chain_launch_kernel(mlp_chain_bwd_bx_kernel<G, PACT>, grid, 64 * kBwW, lds_bytes, q, args, loss ? *loss : LossArgs{});
 }
 // raises the dynamic-LDS limit of the kernels once, outside any stream capture (rlg_mlp_chain_prepare)
 int chain_bx_prepare() {
@@ -418,14 +417,13 @@ int chain_bx_prepare() {
   raised = true;
   return 0;
 }
-int chain_bx_launch_bwd(const ChainArgs& args, int G, int lds_bytes, hipStream_t st, const LossArgs* loss, hipEvent_t ev0,
-                        hipEvent_t ev1) {
+int chain_bx_launch_bwd(const ChainArgs& args, int G, int lds_bytes, const ChainQueue& q, const LossArgs* loss) {
   if (G != 4) return static_cast<int>(hipErrorInvalidValue);
   if (const int e = chain_bx_prepare()) return e;
   bool elu_only = true;       // every layer whose derivative is taken (all but the head)
   for (int L = 0; L + 1 < args.num_layers; ++L) elu_only = elu_only && args.layer[L].act == kChElu;
-  return elu_only ? chain_bx_launch_bwd_as<4, kChElu>(args, lds_bytes, st, loss, ev0, ev1)
-                  : chain_bx_launch_bwd_as<4, kChAny>(args, lds_bytes, st, loss, ev0, ev1);
+  return elu_only ? chain_bx_launch_bwd_as<4, kChElu>(args, lds_bytes, q, loss)
+                  : chain_bx_launch_bwd_as<4, kChAny>(args, lds_bytes, q, loss);
 }
 
 }  // namespace rlg

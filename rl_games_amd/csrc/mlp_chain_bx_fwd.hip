@@ -506,12 +506,12 @@ bool chain_bx_fwd_eligible(const ChainArgs& args) {
 }
 
 template <int HACT>
-static int chain_bx_launch_fwd_as(const ChainArgs& args_in, int lds_bytes, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
+static int chain_bx_launch_fwd_as(const ChainArgs& args_in, int lds_bytes, const ChainQueue& q) {
   ChainArgs args = args_in;
   int grid = static_cast<int>((args.rows + 16 * kFwG - 1) / (16 * kFwG));
   args.fwd_blocks = grid;
   if (args.pack.total_pairs > 0) grid += chain_bx_pack_blocks(args.pack);
-  return chain_launch_timed(mlp_chain_fwd_bx_kernel<HACT>, grid, 64 * kFwW, lds_bytes, st, ev0, ev1, args);
+  return chain_launch_kernel(mlp_chain_fwd_bx_kernel<HACT>, grid, 64 * kFwW, lds_bytes, q, args);
 }
 int chain_bx_fwd_prepare() {
   static bool raised = false;
@@ -524,10 +524,10 @@ int chain_bx_fwd_prepare() {
   raised = true;
   return 0;
 }
-int chain_bx_launch_fwd(const ChainArgs& args, int lds_bytes, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
+int chain_bx_launch_fwd(const ChainArgs& args, int lds_bytes, const ChainQueue& q) {
   if (const int e = chain_bx_fwd_prepare()) return e;
-  return chain_elu_only(args) ? chain_bx_launch_fwd_as<kChElu>(args, lds_bytes, st, ev0, ev1)
-                  : chain_bx_launch_fwd_as<kChAny>(args, lds_bytes, st, ev0, ev1);
+  return chain_elu_only(args) ? chain_bx_launch_fwd_as<kChElu>(args, lds_bytes, q)
+                  : chain_bx_launch_fwd_as<kChAny>(args, lds_bytes, q);
 }
 
 }  // namespace rlg

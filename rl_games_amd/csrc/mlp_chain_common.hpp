@@ -314,12 +314,16 @@ long long chain_bx_plane_offsets(int num_layers, const int* in_features, const i
                                  unsigned* offsets);
 bool chain_bx_bwd_eligible(const ChainArgs& args);
 int chain_bx_prepare();
+// Where a chain launch goes: the stream, and the timing events of rlg_chain_launch on its dispatch (or none)
+struct ChainQueue {
+  hipStream_t st;
+  hipEvent_t ev0, ev1;
+};
 // forward: LDS plan (fills bx_tile_off / bx_stats_off / bx_pass_*), bytes or -1; eligibility; launch
 int chain_bx_fwd_plan(ChainArgs& args);
 bool chain_bx_fwd_eligible(const ChainArgs& args);
-int chain_bx_launch_fwd(const ChainArgs& args, int lds_bytes, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+int chain_bx_launch_fwd(const ChainArgs& args, int lds_bytes, const ChainQueue& q);
 int chain_bx_fwd_prepare();
-int chain_bx_launch_bwd(const ChainArgs& args, int G, int lds_bytes, hipStream_t st, const LossArgs* loss, hipEvent_t ev0,
-                        hipEvent_t ev1);
+int chain_bx_launch_bwd(const ChainArgs& args, int G, int lds_bytes, const ChainQueue& q, const LossArgs* loss);
 
 }  // namespace rlg

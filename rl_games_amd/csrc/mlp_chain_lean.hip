@@ -649,27 +649,24 @@ int rlg_mlp_chain_pack_frags(int num_layers, const float* const* weights, const 
   RLG_RETURN_LAUNCH_STATUS();
 }
 
-int rlg_mlp_chain_forward_lean(int num_layers, const float* const* biases, const int* in_features, const int* out_features,
-                               const int* acts, float* const* act_out, const long long* act_ld, const float* x, long long ldx,
-                               const double* rms_mean, const double* rms_var, float rms_eps, float* xn_out,
-                               const double* rms_batch, const long long* rms_count, double* rms_mean_out,
-                               double* rms_var_out, long long* rms_count_out, long long rows, const void* frags,
-                               void* stream) {
+int rlg_mlp_chain_forward_lean(const rlg_chain_net* net, const rlg_chain_fwd* fwd, const rlg_chain_launch* launch, void* stream) {
   using namespace rlg;
+  if (net == nullptr || fwd == nullptr || launch == nullptr) return static_cast<int>(hipErrorInvalidValue);
+  const long long rows = launch->rows;
   if (rows <= 0) return 0;
+  const void* const frags = fwd->weight_form_or_null;
   if (frags == nullptr || reinterpret_cast<uintptr_t>(frags) % 4 != 0) return static_cast<int>(hipErrorInvalidValue);
   ChainArgs args;
-  if (chain_fill_shape(args, num_layers, in_features, out_features, acts)) return static_cast<int>(hipErrorInvalidValue);
+  if (chain_fill_shape(args, *net)) return static_cast<int>(hipErrorInvalidValue);
+  const int num_layers = net->num_layers;
   LeanPackArgs pk = {};
-  const long long plan = chain_lean_plan(num_layers, in_features, out_features, 0, &pk);
+  const long long plan = chain_lean_plan(num_layers, net->in_features, net->out_features, 0, &pk);
   if (plan < 0) return static_cast<int>(hipErrorNotSupported);
   for (int L = 0; L < num_layers; ++L) {
-    if (biases && reinterpret_cast<uintptr_t>(biases[L]) % 4 != 0) return static_cast<int>(hipErrorInvalidValue);
+    if (net->biases && reinterpret_cast<uintptr_t>(net->biases[L]) % 4 != 0) return static_cast<int>(hipErrorInvalidValue);
   }
-  if (act_out[num_layers - 1] == nullptr) return static_cast<int>(hipErrorInvalidValue);
-  if (const int e = chain_fill_forward(args, biases, act_out, act_ld, x, ldx, rms_mean, rms_var, rms_eps, xn_out, rms_batch,
-                                       rms_count, rms_mean_out, rms_var_out, rms_count_out, rows))
-    return e;
+  if (fwd->act_out[num_layers - 1] == nullptr) return static_cast<int>(hipErrorInvalidValue);
+  if (const int e = chain_fill_forward(args, *net, *fwd, rows)) return e;
   args.dbg = chain_debug_stamps();
   args.lds_b_floats = pk.la.tile_b_floats;
   args.lds_split_floats = 0;
@@ -679,22 +676,38 @@ int rlg_mlp_chain_forward_lean(int num_layers, const float* const* biases, const
   const int lds_bytes = chain_lean_tile_floats(plan) * 4;
   if (lds_bytes > 64 * 1024) return static_cast<int>(hipErrorNotSupported);
   const auto kern = chain_elu_only(args) ? mlp_chain_fwd_lean_kernel<kChElu> : mlp_chain_fwd_lean_kernel<kChAny>;
-  return chain_launch_kernel(kern, static_cast<int>((rows + 15) / 16), 64 * kLeanW, lds_bytes, static_cast<hipStream_t>(stream), args, la);
+  return chain_launch_kernel(kern, static_cast<int>((rows + 15) / 16), 64 * kLeanW, lds_bytes, chain_queue(*launch, stream), args, la);
 }
 
-int rlg_mlp_chain_backward_lean(int num_layers, const int* in_features, const int* out_features, const int* acts,
-                                const float* const* act_in, const long long* act_ld, const float* d_out, long long ld_dout,
-                                float* const* dz_out, const long long* dz_ld, double* const* bias_partials,
-                                const rlg_ppo_loss_desc* ppo_loss, long long rows, const void* frags, void* stream) {
+// Gradient maxima of a lean backward (rlg_chain_bwd; one entry per 16-row workgroup): the waves' maxima sit behind everything
+// else in LDS.  hipErrorInvalidValue for fewer entries per tensor than workgroups.
+static int chain_lean_maxima(rlg::ChainArgs& args, const rlg_chain_bwd& bwd, long long rows, int* lds_bytes) {
   using namespace rlg;
+  if (bwd.maxima_or_null == nullptr) return 0;
+  if (bwd.maxima_stride < (rows + 15) / 16) return static_cast<int>(hipErrorInvalidValue);
+  args.amax = bwd.maxima_or_null;
+  args.amax_stride = bwd.maxima_stride;
+  args.bx_scales_off = (*lds_bytes + 15) & ~15;
+  *lds_bytes = args.bx_scales_off + kChainMaxLayers * kLeanW * 4;
+  return 0;
+}
+
+int rlg_mlp_chain_backward_lean(const rlg_chain_net* net, const rlg_chain_bwd* bwd, const rlg_chain_launch* launch, void* stream) {
+  using namespace rlg;
+  if (net == nullptr || bwd == nullptr || launch == nullptr) return static_cast<int>(hipErrorInvalidValue);
+  if (bwd->maxima_rows_out_or_null) *bwd->maxima_rows_out_or_null = 0;
+  const long long rows = launch->rows;
   if (rows <= 0) return 0;
+  const int num_layers = net->num_layers;
+  const void* const frags = bwd->weight_form_or_null;
+  const rlg_ppo_loss_desc* const ppo_loss = bwd->ppo_loss_or_null;
   if (num_layers < 2 || frags == nullptr || reinterpret_cast<uintptr_t>(frags) % 4 != 0) return static_cast<int>(hipErrorInvalidValue);
   ChainArgs args;
-  if (chain_fill_shape(args, num_layers, in_features, out_features, acts)) return static_cast<int>(hipErrorInvalidValue);
+  if (chain_fill_shape(args, *net)) return static_cast<int>(hipErrorInvalidValue);
   LeanPackArgs pk = {};
-  const long long plan = chain_lean_plan(num_layers, in_features, out_features, 1, &pk);
+  const long long plan = chain_lean_plan(num_layers, net->in_features, net->out_features, 1, &pk);
   if (plan < 0) return static_cast<int>(hipErrorNotSupported);
-  chain_fill_backward(args, act_in, act_ld, d_out, ld_dout, dz_out, dz_ld, bias_partials, rows);
+  chain_fill_backward(args, bwd->act_in, bwd->act_ld, *bwd, rows);
   if (const int e = chain_rows16_status(args)) return e;
   args.lds_b_floats = pk.la.tile_b_floats;
   int lds_bytes = chain_lean_tile_floats(plan) * 4;
@@ -705,27 +718,13 @@ int rlg_mlp_chain_backward_lean(int num_layers, const int* in_features, const in
     const int need = static_cast<int>(ppo_loss_lds_bytes(16, ppo_loss->actions_num, 512));
     if (need > lds_bytes) lds_bytes = need;
   }
-  // gradient maxima for the weight-gradient launch (rlg_mlp_chain_gradient_maxima; one entry per 16-row workgroup here): the
-  // waves' maxima sit behind everything else in LDS
-  args.amax = nullptr;
-  args.amax_stride = 0;
-  {
-    float* entries = nullptr;
-    int stride = 0;
-    chain_take_gradient_maxima(&entries, &stride);
-    if (entries != nullptr) {
-      if (stride < (rows + 15) / 16) return static_cast<int>(hipErrorInvalidValue);
-      args.amax = entries;
-      args.amax_stride = stride;
-      args.bx_scales_off = (lds_bytes + 15) & ~15;
-      lds_bytes = args.bx_scales_off + kChainMaxLayers * kLeanW * 4;
-    }
-  }
+  if (const int e = chain_lean_maxima(args, *bwd, rows, &lds_bytes)) return e;
   if (lds_bytes > 64 * 1024) return static_cast<int>(hipErrorNotSupported);
   LeanArgs la = pk.la;
   la.wf = static_cast<const float*>(frags);
+  if (args.amax != nullptr && bwd->maxima_rows_out_or_null) *bwd->maxima_rows_out_or_null = 16;
   return chain_launch_kernel(mlp_chain_bwd_lean_kernel, static_cast<int>((rows + 15) / 16), 64 * kLeanW, lds_bytes,
-                             static_cast<hipStream_t>(stream), args, la, loss);
+                             chain_queue(*launch, stream), args, la, loss);
 }
 
 // forward and backward fragments of the lean kernels in ONE launch (behind every optimiser step of an agent whose
@@ -752,16 +751,21 @@ int rlg_mlp_chain_pack_frags_both(int num_layers, const float* const* weights, c
   RLG_RETURN_LAUNCH_STATUS();
 }
 
-int rlg_mlp_chain_step_lean(int num_layers, const float* const* biases, const int* in_features, const int* out_features,
-                            const int* acts, float* const* act_out, const long long* act_ld, const float* x, long long ldx,
-                            const double* rms_mean, const double* rms_var, float rms_eps, float* xn_out,
-                            const double* rms_batch, const long long* rms_count, double* rms_mean_out,
-                            double* rms_var_out, long long* rms_count_out, float* d_out, long long ld_dout,
-                            float* const* dz_out, const long long* dz_ld, double* const* bias_partials,
-                            const rlg_ppo_loss_desc* ppo_loss, long long rows, const void* frags_fwd, const void* frags_bwd,
-                            void* stream) {
+int rlg_mlp_chain_step_lean(const rlg_chain_net* net, const rlg_chain_fwd* fwd, const rlg_chain_bwd* bwd,
+                            const rlg_chain_launch* launch, void* stream) {
   using namespace rlg;
+  if (net == nullptr || fwd == nullptr || bwd == nullptr || launch == nullptr) return static_cast<int>(hipErrorInvalidValue);
+  if (bwd->maxima_rows_out_or_null) *bwd->maxima_rows_out_or_null = 0;
+  const long long rows = launch->rows;
   if (rows <= 0) return 0;
+  const int num_layers = net->num_layers;
+  const int* const in_features = net->in_features;
+  const int* const out_features = net->out_features;
+  const float* const* const biases = net->biases;
+  float* const* const act_out = fwd->act_out;
+  const void* const frags_fwd = fwd->weight_form_or_null;
+  const void* const frags_bwd = bwd->weight_form_or_null;
+  const rlg_ppo_loss_desc* const ppo_loss = bwd->ppo_loss_or_null;
   if (num_layers < 2 || ppo_loss == nullptr || frags_fwd == nullptr || frags_bwd == nullptr || chain_debug_stamps() != nullptr)
     return static_cast<int>(hipErrorNotSupported);
   // one 8-wave workgroup per CU holds the loss inputs through the forward (> 128 registers): beyond one round of workgroups
@@ -773,7 +777,7 @@ int rlg_mlp_chain_step_lean(int num_layers, const float* const* biases, const in
     if ((rows + 15) / 16 > cus) return static_cast<int>(hipErrorNotSupported);
   }
   ChainArgs fa;
-  if (chain_fill_shape(fa, num_layers, in_features, out_features, acts) || reinterpret_cast<uintptr_t>(frags_fwd) % 4 != 0)
+  if (chain_fill_shape(fa, *net) || reinterpret_cast<uintptr_t>(frags_fwd) % 4 != 0)
     return static_cast<int>(hipErrorInvalidValue);
   LeanPackArgs fpk = {}, bpk = {};
   const long long fplan = chain_lean_plan(num_layers, in_features, out_features, 0, &fpk);
@@ -783,16 +787,14 @@ int rlg_mlp_chain_step_lean(int num_layers, const float* const* biases, const in
     if (act_out[L] == nullptr) return static_cast<int>(hipErrorNotSupported);       // training form only
     if (biases && reinterpret_cast<uintptr_t>(biases[L]) % 4 != 0) return static_cast<int>(hipErrorInvalidValue);
   }
-  if (const int e = chain_fill_forward(fa, biases, act_out, act_ld, x, ldx, rms_mean, rms_var, rms_eps, xn_out, rms_batch,
-                                       rms_count, rms_mean_out, rms_var_out, rms_count_out, rows))
-    return e;
+  if (const int e = chain_fill_forward(fa, *net, *fwd, rows)) return e;
   fa.dbg = nullptr;
   fa.lds_b_floats = fpk.la.tile_b_floats;
   fa.lds_split_floats = 0;
   fa.no_ksplit = 1;
   ChainArgs ba;
-  if (chain_fill_shape(ba, num_layers, in_features, out_features, acts)) return static_cast<int>(hipErrorInvalidValue);
-  chain_fill_backward(ba, act_out, act_ld, d_out, ld_dout, dz_out, dz_ld, bias_partials, rows);
+  if (chain_fill_shape(ba, *net)) return static_cast<int>(hipErrorInvalidValue);
+  chain_fill_backward(ba, act_out, fwd->act_ld, *bwd, rows);
   if (const int e = chain_rows16_status(ba)) return e;
   ba.with_loss = 1;
   ba.lds_b_floats = bpk.la.tile_b_floats;
@@ -804,28 +806,14 @@ int rlg_mlp_chain_step_lean(int num_layers, const float* const* biases, const in
   if (chain_lean_tile_floats(bplan) * 4 > lds_bytes) lds_bytes = chain_lean_tile_floats(bplan) * 4;
   const int need = static_cast<int>(ppo_loss_lds_bytes(16, d.actions_num, 512));
   if (need > lds_bytes) lds_bytes = need;
-  // gradient maxima for the weight-gradient launch (rlg_mlp_chain_gradient_maxima; one entry per 16-row workgroup here): the
-  // waves' maxima sit behind everything else in LDS
-  ba.amax = nullptr;
-  ba.amax_stride = 0;
-  {
-    float* entries = nullptr;
-    int stride = 0;
-    chain_take_gradient_maxima(&entries, &stride);
-    if (entries != nullptr) {
-      if (stride < (rows + 15) / 16) return static_cast<int>(hipErrorInvalidValue);
-      ba.amax = entries;
-      ba.amax_stride = stride;
-      ba.bx_scales_off = (lds_bytes + 15) & ~15;
-      lds_bytes = ba.bx_scales_off + kChainMaxLayers * kLeanW * 4;
-    }
-  }
+  if (const int e = chain_lean_maxima(ba, *bwd, rows, &lds_bytes)) return e;
   if (lds_bytes > 64 * 1024) return static_cast<int>(hipErrorNotSupported);
   LeanArgs fla = fpk.la, bla = bpk.la;
   fla.wf = static_cast<const float*>(frags_fwd);
   bla.wf = static_cast<const float*>(frags_bwd);
   const auto kern = chain_elu_only(fa) ? mlp_chain_step_lean_kernel<kChElu> : mlp_chain_step_lean_kernel<kChAny>;
-  return chain_launch_kernel(kern, static_cast<int>((rows + 15) / 16), 64 * kLeanW, lds_bytes, static_cast<hipStream_t>(stream), fa, fla,
+  if (ba.amax != nullptr && bwd->maxima_rows_out_or_null) *bwd->maxima_rows_out_or_null = 16;
+  return chain_launch_kernel(kern, static_cast<int>((rows + 15) / 16), 64 * kLeanW, lds_bytes, chain_queue(*launch, stream), fa, fla,
                              ba, bla, loss);
 }
 

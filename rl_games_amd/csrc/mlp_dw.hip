@@ -82,11 +82,6 @@ static bool dw_f16_products() {
   return on && dw_split_products();
 }
 
-// rlg_mlp_dw_gradient_maxima: one-shot, consumed by the next rlg_mlp_dw_launch
-static const float* g_dw_amax = nullptr;
-static int g_dw_amax_stride = 0, g_dw_amax_dz[kDwMaxLayers], g_dw_amax_n = 0, g_dw_amax_rows = 64;
-static float g_dw_scale_x[kDwMaxLayers];
-
 struct DwLayer {
   const float* dz;     // [rows, lda]
   const float* x;      // [rows, ldb]
@@ -861,28 +856,29 @@ long long rlg_mlp_dw_plan(int rows, int out_features, int in_features, int targe
 // and x [rows, Mi] are contiguous (row stride = width).
 // form: kDwExact / kDwBf16 / kDwF16, or -1 = the library's choice (the fp16 form when the launch has its operands' maxima,
 // else what RLG_DW_BF16 says)
-static int dw_launch_impl(int form, int num_layers, const float* const* dz, const float* const* x, float* const* partial,
-                          float* const* grad, const int* out_features, const int* in_features,
-                          const int* plans4, int rows, int num_colsums, const double* const* colsum_partials,
-                          const int* colsum_blocks, const int* colsum_cols, float* const* colsum_out,
-                          const rlg_loss_finalize_desc* loss_finalize, double* norm_partials, float grad_scale,
-                          long long* step_counter, int* finalize_blocks_out, void* stream) {
+static int dw_launch_impl(int form, const rlg_mlp_dw_desc* desc, void* stream) {
   using namespace rlg;
+  if (desc == nullptr) return static_cast<int>(hipErrorInvalidValue);
+  const rlg_mlp_dw_desc& d = *desc;
+  const int num_layers = d.num_layers, rows = d.rows, num_colsums = d.num_colsums;
   if (num_layers <= 0 || num_layers > kDwMaxLayers || rows <= 0 || num_colsums < 0 ||
       num_colsums > kDwMaxLayers || form < -1 || form > kDwF16)
     return static_cast<int>(hipErrorInvalidValue);
   DwArgs args;
   args.num_layers = num_layers;
   args.rows = rows;
-  // fp16 form: the gradients' largest magnitudes per 64 rows - left by the split-fp16 backward (rlg_mlp_dw_gradient_maxima) -
-  // and the other operand's fixed scale; or, for the tools, host-side bounds from the environment; neither: the bf16 form
-  const float* amax = (g_dw_amax_n == num_layers && g_dw_amax_stride >= (rows + g_dw_amax_rows - 1) / g_dw_amax_rows) ? g_dw_amax : nullptr;
-  args.amax_shift = g_dw_amax_rows == 16 ? 4 : 6;
-  const int amax_stride = g_dw_amax_stride;
-  float scale_x[kDwMaxLayers];
-  for (int l = 0; l < kDwMaxLayers; ++l) scale_x[l] = g_dw_scale_x[l];
-  g_dw_amax = nullptr;
-  g_dw_amax_n = 0;
+  // fp16 form: the gradients' largest magnitudes per 64 (16) rows - left by the split-fp16 backward - and the other
+  // operand's fixed scale; or, for the tools, host-side bounds from the environment; neither: the bf16 form
+  const float* amax = nullptr;
+  if (d.maxima_or_null != nullptr) {
+    if (d.maxima_stride <= 0 || (d.maxima_rows_per_entry != 16 && d.maxima_rows_per_entry != 64))
+      return static_cast<int>(hipErrorInvalidValue);
+    for (int l = 0; l < num_layers; ++l) {
+      if (d.dz_slot[l] < 0 || d.dz_slot[l] >= 8 || !(d.x_scale[l] > 0.0f)) return static_cast<int>(hipErrorInvalidValue);
+    }
+    if (d.maxima_stride >= (rows + d.maxima_rows_per_entry - 1) / d.maxima_rows_per_entry) amax = d.maxima_or_null;
+  }
+  args.amax_shift = (amax != nullptr && d.maxima_rows_per_entry == 16) ? 4 : 6;
   const char* ea = std::getenv("RLG_DW_F16_AMAX_DZ");
   const char* eb = std::getenv("RLG_DW_F16_AMAX_X");
   const float host_amax_dz = ea ? static_cast<float>(std::atof(ea)) : 0.0f;
@@ -893,18 +889,18 @@ static int dw_launch_impl(int form, int num_layers, const float* const* dz, cons
   int blocks = 0, fin_blocks = 0;
   for (int l = 0; l < num_layers; ++l) {
     DwLayer& L = args.layer[l];
-    L.dz = dz[l];
-    L.x = x[l];
-    L.partial = partial[l];
-    L.grad = grad[l];
-    L.No = out_features[l];
-    L.Mi = in_features[l];
+    L.dz = d.dz[l];
+    L.x = d.x[l];
+    L.partial = d.partial[l];
+    L.grad = d.grad[l];
+    L.No = d.out_features[l];
+    L.Mi = d.in_features[l];
     L.lda = L.No;
     L.ldb = L.Mi;
-    L.ksplit = plans4[4 * l + 3];
-    L.amax_dz_entries = amax ? amax + static_cast<long long>(g_dw_amax_dz[l]) * amax_stride : nullptr;
+    L.ksplit = d.plans4[4 * l + 3];
+    L.amax_dz_entries = amax ? amax + static_cast<long long>(d.dz_slot[l]) * d.maxima_stride : nullptr;
     L.amax_dz = host_amax_dz;
-    L.scale_x = amax ? scale_x[l] : f16_scale_host(host_amax_x);
+    L.scale_x = amax ? d.x_scale[l] : f16_scale_host(host_amax_x);
     if (L.ksplit < 1 || (reinterpret_cast<uintptr_t>(L.partial) | reinterpret_cast<uintptr_t>(L.grad)) % 16 != 0 ||
         (static_cast<long long>(L.No) * L.Mi) % 4 != 0)
       return static_cast<int>(hipErrorInvalidValue);
@@ -919,17 +915,17 @@ static int dw_launch_impl(int form, int num_layers, const float* const* dz, cons
   cs.count = num_colsums;
   int cs_blocks = 0;
   for (int k = 0; k < num_colsums; ++k) {
-    if (colsum_cols[k] <= 0 || colsum_blocks[k] <= 0) return static_cast<int>(hipErrorInvalidValue);
-    cs.partials[k] = colsum_partials[k];
-    cs.out[k] = colsum_out[k];
-    cs.nblocks[k] = colsum_blocks[k];
-    cs.cols[k] = colsum_cols[k];
-    cs_blocks += (colsum_cols[k] + kCsCols - 1) / kCsCols;
+    if (d.colsum_cols[k] <= 0 || d.colsum_blocks[k] <= 0) return static_cast<int>(hipErrorInvalidValue);
+    cs.partials[k] = d.colsum_partials[k];
+    cs.out[k] = d.colsum_out[k];
+    cs.nblocks[k] = d.colsum_blocks[k];
+    cs.cols[k] = d.colsum_cols[k];
+    cs_blocks += (d.colsum_cols[k] + kCsCols - 1) / kCsCols;
   }
   cs.num_blocks = cs_blocks;
   LossFinalizeItem lf = {};
-  if (loss_finalize) {
-    lf.d = *loss_finalize;
+  if (d.loss_finalize_or_null) {
+    lf.d = *d.loss_finalize_or_null;
     if (!lf.d.partials || lf.d.num_blocks <= 0 || lf.d.actions_num < 0 || !lf.d.scalars8 ||
         (lf.d.actions_num > 0 && !lf.d.d_logstd))
       return static_cast<int>(hipErrorInvalidValue);
@@ -940,54 +936,16 @@ static int dw_launch_impl(int form, int num_layers, const float* const* dz, cons
   if (form == kDwF16) hipLaunchKernelGGL(mlp_dw_f16x3_kernel, dim3(blocks), dim3(256), 0, st, args);
   else if (form == kDwBf16) hipLaunchKernelGGL(mlp_dw_bf16x6_kernel, dim3(blocks), dim3(256), 0, st, args);
   else hipLaunchKernelGGL(mlp_dw_kernel, dim3(blocks), dim3(256), 0, st, args);
-  if (finalize_blocks_out) *finalize_blocks_out = total_vb;
-  NormItem nrm = {norm_partials, norm_partials ? step_counter : nullptr, grad_scale};
+  if (d.finalize_blocks_out_or_null) *d.finalize_blocks_out_or_null = total_vb;
+  NormItem nrm = {d.norm_partials_or_null, d.norm_partials_or_null ? d.step_counter_or_null : nullptr, d.grad_scale};
   hipLaunchKernelGGL(mlp_dw_finalize_kernel, dim3(total_vb), dim3(256), 0, st, args, cs, lf, nrm);
   RLG_RETURN_LAUNCH_STATUS();
 }
 
-int rlg_mlp_dw_gradient_maxima(const float* entries, int stride, int rows_per_entry, const int* dz_slot, const float* x_scale,
-                               int num_layers) {
-  using namespace rlg;
-  g_dw_amax = nullptr;
-  g_dw_amax_n = 0;
-  if (entries == nullptr) return 0;
-  if (num_layers <= 0 || num_layers > kDwMaxLayers || stride <= 0 || (rows_per_entry != 16 && rows_per_entry != 64))
-    return static_cast<int>(hipErrorInvalidValue);
-  g_dw_amax_rows = rows_per_entry;
-  for (int l = 0; l < num_layers; ++l) {
-    if (dz_slot[l] < 0 || dz_slot[l] >= 8 || !(x_scale[l] > 0.0f)) return static_cast<int>(hipErrorInvalidValue);
-    g_dw_amax_dz[l] = dz_slot[l];
-    g_dw_scale_x[l] = x_scale[l];
-  }
-  g_dw_amax = entries;
-  g_dw_amax_stride = stride;
-  g_dw_amax_n = num_layers;
-  return 0;
-}
+int rlg_mlp_dw_launch(const rlg_mlp_dw_desc* desc, void* stream) { return dw_launch_impl(-1, desc, stream); }
 
-int rlg_mlp_dw_launch(int num_layers, const float* const* dz, const float* const* x, float* const* partial,
-                      float* const* grad, const int* out_features, const int* in_features,
-                      const int* plans4, int rows, int num_colsums, const double* const* colsum_partials,
-                      const int* colsum_blocks, const int* colsum_cols, float* const* colsum_out,
-                      const rlg_loss_finalize_desc* loss_finalize, double* norm_partials, float grad_scale,
-                      long long* step_counter, int* finalize_blocks_out, void* stream) {
-  return dw_launch_impl(-1, num_layers, dz, x, partial, grad, out_features, in_features, plans4, rows, num_colsums,
-                        colsum_partials, colsum_blocks, colsum_cols, colsum_out, loss_finalize, norm_partials, grad_scale,
-                        step_counter, finalize_blocks_out, stream);
-}
-
-// rlg_mlp_dw_launch with the product form of THIS launch: 0 exact f32, 1 bf16 planes, 2 fp16 planes (needs the maxima of
-// rlg_mlp_dw_gradient_maxima), -1 the library's choice
-int rlg_mlp_dw_launch_form(int form, int num_layers, const float* const* dz, const float* const* x, float* const* partial,
-                           float* const* grad, const int* out_features, const int* in_features,
-                           const int* plans4, int rows, int num_colsums, const double* const* colsum_partials,
-                           const int* colsum_blocks, const int* colsum_cols, float* const* colsum_out,
-                           const rlg_loss_finalize_desc* loss_finalize, double* norm_partials, float grad_scale,
-                           long long* step_counter, int* finalize_blocks_out, void* stream) {
-  return dw_launch_impl(form, num_layers, dz, x, partial, grad, out_features, in_features, plans4, rows, num_colsums,
-                        colsum_partials, colsum_blocks, colsum_cols, colsum_out, loss_finalize, norm_partials, grad_scale,
-                        step_counter, finalize_blocks_out, stream);
-}
+// rlg_mlp_dw_launch with the product form of THIS launch: 0 exact f32, 1 bf16 planes, 2 fp16 planes (needs the descriptor's
+// maxima), -1 the library's choice
+int rlg_mlp_dw_launch_form(int form, const rlg_mlp_dw_desc* desc, void* stream) { return dw_launch_impl(form, desc, stream); }
 
 }  // extern "C"

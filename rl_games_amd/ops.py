@@ -921,31 +921,20 @@ def chain_split_form():
     return int(_lib.load().rlg_mlp_chain_split_products()), 'fp16'
 
 
-def _time_chain_launch(kind):
-    if chain_timers is None or torch.cuda.is_current_stream_capturing():
-        return
-    from .gae import HipEventPair
-    ev = HipEventPair()
-    chain_timers.setdefault(kind, []).append(ev)
-    _lib.check(_lib.load().rlg_mlp_chain_time_next(ev.start, ev.stop), 'rlg_mlp_chain_time_next')
-
-
-def _untime_chain_launch(kind):
-    """The launch that _time_chain_launch(kind) announced did not happen (the entry declined the shape)."""
-    if chain_timers is None or torch.cuda.is_current_stream_capturing():
-        return
-    if chain_timers.get(kind):
+def _chain_call(kind, entry, *descs, rows, stream, groups=0):
+    """Calls a launching chain entry with `descs` and the launch descriptor of (rows, groups).  With chain_timers a dict,
+    outside stream capture, the launch carries a HipEventPair that is appended under `kind`; an entry that declines the
+    shape (hipErrorNotSupported, 801) has launched nothing: the pair is dropped again.  Returns the entry's code."""
+    launch = _lib.ChainLaunch(rows, groups)
+    timed = chain_timers is not None and not torch.cuda.is_current_stream_capturing()
+    if timed:
+        from .gae import HipEventPair
+        ev = HipEventPair()
+        launch.ev_start_or_null, launch.ev_stop_or_null = ev.start, ev.stop
+        chain_timers.setdefault(kind, []).append(ev)
+    err = entry(*[ctypes.byref(d) for d in descs], ctypes.byref(launch), stream)
+    if timed and err == 801:
         chain_timers[kind].pop()
-    _lib.load().rlg_mlp_chain_time_next(None, None)
-
-
-def _timed_chain_call(kind, entry, *args):
-    """Announces the timing of a launch of `kind` and calls the entry.  An entry that declines the shape
-    (hipErrorNotSupported, 801) has launched nothing: the announcement is withdrawn.  Returns the entry's code."""
-    _time_chain_launch(kind)
-    err = entry(*args)
-    if err == 801:
-        _untime_chain_launch(kind)
     return err
 
 
@@ -974,6 +963,7 @@ class MlpChain:
         self._b = P(*[_need(b, F32, 'bias') for _, b, _ in layers])
         self._in, self._out = I(*self.ins), I(*self.outs)
         self._act = I(*[ACT_KINDS[a] for _, _, a in layers])
+        self._net = _lib.ChainNet(n, *[ctypes.addressof(a) for a in (self._w, self._b, self._in, self._out, self._act)])
         lib = _lib.load()
         _lib.check(lib.rlg_mlp_chain_prepare(), 'rlg_mlp_chain_prepare')
         max_groups = {}
@@ -1010,6 +1000,8 @@ class MlpChain:
         # weight-gradient launch that follows it; rows of the last backward that left them
         self._forms_read = {}
         self._grad_maxima = self._maxima_bwd = None
+        self._maxima_rows = ctypes.c_int(0)   # what the last backward / step entry answered: rows per entry, 0: no maxima
+        self._maxima_rows_at = ctypes.addressof(self._maxima_rows)
         self.maxima_rows_per_entry = 64       # 64: left by the 64-row split kernels, 16: by the lean 16-row kernels
         self._products = 'auto'
         self.products = products
@@ -1029,13 +1021,19 @@ class MlpChain:
             self._products = mode
             self._maxima_bwd = None
 
-    def _request_maxima(self, rows, per):
-        """The next backward / step launch leaves one gradient-maxima entry per `per`-row workgroup (64: split, 16: lean)."""
+    def _request_maxima(self, bwd, rows, per):
+        """`bwd` asks its launch for one gradient-maxima entry per `per`-row workgroup (64: split, 16: lean)."""
         need = max(1024, -(-int(rows) // per))
         if self._grad_maxima is None or self._grad_maxima.shape[1] < need:
             self._grad_maxima = torch.zeros(8, need, dtype=F32, device=self.device)
-        self._maxima_bwd = None
-        _lib.load().rlg_mlp_chain_gradient_maxima(self._grad_maxima.data_ptr(), self._grad_maxima.shape[1])
+        bwd.maxima_or_null, bwd.maxima_stride = self._grad_maxima.data_ptr(), self._grad_maxima.shape[1]
+
+    def _maxima_left(self, rows):
+        """Behind a backward / step launch of `rows` rows: whether it left maxima, and for how many rows per entry."""
+        per = self._maxima_rows.value
+        self._maxima_bwd = rows if per else None
+        if per:
+            self.maxima_rows_per_entry = per
 
     def gradient_maxima(self, rows):
         """[8, entries] fp32: row l = per 64-row workgroup the largest |dZ of layer l| of the backward of this step - when
@@ -1155,9 +1153,8 @@ class MlpChain:
         return _lib.load().rlg_mlp_chain_num_blocks(int(rows), self.groups(rows, direction, requested))
 
     def _forward_args(self, x, outs, rms, eps, xn_out, rms_fold):
-        """What every forward entry takes from act_out to rms_count_out, in that order: pointers and row strides of
-        `outs` (per layer the activation output or None, the heads last), x and its row stride, the normaliser state,
-        eps, xn_out, the five rms_fold pointers."""
+        """rlg_chain_fwd without its weight form: pointers and row strides of `outs` (per layer the activation output or
+        None, the heads last), x and its row stride, the normaliser state, eps, xn_out, the five rms_fold pointers."""
         ptrs = self._P(*[None if t is None else _need(t, F32, 'act_out', contiguous=False) for t in outs])
         lds = self._L(*[0 if t is None else t.stride(0) for t in outs])
         _lib.require_gpu(x, 'x')
@@ -1175,17 +1172,31 @@ class MlpChain:
                 raise ValueError('rms_fold: moments row of 2*in0+1 doubles expected')
             fold = [_need(row, F64, 'moments row'), _need(cnt, torch.int64, 'count'), _need(mean_o, F64, 'mean out'),
                     _need(var_o, F64, 'var out'), _need(cnt_o, torch.int64, 'count out')]
-        return (ptrs, lds, x.data_ptr(), x.stride(0), mean, var, float(np.float32(eps)), _opt(xn_out, F32, 'xn_out'), *fold)
+        fwd = _lib.ChainFwd(ctypes.addressof(ptrs), ctypes.addressof(lds), x.data_ptr(), x.stride(0), mean, var,
+                            float(np.float32(eps)), _opt(xn_out, F32, 'xn_out'), *fold)
+        fwd.arrays = ptrs, lds                          # (alive as long as the descriptor)
+        return fwd
 
-    def _backward_args(self, dz_out, bias_partials):
-        """What every backward entry takes from dz_out to bias_partials: per hidden layer the dZ output and its row
-        stride, the fp64 bias partials or None."""
+    def _backward_args(self, d_heads, acts, dz_out, bias_partials, ppo_loss):
+        """rlg_chain_bwd without its weight form and maxima: d_heads, per hidden layer H (acts; None for the step entries,
+        which read their forward half's), the dZ output and their row strides, the fp64 bias partials or None, the loss
+        descriptor or None.  The entry's answer about maxima goes to _maxima_rows."""
+        h = hl = None
+        if acts is not None:
+            h = self._P(*([_need(t, F32, 'H', contiguous=False) for t in acts] + [None]))
+            hl = self._L(*([t.stride(0) for t in acts] + [0]))
         dz = self._P(*([_need(t, F32, 'dz', contiguous=False) for t in dz_out] + [None]))
         dl = self._L(*([t.stride(0) for t in dz_out] + [0]))
         bp = None
         if bias_partials is not None:
             bp = self._P(*([_need(t, F64, 'bias partials') for t in bias_partials] + [None]))
-        return dz, dl, bp
+        at = ctypes.addressof
+        bwd = _lib.ChainBwd(None if h is None else at(h), None if h is None else at(hl),
+                            _need(d_heads, F32, 'd_heads', contiguous=False), d_heads.stride(0), at(dz), at(dl),
+                            None if bp is None else at(bp), None if ppo_loss is None else at(ppo_loss), None, None, 0,
+                            self._maxima_rows_at)
+        bwd.arrays = h, hl, dz, dl, bp                  # (alive as long as the descriptor)
+        return bwd
 
     def forward(self, x, heads, act_out=None, rms=None, eps=1e-5, xn_out=None, groups=0, rms_fold=None,
                 split_products=None):
@@ -1206,10 +1217,11 @@ class MlpChain:
         route = self._route(rows, kind, groups, split_products)
         token = self.weights_token()
         self.planes.drop_fresh()
+        timer = 'fwd_train' if act_out is not None else 'fwd_infer'
         if route == 'lean':
             self.frags.ensure(token, x)
-            err = _timed_chain_call('fwd_train' if act_out is not None else 'fwd_infer', _lib.load().rlg_mlp_chain_forward_lean,
-                                    n, self._b, self._in, self._out, self._act, *fwd, rows, self._frags_ptr(0), _stream(x))
+            fwd.weight_form_or_null = self._frags_ptr(0)
+            err = _chain_call(timer, _lib.load().rlg_mlp_chain_forward_lean, self._net, fwd, rows=rows, stream=_stream(x))
             if err != 801:                              # (hipErrorNotSupported: the pipelined / unit-structured launch)
                 _lib.check(err, 'rlg_mlp_chain_forward_lean')
                 return
@@ -1223,10 +1235,9 @@ class MlpChain:
             fwd_planes = self._planes_ptr(0)
         elif bwd_split and not self.planes.current(token):
             planes = self._planes_ptr(1)
-        _time_chain_launch('fwd_train' if act_out is not None else 'fwd_infer')
-        _lib.check(_lib.load().rlg_mlp_chain_forward(
-            n, self._w, self._b, self._in, self._out, self._act, *fwd, rows,
-            self.groups(rows, kind, groups), planes, fwd_planes, _stream(x)), 'rlg_mlp_chain_forward')
+        fwd.weight_form_or_null, fwd.pack_backward_planes_or_null = fwd_planes, planes
+        _lib.check(_chain_call(timer, _lib.load().rlg_mlp_chain_forward, self._net, fwd, rows=rows, stream=_stream(x),
+                               groups=self.groups(rows, kind, groups)), 'rlg_mlp_chain_forward')
         if bwd_split:                                   # (behind a launch that succeeded, for the weights as they are)
             self.planes.fresh = (rows, token)
 
@@ -1244,23 +1255,20 @@ class MlpChain:
             return False
         lean = routes == ('lean', 'lean')
         fwd = self._forward_args(x, list(act_out) + [heads], rms, eps, xn_out, rms_fold)
-        bwd = (_need(d_heads, F32, 'd_heads', contiguous=False), d_heads.stride(0), *self._backward_args(dz_out, bias_partials),
-               ctypes.addressof(ppo_loss), rows)
+        bwd = self._backward_args(d_heads, None, dz_out, bias_partials, ppo_loss)
         if lean:
             # (outside the lean step's envelope the caller's two lean launches beat the pipelined one-launch step)
             self.frags.ensure(self.weights_token(), x)
-            self._request_maxima(rows, 16)
-            err = _timed_chain_call('step16', _lib.load().rlg_mlp_chain_step_lean, n, self._b, self._in, self._out, self._act,
-                                    *fwd, *bwd, self._frags_ptr(0), self._frags_ptr(1), _stream(x))
-        else:
-            err = _timed_chain_call('step16', _lib.load().rlg_mlp_chain_step, n, self._w, self._b, self._in, self._out,
-                                    self._act, *fwd, *bwd, _stream(x))
+            fwd.weight_form_or_null, bwd.weight_form_or_null = self._frags_ptr(0), self._frags_ptr(1)
+            self._request_maxima(bwd, rows, 16)
+        entry = 'rlg_mlp_chain_step_lean' if lean else 'rlg_mlp_chain_step'
+        self._maxima_bwd = None
+        err = _chain_call('step16', getattr(_lib.load(), entry), self._net, fwd, bwd, rows=rows, stream=_stream(x))
         if err == 801:                                  # hipErrorNotSupported: outside the fused kernel's envelope
             return False
-        _lib.check(err, 'rlg_mlp_chain_step_lean' if lean else 'rlg_mlp_chain_step')
+        _lib.check(err, entry)
         self.planes.drop_fresh()
-        if lean:
-            self._maxima_bwd, self.maxima_rows_per_entry = rows, 16
+        self._maxima_left(rows)
         return True
 
     def backward(self, d_heads, acts, dz_out, bias_partials=None, groups=0, ppo_loss=None, split_products=None):
@@ -1270,42 +1278,33 @@ class MlpChain:
         it produces d_heads itself (and the loss partials, the mu/sigma write-back).
         split_products: None = the library's choice (_route), False = exact f32 products."""
         rows = d_heads.shape[0]
-        n = self.n
-        h = self._P(*([_need(t, F32, 'H', contiguous=False) for t in acts] + [None]))
-        hl = self._L(*([t.stride(0) for t in acts] + [0]))
-        dz, dl, bp = self._backward_args(dz_out, bias_partials)
-        _lib.require_gpu(d_heads, 'd_heads')
+        bwd = self._backward_args(d_heads, acts, dz_out, bias_partials, ppo_loss)
         route = self._route(rows, 1, groups, split_products)
         token = self.weights_token()
         fresh = self.planes.take_fresh(rows, token)             # (packed with the forward launch of this step)
+        timer = 'bwd_loss' if ppo_loss is not None else 'bwd'
+        self._maxima_bwd = None
         if route == 'lean':
             self.frags.ensure(token, d_heads)
-            self._request_maxima(rows, 16)
-            err = _timed_chain_call(
-                'bwd_loss' if ppo_loss is not None else 'bwd', _lib.load().rlg_mlp_chain_backward_lean,
-                n, self._in, self._out, self._act, h, hl, d_heads.data_ptr(), d_heads.stride(0), dz, dl, bp,
-                None if ppo_loss is None else ctypes.addressof(ppo_loss), rows, self._frags_ptr(1), _stream(d_heads))
+            bwd.weight_form_or_null = self._frags_ptr(1)
+            self._request_maxima(bwd, rows, 16)
+            err = _chain_call(timer, _lib.load().rlg_mlp_chain_backward_lean, self._net, bwd, rows=rows,
+                              stream=_stream(d_heads))
             if err != 801:
                 _lib.check(err, 'rlg_mlp_chain_backward_lean')
-                self._maxima_bwd, self.maxima_rows_per_entry = rows, 16
+                self._maxima_left(rows)
                 return
-        planes = None
+        bwd.weight_form_or_null = bwd.maxima_or_null = None
         if route == 'split':
             if not self.planes.current(token) and not fresh:
                 self.planes.pack(d_heads, 1)
-            planes = self._planes_ptr(1)
-        # the split-fp16 launch leaves the gradient maxima the weight-gradient launch scales by - claimed only where the
-        # library is sure to take that launch (chain_bx_bwd_eligible: 16-byte aligned H / dZ rows of 4-float groups)
-        self._maxima_bwd = None
-        if planes is not None and all(
-                t.data_ptr() % 16 == 0 and t.stride(0) % 4 == 0 and t.shape[1] % 4 == 0 for t in list(acts) + list(dz_out)):
-            self._request_maxima(rows, 64)
-            self._maxima_bwd, self.maxima_rows_per_entry = rows, 64
-        _time_chain_launch('bwd_loss' if ppo_loss is not None else 'bwd')
-        _lib.check(_lib.load().rlg_mlp_chain_backward(
-            n, self._w, self._in, self._out, self._act, h, hl, d_heads.data_ptr(), d_heads.stride(0), dz, dl,
-            bp, None if ppo_loss is None else ctypes.addressof(ppo_loss), rows, self.groups(rows, 1, groups),
-            planes, _stream(d_heads)), 'rlg_mlp_chain_backward')
+            bwd.weight_form_or_null = self._planes_ptr(1)
+            # the split-fp16 launch leaves the gradient maxima the weight-gradient launch scales by; whether it ran is
+            # the library's answer
+            self._request_maxima(bwd, rows, 64)
+        _lib.check(_chain_call(timer, _lib.load().rlg_mlp_chain_backward, self._net, bwd, rows=rows, stream=_stream(d_heads),
+                               groups=self.groups(rows, 1, groups)), 'rlg_mlp_chain_backward')
+        self._maxima_left(rows)
 
 
 # ------------------------------------------------------------------ MLP weight gradients (MFMA)
@@ -1340,6 +1339,8 @@ class MlpDwPlan:
         self._ws = P(*[w.data_ptr() for w in self.workspaces])
         self._no = (ctypes.c_int * n)(*[s[0] for s in self.shapes])
         self._mi = (ctypes.c_int * n)(*[s[1] for s in self.shapes])
+        # rlg_mlp_dw_desc from dz to plans4: the arrays live with the plan
+        self._arrays = [ctypes.addressof(a) for a in (self._dz, self._x, self._ws, self._grad, self._no, self._mi, self._plans)]
         self._device = device
 
     def plan(self, k):
@@ -1375,14 +1376,11 @@ class MlpDwPlan:
         if len(jobs) != self.n:
             raise ValueError('job count does not match the plan')
         nc = len(colsums)
-        if nc:
+        cs = ()
+        if nc:                              # rlg_mlp_dw_desc's colsum_partials, colsum_blocks, colsum_cols, colsum_out
             P = ctypes.c_void_p * nc
-            cs_part = P(*[_need(c[0], F64, 'colsum partials') for c in colsums])
-            cs_out = P(*[_need(c[3], F32, 'colsum out') for c in colsums])
-            cs_blocks = (ctypes.c_int * nc)(*[int(c[1]) for c in colsums])
-            cs_cols = (ctypes.c_int * nc)(*[int(c[2]) for c in colsums])
-        else:
-            cs_part = cs_out = cs_blocks = cs_cols = None
+            cs = (P(*[_need(c[0], F64, 'colsum partials') for c in colsums]), (ctypes.c_int * nc)(*[int(c[1]) for c in colsums]),
+                  (ctypes.c_int * nc)(*[int(c[2]) for c in colsums]), P(*[_need(c[3], F32, 'colsum out') for c in colsums]))
         nfin = ctypes.c_int(0)
         if norm is not None:
             need = self.finalize_blocks(colsums, loss_finalize)
@@ -1397,25 +1395,27 @@ class MlpDwPlan:
             self._dz[k] = _need(dz, F32, 'dz')
             self._x[k] = _need(x, F32, 'x')
             self._grad[k] = _need(grad, F32, 'grad')
+        desc = _lib.MlpDwDesc(
+            self.n, self.rows, *self._arrays, nc, *([ctypes.addressof(a) for a in cs] or [None] * 4),
+            None if loss_finalize is None else ctypes.addressof(loss_finalize),
+            None if norm is None else _need(norm[0], F64, 'norm partials'),
+            1.0 if norm is None else float(np.float32(norm[1])),
+            None if norm is None else _need(norm[2], torch.int64, 'step_counter'), ctypes.addressof(nfin))
         if maxima is not None:
             entries, dzs, xscales = maxima[:3]
-            per = int(maxima[3]) if len(maxima) > 3 else 64           # rows one entry covers: 64, or 16 (the lean kernels)
             if len(dzs) != self.n or len(xscales) != self.n or entries.dim() != 2 or entries.shape[0] != 8:
                 raise ValueError('maxima: [8, entries] fp32, one dz layer and one x scale per job')
-            _lib.check(_lib.load().rlg_mlp_dw_gradient_maxima(
-                _need(entries, F32, 'gradient maxima'), int(entries.shape[1]), per, (ctypes.c_int * self.n)(*[int(v) for v in dzs]),
-                (ctypes.c_float * self.n)(*[float(v) for v in xscales]), self.n), 'rlg_mlp_dw_gradient_maxima')
-        args = (self.n, self._dz, self._x, self._ws, self._grad, self._no,
-                self._mi, self._plans, self.rows, nc, cs_part, cs_blocks, cs_cols, cs_out,
-                None if loss_finalize is None else ctypes.addressof(loss_finalize),
-                None if norm is None else _need(norm[0], F64, 'norm partials'),
-                1.0 if norm is None else float(np.float32(norm[1])),
-                None if norm is None else _need(norm[2], torch.int64, 'step_counter'),
-                ctypes.byref(nfin), _lib.stream_handle(self._device))
+            desc.maxima_or_null, desc.maxima_stride = _need(entries, F32, 'gradient maxima'), int(entries.shape[1])
+            desc.maxima_rows_per_entry = int(maxima[3]) if len(maxima) > 3 else 64   # 64, or 16 (the lean kernels)
+            slots = (ctypes.c_int * self.n)(*[int(v) for v in dzs])
+            scales = (ctypes.c_float * self.n)(*[float(v) for v in xscales])
+            desc.dz_slot, desc.x_scale = ctypes.addressof(slots), ctypes.addressof(scales)
+        stream = _lib.stream_handle(self._device)
         if self.FORMS[form] < 0:
-            _lib.check(_lib.load().rlg_mlp_dw_launch(*args), 'rlg_mlp_dw_launch')
+            _lib.check(_lib.load().rlg_mlp_dw_launch(ctypes.byref(desc), stream), 'rlg_mlp_dw_launch')
         else:
-            _lib.check(_lib.load().rlg_mlp_dw_launch_form(self.FORMS[form], *args), 'rlg_mlp_dw_launch_form')
+            _lib.check(_lib.load().rlg_mlp_dw_launch_form(self.FORMS[form], ctypes.byref(desc), stream),
+                       'rlg_mlp_dw_launch_form')
         return nfin.value
 
 

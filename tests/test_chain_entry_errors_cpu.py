@@ -11,7 +11,9 @@ The table runs in a child process that sees no GPU: should a row ever get past v
 instead of handing fake addresses to a device.  `python tests/test_chain_entry_errors_cpu.py` prints the codes of the
 library that RLG_HIP_LIB selects (one JSON object), which is how two builds are compared.
 
-The expected values are the answers of the library before the entry points shared their argument setup.
+The expected values are the answers of the library before the entry points shared their argument setup, and before
+their arguments travelled as descriptors (rlg_chain_net / _fwd / _bwd / _launch of include/rlg_hip.h): the rows name
+descriptor fields.  What a backward call answers to gradient maxima depends on that call's descriptor alone.
 
 The two stand-alone loss entries take the same kind of descriptor (rlg_ppo_loss_fused the chain's own) and are asked
 beside them, in the same child: no descriptor, and what rlg_ppo_loss_fused itself rejects.
@@ -76,73 +78,69 @@ def _wide():
     return _shape(ins=(24, 64, 20480), outs=(64, 20480, 5))
 
 
-def _forward_side():
-    return dict(biases=_ptrs(20), act_out=_ptrs(40), act_ld=_lls(OUT), x=_addr(60), ldx=IN[0],
-                rms_mean=None, rms_var=None, rms_eps=1e-5, xn_out=None, rms_batch=None, rms_count=None,
-                rms_mean_out=None, rms_var_out=None, rms_count_out=None)
-
-
-def _backward_side():
-    return dict(d_out=_addr(80), ld_dout=OUT[-1], dz_out=_ptrs(100), dz_ld=_lls(OUT), bias_partials=None)
-
-
 # the fold of the normaliser state must publish into a second buffer set
-_RMS = dict(rms_mean=_addr(300), rms_var=_addr(301), rms_batch=_addr(302), rms_count=_addr(303),
+_RMS = dict(rms_mean_or_null=_addr(300), rms_var=_addr(301), rms_batch_or_null=_addr(302), rms_count=_addr(303),
             rms_mean_out=_addr(304), rms_var_out=_addr(305), rms_count_out=_addr(306))
 
-# argument order of each entry (include/rlg_hip.h) and a well-formed call of it - which is never made as it stands
-_ENTRIES = {
-    'forward': (
-        'num_layers weights biases in_features out_features acts act_out act_ld x ldx rms_mean rms_var rms_eps xn_out '
-        'rms_batch rms_count rms_mean_out rms_var_out rms_count_out rows groups pack_planes weight_planes stream',
-        lambda: dict(_shape(), weights=_ptrs(0), **_forward_side(), rows=ROWS, groups=0, pack_planes=None,
-                     weight_planes=None, stream=None)),
-    'backward': (
-        'num_layers weights in_features out_features acts act_in act_ld d_out ld_dout dz_out dz_ld bias_partials '
-        'ppo_loss rows groups weight_planes stream',
-        lambda: dict(_shape(), weights=_ptrs(0), act_in=_ptrs(40), act_ld=_lls(OUT), **_backward_side(), ppo_loss=None,
-                     rows=ROWS, groups=0, weight_planes=None, stream=None)),
-    'step': (
-        'num_layers weights biases in_features out_features acts act_out act_ld x ldx rms_mean rms_var rms_eps xn_out '
-        'rms_batch rms_count rms_mean_out rms_var_out rms_count_out d_out ld_dout dz_out dz_ld bias_partials ppo_loss '
-        'rows stream',
-        lambda: dict(_shape(), weights=_ptrs(0), **_forward_side(), **_backward_side(), ppo_loss=_desc(), rows=ROWS,
-                     stream=None)),
-    'forward_lean': (
-        'num_layers biases in_features out_features acts act_out act_ld x ldx rms_mean rms_var rms_eps xn_out '
-        'rms_batch rms_count rms_mean_out rms_var_out rms_count_out rows frags stream',
-        lambda: dict(_shape(), **_forward_side(), rows=ROWS, frags=_addr(400), stream=None)),
-    'backward_lean': (
-        'num_layers in_features out_features acts act_in act_ld d_out ld_dout dz_out dz_ld bias_partials ppo_loss '
-        'rows frags stream',
-        lambda: dict(_shape(), act_in=_ptrs(40), act_ld=_lls(OUT), **_backward_side(), ppo_loss=None, rows=ROWS,
-                     frags=_addr(401), stream=None)),
-    'step_lean': (
-        'num_layers biases in_features out_features acts act_out act_ld x ldx rms_mean rms_var rms_eps xn_out '
-        'rms_batch rms_count rms_mean_out rms_var_out rms_count_out d_out ld_dout dz_out dz_ld bias_partials ppo_loss '
-        'rows frags_fwd frags_bwd stream',
-        lambda: dict(_shape(), **_forward_side(), **_backward_side(), ppo_loss=_desc(), rows=ROWS, frags_fwd=_addr(400),
-                     frags_bwd=_addr(401), stream=None)),
-}
+# the descriptors each entry takes, in argument order (include/rlg_hip.h), in front of the stream
+_ENTRIES = {'forward': ('net', 'fwd', 'launch'), 'backward': ('net', 'bwd', 'launch'),
+            'step': ('net', 'fwd', 'bwd', 'launch'), 'forward_lean': ('net', 'fwd', 'launch'),
+            'backward_lean': ('net', 'bwd', 'launch'), 'step_lean': ('net', 'fwd', 'bwd', 'launch')}
+
+
+def _well_formed(entry):
+    """{descriptor: {field: value}} of a well-formed call of `entry` - which is never made as it stands"""
+    lean, step = entry.endswith('_lean'), entry.startswith('step')
+    d = dict(net=dict(_shape(), weights=None if lean else _ptrs(0), biases=None if 'backward' in entry else _ptrs(20)),
+             launch=dict(rows=ROWS, groups=0))
+    if 'fwd' in _ENTRIES[entry]:
+        d['fwd'] = dict(act_out=_ptrs(40), act_ld=_lls(OUT), x=_addr(60), ldx=IN[0], rms_eps=1e-5,
+                        weight_form_or_null=_addr(400) if lean else None)
+    if 'bwd' in _ENTRIES[entry]:
+        d['bwd'] = dict(act_in=None if step else _ptrs(40), act_ld=None if step else _lls(OUT), d_out=_addr(80),
+                        ld_dout=OUT[-1], dz_out=_ptrs(100), dz_ld=_lls(OUT), ppo_loss_or_null=_desc() if step else None,
+                        weight_form_or_null=_addr(401) if lean else None)
+    return d
 
 
 _LOSS_ENTRIES = ('ppo_loss_fused', 'ppo_loss_finalize')      # (descriptor, stream)
 
 
 def _call(lib, entry, **over):
+    """Overrides are descriptor fields (fwd_<field> / bwd_<field> where an entry has the field in both halves), or a
+    descriptor's own name with None: that descriptor is passed as NULL."""
     if entry in _LOSS_ENTRIES:
         desc = over['desc']
         return getattr(lib, 'rlg_' + entry)(None if desc is None else ctypes.byref(desc), None)
-    order, base = _ENTRIES[entry]
-    kw = base()
-    unknown = set(over) - set(kw)
-    assert not unknown, (entry, unknown)
-    kw.update(over)
-    args = []
-    for name in order.split():
-        v = kw[name]
-        args.append(ctypes.byref(v) if name == 'ppo_loss' and v is not None else v)
-    return getattr(lib, 'rlg_mlp_chain_' + entry)(*args)
+    from rl_games_amd import _lib
+    classes = dict(net=_lib.ChainNet, fwd=_lib.ChainFwd, bwd=_lib.ChainBwd, launch=_lib.ChainLaunch)
+    fields = _well_formed(entry)
+    for key, v in over.items():
+        if key in fields:
+            assert v is None, key
+            fields[key] = None
+            continue
+        side, _, name = key.partition('_')
+        if side in ('fwd', 'bwd') and side in fields and name in dict(classes[side]._fields_):
+            hit = [(side, name)]
+        else:
+            hit = [(d, key) for d in _ENTRIES[entry] if key in dict(classes[d]._fields_)]
+        assert len(hit) == 1, (entry, key, hit)
+        fields[hit[0][0]][hit[0][1]] = v
+    keep, args = [], []
+    for d in _ENTRIES[entry]:
+        if fields[d] is None:
+            args.append(None)
+            continue
+        desc = classes[d]()
+        for name, v in fields[d].items():
+            if isinstance(v, (ctypes.Array, ctypes.Structure)):      # (arrays, the loss descriptor: by address)
+                keep.append(v)
+                v = ctypes.addressof(v)
+            setattr(desc, name, v)
+        keep.append(desc)
+        args.append(ctypes.byref(desc))
+    return getattr(lib, 'rlg_mlp_chain_' + entry)(*args, None)
 
 
 _BIG_LOSS = dict(actions_num=2000)        # a loss tile beyond the LDS of every backward kernel
@@ -150,7 +148,7 @@ _H_ODD_LD = dict(act_ld=_lls((63, 64, 5)))      # layer 0: rows of H that are no
 
 
 def _rows():
-    """(id, expected code, entry, overrides); a row whose entry is a tuple runs a sequence and answers its last code."""
+    """(id, expected code, entry, overrides); a row whose entry is a tuple runs a sequence and expects a list of codes."""
     t = []
 
     def row(name, expected, entry, **over):
@@ -174,13 +172,13 @@ def _rows():
     # ---- forward side
     for e in ('forward', 'forward_lean'):
         row(f'{e}: no output array of the last layer', INVALID, e, act_out=_ptrs(40, null=(2,)))
-        row(f'{e}: normaliser fold into the buffers it reads', INVALID, e, **dict(_RMS, rms_mean_out=_RMS['rms_mean']))
+        row(f'{e}: normaliser fold into the buffers it reads', INVALID, e, **dict(_RMS, rms_mean_out=_RMS['rms_mean_or_null']))
         row(f'{e}: normaliser fold into the count it reads', INVALID, e, **dict(_RMS, rms_count_out=_RMS['rms_count']))
         row(f'{e}: normaliser fold without a count', INVALID, e, **dict(_RMS, rms_count=None))
-    row('forward_lean: no fragments', INVALID, 'forward_lean', frags=None)
-    row('forward_lean: fragments that are not 4-byte aligned', INVALID, 'forward_lean', frags=_addr(400) + 2)
+    row('forward_lean: no fragments', INVALID, 'forward_lean', weight_form_or_null=None)
+    row('forward_lean: fragments that are not 4-byte aligned', INVALID, 'forward_lean', weight_form_or_null=_addr(400) + 2)
     row('forward_lean: a bias vector that is not 4-byte aligned', INVALID, 'forward_lean', biases=_ptrs(20, offset={1: 2}))
-    row('forward_lean: no fragments AND outside the fragment format', INVALID, 'forward_lean', frags=None,
+    row('forward_lean: no fragments AND outside the fragment format', INVALID, 'forward_lean', weight_form_or_null=None,
         **_wide())
     row('forward_lean: outside the fragment format AND no output array of the last layer', NOT_SUPPORTED, 'forward_lean',
         act_out=_ptrs(40, null=(2,)), **_wide())
@@ -188,15 +186,15 @@ def _rows():
     for e in ('backward', 'backward_lean'):
         row(f'{e}: no dZ array of a hidden layer', INVALID, e, dz_out=_ptrs(100, null=(1,)))
         row(f'{e}: no H array of a hidden layer', INVALID, e, act_in=_ptrs(40, null=(0,)))
-        row(f'{e}: descriptor of another minibatch size', INVALID, e, ppo_loss=_desc(minibatch=ROWS + 1))
-        row(f'{e}: descriptor without actions', INVALID, e, ppo_loss=_desc(actions_num=0))
-        row(f'{e}: descriptor with a mask and no mask sum', INVALID, e, ppo_loss=_desc(mask_or_null=_addr(250)))
-        row(f'{e}: descriptor without partials', INVALID, e, ppo_loss=_desc(partials=None))
-        row(f'{e}: descriptor without d_mu', INVALID, e, ppo_loss=_desc(d_mu=None))
-    row('backward: a loss tile beyond LDS', INVALID, 'backward', ppo_loss=_desc(**_BIG_LOSS))
-    row('backward_lean: a loss tile beyond LDS', NOT_SUPPORTED, 'backward_lean', ppo_loss=_desc(**_BIG_LOSS))
-    row('backward_lean: no fragments', INVALID, 'backward_lean', frags=None)
-    row('backward_lean: fragments that are not 4-byte aligned', INVALID, 'backward_lean', frags=_addr(401) + 2)
+        row(f'{e}: descriptor of another minibatch size', INVALID, e, ppo_loss_or_null=_desc(minibatch=ROWS + 1))
+        row(f'{e}: descriptor without actions', INVALID, e, ppo_loss_or_null=_desc(actions_num=0))
+        row(f'{e}: descriptor with a mask and no mask sum', INVALID, e, ppo_loss_or_null=_desc(mask_or_null=_addr(250)))
+        row(f'{e}: descriptor without partials', INVALID, e, ppo_loss_or_null=_desc(partials=None))
+        row(f'{e}: descriptor without d_mu', INVALID, e, ppo_loss_or_null=_desc(d_mu=None))
+    row('backward: a loss tile beyond LDS', INVALID, 'backward', ppo_loss_or_null=_desc(**_BIG_LOSS))
+    row('backward_lean: a loss tile beyond LDS', NOT_SUPPORTED, 'backward_lean', ppo_loss_or_null=_desc(**_BIG_LOSS))
+    row('backward_lean: no fragments', INVALID, 'backward_lean', weight_form_or_null=None)
+    row('backward_lean: fragments that are not 4-byte aligned', INVALID, 'backward_lean', weight_form_or_null=_addr(401) + 2)
     row('backward_lean: row stride of H not a multiple of 4', NOT_SUPPORTED, 'backward_lean', **_H_ODD_LD)
     row('backward_lean: row stride of dZ not a multiple of 4', NOT_SUPPORTED, 'backward_lean', dz_ld=_lls((64, 66, 5)))
     row('backward_lean: H not 16-byte aligned', NOT_SUPPORTED, 'backward_lean', act_in=_ptrs(40, offset={1: 4}))
@@ -210,17 +208,17 @@ def _rows():
     row('backward_lean: no dZ of layer 0 AND layer 1 rows not 16-byte', INVALID, 'backward_lean',
         dz_out=_ptrs(100, null=(0,)), act_ld=_lls((64, 63, 5)))
     row('backward_lean: rows not 16-byte AND a bad descriptor', NOT_SUPPORTED, 'backward_lean',
-        ppo_loss=_desc(actions_num=0), **_H_ODD_LD)
+        ppo_loss_or_null=_desc(actions_num=0), **_H_ODD_LD)
     row('backward_lean: outside the fragment format AND no dZ', NOT_SUPPORTED, 'backward_lean',
         dz_out=_ptrs(100, null=(0,)), **_wide())
     # ---- the one-launch steps, up to their device query
     for e in ('step', 'step_lean'):
         row(f'{e}: no layers', NOT_SUPPORTED, e, num_layers=0)
         row(f'{e}: one layer', NOT_SUPPORTED, e, num_layers=1)
-        row(f'{e}: no descriptor', NOT_SUPPORTED, e, ppo_loss=None)
-    row('step: a minibatch of the 64-row kernels', NOT_SUPPORTED, 'step', rows=16384, ppo_loss=_desc(minibatch=16384))
-    row('step_lean: no forward fragments', NOT_SUPPORTED, 'step_lean', frags_fwd=None)
-    row('step_lean: no backward fragments', NOT_SUPPORTED, 'step_lean', frags_bwd=None)
+        row(f'{e}: no descriptor', NOT_SUPPORTED, e, ppo_loss_or_null=None)
+    row('step: a minibatch of the 64-row kernels', NOT_SUPPORTED, 'step', rows=16384, ppo_loss_or_null=_desc(minibatch=16384))
+    row('step_lean: no forward fragments', NOT_SUPPORTED, 'step_lean', fwd_weight_form_or_null=None)
+    row('step_lean: no backward fragments', NOT_SUPPORTED, 'step_lean', bwd_weight_form_or_null=None)
     # ---- the stand-alone loss launches
     for e in _LOSS_ENTRIES:
         row(f'{e}: NULL descriptor', INVALID, e, desc=None)
@@ -229,29 +227,30 @@ def _rows():
     row('ppo_loss_fused: descriptor with a mask and no mask sum', INVALID, 'ppo_loss_fused',
         desc=_desc(mask_or_null=_addr(250)))
     row('ppo_loss_fused: a loss tile beyond LDS', INVALID, 'ppo_loss_fused', desc=_desc(**_BIG_LOSS))
-    # ---- the one-shot request for gradient maxima (rlg_mlp_chain_gradient_maxima): rlg_mlp_chain_backward takes it at
-    # its very top, the lean backward late - a request that a declined lean call left pending is still there for the next
-    # call, and rlg_mlp_chain_backward clears it whatever else it does.  A taken request with too few entries per
-    # tensor (stride 1 for 4 workgroups) is hipErrorInvalidValue, in front of the LDS check that answers 801.
-    big = dict(ppo_loss=_desc(**_BIG_LOSS))
-    want = ('gradient_maxima', dict(stride=1))
-    t.append(('maxima: taken by the lean backward, too few entries', INVALID,
-              (want, ('backward_lean', big)), None))
-    t.append(('maxima: taken means cleared', NOT_SUPPORTED,
-              (want, ('backward_lean', big), ('backward_lean', big)), None))
-    t.append(('maxima: a lean call declined for its rows leaves the request pending', INVALID,
-              (want, ('backward_lean', _H_ODD_LD), ('backward_lean', big)), None))
-    t.append(('maxima: a lean call declined for its descriptor leaves the request pending', INVALID,
-              (want, ('backward_lean', dict(ppo_loss=_desc(actions_num=0))), ('backward_lean', big)), None))
-    t.append(('maxima: rlg_mlp_chain_backward clears the request before its rows check', NOT_SUPPORTED,
-              (want, ('backward', dict(rows=0)), ('backward_lean', big)), None))
-    t.append(('maxima: rlg_mlp_chain_backward clears the request before it validates', NOT_SUPPORTED,
-              (want, ('backward', dict(num_layers=1)), ('backward_lean', big)), None))
+    # ---- a NULL descriptor: answered first, in front of the early return for no rows
+    for e, descs in _ENTRIES.items():
+        for d in descs:
+            row(f'{e}: NULL {d} descriptor', INVALID, e, **({d: None} if d == 'launch' else {d: None, 'rows': 0}))
+    # ---- gradient maxima are asked for in the call's own backward descriptor.  The lean backward looks at them behind
+    # its rows check and its loss descriptor: too few entries per tensor (stride 1 for 4 workgroups) is
+    # hipErrorInvalidValue, in front of the LDS check that answers 801.
+    big = dict(ppo_loss_or_null=_desc(**_BIG_LOSS))
+    short = dict(maxima_or_null=_addr(500), maxima_stride=1)
+    row('backward_lean: maxima with too few entries AND a loss tile beyond LDS', INVALID, 'backward_lean', **big, **short)
+    row('backward_lean: the same call without maxima', NOT_SUPPORTED, 'backward_lean', **big)
+    row('backward_lean: maxima with too few entries AND rows not 16-byte', NOT_SUPPORTED, 'backward_lean', **_H_ODD_LD,
+        **short)
+    row('backward_lean: maxima with too few entries AND a bad descriptor', INVALID, 'backward_lean',
+        ppo_loss_or_null=_desc(actions_num=0), **short)
+    # nothing is carried from call to call: each call of a sequence gets the code of its own descriptor
+    t.append(('backward_lean: with short maxima, without, with again', [INVALID, NOT_SUPPORTED, INVALID],
+              (('backward_lean', dict(big, **short)), ('backward_lean', big), ('backward_lean', dict(big, **short))), None))
     return t
 
 
 def run_table():
-    """{row id: code} of the library that rl_games_amd._lib selects"""
+    """{row id: code} of the library that rl_games_amd._lib selects; a row whose entry is a tuple runs a sequence of calls
+    and answers the list of their codes"""
     sys.path.insert(0, ROOT)
     from rl_games_amd import _lib
     lib = _lib.load()
@@ -260,14 +259,8 @@ def run_table():
         assert name not in codes, name
         if isinstance(entry, str):
             codes[name] = _call(lib, entry, **over)
-            continue
-        lib.rlg_mlp_chain_gradient_maxima(None, 0)           # (no request pending from the row before)
-        for step_entry, step_over in entry:
-            if step_entry == 'gradient_maxima':
-                code = lib.rlg_mlp_chain_gradient_maxima(_addr(500), step_over['stride'])
-            else:
-                code = _call(lib, step_entry, **step_over)
-        codes[name] = code
+        else:
+            codes[name] = [_call(lib, step_entry, **step_over) for step_entry, step_over in entry]
     return codes
 
 

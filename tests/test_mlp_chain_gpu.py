@@ -1140,6 +1140,45 @@ def test_dw_fp16_form_with_per_wave_gradient_scales_matches_fp64(rows, per):
         assert e16.pow(2).mean().sqrt() <= 1.5 * eb.pow(2).mean().sqrt() + 1e-10
 
 
+@pytest.mark.parametrize('rows,dz_offset,per', [(8192, 0, 64), (8192, 1, 0), (64, 0, 16)])
+def test_gradient_maxima_are_what_the_backward_launch_says_it_left(rows, dz_offset, per):
+    """gradient_maxima(rows) is the answer of the backward launch itself (maxima_rows_out of rlg_chain_bwd), not a guess
+    at the library's engine choice.  A [24 - 64 - 64 - 5] chain: at 8,192 rows (the smallest minibatch of the 64-row
+    split backward) with aligned buffers the split kernel leaves an entry per 64 rows; with one dZ output that starts
+    4 bytes into its allocation the library takes the exact-product kernel, which leaves none - and the weight-gradient
+    launch of that step, given what the chain answers, is the bf16 form bit for bit; at 64 rows the lean backward leaves
+    an entry per 16 rows."""
+    from rl_games_amd import ops
+    layers, g = _net(24, [64, 64], 5, 'elu', seed=47)
+    chain = ops.MlpChain(layers, DEV)
+    assert chain.split_products(rows, 1) == (rows == 8192) and chain.lean_used(rows, 1) == (rows == 64)
+    x = torch.randn(rows, 24, generator=g).to(DEV)
+    heads = torch.empty(rows, 5, device=DEV)
+    acts = [torch.empty(rows, 64, device=DEV), torch.empty(rows, 64, device=DEV)]
+    chain.forward(x, heads, act_out=acts)
+    d_heads = (1e-3 * torch.randn(rows, 5, generator=g)).to(DEV)
+    dzs = [torch.full((rows, 64), float('nan'), device=DEV),
+           torch.full((rows * 64 + dz_offset,), float('nan'), device=DEV)[dz_offset:].view(rows, 64)]
+    assert dzs[1].data_ptr() % 16 == 4 * dz_offset
+    chain.backward(d_heads, acts, dzs)
+    maxima = chain.gradient_maxima(rows)
+    assert all(bool(torch.isfinite(t).all()) for t in dzs)
+    if per:
+        assert maxima is not None and chain.maxima_rows_per_entry == per
+        assert torch.equal(maxima[1, :rows // per], dzs[1].abs().view(rows // per, -1).max(dim=1).values)
+        return
+    assert maxima is None
+    shapes = [(64, 24), (64, 64), (5, 64)]
+    plan = ops.MlpDwPlan(shapes, rows, DEV)
+    jobs = [(dz, inp, torch.full(s, float('nan'), device=DEV)) for dz, inp, s in zip(dzs + [d_heads], [x] + acts, shapes)]
+    scales = [ops.SPLIT_SCALE_OBS_NORM, ops.SPLIT_SCALE_HIDDEN, ops.SPLIT_SCALE_HIDDEN]
+    plan.launch(jobs, maxima=None if maxima is None else (maxima, [0, 1, 2], scales, chain.maxima_rows_per_entry))
+    got = [j[2].clone() for j in jobs]
+    plan.launch(jobs, form='bf16')
+    for a, (_, _, b) in zip(got, jobs):
+        assert torch.isfinite(a).all() and torch.equal(a, b)
+
+
 @pytest.mark.parametrize('rows', [16384, 4096])
 def test_split_fp16_backward_scales_gradient_rows_by_their_own_maxima(rows):
     """The fp16 backward splits the d heads tile ROW BY ROW: a row of gradients a million times smaller than its tile

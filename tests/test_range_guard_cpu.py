@@ -59,11 +59,25 @@ def _scan_args(num=2, record=A + 0x500400, counts=(100, 7), tags=(1, 2), arrays=
     return [num, (ctypes.c_void_p * n)(*arrays), (ctypes.c_longlong * n)(*counts), (ctypes.c_int * n)(*tags), record]
 
 
-def _dw_args(form):
+_MAXIMA = dict(maxima_or_null=A + 0x400000, maxima_stride=64, maxima_rows_per_entry=64, dz_slot=0, x_scale=16.0)
+
+
+def _dw_args(form, desc=True, **over):
+    """[form, address of an rlg_mlp_dw_desc (desc=False: NULL)]: one [64 x 60] layer over 4,096 rows, no maxima"""
+    if not desc:
+        return [form, None]
+    from rl_games_amd._lib import MlpDwDesc
     P, I = ctypes.c_void_p * 1, ctypes.c_int * 1
-    plan = (ctypes.c_int * 4)(0, 1, 1, 8)
-    return [form, 1, P(A), P(A + 0x100000), P(A + 0x200000), P(A + 0x300000), I(64), I(60), plan, 4096, 0, None, None,
-            None, None, None, None, 1.0, None, None]
+    kw = dict(num_layers=1, rows=4096, dz=P(A), x=P(A + 0x100000), partial=P(A + 0x200000), grad=P(A + 0x300000),
+              out_features=I(64), in_features=I(60), plans4=(ctypes.c_int * 4)(0, 1, 1, 8), grad_scale=1.0)
+    kw.update(over)
+    for name, ctype in (('dz_slot', ctypes.c_int), ('x_scale', ctypes.c_float)):
+        if name in kw:
+            kw[name] = (ctype * 1)(kw[name])
+    _KEEP.extend(v for v in kw.values() if isinstance(v, ctypes.Array))
+    d = MlpDwDesc(**{k: ctypes.addressof(v) if isinstance(v, ctypes.Array) else v for k, v in kw.items()})
+    _KEEP.append(d)
+    return [form, ctypes.addressof(d)]
 
 
 def _rows():
@@ -92,6 +106,18 @@ def _rows():
     t.append(('mlp_dw_launch_form: form 3', 'mlp_dw_launch_form', _dw_args(3)))
     t.append(('mlp_dw_launch_form: form -2', 'mlp_dw_launch_form', _dw_args(-2)))
     t.append(('mlp_dw_launch_form: the fp16 form without its maxima', 'mlp_dw_launch_form', _dw_args(2)))
+    t.append(('mlp_dw_launch_form: NULL descriptor', 'mlp_dw_launch_form', _dw_args(1, desc=False)))
+    # the maxima fields are read only with maxima; a bad one is rejected whatever the form
+    for what, bad in (('16 or 64 rows per entry only', dict(maxima_rows_per_entry=32)), ('a stride of 0', dict(maxima_stride=0)),
+                      ('a dz slot of 8', dict(dz_slot=8)), ('a negative dz slot', dict(dz_slot=-1)),
+                      ('an x scale of 0', dict(x_scale=0.0)), ('an x scale that is NaN', dict(x_scale=float('nan')))):
+        t.append((f'mlp_dw_launch_form: maxima, {what}', 'mlp_dw_launch_form', _dw_args(1, **dict(_MAXIMA, **bad))))
+    # too few entries for the rows (4,096 rows want 64 entries of 64 rows) count as no maxima
+    t.append(('mlp_dw_launch_form: the fp16 form with maxima of too short a stride', 'mlp_dw_launch_form',
+              _dw_args(2, **dict(_MAXIMA, maxima_stride=63))))
+    # nothing stays armed between calls: maxima of a call that is rejected at its top (no rows) do not serve the next one
+    t.append(('mlp_dw_launch_form: the fp16 form without maxima, behind a rejected call that had them', 'mlp_dw_launch_form',
+              (_dw_args(2, rows=0, **_MAXIMA), _dw_args(2))))
     return t
 
 
@@ -102,7 +128,8 @@ def run_table():
     codes = {}
     for name, entry, args in _rows():
         assert name not in codes, name
-        codes[name] = getattr(lib, 'rlg_' + entry)(*args, None)
+        for call in (args if isinstance(args, tuple) else (args,)):      # (a tuple: a sequence of calls, the last one answers)
+            codes[name] = getattr(lib, 'rlg_' + entry)(*call, None)
     # a scan of nothing is no error and no launch
     codes['range_scan: zero arrays'] = lib.rlg_range_scan(0, None, None, None, A + 0x500400, None)
     return codes
@@ -118,7 +145,7 @@ def test_malformed_guard_calls_are_rejected_before_any_launch():
     codes = json.loads(out.stdout.strip().splitlines()[-1])
     assert codes.pop('range_scan: zero arrays') == 0
     names = [name for name, _, _ in _rows()]
-    assert len(names) == 29 and set(codes) == set(names)
+    assert len(names) == 38 and set(codes) == set(names)
     wrong = {name: codes[name] for name in names if codes[name] != INVALID}
     assert not wrong, f'rows that were not answered with hipErrorInvalidValue: {wrong}'
 

@@ -54,9 +54,6 @@ class _Lib:
     def rlg_mlp_chain_num_blocks(self, rows, groups):
         return -(-rows // (16 * groups))
 
-    def rlg_mlp_chain_gradient_maxima(self, ptr, entries):
-        return 0
-
     # ---- launches
     def rlg_mlp_chain_pack_planes(self, n, w, ins, outs, direction, out, stream):
         assert out
@@ -66,28 +63,27 @@ class _Lib:
         assert fwd
         return self._rec(n, 'pack_frags')
 
-    def rlg_mlp_chain_forward(self, n, *a):
-        rows, _, pack_planes, weight_planes, _ = a[-5:]
-        return self._rec(n, 'forward', rows, dict(pack_planes=bool(pack_planes), weight_planes=bool(weight_planes)))
+    # (the launching entries take descriptors by reference: ctypes.byref(d)._obj is d)
+    def rlg_mlp_chain_forward(self, net, fwd, launch, stream):
+        fwd = fwd._obj
+        return self._rec(net._obj.num_layers, 'forward', launch._obj.rows,
+                         dict(pack_planes=bool(fwd.pack_backward_planes_or_null), weight_planes=bool(fwd.weight_form_or_null)))
 
-    def rlg_mlp_chain_forward_lean(self, n, *a):
-        rows, frags, _ = a[-3:]
-        return self._rec(n, 'forward_lean', rows, dict(frags=bool(frags)))
+    def rlg_mlp_chain_forward_lean(self, net, fwd, launch, stream):
+        return self._rec(net._obj.num_layers, 'forward_lean', launch._obj.rows, dict(frags=bool(fwd._obj.weight_form_or_null)))
 
-    def rlg_mlp_chain_backward(self, n, *a):
-        rows, _, planes, _ = a[-4:]
-        return self._rec(n, 'backward', rows, dict(planes=bool(planes)))
+    def rlg_mlp_chain_backward(self, net, bwd, launch, stream):
+        return self._rec(net._obj.num_layers, 'backward', launch._obj.rows, dict(planes=bool(bwd._obj.weight_form_or_null)))
 
-    def rlg_mlp_chain_backward_lean(self, n, *a):
-        rows, frags, _ = a[-3:]
-        return self._rec(n, 'backward_lean', rows, dict(frags=bool(frags)))
+    def rlg_mlp_chain_backward_lean(self, net, bwd, launch, stream):
+        return self._rec(net._obj.num_layers, 'backward_lean', launch._obj.rows, dict(frags=bool(bwd._obj.weight_form_or_null)))
 
-    def rlg_mlp_chain_step(self, n, *a):
-        return self._rec(n, 'step', a[-2], dict(frags=False))
+    def rlg_mlp_chain_step(self, net, fwd, bwd, launch, stream):
+        return self._rec(net._obj.num_layers, 'step', launch._obj.rows, dict(frags=False))
 
-    def rlg_mlp_chain_step_lean(self, n, *a):
-        rows, f0, f1, _ = a[-4:]
-        return self._rec(n, 'step_lean', rows, dict(frags=bool(f0) and bool(f1)))
+    def rlg_mlp_chain_step_lean(self, net, fwd, bwd, launch, stream):
+        return self._rec(net._obj.num_layers, 'step_lean', launch._obj.rows,
+                         dict(frags=bool(fwd._obj.weight_form_or_null) and bool(bwd._obj.weight_form_or_null)))
 
 
 # what the traces are made of

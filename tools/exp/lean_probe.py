@@ -47,26 +47,31 @@ _lib.check(lib.rlg_mlp_chain_pack_frags(n, wp, None, ins, outs, 1, bfrags.data_p
 print('backward fragment stream:', nbytes_b, 'bytes')
 
 
-def lean_backward(d_heads, acts, dzs, parts, desc=None):
-    ai = P(*[t.data_ptr() for t in acts] + [None])
-    ald = LL(*[t.stride(0) for t in acts] + [0])
-    dz = P(*[t.data_ptr() for t in dzs] + [None])
-    dzld = LL(*[t.stride(0) for t in dzs] + [0])
-    bpp = P(*[t.data_ptr() for t in parts] + [None])
-    _lib.check(lib.rlg_mlp_chain_backward_lean(n, ins, outs, acts_code, ai, ald, d_heads.data_ptr(), d_heads.stride(0), dz, dzld, bpp,
-                                               None if desc is None else ctypes.addressof(desc), d_heads.shape[0],
-                                               bfrags.data_ptr(), st), 'backward_lean')
+addr = lambda a: None if a is None else ctypes.addressof(a)      # noqa: E731
+net = _lib.ChainNet(n, addr(wp), addr(bp), addr(ins), addr(outs), addr(acts_code))
 
+
+def _launch(rows):
+    return ctypes.byref(_lib.ChainLaunch(rows, 0))
+
+
+def lean_backward(d_heads, acts, dzs, parts, desc=None):
+    arrays = (P(*[t.data_ptr() for t in acts] + [None]), LL(*[t.stride(0) for t in acts] + [0]),
+              P(*[t.data_ptr() for t in dzs] + [None]), LL(*[t.stride(0) for t in dzs] + [0]),
+              P(*[t.data_ptr() for t in parts] + [None]))
+    ai, ald, dz, dzld, bpp = [addr(a) for a in arrays]
+    bwd = _lib.ChainBwd(ai, ald, d_heads.data_ptr(), d_heads.stride(0), dz, dzld, bpp, addr(desc), bfrags.data_ptr())
+    _lib.check(lib.rlg_mlp_chain_backward_lean(ctypes.byref(net), ctypes.byref(bwd), _launch(d_heads.shape[0]), st),
+               'backward_lean')
 
 
 def lean_forward(x, heads, acts, rms, xn):
     outs_t = list(acts) + [heads] if acts is not None else [None] * (n - 1) + [heads]
     ao = P(*[None if t is None else t.data_ptr() for t in outs_t])
     ald = LL(*[0 if t is None else t.stride(0) for t in outs_t])
-    _lib.check(lib.rlg_mlp_chain_forward_lean(n, bp, ins, outs, acts_code, ao, ald, x.data_ptr(), x.stride(0),
-                                              rms[0].data_ptr(), rms[1].data_ptr(), 1e-5,
-                                              None if xn is None else xn.data_ptr(), None, None, None, None, None,
-                                              x.shape[0], frags.data_ptr(), st), 'forward_lean')
+    fwd = _lib.ChainFwd(addr(ao), addr(ald), x.data_ptr(), x.stride(0), rms[0].data_ptr(), rms[1].data_ptr(), 1e-5,
+                        None if xn is None else xn.data_ptr(), weight_form_or_null=frags.data_ptr())
+    _lib.check(lib.rlg_mlp_chain_forward_lean(ctypes.byref(net), ctypes.byref(fwd), _launch(x.shape[0]), st), 'forward_lean')
 
 
 def timeit(fn, reps=100):
