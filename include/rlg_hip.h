@@ -832,14 +832,51 @@ int rlg_mlp_chain_bx_supported(int num_layers, const int* in_features, const int
  * neither a CU's 512 KB register file nor registers + LDS together, and other widths have no instantiation: the entry
  * points return hipErrorInvalidValue for them. */
 int rlg_lstm_supported(int hidden);
-int rlg_lstm_seq_forward(float* gates, const float* w_hh, const float* h0, const float* c0,
-                         const unsigned char* dones_or_null, float* out, float* c_all_or_null,
-                         float* hprev_or_null, float* h_final_or_null, float* c_final_or_null,
-                         int num_seqs, int seq_len, int hidden, void* stream);
+
+/* The four sequence entries (LSTM / GRU, forward / backward) take an array of one or two problem descriptors and the
+ * shape the problems share: num_seqs, seq_len, hidden.  The descriptors hold one problem's pointers and are read before
+ * the entry returns; a field named *_or_null below (in the comments) may be NULL, every other one is required.
+ * num_problems 1: one launch of the single kernel on ceil(S / tile) workgroups.
+ * num_problems 2: a paired launch of two problems A = problems[0] and B = problems[1] of ONE shape (cell, hidden,
+ * num_seqs, seq_len) that do not depend on each other - the actor's and the critic's recurrence of a `separate: True`
+ * network, each with its own RNN (network_builder.py:272-277, :372-421).  The grid has ceil(S / tile) x 2 workgroups:
+ * row 0 runs problem A, row 1 problem B, each workgroup the code of the single kernel, the tile chosen from ONE problem's
+ * num_seqs exactly as for one problem.  Every output is therefore bit-identical to what the two single launches write
+ * (csrc/rnn_seq.hpp, "paired launches").  An optional output may be given for one problem and NULL for the other.
+ * hipErrorInvalidValue, before the runtime is asked for anything and with nothing launched, in this order: a NULL
+ * problems or a num_problems other than 1 or 2 (answered first); num_seqs <= 0, seq_len <= 0 or a width other than
+ * 16 / 32 / 64 / 128; a NULL required pointer in any problem; with two problems an output buffer of A - gates, out,
+ * c_all / hn_all, hprev, hT, cT; d_gates; d_gx, d_gh - that is also the same-named buffer of B; at 128 units a w_hh of
+ * any problem that is not 16-byte aligned (not rlg_lstm_seq_backward, whose kernel loads w_hh one float at a time). */
+typedef struct rlg_lstm_fwd {
+  float* gates;                     /* [S*T, 4H]: gate inputs on entry, activated gates on exit */
+  const float* w_hh;                /* [4H, H] */
+  const float* h0;                  /* [S, H] */
+  const float* c0;                  /* [S, H] */
+  const unsigned char* dones;       /* _or_null: [S*T]; NULL: no resets */
+  float* out;                       /* [S*T, H]: h_t */
+  float* c_all;                     /* _or_null: [S*T, H]: c_t, for the backward */
+  float* hprev;                     /* _or_null: [S*T, H]: the state entering each step after the reset (dW_hh) */
+  float* hT;                        /* _or_null: [S, H]: h after the last step */
+  float* cT;                        /* _or_null: [S, H]: c after the last step */
+} rlg_lstm_fwd;
+RLG_ABI_SIZE(rlg_lstm_fwd, 80);
+int rlg_lstm_seq_forward(const rlg_lstm_fwd* problems, int num_problems, int num_seqs, int seq_len, int hidden,
+                         void* stream);
+
 /* d_gates [S*T, 4H] = d loss / d gate pre-activations given d_out = d loss / d h_t. */
-int rlg_lstm_seq_backward(const float* gates, const float* c_all, const float* c0,
-                          const unsigned char* dones_or_null, const float* w_hh, const float* d_out,
-                          float* d_gates, int num_seqs, int seq_len, int hidden, void* stream);
+typedef struct rlg_lstm_bwd {
+  const float* gates;               /* the forward's activated gates, c_all and c0 */
+  const float* c_all;
+  const float* c0;
+  const unsigned char* dones;       /* _or_null */
+  const float* w_hh;
+  const float* d_out;               /* [S*T, H] */
+  float* d_gates;
+} rlg_lstm_bwd;
+RLG_ABI_SIZE(rlg_lstm_bwd, 56);
+int rlg_lstm_seq_backward(const rlg_lstm_bwd* problems, int num_problems, int num_seqs, int seq_len, int hidden,
+                          void* stream);
 
 /* Sequence-persistent GRU layer: the same position in the network and the same contract (rows seq*T + t, done rule,
  * one launch for all T steps, weights fetched once per launch) for `rnn: {name: gru, layers: 1}`
@@ -850,60 +887,43 @@ int rlg_lstm_seq_backward(const float* gates, const float* c_all, const float* c
  * gates [S*T, 3H] holds gx = x_t W_ih^T + b_ih on entry and the activated (r, z, n) on exit.  b_hn sits inside the
  * product with r and cannot be folded into the input side, so b_hh [3H] is an argument of its own.
  * For training the forward keeps hn_all [S*T, H] (hn, before the gating by r) and hprev [S*T, H] (the state entering
- * each step after the reset); for inference h_final [S, H].
+ * each step after the reset); for inference hT [S, H].
  * rlg_gru_supported(hidden): 1 for 16, 32, 64 and 128, else 0.  W_hh [3H, H] in LDS as fp32 up to 64 units (48 KB;
  * csrc/gru.hip); at 128 units (192 KB, more than a CU's 160 KB of LDS) in the registers of a 1,024-thread workgroup as
  * operand fragments of v_mfma_f32_16x16x4_f32 (csrc/gru_wide.hip; w_hh must then be 16-byte aligned).  Other widths:
  * hipErrorInvalidValue. */
 int rlg_gru_supported(int hidden);
-int rlg_gru_seq_forward(float* gates, const float* w_hh, const float* b_hh, const float* h0,
-                        const unsigned char* dones_or_null, float* out, float* hn_all_or_null,
-                        float* hprev_or_null, float* h_final_or_null,
-                        int num_seqs, int seq_len, int hidden, void* stream);
+typedef struct rlg_gru_fwd {
+  float* gates;                     /* [S*T, 3H]: gx on entry, activated (r, z, n) on exit */
+  const float* w_hh;                /* [3H, H] */
+  const float* b_hh;                /* [3H] */
+  const float* h0;                  /* [S, H] */
+  const unsigned char* dones;       /* _or_null */
+  float* out;                       /* [S*T, H]: h_t */
+  float* hn_all;                    /* _or_null */
+  float* hprev;                     /* _or_null */
+  float* hT;                        /* _or_null: [S, H]: h after the last step */
+} rlg_gru_fwd;
+RLG_ABI_SIZE(rlg_gru_fwd, 72);
+int rlg_gru_seq_forward(const rlg_gru_fwd* problems, int num_problems, int num_seqs, int seq_len, int hidden,
+                        void* stream);
+
 /* Given d_out = d loss / d h_t:  d_gx [S*T, 3H] = (dr_pre, dz_pre, dn_pre), the gradient of the input side (dW_ih,
  * db_ih, the trunk's dX), and d_gh [S*T, 3H] = (dr_pre, dz_pre, dn_pre * r), the gradient of the hidden side
  * (dW_hh = d_gh^T hprev, db_hh). */
-int rlg_gru_seq_backward(const float* gates, const float* hn_all, const float* hprev,
-                         const unsigned char* dones_or_null, const float* w_hh, const float* d_out,
-                         float* d_gx, float* d_gh, int num_seqs, int seq_len, int hidden, void* stream);
-
-/* Paired sequence launches: two problems A and B of ONE shape (cell, hidden, num_seqs, seq_len) that do not depend on
- * each other - the actor's and the critic's recurrence of a `separate: True` network, each with its own RNN
- * (network_builder.py:272-277, :372-421) - in one launch.  The grid has ceil(S / tile) x 2 workgroups: row 0 runs
- * problem A, row 1 problem B, each workgroup the code of the single kernel, the tile chosen from ONE problem's
- * num_seqs exactly as the single entry chooses it.  Every output is therefore bit-identical to what the two single
- * launches write (csrc/rnn_seq.hpp, "paired launches").
- * Arguments: the pointer list of the single entry for A (suffix _a), the same list for B (suffix _b), then the shared
- * num_seqs, seq_len, hidden, stream.  An optional output may be given for one problem and NULL for the other.
- * hipErrorInvalidValue, before the runtime is asked for anything and with nothing launched: a width other than
- * 16 / 32 / 64 / 128; num_seqs <= 0 or seq_len <= 0; a NULL pointer without _or_null in either problem; at 128 units a
- * w_hh of either problem that is not 16-byte aligned (not rlg_lstm_seq_backward_pair, whose single entry has no such
- * rule either); an output buffer of A - gates, out, c_all / hn_all, hprev, h_final, c_final; d_gates; d_gx, d_gh -
- * that is also the same-named buffer of B. */
-int rlg_lstm_seq_forward_pair(
-    float* gates_a, const float* w_hh_a, const float* h0_a, const float* c0_a, const unsigned char* dones_a_or_null,
-    float* out_a, float* c_all_a_or_null, float* hprev_a_or_null, float* h_final_a_or_null, float* c_final_a_or_null,
-    float* gates_b, const float* w_hh_b, const float* h0_b, const float* c0_b, const unsigned char* dones_b_or_null,
-    float* out_b, float* c_all_b_or_null, float* hprev_b_or_null, float* h_final_b_or_null, float* c_final_b_or_null,
-    int num_seqs, int seq_len, int hidden, void* stream);
-int rlg_lstm_seq_backward_pair(
-    const float* gates_a, const float* c_all_a, const float* c0_a, const unsigned char* dones_a_or_null,
-    const float* w_hh_a, const float* d_out_a, float* d_gates_a,
-    const float* gates_b, const float* c_all_b, const float* c0_b, const unsigned char* dones_b_or_null,
-    const float* w_hh_b, const float* d_out_b, float* d_gates_b,
-    int num_seqs, int seq_len, int hidden, void* stream);
-int rlg_gru_seq_forward_pair(
-    float* gates_a, const float* w_hh_a, const float* b_hh_a, const float* h0_a, const unsigned char* dones_a_or_null,
-    float* out_a, float* hn_all_a_or_null, float* hprev_a_or_null, float* h_final_a_or_null,
-    float* gates_b, const float* w_hh_b, const float* b_hh_b, const float* h0_b, const unsigned char* dones_b_or_null,
-    float* out_b, float* hn_all_b_or_null, float* hprev_b_or_null, float* h_final_b_or_null,
-    int num_seqs, int seq_len, int hidden, void* stream);
-int rlg_gru_seq_backward_pair(
-    const float* gates_a, const float* hn_all_a, const float* hprev_a, const unsigned char* dones_a_or_null,
-    const float* w_hh_a, const float* d_out_a, float* d_gx_a, float* d_gh_a,
-    const float* gates_b, const float* hn_all_b, const float* hprev_b, const unsigned char* dones_b_or_null,
-    const float* w_hh_b, const float* d_out_b, float* d_gx_b, float* d_gh_b,
-    int num_seqs, int seq_len, int hidden, void* stream);
+typedef struct rlg_gru_bwd {
+  const float* gates;               /* the forward's activated gates, hn_all and hprev */
+  const float* hn_all;
+  const float* hprev;
+  const unsigned char* dones;       /* _or_null */
+  const float* w_hh;
+  const float* d_out;               /* [S*T, H] */
+  float* d_gx;
+  float* d_gh;
+} rlg_gru_bwd;
+RLG_ABI_SIZE(rlg_gru_bwd, 64);
+int rlg_gru_seq_backward(const rlg_gru_bwd* problems, int num_problems, int num_seqs, int seq_len, int hidden,
+                         void* stream);
 
 /* Layer normalisation behind the recurrent layer (csrc/rnn_layer_norm.hip): `rnn: {layer_norm: True}`,
  * nn.LayerNorm(rnn_units) over the RNN output [rows, hidden] (network_builder.py:447-500), hidden 16 / 32 / 64 / 128.

@@ -111,16 +111,12 @@ _PROTOTYPES = {
     'rlg_mlp_chain_pack_planes': [_c_int, _P, _P, _P, _c_int, _P, _P],
     'rlg_mlp_chain_bx_supported': [_c_int, _P, _P, _c_ll, _c_int, _c_int],
     'rlg_lstm_supported': [_c_int],
-    'rlg_lstm_seq_forward': [_P] * 10 + [_c_int, _c_int, _c_int, _P],
-    'rlg_lstm_seq_backward': [_P] * 7 + [_c_int, _c_int, _c_int, _P],
-    # paired launches: problem A's pointers, problem B's, then the shared shape
-    'rlg_lstm_seq_forward_pair': [_P] * 20 + [_c_int, _c_int, _c_int, _P],
-    'rlg_lstm_seq_backward_pair': [_P] * 14 + [_c_int, _c_int, _c_int, _P],
+    # sequence entries: (LstmFwd / LstmBwd / GruFwd / GruBwd array, num_problems, num_seqs, seq_len, hidden, stream)
+    'rlg_lstm_seq_forward': [_P, _c_int, _c_int, _c_int, _c_int, _P],
+    'rlg_lstm_seq_backward': [_P, _c_int, _c_int, _c_int, _c_int, _P],
     'rlg_gru_supported': [_c_int],
-    'rlg_gru_seq_forward': [_P] * 9 + [_c_int, _c_int, _c_int, _P],
-    'rlg_gru_seq_backward': [_P] * 8 + [_c_int, _c_int, _c_int, _P],
-    'rlg_gru_seq_forward_pair': [_P] * 18 + [_c_int, _c_int, _c_int, _P],
-    'rlg_gru_seq_backward_pair': [_P] * 16 + [_c_int, _c_int, _c_int, _P],
+    'rlg_gru_seq_forward': [_P, _c_int, _c_int, _c_int, _c_int, _P],
+    'rlg_gru_seq_backward': [_P, _c_int, _c_int, _c_int, _c_int, _P],
     # rnn_layer_norm.hip
     'rlg_rnn_layer_norm_num_blocks': [_c_ll, _c_int],
     'rlg_rnn_layer_norm_forward': [_P, _P, _P, _c_float, _P, _P, _c_ll, _c_int, _P],
@@ -284,6 +280,26 @@ class MlpDwDesc(ctypes.Structure):
                 + [('grad_scale', _c_float), ('step_counter_or_null', _P), ('finalize_blocks_out_or_null', _P),
                    ('maxima_or_null', _P), ('maxima_stride', _c_int), ('maxima_rows_per_entry', _c_int),
                    ('dz_slot', _P), ('x_scale', _P)])
+
+
+class LstmFwd(ctypes.Structure):
+    """rlg_lstm_fwd: one problem of rlg_lstm_seq_forward."""
+    _fields_ = [(n, _P) for n in ('gates', 'w_hh', 'h0', 'c0', 'dones', 'out', 'c_all', 'hprev', 'hT', 'cT')]
+
+
+class LstmBwd(ctypes.Structure):
+    """rlg_lstm_bwd: one problem of rlg_lstm_seq_backward."""
+    _fields_ = [(n, _P) for n in ('gates', 'c_all', 'c0', 'dones', 'w_hh', 'd_out', 'd_gates')]
+
+
+class GruFwd(ctypes.Structure):
+    """rlg_gru_fwd: one problem of rlg_gru_seq_forward."""
+    _fields_ = [(n, _P) for n in ('gates', 'w_hh', 'b_hh', 'h0', 'dones', 'out', 'hn_all', 'hprev', 'hT')]
+
+
+class GruBwd(ctypes.Structure):
+    """rlg_gru_bwd: one problem of rlg_gru_seq_backward."""
+    _fields_ = [(n, _P) for n in ('gates', 'hn_all', 'hprev', 'dones', 'w_hh', 'd_out', 'd_gx', 'd_gh')]
 
 
 def check(err, what):

@@ -279,8 +279,7 @@ class RnnStations:
     def sequence(self, direction, args, seq_length):
         """The sequence kernel as a launch of its own: direction 'forward' / 'backward', args from forward_args /
         backward_args."""
-        cell = 'lstm' if self.lstm is not None else 'gru'
-        getattr(ops, f'{cell}_seq_{direction}')(*args, seq_len=seq_length)
+        ops.rnn_seq('lstm' if self.lstm is not None else 'gru', direction, [args], seq_length)
 
     @property
     def seq_length(self):
@@ -645,7 +644,7 @@ class RecurrentChainPair:
     def _sequence(self, direction, a_args, b_args, seq_length):
         cell = 'lstm' if self.lstm else 'gru'
         if self.paired and paired_launch_pays(cell, self.actor.Hr, direction, a_args[0].shape[0] // seq_length, seq_length):
-            getattr(ops, f'{cell}_seq_{direction}_pair')(a_args, b_args, seq_len=seq_length)
+            ops.rnn_seq(cell, direction, [a_args, b_args], seq_length)
         else:
             self.actor.stations.sequence(direction, a_args, seq_length)
             self.critic.stations.sequence(direction, b_args, seq_length)

@@ -219,34 +219,32 @@ __global__ __launch_bounds__(kSeqThreads) void gru_seq_bwd_pair_kernel(GruBwdArg
 }
 
 // 128 units: W_hh (192 KB) does not fit LDS; csrc/gru_wide.hip keeps it in registers as MFMA fragments.
-int launch_gru_fwd_wide(float* gates, const float* w_hh, const float* b_hh, const float* h0, const uint8_t* dones,
-                        float* out, float* hn_all, float* hprev, float* hT, int S, int T, hipStream_t st);
-int launch_gru_bwd_wide(const float* gates, const float* hn_all, const float* hprev, const uint8_t* dones,
-                        const float* w_hh, const float* d_out, float* d_gx, float* d_gh, int S, int T,
-                        hipStream_t st);
-int launch_gru_fwd_wide_pair(GruFwdArgs a, GruFwdArgs b, int S, int T, hipStream_t st);
-int launch_gru_bwd_wide_pair(GruBwdArgs a, GruBwdArgs b, int S, int T, hipStream_t st);
+int launch_gru_fwd_wide(const GruFwdArgs* problems, int count, int S, int T, hipStream_t st);
+int launch_gru_bwd_wide(const GruBwdArgs* problems, int count, int S, int T, hipStream_t st);
 
 // kernel families for rnn_seq.hpp's launch_seq
 struct GruFwd {
+  using Args = GruFwdArgs;
   template <int H, int SB>
   static constexpr auto kernel = gru_seq_fwd_kernel<H, SB>;
   template <int H, int SB>
   static constexpr auto pair_kernel = gru_seq_fwd_pair_kernel<H, SB>;
   static constexpr size_t lds_floats(int H, int SB) { return static_cast<size_t>(3) * H * H + 2 * SB * H; }
   static constexpr auto wide = launch_gru_fwd_wide;
-  static constexpr auto wide_pair = launch_gru_fwd_wide_pair;
 };
 
 struct GruBwd {
+  using Args = GruBwdArgs;
   template <int H, int SB>
   static constexpr auto kernel = gru_seq_bwd_kernel<H, SB>;
   template <int H, int SB>
   static constexpr auto pair_kernel = gru_seq_bwd_pair_kernel<H, SB>;
   static constexpr size_t lds_floats(int H, int SB) { return static_cast<size_t>(3) * H * H + SB * 3 * H; }
   static constexpr auto wide = launch_gru_bwd_wide;
-  static constexpr auto wide_pair = launch_gru_bwd_wide_pair;
 };
+
+// kernel order of the code object: rnn_seq.hpp
+static_assert(single_kernels_first<GruFwd>() && single_kernels_first<GruBwd>());
 
 }  // namespace rlg
 
@@ -254,45 +252,14 @@ extern "C" {
 
 int rlg_gru_supported(int hidden) { return rlg::seq_hidden_supported(hidden) ? 1 : 0; }
 
-int rlg_gru_seq_forward(float* gates, const float* w_hh, const float* b_hh, const float* h0,
-                        const unsigned char* dones_or_null, float* out, float* hn_all_or_null,
-                        float* hprev_or_null, float* h_final_or_null, int num_seqs, int seq_len, int hidden,
+int rlg_gru_seq_forward(const rlg_gru_fwd* problems, int num_problems, int num_seqs, int seq_len, int hidden,
                         void* stream) {
-  if (num_seqs <= 0 || seq_len <= 0) return static_cast<int>(hipErrorInvalidValue);
-  return rlg::launch_seq<rlg::GruFwd>(hidden, num_seqs, seq_len, static_cast<hipStream_t>(stream), gates, w_hh, b_hh,
-                                      h0, dones_or_null, out, hn_all_or_null, hprev_or_null, h_final_or_null);
+  return rlg::launch_seq<rlg::GruFwd>(problems, num_problems, hidden, num_seqs, seq_len, stream);
 }
 
-int rlg_gru_seq_backward(const float* gates, const float* hn_all, const float* hprev,
-                         const unsigned char* dones_or_null, const float* w_hh, const float* d_out, float* d_gx,
-                         float* d_gh, int num_seqs, int seq_len, int hidden, void* stream) {
-  if (num_seqs <= 0 || seq_len <= 0) return static_cast<int>(hipErrorInvalidValue);
-  return rlg::launch_seq<rlg::GruBwd>(hidden, num_seqs, seq_len, static_cast<hipStream_t>(stream), gates, hn_all,
-                                      hprev, dones_or_null, w_hh, d_out, d_gx, d_gh);
-}
-
-int rlg_gru_seq_forward_pair(
-    float* gates_a, const float* w_hh_a, const float* b_hh_a, const float* h0_a, const unsigned char* dones_a_or_null,
-    float* out_a, float* hn_all_a_or_null, float* hprev_a_or_null, float* h_final_a_or_null,
-    float* gates_b, const float* w_hh_b, const float* b_hh_b, const float* h0_b, const unsigned char* dones_b_or_null,
-    float* out_b, float* hn_all_b_or_null, float* hprev_b_or_null, float* h_final_b_or_null,
-    int num_seqs, int seq_len, int hidden, void* stream) {
-  const rlg::GruFwdArgs a{gates_a, w_hh_a, b_hh_a, h0_a, dones_a_or_null, out_a, hn_all_a_or_null, hprev_a_or_null,
-                          h_final_a_or_null};
-  const rlg::GruFwdArgs b{gates_b, w_hh_b, b_hh_b, h0_b, dones_b_or_null, out_b, hn_all_b_or_null, hprev_b_or_null,
-                          h_final_b_or_null};
-  return rlg::launch_seq_pair<rlg::GruFwd>(hidden, num_seqs, seq_len, static_cast<hipStream_t>(stream), a, b);
-}
-
-int rlg_gru_seq_backward_pair(
-    const float* gates_a, const float* hn_all_a, const float* hprev_a, const unsigned char* dones_a_or_null,
-    const float* w_hh_a, const float* d_out_a, float* d_gx_a, float* d_gh_a,
-    const float* gates_b, const float* hn_all_b, const float* hprev_b, const unsigned char* dones_b_or_null,
-    const float* w_hh_b, const float* d_out_b, float* d_gx_b, float* d_gh_b,
-    int num_seqs, int seq_len, int hidden, void* stream) {
-  const rlg::GruBwdArgs a{gates_a, hn_all_a, hprev_a, dones_a_or_null, w_hh_a, d_out_a, d_gx_a, d_gh_a};
-  const rlg::GruBwdArgs b{gates_b, hn_all_b, hprev_b, dones_b_or_null, w_hh_b, d_out_b, d_gx_b, d_gh_b};
-  return rlg::launch_seq_pair<rlg::GruBwd>(hidden, num_seqs, seq_len, static_cast<hipStream_t>(stream), a, b);
+int rlg_gru_seq_backward(const rlg_gru_bwd* problems, int num_problems, int num_seqs, int seq_len, int hidden,
+                         void* stream) {
+  return rlg::launch_seq<rlg::GruBwd>(problems, num_problems, hidden, num_seqs, seq_len, stream);
 }
 
 }  // extern "C"

@@ -207,29 +207,16 @@ __global__ __launch_bounds__(kWideThreads) void gru_seq_bwd_wide_pair_kernel(Gru
   gru_seq_bwd_wide_body(p.gates, p.hn_all, p.hprev, p.dones, p.w_hh, p.d_out, p.d_gx, p.d_gh, S, T);
 }
 
-int launch_gru_fwd_wide(float* gates, const float* w_hh, const float* b_hh, const float* h0, const uint8_t* dones,
-                        float* out, float* hn_all, float* hprev, float* hT, int S, int T, hipStream_t st) {
-  if ((reinterpret_cast<uintptr_t>(w_hh) & 15u) != 0) return static_cast<int>(hipErrorInvalidValue);
-  return launch_tile<gru_seq_fwd_wide_kernel>(S, kWideSB, kWideThreads, 0, st, gates, w_hh, b_hh, h0, dones, out,
-                                              hn_all, hprev, hT, S, T);
+int launch_gru_fwd_wide(const GruFwdArgs* problems, int count, int S, int T, hipStream_t st) {
+  if (!wide_aligned(problems, count)) return static_cast<int>(hipErrorInvalidValue);
+  return launch_problems<gru_seq_fwd_wide_kernel, gru_seq_fwd_wide_pair_kernel>(problems, count, S, T, kWideSB,
+                                                                                kWideThreads, 0, st);
 }
 
-int launch_gru_bwd_wide(const float* gates, const float* hn_all, const float* hprev, const uint8_t* dones,
-                        const float* w_hh, const float* d_out, float* d_gx, float* d_gh, int S, int T,
-                        hipStream_t st) {
-  if ((reinterpret_cast<uintptr_t>(w_hh) & 15u) != 0) return static_cast<int>(hipErrorInvalidValue);
-  return launch_tile<gru_seq_bwd_wide_kernel>(S, kWideSB, kWideThreads, 0, st, gates, hn_all, hprev, dones, w_hh,
-                                              d_out, d_gx, d_gh, S, T);
-}
-
-int launch_gru_fwd_wide_pair(GruFwdArgs a, GruFwdArgs b, int S, int T, hipStream_t st) {
-  if (!wide_pair_aligned(a.w_hh, b.w_hh)) return static_cast<int>(hipErrorInvalidValue);
-  return launch_tile<gru_seq_fwd_wide_pair_kernel, 2>(S, kWideSB, kWideThreads, 0, st, a, b, S, T);
-}
-
-int launch_gru_bwd_wide_pair(GruBwdArgs a, GruBwdArgs b, int S, int T, hipStream_t st) {
-  if (!wide_pair_aligned(a.w_hh, b.w_hh)) return static_cast<int>(hipErrorInvalidValue);
-  return launch_tile<gru_seq_bwd_wide_pair_kernel, 2>(S, kWideSB, kWideThreads, 0, st, a, b, S, T);
+int launch_gru_bwd_wide(const GruBwdArgs* problems, int count, int S, int T, hipStream_t st) {
+  if (!wide_aligned(problems, count)) return static_cast<int>(hipErrorInvalidValue);
+  return launch_problems<gru_seq_bwd_wide_kernel, gru_seq_bwd_wide_pair_kernel>(problems, count, S, T, kWideSB,
+                                                                                kWideThreads, 0, st);
 }
 
 }  // namespace rlg

@@ -214,33 +214,32 @@ __global__ __launch_bounds__(kSeqThreads) void lstm_seq_bwd_pair_kernel(LstmBwdA
 }
 
 // 128 units: W_hh (256 KB) does not fit LDS; csrc/lstm_wide.hip keeps it in registers as MFMA fragments.
-int launch_lstm_fwd_wide(float* gates, const float* w_hh, const float* h0, const float* c0, const uint8_t* dones,
-                         float* out, float* c_all, float* hprev, float* hT, float* cT, int S, int T, hipStream_t st);
-int launch_lstm_bwd_wide(const float* gates, const float* c_all, const float* c0, const uint8_t* dones,
-                         const float* w_hh, const float* d_out, float* d_gates, int S, int T, hipStream_t st);
-int launch_lstm_fwd_wide_pair(LstmFwdArgs a, LstmFwdArgs b, int S, int T, hipStream_t st);
-int launch_lstm_bwd_wide_pair(LstmBwdArgs a, LstmBwdArgs b, int S, int T, hipStream_t st);
+int launch_lstm_fwd_wide(const LstmFwdArgs* problems, int count, int S, int T, hipStream_t st);
+int launch_lstm_bwd_wide(const LstmBwdArgs* problems, int count, int S, int T, hipStream_t st);
 
 // kernel families for rnn_seq.hpp's launch_seq
 struct LstmFwd {
+  using Args = LstmFwdArgs;
   template <int H, int SB>
   static constexpr auto kernel = lstm_seq_fwd_kernel<H, SB>;
   template <int H, int SB>
   static constexpr auto pair_kernel = lstm_seq_fwd_pair_kernel<H, SB>;
   static constexpr size_t lds_floats(int H, int SB) { return static_cast<size_t>(4) * H * H + 2 * SB * H; }
   static constexpr auto wide = launch_lstm_fwd_wide;
-  static constexpr auto wide_pair = launch_lstm_fwd_wide_pair;
 };
 
 struct LstmBwd {
+  using Args = LstmBwdArgs;
   template <int H, int SB>
   static constexpr auto kernel = lstm_seq_bwd_kernel<H, SB>;
   template <int H, int SB>
   static constexpr auto pair_kernel = lstm_seq_bwd_pair_kernel<H, SB>;
   static constexpr size_t lds_floats(int H, int SB) { return static_cast<size_t>(4) * H * H + SB * 4 * H; }
   static constexpr auto wide = launch_lstm_bwd_wide;
-  static constexpr auto wide_pair = launch_lstm_bwd_wide_pair;
 };
+
+// kernel order of the code object: rnn_seq.hpp
+static_assert(single_kernels_first<LstmFwd>() && single_kernels_first<LstmBwd>());
 
 }  // namespace rlg
 
@@ -248,46 +247,14 @@ extern "C" {
 
 int rlg_lstm_supported(int hidden) { return rlg::seq_hidden_supported(hidden) ? 1 : 0; }
 
-int rlg_lstm_seq_forward(float* gates, const float* w_hh, const float* h0, const float* c0,
-                         const unsigned char* dones_or_null, float* out, float* c_all_or_null,
-                         float* hprev_or_null, float* h_final_or_null, float* c_final_or_null,
-                         int num_seqs, int seq_len, int hidden, void* stream) {
-  if (num_seqs <= 0 || seq_len <= 0) return static_cast<int>(hipErrorInvalidValue);
-  return rlg::launch_seq<rlg::LstmFwd>(hidden, num_seqs, seq_len, static_cast<hipStream_t>(stream), gates, w_hh, h0,
-                                       c0, dones_or_null, out, c_all_or_null, hprev_or_null, h_final_or_null,
-                                       c_final_or_null);
+int rlg_lstm_seq_forward(const rlg_lstm_fwd* problems, int num_problems, int num_seqs, int seq_len, int hidden,
+                         void* stream) {
+  return rlg::launch_seq<rlg::LstmFwd>(problems, num_problems, hidden, num_seqs, seq_len, stream);
 }
 
-int rlg_lstm_seq_backward(const float* gates, const float* c_all, const float* c0,
-                          const unsigned char* dones_or_null, const float* w_hh, const float* d_out,
-                          float* d_gates, int num_seqs, int seq_len, int hidden, void* stream) {
-  if (num_seqs <= 0 || seq_len <= 0) return static_cast<int>(hipErrorInvalidValue);
-  return rlg::launch_seq<rlg::LstmBwd>(hidden, num_seqs, seq_len, static_cast<hipStream_t>(stream), gates, c_all, c0,
-                                       dones_or_null, w_hh, d_out, d_gates);
-}
-
-int rlg_lstm_seq_forward_pair(
-    float* gates_a, const float* w_hh_a, const float* h0_a, const float* c0_a, const unsigned char* dones_a_or_null,
-    float* out_a, float* c_all_a_or_null, float* hprev_a_or_null, float* h_final_a_or_null, float* c_final_a_or_null,
-    float* gates_b, const float* w_hh_b, const float* h0_b, const float* c0_b, const unsigned char* dones_b_or_null,
-    float* out_b, float* c_all_b_or_null, float* hprev_b_or_null, float* h_final_b_or_null, float* c_final_b_or_null,
-    int num_seqs, int seq_len, int hidden, void* stream) {
-  const rlg::LstmFwdArgs a{gates_a, w_hh_a, h0_a, c0_a, dones_a_or_null, out_a, c_all_a_or_null, hprev_a_or_null,
-                           h_final_a_or_null, c_final_a_or_null};
-  const rlg::LstmFwdArgs b{gates_b, w_hh_b, h0_b, c0_b, dones_b_or_null, out_b, c_all_b_or_null, hprev_b_or_null,
-                           h_final_b_or_null, c_final_b_or_null};
-  return rlg::launch_seq_pair<rlg::LstmFwd>(hidden, num_seqs, seq_len, static_cast<hipStream_t>(stream), a, b);
-}
-
-int rlg_lstm_seq_backward_pair(
-    const float* gates_a, const float* c_all_a, const float* c0_a, const unsigned char* dones_a_or_null,
-    const float* w_hh_a, const float* d_out_a, float* d_gates_a,
-    const float* gates_b, const float* c_all_b, const float* c0_b, const unsigned char* dones_b_or_null,
-    const float* w_hh_b, const float* d_out_b, float* d_gates_b,
-    int num_seqs, int seq_len, int hidden, void* stream) {
-  const rlg::LstmBwdArgs a{gates_a, c_all_a, c0_a, dones_a_or_null, w_hh_a, d_out_a, d_gates_a};
-  const rlg::LstmBwdArgs b{gates_b, c_all_b, c0_b, dones_b_or_null, w_hh_b, d_out_b, d_gates_b};
-  return rlg::launch_seq_pair<rlg::LstmBwd>(hidden, num_seqs, seq_len, static_cast<hipStream_t>(stream), a, b);
+int rlg_lstm_seq_backward(const rlg_lstm_bwd* problems, int num_problems, int num_seqs, int seq_len, int hidden,
+                          void* stream) {
+  return rlg::launch_seq<rlg::LstmBwd>(problems, num_problems, hidden, num_seqs, seq_len, stream);
 }
 
 }  // extern "C"

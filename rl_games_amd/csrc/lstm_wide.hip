@@ -205,28 +205,16 @@ __global__ __launch_bounds__(kWideThreads) void lstm_seq_bwd_wide_pair_kernel(Ls
   lstm_seq_bwd_wide_body(p.gates, p.c_all, p.c0, p.dones, p.w_hh, p.d_out, p.d_gates, S, T);
 }
 
-int launch_lstm_fwd_wide(float* gates, const float* w_hh, const float* h0, const float* c0, const uint8_t* dones,
-                         float* out, float* c_all, float* hprev, float* hT, float* cT, int S, int T,
-                         hipStream_t st) {
-  if ((reinterpret_cast<uintptr_t>(w_hh) & 15u) != 0) return static_cast<int>(hipErrorInvalidValue);
-  return launch_tile<lstm_seq_fwd_wide_kernel>(S, kWideSB, kWideThreads, 0, st, gates, w_hh, h0, c0, dones, out, c_all,
-                                               hprev, hT, cT, S, T);
+int launch_lstm_fwd_wide(const LstmFwdArgs* problems, int count, int S, int T, hipStream_t st) {
+  if (!wide_aligned(problems, count)) return static_cast<int>(hipErrorInvalidValue);
+  return launch_problems<lstm_seq_fwd_wide_kernel, lstm_seq_fwd_wide_pair_kernel>(problems, count, S, T, kWideSB,
+                                                                                  kWideThreads, 0, st);
 }
 
-int launch_lstm_bwd_wide(const float* gates, const float* c_all, const float* c0, const uint8_t* dones,
-                         const float* w_hh, const float* d_out, float* d_gates, int S, int T, hipStream_t st) {
-  return launch_tile<lstm_seq_bwd_wide_kernel>(S, kWideSB, kWideThreads, 0, st, gates, c_all, c0, dones, w_hh, d_out,
-                                               d_gates, S, T);
-}
-
-int launch_lstm_fwd_wide_pair(LstmFwdArgs a, LstmFwdArgs b, int S, int T, hipStream_t st) {
-  if (!wide_pair_aligned(a.w_hh, b.w_hh)) return static_cast<int>(hipErrorInvalidValue);
-  return launch_tile<lstm_seq_fwd_wide_pair_kernel, 2>(S, kWideSB, kWideThreads, 0, st, a, b, S, T);
-}
-
-// (no alignment rule, as launch_lstm_bwd_wide: rnn_seq.hpp's list of asymmetries)
-int launch_lstm_bwd_wide_pair(LstmBwdArgs a, LstmBwdArgs b, int S, int T, hipStream_t st) {
-  return launch_tile<lstm_seq_bwd_wide_pair_kernel, 2>(S, kWideSB, kWideThreads, 0, st, a, b, S, T);
+// (no alignment rule: rnn_seq.hpp's list of asymmetries)
+int launch_lstm_bwd_wide(const LstmBwdArgs* problems, int count, int S, int T, hipStream_t st) {
+  return launch_problems<lstm_seq_bwd_wide_kernel, lstm_seq_bwd_wide_pair_kernel>(problems, count, S, T, kWideSB,
+                                                                                  kWideThreads, 0, st);
 }
 
 }  // namespace rlg

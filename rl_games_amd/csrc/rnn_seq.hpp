@@ -35,7 +35,10 @@
 // the asymmetries above.  The problems' argument sets travel by value as the *Args structs below.
 #pragma once
 
+#include <type_traits>
+
 #include "rlg_device.hpp"
+#include "rlg_hip.h"
 
 namespace rlg {
 
@@ -55,21 +58,15 @@ __device__ __forceinline__ float step_keep(const uint8_t* dones, long long row) 
   return (dones && dones[row]) ? 0.0f : 1.0f;
 }
 
-// One problem's arguments, in the order of the single kernels' argument lists.  complete(): no required pointer is
-// NULL; shares_output(): a buffer this problem writes is the one the other writes under the same name.
+// One problem's arguments: the fields of the public descriptor (include/rlg_hip.h states them, in the order of the
+// single kernels' argument lists), under the name the paired kernels' symbols carry.  complete(): no required pointer
+// is NULL; shares_output(): a buffer this problem writes is the one the other writes under the same name;
+// positional(fn): fn(the fields as the single kernel takes them).
 static inline bool same_buffer(const void* p, const void* q) { return p != nullptr && p == q; }
 
-struct LstmFwdArgs {
-  float* gates;
-  const float* w_hh;
-  const float* h0;
-  const float* c0;
-  const uint8_t* dones;
-  float* out;
-  float* c_all;
-  float* hprev;
-  float* hT;
-  float* cT;
+struct LstmFwdArgs : rlg_lstm_fwd {
+  template <typename Fn>
+  int positional(Fn fn) const { return fn(gates, w_hh, h0, c0, dones, out, c_all, hprev, hT, cT); }
   bool complete() const { return gates && w_hh && h0 && c0 && out; }
   bool shares_output(const LstmFwdArgs& o) const {
     return same_buffer(gates, o.gates) || same_buffer(out, o.out) || same_buffer(c_all, o.c_all) ||
@@ -77,28 +74,16 @@ struct LstmFwdArgs {
   }
 };
 
-struct LstmBwdArgs {
-  const float* gates;
-  const float* c_all;
-  const float* c0;
-  const uint8_t* dones;
-  const float* w_hh;
-  const float* d_out;
-  float* d_gates;
+struct LstmBwdArgs : rlg_lstm_bwd {
+  template <typename Fn>
+  int positional(Fn fn) const { return fn(gates, c_all, c0, dones, w_hh, d_out, d_gates); }
   bool complete() const { return gates && c_all && c0 && w_hh && d_out && d_gates; }
   bool shares_output(const LstmBwdArgs& o) const { return same_buffer(d_gates, o.d_gates); }
 };
 
-struct GruFwdArgs {
-  float* gates;
-  const float* w_hh;
-  const float* b_hh;
-  const float* h0;
-  const uint8_t* dones;
-  float* out;
-  float* hn_all;
-  float* hprev;
-  float* hT;
+struct GruFwdArgs : rlg_gru_fwd {
+  template <typename Fn>
+  int positional(Fn fn) const { return fn(gates, w_hh, b_hh, h0, dones, out, hn_all, hprev, hT); }
   bool complete() const { return gates && w_hh && b_hh && h0 && out; }
   bool shares_output(const GruFwdArgs& o) const {
     return same_buffer(gates, o.gates) || same_buffer(out, o.out) || same_buffer(hn_all, o.hn_all) ||
@@ -106,15 +91,9 @@ struct GruFwdArgs {
   }
 };
 
-struct GruBwdArgs {
-  const float* gates;
-  const float* hn_all;
-  const float* hprev;
-  const uint8_t* dones;
-  const float* w_hh;
-  const float* d_out;
-  float* d_gx;
-  float* d_gh;
+struct GruBwdArgs : rlg_gru_bwd {
+  template <typename Fn>
+  int positional(Fn fn) const { return fn(gates, hn_all, hprev, dones, w_hh, d_out, d_gx, d_gh); }
   bool complete() const { return gates && hn_all && hprev && w_hh && d_out && d_gx && d_gh; }
   bool shares_output(const GruBwdArgs& o) const { return same_buffer(d_gx, o.d_gx) || same_buffer(d_gh, o.d_gh); }
 };
@@ -342,60 +321,78 @@ static int seq_per_block(int S, int H) {
   return sb;
 }
 
-// A kernel family F (one cell, one direction) gives: F::kernel<H, SB>, the narrow kernel; F::lds_floats(H, SB), its
-// dynamic LDS; F::wide(args..., S, T, stream), the 128-unit launcher; and for paired launches (Pair: args are the two
-// problems' *Args) F::pair_kernel<H, SB> and F::wide_pair(a, b, S, T, stream).
-template <typename F, int H, int SB, bool Pair, typename... Args>
-static int launch_narrow_sb(int S, int T, hipStream_t st, Args... args) {
+// One or two problems on one kernel pair: the single kernel takes problem 0's fields as positional arguments, the
+// paired kernel both problems by value; grid and LDS are those of ONE problem either way.
+template <auto Kernel, auto PairKernel, typename A>
+static int launch_problems(const A* p, int count, int S, int T, int sb, int threads, size_t shm, hipStream_t st) {
+  if (count == 2) return launch_tile<PairKernel, 2>(S, sb, threads, shm, st, p[0], p[1], S, T);
+  return p[0].positional([&](auto... field) { return launch_tile<Kernel>(S, sb, threads, shm, st, field..., S, T); });
+}
+
+// The wide forms' 16-byte rule for w_hh, on each problem
+template <typename A>
+static bool wide_aligned(const A* p, int count) {
+  uintptr_t bits = 0;
+  for (int i = 0; i < count; ++i) bits |= reinterpret_cast<uintptr_t>(p[i].w_hh);
+  return (bits & 15u) == 0;
+}
+
+// A kernel family F (one cell, one direction) gives: F::Args, its problems' type; F::kernel<H, SB> and
+// F::pair_kernel<H, SB>, the narrow kernels; F::lds_floats(H, SB), their dynamic LDS; F::wide(problems, count, S, T,
+// stream), the 128-unit launcher.
+template <typename F, int H, int SB>
+static int launch_narrow_sb(const typename F::Args* p, int count, int S, int T, hipStream_t st) {
   if constexpr (SB < kSeqThreads / H) {
     return static_cast<int>(hipErrorInvalidValue);
-  } else if constexpr (Pair) {
-    return launch_tile<F::template pair_kernel<H, SB>, 2>(S, SB, kSeqThreads, F::lds_floats(H, SB) * sizeof(float), st,
-                                                          args..., S, T);
   } else {
-    return launch_tile<F::template kernel<H, SB>>(S, SB, kSeqThreads, F::lds_floats(H, SB) * sizeof(float), st,
-                                                  args..., S, T);
+    return launch_problems<F::template kernel<H, SB>, F::template pair_kernel<H, SB>>(
+        p, count, S, T, SB, kSeqThreads, F::lds_floats(H, SB) * sizeof(float), st);
   }
 }
 
-template <typename F, int H, bool Pair, typename... Args>
-static int launch_narrow(int S, int T, hipStream_t st, Args... args) {
+template <typename F, int H>
+static int launch_narrow(const typename F::Args* p, int count, int S, int T, hipStream_t st) {
   switch (seq_per_block(S, H)) {                        // S of ONE problem, also for a pair
-    case 16: return launch_narrow_sb<F, H, 16, Pair>(S, T, st, args...);
-    case 8: return launch_narrow_sb<F, H, 8, Pair>(S, T, st, args...);
-    default: return launch_narrow_sb<F, H, 4, Pair>(S, T, st, args...);
+    case 16: return launch_narrow_sb<F, H, 16>(p, count, S, T, st);
+    case 8: return launch_narrow_sb<F, H, 8>(p, count, S, T, st);
+    default: return launch_narrow_sb<F, H, 4>(p, count, S, T, st);
   }
 }
 
-// The wide forms' 16-byte rule for w_hh, for both problems of a paired launch
-static bool wide_pair_aligned(const float* w_hh_a, const float* w_hh_b) {
-  return ((reinterpret_cast<uintptr_t>(w_hh_a) | reinterpret_cast<uintptr_t>(w_hh_b)) & 15u) == 0;
+// A file's kernels stand in its code object in the order of their first use.  lstm.hip and gru.hip assert this for
+// their forward and backward family in front of their entry points: that names F's single kernels, in the order
+// launch_narrow reaches them, ahead of every paired kernel - the order the files have always had - so that a change on
+// the host side leaves a file's disassembly comparable hash for hash (profiles/rnn_seq_descriptors.txt).
+template <typename F>
+constexpr bool single_kernels_first() {
+  return F::template kernel<16, 16> && F::template kernel<32, 16> && F::template kernel<32, 8> &&
+         F::template kernel<64, 16> && F::template kernel<64, 8> && F::template kernel<64, 4>;
 }
 
 static bool seq_hidden_supported(int hidden) { return hidden == 16 || hidden == 32 || hidden == 64 || hidden == 128; }
 
-template <typename F, bool Pair = false, typename... Args>
-static int launch_seq(int hidden, int S, int T, hipStream_t st, Args... args) {
-  switch (hidden) {
-    case 16: return launch_narrow<F, 16, Pair>(S, T, st, args...);
-    case 32: return launch_narrow<F, 32, Pair>(S, T, st, args...);
-    case 64: return launch_narrow<F, 64, Pair>(S, T, st, args...);
-    case 128:
-      if constexpr (Pair) {
-        return F::wide_pair(args..., S, T, st);
-      } else {
-        return F::wide(args..., S, T, st);
-      }
-    default: return static_cast<int>(hipErrorInvalidValue);
+// The four entry points: `count` (1 or 2) problems of one shape.  Everything is checked here, on the host, before the
+// runtime is asked for anything; the wide launchers' alignment rule comes last.
+template <typename F, typename D>
+static int launch_seq(const D* problems, int count, int hidden, int S, int T, void* stream) {
+  using A = typename F::Args;
+  static_assert(std::is_base_of_v<D, A> && sizeof(A) == sizeof(D), "F::Args is the public descriptor and nothing else");
+  constexpr int invalid = static_cast<int>(hipErrorInvalidValue);
+  if (problems == nullptr || (count != 1 && count != 2)) return invalid;
+  if (S <= 0 || T <= 0 || !seq_hidden_supported(hidden)) return invalid;
+  A p[2] = {};
+  for (int i = 0; i < count; ++i) {
+    static_cast<D&>(p[i]) = problems[i];
+    if (!p[i].complete()) return invalid;
   }
-}
-
-// The paired entry points: everything is checked here, on the host, before the runtime is asked for anything.
-template <typename F, typename A>
-static int launch_seq_pair(int hidden, int S, int T, hipStream_t st, const A& a, const A& b) {
-  if (S <= 0 || T <= 0 || !seq_hidden_supported(hidden)) return static_cast<int>(hipErrorInvalidValue);
-  if (!a.complete() || !b.complete() || a.shares_output(b)) return static_cast<int>(hipErrorInvalidValue);
-  return launch_seq<F, true>(hidden, S, T, st, a, b);
+  if (count == 2 && p[0].shares_output(p[1])) return invalid;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  switch (hidden) {
+    case 16: return launch_narrow<F, 16>(p, count, S, T, st);
+    case 32: return launch_narrow<F, 32>(p, count, S, T, st);
+    case 64: return launch_narrow<F, 64>(p, count, S, T, st);
+    default: return F::wide(p, count, S, T, st);        // 128
+  }
 }
 
 }  // namespace rlg

@@ -1419,7 +1419,89 @@ class MlpDwPlan:
         return nfin.value
 
 
-# ------------------------------------------------------------------ recurrent policy (LSTM)
+# ------------------------------------------------------------------ recurrent policy (LSTM, GRU)
+
+# One problem's descriptor (_lib.LstmFwd, ...) from the arguments of the wrapper below it: the shapes that must agree
+# with gates, then _need or _opt per field, in the descriptor's order.
+
+def _lstm_fwd(gates, w_hh, h0, c0, dones, out, c_all=None, hprev=None, h_final=None, c_final=None):
+    G = gates.shape[1]
+    H = G // 4
+    if G != 4 * H or tuple(w_hh.shape) != (G, H) or out.shape != (gates.shape[0], H):
+        raise ValueError(f'gates [rows, 4H], w_hh [4H, H] and out [rows, H] do not agree: {tuple(gates.shape)}, '
+                         f'{tuple(w_hh.shape)}, {tuple(out.shape)}')
+    return _lib.LstmFwd(_need(gates, F32, 'gates'), _need(w_hh, F32, 'w_hh'), _need(h0, F32, 'h0'),
+                        _need(c0, F32, 'c0'), _opt(dones, torch.uint8, 'dones'), _need(out, F32, 'out'),
+                        _opt(c_all, F32, 'c_all'), _opt(hprev, F32, 'hprev'), _opt(h_final, F32, 'h_final'),
+                        _opt(c_final, F32, 'c_final'))
+
+
+def _lstm_bwd(gates, c_all, c0, dones, w_hh, d_out, d_gates):
+    G = gates.shape[1]
+    H = G // 4
+    if G != 4 * H or tuple(w_hh.shape) != (G, H) or d_gates.shape != gates.shape:
+        raise ValueError(f'gates / d_gates [rows, 4H] and w_hh [4H, H] do not agree: {tuple(gates.shape)}, '
+                         f'{tuple(d_gates.shape)}, {tuple(w_hh.shape)}')
+    return _lib.LstmBwd(_need(gates, F32, 'gates'), _need(c_all, F32, 'c_all'), _need(c0, F32, 'c0'),
+                        _opt(dones, torch.uint8, 'dones'), _need(w_hh, F32, 'w_hh'), _need(d_out, F32, 'd_out'),
+                        _need(d_gates, F32, 'd_gates'))
+
+
+def _gru_fwd(gates, w_hh, b_hh, h0, dones, out, hn_all=None, hprev=None, h_final=None):
+    G = gates.shape[1]
+    H = G // 3
+    if G != 3 * H or tuple(w_hh.shape) != (G, H) or b_hh.numel() != G:
+        raise ValueError(f'gates [rows, 3H], w_hh [3H, H] and b_hh [3H] do not agree: {tuple(gates.shape)}, '
+                         f'{tuple(w_hh.shape)}, {tuple(b_hh.shape)}')
+    return _lib.GruFwd(_need(gates, F32, 'gates'), _need(w_hh, F32, 'w_hh'), _need(b_hh, F32, 'b_hh'),
+                       _need(h0, F32, 'h0'), _opt(dones, torch.uint8, 'dones'), _need(out, F32, 'out'),
+                       _opt(hn_all, F32, 'hn_all'), _opt(hprev, F32, 'hprev'), _opt(h_final, F32, 'h_final'))
+
+
+def _gru_bwd(gates, hn_all, hprev, dones, w_hh, d_out, d_gx, d_gh):
+    G = gates.shape[1]
+    H = G // 3
+    if G != 3 * H or tuple(w_hh.shape) != (G, H) or d_gx.shape != gates.shape or d_gh.shape != gates.shape:
+        raise ValueError(f'gates / d_gx / d_gh [rows, 3H] and w_hh [3H, H] do not agree: {tuple(gates.shape)}, '
+                         f'{tuple(d_gx.shape)}, {tuple(d_gh.shape)}, {tuple(w_hh.shape)}')
+    return _lib.GruBwd(_need(gates, F32, 'gates'), _need(hn_all, F32, 'hn_all'), _need(hprev, F32, 'hprev'),
+                       _opt(dones, torch.uint8, 'dones'), _need(w_hh, F32, 'w_hh'), _need(d_out, F32, 'd_out'),
+                       _need(d_gx, F32, 'd_gx'), _need(d_gh, F32, 'd_gh'))
+
+
+# (cell, direction): the entry, one problem's descriptor from its arguments, an array of two, the gates per unit
+_RNN_SEQ = {
+    ('lstm', 'forward'): ('rlg_lstm_seq_forward', _lstm_fwd, _lib.LstmFwd * 2, 4),
+    ('lstm', 'backward'): ('rlg_lstm_seq_backward', _lstm_bwd, _lib.LstmBwd * 2, 4),
+    ('gru', 'forward'): ('rlg_gru_seq_forward', _gru_fwd, _lib.GruFwd * 2, 3),
+    ('gru', 'backward'): ('rlg_gru_seq_backward', _gru_bwd, _lib.GruBwd * 2, 3),
+}
+
+
+def rnn_seq(cell, direction, problems, seq_len):
+    """One sequence launch: cell 'lstm' / 'gru', direction 'forward' / 'backward', on one or two problems - each the
+    arguments of {cell}_seq_{direction} below in its order, without seq_len, as a tuple.  Two problems have one shape
+    and run in ONE launch (twice the workgroups; bit-identical to the two single launches); dones and the optional
+    outputs may be given for one problem and not for the other.  No output buffer may be shared.
+    (The four single-problem wrappers below make the same call for one problem without the way through the table: a
+    T = 1 launch is host-bound, and they are what a caller outside a captured graph uses.)"""
+    entry, describe, pair_type, gates_per_unit = _RNN_SEQ[cell, direction]
+    n = len(problems)
+    if n != 1 and n != 2:
+        raise ValueError(f'{entry}: one or two problems, {n} given')
+    gates = problems[0][0]
+    if n == 2:
+        descs = pair_type(describe(*problems[0]), describe(*problems[1]))
+        if problems[1][0].shape != gates.shape:
+            raise ValueError(f'a paired launch needs two problems of one shape: gates {tuple(gates.shape)} and '
+                             f'{tuple(problems[1][0].shape)}')
+    B, G = gates.shape
+    if (B // seq_len) * seq_len != B:
+        raise ValueError(f'rows ({B}) must be a multiple of seq_len ({seq_len})')
+    if n == 1:
+        descs = ctypes.byref(describe(*problems[0]))
+    _lib.check(getattr(_lib.load(), entry)(descs, n, B // seq_len, seq_len, G // gates_per_unit, _stream(gates)), entry)
+
 
 def lstm_supported(hidden):
     """16, 32, 64 (W_hh in LDS, csrc/lstm.hip) and 128 (W_hh in registers as MFMA fragments, csrc/lstm_wide.hip)."""
@@ -1432,79 +1514,24 @@ def lstm_seq_forward(gates, w_hh, h0, c0, dones, out, c_all=None, hprev=None, h_
     c_all / hprev [S*T, H] (cell states, state entering each step after the reset) are kept for backward when given,
     h_final / c_final [S, H] likewise.  H must satisfy lstm_supported: csrc/lstm.hip (16/32/64) or
     csrc/lstm_wide.hip (128, w_hh 16-byte aligned)."""
-    lib = _lib.load()
     B, G = gates.shape
-    H = G // 4
-    S = B // seq_len
-    if S * seq_len != B:
+    if (B // seq_len) * seq_len != B:
         raise ValueError(f'rows ({B}) must be a multiple of seq_len ({seq_len})')
-    ptrs = _lstm_forward_pointers(gates, w_hh, h0, c0, dones, out, c_all, hprev, h_final, c_final)
-    _lib.check(lib.rlg_lstm_seq_forward(*ptrs, S, seq_len, H, _stream(gates)), 'rlg_lstm_seq_forward')
+    desc = _lstm_fwd(gates, w_hh, h0, c0, dones, out, c_all, hprev, h_final, c_final)
+    _lib.check(_lib.load().rlg_lstm_seq_forward(ctypes.byref(desc), 1, B // seq_len, seq_len, G // 4, _stream(gates)),
+               'rlg_lstm_seq_forward')
 
 
 def lstm_seq_backward(gates, c_all, c0, dones, w_hh, d_out, d_gates, seq_len):
     """d_gates [S*T, 4H] = d loss / d gate pre-activations from d_out [S*T, H] and what lstm_seq_forward kept.
     Same widths as lstm_seq_forward; the weight gradients are whole-sequence products of d_gates outside."""
-    lib = _lib.load()
     B, G = gates.shape
     if (B // seq_len) * seq_len != B:
         raise ValueError(f'rows ({B}) must be a multiple of seq_len ({seq_len})')
-    ptrs = _lstm_backward_pointers(gates, c_all, c0, dones, w_hh, d_out, d_gates)
-    _lib.check(lib.rlg_lstm_seq_backward(*ptrs, B // seq_len, seq_len, G // 4, _stream(gates)), 'rlg_lstm_seq_backward')
+    desc = _lstm_bwd(gates, c_all, c0, dones, w_hh, d_out, d_gates)
+    _lib.check(_lib.load().rlg_lstm_seq_backward(ctypes.byref(desc), 1, B // seq_len, seq_len, G // 4, _stream(gates)),
+               'rlg_lstm_seq_backward')
 
-
-def _pair_shape(a_gates, b_gates, gates_per_unit, seq_len):
-    """(S, H) of a paired launch: the two problems have one shape."""
-    if a_gates.shape != b_gates.shape:
-        raise ValueError(f'a paired launch needs two problems of one shape: gates {tuple(a_gates.shape)} and '
-                         f'{tuple(b_gates.shape)}')
-    B, G = a_gates.shape
-    if (B // seq_len) * seq_len != B:
-        raise ValueError(f'rows ({B}) must be a multiple of seq_len ({seq_len})')
-    return B // seq_len, G // gates_per_unit
-
-
-def _lstm_forward_pointers(gates, w_hh, h0, c0, dones, out, c_all=None, hprev=None, h_final=None, c_final=None):
-    G = gates.shape[1]
-    H = G // 4
-    if G != 4 * H or tuple(w_hh.shape) != (G, H) or out.shape != (gates.shape[0], H):
-        raise ValueError(f'gates [rows, 4H], w_hh [4H, H] and out [rows, H] do not agree: {tuple(gates.shape)}, '
-                         f'{tuple(w_hh.shape)}, {tuple(out.shape)}')
-    return (_need(gates, F32, 'gates'), _need(w_hh, F32, 'w_hh'), _need(h0, F32, 'h0'), _need(c0, F32, 'c0'),
-            _opt(dones, torch.uint8, 'dones'), _need(out, F32, 'out'), _opt(c_all, F32, 'c_all'),
-            _opt(hprev, F32, 'hprev'), _opt(h_final, F32, 'h_final'), _opt(c_final, F32, 'c_final'))
-
-
-def _lstm_backward_pointers(gates, c_all, c0, dones, w_hh, d_out, d_gates):
-    G = gates.shape[1]
-    H = G // 4
-    if G != 4 * H or tuple(w_hh.shape) != (G, H) or d_gates.shape != gates.shape:
-        raise ValueError(f'gates / d_gates [rows, 4H] and w_hh [4H, H] do not agree: {tuple(gates.shape)}, '
-                         f'{tuple(d_gates.shape)}, {tuple(w_hh.shape)}')
-    return (_need(gates, F32, 'gates'), _need(c_all, F32, 'c_all'), _need(c0, F32, 'c0'),
-            _opt(dones, torch.uint8, 'dones'), _need(w_hh, F32, 'w_hh'), _need(d_out, F32, 'd_out'),
-            _need(d_gates, F32, 'd_gates'))
-
-
-def lstm_seq_forward_pair(a, b, seq_len=1):
-    """Two lstm_seq_forward problems of one shape in ONE launch (twice the workgroups; bit-identical to the two single
-    launches).  a, b: one problem each, the arguments of lstm_seq_forward in its order, without seq_len, as a tuple;
-    dones and the optional outputs may be given for one problem and not for the other.  No output buffer may be shared."""
-    lib = _lib.load()
-    pa, pb = _lstm_forward_pointers(*a), _lstm_forward_pointers(*b)
-    S, H = _pair_shape(a[0], b[0], 4, seq_len)
-    _lib.check(lib.rlg_lstm_seq_forward_pair(*pa, *pb, S, seq_len, H, _stream(a[0])), 'rlg_lstm_seq_forward_pair')
-
-
-def lstm_seq_backward_pair(a, b, seq_len):
-    """Two lstm_seq_backward problems of one shape in one launch; a, b as for lstm_seq_forward_pair."""
-    lib = _lib.load()
-    pa, pb = _lstm_backward_pointers(*a), _lstm_backward_pointers(*b)
-    S, H = _pair_shape(a[0], b[0], 4, seq_len)
-    _lib.check(lib.rlg_lstm_seq_backward_pair(*pa, *pb, S, seq_len, H, _stream(a[0])), 'rlg_lstm_seq_backward_pair')
-
-
-# ------------------------------------------------------------------ recurrent policy (GRU)
 
 def gru_supported(hidden):
     """16, 32, 64 (W_hh in LDS, csrc/gru.hip) and 128 (W_hh in registers as MFMA fragments, csrc/gru_wide.hip)."""
@@ -1516,68 +1543,42 @@ def gru_seq_forward(gates, w_hh, b_hh, h0, dones, out, hn_all=None, hprev=None, 
     hn_all / hprev [S*T, H] (W_hn h + b_hn before the gating by r, state entering each step after the reset) are kept
     for backward when given, h_final [S, H] likewise.  H must satisfy gru_supported: csrc/gru.hip (16/32/64) or
     csrc/gru_wide.hip (128, w_hh 16-byte aligned)."""
-    lib = _lib.load()
     B, G = gates.shape
-    H = G // 3
-    S = B // seq_len
-    if S * seq_len != B:
+    if (B // seq_len) * seq_len != B:
         raise ValueError(f'rows ({B}) must be a multiple of seq_len ({seq_len})')
-    ptrs = _gru_forward_pointers(gates, w_hh, b_hh, h0, dones, out, hn_all, hprev, h_final)
-    _lib.check(lib.rlg_gru_seq_forward(*ptrs, S, seq_len, H, _stream(gates)), 'rlg_gru_seq_forward')
+    desc = _gru_fwd(gates, w_hh, b_hh, h0, dones, out, hn_all, hprev, h_final)
+    _lib.check(_lib.load().rlg_gru_seq_forward(ctypes.byref(desc), 1, B // seq_len, seq_len, G // 3, _stream(gates)),
+               'rlg_gru_seq_forward')
 
 
 def gru_seq_backward(gates, hn_all, hprev, dones, w_hh, d_out, d_gx, d_gh, seq_len):
     """From d_out [S*T, H] and what gru_seq_forward kept: d_gx [S*T, 3H] = (dr_pre, dz_pre, dn_pre), the gradient of
     x W_ih^T + b_ih, and d_gh [S*T, 3H] = (dr_pre, dz_pre, dn_pre * r), the gradient of h W_hh^T + b_hh.  The weight
     gradients are whole-sequence products of the two outside (dW_ih = d_gx^T x, dW_hh = d_gh^T hprev)."""
-    lib = _lib.load()
     B, G = gates.shape
-    H = G // 3
-    S = B // seq_len
-    if S * seq_len != B:
+    if (B // seq_len) * seq_len != B:
         raise ValueError(f'rows ({B}) must be a multiple of seq_len ({seq_len})')
-    ptrs = _gru_backward_pointers(gates, hn_all, hprev, dones, w_hh, d_out, d_gx, d_gh)
-    _lib.check(lib.rlg_gru_seq_backward(*ptrs, S, seq_len, H, _stream(gates)), 'rlg_gru_seq_backward')
+    desc = _gru_bwd(gates, hn_all, hprev, dones, w_hh, d_out, d_gx, d_gh)
+    _lib.check(_lib.load().rlg_gru_seq_backward(ctypes.byref(desc), 1, B // seq_len, seq_len, G // 3, _stream(gates)),
+               'rlg_gru_seq_backward')
 
 
-def _gru_forward_pointers(gates, w_hh, b_hh, h0, dones, out, hn_all=None, hprev=None, h_final=None):
-    G = gates.shape[1]
-    H = G // 3
-    if G != 3 * H or tuple(w_hh.shape) != (G, H) or b_hh.numel() != G:
-        raise ValueError(f'gates [rows, 3H], w_hh [3H, H] and b_hh [3H] do not agree: {tuple(gates.shape)}, '
-                         f'{tuple(w_hh.shape)}, {tuple(b_hh.shape)}')
-    return (_need(gates, F32, 'gates'), _need(w_hh, F32, 'w_hh'), _need(b_hh, F32, 'b_hh'), _need(h0, F32, 'h0'),
-            _opt(dones, torch.uint8, 'dones'), _need(out, F32, 'out'), _opt(hn_all, F32, 'hn_all'),
-            _opt(hprev, F32, 'hprev'), _opt(h_final, F32, 'h_final'))
+# Two problems of one shape in ONE launch, a and b each a tuple as rnn_seq takes it: the names under which
+# tests/test_rnn_pair_gpu.py makes its paired launches; everything else calls rnn_seq.
+def lstm_seq_forward_pair(a, b, seq_len=1):
+    rnn_seq('lstm', 'forward', (a, b), seq_len)
 
 
-def _gru_backward_pointers(gates, hn_all, hprev, dones, w_hh, d_out, d_gx, d_gh):
-    G = gates.shape[1]
-    H = G // 3
-    if G != 3 * H or tuple(w_hh.shape) != (G, H) or d_gx.shape != gates.shape or d_gh.shape != gates.shape:
-        raise ValueError(f'gates / d_gx / d_gh [rows, 3H] and w_hh [3H, H] do not agree: {tuple(gates.shape)}, '
-                         f'{tuple(d_gx.shape)}, {tuple(d_gh.shape)}, {tuple(w_hh.shape)}')
-    return (_need(gates, F32, 'gates'), _need(hn_all, F32, 'hn_all'), _need(hprev, F32, 'hprev'),
-            _opt(dones, torch.uint8, 'dones'), _need(w_hh, F32, 'w_hh'), _need(d_out, F32, 'd_out'),
-            _need(d_gx, F32, 'd_gx'), _need(d_gh, F32, 'd_gh'))
+def lstm_seq_backward_pair(a, b, seq_len):
+    rnn_seq('lstm', 'backward', (a, b), seq_len)
 
 
 def gru_seq_forward_pair(a, b, seq_len=1):
-    """Two gru_seq_forward problems of one shape in ONE launch (twice the workgroups; bit-identical to the two single
-    launches).  a, b: one problem each, the arguments of gru_seq_forward in its order, without seq_len, as a tuple;
-    dones and the optional outputs may be given for one problem and not for the other.  No output buffer may be shared."""
-    lib = _lib.load()
-    pa, pb = _gru_forward_pointers(*a), _gru_forward_pointers(*b)
-    S, H = _pair_shape(a[0], b[0], 3, seq_len)
-    _lib.check(lib.rlg_gru_seq_forward_pair(*pa, *pb, S, seq_len, H, _stream(a[0])), 'rlg_gru_seq_forward_pair')
+    rnn_seq('gru', 'forward', (a, b), seq_len)
 
 
 def gru_seq_backward_pair(a, b, seq_len):
-    """Two gru_seq_backward problems of one shape in one launch; a, b as for gru_seq_forward_pair."""
-    lib = _lib.load()
-    pa, pb = _gru_backward_pointers(*a), _gru_backward_pointers(*b)
-    S, H = _pair_shape(a[0], b[0], 3, seq_len)
-    _lib.check(lib.rlg_gru_seq_backward_pair(*pa, *pb, S, seq_len, H, _stream(a[0])), 'rlg_gru_seq_backward_pair')
+    rnn_seq('gru', 'backward', (a, b), seq_len)
 
 
 # ------------------------------------------------------------------ layer norm behind the recurrent layer

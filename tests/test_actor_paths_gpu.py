@@ -7,7 +7,10 @@ folded (_fold); the comparison leaves out the host-side size queries (_launches)
 objects, so they pin what that refactor had to keep: no launch added, dropped or reordered on any path, eager or captured.
 The recording is the parent's, byte for byte, with ONE difference made on reading it (RETIRED): the three one-shot setters
 that announced gradient maxima and timing events to the NEXT launch are gone - those arguments travel in the launches' own
-descriptors - so their names are taken out of the recorded lists, and nothing else is.
+descriptors - so their names are taken out of the recorded lists, and nothing else is.  And ONE renaming (RENAMED): a
+paired sequence launch is a call of the single entry's name with two problems, so rlg_lstm_seq_forward_pair /
+rlg_lstm_seq_backward_pair are read as rlg_lstm_seq_forward / rlg_lstm_seq_backward; a paired launch stays ONE call
+where two single launches are two, so the order check keeps its force.
 A change that moves a launch on purpose records them again:
 
     python tests/test_actor_paths_gpu.py --record tests/golden/actor_path_traces.json [--digests digests.txt]
@@ -34,6 +37,8 @@ N, HZ, T, MB = 64, 8, 4, 256          # 64 envs x horizon 8 in sequences of 4: t
 RNN16 = {'name': 'lstm', 'units': 16, 'layers': 1}
 # entries of the recording that the library no longer has
 RETIRED = {'rlg_mlp_chain_gradient_maxima', 'rlg_mlp_dw_gradient_maxima', 'rlg_mlp_chain_time_next'}
+# entries of the recording that the library has under another name
+RENAMED = {'rlg_lstm_seq_forward_pair': 'rlg_lstm_seq_forward', 'rlg_lstm_seq_backward_pair': 'rlg_lstm_seq_backward'}
 
 
 class _Recorder:
@@ -249,7 +254,8 @@ def _write_traces(path, traces):
 def traces():
     with open(TRACES) as f:
         data = json.load(f)
-    return {case: [n for n in (data['names'][i] for i in _unfold(t)) if n not in RETIRED] for case, t in data['traces'].items()}
+    return {case: [RENAMED.get(n, n) for n in (data['names'][i] for i in _unfold(t)) if n not in RETIRED]
+            for case, t in data['traces'].items()}
 
 
 def test_every_case_has_a_recorded_trace(traces):

@@ -1,19 +1,23 @@
-"""CPU: what the four paired sequence entry points answer to malformed calls.
+"""CPU: what the four sequence entry points answer to malformed calls.
 
-rlg_lstm_seq_forward_pair / _backward_pair and rlg_gru_seq_forward_pair / _backward_pair take the argument set of
-their single entry twice (problem A, problem B) and one shape.  They check everything on the host and answer
-hipErrorInvalidValue before they ask the HIP runtime for anything: an unsupported width, S or T <= 0, a NULL required
-pointer in either problem, a w_hh of either problem that breaks the 128-unit forms' 16-byte rule, an output buffer of
-A that is also the same-named buffer of B.  The pointers are small fake aligned addresses - the host code
+rlg_lstm_seq_forward / _backward and rlg_gru_seq_forward / _backward take an array of one or two problem descriptors
+and one shape.  They check everything on the host and answer hipErrorInvalidValue before they ask the HIP runtime for
+anything: a NULL array or a count other than 1 or 2, an unsupported width, S or T <= 0, a NULL required pointer in any
+problem, a w_hh of any problem that breaks the 128-unit forms' 16-byte rule and, with two problems, an output buffer
+of A that is also the same-named buffer of B.  The pointers are small fake aligned addresses - the host code
 dereferences none of them.
 
 The table runs in a child process that sees no GPU, as tests/test_chain_entry_errors_cpu.py does: should a row ever
 get past validation, its launch fails there, with the runtime's own code, instead of handing fake addresses to a
-device.  One well-formed call per entry shows that code: it is not hipErrorInvalidValue, so a row that answers
-hipErrorInvalidValue was stopped by the checks.
+device.  One well-formed call per entry and count shows that code: it is not hipErrorInvalidValue, so a row that
+answers hipErrorInvalidValue was stopped by the checks.
 
-rlg_lstm_seq_backward_pair has no alignment row: launch_lstm_bwd_wide does not check w_hh (csrc/rnn_seq.hpp's list
-of asymmetries) and the paired form inherits that.
+rlg_lstm_seq_backward has no alignment rule: launch_lstm_bwd_wide does not check w_hh (csrc/rnn_seq.hpp's list of
+asymmetries), with one problem or two; its off-alignment rows are "not rejected".
+
+The fields' positions come from the ctypes mirrors of the descriptors (rl_games_amd/_lib.py); which of them are
+required and which are written is stated here, by name, so a mirror whose order is not the header's fails the rows of
+the fields it misplaces.
 """
 import json
 import os
@@ -24,26 +28,31 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 INVALID = 1
 
-# argument names of ONE problem, in ABI order; '?' marks the optional ones, '>' the buffers the kernel writes
-_PROBLEM = {
-    'rlg_lstm_seq_forward_pair': '>gates w_hh h0 c0 ?dones >out ?>c_all ?>hprev ?>h_final ?>c_final',
-    'rlg_lstm_seq_backward_pair': 'gates c_all c0 ?dones w_hh d_out >d_gates',
-    'rlg_gru_seq_forward_pair': '>gates w_hh b_hh h0 ?dones >out ?>hn_all ?>hprev ?>h_final',
-    'rlg_gru_seq_backward_pair': 'gates hn_all hprev ?dones w_hh d_out >d_gx >d_gh',
+# entry: (descriptor class of _lib, the optional fields, the buffers the kernel writes)
+_ENTRIES = {
+    'rlg_lstm_seq_forward': ('LstmFwd', 'dones c_all hprev hT cT', 'gates out c_all hprev hT cT'),
+    'rlg_lstm_seq_backward': ('LstmBwd', 'dones', 'd_gates'),
+    'rlg_gru_seq_forward': ('GruFwd', 'dones hn_all hprev hT', 'gates out hn_all hprev hT'),
+    'rlg_gru_seq_backward': ('GruBwd', 'dones', 'd_gx d_gh'),
 }
-_ALIGNED_W_HH = ('rlg_lstm_seq_forward_pair', 'rlg_gru_seq_forward_pair', 'rlg_gru_seq_backward_pair')
+_ALIGNED_W_HH = ('rlg_lstm_seq_forward', 'rlg_gru_seq_forward', 'rlg_gru_seq_backward')
+
+
+def _descriptor(entry):
+    from rl_games_amd import _lib
+    return getattr(_lib, _ENTRIES[entry][0])
 
 
 def _names(entry):
-    return [n.lstrip('?>') for n in _PROBLEM[entry].split()]
+    return [n for n, _ in _descriptor(entry)._fields_]
 
 
 def _required(entry):
-    return [n.lstrip('>') for n in _PROBLEM[entry].split() if not n.startswith('?')]
+    return [n for n in _names(entry) if n not in _ENTRIES[entry][1].split()]
 
 
 def _outputs(entry):
-    return [n.lstrip('?>') for n in _PROBLEM[entry].split() if '>' in n]
+    return [n for n in _names(entry) if n in _ENTRIES[entry][2].split()]
 
 
 def _problem(entry, which):
@@ -52,12 +61,14 @@ def _problem(entry, which):
 
 
 def _rows():
-    """(id, entry, A overrides, B overrides, shape overrides, rejected)"""
+    """(id, entry, num_problems, A overrides, B overrides, shape overrides, rejected); the shape override
+    `no_array` passes NULL for the descriptor array"""
     t = []
-    for e in _PROBLEM:
-        def row(name, a=None, b=None, rejected=True, **shape):
-            t.append((f'{e}: {name}', e, a or {}, b or {}, shape, rejected))
+    for e in _ENTRIES:
+        def row(name, count=2, a=None, b=None, rejected=True, **shape):
+            t.append((f'{e}: {name}', e, count, a or {}, b or {}, shape, rejected))
 
+        # two problems
         row('well formed (reaches the runtime)', rejected=False)
         for h in (0, 12, 24, 48, 96, 256):
             row(f'width {h}', hidden=h)
@@ -75,6 +86,26 @@ def _rows():
         if e in _ALIGNED_W_HH:
             row('A: w_hh 4 bytes off at 128 units', a={'w_hh': _problem(e, 0)['w_hh'] + 4}, hidden=128)
             row('B: w_hh 8 bytes off at 128 units', b={'w_hh': _problem(e, 1)['w_hh'] + 8}, hidden=128)
+
+        # one problem
+        row('single: well formed (reaches the runtime)', 1, rejected=False)
+        for h in (0, 12, 24, 48, 96, 256):
+            row(f'single: width {h}', 1, hidden=h)
+        row('single: S = 0', 1, num_seqs=0)
+        row('single: S < 0', 1, num_seqs=-3)
+        row('single: T = 0', 1, seq_len=0)
+        row('single: T < 0', 1, seq_len=-1)
+        for n in _required(e):
+            row(f'single: without {n}', 1, a={n: None})
+            row(f'single: without {n} at 128 units', 1, a={n: None}, hidden=128)
+        row('single: w_hh 4 bytes off at 128 units', 1, a={'w_hh': _problem(e, 0)['w_hh'] + 4}, hidden=128,
+            rejected=e in _ALIGNED_W_HH)
+
+        # the array itself
+        row('no array', 1, no_array=True)
+        row('0 problems', 0)
+        row('3 problems', 3)
+        row('-1 problems', -1)
     return t
 
 
@@ -84,12 +115,15 @@ def run_table():
     from rl_games_amd import _lib
     lib = _lib.load()
     codes = {}
-    for name, entry, a_over, b_over, shape, _ in _rows():
+    for name, entry, count, a_over, b_over, shape, _ in _rows():
         assert name not in codes, name
-        a, b = dict(_problem(entry, 0), **a_over), dict(_problem(entry, 1), **b_over)
-        dims = dict(dict(num_seqs=5, seq_len=4, hidden=64), **shape)
-        args = [a[n] for n in _names(entry)] + [b[n] for n in _names(entry)]
-        codes[name] = getattr(lib, entry)(*args, dims['num_seqs'], dims['seq_len'], dims['hidden'], None)
+        problems = (_descriptor(entry) * 2)()
+        for desc, fields in zip(problems, (dict(_problem(entry, 0), **a_over), dict(_problem(entry, 1), **b_over))):
+            for n, v in fields.items():
+                setattr(desc, n, v)
+        dims = dict(dict(num_seqs=5, seq_len=4, hidden=64, no_array=False), **shape)
+        codes[name] = getattr(lib, entry)(None if dims['no_array'] else problems, count, dims['num_seqs'],
+                                          dims['seq_len'], dims['hidden'], None)
     return codes
 
 
@@ -102,7 +136,7 @@ def test_malformed_paired_calls_are_rejected_on_the_host():
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     codes = json.loads(out.stdout.strip().splitlines()[-1])
     rows = _rows()
-    assert len(rows) >= 140
+    assert len(rows) >= 257
     assert set(codes) == {r[0] for r in rows}
     wrong = {name: codes[name] for name, *_, rejected in rows if (codes[name] == INVALID) != rejected}
     assert not wrong, f'codes of the rows that were (not) rejected against the table: {wrong}'

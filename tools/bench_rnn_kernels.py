@@ -126,14 +126,13 @@ def bench_pair(cell, H, S, T):
         return (p['gates'], p['kept'], p['hprev'], p['dones'], p['w_hh'], p['d_out'], p['dg'], p['dgh'])
 
     a, b = problem(1), problem(2)
-    f1, f2 = getattr(ops, f'{cell}_seq_forward'), getattr(ops, f'{cell}_seq_forward_pair')
-    b1, b2 = getattr(ops, f'{cell}_seq_backward'), getattr(ops, f'{cell}_seq_backward_pair')
+    f1, b1 = getattr(ops, f'{cell}_seq_forward'), getattr(ops, f'{cell}_seq_backward')
     fa, fb = fwd_args(a, train), fwd_args(b, train)
 
     def fwd_singles():
         f1(*fa, seq_len=T)
         f1(*fb, seq_len=T)
-    res = [alternate(lambda: f2(fa, fb, seq_len=T), fwd_singles)]
+    res = [alternate(lambda: ops.rnn_seq(cell, 'forward', [fa, fb], T), fwd_singles)]
     # what the backward reads: one training forward from the gate inputs
     for p in (a, b):
         p['gates'].copy_(p['gin'])
@@ -143,7 +142,7 @@ def bench_pair(cell, H, S, T):
     def bwd_singles():
         b1(*ba, T)
         b1(*bb, T)
-    res.append(alternate(lambda: b2(ba, bb, T), bwd_singles))
+    res.append(alternate(lambda: ops.rnn_seq(cell, 'backward', [ba, bb], T), bwd_singles))
     for name, (mp, ms, sp, ss) in zip(('forward', 'backward'), res):
         print(f'{cell:4s} {H:4d} {S:6,d} {T:3d} {name:9s} {mp:9.1f} {ms:9.1f}   {mp / ms:5.2f}   {100 * sp:5.1f} %  {100 * ss:5.1f} %',
               flush=True)
