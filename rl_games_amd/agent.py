@@ -23,7 +23,6 @@ What runs where (per epoch):
   minibatch : obs normaliser 3 launches, fused loss fwd+bwd+KL 2 launches, clip+Adam+adaptive-lr
               2 launches, one all-reduce; learning rate and KL stay on the device.
 """
-import gc
 import os
 import time
 from datetime import datetime
@@ -38,6 +37,7 @@ from .actor_paths import AutogradPath, Plan
 from .diagnostics import DefaultDiagnostics, PpoDiagnostics
 from .flat_optim import FlatAdam
 from .gae import compute_gae, gae_returns_advantages
+from .hip_graphs import GraphCaptureError, GraphCapturer, StepGraphs, UpdateGraphs
 from .lr_control import AdaptiveScheduler, IdentityScheduler, LinearScheduler
 from .minibatch import PPODataset
 from .normalizers import GeneralizedMovingStats
@@ -59,10 +59,6 @@ def rescale_actions(low, high, action):
     d = (high - low) / 2.0
     m = (high + low) / 2.0
     return action * d + m
-
-
-class GraphCaptureError(RuntimeError):
-    """A HIP graph capture failed; nothing ran on the device and host mirrors were rolled back."""
 
 
 class NullObserver:
@@ -391,12 +387,12 @@ class A2CAgent:
         self._host_lr = self.last_lr
         self.train_result = None
         self.kernel_timers = None
-        # HIP graphs: one captured graph per minibatch index (forward/loss/backward) + one for the
-        # optimiser kernels; the first epoch always runs eagerly (allocations, GEMM selection).
+        # HIP graphs (hip_graphs.py): the update graphs and the rollout's step graphs, captured into one pool; the
+        # first epoch always runs eagerly (allocations, GEMM selection).
         self._hip_graphs = bool(config.get('hip_graphs', True))
-        self._graphs, self._graph_opt, self._graph_sig, self._graph_pool = {}, None, None, None
-        self._graph_epoch = None
-        self._graph_norm_state = None
+        self._capturer = GraphCapturer(forms, self.optimizer)
+        self._update_graphs = UpdateGraphs()
+        self._rollout_graphs, self._rollout_graph_key = StepGraphs(self._capturer), None
         self.last_allreduce = None    # 'ipc' | 'rccl' once a multi-GPU step has run (bench.py reports it)
         self._graph_failed = False
         self._fold_ready = False      # this epoch's minibatch observation moments are precomputed
@@ -405,7 +401,6 @@ class A2CAgent:
         self._ar_norm_partials = None
         self._fold_index = None
         self._ipc_comm = None
-        self._rollout_graphs, self._rollout_graph_key, self._rollout_static = {}, None, None
         self._rnn_state_store = None
         self._eager_epochs = 0
         self._graph_rows = torch.zeros(max(1, self.num_minibatches), 8, dtype=torch.float32, device=dev)
@@ -751,7 +746,6 @@ class A2CAgent:
         if self._rollout_graph_key != key:
             self._rollout_graphs.clear()
             self._rollout_graph_key = key
-            self._rollout_static = None
         if direct:
             fields = {'obses': obs, 'dones': self.dones}
             if states is not None:
@@ -759,35 +753,13 @@ class A2CAgent:
             buf.store_step(n, fields)
             args = (n, buf.storage['obses'][:, n, :], None, None, False,
                     None if states is None else buf.storage['states'][:, n, :])
-        else:
-            if self._rollout_static is None:
-                st = {'obs': torch.empty_like(obs).contiguous(), 'dones': torch.empty_like(self.dones)}
-                if self.is_rnn:
-                    st['rnn'] = [torch.empty_like(s) for s in self.rnn_states]
-                if states is not None:
-                    st['states'] = torch.empty_like(states).contiguous()
-                if self._critic_steps_rnn():
-                    st['cv_rnn'] = [torch.empty_like(s) for s in self.central_value_net.rnn_states]
-                self._rollout_static = st
-            st = self._rollout_static
-            st['obs'].copy_(obs)
-            st['dones'].copy_(self.dones)
-            if self.is_rnn:
-                for dst, src in zip(st['rnn'], self.rnn_states):
-                    dst.copy_(src)
-            if states is not None:
-                st['states'].copy_(states)
-            if 'cv_rnn' in st:
-                for dst, src in zip(st['cv_rnn'], self.central_value_net.rnn_states):
-                    dst.copy_(src)
-            args = (n, st['obs'], st['dones'], st.get('rnn'), True, st.get('states'), st.get('cv_rnn'))
-        entry = self._rollout_graphs.get((n, direct))
-        if entry is None:
-            out = []
-            g = self._capture(lambda: out.append(self._policy_step_kernels(*args)))
-            entry = self._rollout_graphs[(n, direct)] = (g, out[0])
-        entry[0].replay()
-        return entry[1]
+            inputs, body = None, lambda: self._policy_step_kernels(*args)
+        else:                                                    # (by the names _policy_step_kernels takes them under)
+            inputs = {'obs_raw': obs, 'dones': self.dones, 'rnn_states': self.rnn_states if self.is_rnn else None,
+                      'states': states,
+                      'cv_rnn_states': self.central_value_net.rnn_states if self._critic_steps_rnn() else None}
+            body = lambda **static: self._policy_step_kernels(n, **static)
+        return self._rollout_graphs.step(direct, body, inputs, index=n)     # (one set of statics for all steps)
 
     def _rollout_graphs_usable(self):
         return (self._hip_graphs and self.config.get('rollout_graphs', True) and self._eager_epochs >= 1
@@ -1333,64 +1305,32 @@ class A2CAgent:
         return (self._hip_graphs and self._path.graphs and self._eager_epochs >= 1
                 and self.dataset.values_dict.get('rnn_masks') is None and not self._graph_failed)
 
-    def _capture(self, body):
-        """Capture `body` into a HIP graph.  Capturing executes nothing on the device; host mirrors
-        that the body advances (the optimiser's step count, the weight forms' stamps) are restored afterwards, also when the
-        capture fails (GraphCaptureError: the update then continues on the eager path).  A rollout step
-        advances none of them."""
-        if self._graph_pool is None:
-            self._graph_pool = torch.cuda.graph_pool_handle()
-        g = torch.cuda.CUDAGraph()
-        count0, version0 = self.optimizer.step_count, self.optimizer.weights_version
-        # No automatic garbage collection while the stream is capturing: a cycle that owns device objects of an
-        # earlier graph (torch.cuda.graph collects once on entry, but the body allocates hundreds of Python objects)
-        # would be finalised in the middle of the capture, and releasing device resources there aborts the process.
-        gc_was_enabled = gc.isenabled()
-        gc.disable()
-        try:
-            with self._form_chains.captured(), \
-                    torch.cuda.graph(g, pool=self._graph_pool, capture_error_mode='thread_local'):
-                body()
-        except Exception as e:
-            raise GraphCaptureError('HIP graph capture failed') from e
-        finally:
-            if gc_was_enabled:
-                gc.enable()
-            self.optimizer.step_count, self.optimizer.weights_version = count0, version0
-        return g
-
-    def _drop_stale_graphs(self):
-        sig = self._graph_signature()
-        if sig != self._graph_sig:
-            self._graphs.clear()
-            self._graph_opt = self._graph_epoch = None
-            self._graph_sig = sig
-
     def _graph_minibatch(self, i):
         """Replay (capturing on first use) the forward/loss/backward graph of minibatch i, run the
         gradient all-reduce eagerly, then replay the (norm, Adam, lr) graph."""
-        self._drop_stale_graphs()
-        g = self._graphs.get(i)
+        graphs, capture = self._update_graphs, self._capturer.capture
+        graphs.refresh(self._graph_signature())
+        g = graphs.minibatch.get(i)
         if g is None:
             item = self.dataset[i]
-            g = self._graphs[i] = self._capture(lambda: self._with_fold(i, self._forward_loss_backward, item,
-                                                                       self._graph_rows[i]))
-            self._graph_norm_state = self._norm_ready      # what the captured launches will have produced
+            g = graphs.minibatch[i] = capture(lambda: self._with_fold(i, self._forward_loss_backward, item,
+                                                                      self._graph_rows[i]))
+            graphs.norm_state = self._norm_ready      # what the captured launches will have produced
         self._form_chains.before_replay()
-        if self._graph_opt is None:
+        if graphs.optimizer is None:
             # Captured BEFORE anything of this minibatch runs (a failed capture then leaves minibatch i untouched
             # for the eager path), knowing which launch in front of it produces the gradient norm - the
             # weight-gradient finalise on one GPU, the native all-reduce on several - so that the graph carries no
             # grad_sumsq of its own.
-            self._norm_ready = self._graph_norm_state
+            self._norm_ready = graphs.norm_state
             if self.multi_gpu:
                 self._all_reduce_norm_plan(self._native_comm())
-            self._graph_opt = self._capture(self._optimizer_kernels)
+            graphs.optimizer = capture(self._optimizer_kernels)
         g.replay()
         if self.multi_gpu:
             self._all_reduce_grads()
         self._norm_ready = None
-        self._graph_opt.replay()
+        graphs.optimizer.replay()
         self.optimizer.step_done()
         self._form_chains.after_step(self.optimizer, packed=True)
 
@@ -1398,8 +1338,9 @@ class A2CAgent:
         """Single-GPU runs with nothing to do on the host between minibatches (device-side or
         per-epoch lr schedule): ALL minibatches of a mini-epoch - forward, loss, backward, clip, Adam,
         lr update, nmb times - are one HIP graph, replayed once per mini-epoch."""
-        self._drop_stale_graphs()
-        if self._graph_epoch is None:
+        graphs = self._update_graphs
+        graphs.refresh(self._graph_signature())
+        if graphs.epoch is None:
             def body():
                 for i in range(nmb):
                     self._with_fold(i, self._forward_loss_backward, self.dataset[i], self._graph_rows[i])
@@ -1408,9 +1349,9 @@ class A2CAgent:
                     self._optimizer_kernels()
                 if self._fold_ready:
                     self.model.running_mean_std.fold_sync(nmb)
-            self._graph_epoch = self._capture(body)
+            graphs.epoch = self._capturer.capture(body)
         self._form_chains.before_replay()
-        self._graph_epoch.replay()
+        graphs.epoch.replay()
         self.optimizer.step_count += nmb
         self.optimizer.weights_version += nmb
         self._form_chains.after_step(self.optimizer, packed=True)
@@ -1476,8 +1417,8 @@ class A2CAgent:
                     # remaining minibatches of this mini-epoch (and all later ones) run eagerly.
                     print(f'rl_games_amd: HIP graph capture failed ({e.__cause__!r}); continuing eagerly')
                     self._graph_failed = True
-                    self._graphs.clear()
-                    self._graph_opt = self._graph_epoch = None
+                    self._update_graphs.clear()
+                    self._rollout_graphs.clear()      # (never used again: _rollout_graphs_usable)
                     use_graphs = False
                 self._mb_scalars[first:first + done].copy_(self._graph_rows[:done])
                 self._mb_index += done
@@ -1577,12 +1518,13 @@ class A2CAgent:
 
     def _set_chain_products(self, mode):
         """Every chain of the agent (and of its central value network) on `mode`, the weight-gradient launches on the
-        matching form.  Captured graphs hold the other mode's launches: the update graphs go with the signature, the
-        rollout's step graphs here, and the next epoch runs eagerly like the first."""
+        matching form.  Captured graphs hold the other mode's launches: they go (the mode is part of the update graphs'
+        signature too), and the next epoch runs eagerly like the first."""
         self._form_chains.set_products(mode)
         for e in self._range_engines():
             e.weight_grads.form = 'exact' if mode == 'exact' else None
         if mode != self.chain_products:
+            self._update_graphs.clear()
             self._rollout_graphs.clear()
             self._eager_epochs = 0
         self.chain_products = mode

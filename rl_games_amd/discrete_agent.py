@@ -24,6 +24,16 @@ from . import ops
 from .agent import A2CAgent
 
 
+def draw_exp_noise(noise, rows, branch_sizes):
+    """The Exp(1) draws of Categorical.sample() (multinomial's one-sample path) into the flat `noise`: one exponential_
+    per branch, in branch order, on its contiguous [rows, n_b] block.  Every categorical head of the package draws here -
+    agents and players consume the generator alike."""
+    at = 0
+    for size in branch_sizes:
+        noise[at:at + rows * size].view(rows, size).exponential_()
+        at += rows * size
+
+
 class DiscreteA2CAgent(A2CAgent):
     def _init_action_space(self, config):
         """DiscreteA2CBase.__init__ (a2c_common.py:1206-1222)."""
@@ -75,12 +85,7 @@ class DiscreteA2CAgent(A2CAgent):
         return super()._fast_policy_step(n)
 
     def _draw_exp_noise(self, rows):
-        """The Exp(1) draws of Categorical.sample() (multinomial's one-sample path): one exponential_ per branch, in
-        branch order, on a contiguous [rows, n_b] block."""
-        at = 0
-        for size in self.branch_sizes:
-            self._roll_noise[at:at + rows * size].view(rows, size).exponential_()
-            at += rows * size
+        draw_exp_noise(self._roll_noise, rows, self.branch_sizes)
 
     _draw_value_noise = _draw_exp_noise     # (get_values runs the model's whole eval forward, which samples actions)
 

@@ -4,14 +4,14 @@ its second call on, and the episode accounting of run() on the device (one host 
 Which engine runs the network, and whether one does, is actor_paths.Plan's answer - the player is shown to it as the
 agent it asks (_PlayAgent): the same eligibility checks, arena layouts and infer sequences as the agents' rollout.
 """
-import gc
-
 import torch
 
 from . import ops
 from .actor_paths import EnginePath, Plan
-from .agent import A2CAgent, GraphCaptureError
+from .agent import A2CAgent
+from .discrete_agent import draw_exp_noise
 from .flat_optim import FlatArena
+from .hip_graphs import GraphCaptureError, GraphCapturer, StepGraphs
 from .weight_forms import ChainFormSet
 
 TRAIN_ROWS = 16        # rows the engines' training buffers are sized for where a constructor takes them apart (infer_rows)
@@ -71,7 +71,7 @@ class FusedPlay:
             return
         self.path, self.rows = path, rows
         self._forms = ChainFormSet(path.chain_forms())
-        self._graphs, self._static, self._seen, self._pool = {}, {}, set(), None
+        self._graphs, self._seen = StepGraphs(GraphCapturer(self._forms)), set()
         self.replayed = False                       # the last step was a graph replay
         dev = player.device
         if agent.is_discrete:
@@ -96,10 +96,8 @@ class FusedPlay:
         if self._agent.is_discrete:
             noise = None
             if not deterministic:
-                noise, at = self._noise, 0
-                for size in self._agent.branch_sizes:            # (as DiscreteA2CAgent._draw_exp_noise)
-                    noise[at:at + rows * size].view(rows, size).exponential_()
-                    at += rows * size
+                noise = self._noise
+                draw_exp_noise(noise, rows, self._agent.branch_sizes)
             ops.play_categorical_head(heads[0], self._agent.branch_sizes, noise, masks, actions)
         else:
             noise = None
@@ -109,23 +107,6 @@ class FusedPlay:
             bounds = (player.actions_low, player.actions_high) if player.clip_actions else None
             ops.play_policy_head(heads[:, 1:], player.model.a2c_network.sigma.data, noise, actions, bounds)
         return actions, (self.path.last_states if self._agent.is_rnn else None)
-
-    def _capture(self, body):
-        """A2CAgent._capture for a step that advances no host mirror."""
-        if self._pool is None:
-            self._pool = torch.cuda.graph_pool_handle()
-        g = torch.cuda.CUDAGraph()
-        gc_was_enabled = gc.isenabled()
-        gc.disable()
-        try:
-            with self._forms.captured(), torch.cuda.graph(g, pool=self._pool, capture_error_mode='thread_local'):
-                body()
-        except Exception as e:
-            raise GraphCaptureError('HIP graph capture failed') from e
-        finally:
-            if gc_was_enabled:
-                gc.enable()
-        return g
 
     @torch.no_grad()
     def step(self, obs, masks, deterministic):
@@ -144,29 +125,14 @@ class FusedPlay:
             self.replayed = False
             actions, states = self._kernels(obs, player.states, masks, deterministic)
         else:
-            st = self._static.get(key)
-            if st is None:
-                st = self._static[key] = (torch.empty_like(obs),
-                                          None if player.states is None else [torch.empty_like(s) for s in player.states],
-                                          None if masks is None else torch.empty_like(masks))
-            st[0].copy_(obs)
-            for dst, src in zip(st[1] or (), player.states or ()):
-                dst.copy_(src)
-            if masks is not None:
-                st[2].copy_(masks)
-            entry = self._graphs.get(key)
-            if entry is None:
-                out = []
-                try:
-                    g = self._capture(lambda: out.append(self._kernels(st[0], st[1], st[2], deterministic)))
-                except GraphCaptureError as e:
-                    print(f'rl_games_amd: HIP graph capture of the play step failed ({e.__cause__!r}); continuing eagerly')
-                    self._graphs_ok = False
-                    return self.step(obs, masks, deterministic)
-                entry = self._graphs[key] = (g, out[0])
-            entry[0].replay()
+            try:
+                body = lambda **static: self._kernels(**static, deterministic=deterministic)
+                actions, states = self._graphs.step(key, body, {'obs': obs, 'states': player.states, 'masks': masks})
+            except GraphCaptureError as e:
+                print(f'rl_games_amd: HIP graph capture of the play step failed ({e.__cause__!r}); continuing eagerly')
+                self._graphs_ok = False
+                return self.step(obs, masks, deterministic)
             self.replayed = True
-            actions, states = entry[1]
         if states is not None:
             player.states = list(states)
         return actions

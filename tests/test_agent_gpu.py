@@ -1140,7 +1140,7 @@ def test_hip_graph_replays_are_bit_identical_to_eager_training(cfg):
         for _ in range(6):
             agent.update_epoch()
             agent.train_epoch()
-        assert (agent._graph_epoch is not None or bool(agent._graphs)) == graphs
+        assert (agent._update_graphs.epoch is not None or bool(agent._update_graphs.minibatch)) == graphs
         res.append((agent.optimizer.flat_params.clone(), agent.optimizer.exp_avg.clone(),
                     agent.optimizer.exp_avg_sq.clone(), agent.model.running_mean_std.running_mean.clone(),
                     agent.model.value_mean_std.running_var.clone(), agent.optimizer.last_and_next_lr()))
@@ -1173,7 +1173,7 @@ def test_weights_set_between_epochs_reach_the_replayed_rollout_and_update_graphs
                 agent.set_weights(w)
             agent.update_epoch()
             agent.train_epoch()
-        assert (agent._graph_epoch is not None or bool(agent._graphs)) == graphs
+        assert (agent._update_graphs.epoch is not None or bool(agent._update_graphs.minibatch)) == graphs
         if graphs:
             assert agent._lean_chain() is not None and len(agent._rollout_graphs) > 0
         res.append((agent.optimizer.flat_params.clone(), agent.optimizer.exp_avg.clone(), agent.optimizer.exp_avg_sq.clone(),
@@ -1226,7 +1226,7 @@ def test_weights_written_from_outside_the_package_invalidate_the_derived_copies(
 
 
 def test_a_failed_capture_leaves_nothing_marked_as_packed(monkeypatch):
-    """_capture puts the host mirrors back behind a capture that failed part-way: the optimiser's step count AND
+    """GraphCapturer.capture puts the host mirrors back behind a capture that failed part-way: the optimiser's step count AND
     weights_version, and what the chains believe their planes / fragments hold (the body's pack launches were recorded,
     never run).  The second (= last) minibatch of the first captured mini-epoch raises - behind a whole recorded step whose
     optimiser launch had marked the planes / fragments as those of the next weights; the epoch continues eagerly and ends

@@ -223,7 +223,7 @@ def _headline_epoch(use_diagnostics, monkeypatch):
         agent.diagnostics.debug_neglogp = torch.full((len(agent.dataset), agent.minibatch_size), float('nan'), device=DEV)
     agent.update_epoch()
     res = agent.train_epoch()
-    assert agent._graph_epoch is not None and not agent._graph_failed
+    assert agent._update_graphs.epoch is not None and not agent._graph_failed
     if use_diagnostics:
         agent.diagnostics.epoch(agent, current_epoch=1)
     torch.cuda.synchronize()

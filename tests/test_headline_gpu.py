@@ -145,7 +145,7 @@ def test_full_size_minibatches_on_the_benchmarked_path_match_oracle(graphs):
     agent.update_epoch()
     res = agent.train_epoch()
     if graphs:
-        assert agent._graph_epoch is not None and not agent._graph_failed
+        assert agent._update_graphs.epoch is not None and not agent._graph_failed
     assert agent._engine.last_dw_path == 'mfma' and agent._engine.last_dw_library_jobs == 0
     oracle = _oracle_for(params, caps[0], N, 108, 21)
     ref = oracle.update(caps[0]['batch'])
@@ -403,7 +403,7 @@ def test_whole_epoch_of_320_steps_matches_oracle(N, MB):
     agent._eager_epochs = 1               # capture + replay already in the first epoch, like bench.py's timed epochs
     agent.update_epoch()
     res = agent.train_epoch()
-    assert agent._graph_epoch is not None and not agent._graph_failed
+    assert agent._update_graphs.epoch is not None and not agent._graph_failed
     assert agent._engine.last_dw_path == 'mfma' and agent._engine.last_dw_library_jobs == 0
     rows = agent._mb_scalars[:ME * NMB, :5].cpu()      # [a_loss, c_loss, entropy, b_loss, kl] per optimiser step
     assert len(res[4]) == ME * NMB

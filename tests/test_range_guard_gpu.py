@@ -612,8 +612,8 @@ def test_exact_policy_drops_the_epoch_switches_to_exact_products_and_trains_on(c
     for _ in range(2):
         out = _epoch(agent)                               # the second one on captured graphs
     assert all(torch.isfinite(x) for x in out[4] + out[5])
-    sig_auto = agent._graph_sig
-    assert sig_auto is not None and (agent._graph_epoch is not None or agent._graphs)
+    sig_auto = agent._update_graphs.signature
+    assert sig_auto is not None and (agent._update_graphs.epoch is not None or agent._update_graphs.minibatch)
     _poison(agent)
     before = _state(agent)
     capsys.readouterr()
@@ -630,8 +630,9 @@ def test_exact_policy_drops_the_epoch_switches_to_exact_products_and_trains_on(c
     assert printed.count('range guard tripped') == 1 and 'exact fp32 products' in printed
     assert torch.isfinite(agent.optimizer.flat_params).all() and not torch.equal(agent.optimizer.flat_params, params)
     # the update graphs were captured again, under another signature
-    assert agent._graph_sig != sig_auto and agent._graph_sig[-2:] == ('exact', True) and sig_auto[-2:] == ('auto', True)
-    assert agent._graph_epoch is not None or agent._graphs
+    assert agent._update_graphs.signature != sig_auto
+    assert agent._update_graphs.signature[-2:] == ('exact', True) and sig_auto[-2:] == ('auto', True)
+    assert agent._update_graphs.epoch is not None or agent._update_graphs.minibatch
 
 
 def test_exact_policy_on_an_update_trip_and_non_finite_inputs_on_exact_products():

@@ -48,7 +48,7 @@ def main():
     on, agent = ms_per_epoch(True, a.epochs, a.warmup)
     keys = {k: float(v.reshape(-1)[0]) for k, v in agent.diagnostics.diag_dict.items()}
     print(json.dumps({'ms_per_epoch_off': round(off, 3), 'ms_per_epoch_on': round(on, 3),
-                      'added_pct': round(100.0 * (on - off) / off, 2), 'graph': agent._graph_epoch is not None,
+                      'added_pct': round(100.0 * (on - off) / off, 2), 'graph': agent._update_graphs.epoch is not None,
                       'diag': keys}))
 
 
