@@ -111,17 +111,35 @@ int rlg_rollout_post_step_num_blocks(int num_envs);
  * clamp to [rmin, rmax], bit 1 = log_val: log of the shaped reward behind the clamp), time-out bootstrap (a2c_common.py:1021-1023), update_data('rewards') (:1025),
  * current_rewards/current_shaped_rewards/current_lengths accumulate + zero-on-done
  * (:1027-1051).  Finished-episode sums go to ep_partials[step][block][2V+2] (fp64) and are
- * folded into the meters by rlg_episode_meters_update.  time_outs_kind: 0 none, 1 u8/bool,
- * 2 fp32.  live_rows (next_step autoreset mask, :1002-1006) may be NULL. value_size <= 8.
- * num_envs counts rows (envs x agents); with num_agents > 1 only the first agent row of an env
- * feeds the meters (all_done_indices[::num_agents], :1040-1044). */
-int rlg_rollout_post_step(const float* rewards, const uint8_t* dones, const void* time_outs,
-                          int time_outs_kind, const float* values, const float* live_rows,
-                          float* rewards_buf, float* cur_rewards, float* cur_shaped,
-                          float* cur_lengths, double* ep_partials, float shift, float scale,
-                          float rmin, float rmax, int clamp_rewards, int bootstrap, float gamma,
-                          int num_envs, int horizon, int value_size, int step, int num_agents,
-                          void* stream);
+ * folded into the meters by rlg_episode_meters_update.  N counts rows (envs x agents); with num_agents > 1 only the
+ * first agent row of an env feeds the meters (all_done_indices[::num_agents], :1040-1044).
+ * Required: rewards, dones, values, rewards_buf, cur_rewards, cur_shaped, cur_lengths, ep_partials.  May be NULL:
+ * time_outs (time_outs_kind and bootstrap are then read as 0), live_rows.  num_agents < 1 is read as 1.
+ * A NULL descriptor: hipErrorInvalidValue.  N <= 0 returns 0 without a launch.  Then, before the runtime is asked for
+ * anything, hipErrorInvalidValue for a NULL required pointer, V outside [1, 8], step outside [0, H).  Like every
+ * descriptor of this header it is read before the entry returns. */
+typedef struct rlg_post_step_desc {
+  const float* rewards;        /* [N, V] raw env rewards of this step */
+  const uint8_t* dones;        /* [N] done flags produced by this step */
+  const void* time_outs;       /* [N] or NULL (infos['time_outs']) */
+  int time_outs_kind;          /* 0 none, 1 uint8 / bool, 2 fp32 */
+  const float* values;         /* [N, V] critic values of this step (res_dict['values']) */
+  const float* live_rows;      /* [N] or NULL: 1 - prev_dones (next_step autoreset mask, :1002-1006) */
+  float* rewards_buf;          /* env-major [N][H][V] */
+  float* cur_rewards;          /* [N, V] */
+  float* cur_shaped;           /* [N, V] */
+  float* cur_lengths;          /* [N] */
+  double* ep_partials;         /* [H][rlg_rollout_post_step_num_blocks(N)][2V+2]: sum rew[V], sum shaped[V], sum len, count */
+  float shift, scale, rmin, rmax;
+  int clamp_rewards;
+  int bootstrap;               /* value_bootstrap and 'time_outs' in infos */
+  float gamma;
+  int N, H, V, step;           /* rows, horizon, value_size <= 8, the buffer slot written */
+  int num_agents;              /* meters take one row per env: rows with row % num_agents == 0 */
+} rlg_post_step_desc;
+RLG_ABI_SIZE(rlg_post_step_desc, 136);
+
+int rlg_rollout_post_step(const rlg_post_step_desc* desc, void* stream);
 
 /* Replays AverageMeter.update (rl_games/algos_torch/torch_ext.py:333-342) for the three
  * episode meters (game_rewards, game_shaped_rewards, game_lengths; a2c_common.py:1042-1044)
@@ -135,35 +153,52 @@ int rlg_episode_meters_update(const double* ep_partials, int horizon, int num_bl
  * the update_data writes of its outputs (a2c_common.py:1008-1009).  heads [N, ld]: column 0 the
  * critic value, columns 1..A the action means; noise [N, A] ~ N(0,1).  Writes actions/mus/
  * sigmas/neglogpacs/values of step `step` into the env-major buffer fields and the contiguous
- * actions [N, A] / de-normalised values [N] the env step and the post-step kernel consume. */
-int rlg_rollout_policy_head(const float* heads, int ld_heads, const float* logstd, const float* noise,
-                            const double* value_mean_or_null, const double* value_var_or_null,
-                            float eps, float* actions_out, float* values_out, float* buf_actions,
-                            float* buf_mus, float* buf_sigmas, float* buf_neglogp, float* buf_values,
-                            /* optional [N, A]: rescale_actions(low, high, clamp(actions, -1, 1)) - what
-                             * preprocess_actions hands to the env when clip_actions is set
-                             * (a2c_common.py:725-733); act_low / act_high [A] */
-                            float* env_actions_out_or_null, const float* act_low, const float* act_high,
-                            int num_envs, int horizon, int actions_num, int step, void* stream);
+ * actions [N, A] / de-normalised values [N] the env step and the post-step kernel consume.
+ * Value-source contract: value == NULL is column 0 of the heads - the entry reads (value, ld_value, value_repeat) as
+ * (heads, ld, 1) and looks at neither ld_value nor value_repeat.  With value given - the rollout of an agent with a
+ * central value network (a2c_common.py:593-600, central_value.py:208-228), whose critic's value replaces the actor's -
+ * row r (env-major, r = env * value_repeat + agent) reads value[(r / value_repeat) * ld_value], de-normalised with the
+ * statistics passed here (the critic's value_mean_std), and the heads' column 0 is not read: value.repeat(1, A)
+ * .view(N * A, -1) of central_value.py:223-225 with value_repeat = A; ld_value < 1 or value_repeat < 1:
+ * hipErrorInvalidValue.  Numeric contract: the outputs with value = the heads' own column 0, ld_value = ld,
+ * value_repeat = 1 are those of value == NULL, bit for bit.
+ * Required: heads, logstd, noise, the two outputs and the five buffer fields.  May be NULL: value; v_mean and v_var
+ * together (no de-normalisation); env_actions_out (then act_low / act_high are not read).
+ * A NULL descriptor: hipErrorInvalidValue.  N <= 0 returns 0 without a launch.  Then, before the runtime is asked for
+ * anything, hipErrorInvalidValue for a NULL required pointer, v_mean without v_var, env_actions_out without act_low /
+ * act_high, A <= 0, step outside [0, H). */
+typedef struct rlg_policy_head_desc {
+  const float* heads;      /* [N, ld] */
+  int ld;
+  const float* value;      /* NULL, or [ceil(N / value_repeat), ld_value], column 0 */
+  long long ld_value;
+  int value_repeat;
+  const float* logstd;     /* [A] */
+  const float* noise;      /* [N, A] standard normal */
+  const double* v_mean;    /* value RunningMeanStd (fp64), or NULL when normalize_value is off */
+  const double* v_var;
+  float eps;
+  float* actions_out;      /* [N, A] contiguous (goes to the env) */
+  float* values_out;       /* [N] de-normalised values (the time-out bootstrap needs them) */
+  float* buf_actions;      /* env-major [N][H][A] */
+  float* buf_mus;
+  float* buf_sigmas;
+  float* buf_neglogp;      /* [N][H] */
+  float* buf_values;       /* [N][H] */
+  /* optional [N, A]: rescale_actions(low, high, clamp(actions, -1, 1)) - what preprocess_actions hands to the env when
+   * clip_actions is set (a2c_common.py:725-733); act_low / act_high [A] */
+  float* env_actions_out;
+  const float* act_low;
+  const float* act_high;
+  int N, H, A, step;       /* rows, horizon, actions_num, the buffer slot written */
+} rlg_policy_head_desc;
+RLG_ABI_SIZE(rlg_policy_head_desc, 176);
 
-/* rlg_rollout_policy_head with the value taken from a separate column: the rollout of an agent with a central value
- * network (a2c_common.py:593-600, central_value.py:208-228), whose critic's value replaces the actor's.
- * Value-source contract: row r (env-major, r = env * value_repeat + agent) reads value[(r / value_repeat) * ld_value],
- * de-normalised with the statistics passed here (the critic's value_mean_std), and the heads' column 0 is not read:
- * value.repeat(1, A).view(N * A, -1) of central_value.py:223-225 with value_repeat = A.  value_repeat < 1 or
- * ld_value < 1: hipErrorInvalidValue.  Numeric contract as rlg_rollout_policy_head, whose outputs are this entry's
- * with (value, ld_value, value_repeat) = (heads, ld_heads, 1), bit for bit. */
-int rlg_rollout_policy_head_cv(const float* heads, int ld_heads, const float* value, int ld_value, int value_repeat,
-                               const float* logstd, const float* noise, const double* value_mean_or_null,
-                               const double* value_var_or_null, float eps, float* actions_out, float* values_out,
-                               float* buf_actions, float* buf_mus, float* buf_sigmas, float* buf_neglogp,
-                               float* buf_values, float* env_actions_out_or_null, const float* act_low,
-                               const float* act_high, int num_envs, int horizon, int actions_num, int step,
-                               void* stream);
+int rlg_rollout_policy_head(const rlg_policy_head_desc* desc, void* stream);
 
 /* Categorical rollout head (discrete_a2c / multi_discrete_a2c eval branch: rl_games/algos_torch/models.py:95-125,
  * :157-206, CategoricalMasked common/extensions/distributions.py:24-47, denorm_value :58-60) fused with the
- * update_data writes of its outputs (a2c_common.py:1008-1009).  logits [N, sum(sizes)] and value [N] (column 0) with
+ * update_data writes of its outputs (a2c_common.py:1008-1009).  logits [N, sum(sizes)] and value (column 0) with
  * any row strides (the chain's heads: one tensor [value | logits] for a shared trunk); branch_sizes a HOST array of
  * num_branches <= 16 sizes (more: hipErrorNotSupported); masks bool [N, sum(sizes)] or NULL.  Writes actions_out
  * [N, B] (int64, what env_step receives), de-normalised values_out [N], and slot `step` of the env-major buffer
@@ -178,24 +213,40 @@ int rlg_rollout_policy_head_cv(const float* heads, int ld_heads, const float* va
  * RNG contract: exp_noise holds the Exp(1) draws q in branch-major blocks, block b = [N, sizes[b]] contiguous at
  * N * (sizes[0] + ... + sizes[b-1]).  Drawing block b with exponential_ on the default generator, in branch order,
  * is exactly what Categorical(logits).sample() draws (multinomial's one-sample path: argmax(probs / Exp(1))), so
- * the actions are the torch path's, except where its top two p/q lie within a few ulps of each other. */
-int rlg_rollout_categorical_head(const float* logits, int ld_logits, const float* value, int ld_value,
-                                 const int* branch_sizes, int num_branches, const float* exp_noise,
-                                 const uint8_t* masks_or_null, int ld_masks, const double* v_mean_or_null,
-                                 const double* v_var_or_null, float eps, int64_t* actions_out, float* values_out,
-                                 int64_t* buf_actions, float* buf_neglogp, float* buf_values, int num_envs,
-                                 int horizon, int step, void* stream);
+ * the actions are the torch path's, except where its top two p/q lie within a few ulps of each other.
+ * Value-source contract: row r reads value[(r / value_repeat) * ld_value]; value_repeat = 1 is one value per row,
+ * value_repeat = num_agents a central value network's one state row per env.  ld_value < 1 or value_repeat < 1:
+ * hipErrorInvalidValue.
+ * Required: logits, branch_sizes, exp_noise, value, the two outputs and the three buffer fields.  May be NULL:
+ * masks_or_null (ld_masks is then not read); v_mean_or_null and v_var_or_null together.
+ * A NULL descriptor: hipErrorInvalidValue.  num_envs <= 0 returns 0 without a launch.  Then, before the runtime is asked
+ * for anything, more than 16 branches hipErrorNotSupported, and hipErrorInvalidValue for a NULL required pointer, v_mean
+ * without v_var, no branch, a branch size < 1, ld_logits (with masks: ld_masks) below sum(sizes), step outside
+ * [0, horizon). */
+typedef struct rlg_categorical_head_desc {
+  const float* logits;
+  int ld_logits;
+  const int* branch_sizes;     /* host array [num_branches] */
+  int num_branches;
+  const float* exp_noise;
+  const uint8_t* masks_or_null;
+  int ld_masks;
+  const float* value;          /* [ceil(num_envs / value_repeat), ld_value], column 0 */
+  int ld_value;
+  int value_repeat;
+  const double* v_mean_or_null;   /* value RunningMeanStd (fp64), or NULL when normalize_value is off */
+  const double* v_var_or_null;
+  float eps;
+  int64_t* actions_out;
+  float* values_out;
+  int64_t* buf_actions;
+  float* buf_neglogp;
+  float* buf_values;
+  int num_envs, horizon, step;
+} rlg_categorical_head_desc;
+RLG_ABI_SIZE(rlg_categorical_head_desc, 152);
 
-/* rlg_rollout_categorical_head with value_repeat rows per value row (a central value network's one state row per env
- * for num_agents = value_repeat agents).  Value-source contract: row r reads value[(r / value_repeat) * ld_value];
- * value_repeat < 1: hipErrorInvalidValue.  Numeric and RNG contracts as rlg_rollout_categorical_head, which is this
- * entry with value_repeat = 1. */
-int rlg_rollout_categorical_head_cv(const float* logits, int ld_logits, const float* value, int ld_value,
-                                    int value_repeat, const int* branch_sizes, int num_branches,
-                                    const float* exp_noise, const uint8_t* masks_or_null, int ld_masks,
-                                    const double* v_mean_or_null, const double* v_var_or_null, float eps,
-                                    int64_t* actions_out, float* values_out, int64_t* buf_actions, float* buf_neglogp,
-                                    float* buf_values, int num_envs, int horizon, int step, void* stream);
+int rlg_rollout_categorical_head(const rlg_categorical_head_desc* desc, void* stream);
 
 /* play_steps_rnn zero-on-done: s[:, done_envs, :] = 0 (a2c_common.py:1150-1153).
  * states [layers][num_envs][units] contiguous. */
@@ -401,16 +452,39 @@ int rlg_value_loss(const float* values, const float* old_values, const float* re
  * The heads may live inside wider rows (the fused chain's [value | logits] head matrix and its gradient): values /
  * d_values take an element stride, d_logits a row stride; separate contiguous tensors are ld_values = ld_d_values = 1,
  * ld_d_logits = n.  Each row's neglogp (the sum over the branches, as the loss used it) is also stored into
- * new_neglogp_or_null [mb] - the per-minibatch diagnostics read it (rlg_ppo_diag).  NULL: no store. */
+ * new_neglogp_or_null [mb] - the per-minibatch diagnostics read it (rlg_ppo_diag).  NULL: no store.
+ * Required: every pointer not named _or_null; mask_or_null needs mask_sum_or_null.  Before the runtime is asked for
+ * anything, hipErrorInvalidValue for a NULL descriptor or required pointer, minibatch <= 0, num_branches outside
+ * [1, 16], a branch size < 1, ld_values or ld_d_values < 1, ld_logits or ld_d_logits below n, a mask without its sum. */
 int rlg_ppo_loss_discrete_num_blocks(int minibatch);
-int rlg_ppo_loss_discrete_nlp(const float* logits, long long ld_logits, const float* values, long long ld_values,
-                              const long long* actions, const unsigned char* action_masks_or_null,
-                              const int* branch_sizes, int num_branches, const float* old_neglogp,
-                              const float* advantages, const float* old_values, const float* returns,
-                              const float* mask_or_null, const float* mask_sum_or_null, float* d_logits,
-                              long long ld_d_logits, float* d_values, long long ld_d_values, double* partials,
-                              int minibatch, float e_clip, float critic_coef, float entropy_coef, int clip_value,
-                              int use_smooth_clamp, float* new_neglogp_or_null, void* stream);
+typedef struct rlg_discrete_loss_desc {
+  const float* logits;
+  long long ld_logits;
+  const float* values;
+  long long ld_values;
+  const long long* actions;
+  const unsigned char* action_masks_or_null;
+  const int* branch_sizes;     /* host array [num_branches] */
+  int num_branches;
+  const float* old_neglogp;
+  const float* advantages;
+  const float* old_values;
+  const float* returns;
+  const float* mask_or_null;
+  const float* mask_sum_or_null;
+  float* d_logits;
+  long long ld_d_logits;
+  float* d_values;
+  long long ld_d_values;
+  double* partials;
+  int minibatch;
+  float e_clip, critic_coef, entropy_coef;
+  int clip_value, use_smooth_clamp;
+  float* new_neglogp_or_null;
+} rlg_discrete_loss_desc;
+RLG_ABI_SIZE(rlg_discrete_loss_desc, 184);
+
+int rlg_ppo_loss_discrete_nlp(const rlg_discrete_loss_desc* desc, void* stream);
 
 /* PPO diagnostics (`use_diagnostics`; rl_games/common/diagnostics.py, torch_ext.py:182-227), csrc/ppo_diag.hip.  A row of
  * the diagnostics table is rlg_ppo_diag_stats() = 10 fp64: {rows, W = sum m, C = sum m*clipped, mean_ret, M2_ret,

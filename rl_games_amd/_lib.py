@@ -40,20 +40,12 @@ _PROTOTYPES = {
                                ctypes.POINTER(_c_int), _c_int, _c_int, _c_int, _P],
     'rlg_rollout_store_streaming': [_c_int],
     'rlg_rollout_post_step_num_blocks': [_c_int],
-    'rlg_rollout_post_step': [_P, _P, _P, _c_int, _P, _P, _P, _P, _P, _P, _P, _c_float, _c_float,
-                              _c_float, _c_float, _c_int, _c_int, _c_float, _c_int, _c_int, _c_int,
-                              _c_int, _c_int, _P],
+    'rlg_rollout_post_step': [_P, _P],               # (PostStepDesc, stream)
     'rlg_episode_meters_update': [_P, _c_int, _c_int, _c_int, _c_int, _P, _P, _P, _P, _P, _P],
     'rlg_rnn_zero_done_states': [_P, _P, _c_int, _c_int, _c_int, _P],
-    'rlg_rollout_policy_head': [_P, _c_int, _P, _P, _P, _P, _c_float, _P, _P, _P, _P, _P, _P, _P,
-                                _P, _P, _P, _c_int, _c_int, _c_int, _c_int, _P],
-    'rlg_rollout_policy_head_cv': [_P, _c_int, _P, _c_int, _c_int, _P, _P, _P, _P, _c_float, _P, _P, _P, _P, _P, _P,
-                                   _P, _P, _P, _P, _c_int, _c_int, _c_int, _c_int, _P],
+    'rlg_rollout_policy_head': [_P, _P],             # (PolicyHeadDesc, stream)
     # rollout_categorical.hip
-    'rlg_rollout_categorical_head': [_P, _c_int, _P, _c_int, ctypes.POINTER(_c_int), _c_int, _P, _P, _c_int, _P, _P,
-                                     _c_float, _P, _P, _P, _P, _P, _c_int, _c_int, _c_int, _P],
-    'rlg_rollout_categorical_head_cv': [_P, _c_int, _P, _c_int, _c_int, ctypes.POINTER(_c_int), _c_int, _P, _P, _c_int,
-                                        _P, _P, _c_float, _P, _P, _P, _P, _P, _c_int, _c_int, _c_int, _P],
+    'rlg_rollout_categorical_head': [_P, _P],        # (CategoricalHeadDesc, stream)
     # play.hip
     'rlg_play_policy_head': [_P, _c_int, _c_int, _P, _P, _P, _P, _P, _c_int, _c_int, _P],
     'rlg_play_categorical_head': [_P, _c_int, ctypes.POINTER(_c_int), _c_int, _P, _P, _c_int, _P, _c_int, _P],
@@ -127,8 +119,7 @@ _PROTOTYPES = {
     'rlg_rnn_value_tail': [_P] * 13 + [_c_int, _c_ll, _c_int, _c_float, _c_int, _P],
     'rlg_value_loss': [_P, _P, _P, _P, _P, _P, _P, _c_int, _c_float, _c_int, _P],
     'rlg_ppo_loss_discrete_num_blocks': [_c_int],
-    'rlg_ppo_loss_discrete_nlp': [_P, _c_ll, _P, _c_ll, _P, _P, _P, _c_int, _P, _P, _P, _P, _P, _P, _P, _c_ll, _P,
-                                  _c_ll, _P, _c_int, _c_float, _c_float, _c_float, _c_int, _c_int, _P, _P],
+    'rlg_ppo_loss_discrete_nlp': [_P, _P],           # (DiscreteLossDesc, stream)
     # ppo_diag.hip
     'rlg_ppo_diag_stats': [],
     'rlg_ppo_diag_num_blocks': [_c_int],
@@ -231,6 +222,47 @@ class LossFinalizeDesc(ctypes.Structure):
                 ('d_mu_bias_or_null', ctypes.c_void_p), ('d_value_bias_or_null', ctypes.c_void_p)]
 
 
+# Every pointer field of the descriptors below is a plain address (ctypes.addressof for host arrays and descriptors):
+# whoever fills one keeps what it points at alive until the entry has returned.
+class DiscreteLossDesc(ctypes.Structure):
+    """rlg_discrete_loss_desc (include/rlg_hip.h): the arguments of rlg_ppo_loss_discrete_nlp."""
+    _fields_ = ([('logits', _P), ('ld_logits', _c_ll), ('values', _P), ('ld_values', _c_ll), ('actions', _P),
+                 ('action_masks_or_null', _P), ('branch_sizes', _P), ('num_branches', _c_int)]
+                + [(n, _P) for n in ('old_neglogp', 'advantages', 'old_values', 'returns', 'mask_or_null',
+                                     'mask_sum_or_null')]
+                + [('d_logits', _P), ('ld_d_logits', _c_ll), ('d_values', _P), ('ld_d_values', _c_ll), ('partials', _P),
+                   ('minibatch', _c_int), ('e_clip', _c_float), ('critic_coef', _c_float), ('entropy_coef', _c_float),
+                   ('clip_value', _c_int), ('use_smooth_clamp', _c_int), ('new_neglogp_or_null', _P)])
+
+
+class PostStepDesc(ctypes.Structure):
+    """rlg_post_step_desc (include/rlg_hip.h): the arguments of rlg_rollout_post_step."""
+    _fields_ = ([('rewards', _P), ('dones', _P), ('time_outs', _P), ('time_outs_kind', _c_int)]
+                + [(n, _P) for n in ('values', 'live_rows', 'rewards_buf', 'cur_rewards', 'cur_shaped', 'cur_lengths',
+                                     'ep_partials')]
+                + [(n, _c_float) for n in ('shift', 'scale', 'rmin', 'rmax')]
+                + [('clamp_rewards', _c_int), ('bootstrap', _c_int), ('gamma', _c_float)]
+                + [(n, _c_int) for n in ('N', 'H', 'V', 'step', 'num_agents')])
+
+
+class PolicyHeadDesc(ctypes.Structure):
+    """rlg_policy_head_desc (include/rlg_hip.h): the arguments of rlg_rollout_policy_head."""
+    _fields_ = ([('heads', _P), ('ld', _c_int), ('value', _P), ('ld_value', _c_ll), ('value_repeat', _c_int),
+                 ('logstd', _P), ('noise', _P), ('v_mean', _P), ('v_var', _P), ('eps', _c_float)]
+                + [(n, _P) for n in ('actions_out', 'values_out', 'buf_actions', 'buf_mus', 'buf_sigmas', 'buf_neglogp',
+                                     'buf_values', 'env_actions_out', 'act_low', 'act_high')]
+                + [(n, _c_int) for n in ('N', 'H', 'A', 'step')])
+
+
+class CategoricalHeadDesc(ctypes.Structure):
+    """rlg_categorical_head_desc (include/rlg_hip.h): the arguments of rlg_rollout_categorical_head."""
+    _fields_ = ([('logits', _P), ('ld_logits', _c_int), ('branch_sizes', _P), ('num_branches', _c_int),
+                 ('exp_noise', _P), ('masks_or_null', _P), ('ld_masks', _c_int), ('value', _P), ('ld_value', _c_int),
+                 ('value_repeat', _c_int), ('v_mean_or_null', _P), ('v_var_or_null', _P), ('eps', _c_float)]
+                + [(n, _P) for n in ('actions_out', 'values_out', 'buf_actions', 'buf_neglogp', 'buf_values')]
+                + [(n, _c_int) for n in ('num_envs', 'horizon', 'step')])
+
+
 class AdamDesc(ctypes.Structure):
     """rlg_adam_desc (include/rlg_hip.h): the optimiser step of the four rlg_adam_* entries."""
     _fields_ = ([(n, ctypes.c_void_p) for n in ('params', 'grads', 'exp_avg', 'exp_avg_sq')]
@@ -243,8 +275,6 @@ class AdamDesc(ctypes.Structure):
                 + [('stats_out_or_null', ctypes.c_void_p), ('skip_flag_or_null', ctypes.c_void_p)])
 
 
-# Every pointer field of the descriptors below is a plain address (ctypes.addressof for host arrays and descriptors):
-# whoever fills one keeps what it points at alive until the entry has returned.
 class ChainNet(ctypes.Structure):
     """rlg_chain_net (include/rlg_hip.h): the network of the six launching chain entries, stated once per chain."""
     _fields_ = [('num_layers', _c_int)] + [(n, _P) for n in ('weights', 'biases', 'in_features', 'out_features', 'acts')]

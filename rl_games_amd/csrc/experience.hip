@@ -20,6 +20,7 @@
 // in and the same out.
 
 #include "rlg_device.hpp"
+#include "rlg_hip.h"
 
 namespace rlg {
 
@@ -88,25 +89,9 @@ __global__ __launch_bounds__(kStoreBlock) void rollout_store_kernel(StoreSegment
 // Post-step: rewards, accumulators, finished-episode partial sums
 // ---------------------------------------------------------------------------------
 
-struct PostStepArgs {
-  const float* rewards;        // [N, V] raw env rewards of this step
-  const uint8_t* dones;        // [N] done flags produced by this step
-  const void* time_outs;       // [N] or nullptr   (infos['time_outs'])
-  int time_outs_kind;          // 0 none, 1 uint8/bool, 2 float32
-  const float* values;         // [N, V] critic values of this step (res_dict['values'])
-  const float* live_rows;      // [N] or nullptr: 1 - prev_dones (next_step autoreset mask)
-  float* rewards_buf;          // env-major [N][H][V]
-  float* cur_rewards;          // [N, V]
-  float* cur_shaped;           // [N, V]
-  float* cur_lengths;          // [N]
-  double* ep_partials;         // [H][nblocks][2V+2]: sum rew[V], sum shaped[V], sum len, count
-  float shift, scale, rmin, rmax;
-  int clamp_rewards;           // bit 0: clamp to [rmin, rmax] (0: the bounds are -inf/+inf); bit 1: log_val (log of the shaped reward)
-  int bootstrap;               // value_bootstrap and 'time_outs' in infos
-  float gamma;
-  int N, H, V, step;
-  int num_agents;              // meters take one row per env: rows with row % num_agents == 0
-};
+// The kernel's argument: the fields of the public descriptor (include/rlg_hip.h documents each of them), under the name
+// the kernel's symbol carries.
+struct PostStepArgs : rlg_post_step_desc {};
 
 constexpr int kPostBlock = 256;
 constexpr int kMaxV = 8;
@@ -263,31 +248,9 @@ __global__ __launch_bounds__(256) void episode_meters_kernel(
 // heads: [N, 1+A] fused (value | mu) output of the MLP.  One thread per env.  The value of row r is read from
 // value[(r / value_repeat) * ld_value]: column 0 of the heads (value = heads, ld_value = ld, value_repeat = 1), or a
 // central value network's output with one row per env for num_agents = value_repeat rows (central_value.py:223-225).
-struct PolicyHeadArgs {
-  const float* heads;      // [N, ld]
-  int ld;
-  const float* value;      // [ceil(N / value_repeat), ld_value], column 0
-  long long ld_value;
-  int value_repeat;
-  const float* logstd;     // [A]
-  const float* noise;      // [N, A] standard normal
-  const double* v_mean;    // value RunningMeanStd (fp64) or nullptr when normalize_value is off
-  const double* v_var;
-  float eps;
-  float* actions_out;      // [N, A] contiguous (goes to the env)
-  float* values_out;       // [N]    de-normalised values (time-out bootstrap needs them)
-  float* buf_actions;      // env-major [N][H][A]
-  float* buf_mus;
-  float* buf_sigmas;
-  float* buf_neglogp;      // [N][H]
-  float* buf_values;       // [N][H]
-  // optional: what goes to the env when clip_actions is set (a2c_common.py:725-733 preprocess_actions:
-  // rescale_actions(low, high, clamp(actions, -1, 1)), torch_ext.py rescale_actions)
-  float* env_actions_out;  // [N, A] or nullptr
-  const float* act_low;    // [A]
-  const float* act_high;   // [A]
-  int N, H, A, step;
-};
+// The kernels' argument is the public descriptor (include/rlg_hip.h) under the name their symbols carry; the entry has
+// put (heads, ld, 1) where the caller left `value` NULL.
+struct PolicyHeadArgs : rlg_policy_head_desc {};
 
 // Two phases per 256-env block.  A: one thread per env reduces sum z^2 / sum logstd over the
 // actions and writes the per-env scalars.  B: the block's 256*A (env, action) elements are walked
@@ -469,42 +432,18 @@ int rlg_rollout_post_step_num_blocks(int num_envs) {
   return (num_envs + rlg::kPostBlock - 1) / rlg::kPostBlock;
 }
 
-int rlg_rollout_post_step(const float* rewards, const uint8_t* dones, const void* time_outs,
-                          int time_outs_kind, const float* values, const float* live_rows,
-                          float* rewards_buf, float* cur_rewards, float* cur_shaped,
-                          float* cur_lengths, double* ep_partials, float shift, float scale,
-                          float rmin, float rmax, int clamp_rewards, int bootstrap, float gamma,
-                          int num_envs, int horizon, int value_size, int step, int num_agents,
-                          void* stream) {
+int rlg_rollout_post_step(const rlg_post_step_desc* desc, void* stream) {
   using namespace rlg;
-  if (num_envs <= 0) return 0;
-  if (value_size < 1 || value_size > kMaxV || step < 0 || step >= horizon)
+  if (!desc) return static_cast<int>(hipErrorInvalidValue);
+  if (desc->N <= 0) return 0;
+  PostStepArgs a{*desc};
+  if (!a.rewards || !a.dones || !a.values || !a.rewards_buf || !a.cur_rewards || !a.cur_shaped || !a.cur_lengths ||
+      !a.ep_partials || a.V < 1 || a.V > kMaxV || a.step < 0 || a.step >= a.H)
     return static_cast<int>(hipErrorInvalidValue);
-  PostStepArgs a;
-  a.rewards = rewards;
-  a.dones = dones;
-  a.time_outs = time_outs;
-  a.time_outs_kind = time_outs ? time_outs_kind : 0;
-  a.values = values;
-  a.live_rows = live_rows;
-  a.rewards_buf = rewards_buf;
-  a.cur_rewards = cur_rewards;
-  a.cur_shaped = cur_shaped;
-  a.cur_lengths = cur_lengths;
-  a.ep_partials = ep_partials;
-  a.shift = shift;
-  a.scale = scale;
-  a.rmin = rmin;
-  a.rmax = rmax;
-  a.clamp_rewards = clamp_rewards;
-  a.bootstrap = (bootstrap && time_outs && a.time_outs_kind != 0) ? 1 : 0;
-  a.gamma = gamma;
-  a.N = num_envs;
-  a.H = horizon;
-  a.V = value_size;
-  a.step = step;
-  a.num_agents = num_agents < 1 ? 1 : num_agents;
-  const int grid = rlg_rollout_post_step_num_blocks(num_envs);
+  if (!a.time_outs) a.time_outs_kind = 0;
+  a.bootstrap = (a.bootstrap && a.time_outs_kind != 0) ? 1 : 0;
+  if (a.num_agents < 1) a.num_agents = 1;
+  const int grid = rlg_rollout_post_step_num_blocks(a.N);
   hipLaunchKernelGGL(rollout_post_step_kernel, dim3(grid), dim3(kPostBlock), 0,
                      static_cast<hipStream_t>(stream), a);
   RLG_RETURN_LAUNCH_STATUS();
@@ -522,41 +461,24 @@ int rlg_episode_meters_update(const double* ep_partials, int horizon, int num_bl
   RLG_RETURN_LAUNCH_STATUS();
 }
 
-int rlg_rollout_policy_head_cv(const float* heads, int ld_heads, const float* value, int ld_value, int value_repeat,
-                               const float* logstd, const float* noise, const double* value_mean_or_null,
-                               const double* value_var_or_null, float eps, float* actions_out, float* values_out,
-                               float* buf_actions, float* buf_mus, float* buf_sigmas, float* buf_neglogp,
-                               float* buf_values, float* env_actions_out, const float* act_low, const float* act_high,
-                               int num_envs, int horizon, int actions_num, int step, void* stream) {
-  if (num_envs <= 0) return 0;
-  if (step < 0 || step >= horizon || actions_num <= 0) return static_cast<int>(hipErrorInvalidValue);
-  if (env_actions_out && (!act_low || !act_high)) return static_cast<int>(hipErrorInvalidValue);
-  if (!value || ld_value < 1 || value_repeat < 1) return static_cast<int>(hipErrorInvalidValue);
-  rlg::PolicyHeadArgs p;
-  p.heads = heads;
-  p.ld = ld_heads;
-  p.value = value;
-  p.ld_value = ld_value;
-  p.value_repeat = value_repeat;
-  p.logstd = logstd;
-  p.noise = noise;
-  p.v_mean = value_mean_or_null;
-  p.v_var = value_var_or_null;
-  p.eps = eps;
-  p.actions_out = actions_out;
-  p.values_out = values_out;
-  p.buf_actions = buf_actions;
-  p.buf_mus = buf_mus;
-  p.buf_sigmas = buf_sigmas;
-  p.buf_neglogp = buf_neglogp;
-  p.buf_values = buf_values;
-  p.N = num_envs;
-  p.H = horizon;
-  p.A = actions_num;
-  p.step = step;
-  p.env_actions_out = env_actions_out;
-  p.act_low = act_low;
-  p.act_high = act_high;
+int rlg_rollout_policy_head(const rlg_policy_head_desc* desc, void* stream) {
+  if (!desc) return static_cast<int>(hipErrorInvalidValue);
+  if (desc->N <= 0) return 0;
+  rlg::PolicyHeadArgs p{*desc};
+  if (!p.heads || !p.logstd || !p.noise || !p.actions_out || !p.values_out || !p.buf_actions || !p.buf_mus ||
+      !p.buf_sigmas || !p.buf_neglogp || !p.buf_values)
+    return static_cast<int>(hipErrorInvalidValue);
+  if (p.step < 0 || p.step >= p.H || p.A <= 0 || (p.v_mean && !p.v_var))
+    return static_cast<int>(hipErrorInvalidValue);
+  if (p.env_actions_out && (!p.act_low || !p.act_high)) return static_cast<int>(hipErrorInvalidValue);
+  if (!p.value) {                      // column 0 of the heads
+    p.value = p.heads;
+    p.ld_value = p.ld;
+    p.value_repeat = 1;
+  } else if (p.ld_value < 1 || p.value_repeat < 1) {
+    return static_cast<int>(hipErrorInvalidValue);
+  }
+  const int ld_heads = p.ld, actions_num = p.A, num_envs = p.N;
   // one wave per workgroup: 8,192 envs (a rank of 8) are 128 workgroups instead of 32 - the kernel is a chain of dependent
   // memory round trips per workgroup, so it wants every CU (16 -> 8 us there); the layout of the work inside a
   // workgroup (phase A one thread per env, phase B consecutive threads on consecutive addresses) is unchanged
@@ -575,18 +497,6 @@ int rlg_rollout_policy_head_cv(const float* heads, int ld_heads, const float* va
                        static_cast<hipStream_t>(stream), p);
   }
   RLG_RETURN_LAUNCH_STATUS();
-}
-
-int rlg_rollout_policy_head(const float* heads, int ld_heads, const float* logstd, const float* noise,
-                            const double* value_mean_or_null, const double* value_var_or_null,
-                            float eps, float* actions_out, float* values_out, float* buf_actions,
-                            float* buf_mus, float* buf_sigmas, float* buf_neglogp, float* buf_values,
-                            float* env_actions_out, const float* act_low, const float* act_high,
-                            int num_envs, int horizon, int actions_num, int step, void* stream) {
-  return rlg_rollout_policy_head_cv(heads, ld_heads, heads, ld_heads, 1, logstd, noise, value_mean_or_null,
-                                    value_var_or_null, eps, actions_out, values_out, buf_actions, buf_mus, buf_sigmas,
-                                    buf_neglogp, buf_values, env_actions_out, act_low, act_high, num_envs, horizon,
-                                    actions_num, step, stream);
 }
 
 int rlg_rnn_zero_done_states(float* states, const uint8_t* dones, int layers, int num_envs,

@@ -298,6 +298,48 @@ __global__ __launch_bounds__(256) void value_loss_kernel(
   }
 }
 
+// Host: the discrete kernel's argument from the public descriptor, with the branch table (off, n, nb); false for a
+// description the header rejects.
+static bool discrete_loss_args(DiscreteLossArgs& p, const rlg_discrete_loss_desc& d) {
+  if (d.minibatch <= 0 || d.num_branches <= 0 || d.num_branches > kMaxBranches || !d.branch_sizes) return false;
+  if (!d.logits || !d.values || !d.actions || !d.old_neglogp || !d.advantages || !d.old_values || !d.returns ||
+      !d.d_logits || !d.d_values || !d.partials || (d.mask_or_null && !d.mask_sum_or_null))
+    return false;
+  p.off[0] = 0;
+  for (int b = 0; b < d.num_branches; ++b) {
+    if (d.branch_sizes[b] <= 0) return false;
+    p.off[b + 1] = p.off[b] + d.branch_sizes[b];
+  }
+  p.nb = d.num_branches;
+  p.n = p.off[p.nb];
+  if (d.ld_values <= 0 || d.ld_d_values <= 0 || d.ld_logits < p.n || d.ld_d_logits < p.n) return false;
+  p.logits = d.logits;
+  p.ld = d.ld_logits;
+  p.values = d.values;
+  p.ld_values = d.ld_values;
+  p.actions = d.actions;
+  p.action_masks = d.action_masks_or_null;
+  p.old_neglogp = d.old_neglogp;
+  p.advantages = d.advantages;
+  p.old_values = d.old_values;
+  p.returns = d.returns;
+  p.mask = d.mask_or_null;
+  p.mask_sum = d.mask_sum_or_null;
+  p.d_logits = d.d_logits;
+  p.d_values = d.d_values;
+  p.ld_d_logits = d.ld_d_logits;
+  p.ld_d_values = d.ld_d_values;
+  p.partials = d.partials;
+  p.mb = d.minibatch;
+  p.e_clip = d.e_clip;
+  p.critic_coef = d.critic_coef;
+  p.entropy_coef = d.entropy_coef;
+  p.clip_value = d.clip_value;
+  p.smooth = d.use_smooth_clamp;
+  p.new_neglogp = d.new_neglogp_or_null;
+  return true;
+}
+
 }  // namespace rlg
 
 extern "C" {
@@ -344,53 +386,11 @@ int rlg_value_loss(const float* values, const float* old_values, const float* re
 
 int rlg_ppo_loss_discrete_num_blocks(int minibatch) { return (minibatch + 255) / 256; }
 
-int rlg_ppo_loss_discrete_nlp(const float* logits, long long ld_logits, const float* values, long long ld_values,
-                              const long long* actions, const unsigned char* action_masks_or_null,
-                              const int* branch_sizes, int num_branches, const float* old_neglogp,
-                              const float* advantages, const float* old_values, const float* returns,
-                              const float* mask_or_null, const float* mask_sum_or_null, float* d_logits,
-                              long long ld_d_logits, float* d_values, long long ld_d_values, double* partials,
-                              int minibatch, float e_clip, float critic_coef, float entropy_coef, int clip_value,
-                              int use_smooth_clamp, float* new_neglogp_or_null, void* stream) {
+int rlg_ppo_loss_discrete_nlp(const rlg_discrete_loss_desc* desc, void* stream) {
   using namespace rlg;
-  if (minibatch <= 0 || num_branches <= 0 || num_branches > kMaxBranches)
-    return static_cast<int>(hipErrorInvalidValue);
-  if (mask_or_null && !mask_sum_or_null) return static_cast<int>(hipErrorInvalidValue);
-  if (ld_values <= 0 || ld_d_values <= 0) return static_cast<int>(hipErrorInvalidValue);
   DiscreteLossArgs p;
-  p.off[0] = 0;
-  for (int b = 0; b < num_branches; ++b) {
-    if (branch_sizes[b] <= 0) return static_cast<int>(hipErrorInvalidValue);
-    p.off[b + 1] = p.off[b] + branch_sizes[b];
-  }
-  p.logits = logits;
-  p.ld = ld_logits;
-  p.values = values;
-  p.ld_values = ld_values;
-  p.actions = actions;
-  p.action_masks = action_masks_or_null;
-  p.old_neglogp = old_neglogp;
-  p.advantages = advantages;
-  p.old_values = old_values;
-  p.returns = returns;
-  p.mask = mask_or_null;
-  p.mask_sum = mask_sum_or_null;
-  p.d_logits = d_logits;
-  p.d_values = d_values;
-  p.ld_d_logits = ld_d_logits;
-  p.ld_d_values = ld_d_values;
-  p.partials = partials;
-  p.mb = minibatch;
-  p.nb = num_branches;
-  p.n = p.off[num_branches];
-  if (ld_logits < p.n || ld_d_logits < p.n) return static_cast<int>(hipErrorInvalidValue);
-  p.e_clip = e_clip;
-  p.critic_coef = critic_coef;
-  p.entropy_coef = entropy_coef;
-  p.clip_value = clip_value;
-  p.smooth = use_smooth_clamp;
-  p.new_neglogp = new_neglogp_or_null;
-  hipLaunchKernelGGL(ppo_loss_discrete_kernel, dim3(rlg_ppo_loss_discrete_num_blocks(minibatch)), dim3(256), 0,
+  if (!desc || !discrete_loss_args(p, *desc)) return static_cast<int>(hipErrorInvalidValue);
+  hipLaunchKernelGGL(ppo_loss_discrete_kernel, dim3(rlg_ppo_loss_discrete_num_blocks(p.mb)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), p);
   RLG_RETURN_LAUNCH_STATUS();
 }

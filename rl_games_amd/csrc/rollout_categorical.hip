@@ -17,6 +17,7 @@
 // branches in order, each with 64-lane reductions.  The kernel is launch- and latency-bound either way.
 
 #include "categorical_rows.hpp"
+#include "rlg_hip.h"
 
 namespace rlg {
 
@@ -109,39 +110,46 @@ __global__ __launch_bounds__(kCatWaveBlock) void rollout_categorical_wave_kernel
   }
 }
 
+// Host: the kernels' argument from the public descriptor - the rows with their branch table (categorical_rows_setup), then
+// what the rollout adds; the hipError_t of a bad description.
+static int categorical_head_args(CategoricalHeadArgs& p, const rlg_categorical_head_desc& d) {
+  const int bad = categorical_rows_setup(p, d.logits, d.ld_logits, d.branch_sizes, d.num_branches, d.exp_noise,
+                                         d.masks_or_null, d.ld_masks, d.num_envs);
+  if (bad) return bad;
+  p.value = d.value;
+  p.v_mean = d.v_mean_or_null;
+  p.v_var = d.v_var_or_null;
+  p.actions_out = reinterpret_cast<long long*>(d.actions_out);
+  p.values_out = d.values_out;
+  p.buf_actions = reinterpret_cast<long long*>(d.buf_actions);
+  p.buf_neglogp = d.buf_neglogp;
+  p.buf_values = d.buf_values;
+  p.ld_value = d.ld_value;
+  p.eps = d.eps;
+  p.H = d.horizon;
+  p.step = d.step;
+  p.value_repeat = d.value_repeat;
+  return 0;
+}
+
 }  // namespace rlg
 
 extern "C" {
 
-int rlg_rollout_categorical_head_cv(const float* logits, int ld_logits, const float* value, int ld_value,
-                                    int value_repeat, const int* branch_sizes, int num_branches,
-                                    const float* exp_noise, const uint8_t* masks_or_null, int ld_masks,
-                                    const double* v_mean_or_null, const double* v_var_or_null, float eps,
-                                    int64_t* actions_out, float* values_out, int64_t* buf_actions, float* buf_neglogp,
-                                    float* buf_values, int num_envs, int horizon, int step, void* stream) {
+int rlg_rollout_categorical_head(const rlg_categorical_head_desc* desc, void* stream) {
   using namespace rlg;
+  if (!desc) return static_cast<int>(hipErrorInvalidValue);
+  const rlg_categorical_head_desc& d = *desc;
+  const int num_envs = d.num_envs;
   if (num_envs <= 0) return 0;
-  if (num_branches > kMaxBranches) return static_cast<int>(hipErrorNotSupported);
-  if (num_branches < 1 || !branch_sizes || step < 0 || step >= horizon || (v_mean_or_null && !v_var_or_null) ||
-      value_repeat < 1 || ld_value < 1)
+  if (d.num_branches > kMaxBranches) return static_cast<int>(hipErrorNotSupported);
+  if (!d.logits || !d.exp_noise || !d.value || !d.actions_out || !d.values_out || !d.buf_actions || !d.buf_neglogp ||
+      !d.buf_values || d.step < 0 || d.step >= d.horizon || (d.v_mean_or_null && !d.v_var_or_null) ||
+      d.value_repeat < 1 || d.ld_value < 1)
     return static_cast<int>(hipErrorInvalidValue);
   CategoricalHeadArgs p;
-  const int bad = categorical_rows_setup(p, logits, ld_logits, branch_sizes, num_branches, exp_noise, masks_or_null,
-                                         ld_masks, num_envs);
+  const int bad = categorical_head_args(p, d);
   if (bad) return bad;
-  p.value_repeat = value_repeat;
-  p.value = value;
-  p.v_mean = v_mean_or_null;
-  p.v_var = v_var_or_null;
-  p.actions_out = reinterpret_cast<long long*>(actions_out);
-  p.values_out = values_out;
-  p.buf_actions = reinterpret_cast<long long*>(buf_actions);
-  p.buf_neglogp = buf_neglogp;
-  p.buf_values = buf_values;
-  p.ld_value = ld_value;
-  p.eps = eps;
-  p.H = horizon;
-  p.step = step;
   const int ld = p.S | 1;
   if (ld <= kCatTileMaxStride) {
     const size_t lds = static_cast<size_t>(kCatTileRows) * (2 * ld + p.B + p.pow2 + 1) * sizeof(float);
@@ -153,18 +161,6 @@ int rlg_rollout_categorical_head_cv(const float* logits, int ld_logits, const fl
                        dim3(kCatWaveBlock), 0, static_cast<hipStream_t>(stream), p);
   }
   RLG_RETURN_LAUNCH_STATUS();
-}
-
-int rlg_rollout_categorical_head(const float* logits, int ld_logits, const float* value, int ld_value,
-                                 const int* branch_sizes, int num_branches, const float* exp_noise,
-                                 const uint8_t* masks_or_null, int ld_masks, const double* v_mean_or_null,
-                                 const double* v_var_or_null, float eps, int64_t* actions_out, float* values_out,
-                                 int64_t* buf_actions, float* buf_neglogp, float* buf_values, int num_envs,
-                                 int horizon, int step, void* stream) {
-  return rlg_rollout_categorical_head_cv(logits, ld_logits, value, ld_value, 1, branch_sizes, num_branches, exp_noise,
-                                         masks_or_null, ld_masks, v_mean_or_null, v_var_or_null, eps, actions_out,
-                                         values_out, buf_actions, buf_neglogp, buf_values, num_envs, horizon, step,
-                                         stream);
 }
 
 }  // extern "C"

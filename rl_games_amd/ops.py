@@ -85,16 +85,15 @@ def rollout_post_step(rewards, dones, time_outs, values, live_rows, rewards_buf,
             _lib.require_gpu(time_outs, 'time_outs')
         else:
             raise ValueError(f'time_outs dtype {time_outs.dtype} unsupported')
-    _lib.check(lib.rlg_rollout_post_step(
-        _need(rewards, F32, 'rewards'), _need(dones, U8, 'dones'), to_ptr, kind,
-        _need(values, F32, 'values'), _opt(live_rows, F32, 'live_rows'),
-        _need(rewards_buf, F32, 'rewards_buf'), _need(cur_rewards, F32, 'cur_rewards'),
-        _need(cur_shaped, F32, 'cur_shaped'), _need(cur_lengths, F32, 'cur_lengths'),
-        _need(ep_partials, F64, 'ep_partials'), float(np.float32(shift)), float(np.float32(scale)),
-        float(np.float32(max(rmin, -3.0e38))), float(np.float32(min(rmax, 3.0e38))), clamp,
-        1 if bootstrap else 0, float(np.float32(gamma)), N, horizon, V, step, int(num_agents),
-        _stream(rewards)),
-        'rlg_rollout_post_step')
+    desc = _lib.PostStepDesc(
+        rewards=_need(rewards, F32, 'rewards'), dones=_need(dones, U8, 'dones'), time_outs=to_ptr, time_outs_kind=kind,
+        values=_need(values, F32, 'values'), live_rows=_opt(live_rows, F32, 'live_rows'),
+        rewards_buf=_need(rewards_buf, F32, 'rewards_buf'), cur_rewards=_need(cur_rewards, F32, 'cur_rewards'),
+        cur_shaped=_need(cur_shaped, F32, 'cur_shaped'), cur_lengths=_need(cur_lengths, F32, 'cur_lengths'),
+        ep_partials=_need(ep_partials, F64, 'ep_partials'), shift=shift, scale=scale, rmin=max(rmin, -3.0e38),
+        rmax=min(rmax, 3.0e38), clamp_rewards=clamp, bootstrap=1 if bootstrap else 0, gamma=gamma, N=N, H=horizon, V=V,
+        step=step, num_agents=int(num_agents))
+    _lib.check(lib.rlg_rollout_post_step(ctypes.addressof(desc), _stream(rewards)), 'rlg_rollout_post_step')
 
 
 def episode_meters_update(ep_partials, horizon, num_blocks, value_size, max_size, mean_rewards,
@@ -113,28 +112,28 @@ def rollout_policy_head(heads, logstd, noise, value_stats, eps, actions_out, val
     """storage: ExperienceBuffer.storage (env-major fields).  value_stats = (mean, var) or None.
     env_actions = (out [N, A], low [A], high [A]): also rescale_actions(low, high, clamp(actions, -1, 1)).
     value: None (column 0 of the heads) or a [N / value_repeat, 1] view with any row stride (a central value network's
-    output): row r of the step gets the value of row r // value_repeat (rlg_rollout_policy_head_cv)."""
+    output): row r of the step gets the value of row r // value_repeat."""
     lib = _lib.load()
     N, A = noise.shape
-    vm = vv = None
+    desc = _lib.PolicyHeadDesc(
+        heads=_need(heads, F32, 'heads'), ld=heads.stride(0), logstd=_need(logstd, F32, 'logstd'),
+        noise=_need(noise, F32, 'noise'), eps=eps, actions_out=_need(actions_out, F32, 'actions_out'),
+        values_out=_need(values_out, F32, 'values_out'), buf_actions=_need(storage['actions'], F32, 'actions'),
+        buf_mus=_need(storage['mus'], F32, 'mus'), buf_sigmas=_need(storage['sigmas'], F32, 'sigmas'),
+        buf_neglogp=_need(storage['neglogpacs'], F32, 'neglogpacs'), buf_values=_need(storage['values'], F32, 'values'),
+        N=N, H=horizon, A=A, step=step)
     if value_stats is not None:
-        vm, vv = _need(value_stats[0], F64, 'value mean'), _need(value_stats[1], F64, 'value var')
+        desc.v_mean, desc.v_var = _need(value_stats[0], F64, 'value mean'), _need(value_stats[1], F64, 'value var')
     if value is None:
         if value_repeat != 1:
             raise ValueError('value_repeat needs a value tensor')
-        entry, source = 'rlg_rollout_policy_head', ()
     else:
-        entry, source = 'rlg_rollout_policy_head_cv', _value_column(value, N, value_repeat) + (int(value_repeat),)
-    _lib.check(getattr(lib, entry)(
-        _need(heads, F32, 'heads'), heads.stride(0), *source, _need(logstd, F32, 'logstd'), _need(noise, F32, 'noise'),
-        vm, vv, float(np.float32(eps)), _need(actions_out, F32, 'actions_out'),
-        _need(values_out, F32, 'values_out'), _need(storage['actions'], F32, 'actions'),
-        _need(storage['mus'], F32, 'mus'), _need(storage['sigmas'], F32, 'sigmas'),
-        _need(storage['neglogpacs'], F32, 'neglogpacs'), _need(storage['values'], F32, 'values'),
-        None if env_actions is None else _need(env_actions[0], F32, 'env actions'),
-        None if env_actions is None else _need(env_actions[1], F32, 'actions low'),
-        None if env_actions is None else _need(env_actions[2], F32, 'actions high'),
-        N, horizon, A, step, _stream(heads)), entry)
+        desc.value, desc.ld_value = _value_column(value, N, value_repeat)
+        desc.value_repeat = int(value_repeat)
+    if env_actions is not None:
+        desc.env_actions_out = _need(env_actions[0], F32, 'env actions')
+        desc.act_low, desc.act_high = _need(env_actions[1], F32, 'actions low'), _need(env_actions[2], F32, 'actions high')
+    _lib.check(lib.rlg_rollout_policy_head(ctypes.addressof(desc), _stream(heads)), 'rlg_rollout_policy_head')
 
 
 CATEGORICAL_MAX_BRANCHES = 16
@@ -160,6 +159,22 @@ def _value_column(value, N, value_repeat):
     return _row_view(value, F32, N // int(value_repeat), 1, 'value')
 
 
+def _categorical_rows(logits, branch_sizes, noise, masks):
+    """What both categorical heads are told about their rows, checked: (the sizes as a C int array, N, B, logits
+    address and row stride, noise address or None, masks address or None and row stride)."""
+    sizes = [int(s) for s in branch_sizes]
+    N, S, B = logits.shape[0], sum(sizes), len(sizes)
+    lg, ld_lg = _row_view(logits, F32, N, S, 'logits')
+    if noise is not None:
+        _need(noise, F32, 'noise')
+        if noise.numel() < N * S:
+            raise ValueError(f'noise: {noise.numel()} draws for {N} x {S}')
+    mp, ld_m = None, 0
+    if masks is not None:
+        mp, ld_m = _row_view(masks.view(U8) if masks.dtype == torch.bool else masks, U8, N, S, 'masks')
+    return (ctypes.c_int * B)(*sizes), N, B, lg, ld_lg, None if noise is None else noise.data_ptr(), mp, ld_m
+
+
 def rollout_categorical_head(logits, value, branch_sizes, noise, masks, value_stats, eps, actions_out, values_out,
                              storage, horizon, step, value_repeat=1):
     """Categorical rollout head (csrc/rollout_categorical.hip).  logits [N, sum(sizes)] and value [N, 1] (views of the
@@ -168,21 +183,12 @@ def rollout_categorical_head(logits, value, branch_sizes, noise, masks, value_st
     (mean, var) or None; actions_out int64 [N] / [N, B]; values_out fp32 [N]; storage: ExperienceBuffer.storage
     (env-major 'actions', 'neglogpacs', 'values').  Slot `step` of those fields is written.  value_repeat > 1: value
     has N / value_repeat rows (a central value network's output), row r of the step gets the value of row
-    r // value_repeat (rlg_rollout_categorical_head_cv)."""
+    r // value_repeat."""
     lib = _lib.load()
-    sizes = [int(s) for s in branch_sizes]
-    N, S, B = logits.shape[0], sum(sizes), len(sizes)
-    lg, ld_lg = _row_view(logits, F32, N, S, 'logits')
+    if noise is None:
+        raise ValueError('noise is None')
+    arr, N, B, lg, ld_lg, qp, mp, ld_m = _categorical_rows(logits, branch_sizes, noise, masks)
     vp, ld_v = _value_column(value, N, value_repeat)
-    _need(noise, F32, 'noise')
-    if noise.numel() < N * S:
-        raise ValueError(f'noise: {noise.numel()} draws for {N} x {S}')
-    mp, ld_m = None, 0
-    if masks is not None:
-        mp, ld_m = _row_view(masks.view(U8) if masks.dtype == torch.bool else masks, U8, N, S, 'masks')
-    vm = vv = None
-    if value_stats is not None:
-        vm, vv = _need(value_stats[0], F64, 'value mean'), _need(value_stats[1], F64, 'value var')
     if actions_out.numel() != N * B or values_out.numel() != N:
         raise ValueError('actions_out [N, B] / values_out [N] expected')
     fields = ((storage['actions'], torch.int64, N * horizon * B), (storage['neglogpacs'], F32, N * horizon),
@@ -190,15 +196,16 @@ def rollout_categorical_head(logits, value, branch_sizes, noise, masks, value_st
     for t, dtype, numel in fields:
         if t.numel() != numel:
             raise ValueError(f'buffer field of {t.numel()} elements, expected {numel}')
-    arr = (ctypes.c_int * B)(*sizes)
-    if value_repeat == 1:
-        entry, source = 'rlg_rollout_categorical_head', (vp, ld_v)
-    else:
-        entry, source = 'rlg_rollout_categorical_head_cv', (vp, ld_v, int(value_repeat))
-    _lib.check(getattr(lib, entry)(
-        lg, ld_lg, *source, arr, B, noise.data_ptr(), mp, ld_m, vm, vv, float(np.float32(eps)),
-        _need(actions_out, torch.int64, 'actions_out'), _need(values_out, F32, 'values_out'),
-        *[_need(t, dtype, 'buffer field') for t, dtype, _ in fields], N, horizon, step, _stream(value)), entry)
+    buf_actions, buf_neglogp, buf_values = [_need(t, dtype, 'buffer field') for t, dtype, _ in fields]
+    desc = _lib.CategoricalHeadDesc(
+        logits=lg, ld_logits=ld_lg, branch_sizes=ctypes.addressof(arr), num_branches=B, exp_noise=qp, masks_or_null=mp,
+        ld_masks=ld_m, value=vp, ld_value=ld_v, value_repeat=int(value_repeat), eps=eps,
+        actions_out=_need(actions_out, torch.int64, 'actions_out'), values_out=_need(values_out, F32, 'values_out'),
+        buf_actions=buf_actions, buf_neglogp=buf_neglogp, buf_values=buf_values, num_envs=N, horizon=horizon, step=step)
+    if value_stats is not None:
+        desc.v_mean_or_null = _need(value_stats[0], F64, 'value mean')
+        desc.v_var_or_null = _need(value_stats[1], F64, 'value var')
+    _lib.check(lib.rlg_rollout_categorical_head(ctypes.addressof(desc), _stream(value)), 'rlg_rollout_categorical_head')
 
 
 def rnn_zero_done_states(states, dones):
@@ -226,21 +233,12 @@ def play_policy_head(mu, logstd, noise, actions_out, bounds=None):
 def play_categorical_head(logits, branch_sizes, noise, masks, actions_out):
     """logits [N, sum(sizes)] (a view, any row stride); noise: the Exp(1) draws of rollout_categorical_head or None
     (arg-max); masks: bool / uint8 [N, sum(sizes)] view or None; actions_out int64 [N] / [N, B]."""
-    sizes = [int(s) for s in branch_sizes]
-    N, S, B = logits.shape[0], sum(sizes), len(sizes)
-    lg, ld_lg = _row_view(logits, F32, N, S, 'logits')
-    if noise is not None:
-        _need(noise, F32, 'noise')
-        if noise.numel() < N * S:
-            raise ValueError(f'noise: {noise.numel()} draws for {N} x {S}')
-    mp, ld_m = None, 0
-    if masks is not None:
-        mp, ld_m = _row_view(masks.view(U8) if masks.dtype == torch.bool else masks, U8, N, S, 'masks')
+    arr, N, B, lg, ld_lg, qp, mp, ld_m = _categorical_rows(logits, branch_sizes, noise, masks)
     if actions_out.numel() != N * B:
         raise ValueError('actions_out [N, B] expected')
     _lib.check(_lib.load().rlg_play_categorical_head(
-        lg, ld_lg, (ctypes.c_int * B)(*sizes), B, None if noise is None else noise.data_ptr(), mp, ld_m,
-        _need(actions_out, torch.int64, 'actions_out'), N, _stream(logits)), 'rlg_play_categorical_head')
+        lg, ld_lg, arr, B, qp, mp, ld_m, _need(actions_out, torch.int64, 'actions_out'), N, _stream(logits)),
+        'rlg_play_categorical_head')
 
 
 def play_post_step_blocks(rows):
@@ -570,7 +568,6 @@ def ppo_loss_discrete(logits, values, actions, old_neglogp, advantages, old_valu
     """Categorical PPO loss + gradients.  branch_sizes: widths of the multi-discrete heads
     (default: one head of logits.shape[1]); actions [mb] or [mb, branches] int64; action_masks
     [mb, n] bool/uint8 or None; new_neglogp: fp32 [mb] that receives each row's neglogp, or None."""
-    import ctypes
     lib = _lib.load()
     mb, n = logits.shape
     _lib.require_gpu(logits, 'logits')
@@ -596,16 +593,18 @@ def ppo_loss_discrete(logits, values, actions, old_neglogp, advantages, old_valu
     arr = (ctypes.c_int * len(sizes))(*sizes)
     if new_neglogp is not None and tuple(new_neglogp.shape) != (mb,):
         raise ValueError('new_neglogp must be [minibatch]')
-    _lib.check(lib.rlg_ppo_loss_discrete_nlp(
-        logits.data_ptr(), logits.stride(0), values.data_ptr(), max(values.stride(0), 1),
-        _need(actions, torch.int64, 'actions'), am, arr, len(sizes), _need(old_neglogp, F32, 'old_neglogp'),
-        _need(advantages, F32, 'advantages'), _need(old_values, F32, 'old_values'),
-        _need(returns, F32, 'returns'), _opt(mask, F32, 'mask'), _opt(mask_sum, F32, 'mask_sum'),
-        d_logits.data_ptr(), d_logits.stride(0), d_values.data_ptr(), max(d_values.stride(0), 1),
-        _need(partials, F64, 'partials'),
-        mb, float(np.float32(e_clip)), float(np.float32(critic_coef)), float(np.float32(entropy_coef)),
-        1 if clip_value else 0, _surrogate_kind(smooth), _opt(new_neglogp, F32, 'new_neglogp'), _stream(logits)),
-        'rlg_ppo_loss_discrete_nlp')
+    desc = _lib.DiscreteLossDesc(
+        logits=logits.data_ptr(), ld_logits=logits.stride(0), values=values.data_ptr(),
+        ld_values=max(values.stride(0), 1), actions=_need(actions, torch.int64, 'actions'), action_masks_or_null=am,
+        branch_sizes=ctypes.addressof(arr), num_branches=len(sizes), old_neglogp=_need(old_neglogp, F32, 'old_neglogp'),
+        advantages=_need(advantages, F32, 'advantages'), old_values=_need(old_values, F32, 'old_values'),
+        returns=_need(returns, F32, 'returns'), mask_or_null=_opt(mask, F32, 'mask'),
+        mask_sum_or_null=_opt(mask_sum, F32, 'mask_sum'), d_logits=d_logits.data_ptr(), ld_d_logits=d_logits.stride(0),
+        d_values=d_values.data_ptr(), ld_d_values=max(d_values.stride(0), 1), partials=_need(partials, F64, 'partials'),
+        minibatch=mb, e_clip=e_clip, critic_coef=critic_coef, entropy_coef=entropy_coef,
+        clip_value=1 if clip_value else 0, use_smooth_clamp=_surrogate_kind(smooth),
+        new_neglogp_or_null=_opt(new_neglogp, F32, 'new_neglogp'))
+    _lib.check(lib.rlg_ppo_loss_discrete_nlp(ctypes.addressof(desc), _stream(logits)), 'rlg_ppo_loss_discrete_nlp')
 
 
 def ppo_diag_stats():

@@ -10,7 +10,10 @@ that announced gradient maxima and timing events to the NEXT launch are gone - t
 descriptors - so their names are taken out of the recorded lists, and nothing else is.  And ONE renaming (RENAMED): a
 paired sequence launch is a call of the single entry's name with two problems, so rlg_lstm_seq_forward_pair /
 rlg_lstm_seq_backward_pair are read as rlg_lstm_seq_forward / rlg_lstm_seq_backward; a paired launch stays ONE call
-where two single launches are two, so the order check keeps its force.
+where two single launches are two, so the order check keeps its force.  And in the file's table of names, the two
+rollout heads that took a central value network's column under a name of their own stand under rlg_rollout_policy_head /
+rlg_rollout_categorical_head (the table holds each of these two names twice): the value column is a field of the one
+entry's descriptor, and the lists of indices are as recorded.
 A change that moves a launch on purpose records them again:
 
     python tests/test_actor_paths_gpu.py --record tests/golden/actor_path_traces.json [--digests digests.txt]

@@ -42,7 +42,9 @@ def test_descriptor_classes_have_the_sizes_the_header_asserts():
     sizes = {name: int(n) for name, n in re.findall(r'^RLG_ABI_SIZE\((\w+), (\d+)\);', text, flags=re.M)}
     assert sizes == {'rlg_adam_desc': 184, 'rlg_ppo_loss_desc': 176, 'rlg_loss_finalize_desc': 80, 'rlg_chain_net': 48,
                      'rlg_chain_fwd': 120, 'rlg_chain_bwd': 96, 'rlg_chain_launch': 32, 'rlg_mlp_dw_desc': 176,
-                     'rlg_lstm_fwd': 80, 'rlg_lstm_bwd': 56, 'rlg_gru_fwd': 72, 'rlg_gru_bwd': 64}
+                     'rlg_lstm_fwd': 80, 'rlg_lstm_bwd': 56, 'rlg_gru_fwd': 72, 'rlg_gru_bwd': 64,
+                     'rlg_post_step_desc': 136, 'rlg_policy_head_desc': 176, 'rlg_categorical_head_desc': 152,
+                     'rlg_discrete_loss_desc': 184}
     assert ctypes.sizeof(_lib.AdamDesc) == sizes['rlg_adam_desc']
     assert ctypes.sizeof(_lib.PpoLossDesc) == sizes['rlg_ppo_loss_desc']
     assert ctypes.sizeof(_lib.LossFinalizeDesc) == sizes['rlg_loss_finalize_desc']
@@ -55,6 +57,10 @@ def test_descriptor_classes_have_the_sizes_the_header_asserts():
     assert ctypes.sizeof(_lib.LstmBwd) == sizes['rlg_lstm_bwd']
     assert ctypes.sizeof(_lib.GruFwd) == sizes['rlg_gru_fwd']
     assert ctypes.sizeof(_lib.GruBwd) == sizes['rlg_gru_bwd']
+    assert ctypes.sizeof(_lib.PostStepDesc) == sizes['rlg_post_step_desc']
+    assert ctypes.sizeof(_lib.PolicyHeadDesc) == sizes['rlg_policy_head_desc']
+    assert ctypes.sizeof(_lib.CategoricalHeadDesc) == sizes['rlg_categorical_head_desc']
+    assert ctypes.sizeof(_lib.DiscreteLossDesc) == sizes['rlg_discrete_loss_desc']
 
 
 def test_host_queries_without_gpu():

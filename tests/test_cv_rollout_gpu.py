@@ -1,6 +1,6 @@
 """The fused rollout of agents with a central value network: the head kernels' value source
-(ops.rollout_policy_head / rollout_categorical_head with `value=` / `value_repeat=`, the `_cv` entries of
-csrc/experience.hip and csrc/rollout_categorical.hip) against the existing entries and a torch restatement, and the
+(ops.rollout_policy_head / rollout_categorical_head with `value=` / `value_repeat=`, the value fields of the two heads'
+descriptors, csrc/experience.hip and csrc/rollout_categorical.hip) against the heads' own column and a torch restatement, and the
 agents' rollout with `fused_rollout` on against off (a2c_common.py:593-617 get_action_values / get_values with a central
 value: the critic's de-normalised value, repeated for the agents of an env), with the step graphs on against off, after
 new critic weights between epochs, and the eligibility rule."""
@@ -80,31 +80,48 @@ def test_policy_head_value_source(N, A):
             others = [t for t in range(H) if t != STEP]
             assert (st['values'][:, others] == -99.0).all()
             if repeat == 1:                                     # the new entry with the heads' own value column
-                a1, v1, st1, _ = _run_cont(h, logstd, noise, vstats, value=h[:, :1], repeat=1, clip=clip)
+                a1, v1, st1, env1 = _run_cont(h, logstd, noise, vstats, value=h[:, :1], repeat=1, clip=clip)
                 assert torch.equal(a1, ref_a) and torch.equal(v1, ref_v)
                 for k in st1:
                     assert torch.equal(st1[k], ref_st[k]), k
+                # value=None travels as a NULL field, for which the entry puts the heads' column 0 itself: every output
+                # and buffer field of that run against the run that names the column
+                a0, v0, st0, env0 = _run_cont(h, logstd, noise, vstats, value=None, clip=clip)
+                assert torch.equal(a0, a1) and torch.equal(v0, v1) and torch.equal(env0, env1)
+                for k in st1:
+                    assert torch.equal(st0[k], st1[k]), k
 
 
 def test_head_entries_reject_value_repeat_below_one():
     from rl_games_amd import _lib
     lib = _lib.load()
     N, A = 8, 2
-    heads, noise = torch.zeros(N, 1 + A, device=DEV), torch.zeros(N, A, device=DEV)
-    st, out = _cont_storage(N, A), torch.empty(N, A, device=DEV)
-    p = [t.data_ptr() for t in (st['actions'], st['mus'], st['sigmas'], st['neglogpacs'], st['values'])]
+    heads, noise = torch.zeros(N, 1 + A, device=DEV), torch.ones(N, A, device=DEV)
+    logstd, st = torch.zeros(A, device=DEV), _cont_storage(N, A)
+    acts, vals = torch.empty(N, A, device=DEV), torch.empty(N, device=DEV)
+    sizes = (ctypes.c_int * 1)(A)
+    cat_acts = torch.empty(N, dtype=torch.int64, device=DEV)
+    cat_buf = torch.empty(N, H, dtype=torch.int64, device=DEV)
     for repeat in (0, -2):
-        err = lib.rlg_rollout_policy_head_cv(heads.data_ptr(), 1 + A, heads.data_ptr(), 1 + A, repeat,
-                                             torch.zeros(A, device=DEV).data_ptr(), noise.data_ptr(), None, None, 1e-5,
-                                             out.data_ptr(), out.data_ptr(), *p, None, None, None, N, H, A, STEP, None)
+        head = _lib.PolicyHeadDesc(
+            heads=heads.data_ptr(), ld=1 + A, value=heads.data_ptr(), ld_value=1 + A, value_repeat=repeat,
+            logstd=logstd.data_ptr(), noise=noise.data_ptr(), eps=1e-5, actions_out=acts.data_ptr(),
+            values_out=vals.data_ptr(), buf_actions=st['actions'].data_ptr(), buf_mus=st['mus'].data_ptr(),
+            buf_sigmas=st['sigmas'].data_ptr(), buf_neglogp=st['neglogpacs'].data_ptr(),
+            buf_values=st['values'].data_ptr(), N=N, H=H, A=A, step=STEP)
+        err = lib.rlg_rollout_policy_head(ctypes.addressof(head), None)
         assert err == 1, err                                    # hipErrorInvalidValue
-        sizes = (ctypes.c_int * 1)(2)
-        acts = torch.empty(N, dtype=torch.int64, device=DEV)
-        err = lib.rlg_rollout_categorical_head_cv(noise.data_ptr(), A, heads.data_ptr(), 1, repeat, sizes, 1,
-                                                  noise.data_ptr(), None, 0, None, None, 1e-5, acts.data_ptr(),
-                                                  out.data_ptr(), acts.data_ptr(), out.data_ptr(), out.data_ptr(), N, H,
-                                                  STEP, None)
+        cat = _lib.CategoricalHeadDesc(
+            logits=heads[:, 1:].data_ptr(), ld_logits=1 + A, branch_sizes=ctypes.addressof(sizes), num_branches=1,
+            exp_noise=noise.data_ptr(), value=heads.data_ptr(), ld_value=1 + A, value_repeat=repeat, eps=1e-5,
+            actions_out=cat_acts.data_ptr(), values_out=vals.data_ptr(), buf_actions=cat_buf.data_ptr(),
+            buf_neglogp=st['neglogpacs'].data_ptr(), buf_values=st['values'].data_ptr(), num_envs=N, horizon=H,
+            step=STEP)
+        err = lib.rlg_rollout_categorical_head(ctypes.addressof(cat), None)
         assert err == 1, err
+    head.value_repeat = cat.value_repeat = 1                    # the same descriptors are launched once the field is valid
+    assert lib.rlg_rollout_policy_head(ctypes.addressof(head), None) == 0
+    assert lib.rlg_rollout_categorical_head(ctypes.addressof(cat), None) == 0
     torch.cuda.synchronize()
 
 
