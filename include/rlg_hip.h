@@ -845,6 +845,46 @@ int rlg_mlp_chain_backward(const rlg_chain_net* net, const rlg_chain_bwd* bwd, c
 int rlg_mlp_chain_step(const rlg_chain_net* net, const rlg_chain_fwd* fwd, const rlg_chain_bwd* bwd,
                        const rlg_chain_launch* launch, void* stream);
 
+/* ---- the chain for trunks whose layers end in a row normalisation (csrc/mlp_chain_ln.hip) ------------------------------
+ * `network.normalization: layer_norm` (rl_games/algos_torch/network_builder.py:105-130): Linear -> activation ->
+ * LayerNorm(width) per hidden layer, a linear head behind them.  Exact f32 products; rlg_chain_net / _fwd / _bwd / _launch
+ * as for rlg_mlp_chain_forward / _backward, plus one descriptor for the normalisations, every array indexed by layer:
+ * forward : act_out[l] receives y_l = (A_l - mean) rstd gamma + beta behind a normalisation (A_l = act(Linear_l) itself
+ *           behind none) - the next layer's input and X of its weight gradient; pre_out[l] receives A_l and stats[l] the
+ *           rows' (mean, rstd) as [rows, 2] fp32: what the backward reads.  Inference: only act_out[last] given.
+ *           mean first, then the centred sum of squares, both in fp64; biased variance; rstd = 1 / sqrt(var + eps).
+ * backward: dY_l = dZ_{l+1} W_{l+1};  g = dY gamma, xhat = (A - mean) rstd, dA = rstd (g - mean_H(g) - xhat mean_H(g xhat))
+ *           (never through y / gamma: a zero gamma is fine);  dZ_l = dA act'(A_l) -> dz_out[l].  act_in[l] is read for
+ *           layers without a normalisation only.  Per workgroup one fp64 row [out_l] of column sums each, plain stores:
+ *           bias_partials (dZ_l), gamma_partials (dY_l xhat_l), beta_partials (dY_l); rows: rlg_mlp_chain_num_blocks(rows,
+ *           resolved groups); finished by rlg_colsum_finalize or rlg_mlp_dw_launch's colsum items.
+ * Fields of the shared descriptors that these kernels do not serve answer hipErrorNotSupported before anything is
+ * launched: rms_batch_or_null, weight_form_or_null, pack_backward_planes_or_null, ppo_loss_or_null, maxima_or_null.
+ * A backward whose A / dZ rows are not 16-byte aligned whole 4-float groups: hipErrorNotSupported as well.
+ * rlg_mlp_chain_ln_groups: the 16-row groups per workgroup (1 / 2 / 4) a launch with groups = 0 runs - from the rows and from
+ * the LDS the widths need (forward: the input plus the output tile of the widest adjacent pair, backward: the widest tile plus
+ * the widest hidden one; a tile: 16 G rows x the width in whole 64-feature k-batches; in 160 KiB) - or 0 for a network outside the envelope: hidden widths that are no multiples of 4, a
+ * width that does not fit with one group, more than 8 layers.  direction as for rlg_mlp_chain_groups (0 inference forward,
+ * 1 backward, 2 training forward).  It also raises the kernels' LDS limit, once per process: call it outside stream
+ * capture before the first captured launch.  Its answer is host arithmetic alone: should raising the limit fail, the launch
+ * entries return that hipError_t. */
+typedef struct rlg_chain_ln {
+  const float* const* gamma;        /* [out_l]; a NULL entry: no normalisation behind this layer (always so for the last) */
+  const float* const* beta;
+  const float* eps;                 /* per layer */
+  float* const* pre_out;            /* A_l [rows, out_l], row strides pre_ld: written by the forward (NULL: inference), read */
+  const long long* pre_ld;          /*   by the backward */
+  float* const* stats;              /* (mean, rstd) [rows, 2] fp32: likewise */
+  double* const* gamma_partials_or_null;   /* backward: [num_blocks, out_l] fp64 */
+  double* const* beta_partials_or_null;
+} rlg_chain_ln;       /* 64 bytes: asserted with RLG_ABI_SIZE where the entries are defined (csrc/mlp_chain_ln.hip) */
+
+int rlg_mlp_chain_ln_groups(int num_layers, const int* in_features, const int* out_features, long long rows, int direction);
+int rlg_mlp_chain_ln_forward(const rlg_chain_net* net, const rlg_chain_fwd* fwd, const rlg_chain_ln* ln,
+                             const rlg_chain_launch* launch, void* stream);
+int rlg_mlp_chain_ln_backward(const rlg_chain_net* net, const rlg_chain_bwd* bwd, const rlg_chain_ln* ln,
+                              const rlg_chain_launch* launch, void* stream);
+
 /* The 16-row launches of a data-parallel rank's minibatches (< 16,384 rows; rollouts of that size) in their LEAN form
  * (round 4; csrc/mlp_chain_lean.hip, mlp_chain_fwd_lean_kernel / mlp_chain_bwd_lean_kernel): the weights as FRAGMENTS (round 6: two fp16 planes of 64 w per group of 32 k values where rounds 4 - 5 had two fp32 chunks - the same bytes; csrc/split_f16.hpp) in
  * the order each of the 8 waves of a workgroup consumes them - one linear stream per wave across blocks and layers, zero

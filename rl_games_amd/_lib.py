@@ -90,6 +90,10 @@ _PROTOTYPES = {
     'rlg_mlp_chain_forward': [_P, _P, _P, _P],       # (ChainNet, ChainFwd, ChainLaunch, stream)
     'rlg_mlp_chain_step': [_P, _P, _P, _P, _P],      # (ChainNet, ChainFwd, ChainBwd, ChainLaunch, stream)
     'rlg_mlp_chain_backward': [_P, _P, _P, _P],      # (ChainNet, ChainBwd, ChainLaunch, stream)
+    # mlp_chain_ln.hip: trunks whose layers end in a layer norm
+    'rlg_mlp_chain_ln_groups': [_c_int, _P, _P, _c_ll, _c_int],
+    'rlg_mlp_chain_ln_forward': [_P, _P, _P, _P, _P],     # (ChainNet, ChainFwd, ChainLn, ChainLaunch, stream)
+    'rlg_mlp_chain_ln_backward': [_P, _P, _P, _P, _P],    # (ChainNet, ChainBwd, ChainLn, ChainLaunch, stream)
     # lean 16-row forward (csrc/mlp_chain_lean.hip, mlp_chain_fwd_lean_kernel)
     'rlg_mlp_chain_frags_bytes': [_c_int, _P, _P, _c_int],
     'rlg_mlp_chain_pack_frags': [_c_int, _P, _P, _P, _P, _c_int, _P, _P],
@@ -293,6 +297,12 @@ class ChainBwd(ctypes.Structure):
     _fields_ = [('act_in', _P), ('act_ld', _P), ('d_out', _P), ('ld_dout', _c_ll), ('dz_out', _P), ('dz_ld', _P),
                 ('bias_partials_or_null', _P), ('ppo_loss_or_null', _P), ('weight_form_or_null', _P),
                 ('maxima_or_null', _P), ('maxima_stride', _c_int), ('maxima_rows_out_or_null', _P)]
+
+
+class ChainLn(ctypes.Structure):
+    """rlg_chain_ln: the layer norms of a chain, every array indexed by layer."""
+    _fields_ = [(n, _P) for n in ('gamma', 'beta', 'eps', 'pre_out', 'pre_ld', 'stats', 'gamma_partials_or_null',
+                                  'beta_partials_or_null')]
 
 
 class ChainLaunch(ctypes.Structure):

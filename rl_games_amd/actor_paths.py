@@ -457,8 +457,8 @@ class Plan:
                 self.why = 'one linear value column only'
             elif net.is_rnn():
                 self.why = rnn_why
-            elif not getattr(net, 'plain_trunk', True):
-                self.why = 'plain Linear + activation trunks only'
+            elif not getattr(net, 'chain_trunk', getattr(net, 'plain_trunk', True)):
+                self.why = 'sequential Linear + activation (+ layer norm) trunks only'
             return
         general = (agent.value_size != 1 or not getattr(net, 'fixed_sigma', True) or not getattr(net, 'plain_sigma', True))
         if general:

@@ -36,8 +36,8 @@ def _value_chain(net, arena, max_rows):
     the optimiser.  Raises NotImplementedError for networks outside the kernels' envelope (the caller keeps autograd)."""
     if not isinstance(net.value_act, nn.Identity) or net.value.out_features != 1:
         raise NotImplementedError('one linear value column only')
-    if not getattr(net, 'plain_trunk', True) or net.is_rnn():
-        raise NotImplementedError('plain Linear + activation trunks only')
+    if not getattr(net, 'chain_trunk', getattr(net, 'plain_trunk', True)) or net.is_rnn():
+        raise NotImplementedError('sequential Linear + activation (+ layer norm) trunks only')
     return ChainNet(net.actor_mlp, [net.value], arena, max_rows)
 
 

@@ -19,6 +19,8 @@ RecurrentChainNet and mlp_engine.ManualMLP alike; each engine keeps its own trun
 Users: the central value network (central_value.py, one value column) and the discrete-action agent (discrete_agent.py:
 [value | logits] behind a shared trunk, or one chain per trunk with `separate: True` as in ppo_cartpole.yaml).  The
 continuous actor's engine is mlp_engine.ManualMLP (loss inside the backward launch, a per-layer trunk mode, HIP graphs).
+Both users' trunks may end their layers in a layer norm (`network.normalization: layer_norm`, norm_trunk): ChainNet then
+runs the chain of csrc/mlp_chain_ln.hip (`ops.MlpChainLn`) and finishes the norms' gradients with the bias gradients.
 RecurrentChainNet is the recurrent engine of the discrete agent and the central value critic: the trunk + gate-input
 product as one chain, then RnnStations, an optional layer norm and the heads.  RecurrentChainPair drives two of them
 - the separate actor / critic trunks of a continuous policy, each with its own RNN - with one paired sequence launch.  The
@@ -68,6 +70,32 @@ def plain_trunk(trunk, identity_ok=True):
     if any(l.out_features % 4 for l in linears):
         raise NotImplementedError('hidden widths must be multiples of 4')
     return linears, name
+
+
+def norm_trunk(trunk):
+    """(linears, norms, activation name) of an nn.Sequential of `Linear, activation[, LayerNorm(width)]` groups with one
+    activation kind - what `network.normalization: layer_norm` builds (policy.build_trunk) and an `ops.MlpChainLn` takes.
+    norms: per layer the nn.LayerNorm behind it or None; a trunk without any is plain_trunk's, with its answers."""
+    mods = list(trunk) if isinstance(trunk, nn.Sequential) else None
+    if mods is None:
+        raise NotImplementedError('sequential trunks only (no D2RL)')
+    plain, norms = [], []
+    for k, m in enumerate(mods):
+        if isinstance(m, nn.LayerNorm):
+            lin = mods[k - 2] if k >= 2 else None
+            if not isinstance(lin, nn.Linear) or isinstance(mods[k - 1], (nn.Linear, nn.LayerNorm)) or norms[-1] is not None:
+                raise NotImplementedError('a layer norm directly behind a Linear + activation pair only')
+            if tuple(m.normalized_shape) != (lin.out_features,) or m.weight is None or m.bias is None:
+                raise NotImplementedError("layer norm over exactly the layer's width, with weight and bias, only")
+            norms[-1] = m
+        elif isinstance(m, nn.modules.batchnorm._BatchNorm):
+            raise NotImplementedError('batch norm runs as torch modules')
+        else:
+            plain.append(m)
+            if isinstance(m, nn.Linear):
+                norms.append(None)
+    linears, name = plain_trunk(plain)
+    return linears, norms, name
 
 
 def head_span(heads, arena):
@@ -317,13 +345,18 @@ class RnnStations:
         return dg, jobs, colsums
 
 
+def _rows_of(buffers, rows):
+    return [None if t is None else t[:rows] for t in buffers]
+
+
 class ChainNet:
-    """trunk: nn.Sequential of Linear + activation pairs; heads: list of nn.Linear over the trunk's output whose
+    """trunk: nn.Sequential of Linear + activation pairs, each optionally followed by an nn.LayerNorm over the layer's
+    width (norm_trunk: such a trunk runs ops.MlpChainLn, one without any norm ops.MlpChain as ever); heads: list of nn.Linear over the trunk's output whose
     weights (and biases) are adjacent in `arena`, in that order (arena_layout) - their columns side by side are the
     chain's last layer.  Raises NotImplementedError for networks outside the kernels' envelope."""
 
     def __init__(self, trunk, heads, arena, max_rows, infer_rows=0):
-        self.linears, name = plain_trunk(trunk)
+        self.linears, self.norms, name = norm_trunk(trunk)
         heads = list(heads)
         if any(h.in_features != self.linears[-1].out_features for h in heads):
             raise NotImplementedError('heads must read the last hidden layer')
@@ -331,7 +364,14 @@ class ChainNet:
         dev = self.head_w.device
         widths = [l.out_features for l in self.linears]
         layers = [(l.weight, l.bias, name) for l in self.linears] + [(self.head_w, self.head_b, 'None')]
-        self.chain = ops.MlpChain(layers, dev, weights_version=arena.weights_token)
+        self.normed = any(m is not None for m in self.norms)
+        if self.normed:
+            # layers that end in a layer norm: the chain of csrc/mlp_chain_ln.hip.  Hs[l] is then y_l, the norm's output -
+            # the next layer's input and X of its weight gradient; the backward reads pre[l] (the activation) and stats[l]
+            norms = [None if m is None else (m.weight, m.bias, m.eps) for m in self.norms] + [None]
+            self.chain = ops.MlpChainLn(layers, norms, dev, weights_version=arena.weights_token)
+        else:
+            self.chain = ops.MlpChain(layers, dev, weights_version=arena.weights_token)
         self.Hs = [torch.empty(max_rows, w, device=dev) for w in widths]
         self.dA = [torch.empty(max_rows, w, device=dev) for w in widths]
         self.heads = torch.empty(max_rows, self.head_cols, device=dev)
@@ -340,6 +380,13 @@ class ChainNet:
         self.infer_heads = torch.empty(infer_rows, self.head_cols, device=dev)
         nb = (max_rows + 15) // 16                          # one partial row per 16-row group at most
         self.partials = [torch.empty(nb * w, dtype=torch.float64, device=dev) for w in widths]
+        if self.normed:
+            def per_norm(make):
+                return [None if m is None else make(w) for m, w in zip(self.norms, widths)]
+            self.pre = per_norm(lambda w: torch.empty(max_rows, w, device=dev))
+            self.stats = per_norm(lambda w: torch.empty(max_rows, 2, device=dev))
+            self.gamma_partials = per_norm(lambda w: torch.empty(nb * w, dtype=torch.float64, device=dev))
+            self.beta_partials = per_norm(lambda w: torch.empty(nb * w, dtype=torch.float64, device=dev))
         self.weight_grads = WeightGrads()
         self._rows = 0
         self._x = None
@@ -357,7 +404,10 @@ class ChainNet:
             x = x.contiguous()
         heads = self.heads[:rows]
         xn = self.xn[:rows] if rms is not None else None
-        self.chain.forward(x, heads, act_out=[h[:rows] for h in self.Hs], rms=rms, eps=eps, xn_out=xn)
+        ln = {}
+        if self.normed:
+            ln = dict(pre_out=_rows_of(self.pre, rows), stats=_rows_of(self.stats, rows))
+        self.chain.forward(x, heads, act_out=[h[:rows] for h in self.Hs], rms=rms, eps=eps, xn_out=xn, **ln)
         self._rows, self._x = rows, (xn if rms is not None else x)
         return heads
 
@@ -384,8 +434,18 @@ class ChainNet:
         d_heads = self.d_heads[:rows]
         nblk = self.chain.num_blocks(rows, 1)
         acts, dzs, parts = trunk_views(self.linears, self.Hs, self.dA, self.partials, rows, nblk)
-        self.chain.backward(d_heads, acts, dzs, parts)
+        if self.normed:
+            gparts, bparts = ([None if p is None else p[:nblk * l.out_features] for p, l in zip(ps, self.linears)]
+                              for ps in (self.gamma_partials, self.beta_partials))
+            self.chain.backward(d_heads, acts, _rows_of(self.pre, rows), _rows_of(self.stats, rows), dzs, parts, gparts, bparts)
+        else:
+            self.chain.backward(d_heads, acts, dzs, parts)
         jobs, colsums = trunk_jobs(self.linears, self._x, acts, dzs, parts, nblk)
+        if self.normed:
+            # the norms' weight / bias gradients: column sums like the bias gradients, finished by the same launch
+            for m, gp, bp in zip(self.norms, gparts, bparts):
+                if m is not None:
+                    colsums += [(gp, nblk, m.weight.numel(), m.weight.grad), (bp, nblk, m.bias.numel(), m.bias.grad)]
         if self.head_cols == 1:
             # one output column - a weighted column sum of the last activations, and the sum of d heads
             torch.mv(acts[-1].t(), d_heads.view(-1), out=self.head_w_grad.view(-1))

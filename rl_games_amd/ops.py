@@ -937,20 +937,13 @@ def _chain_call(kind, entry, *descs, rows, stream, groups=0):
     return err
 
 
-class MlpChain:
-    """The whole MLP (hidden layers + the fused value|mu head as the last layer) as ONE forward and
-    ONE backward launch (csrc/mlp_chain.hip).  `layers`: list of (weight [out, in], bias [out], act
-    name) - tensors are referenced, not copied, so optimiser updates are seen.  Raises
-    NotImplementedError if the network does not fit the LDS even with one 16-row group.
-    products: 'auto' - the library's choice per launch: fp16 plane products under fixed operand scales (the 64-row split
-    kernels, the lean 16-row kernels; |weight| < 1023, |hidden activation| < 4094) wherever they apply - or 'exact': every
-    launch of forward / backward / step takes the exact-f32-product kernels that split_products=False selects, which
-    have the full fp32 range.  The attribute may be set at any time; it is part of cache_state().
-    Derived weight copies (weight_forms.py), both fp16 plane fragments: `planes` (64-row split kernels), `frags` (lean)."""
+class _ChainArgs:
+    """What MlpChain and MlpChainLn share: the rlg_chain_net of `layers` stated once, the builders of the forward and
+    backward descriptors with their shape and alignment validation, the weights token."""
 
     PRODUCTS = ('auto', 'exact')
 
-    def __init__(self, layers, device, weights_version=None, products='auto'):
+    def _state_net(self, layers, device, weights_version):
         self.n = n = len(layers)
         self.layers = layers
         self.device = device
@@ -963,6 +956,79 @@ class MlpChain:
         self._in, self._out = I(*self.ins), I(*self.outs)
         self._act = I(*[ACT_KINDS[a] for _, _, a in layers])
         self._net = _lib.ChainNet(n, *[ctypes.addressof(a) for a in (self._w, self._b, self._in, self._out, self._act)])
+        # callable -> a value that changes whenever the weights do (FlatArena.weights_token)
+        self._weights_version = weights_version
+        self._maxima_slot()
+
+    def _maxima_slot(self):
+        """The host int a backward / step entry answers in: rows per gradient-maxima entry, 0: it left none."""
+        self._maxima_rows = ctypes.c_int(0)
+        self._maxima_rows_at = ctypes.addressof(self._maxima_rows)
+
+    def weights_token(self):
+        return None if self._weights_version is None else self._weights_version()
+
+    def _forward_args(self, x, outs, rms, eps, xn_out, rms_fold):
+        """rlg_chain_fwd without its weight form: pointers and row strides of `outs` (per layer the activation output or
+        None, the heads last), x and its row stride, the normaliser state, eps, xn_out, the five rms_fold pointers."""
+        ptrs = self._P(*[None if t is None else _need(t, F32, 'act_out', contiguous=False) for t in outs])
+        lds = self._L(*[0 if t is None else t.stride(0) for t in outs])
+        _lib.require_gpu(x, 'x')
+        if x.dtype != F32 or (x.dim() == 2 and x.shape[1] != 1 and x.stride(1) != 1):
+            raise ValueError('x: fp32 rows with unit inner stride expected')
+        mean = var = None
+        if rms is not None:
+            mean, var = _need(rms[0], F64, 'running_mean'), _need(rms[1], F64, 'running_var')
+        fold = [None] * 5
+        if rms_fold is not None:
+            if rms is None:
+                raise ValueError('rms_fold needs rms')
+            row, cnt, mean_o, var_o, cnt_o = rms_fold
+            if row.numel() != 2 * self.ins[0] + 1:
+                raise ValueError('rms_fold: moments row of 2*in0+1 doubles expected')
+            fold = [_need(row, F64, 'moments row'), _need(cnt, torch.int64, 'count'), _need(mean_o, F64, 'mean out'),
+                    _need(var_o, F64, 'var out'), _need(cnt_o, torch.int64, 'count out')]
+        fwd = _lib.ChainFwd(ctypes.addressof(ptrs), ctypes.addressof(lds), x.data_ptr(), x.stride(0), mean, var,
+                            float(np.float32(eps)), _opt(xn_out, F32, 'xn_out'), *fold)
+        fwd.arrays = ptrs, lds                          # (alive as long as the descriptor)
+        return fwd
+
+    def _backward_args(self, d_heads, acts, dz_out, bias_partials, ppo_loss):
+        """rlg_chain_bwd without its weight form and maxima: d_heads, per hidden layer H (acts; None for the step entries,
+        which read their forward half's), the dZ output and their row strides, the fp64 bias partials or None, the loss
+        descriptor or None.  The entry's answer about maxima goes to _maxima_rows."""
+        h = hl = None
+        if acts is not None:
+            h = self._P(*([_need(t, F32, 'H', contiguous=False) for t in acts] + [None]))
+            hl = self._L(*([t.stride(0) for t in acts] + [0]))
+        dz = self._P(*([_need(t, F32, 'dz', contiguous=False) for t in dz_out] + [None]))
+        dl = self._L(*([t.stride(0) for t in dz_out] + [0]))
+        bp = None
+        if bias_partials is not None:
+            bp = self._P(*([_need(t, F64, 'bias partials') for t in bias_partials] + [None]))
+        at = ctypes.addressof
+        bwd = _lib.ChainBwd(None if h is None else at(h), None if h is None else at(hl),
+                            _need(d_heads, F32, 'd_heads', contiguous=False), d_heads.stride(0), at(dz), at(dl),
+                            None if bp is None else at(bp), None if ppo_loss is None else at(ppo_loss), None, None, 0,
+                            self._maxima_rows_at)
+        bwd.arrays = h, hl, dz, dl, bp                  # (alive as long as the descriptor)
+        return bwd
+
+
+class MlpChain(_ChainArgs):
+    """The whole MLP (hidden layers + the fused value|mu head as the last layer) as ONE forward and
+    ONE backward launch (csrc/mlp_chain.hip).  `layers`: list of (weight [out, in], bias [out], act
+    name) - tensors are referenced, not copied, so optimiser updates are seen.  Raises
+    NotImplementedError if the network does not fit the LDS even with one 16-row group.
+    products: 'auto' - the library's choice per launch: fp16 plane products under fixed operand scales (the 64-row split
+    kernels, the lean 16-row kernels; |weight| < 1023, |hidden activation| < 4094) wherever they apply - or 'exact': every
+    launch of forward / backward / step takes the exact-f32-product kernels that split_products=False selects, which
+    have the full fp32 range.  The attribute may be set at any time; it is part of cache_state().
+    Derived weight copies (weight_forms.py), both fp16 plane fragments: `planes` (64-row split kernels), `frags` (lean)."""
+
+    def __init__(self, layers, device, weights_version=None, products='auto'):
+        self._state_net(layers, device, weights_version)
+        n = self.n
         lib = _lib.load()
         _lib.check(lib.rlg_mlp_chain_prepare(), 'rlg_mlp_chain_prepare')
         max_groups = {}
@@ -984,6 +1050,8 @@ class MlpChain:
         """Host-side tests: a chain of `n` layers from the library's answers about its shape.  It can launch nothing."""
         c = cls.__new__(cls)
         c.n, c.device, c._in, c._out = n, device, None, None
+        c._weights_version = weights_version
+        c._maxima_slot()
         c._set_shape(max_groups, frag_bytes, lean, weights_version, products)
         return c
 
@@ -991,16 +1059,12 @@ class MlpChain:
         self.max_groups = max_groups
         self._frag_bytes = frag_bytes
         self._lean = lean and frag_bytes[0] >= 0
-        # callable -> a value that changes whenever the weights do (FlatArena.weights_token): the forms' stamp
-        self._weights_version = weights_version
         self.planes = weight_forms.PlanesForm(self._alloc_planes, self._launch_pack_planes, jobs=2 * self.n - 1)
         self.frags = weight_forms.WeightForm(self._alloc_frags, self._launch_pack_frags)
         # split-fp16 backward: per 64-row workgroup the largest magnitude of every dZ tensor (csrc/bx_form.hpp), for the
         # weight-gradient launch that follows it; rows of the last backward that left them
         self._forms_read = {}
         self._grad_maxima = self._maxima_bwd = None
-        self._maxima_rows = ctypes.c_int(0)   # what the last backward / step entry answered: rows per entry, 0: no maxima
-        self._maxima_rows_at = ctypes.addressof(self._maxima_rows)
         self.maxima_rows_per_entry = 64       # 64: left by the 64-row split kernels, 16: by the lean 16-row kernels
         self._products = 'auto'
         self.products = products
@@ -1071,9 +1135,6 @@ class MlpChain:
             routes = [self._route(r, k) for r, k in key[1]]
             self._forms_read[key] = ('lean' in routes, 'split' in routes)
         return self._forms_read[key]
-
-    def weights_token(self):
-        return None if self._weights_version is None else self._weights_version()
 
     def cache_state(self):
         """What the forms hold, for callers that record launches WITHOUT running them (graph capture) and put it back behind
@@ -1150,52 +1211,6 @@ class MlpChain:
 
     def num_blocks(self, rows, direction, requested=0):
         return _lib.load().rlg_mlp_chain_num_blocks(int(rows), self.groups(rows, direction, requested))
-
-    def _forward_args(self, x, outs, rms, eps, xn_out, rms_fold):
-        """rlg_chain_fwd without its weight form: pointers and row strides of `outs` (per layer the activation output or
-        None, the heads last), x and its row stride, the normaliser state, eps, xn_out, the five rms_fold pointers."""
-        ptrs = self._P(*[None if t is None else _need(t, F32, 'act_out', contiguous=False) for t in outs])
-        lds = self._L(*[0 if t is None else t.stride(0) for t in outs])
-        _lib.require_gpu(x, 'x')
-        if x.dtype != F32 or (x.dim() == 2 and x.shape[1] != 1 and x.stride(1) != 1):
-            raise ValueError('x: fp32 rows with unit inner stride expected')
-        mean = var = None
-        if rms is not None:
-            mean, var = _need(rms[0], F64, 'running_mean'), _need(rms[1], F64, 'running_var')
-        fold = [None] * 5
-        if rms_fold is not None:
-            if rms is None:
-                raise ValueError('rms_fold needs rms')
-            row, cnt, mean_o, var_o, cnt_o = rms_fold
-            if row.numel() != 2 * self.ins[0] + 1:
-                raise ValueError('rms_fold: moments row of 2*in0+1 doubles expected')
-            fold = [_need(row, F64, 'moments row'), _need(cnt, torch.int64, 'count'), _need(mean_o, F64, 'mean out'),
-                    _need(var_o, F64, 'var out'), _need(cnt_o, torch.int64, 'count out')]
-        fwd = _lib.ChainFwd(ctypes.addressof(ptrs), ctypes.addressof(lds), x.data_ptr(), x.stride(0), mean, var,
-                            float(np.float32(eps)), _opt(xn_out, F32, 'xn_out'), *fold)
-        fwd.arrays = ptrs, lds                          # (alive as long as the descriptor)
-        return fwd
-
-    def _backward_args(self, d_heads, acts, dz_out, bias_partials, ppo_loss):
-        """rlg_chain_bwd without its weight form and maxima: d_heads, per hidden layer H (acts; None for the step entries,
-        which read their forward half's), the dZ output and their row strides, the fp64 bias partials or None, the loss
-        descriptor or None.  The entry's answer about maxima goes to _maxima_rows."""
-        h = hl = None
-        if acts is not None:
-            h = self._P(*([_need(t, F32, 'H', contiguous=False) for t in acts] + [None]))
-            hl = self._L(*([t.stride(0) for t in acts] + [0]))
-        dz = self._P(*([_need(t, F32, 'dz', contiguous=False) for t in dz_out] + [None]))
-        dl = self._L(*([t.stride(0) for t in dz_out] + [0]))
-        bp = None
-        if bias_partials is not None:
-            bp = self._P(*([_need(t, F64, 'bias partials') for t in bias_partials] + [None]))
-        at = ctypes.addressof
-        bwd = _lib.ChainBwd(None if h is None else at(h), None if h is None else at(hl),
-                            _need(d_heads, F32, 'd_heads', contiguous=False), d_heads.stride(0), at(dz), at(dl),
-                            None if bp is None else at(bp), None if ppo_loss is None else at(ppo_loss), None, None, 0,
-                            self._maxima_rows_at)
-        bwd.arrays = h, hl, dz, dl, bp                  # (alive as long as the descriptor)
-        return bwd
 
     def forward(self, x, heads, act_out=None, rms=None, eps=1e-5, xn_out=None, groups=0, rms_fold=None,
                 split_products=None):
@@ -1304,6 +1319,87 @@ class MlpChain:
         _lib.check(_chain_call(timer, _lib.load().rlg_mlp_chain_backward, self._net, bwd, rows=rows, stream=_stream(d_heads),
                                groups=self.groups(rows, 1, groups)), 'rlg_mlp_chain_backward')
         self._maxima_left(rows)
+
+
+class MlpChainLn(_ChainArgs):
+    """MlpChain's counterpart for a trunk whose layers end in a layer norm (csrc/mlp_chain_ln.hip): Linear -> act ->
+    optional LayerNorm per hidden layer and the linear head(s), as ONE forward and ONE backward launch on exact f32
+    products.  `layers` as for MlpChain; `norms`: per layer (gamma [out], beta [out], eps) or None - None for the last.
+    Tensors are referenced, not copied.  Raises NotImplementedError for a network outside the kernels' envelope
+    (rlg_mlp_chain_ln_groups: hidden widths that are no multiples of 4, a width that does not fit the LDS, > 8 layers).
+    No derived weight copies and one product form: what weight_forms.ChainFormSet asks a chain (products, forms_read,
+    weights_token, cache_state) has the answers of a chain that reads the weights as they are."""
+
+    def __init__(self, layers, norms, device, weights_version=None):
+        if len(norms) != len(layers) or norms[-1] is not None:
+            raise ValueError('MlpChainLn: one entry of `norms` per layer, None for the last')
+        self._state_net(layers, device, weights_version)
+        self.norms, n, P = norms, self.n, self._P
+        for k, nm in enumerate(norms):
+            if nm is not None and (nm[0].numel() != self.outs[k] or nm[1].numel() != self.outs[k]):
+                raise ValueError(f'MlpChainLn: layer norm {k} must span the layer\'s {self.outs[k]} features')
+        self._gamma = P(*[None if nm is None else _need(nm[0], F32, 'gamma') for nm in norms])
+        self._beta = P(*[None if nm is None else _need(nm[1], F32, 'beta') for nm in norms])
+        self._eps = (ctypes.c_float * n)(*[0.0 if nm is None else float(nm[2]) for nm in norms])
+        if any(self.groups(1, d) == 0 for d in ((0, 1) if n > 1 else (0,))):      # (also raises the kernels' LDS limit)
+            raise NotImplementedError('MLP outside the envelope of the layer-norm chain kernels')
+        self.products = 'auto'      # one product form, exact f32: the attribute only travels (ChainFormSet.set_products)
+
+    def forms_read(self, launches):
+        return False, False
+
+    def cache_state(self):
+        return weight_forms.ChainSnapshot(None, None, None, False, self.products)
+
+    def restore_cache_state(self, state):
+        self.products = state.products
+
+    def groups(self, rows, direction, requested=0):
+        """16-row groups per workgroup of a launch: `requested` (1 / 2 / 4), else the library's choice from the rows and the
+        LDS the widths need; 0: outside the envelope.  direction: 0 inference forward, 1 backward, 2 training forward."""
+        if requested in (1, 2, 4):
+            return requested
+        return int(_lib.load().rlg_mlp_chain_ln_groups(self.n, self._in, self._out, int(rows), int(direction)))
+
+    def num_blocks(self, rows, direction, requested=0):
+        return _lib.load().rlg_mlp_chain_num_blocks(int(rows), self.groups(rows, direction, requested))
+
+    def _ln_args(self, pre, stats, gamma_partials=None, beta_partials=None):
+        """rlg_chain_ln: per layer (None where there is no norm) A's buffer, the row statistics, the two partial arrays."""
+        def table(ts, dtype, name, contiguous=True):
+            if ts is None:
+                return None
+            return self._P(*[None if t is None else _need(t, dtype, name, contiguous) for t in list(ts) + [None] * (self.n - len(ts))])
+        pp, sp = table(pre, F32, 'pre_out', False), table(stats, F32, 'stats')
+        gp, bp = table(gamma_partials, F64, 'gamma partials'), table(beta_partials, F64, 'beta partials')
+        pl = None if pre is None else self._L(*[0 if t is None else t.stride(0) for t in list(pre) + [None] * (self.n - len(pre))])
+        at = ctypes.addressof
+        ln = _lib.ChainLn(at(self._gamma), at(self._beta), at(self._eps), *[None if a is None else at(a) for a in (pp, pl, sp, gp, bp)])
+        ln.arrays = pp, pl, sp, gp, bp                  # (alive as long as the descriptor)
+        return ln
+
+    def forward(self, x, heads, act_out=None, pre_out=None, stats=None, rms=None, eps=1e-5, xn_out=None, groups=0):
+        """x [rows, in0] (row stride free), heads [rows, out_last] out.  Training: act_out per hidden layer [rows, out_l]
+        (the layer's output: y behind a norm), pre_out / stats per hidden layer - [rows, out_l] for the activation in front
+        of the norm and [rows, 2] for (mean, rstd), None where there is no norm.  rms = (running_mean, running_var) fp64:
+        the observations are normalised on the way in, the state as it is (xn_out optionally receives them)."""
+        rows = x.shape[0]
+        outs = list(act_out) if act_out is not None else [None] * (self.n - 1)
+        fwd = self._forward_args(x, outs + [heads], rms, eps, xn_out, None)
+        ln = self._ln_args(pre_out, stats)
+        _lib.check(_chain_call('fwd_train' if act_out is not None else 'fwd_infer', _lib.load().rlg_mlp_chain_ln_forward,
+                               self._net, fwd, ln, rows=rows, stream=_stream(x), groups=groups), 'rlg_mlp_chain_ln_forward')
+
+    def backward(self, d_heads, acts, pre, stats, dz_out, bias_partials=None, gamma_partials=None, beta_partials=None,
+                 groups=0):
+        """d_heads [rows, out_last]; per hidden layer: acts (the forward's act_out), pre / stats (the forward's, None where
+        there is no norm), the dZ_l output, and fp64 [num_blocks(rows, 1), out_l] partials of the bias gradient and - normed
+        layers - of the norm's weight and bias gradients."""
+        rows = d_heads.shape[0]
+        bwd = self._backward_args(d_heads, acts, dz_out, bias_partials, None)
+        ln = self._ln_args(pre, stats, gamma_partials, beta_partials)
+        _lib.check(_chain_call('bwd', _lib.load().rlg_mlp_chain_ln_backward, self._net, bwd, ln, rows=rows,
+                               stream=_stream(d_heads), groups=groups), 'rlg_mlp_chain_ln_backward')
 
 
 # ------------------------------------------------------------------ MLP weight gradients (MFMA)

@@ -147,10 +147,11 @@ def build_trunk(input_size, units, activation, norm_func_name=None, norm_only_fi
 
 class ActorCriticNetwork(nn.Module):
     """`a2c_network`: MLP trunk (+ optional RNN) with mu / value heads.  The plain layouts - Linear + activation trunks,
-    a single-layer LSTM behind the trunk - run on this library's fused kernels (`plain_trunk`); layer normalisation, D2RL
-    trunks, an RNN in front of the MLP, concatenated RNN inputs / outputs and layer norm behind the RNN (round 6) are
-    built like the reference builds them and run as torch modules with autograd between the HIP rollout, dataset, loss
-    and optimiser kernels."""
+    a single-layer LSTM behind the trunk - run on this library's fused kernels (`plain_trunk`), and so do feed-forward
+    sequential trunks with layer normalisation for the discrete agent and the central value critic (`chain_trunk`);
+    layer normalisation elsewhere, D2RL trunks, an RNN in front of the MLP, concatenated RNN inputs / outputs and layer
+    norm behind the RNN (round 6) are built like the reference builds them and run as torch modules with autograd
+    between the HIP rollout, dataset, loss and optimiser kernels."""
 
     def __init__(self, net_params, actions_num, input_shape, value_size=1, num_seqs=1):
         super().__init__()
@@ -266,6 +267,10 @@ class ActorCriticNetwork(nn.Module):
                               not (self.rnn_before_mlp or self.rnn_concat_input or self.rnn_concat_output))
         self.plain_trunk_rnn_ln = plain_but_separate and not (self.separate and self.has_rnn)
         self.plain_trunk = self.plain_trunk_rnn_ln and not self.rnn_ln
+        # ... a feed-forward sequential trunk, plain or with `normalization: layer_norm`: what chain_net.ChainNet takes
+        # (the discrete agent, the central value critic); it looks at the modules itself (chain_net.norm_trunk)
+        self.chain_trunk = (not self._trunk_kw['d2rl'] and self._trunk_kw['norm_func_name'] in (None, 'layer_norm')
+                            and not self.has_rnn)
         # ... plain but for separate trunks that each have an RNN (and maybe a layer norm) of their own: what
         # chain_net.RecurrentChainPair takes (the continuous agent)
         self.plain_separate_rnn = plain_but_separate and self.separate and self.has_rnn
