@@ -1091,6 +1091,30 @@ int rlg_narrow_dw_blocks(long long rows);
 int rlg_narrow_dw(const float* dz, long long lddz, const float* x, long long ldx, float* grad, double* partials,
                   long long rows, int out_features, int in_features, void* stream);
 
+/* ---- weight gradients of layers whose widths are no multiples of 4 (csrc/mlp_dw_ragged.hip) ---------------------
+ * grad [out, in] = dZ [rows, out]^T X [rows, in] - grad_output.t().mm(input) of a first nn.Linear over 9, 17, 98 ...
+ * observations (network_builder.py:118-147), which rlg_mlp_dw_launch does not take.  out 1 .. 1024, in 1 .. 512, rows
+ * 1 .. 2^30; dz and x dense row-major (row stride = width); dz, x, grad and workspace 16-byte aligned.  Exact fp32
+ * products on v_mfma_f32_16x16x4_f32, fp32 sums inside a workgroup's run of rows, the workgroups' partial tiles summed in
+ * index order in fp64 by a second kernel of the same call: no atomics, the same inputs give the same bits.  Nothing
+ * behind row `rows` of dz and x is read.
+ *   rlg_mlp_dw_ragged_workspace: floats of workspace a call needs (host arithmetic), or 0 outside the envelope.
+ *   rlg_mlp_dw_ragged: two launches, no synchronisation.  A shape or an alignment outside the envelope:
+ *     hipErrorNotSupported (801), nothing launched - the caller keeps its library product.  A NULL pointer or a
+ *     workspace of fewer than rlg_mlp_dw_ragged_workspace floats: hipErrorInvalidValue. */
+typedef struct rlg_dw_ragged {
+  const float* dz;                  /* [rows, out_features] */
+  const float* x;                   /* [rows, in_features] */
+  float* grad;                      /* [out_features, in_features], every element written */
+  float* workspace;                 /* every float that is read was written by the same call */
+  long long workspace_floats;
+  long long rows;
+  int out_features, in_features;
+} rlg_dw_ragged;      /* 56 bytes: asserted with RLG_ABI_SIZE where the entries are defined (csrc/mlp_dw_ragged.hip) */
+
+long long rlg_mlp_dw_ragged_workspace(long long rows, int out_features, int in_features);
+int rlg_mlp_dw_ragged(const rlg_dw_ragged* desc, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * In-graph gradient all-reduce over peer-mapped device memory (csrc/ipc_allreduce.hip)
  *   replaces dist.all_reduce(SUM) of the flattened gradients in A2CBase.trancate_gradients_and_step

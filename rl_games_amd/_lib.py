@@ -80,6 +80,9 @@ _PROTOTYPES = {
     'rlg_narrow_dx': [_P, _c_ll, _P, _P, _c_ll, _c_ll, _c_int, _c_int, _P],
     'rlg_narrow_dw_blocks': [_c_ll],
     'rlg_narrow_dw': [_P, _c_ll, _P, _c_ll, _P, _P, _c_ll, _c_int, _c_int, _P],
+    # mlp_dw_ragged.hip: widths that are no multiples of 4
+    'rlg_mlp_dw_ragged_workspace': [_c_ll, _c_int, _c_int],
+    'rlg_mlp_dw_ragged': [_P, _P],                   # (DwRagged, stream)
     # mlp_chain.hip
     'rlg_mlp_chain_prepare': [],
     'rlg_mlp_chain_groups': [_c_ll, _c_int, _c_int],
@@ -179,7 +182,7 @@ def exported_prototypes():
 
 
 _RETURNS_LONG_LONG = {'rlg_mlp_dw_plan', 'rlg_stats_sync_flat_size', 'rlg_mlp_chain_planes_bytes', 'rlg_mlp_chain_planes_offset',
-                      'rlg_mlp_chain_frags_bytes'}
+                      'rlg_mlp_chain_frags_bytes', 'rlg_mlp_dw_ragged_workspace'}
 
 
 def load():
@@ -320,6 +323,12 @@ class MlpDwDesc(ctypes.Structure):
                 + [('grad_scale', _c_float), ('step_counter_or_null', _P), ('finalize_blocks_out_or_null', _P),
                    ('maxima_or_null', _P), ('maxima_stride', _c_int), ('maxima_rows_per_entry', _c_int),
                    ('dz_slot', _P), ('x_scale', _P)])
+
+
+class DwRagged(ctypes.Structure):
+    """rlg_dw_ragged: one weight gradient of rlg_mlp_dw_ragged."""
+    _fields_ = ([(n, _P) for n in ('dz', 'x', 'grad', 'workspace')]
+                + [('workspace_floats', _c_ll), ('rows', _c_ll), ('out_features', _c_int), ('in_features', _c_int)])
 
 
 class LstmFwd(ctypes.Structure):

@@ -127,14 +127,16 @@ class WeightGrads:
     gradients in the arena.  Everything inside the envelope of the MFMA launch (csrc/mlp_dw.hip: input columns a
     multiple of 4, contiguous 16-byte aligned operands, at most _DW_MAX_ITEMS matrices) is ONE `ops.MlpDwPlan` launch,
     the heaviest matrix's blocks first; its finalise launch also finishes up to _DW_MAX_ITEMS bias column sums and the
-    PPO loss partials.  What is left - a first layer over 9 state features, say - is a library product each, or with
-    `narrow` the narrow kernel of csrc/mlp_narrow.hip where it applies (the two give different bits).
+    PPO loss partials.  What is left - a first layer over 9 state features, say - is a launch each: with `narrow` the
+    narrow kernel of csrc/mlp_narrow.hip where it applies, else with `ragged` the MFMA kernel for widths off a multiple
+    of 4 (csrc/mlp_dw_ragged.hip: GPU tensors, dense, 16-byte aligned, ops.ragged_dw_supported), else a library product
+    (the three give different bits).
     mfma=False: no MFMA launch at all.  Plans (and the shapes the launch declined) are kept per shape key.
     form: the product form of the MFMA launch (ops.MlpDwPlan.launch) - None: the library's choice, 'exact': f32 products
     whatever maxima the step carries (an agent on `chain_products: exact`)."""
 
-    def __init__(self, mfma=True, narrow=False):
-        self.mfma, self.narrow = bool(mfma), bool(narrow)
+    def __init__(self, mfma=True, narrow=False, ragged=True):
+        self.mfma, self.narrow, self.ragged = bool(mfma), bool(narrow), bool(ragged)
         self.form = None
         self._plans = {}
         self.last_dw_path = None            # 'mfma' / 'library': whether the last finish() had an MFMA launch
@@ -197,6 +199,9 @@ class WeightGrads:
             if (self.narrow and g.shape[1] <= ops.NARROW_MAX and g.shape[0] <= 256 and dz.stride(1) == 1
                     and x.stride(1) == 1 and g.is_contiguous()):
                 ops.narrow_dw(dz, x, g)            # a first layer over a few observations (obs 3)
+            elif (self.ragged and g.is_cuda and all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in (dz, x, g))
+                    and ops.ragged_dw_supported(dz.shape[0], g.shape[0], g.shape[1])):
+                ops.ragged_dw(dz, x, g)            # a first layer over 98 observations (SMAC), 17, 105 (MuJoCo)
             else:
                 torch.mm(dz.t(), x, out=g)
                 self.last_dw_library_jobs += 1

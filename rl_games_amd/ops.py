@@ -905,6 +905,46 @@ def narrow_dw(dz, x, grad):
                                  _narrow_scratch[key].data_ptr(), rows, No, Mi, _stream(dz)), 'rlg_narrow_dw')
 
 
+_ragged_scratch = {}
+
+
+# the shortest minibatch at which the kernel was measured to beat the library product on the device; at 2,560 and 4,096
+# rows it takes 1.6 times as long, between 4,096 and 20,480 nothing is measured (profiles/dw_ragged.txt)
+RAGGED_MIN_ROWS = 20480
+
+
+def ragged_dw_supported(rows, No, Mi):
+    """Whether grad [No, Mi] = dz[rows, No].T @ x[rows, Mi] should go to csrc/mlp_dw_ragged.hip: inside its envelope (No
+    1 .. 1024, Mi 1 .. 512: rlg_mlp_dw_ragged_workspace > 0) and at least RAGGED_MIN_ROWS rows, below which the library
+    product is the faster one.  ragged_dw itself runs the whole envelope."""
+    return rows >= RAGGED_MIN_ROWS and _lib.load().rlg_mlp_dw_ragged_workspace(rows, No, Mi) > 0
+
+
+def ragged_dw(dz, x, grad):
+    """grad [out, in] = dz[rows, out].T @ x[rows, in] for widths that need not be multiples of 4 (csrc/mlp_dw_ragged.hip):
+    exact fp32 products on the matrix cores, bit-reproducible.  dz and x dense (row stride = width), every base pointer
+    16-byte aligned.  NotImplementedError: outside the kernel's envelope (hipErrorNotSupported), nothing was launched."""
+    rows, No = dz.shape
+    Mi = x.shape[1]
+    if x.shape[0] != rows or tuple(grad.shape) != (No, Mi) or dz.stride(1) != 1 or x.stride(1) != 1:
+        raise ValueError('ragged_dw: shape mismatch')
+    _lib.require_gpu(dz, 'dz')
+    lib = _lib.load()
+    need = lib.rlg_mlp_dw_ragged_workspace(rows, No, Mi)
+    if need <= 0 or not (dz.is_contiguous() and x.is_contiguous()):
+        raise NotImplementedError(f'ragged_dw: [{rows} x {No}]^T [{rows} x {Mi}] with strides {dz.stride()}, {x.stride()} is '
+                                  f'outside the kernel\'s envelope')
+    key = (str(dz.device), need)
+    if key not in _ragged_scratch:          # (fixed address per shape: the launches are replayed from HIP graphs)
+        _ragged_scratch[key] = torch.empty(need, dtype=F32, device=dz.device)
+    desc = _lib.DwRagged(_need(dz, F32, 'dz'), _need(x, F32, 'x'), _need(grad, F32, 'grad'),
+                         _ragged_scratch[key].data_ptr(), need, rows, No, Mi)
+    err = lib.rlg_mlp_dw_ragged(ctypes.addressof(desc), _stream(dz))
+    if err == 801:
+        raise NotImplementedError('ragged_dw: operands outside the kernel\'s envelope (16-byte aligned base pointers)')
+    _lib.check(err, 'rlg_mlp_dw_ragged')
+
+
 # ------------------------------------------------------------------ fused MLP chain (MFMA, LDS-resident)
 
 chain_timers = None     # bench.py: {'fwd': [...], 'bwd': [...]} of gae.HipEventPair, one per eager chain launch
