@@ -885,6 +885,35 @@ int rlg_mlp_chain_ln_forward(const rlg_chain_net* net, const rlg_chain_fwd* fwd,
 int rlg_mlp_chain_ln_backward(const rlg_chain_net* net, const rlg_chain_bwd* bwd, const rlg_chain_ln* ln,
                               const rlg_chain_launch* launch, void* stream);
 
+/* ---- separate actor / critic MLPs as one twin-trunk chain (csrc/mlp_chain_twin.hip) ------------------------------------
+ * `network.separate: True` without an RNN (rl_games/algos_torch/network_builder.py:224-311: actor_mlp -> mu, critic_mlp ->
+ * value over the same observations): one workgroup per row tile reads and normalises the observations once and runs both
+ * trunks on them, the actor's first.  Exact f32 products.  One rlg_chain_net per trunk (hidden layers + the head as the
+ * last layer); the forward and backward halves are the descriptors of rlg_mlp_chain_forward / _backward, one per trunk:
+ * forward : the observations, the normaliser state and its fold (rms_batch_or_null, as for rlg_mlp_chain_forward) and
+ *           xn_out are read from actor_fwd; critic_fwd may repeat x / ldx, its other input fields are not read (a fold or
+ *           an xn_out there: hipErrorInvalidValue).  act_out[last] of each half receives that trunk's head through its own
+ *           row stride - mu at heads + 1 and the value at heads of one [rows, 1 + A] array gives the joint row
+ *           [value | mu] that rlg_rollout_policy_head and rlg_ppo_loss_fused read.  Hidden act_out given: training.
+ * backward: d_out / ld_dout of each half is d loss / d head of that trunk; act_in, dz_out, bias_partials per hidden layer
+ *           as for rlg_mlp_chain_backward ([rlg_mlp_chain_num_blocks(rows, resolved groups), out_l] fp64 rows, plain
+ *           stores).  No dX of the observations.  H / dZ rows that are not 16-byte aligned whole 4-float groups:
+ *           hipErrorNotSupported.
+ * weight_form_or_null, pack_backward_planes_or_null, ppo_loss_or_null, maxima_or_null: hipErrorNotSupported, nothing is
+ * launched.  A malformed network is hipErrorInvalidValue, one outside the envelope hipErrorNotSupported.
+ * rlg_mlp_chain_twin_supported: the 16-row groups per workgroup (1 / 2 / 4) a launch with groups = 0 runs - 2 from 8,192
+ * rows, 4 from 16,384, while two workgroups fit a CU's LDS - or 0, launching nothing, outside the envelope: each trunk 1 to
+ * 4 hidden layers, one activation kind (elu / relu / tanh) in both, hidden widths multiples of 4 up to 512 that fit the
+ * LDS with one group, identity heads, one value column, no layer norm (a non-NULL gamma in either rlg_chain_ln).  Only the
+ * shapes and activation kinds of the nets are read.  direction: 0 inference forward, 1 backward, 2 training forward.  It also
+ * raises the kernels' LDS limit, once per process: call it outside stream capture before the first captured launch. */
+int rlg_mlp_chain_twin_supported(const rlg_chain_net* actor, const rlg_chain_net* critic, const rlg_chain_ln* actor_ln_or_null,
+                                 const rlg_chain_ln* critic_ln_or_null, long long rows, int direction);
+int rlg_mlp_chain_twin_forward(const rlg_chain_net* actor, const rlg_chain_net* critic, const rlg_chain_fwd* actor_fwd,
+                               const rlg_chain_fwd* critic_fwd, const rlg_chain_launch* launch, void* stream);
+int rlg_mlp_chain_twin_backward(const rlg_chain_net* actor, const rlg_chain_net* critic, const rlg_chain_bwd* actor_bwd,
+                                const rlg_chain_bwd* critic_bwd, const rlg_chain_launch* launch, void* stream);
+
 /* The 16-row launches of a data-parallel rank's minibatches (< 16,384 rows; rollouts of that size) in their LEAN form
  * (round 4; csrc/mlp_chain_lean.hip, mlp_chain_fwd_lean_kernel / mlp_chain_bwd_lean_kernel): the weights as FRAGMENTS (round 6: two fp16 planes of 64 w per group of 32 k values where rounds 4 - 5 had two fp32 chunks - the same bytes; csrc/split_f16.hpp) in
  * the order each of the 8 waves of a workgroup consumes them - one linear stream per wave across blocks and layers, zero

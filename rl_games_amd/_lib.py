@@ -97,6 +97,10 @@ _PROTOTYPES = {
     'rlg_mlp_chain_ln_groups': [_c_int, _P, _P, _c_ll, _c_int],
     'rlg_mlp_chain_ln_forward': [_P, _P, _P, _P, _P],     # (ChainNet, ChainFwd, ChainLn, ChainLaunch, stream)
     'rlg_mlp_chain_ln_backward': [_P, _P, _P, _P, _P],    # (ChainNet, ChainBwd, ChainLn, ChainLaunch, stream)
+    # mlp_chain_twin.hip: separate actor / critic MLPs, both trunks per row tile
+    'rlg_mlp_chain_twin_supported': [_P, _P, _P, _P, _c_ll, _c_int],   # (ChainNet x 2, ChainLn or NULL x 2, rows, direction)
+    'rlg_mlp_chain_twin_forward': [_P, _P, _P, _P, _P, _P],    # (ChainNet x 2, ChainFwd x 2, ChainLaunch, stream)
+    'rlg_mlp_chain_twin_backward': [_P, _P, _P, _P, _P, _P],   # (ChainNet x 2, ChainBwd x 2, ChainLaunch, stream)
     # lean 16-row forward (csrc/mlp_chain_lean.hip, mlp_chain_fwd_lean_kernel)
     'rlg_mlp_chain_frags_bytes': [_c_int, _P, _P, _c_int],
     'rlg_mlp_chain_pack_frags': [_c_int, _P, _P, _P, _P, _c_int, _P, _P],

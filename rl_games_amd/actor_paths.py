@@ -1,5 +1,5 @@
 """Which engine runs an agent's network: one object per way of running the actor, chosen once when the agent is built
-- engine, pair, chains, recurrent, autograd or general; the table with each path's conditions: DESIGN.md 4.1a.
+- engine, pair, twin, chains, recurrent, autograd or general; the table with each path's conditions: DESIGN.md 4.1a.
 The choice has two phases, because the arena layout must exist before FlatAdam and the engine after it: a Plan holds the
 path's class, the layout and the reason a faster path was declined; Plan.build makes the path once the optimiser exists.
 A path answers what the agents need to know about their network: the engines that finish weight gradients, the chains
@@ -11,7 +11,8 @@ import torch
 from torch import nn
 
 from . import ops
-from .chain_net import ChainNet, RecurrentChainNet, RecurrentChainPair, arena_layout, rnn_cell_declined
+from .chain_net import (ChainNet, RecurrentChainNet, RecurrentChainPair, TwinChainNet, arena_layout, plain_trunk,
+                        rnn_cell_declined)
 from .mlp_engine import ManualMLP
 from .normalizers import launch_stats
 from .weight_forms import _ChainForms
@@ -337,6 +338,73 @@ class PairPath(AutogradPath):
         self.pair.backward()
 
 
+class TwinPath(AutogradPath):
+    """Separate actor / critic MLPs of a continuous policy without an RNN on chain_net.TwinChainNet - update and rollout:
+    one forward launch for both trunks (the observations read and normalised once), the continuous loss launch writing
+    d mu / d value into the engine's two d_heads, one backward launch, the weight gradients.  Updates stay eager: the step
+    graphs alone read its chain."""
+    kind = 'twin'
+    rollout_ok = property(lambda self: fp32_space(self.agent.observation_space))
+
+    @staticmethod
+    def declined(net):
+        """Why a pair of plain trunks stays off the twin chain (None: it is eligible) - the kernel's envelope
+        (rlg_mlp_chain_twin_supported) but for the LDS, which the library answers when the engine is built: asked in front
+        of the optimiser, so that a declined network keeps the arena order it always had."""
+        if not all(isinstance(a, nn.Identity) for a in (net.mu_act, net.value_act, net.sigma_act)):
+            return 'identity head activations only'
+        try:
+            trunks = [plain_trunk(t, identity_ok=False) for t in (net.actor_mlp, net.critic_mlp)]
+        except NotImplementedError as e:
+            return str(e)
+        if trunks[0][1] != trunks[1][1]:
+            return 'one activation kind in both trunks'
+        if any(not 1 <= len(ls) <= 4 or any(l.out_features > 512 for l in ls) for ls, _ in trunks):
+            return '1 to 4 hidden layers of at most 512 units per trunk'
+        return None
+
+    @staticmethod
+    def layout(net):
+        """The matrices first, each trunk's bias vectors directly behind them, the head biases last (PairPath.layout)."""
+        first = [m.bias for trunk in (net.actor_mlp, net.critic_mlp) for m in trunk if isinstance(m, nn.Linear)]
+        return arena_layout(list(net.parameters()), [[net.mu], [net.value]], first_vectors=first)
+
+    def __init__(self, agent):
+        super().__init__(agent)
+        net = agent.model.a2c_network
+        self.twin = TwinChainNet(net.actor_mlp, net.mu, net.critic_mlp, net.value, agent.optimizer, agent.minibatch_size,
+                                 infer_rows=agent.num_actors * agent.num_agents)
+        self.twin.head_bias_done = True          # (update(): the loss finalise launch leaves them)
+        self.engines = [self.twin]
+
+    def takes(self, obs):
+        return obs.dtype == torch.float32          # (the chain reads the observations raw)
+
+    def infer(self, obs, rnn_states, logits_only=False):
+        """Joint heads [rows, 1 + A] ([value | mu]) of a rollout step, the normaliser in eval mode inside the launch."""
+        a = self.agent
+        return self.twin.infer(_unit_stride(obs), a._obs_rms(), a._obs_eps())
+
+    values = EnginePath.values
+
+    @torch.no_grad()
+    def update(self, inp, row):
+        a, twin = self.agent, self.twin
+        net = a.model.a2c_network
+        obs = a._preproc_obs(inp['obs'])
+        a.optimizer.zero_grad()
+        rms, eps = launch_stats(self._stats_module(), obs)         # statistics first (models.py:54-56)
+        heads = twin.forward(obs, rms, eps)
+        mb = heads.shape[0]
+        mu, d_mu, d_value = heads[:, 1:], twin.d_heads[0][:mb], twin.d_heads[1][:mb, 0]
+        args, fin = a._ppo_loss_setup(inp, mu, net.sigma, heads[:, 0], d_mu, d_value)
+        ops.ppo_loss_fused(*args)
+        ops.ppo_loss_finalize(*fin(ops.ppo_loss_blocks(mb), row, net.mu.bias.grad, net.value.bias.grad))
+        twin.backward()
+        a._norm_ready = None
+        a._diag_update(inp, (mu, net.sigma))
+
+
 class ChainsPath(AutogradPath):
     """A feed-forward discrete network on the fused chain kernels: one ChainNet over [value | logits] behind a shared
     trunk, one per trunk with `separate: True` ([logits], [value])."""
@@ -473,6 +541,13 @@ class Plan:
             self.why = PairPath.declined(agent, config, general)
             if self.why is None:
                 self.layout = PairPath.layout(net) + rest
+        elif (net.is_separate_critic() and not net.is_rnn() and not general and getattr(net, 'plain_trunk', True)
+                and config.get('fused_mlp', True) and config.get('manual_mlp', True)):
+            self.cls = TwinPath
+            self.notice = 'separate MLP trunks outside the twin chain kernel ({}); using autograd'
+            self.why = TwinPath.declined(net)
+            if self.why is None:
+                self.layout = TwinPath.layout(net) + rest
 
     def build(self, agent):
         """Behind the optimiser: the planned path, or - declined, or its engine refuses the network - the notice and

@@ -23,7 +23,8 @@ Both users' trunks may end their layers in a layer norm (`network.normalization:
 runs the chain of csrc/mlp_chain_ln.hip (`ops.MlpChainLn`) and finishes the norms' gradients with the bias gradients.
 RecurrentChainNet is the recurrent engine of the discrete agent and the central value critic: the trunk + gate-input
 product as one chain, then RnnStations, an optional layer norm and the heads.  RecurrentChainPair drives two of them
-- the separate actor / critic trunks of a continuous policy, each with its own RNN - with one paired sequence launch.  The
+- the separate actor / critic trunks of a continuous policy, each with its own RNN - with one paired sequence launch;
+TwinChainNet runs such a policy's two trunks WITHOUT an RNN on the twin-trunk chain (`ops.MlpChainTwin`).  The
 agents' rollout graphs read these chains too; they hold no pack launch, so the agent brings each chain's weight fragments
 / planes up to date in front of a replay along with its other chains (weight_forms.ChainFormSet.before_replay).
 """
@@ -744,3 +745,93 @@ class RecurrentChainPair:
         self._sequence('backward', a_args, b_args, self._T)
         self.actor.backward_post_rnn()
         self.critic.backward_post_rnn()
+
+
+class TwinChainNet:
+    """Separate actor / critic MLPs of a continuous policy without an RNN (`separate: True`, network_builder.py:224-311)
+    on the twin-trunk chain (csrc/mlp_chain_twin.hip, `ops.MlpChainTwin`): ONE forward launch reads and normalises the
+    observations once and runs both trunks, ONE backward launch runs the d mu chain through the actor trunk and the
+    d value chain through the critic trunk; every weight gradient of both trunks and both heads is one WeightGrads.finish
+    (two for more than _DW_MAX_ITEMS matrices).  The heads land in one joint row [value | mu]: `heads` of the last
+    forward(), `joint_heads` of the last infer() - what ops.rollout_policy_head and the PPO loss launch read.  The loss
+    launch writes d mu / d value into `d_heads` = (actor's [rows, A], critic's [rows, 1]).
+    actor_mlp / critic_mlp: nn.Sequential of Linear + activation pairs, one activation kind in both; mu / value: the
+    nn.Linear heads.  Raises NotImplementedError for networks outside the kernels' envelope."""
+
+    def __init__(self, actor_mlp, mu, critic_mlp, value, arena, max_rows, infer_rows=0):
+        trunks = [norm_trunk(t) for t in (actor_mlp, critic_mlp)]
+        if trunks[0][2] != trunks[1][2] or trunks[0][2] == 'None':
+            raise NotImplementedError('one activation kind among elu / relu / tanh in both trunks')
+        self.linears = [t[0] for t in trunks]
+        self.head_mods = [mu, value]
+        if any(h.in_features != ls[-1].out_features for h, ls in zip(self.head_mods, self.linears)) or value.out_features != 1:
+            raise NotImplementedError('mu and one value column over the last hidden layers')
+        name, dev = trunks[0][2], mu.weight.device
+        layers = [[(l.weight, l.bias, name) for l in ls] + [(h.weight, h.bias, 'None')]
+                  for ls, h in zip(self.linears, self.head_mods)]
+        norms = [[None if m is None else (m.weight, m.bias, m.eps) for m in t[1]] + [None] for t in trunks]
+        self.chain = ops.MlpChainTwin(layers[0], layers[1], dev, weights_version=arena.weights_token, norms=norms)
+        A = mu.out_features
+        nb = (max_rows + 15) // 16                          # one partial row per 16-row group at most
+        self.Hs = [[torch.empty(max_rows, l.out_features, device=dev) for l in ls] for ls in self.linears]
+        self.dA = [[torch.empty(max_rows, l.out_features, device=dev) for l in ls] for ls in self.linears]
+        self.partials = [[torch.empty(nb * l.out_features, dtype=torch.float64, device=dev) for l in ls] for ls in self.linears]
+        self.heads = torch.empty(max_rows, 1 + A, device=dev)
+        self.joint_heads = torch.empty(max(int(infer_rows), 1), 1 + A, device=dev)
+        self.d_heads = (torch.empty(max_rows, A, device=dev), torch.empty(max_rows, 1, device=dev))
+        self.xn = torch.empty(max_rows, self.linears[0][0].in_features, device=dev)
+        self.weight_grads = WeightGrads()
+        self.head_bias_done = False         # the loss finalise launch writes the heads' bias gradients (actor_paths.TwinPath)
+        self._rows = 0
+        self._x = None
+
+    @property
+    def last_dw_path(self):
+        return self.weight_grads.last_dw_path
+
+    @torch.no_grad()
+    def forward(self, x, rms, eps, rms_fold=None):
+        """x [rows, in] RAW observations; rms = (running_mean, running_var) or None, rms_fold as for ops.MlpChain.forward.
+        Returns the joint heads [rows, 1 + A] and keeps what backward() reads."""
+        rows = x.shape[0]
+        if not x.is_contiguous():
+            x = x.contiguous()
+        heads = self.heads[:rows]
+        xn = self.xn[:rows] if rms is not None else None
+        self.chain.forward(x, heads[:, 1:], heads[:, :1], act_out=[[h[:rows] for h in hs] for hs in self.Hs], rms=rms, eps=eps,
+                           xn_out=xn, rms_fold=rms_fold)
+        self._rows, self._x = rows, (xn if rms is not None else x)
+        return heads
+
+    @torch.no_grad()
+    def infer(self, x, rms, eps):
+        """Inference forward of a rollout step: x [rows, in] RAW observations with any row stride, normalised inside the
+        launch with the statistics as they are.  Returns joint_heads[:rows]."""
+        rows = x.shape[0]
+        if self.joint_heads.shape[0] < rows:
+            raise ValueError(f'{rows} rows in a step of a twin chain built for {self.joint_heads.shape[0]}')
+        heads = self.joint_heads[:rows]
+        self.chain.forward(x, heads[:, 1:], heads[:, :1], rms=rms, eps=eps)
+        return heads
+
+    @torch.no_grad()
+    def backward(self):
+        """d loss / d mu in d_heads[0][:rows], d loss / d value in d_heads[1][:rows] -> every gradient of both trunks and
+        both heads in the arena (overwritten)."""
+        rows = self._rows
+        d_heads = [d[:rows] for d in self.d_heads]
+        nblk = self.chain.num_blocks(rows, 1)
+        views = [trunk_views(ls, hs, dzs, ps, rows, nblk)
+                 for ls, hs, dzs, ps in zip(self.linears, self.Hs, self.dA, self.partials)]
+        acts, dzs, parts = zip(*views)
+        self.chain.backward(d_heads[0], d_heads[1], acts, dzs, parts)
+        work = []
+        for ls, head, d, a, dz, p in zip(self.linears, self.head_mods, d_heads, acts, dzs, parts):
+            jobs, colsums = trunk_jobs(ls, self._x, a, dz, p, nblk)
+            work.append(([(d, a[-1], head.weight.grad)] + jobs, colsums))
+            if not self.head_bias_done:
+                torch.sum(d, dim=0, out=head.bias.grad)
+        if sum(len(jobs) for jobs, _ in work) <= _DW_MAX_ITEMS:
+            work = [(work[0][0] + work[1][0], work[0][1] + work[1][1])]
+        for jobs, colsums in work:
+            self.weight_grads.finish(jobs, rows, colsums)

@@ -89,6 +89,25 @@ def lunar_separate_rnn(num_actors=16, units=64, cell='lstm', layer_norm=False, *
             'config': cfg}
 
 
+def mujoco_separate_mlp(num_actors=4096, units=(256, 128, 64), critic_units=None, activation='elu', obs_dim=17, act_dim=6,
+                        **over):
+    """A continuous policy with separate actor / critic MLPs and no RNN - the network of the reference's
+    `continuous_a2c_logstd` configs with `separate: True` (rl_games/configs/ppo_continuous.yaml, ppo_reacher.yaml,
+    ppo_lunar.yaml) at the width of its MuJoCo runs - HalfCheetah / Walker2d-shaped obs 17 / act 6, 16 steps.
+    critic_units: another shape for the critic trunk (`mlp.critic_units`, policy.py; None: the actor's, as the reference
+    builds it)."""
+    net = _network(units)
+    net['separate'] = True
+    net['mlp']['activation'] = activation
+    if critic_units is not None:
+        net['mlp']['critic_units'] = list(critic_units)
+    horizon = over.pop('horizon_length', 16)
+    minibatch = over.pop('minibatch_size', min(32768, num_actors * horizon))
+    return {'algo': {'name': 'a2c_continuous'}, 'model': {'name': 'continuous_a2c_logstd'}, 'network': net,
+            'config': _config('mujoco_separate_mlp', num_actors, horizon, minibatch, over.pop('mini_epochs', 4),
+                              {'obs_dim': obs_dim, 'act_dim': act_dim}, **over)}
+
+
 def tiny(num_actors=256, horizon=8, obs_dim=12, act_dim=3, **over):
     """Small config for smoke tests."""
     return {'algo': {'name': 'a2c_continuous'}, 'model': {'name': 'continuous_a2c_logstd'},

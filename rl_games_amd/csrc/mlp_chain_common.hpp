@@ -248,8 +248,9 @@ __device__ __forceinline__ float row16_sum(float t) {
 // mean32 / denominator of the observation normaliser into scratch[0 .. in0) / scratch[in0p .. in0p + in0), exactly
 // like rms_apply_kernel mode 0 (running_mean_std.py:112-113); with a.rms_batch the minibatch's moments are folded into
 // the state first (training-mode RunningMeanStd.forward) and workgroup 0 publishes the new state.  No barrier inside.
-template <int W>
-__device__ __forceinline__ void chain_norm_stats(const ChainArgs& a, float* scratch, int in0, int in0p) {
+// Args: ChainArgs, or any launch argument with its rms_* fields and rows (csrc/mlp_chain_twin.hip).
+template <int W, class Args>
+__device__ __forceinline__ void chain_norm_stats(const Args& a, float* scratch, int in0, int in0p) {
   for (int f = threadIdx.x; f < in0; f += (64 * W)) {
     double mean = a.rms_mean[f], var = a.rms_var[f];
     if (a.rms_batch) {

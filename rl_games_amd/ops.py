@@ -1442,6 +1442,100 @@ class MlpChainLn(_ChainArgs):
                                stream=_stream(d_heads), groups=groups), 'rlg_mlp_chain_ln_backward')
 
 
+class _TrunkArgs(_ChainArgs):
+    """One trunk of an MlpChainTwin: its rlg_chain_net and the builders of its descriptor halves."""
+
+    def __init__(self, layers, device):
+        self._state_net(layers, device, None)
+
+
+class MlpChainTwin:
+    """Separate actor / critic MLPs over the same observations as ONE forward and ONE backward launch
+    (csrc/mlp_chain_twin.hip): a workgroup reads and normalises its row tile once and runs both trunks on it, exact f32
+    products.  actor_layers / critic_layers: as `layers` of MlpChain, the head (mu: [A, K], value: [1, K], act 'None') last;
+    tensors are referenced, not copied.  norms: per trunk the `norms` list of MlpChainLn or None - the kernels have no
+    normalisation station, the library's query says so.  Raises NotImplementedError for a pair outside the envelope
+    (rlg_mlp_chain_twin_supported: 1 - 4 hidden layers per trunk, one of elu / relu / tanh in both, hidden widths
+    multiples of 4 up to 512 that fit the LDS, one value column, no layer norm) - nothing is launched.
+    No derived weight copies and one product form: towards weight_forms.ChainFormSet it answers like MlpChainLn."""
+
+    def __init__(self, actor_layers, critic_layers, device, weights_version=None, norms=(None, None)):
+        self._state(actor_layers, critic_layers, device, weights_version, norms)
+        if any(self.groups(1, d) == 0 for d in (0, 1)):                 # (also raises the kernels' LDS limit)
+            raise NotImplementedError('separate MLP trunks outside the envelope of the twin chain kernels')
+
+    def _state(self, actor_layers, critic_layers, device, weights_version, norms):
+        self.trunks = (_TrunkArgs(actor_layers, device), _TrunkArgs(critic_layers, device))
+        self.device = device
+        self._weights_version = weights_version
+        self._ln = [self._ln_query(t, nm) for t, nm in zip(self.trunks, norms)]
+        self.products = 'auto'      # one product form, exact f32: the attribute only travels (ChainFormSet.set_products)
+
+    @classmethod
+    def supported(cls, actor_layers, critic_layers, norms=(None, None), rows=1, direction=0):
+        """rlg_mlp_chain_twin_supported for these trunks: the 16-row groups of such a launch, 0 outside the envelope."""
+        self = cls.__new__(cls)
+        self._state(actor_layers, critic_layers, actor_layers[0][0].device, None, norms)
+        return self.groups(rows, direction)
+
+    @staticmethod
+    def _ln_query(trunk, norms):
+        """rlg_chain_ln of a trunk's layer norms for the query (gamma alone is read), or None."""
+        if norms is None or all(nm is None for nm in norms):
+            return None
+        gamma = trunk._P(*[None if nm is None else _need(nm[0], F32, 'gamma') for nm in list(norms) + [None] * (trunk.n - len(norms))])
+        ln = _lib.ChainLn(ctypes.addressof(gamma))
+        ln.arrays = gamma                               # (alive as long as the descriptor)
+        return ln
+
+    def weights_token(self):
+        return None if self._weights_version is None else self._weights_version()
+
+    def forms_read(self, launches):
+        return False, False
+
+    def cache_state(self):
+        return weight_forms.ChainSnapshot(None, None, None, False, self.products)
+
+    def restore_cache_state(self, state):
+        self.products = state.products
+
+    def groups(self, rows, direction, requested=0):
+        """16-row groups per workgroup of a launch: `requested` (1 / 2 / 4), else the library's choice from the rows and the
+        LDS the widths need; 0: outside the envelope.  direction: 0 inference forward, 1 backward, 2 training forward."""
+        nets = [ctypes.byref(t._net) for t in self.trunks]
+        lns = [None if ln is None else ctypes.byref(ln) for ln in self._ln]
+        G = int(_lib.load().rlg_mlp_chain_twin_supported(*nets, *lns, int(rows), int(direction)))
+        return requested if (G and requested in (1, 2, 4)) else G
+
+    def num_blocks(self, rows, direction, requested=0):
+        return _lib.load().rlg_mlp_chain_num_blocks(int(rows), self.groups(rows, direction, requested))
+
+    def forward(self, x, mu, value, act_out=None, rms=None, eps=1e-5, xn_out=None, groups=0, rms_fold=None):
+        """x [rows, in0] (row stride free); mu [rows, A] and value [rows, 1] out, each with its own row stride (two views
+        of one [rows, 1 + A] array: the joint row [value | mu]).  Training: act_out = (actor's, critic's) lists of
+        [rows, out_l] per hidden layer.  rms / xn_out / rms_fold as for MlpChain.forward: the observations are normalised
+        once, for both trunks."""
+        rows = x.shape[0]
+        outs = [[None] * (t.n - 1) for t in self.trunks] if act_out is None else [list(o) for o in act_out]
+        a, c = self.trunks
+        fwd_a = a._forward_args(x, outs[0] + [mu], rms, eps, xn_out, rms_fold)
+        fwd_c = c._forward_args(x, outs[1] + [value], None, eps, None, None)
+        _lib.check(_chain_call('fwd_train' if act_out is not None else 'fwd_infer', _lib.load().rlg_mlp_chain_twin_forward,
+                               a._net, c._net, fwd_a, fwd_c, rows=rows, stream=_stream(x), groups=groups),
+                   'rlg_mlp_chain_twin_forward')
+
+    def backward(self, d_mu, d_value, acts, dz_out, bias_partials=None, groups=0):
+        """d_mu [rows, A], d_value [rows, 1]; acts / dz_out / bias_partials: (actor's, critic's) lists per hidden layer -
+        H_l (the forward's act_out), the dZ_l output, fp64 [num_blocks(rows, 1), out_l] or None."""
+        rows = d_mu.shape[0]
+        parts = (None, None) if bias_partials is None else bias_partials
+        bwd = [t._backward_args(d, h, dz, p, None)
+               for t, d, h, dz, p in zip(self.trunks, (d_mu, d_value), acts, dz_out, parts)]
+        _lib.check(_chain_call('bwd', _lib.load().rlg_mlp_chain_twin_backward, self.trunks[0]._net, self.trunks[1]._net,
+                               *bwd, rows=rows, stream=_stream(d_mu), groups=groups), 'rlg_mlp_chain_twin_backward')
+
+
 # ------------------------------------------------------------------ MLP weight gradients (MFMA)
 
 class MlpDwPlan:

@@ -194,7 +194,7 @@ class ActorCriticNetwork(nn.Module):
         assert len(input_shape) == 1, 'flat observations only'
         in_size = input_shape[0]
         out_size = self._build_body(net_params, in_size)
-        self.value = nn.Linear(out_size, value_size)
+        self.value = nn.Linear(self.critic_out, value_size)
         self.value_act = _activation(net_params.get('value_activation', 'None'))
         self.mu = nn.Linear(out_size, actions_num)
         self.mu_act = _activation(self.space_config['mu_activation'])
@@ -259,8 +259,16 @@ class ActorCriticNetwork(nn.Module):
                 if self.rnn_ln:
                     self.layer_norm = nn.LayerNorm(self.rnn_units)
         self.actor_mlp = build_trunk(mlp_in, self.units, **self._trunk_kw)
+        self.critic_out = out_size
         if self.separate:                                      # network_builder.py:292-293
-            self.critic_mlp = build_trunk(mlp_in, self.units, **self._trunk_kw)
+            # `mlp.critic_units` (this library's; the reference builds both trunks from `units`): a critic trunk of
+            # another shape, feed-forward policies only
+            critic_units = list(mlp.get('critic_units') or self.units)
+            if critic_units != self.units:
+                if self.has_rnn:
+                    raise NotImplementedError('mlp.critic_units with an rnn')
+                self.critic_out = critic_units[-1]
+            self.critic_mlp = build_trunk(mlp_in, critic_units, **self._trunk_kw)
         # what the fused engines take (mlp_engine.ManualMLP): Linear + activation pairs, the RNN plainly behind them
         # ... plain but for a layer norm behind the RNN: what chain_net.RecurrentChainNet takes (the discrete agent)
         plain_but_separate = (not self._trunk_kw['d2rl'] and self._trunk_kw['norm_func_name'] is None and
@@ -286,7 +294,7 @@ class ActorCriticNetwork(nn.Module):
         self.value_size, self.num_seqs, self.actions_num = value_size, num_seqs, 0
         assert len(input_shape) == 1, 'flat states only'
         last = self._build_body(net_params, input_shape[0])      # (round 6: layer norm / D2RL trunks and an RNN as well)
-        self.value = nn.Linear(last, value_size)
+        self.value = nn.Linear(self.critic_out, value_size)
         self.value_act = _activation(net_params.get('value_activation', 'None'))
         mlp_init = _initializer(mlp['initializer'])
         for m in self.modules():
@@ -300,7 +308,7 @@ class ActorCriticNetwork(nn.Module):
         self.value_size, self.num_seqs, self.actions_num = value_size, num_seqs, actions_num
         assert len(input_shape) == 1, 'flat observations only'
         last = self._build_body(net_params, input_shape[0])      # (an RNN as for the continuous policy, round 6)
-        self.value = nn.Linear(last, value_size)
+        self.value = nn.Linear(self.critic_out, value_size)
         self.value_act = _activation(net_params.get('value_activation', 'None'))
         if self.is_multi_discrete:                              # network_builder.py:303-304
             self.logits = nn.ModuleList([nn.Linear(last, int(n)) for n in actions_num])
