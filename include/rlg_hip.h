@@ -196,6 +196,43 @@ RLG_ABI_SIZE(rlg_policy_head_desc, 176);
 
 int rlg_rollout_policy_head(const rlg_policy_head_desc* desc, void* stream);
 
+/* The same rollout step for a policy with a sigma head (csrc/ppo_loss_sigma.hip): raw_sigma [N, A] (row stride
+ * ld_raw_sigma; e.g. columns 1 + A .. 2 A of heads [value | mu | raw sigma]) in place of logstd [A], and the sigma form
+ * of rlg_ppo_loss_sigma_desc - sigma and log sigma of every element by the device function the loss kernel uses;
+ * action = mu + sigma * noise; the neglogp's sums over the A columns left to right in fp32.  Value source, value
+ * de-normalisation, env_actions_out and the buffer writes (slot `step` only) are rlg_rollout_policy_head's.
+ * A NULL descriptor: hipErrorInvalidValue.  N <= 0 returns 0 without a launch.  Then, before the runtime is asked for
+ * anything, hipErrorInvalidValue for what rlg_rollout_policy_head rejects (raw_sigma for logstd), ld < 1 + A,
+ * ld_raw_sigma < A, or a sigma form rlg_ppo_loss_sigma rejects.  Size (208 bytes): asserted where the entry is defined. */
+typedef struct rlg_policy_head_sigma_desc {
+  const float* heads;      /* [N, ld]: column 0 the value, columns 1..A mu */
+  int ld;
+  const float* value;      /* NULL, or [ceil(N / value_repeat), ld_value], column 0 */
+  long long ld_value;
+  int value_repeat;
+  const float* raw_sigma;  /* [N, A] view */
+  long long ld_raw_sigma;
+  const float* noise;      /* [N, A] standard normal */
+  const double* v_mean;    /* value RunningMeanStd (fp64), or NULL when normalize_value is off */
+  const double* v_var;
+  float eps;
+  float* actions_out;      /* [N, A] contiguous (goes to the env) */
+  float* values_out;       /* [N] de-normalised values */
+  float* buf_actions;      /* env-major [N][H][A] */
+  float* buf_mus;
+  float* buf_sigmas;
+  float* buf_neglogp;      /* [N][H] */
+  float* buf_values;       /* [N][H] */
+  float* env_actions_out;  /* optional [N, A], with act_low / act_high [A] */
+  const float* act_low;
+  const float* act_high;
+  int N, H, A, step;
+  int sigma_kind, has_bounds;
+  float sigma_lo, sigma_hi, min_sigma;
+} rlg_policy_head_sigma_desc;
+
+int rlg_rollout_policy_head_sigma(const rlg_policy_head_sigma_desc* desc, void* stream);
+
 /* Categorical rollout head (discrete_a2c / multi_discrete_a2c eval branch: rl_games/algos_torch/models.py:95-125,
  * :157-206, CategoricalMasked common/extensions/distributions.py:24-47, denorm_value :58-60) fused with the
  * update_data writes of its outputs (a2c_common.py:1008-1009).  logits [N, sum(sizes)] and value (column 0) with
@@ -485,6 +522,58 @@ typedef struct rlg_discrete_loss_desc {
 RLG_ABI_SIZE(rlg_discrete_loss_desc, 184);
 
 int rlg_ppo_loss_discrete_nlp(const rlg_discrete_loss_desc* desc, void* stream);
+
+/* Continuous policy with a sigma HEAD (`fixed_sigma: False`) and any sigma form of the reference
+ * (`apply_sigma_parametrization`, rl_games/algos_torch/models.py:272-301) - csrc/ppo_loss_sigma.hip.  As
+ * rlg_ppo_loss_fused, but sigma is a function of each row's raw head output raw_sigma [rows, A]:
+ *   sigma_kind 0 'exp':      l = has_bounds ? clamp(raw, sigma_lo, sigma_hi) : raw;  sigma = exp(l);
+ *                            min_sigma > 0: sigma += min_sigma, log sigma = log(sigma);  else log sigma = l
+ *   sigma_kind 1 'softplus': sigma = softplus(raw) + min_sigma           (torch's: the identity above 20)
+ *   sigma_kind 2 'linear':   f = max(min_sigma, 1e-3);  sigma = f + softplus(raw - f)      ('scalar' in a config)
+ *   (1, 2: log sigma = log(sigma); the entropy takes log(sigma) in every form.)
+ * Emits the COMPLETE gradient of
+ *   loss = a_loss + 0.5 c_loss critic_coef - entropy entropy_coef + b_loss bounds_coef
+ * with respect to mu, raw_sigma (d_raw_sigma [rows, A]; the entropy term included; zero strictly outside the bounds, the
+ * clamp passing the gradient at them) and the value, scaled by 1 / rows or mask / max(sum(mask), 1); each row's neglogp
+ * into new_neglogp_or_null [rows]; with write_back the step's mu / sigma over old_mu / old_sigma, read first for the KL.
+ * mu / raw_sigma / d_mu / d_raw_sigma take row strides and values / d_values element strides (elements), so that all six
+ * can be views of [rows, 1 + 2 A] head rows [value | mu | raw sigma] and of their gradient.
+ * partials: fp64 [rlg_ppo_loss_sigma_num_blocks(rows)][7], one row per 256-row workgroup, in the layout
+ * rlg_ppo_loss_finalize folds with actions_num = 0 (as for the discrete loss; its d_logstd is not written then).
+ * Numeric contract: fp32, one rounding per op; a row's sums over its A columns are added left to right, in fp32.
+ * actions_num: what rlg_ppo_loss_fused accepts.  Before the runtime is asked for anything, hipErrorInvalidValue for a
+ * NULL descriptor or required pointer (every one not named _or_null), rows <= 0, actions_num out of range, a row stride
+ * below actions_num or an element stride below 1, a mask without its sum, a sigma_kind / use_smooth_clamp / bound_kind
+ * that is none of the above, sigma_lo > sigma_hi with has_bounds, min_sigma < 0.
+ * The descriptor's size (248 bytes) is asserted where the entry is defined. */
+int rlg_ppo_loss_sigma_num_blocks(int rows);
+typedef struct rlg_ppo_loss_sigma_desc {
+  const float* mu;             /* [rows, A] view, row stride ld_mu */
+  const float* raw_sigma;      /* [rows, A] view, row stride ld_raw_sigma: the sigma head's output */
+  const float* values;         /* [rows] view, stride ld_values */
+  const float* actions;        /* [rows, A] */
+  const float* old_neglogp;    /* [rows] */
+  const float* advantages;
+  const float* old_values;
+  const float* returns;
+  float* old_mu;               /* [rows, A] read, then overwritten when write_back */
+  float* old_sigma;
+  const float* mask_or_null;
+  const float* mask_sum_or_null;
+  float* d_mu;                 /* [rows, A] view, row stride ld_d_mu */
+  float* d_raw_sigma;          /* [rows, A] view, row stride ld_d_raw_sigma */
+  float* d_values;             /* [rows] view, stride ld_d_values */
+  float* new_neglogp_or_null;  /* [rows] */
+  double* partials;
+  long long ld_mu, ld_raw_sigma, ld_values, ld_d_mu, ld_d_raw_sigma, ld_d_values;
+  int rows, actions_num;
+  float e_clip, critic_coef, entropy_coef, bounds_coef;
+  int clip_value, use_smooth_clamp, bound_kind, write_back;
+  int sigma_kind, has_bounds;
+  float sigma_lo, sigma_hi, min_sigma;
+} rlg_ppo_loss_sigma_desc;
+
+int rlg_ppo_loss_sigma(const rlg_ppo_loss_sigma_desc* desc, void* stream);
 
 /* PPO diagnostics (`use_diagnostics`; rl_games/common/diagnostics.py, torch_ext.py:182-227), csrc/ppo_diag.hip.  A row of
  * the diagnostics table is rlg_ppo_diag_stats() = 10 fp64: {rows, W = sum m, C = sum m*clipped, mean_ret, M2_ret,

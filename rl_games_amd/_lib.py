@@ -131,6 +131,10 @@ _PROTOTYPES = {
     'rlg_value_loss': [_P, _P, _P, _P, _P, _P, _P, _c_int, _c_float, _c_int, _P],
     'rlg_ppo_loss_discrete_num_blocks': [_c_int],
     'rlg_ppo_loss_discrete_nlp': [_P, _P],           # (DiscreteLossDesc, stream)
+    # ppo_loss_sigma.hip: continuous policies with a sigma head / any sigma form
+    'rlg_ppo_loss_sigma_num_blocks': [_c_int],
+    'rlg_ppo_loss_sigma': [_P, _P],                  # (PpoLossSigmaDesc, stream)
+    'rlg_rollout_policy_head_sigma': [_P, _P],       # (PolicyHeadSigmaDesc, stream)
     # ppo_diag.hip
     'rlg_ppo_diag_stats': [],
     'rlg_ppo_diag_num_blocks': [_c_int],
@@ -244,6 +248,32 @@ class DiscreteLossDesc(ctypes.Structure):
                 + [('d_logits', _P), ('ld_d_logits', _c_ll), ('d_values', _P), ('ld_d_values', _c_ll), ('partials', _P),
                    ('minibatch', _c_int), ('e_clip', _c_float), ('critic_coef', _c_float), ('entropy_coef', _c_float),
                    ('clip_value', _c_int), ('use_smooth_clamp', _c_int), ('new_neglogp_or_null', _P)])
+
+
+_SIGMA_FORM = [('sigma_kind', _c_int), ('has_bounds', _c_int), ('sigma_lo', _c_float), ('sigma_hi', _c_float),
+               ('min_sigma', _c_float)]
+
+
+class PpoLossSigmaDesc(ctypes.Structure):
+    """rlg_ppo_loss_sigma_desc (include/rlg_hip.h): the arguments of rlg_ppo_loss_sigma."""
+    _fields_ = ([(n, _P) for n in (
+        'mu', 'raw_sigma', 'values', 'actions', 'old_neglogp', 'advantages', 'old_values', 'returns', 'old_mu',
+        'old_sigma', 'mask_or_null', 'mask_sum_or_null', 'd_mu', 'd_raw_sigma', 'd_values', 'new_neglogp_or_null',
+        'partials')]
+        + [(n, _c_ll) for n in ('ld_mu', 'ld_raw_sigma', 'ld_values', 'ld_d_mu', 'ld_d_raw_sigma', 'ld_d_values')]
+        + [('rows', _c_int), ('actions_num', _c_int)]
+        + [(n, _c_float) for n in ('e_clip', 'critic_coef', 'entropy_coef', 'bounds_coef')]
+        + [(n, _c_int) for n in ('clip_value', 'use_smooth_clamp', 'bound_kind', 'write_back')] + _SIGMA_FORM)
+
+
+class PolicyHeadSigmaDesc(ctypes.Structure):
+    """rlg_policy_head_sigma_desc (include/rlg_hip.h): the arguments of rlg_rollout_policy_head_sigma."""
+    _fields_ = ([('heads', _P), ('ld', _c_int), ('value', _P), ('ld_value', _c_ll), ('value_repeat', _c_int),
+                 ('raw_sigma', _P), ('ld_raw_sigma', _c_ll), ('noise', _P), ('v_mean', _P), ('v_var', _P),
+                 ('eps', _c_float)]
+                + [(n, _P) for n in ('actions_out', 'values_out', 'buf_actions', 'buf_mus', 'buf_sigmas', 'buf_neglogp',
+                                     'buf_values', 'env_actions_out', 'act_low', 'act_high')]
+                + [(n, _c_int) for n in ('N', 'H', 'A', 'step')] + _SIGMA_FORM)
 
 
 class PostStepDesc(ctypes.Structure):

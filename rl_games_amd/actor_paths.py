@@ -1,5 +1,5 @@
 """Which engine runs an agent's network: one object per way of running the actor, chosen once when the agent is built
-- engine, pair, twin, chains, recurrent, autograd or general; the table with each path's conditions: DESIGN.md 4.1a.
+- engine, pair, twin, sigma, chains, recurrent, autograd or general; the table with each path's conditions: DESIGN.md 4.1a.
 The choice has two phases, because the arena layout must exist before FlatAdam and the engine after it: a Plan holds the
 path's class, the layout and the reason a faster path was declined; Plan.build makes the path once the optimiser exists.
 A path answers what the agents need to know about their network: the engines that finish weight gradients, the chains
@@ -57,6 +57,7 @@ class AutogradPath:
     rollout_ok = False                             # the rollout can run fused (for the agent's observation space)
     last_states = None                             # the next RNN states behind infer()
     norm_ok = None                                 # the finalise launch leaves the gradient norm (EnginePath)
+    row_sigma = False                              # infer()'s heads carry a raw sigma per row behind mu (SigmaPath)
 
     def __init__(self, agent):
         self.agent = agent
@@ -405,6 +406,92 @@ class TwinPath(AutogradPath):
         a._diag_update(inp, (mu, net.sigma))
 
 
+class SigmaPath(AutogradPath):
+    """A continuous policy whose sigma is a HEAD over the shared trunk (`fixed_sigma: False`), in any sigma form - exp with
+    or without logstd_bounds / min_sigma, softplus, linear - on one chain_net.ChainNet over [value | mu | raw sigma], with
+    the loss and rollout-head kernels of csrc/ppo_loss_sigma.hip.  Opt-in (`sigma_head_kernels: True`); update and rollout
+    without autograd.  Updates stay eager: the step graphs alone read its chain."""
+    kind, row_sigma = 'sigma', True
+    rollout_ok = property(lambda self: fp32_space(self.agent.observation_space))
+
+    @staticmethod
+    def declined(agent, config):
+        """Why a sigma-head network stays off the kernels (None: it is eligible) - asked in front of the optimiser, so
+        that a declined network keeps the arena order it always had."""
+        net = agent.model.a2c_network
+        if agent.value_size != 1:
+            return 'one value column only'
+        if net.is_separate_critic():
+            return 'a shared trunk only'
+        if net.is_rnn():
+            return 'feed-forward networks only'
+        if not (config.get('fused_mlp', True) and config.get('manual_mlp', True)):
+            return 'fused_mlp / manual_mlp is off'
+        if not all(isinstance(a, nn.Identity) for a in (net.mu_act, net.value_act, net.sigma_act)):
+            return 'identity head activations only'
+        if not fp32_space(agent.observation_space):
+            # (decided here, not at call time: what would take such a minibatch is GeneralPath, with its arena order)
+            return 'fp32 observation spaces only'
+        if not getattr(net, 'plain_trunk', True):
+            return 'plain Linear + activation trunks only'
+        try:
+            plain_trunk(net.actor_mlp)
+        except NotImplementedError as e:
+            return str(e)
+        return None
+
+    @staticmethod
+    def layout(net):
+        return arena_layout(list(net.parameters()), [[net.value, net.mu, net.sigma]])
+
+    def __init__(self, agent):
+        super().__init__(agent)
+        net = agent.model.a2c_network
+        self.chain = ChainNet(net.actor_mlp, [net.value, net.mu, net.sigma], agent.optimizer, agent.minibatch_size,
+                              infer_rows=agent.num_actors * agent.num_agents)
+        self.engines = [self.chain]
+        self.form = ops.sigma_form(net)
+        dev = agent.ppo_device
+        self.new_neglogp = torch.empty(agent.minibatch_size, dtype=torch.float32, device=dev)
+        self._no_logstd = torch.zeros(1, dtype=torch.float32, device=dev)      # (the finalise launch's d_logstd: unused)
+
+    def takes(self, obs):
+        return obs.dtype == torch.float32          # (the chain reads the observations raw)
+
+    def infer(self, obs, rnn_states, logits_only=False):
+        """Heads [rows, 1 + 2 A] ([value | mu | raw sigma]) of a rollout step, the normaliser in eval mode inside the
+        launch."""
+        a = self.agent
+        return self.chain.infer(_unit_stride(obs), a._obs_rms(), a._obs_eps())
+
+    values = EnginePath.values
+
+    @torch.no_grad()
+    def update(self, inp, row):
+        """Statistics, chain forward, loss (every gradient of the heads, the entropy's included), finalise with no
+        parameter vector to fold, chain backward.  Leaves what GeneralPath.update leaves: the scalars in `row`, the KL in
+        the arena's tail slot, mu / sigma written back into the dataset, the diagnostics fed from the rows' new neglogp."""
+        a, chain = self.agent, self.chain
+        obs = a._preproc_obs(inp['obs'])
+        a.optimizer.zero_grad()
+        rms, eps = launch_stats(self._stats_module(), obs)         # statistics first (models.py:54-56)
+        heads = chain.forward(obs, rms, eps)
+        mb, A = heads.shape[0], a.actions_num
+        d_heads, nlp = chain.d_heads[:mb], self.new_neglogp[:mb]
+        mask, mask_sum = ops.sequence_mask(inp.get('rnn_masks', None))
+        coef_c, coef_b, kind = a._loss_scalars()
+        ops.ppo_loss_sigma(heads[:, 1:1 + A], heads[:, 1 + A:], heads[:, 0], inp['actions'], inp['old_logp_actions'],
+                           inp['advantages'], inp['old_values'].reshape(-1), inp['returns'].reshape(-1), inp['mu'],
+                           inp['sigma'], d_heads[:, 1:1 + A], d_heads[:, 1 + A:], d_heads[:, 0], a._loss_partials,
+                           self.form, a.e_clip, coef_c, a.entropy_coef, coef_b, a.clip_value, a.surrogate, kind, True,
+                           mask, mask_sum, new_neglogp=nlp)
+        ops.ppo_loss_finalize(a._loss_partials, ops.ppo_loss_sigma_blocks(mb), 0, mb, mask is not None, coef_c,
+                              a.entropy_coef, coef_b, row, self._no_logstd, a.optimizer.kl_slot)
+        chain.backward()
+        a._norm_ready = None
+        a._diag_minibatch(inp, new_neglogp=nlp)
+
+
 class ChainsPath(AutogradPath):
     """A feed-forward discrete network on the fused chain kernels: one ChainNet over [value | logits] behind a shared
     trunk, one per trunk with `separate: True` ([logits], [value])."""
@@ -548,6 +635,14 @@ class Plan:
             self.why = TwinPath.declined(net)
             if self.why is None:
                 self.layout = TwinPath.layout(net) + rest
+        elif (config.get('sigma_head_kernels', False) and not getattr(net, 'fixed_sigma', True)
+                and getattr(agent, 'trains', True)):
+            # (training agents only: a player - play_engine._PlayAgent - keeps the answer it always got for such a network)
+            self.cls = SigmaPath
+            self.notice = 'sigma head outside the sigma-head kernels ({}); using autograd'
+            self.why = SigmaPath.declined(agent, config)
+            if self.why is None:
+                self.layout = SigmaPath.layout(net) + rest
 
     def build(self, agent):
         """Behind the optimiser: the planned path, or - declined, or its engine refuses the network - the notice and

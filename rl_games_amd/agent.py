@@ -335,8 +335,9 @@ class A2CAgent:
         self.optimizer = FlatAdam(self.model.parameters(), self.last_lr, eps=1e-08,
                                   weight_decay=self.weight_decay, layout=plan.layout)
         self._path = plan.build(self)
-        # where a step or a minibatch goes whose observations the path does not take (takes())
-        self._autograd = self._path if type(self._path) is AutogradPath else AutogradPath(self)
+        # where a step or a minibatch goes whose observations the path does not take (takes()): the plan's fallback -
+        # GeneralPath for a network the fused loss kernels do not carry (a sigma head on SigmaPath), else AutogradPath
+        self._autograd = self._path if type(self._path) is plan.fallback else plan.fallback(self)
         self.dataset = PPODataset(self.batch_size, self.minibatch_size, self.is_discrete, self.is_rnn,
                                   dev, self.seq_length)
         self.central_value_net = None
@@ -800,10 +801,16 @@ class A2CAgent:
             if self._roll_env_actions is None or self._roll_env_actions.shape != self._roll_actions.shape:
                 self._roll_env_actions = torch.empty_like(self._roll_actions)
             env_actions = (self._roll_env_actions, self.actions_low, self.actions_high)
-        ops.rollout_policy_head(heads, self.model.a2c_network.sigma.data, self._roll_noise, vs, eps,
-                                self._roll_actions, self._roll_values, self.experience_buffer.storage, self.horizon_length,
-                                n, env_actions=env_actions, value=value,
-                                value_repeat=self.num_agents if value is not None else 1)
+        tail = (self._roll_noise, vs, eps, self._roll_actions, self._roll_values, self.experience_buffer.storage,
+                self.horizon_length, n)
+        repeat = self.num_agents if value is not None else 1
+        if self._path.row_sigma:
+            # heads [value | mu | raw sigma]: sigma is a function of the row (actor_paths.SigmaPath)
+            ops.rollout_policy_head_sigma(heads, heads[:, 1 + self.actions_num:], self._path.form, *tail,
+                                          env_actions=env_actions, value=value, value_repeat=repeat)
+        else:
+            ops.rollout_policy_head(heads, self.model.a2c_network.sigma.data, *tail, env_actions=env_actions, value=value,
+                                    value_repeat=repeat)
         return self._roll_env_actions if self.clip_actions else self._roll_actions
 
     def _store_step_inputs(self, n, obs_raw, dones, states):

@@ -108,6 +108,26 @@ def mujoco_separate_mlp(num_actors=4096, units=(256, 128, 64), critic_units=None
                               {'obs_dim': obs_dim, 'act_dim': act_dim}, **over)}
 
 
+def pendulum_sigma_head(num_actors=64, units=(32, 32), sigma_parametrization='exp', logstd_bounds=(-5.0, 2.0),
+                        min_sigma=0.0, obs_dim=3, act_dim=1, sigma_head_kernels=True, **over):
+    """A continuous policy whose sigma is a head over the shared trunk (`fixed_sigma: False`) - the network of the
+    reference's rl_games/configs/ppo_pendulum.yaml, Pendulum-shaped obs 3 / act 1 - with the sigma form options of
+    `apply_sigma_parametrization` (models.py:272-301): sigma_parametrization 'exp' / 'softplus' / 'linear' ('scalar'),
+    logstd_bounds (exp only; None: none), min_sigma.  sigma_head_kernels (this library's key, default here: on): loss and
+    rollout head on csrc/ppo_loss_sigma.hip (actor_paths.SigmaPath) instead of torch ops under autograd."""
+    net = _network(units)
+    space = net['space']['continuous']
+    space.update(fixed_sigma=False, sigma_parametrization=sigma_parametrization, min_sigma=float(min_sigma))
+    if logstd_bounds is not None and sigma_parametrization == 'exp':
+        space['logstd_bounds'] = [float(logstd_bounds[0]), float(logstd_bounds[1])]
+    horizon = over.pop('horizon_length', 16)
+    minibatch = over.pop('minibatch_size', min(32768, num_actors * horizon))
+    return {'algo': {'name': 'a2c_continuous'}, 'model': {'name': 'continuous_a2c_logstd'}, 'network': net,
+            'config': _config('pendulum_sigma_head', num_actors, horizon, minibatch, over.pop('mini_epochs', 4),
+                              {'obs_dim': obs_dim, 'act_dim': act_dim}, entropy_coef=over.pop('entropy_coef', 1e-3),
+                              sigma_head_kernels=bool(sigma_head_kernels), **over)}
+
+
 def tiny(num_actors=256, horizon=8, obs_dim=12, act_dim=3, **over):
     """Small config for smoke tests."""
     return {'algo': {'name': 'a2c_continuous'}, 'model': {'name': 'continuous_a2c_logstd'},

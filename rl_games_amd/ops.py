@@ -607,6 +607,100 @@ def ppo_loss_discrete(logits, values, actions, old_neglogp, advantages, old_valu
     _lib.check(lib.rlg_ppo_loss_discrete_nlp(ctypes.addressof(desc), _stream(logits)), 'rlg_ppo_loss_discrete_nlp')
 
 
+SIGMA_KINDS = {'exp': 0, 'softplus': 1, 'linear': 2, 'scalar': 2}
+
+
+def sigma_form(net):
+    """The sigma form fields of rlg_ppo_loss_sigma_desc / rlg_policy_head_sigma_desc for a network (policy.py,
+    `sigma_and_logstd`; models.py:272-301) or a dict of them: sigma_parametrization ('scalar' is 'linear'), logstd_bounds
+    (None or (lo, hi)) and min_sigma -> dict(sigma_kind, has_bounds, sigma_lo, sigma_hi, min_sigma).  Bounds clamp the
+    'exp' form only (the others never look at them)."""
+    get = net.get if isinstance(net, dict) else lambda k, d=None: getattr(net, k, d)
+    name = get('sigma_parametrization', 'exp') or 'exp'
+    if name not in SIGMA_KINDS:
+        raise ValueError(f"sigma_parametrization '{name}'")
+    kind = SIGMA_KINDS[name]
+    bounds = get('logstd_bounds', None) if kind == 0 else None
+    lo, hi = (float(bounds[0]), float(bounds[1])) if bounds is not None else (0.0, 0.0)
+    return dict(sigma_kind=kind, has_bounds=0 if bounds is None else 1, sigma_lo=float(np.float32(lo)),
+                sigma_hi=float(np.float32(hi)), min_sigma=float(np.float32(get('min_sigma', 0.0) or 0.0)))
+
+
+def ppo_loss_sigma_blocks(rows):
+    return _lib.load().rlg_ppo_loss_sigma_num_blocks(int(rows))
+
+
+def ppo_loss_sigma(mu, raw_sigma, values, actions, old_neglogp, advantages, old_values, returns, old_mu, old_sigma,
+                   d_mu, d_raw_sigma, d_values, partials, form, e_clip, critic_coef, entropy_coef, bounds_coef,
+                   clip_value=True, smooth=False, bound_kind=1, write_back=True, mask=None, mask_sum=None,
+                   new_neglogp=None):
+    """The PPO loss of a policy with a sigma head and its whole backward (include/rlg_hip.h, rlg_ppo_loss_sigma): mu /
+    raw_sigma / d_mu / d_raw_sigma [rows, A] and values / d_values [rows] may be strided views of [value | mu | raw sigma]
+    head rows; form: sigma_form(net); partials: fp64, ppo_loss_sigma_blocks(rows) * 7 - for ppo_loss_finalize with
+    actions_num 0; new_neglogp: fp32 [rows] or None."""
+    rows, A = mu.shape
+    for name, t in (('raw_sigma', raw_sigma), ('d_mu', d_mu), ('d_raw_sigma', d_raw_sigma), ('actions', actions),
+                    ('old_mu', old_mu), ('old_sigma', old_sigma)):
+        if tuple(t.shape) != (rows, A):
+            raise ValueError(f'{name}: [{rows}, {A}] expected, got {tuple(t.shape)}')
+    for name, t in (('values', values), ('d_values', d_values), ('old_neglogp', old_neglogp), ('advantages', advantages),
+                    ('old_values', old_values), ('returns', returns), ('mask', mask), ('new_neglogp', new_neglogp)):
+        if t is not None and t.numel() != rows:
+            raise ValueError(f'{name}: {rows} elements expected, got {t.numel()}')
+    if partials.numel() < ppo_loss_sigma_blocks(rows) * 7:
+        raise ValueError('ppo_loss_sigma: partials too small')
+    mu_p, ld_mu = _row_view(mu, F32, rows, A, 'mu')
+    raw_p, ld_raw = _row_view(raw_sigma, F32, rows, A, 'raw_sigma')
+    dmu_p, ld_dmu = _row_view(d_mu, F32, rows, A, 'd_mu')
+    draw_p, ld_draw = _row_view(d_raw_sigma, F32, rows, A, 'd_raw_sigma')
+    val_p, ld_val = _rows_view(values.reshape(rows) if values.dim() == 2 else values, 'values')
+    dval_p, ld_dval = _rows_view(d_values.reshape(rows) if d_values.dim() == 2 else d_values, 'd_values')
+    desc = _lib.PpoLossSigmaDesc(
+        mu=mu_p, raw_sigma=raw_p, values=val_p, actions=_need(actions, F32, 'actions'),
+        old_neglogp=_need(old_neglogp, F32, 'old_neglogp'), advantages=_need(advantages, F32, 'advantages'),
+        old_values=_need(old_values, F32, 'old_values'), returns=_need(returns, F32, 'returns'),
+        old_mu=_need(old_mu, F32, 'old_mu'), old_sigma=_need(old_sigma, F32, 'old_sigma'),
+        mask_or_null=_opt(mask, F32, 'mask'), mask_sum_or_null=_opt(mask_sum, F32, 'mask_sum'), d_mu=dmu_p,
+        d_raw_sigma=draw_p, d_values=dval_p, new_neglogp_or_null=_opt(new_neglogp, F32, 'new_neglogp'),
+        partials=_need(partials, F64, 'partials'), ld_mu=ld_mu, ld_raw_sigma=ld_raw, ld_values=max(ld_val, 1),
+        ld_d_mu=ld_dmu, ld_d_raw_sigma=ld_draw, ld_d_values=max(ld_dval, 1), rows=rows, actions_num=A,
+        e_clip=float(np.float32(e_clip)), critic_coef=float(np.float32(critic_coef)),
+        entropy_coef=float(np.float32(entropy_coef)), bounds_coef=float(np.float32(bounds_coef)),
+        clip_value=1 if clip_value else 0, use_smooth_clamp=_surrogate_kind(smooth), bound_kind=int(bound_kind),
+        write_back=1 if write_back else 0, **form)
+    _lib.check(_lib.load().rlg_ppo_loss_sigma(ctypes.addressof(desc), _stream(mu)), 'rlg_ppo_loss_sigma')
+
+
+def rollout_policy_head_sigma(heads, raw_sigma, form, noise, value_stats, eps, actions_out, values_out, storage, horizon,
+                              step, env_actions=None, value=None, value_repeat=1):
+    """rollout_policy_head for a policy with a sigma head: heads [N, ld] = [value | mu | ...] (any row stride),
+    raw_sigma [N, A] the sigma head's output (a view, e.g. heads[:, 1 + A:]), form: sigma_form(net)."""
+    N, A = noise.shape
+    heads_p, ld = _row_view(heads, F32, N, heads.shape[1], 'heads')
+    if heads.shape[1] < 1 + A:
+        raise ValueError(f'heads: at least {1 + A} columns expected')
+    raw_p, ld_raw = _row_view(raw_sigma, F32, N, A, 'raw_sigma')
+    desc = _lib.PolicyHeadSigmaDesc(
+        heads=heads_p, ld=ld, raw_sigma=raw_p, ld_raw_sigma=ld_raw, noise=_need(noise, F32, 'noise'), eps=eps,
+        actions_out=_need(actions_out, F32, 'actions_out'), values_out=_need(values_out, F32, 'values_out'),
+        buf_actions=_need(storage['actions'], F32, 'actions'), buf_mus=_need(storage['mus'], F32, 'mus'),
+        buf_sigmas=_need(storage['sigmas'], F32, 'sigmas'), buf_neglogp=_need(storage['neglogpacs'], F32, 'neglogpacs'),
+        buf_values=_need(storage['values'], F32, 'values'), N=N, H=horizon, A=A, step=step, **form)
+    if value_stats is not None:
+        desc.v_mean, desc.v_var = _need(value_stats[0], F64, 'value mean'), _need(value_stats[1], F64, 'value var')
+    if value is None:
+        if value_repeat != 1:
+            raise ValueError('value_repeat needs a value tensor')
+    else:
+        desc.value, desc.ld_value = _value_column(value, N, value_repeat)
+        desc.value_repeat = int(value_repeat)
+    if env_actions is not None:
+        desc.env_actions_out = _need(env_actions[0], F32, 'env actions')
+        desc.act_low, desc.act_high = _need(env_actions[1], F32, 'actions low'), _need(env_actions[2], F32, 'actions high')
+    _lib.check(_lib.load().rlg_rollout_policy_head_sigma(ctypes.addressof(desc), _stream(heads)),
+               'rlg_rollout_policy_head_sigma')
+
+
 def ppo_diag_stats():
     """Doubles per row of the diagnostics table (rlg_ppo_diag)."""
     return _lib.load().rlg_ppo_diag_stats()

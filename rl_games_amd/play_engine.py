@@ -22,6 +22,7 @@ class _PlayAgent:
     """What actor_paths.Plan and its paths ask an agent, answered for a player of `rows` rows: no optimiser (a FlatArena
     in its place), no minibatches (TRAIN_ROWS), one agent per row."""
     num_agents, minibatch_size, _roll_obs_norm = 1, TRAIN_ROWS, None
+    trains = False         # (Plan: the paths that exist for training agents only - SigmaPath - are not offered)
     _obs_rms, _obs_eps = A2CAgent._obs_rms, A2CAgent._obs_eps
 
     def __init__(self, player, rows):
