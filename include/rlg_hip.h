@@ -1157,6 +1157,29 @@ RLG_ABI_SIZE(rlg_gru_bwd, 64);
 int rlg_gru_seq_backward(const rlg_gru_bwd* problems, int num_problems, int num_seqs, int seq_len, int hidden,
                          void* stream);
 
+/* The same two cells at 256 hidden units, on the "streamed" product scheme (csrc/rnn_stream.hip): W_hh (1 MB / 768 KB) fits
+ * neither registers nor LDS, so a workgroup keeps a tile of 16 sequences for all seq_len steps and streams the weights from
+ * L2 every step, as operand fragments of v_mfma_f32_16x16x4_f32 (exact fp32 products) packed once per weight version in the
+ * order each wave consumes them.  The contract is the one of the sequence entries above - rows seq*T + t, the done rule, one
+ * launch for all steps, in-place gates, deterministic bits, the same bits with and without the optional outputs - and
+ * rlg_lstm_supported(256) / rlg_gru_supported(256) stay 0: these are entries of their own.
+ * cell: 0 LSTM, 1 GRU.  rlg_rnn_stream_supported: 1 for (0, 256) and (1, 256), else 0.
+ * rlg_rnn_stream_pack_bytes: size of the packed form [forward stream | backward stream], -1 where not supported.
+ * rlg_rnn_stream_pack: one launch that writes both streams from w_hh [NG*256, 256]; the kernels read only the packed form,
+ * so it has to run again whenever w_hh changes.
+ * rlg_rnn_stream_forward / _backward: `problem` is ONE rlg_lstm_fwd / rlg_gru_fwd (rlg_lstm_bwd / rlg_gru_bwd) descriptor
+ * of the cell (its w_hh must be set, as for the entries above, and is not read), `packed` what rlg_rnn_stream_pack wrote.
+ * hipErrorInvalidValue, with nothing launched: a NULL problem or packed form, num_seqs <= 0, seq_len <= 0, a (cell, hidden)
+ * that is not supported, a NULL required pointer, a packed form or w_hh (pack) that is not 16-byte aligned; forward: gates,
+ * h0, out or a given c_all / hn_all, hprev, hT, cT that is not 16-byte aligned (they move 16 bytes at a time). */
+int rlg_rnn_stream_supported(int cell, int hidden);
+long long rlg_rnn_stream_pack_bytes(int cell, int hidden);
+int rlg_rnn_stream_pack(int cell, int hidden, const float* w_hh, void* packed, void* stream);
+int rlg_rnn_stream_forward(int cell, const void* problem, const void* packed, int num_seqs, int seq_len, int hidden,
+                           void* stream);
+int rlg_rnn_stream_backward(int cell, const void* problem, const void* packed, int num_seqs, int seq_len, int hidden,
+                            void* stream);
+
 /* Layer normalisation behind the recurrent layer (csrc/rnn_layer_norm.hip): `rnn: {layer_norm: True}`,
  * nn.LayerNorm(rnn_units) over the RNN output [rows, hidden] (network_builder.py:447-500), hidden 16 / 32 / 64 / 128.
  *   forward:  y = (x - mean) * rstd * gamma + beta, biased variance from the centred values, rstd = 1 / sqrt(var + eps);

@@ -120,6 +120,12 @@ _PROTOTYPES = {
     'rlg_gru_supported': [_c_int],
     'rlg_gru_seq_forward': [_P, _c_int, _c_int, _c_int, _c_int, _P],
     'rlg_gru_seq_backward': [_P, _c_int, _c_int, _c_int, _c_int, _P],
+    # rnn_stream.hip: 256 units; (cell, LstmFwd / GruFwd / LstmBwd / GruBwd, packed form, num_seqs, seq_len, hidden, stream)
+    'rlg_rnn_stream_supported': [_c_int, _c_int],
+    'rlg_rnn_stream_pack_bytes': [_c_int, _c_int],
+    'rlg_rnn_stream_pack': [_c_int, _c_int, _P, _P, _P],
+    'rlg_rnn_stream_forward': [_c_int, _P, _P, _c_int, _c_int, _c_int, _P],
+    'rlg_rnn_stream_backward': [_c_int, _P, _P, _c_int, _c_int, _c_int, _P],
     # rnn_layer_norm.hip
     'rlg_rnn_layer_norm_num_blocks': [_c_ll, _c_int],
     'rlg_rnn_layer_norm_forward': [_P, _P, _P, _c_float, _P, _P, _c_ll, _c_int, _P],
@@ -190,7 +196,7 @@ def exported_prototypes():
 
 
 _RETURNS_LONG_LONG = {'rlg_mlp_dw_plan', 'rlg_stats_sync_flat_size', 'rlg_mlp_chain_planes_bytes', 'rlg_mlp_chain_planes_offset',
-                      'rlg_mlp_chain_frags_bytes', 'rlg_mlp_dw_ragged_workspace'}
+                      'rlg_mlp_chain_frags_bytes', 'rlg_mlp_dw_ragged_workspace', 'rlg_rnn_stream_pack_bytes'}
 
 
 def load():

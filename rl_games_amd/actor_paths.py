@@ -25,6 +25,12 @@ def train_forward(engine, normaliser, obs, rnn_states, dones, seq_length, **kw):
     return engine.forward(obs, rms, eps, rnn_states, dones, seq_length, keep=True, **kw)
 
 
+def wide_rnn(agent, config):
+    """`wide_rnn_kernels: True` (default off): a single-layer 256-unit LSTM / GRU runs on the streamed kernels of
+    csrc/rnn_stream.hip.  Training agents only: a player keeps the answer it always got for such a network."""
+    return bool(config.get('wide_rnn_kernels', False)) and getattr(agent, 'trains', True)
+
+
 def fp32_space(space):
     dtype = getattr(space, 'dtype', None)
     return dtype is not None and np.dtype(dtype) == np.float32
@@ -152,7 +158,7 @@ class EnginePath(AutogradPath):
         self.engine = ManualMLP(model.a2c_network, agent.optimizer,
                                 max(agent.minibatch_size, agent.num_actors * agent.num_agents),
                                 mfma_dw=bool(cfg.get('mfma_dw', True)), inplace_act=bool(cfg.get('inplace_act', True)),
-                                fused_chain=bool(cfg.get('fused_mlp', True)))
+                                fused_chain=bool(cfg.get('fused_mlp', True)), wide_rnn=wide_rnn(agent, cfg))
         self.engines = [self.engine]
         self.grads_overwritten = len(list(model.parameters())) == len(list(model.a2c_network.parameters()))
         self.norm_ok = self.norm_partials = None      # decided on first use (norm_in_finalize)
@@ -548,20 +554,21 @@ class RecurrentPath(ChainsPath):
     last_states = property(lambda self: self.recurrent.last_states)
 
     @staticmethod
-    def declined(net, config):
-        """Why a recurrent network stays off the engine (None: it is eligible)."""
+    def declined(net, config, stream=False):
+        """Why a recurrent network stays off the engine (None: it is eligible).  stream: wide_rnn(agent, config)."""
         if not config.get('manual_lstm', True):
             return 'manual_lstm is off'
         if not getattr(net, 'plain_trunk_rnn_ln', False) or net.is_separate_critic():
             return 'plain Linear + activation trunks only'
-        return rnn_cell_declined(net.rnn_name, net.rnn_layers, net.rnn_units)
+        return rnn_cell_declined(net.rnn_name, net.rnn_layers, net.rnn_units, stream)
 
     def __init__(self, agent):
         AutogradPath.__init__(self, agent)
         net = agent.model.a2c_network
         self.recurrent = RecurrentChainNet(net.actor_mlp, net.rnn.rnn, net.layer_norm if net.rnn_ln else None,
                                            chain_heads(net)[0], agent.optimizer, agent.minibatch_size,
-                                           infer_rows=agent.num_actors * agent.num_agents)
+                                           infer_rows=agent.num_actors * agent.num_agents,
+                                           wide_rnn=wide_rnn(agent, agent.config))
         self.engines = [self.recurrent]
 
     def infer(self, obs, rnn_states=None, logits_only=False):
@@ -602,7 +609,7 @@ class Plan:
             if not config.get('fused_mlp', True):
                 return
             self.notice = 'discrete network outside the fused chain kernels ({}); using autograd'
-            rnn_why = RecurrentPath.declined(net, config) if net.is_rnn() else None
+            rnn_why = RecurrentPath.declined(net, config, wide_rnn(agent, config)) if net.is_rnn() else None
             first = ()
             if net.is_rnn() and rnn_why is None:
                 first = [m.bias for m in net.actor_mlp if isinstance(m, nn.Linear)]      # (RecurrentChainNet's trunk)

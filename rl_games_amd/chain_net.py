@@ -32,6 +32,7 @@ import torch
 from torch import nn
 
 from . import ops
+from .weight_forms import WeightForm
 
 _DW_MAX_ITEMS = 8          # weight matrices / column-sum jobs of one ops.MlpDwPlan launch (csrc/mlp_dw.hip, kDwMaxLayers)
 _ACT_NAMES = {nn.ELU: 'elu', nn.ReLU: 'relu', nn.Tanh: 'tanh', nn.Identity: 'None'}
@@ -115,11 +116,14 @@ def head_span(heads, arena):
 RNN_CELLS = 'a single-layer LSTM or GRU with 16/32/64/128 units'
 
 
-def rnn_cell_declined(name, layers, units):
-    """Why the sequence-persistent kernels do not take a recurrent cell ('lstm' / 'gru', layers, units), or None."""
+def rnn_cell_declined(name, layers, units, stream=False):
+    """Why the sequence-persistent kernels do not take a recurrent cell ('lstm' / 'gru', layers, units), or None.
+    stream (`wide_rnn_kernels: True`): the streamed kernels' width (256 units, csrc/rnn_stream.hip) is taken as well."""
     supported = {'lstm': ops.lstm_supported, 'gru': ops.gru_supported}.get(name)
-    if supported is None or layers != 1 or not supported(units):
+    if supported is None or layers != 1:
         return RNN_CELLS + ' only'
+    if not supported(units) and not (stream and ops.rnn_stream_supported(name, units)):
+        return RNN_CELLS + (' (256 with wide_rnn_kernels)' if stream else '') + ' only'
     return None
 
 
@@ -235,18 +239,30 @@ class RnnStations:
     csrc/gru*.hip) and, behind their backward, the bias column sums and the two weight-gradient jobs.  No trunk, no
     layer norm, no heads and no loss: the engine writes `gates[:rows]`, reads `rnn_out[:rows]`, and hands
     `d_rnn_out[:rows]` (or a buffer of its own) to backward_args.
-    rnn: the torch.nn.LSTM / GRU module (parameters only); rows: the most rows of a forward."""
+    rnn: the torch.nn.LSTM / GRU module (parameters only); rows: the most rows of a forward.
+    stream: a 256-unit cell is taken too, on the streamed kernels of csrc/rnn_stream.hip.  The stations then own W_hh's
+    packed form (`packed`, allocated here, in front of any graph capture; `stream_form`, its versioned copy) and hand it
+    to every sequence launch.  weights_version: FlatArena.weights_token - the form is packed again when it changes
+    (None: in front of every launch).  Under a graph capture the pack launch is recorded with the sequence launch and
+    the stamp left alone: a replay packs from the weights of its own time."""
 
-    def __init__(self, rnn, rows, device):
+    def __init__(self, rnn, rows, device, stream=False, weights_version=None):
         self.lstm = rnn if isinstance(rnn, nn.LSTM) else None
         self.gru = rnn if isinstance(rnn, nn.GRU) else None
         if self.lstm is None and self.gru is None:
             raise NotImplementedError('LSTM or GRU only')
         H = rnn.hidden_size
-        if (rnn_cell_declined('lstm' if self.lstm is not None else 'gru', rnn.num_layers, H) or rnn.bidirectional
+        cell = 'lstm' if self.lstm is not None else 'gru'
+        if (rnn_cell_declined(cell, rnn.num_layers, H, stream) or rnn.bidirectional
                 or not rnn.bias or getattr(rnn, 'proj_size', 0)):
             raise NotImplementedError(RNN_CELLS + ' only')
-        self.rnn, self.Hr = rnn, H
+        self.rnn, self.Hr, self.cell = rnn, H, cell
+        self.packed = self.stream_form = None
+        if stream and ops.rnn_stream_supported(cell, H):
+            self.packed = torch.empty(ops.rnn_stream_pack_floats(cell, H), device=device)
+            self.stream_form = WeightForm(lambda: self.packed,
+                                          lambda _: ops.rnn_stream_pack(cell, rnn.weight_hh_l0, self.packed))
+            self._weights_version = weights_version
         self.Gr = G = (4 if self.lstm is not None else 3) * H        # gate columns
         # the bias of the gate-input product.  LSTM: b_ih + b_hh, summed into bias_sum by every forward.  GRU: b_hn is
         # multiplied by r inside the cell, so only b_ih belongs to the input side - bias_ih_l0 itself; the kernel adds
@@ -313,7 +329,12 @@ class RnnStations:
     def sequence(self, direction, args, seq_length):
         """The sequence kernel as a launch of its own: direction 'forward' / 'backward', args from forward_args /
         backward_args."""
-        ops.rnn_seq('lstm' if self.lstm is not None else 'gru', direction, [args], seq_length)
+        if self.packed is not None:
+            if torch.cuda.is_current_stream_capturing():
+                self.stream_form.pack(None)
+            else:
+                self.stream_form.ensure(None if self._weights_version is None else self._weights_version(), None)
+        ops.rnn_seq(self.cell, direction, [args], seq_length, packed=self.packed)
 
     @property
     def seq_length(self):
@@ -463,7 +484,7 @@ class ChainNet:
 
 class RecurrentChainNet:
     """One trunk of a recurrent policy without autograd:
-        obs -> [Linear + act] x L -> W_ih x + b -> LSTM | GRU (one layer, 16 / 32 / 64 / 128 units)
+        obs -> [Linear + act] x L -> W_ih x + b -> LSTM | GRU (one layer, 16 / 32 / 64 / 128 units; wide_rnn: 256 too)
             -> optional nn.LayerNorm(units) -> heads
     for arbitrary head columns (`heads`: nn.Linear modules over the recurrent features, adjacent in `arena` as for
     ChainNet).  The normaliser, the trunk and the gate-input product are one `ops.MlpChain` launch whose last (linear)
@@ -479,10 +500,14 @@ class RecurrentChainNet:
     `loss_partials[:loss_blocks]`; backward() then starts at the recurrent features.
     Raises NotImplementedError for networks outside the kernels' envelope - there is no per-layer fallback."""
 
-    def __init__(self, trunk, rnn, layer_norm, heads, arena, max_rows, infer_rows=0, value_tail=False):
+    def __init__(self, trunk, rnn, layer_norm, heads, arena, max_rows, infer_rows=0, value_tail=False, wide_rnn=False):
         self.linears, name = plain_trunk(trunk, identity_ok=False)
         rows = max(int(max_rows), int(infer_rows), 1)
-        self.stations = st = RnnStations(rnn, rows, self.linears[0].weight.device)
+        self.stations = st = RnnStations(rnn, rows, self.linears[0].weight.device, stream=wide_rnn,
+                                         weights_version=arena.weights_token)
+        if st.packed is not None and (layer_norm is not None or value_tail):
+            raise NotImplementedError('256 units without a layer norm or a value tail only (csrc/rnn_layer_norm.hip and '
+                                      'csrc/rnn_value_tail.hip stop at 128)')
         self.lstm, self.gru, self.rnn, self.Hr, self.Gr = st.lstm, st.gru, st.rnn, st.Hr, st.Gr
         H = st.Hr
         if rnn.input_size != self.linears[-1].out_features:

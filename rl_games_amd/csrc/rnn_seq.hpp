@@ -6,6 +6,9 @@
 //       narrow (16 / 32 / 64 units): W_hh in LDS, VALU FMAs, 256 threads, a tile of 16, 8 or 4 sequences; thread
 //         (j = tid % H, grp = tid / H) owns hidden unit j of the R sequences grp*R .. grp*R + R - 1 of the tile;
 //       wide (128 units): W_hh in registers as v_mfma_f32_16x16x4_f32 fragments, 1,024 threads, a tile of 16;
+//       (a third scheme, streamed - 256 units: W_hh from L2 every timestep as packed fragments of the same MFMA - has its
+//       kernels, entry points and description in csrc/rnn_stream.hip; it uses the cell formulas, tile_slot, step_keep,
+//       the *Args structs and launch_tile of this file);
 //   * a CELL: what a hidden unit does with its pre-activations, forward and backward, which does not know the scheme.
 // Each scheme and each cell formula is written once, here; the .hip files hold the kernels (argument lists, LDS
 // layout, the time loop, loads and stores) and what is specific to their cell or width.

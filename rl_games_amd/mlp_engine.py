@@ -40,12 +40,14 @@ from .chain_net import RnnStations, WeightGrads, arena_layout, head_span, plain_
 
 
 class ManualMLP:
-    def __init__(self, net, arena, max_rows, mfma_dw=True, inplace_act=True, fused_chain=True):
+    def __init__(self, net, arena, max_rows, mfma_dw=True, inplace_act=True, fused_chain=True, wide_rnn=False):
         """net: policy.ActorCriticNetwork (no RNN); arena: FlatArena laid out by `layout(net)`.
         mfma_dw: weight gradients through the one-launch f32-MFMA kernel (csrc/mlp_dw.hip).
         fused_chain: the whole MLP (observation normaliser, hidden layers, fused value|mu head) as
         ONE forward launch and ONE backward launch with the activations of a row tile resident in
         LDS (csrc/mlp_chain.hip); plain MLP policies only (the LSTM path keeps the per-layer GEMMs).
+        wide_rnn (`wide_rnn_kernels: True`): a 256-unit LSTM / GRU is taken too, on the streamed kernels of
+        csrc/rnn_stream.hip (chain_net.RnnStations owns W_hh's packed form).
         (Measured and rejected: forking the library dW GEMMs onto a second stream - multi-branch
         hipGraphs cost more in cross-branch dependencies than the overlap gains.)"""
         self.net = net
@@ -66,7 +68,8 @@ class ManualMLP:
         dev = self.head_w.device
         self.max_rows = max_rows
         # the recurrent cell between the trunk and the heads: chain_net.RnnStations, the one RecurrentChainNet runs on
-        self.stations = RnnStations(net.rnn.rnn, max_rows, dev) if getattr(net, 'has_rnn', False) else None
+        self.stations = (RnnStations(net.rnn.rnn, max_rows, dev, stream=wide_rnn, weights_version=arena.weights_token)
+                         if getattr(net, 'has_rnn', False) else None)
         st = self.stations
         # the cell's torch module (parameters only): by kind, and whichever of the two it is
         self.lstm, self.gru, self.rnn = (st.lstm, st.gru, st.rnn) if st is not None else (None, None, None)

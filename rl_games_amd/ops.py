@@ -1801,15 +1801,32 @@ _RNN_SEQ = {
 }
 
 
-def rnn_seq(cell, direction, problems, seq_len):
+def rnn_seq(cell, direction, problems, seq_len, packed=None):
     """One sequence launch: cell 'lstm' / 'gru', direction 'forward' / 'backward', on one or two problems - each the
     arguments of {cell}_seq_{direction} below in its order, without seq_len, as a tuple.  Two problems have one shape
     and run in ONE launch (twice the workgroups; bit-identical to the two single launches); dones and the optional
     outputs may be given for one problem and not for the other.  No output buffer may be shared.
+    packed: the problem's W_hh in the streamed form (rnn_stream_pack; stations built for 256 units hand it on) - ONE
+    problem, on the streamed kernels of csrc/rnn_stream.hip, which read nothing else of W_hh.
     (The four single-problem wrappers below make the same call for one problem without the way through the table: a
     T = 1 launch is host-bound, and they are what a caller outside a captured graph uses.)"""
     entry, describe, pair_type, gates_per_unit = _RNN_SEQ[cell, direction]
     n = len(problems)
+    if packed is not None:
+        if n != 1:
+            raise ValueError(f'the streamed kernels take one problem, {n} given')
+        gates = problems[0][0]
+        B, G = gates.shape
+        H = G // gates_per_unit
+        if (B // seq_len) * seq_len != B:
+            raise ValueError(f'rows ({B}) must be a multiple of seq_len ({seq_len})')
+        if packed.numel() != rnn_stream_pack_floats(cell, H):
+            raise ValueError(f'packed form of {packed.numel()} floats for a {cell} of {H} units')
+        desc = describe(*problems[0])
+        entry = 'rlg_rnn_stream_' + direction
+        _lib.check(getattr(_lib.load(), entry)(_STREAM_CELLS[cell], ctypes.byref(desc), _need(packed, F32, 'packed'),
+                                               B // seq_len, seq_len, H, _stream(gates)), entry)
+        return
     if n != 1 and n != 2:
         raise ValueError(f'{entry}: one or two problems, {n} given')
     gates = problems[0][0]
@@ -1824,6 +1841,32 @@ def rnn_seq(cell, direction, problems, seq_len):
     if n == 1:
         descs = ctypes.byref(describe(*problems[0]))
     _lib.check(getattr(_lib.load(), entry)(descs, n, B // seq_len, seq_len, G // gates_per_unit, _stream(gates)), entry)
+
+
+_STREAM_CELLS = {'lstm': 0, 'gru': 1}
+
+
+def rnn_stream_supported(cell, hidden):
+    """('lstm', 256) and ('gru', 256): W_hh streamed from L2 every timestep as packed MFMA fragments (csrc/rnn_stream.hip)."""
+    return cell in _STREAM_CELLS and bool(_lib.load().rlg_rnn_stream_supported(_STREAM_CELLS[cell], int(hidden)))
+
+
+def rnn_stream_pack_floats(cell, hidden):
+    """fp32 elements of the packed form [forward stream | backward stream] that rnn_stream_pack fills."""
+    nbytes = int(_lib.load().rlg_rnn_stream_pack_bytes(_STREAM_CELLS[cell], int(hidden)))
+    if nbytes < 0:
+        raise NotImplementedError(f'no streamed kernels for a {cell} of {hidden} units')
+    return nbytes // 4
+
+
+def rnn_stream_pack(cell, w_hh, packed):
+    """packed [rnn_stream_pack_floats] <- w_hh [NG*H, H], one launch; again whenever w_hh has changed."""
+    H = w_hh.shape[1]
+    if packed.numel() != rnn_stream_pack_floats(cell, H) or w_hh.shape[0] != (4 if cell == 'lstm' else 3) * H:
+        raise ValueError(f'rnn_stream_pack: w_hh {tuple(w_hh.shape)} and a packed form of {packed.numel()} floats do not agree')
+    _lib.check(_lib.load().rlg_rnn_stream_pack(_STREAM_CELLS[cell], H, _need(w_hh, F32, 'w_hh'), _need(packed, F32, 'packed'),
+                                               _stream(w_hh)), 'rlg_rnn_stream_pack')
+    return packed
 
 
 def lstm_supported(hidden):

@@ -3,6 +3,11 @@ forward (training: everything kept for backward; inference: final states only) a
 H in {64, 128} at (S, T) in {(1024, 16), (4096, 1), (4096, 16)}.  Device events around 100 launches after 10 warm-up
 launches, 5 % dones; the copy that restores the gate inputs in front of each forward is timed alone and subtracted.
 
+    python tools/bench_rnn_kernels.py --stream
+
+times the streamed 256-unit kernels (csrc/rnn_stream.hip, tile of 16 sequences; the pack launch is outside the timed
+windows) at S in {1,024, 4,096} x T in {1, 16}, the 128-unit rows of the same session beside them.
+
     python tools/bench_rnn_kernels.py --pair
 
 times the paired launches (csrc/rnn_seq.hpp, "paired launches": two problems of one shape in one launch) against the
@@ -47,10 +52,18 @@ def bench(cell, H, S, T):
     out, kept, hprev = (torch.empty(rows, H, device=DEV) for _ in range(3))
     hT, cT = torch.empty(S, H, device=DEV), torch.empty(S, H, device=DEV)
     dg, dgh = torch.empty_like(gin), torch.empty_like(gin)
+    packed = None
+    if H == 256:
+        packed = ops.rnn_stream_pack(cell, w_hh, torch.empty(ops.rnn_stream_pack_floats(cell, H), device=DEV))
 
     def fwd(train):
         gates.copy_(gin)
-        if cell == 'lstm':
+        keep = (kept if train else None, hprev if train else None, None if train else hT)
+        if packed is not None and cell == 'lstm':
+            ops.rnn_seq(cell, 'forward', [(gates, w_hh, h0, c0, dones, out) + keep + (None if train else cT,)], T, packed=packed)
+        elif packed is not None:
+            ops.rnn_seq(cell, 'forward', [(gates, w_hh, b_hh, h0, dones, out) + keep], T, packed=packed)
+        elif cell == 'lstm':
             ops.lstm_seq_forward(gates, w_hh, h0, c0, dones, out, kept if train else None, hprev if train else None,
                                  None if train else hT, None if train else cT, seq_len=T)
         else:
@@ -58,7 +71,11 @@ def bench(cell, H, S, T):
                                 None if train else hT, seq_len=T)
 
     def bwd():
-        if cell == 'lstm':
+        if packed is not None and cell == 'lstm':
+            ops.rnn_seq(cell, 'backward', [(gates, kept, c0, dones, w_hh, d_out, dg)], T, packed=packed)
+        elif packed is not None:
+            ops.rnn_seq(cell, 'backward', [(gates, kept, hprev, dones, w_hh, d_out, dg, dgh)], T, packed=packed)
+        elif cell == 'lstm':
             ops.lstm_seq_backward(gates, kept, c0, dones, w_hh, d_out, dg, T)
         else:
             ops.gru_seq_backward(gates, kept, hprev, dones, w_hh, d_out, dg, dgh, T)
@@ -155,6 +172,13 @@ if '--pair' in sys.argv[1:]:
             for S in (16, 256, 4096):
                 for T in (1, 16):
                     bench_pair(cell, H, S, T)
+elif '--stream' in sys.argv[1:]:
+    print('cell    H      S   T   fwd train    fwd inf   backward   [us per launch]')
+    for S in (1024, 4096):
+        for T in (1, 16):
+            for cell in ('lstm', 'gru'):
+                for H in (128, 256):
+                    bench(cell, H, S, T)
 else:
     print('cell    H      S   T   fwd train    fwd inf   backward   [us per launch]')
     for H in (64, 128):
