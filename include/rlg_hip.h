@@ -86,6 +86,35 @@ int rlg_gae_envmajor_raw(const float* rewards, const float* values, const uint8_
                          const float* last_values, const uint8_t* last_dones, float* gae_out,
                          int num_envs, int horizon, float gamma, float gamma_tau, void* stream);
 
+/* The env-major pass for long horizons: horizon % 4 == 0 and 64 < horizon <= 2^20 (rlg_gae_long_supported;
+ * rlg_gae_envmajor_supported keeps its envelope, the two do not overlap).  Same layout, arithmetic and outputs as
+ * rlg_gae_envmajor_fused / _raw, same rows of moment_partials (rlg_gae_envmajor_num_partials); a wave walks its 64 env
+ * rows from the end of time in chunks of 32 steps and carries the recurrence through the chunk boundaries, so every
+ * A_t, return and advantage has the bits of the scalar scan.  The partial sums are taken in another order than the
+ * short kernel's or rlg_triple_moments' (fp64: differences in the last bits).
+ *   raw = 0: out = returns, advantages_or_null required, moment_partials_or_null optional.
+ *   raw = 1: out = A_t; the two other outputs are not touched.
+ * rewards, values, dones, out and advantages 16-byte aligned.  A NULL descriptor or required pointer, a horizon outside
+ * the envelope, a misaligned base or only one of the two events: hipErrorInvalidValue, nothing launched. */
+typedef struct rlg_gae_long_desc {
+  const float* rewards;             /* [num_envs, horizon] */
+  const float* values;              /* [num_envs, horizon] */
+  const uint8_t* dones;             /* [num_envs, horizon] */
+  const float* last_values;         /* [num_envs] */
+  const uint8_t* last_dones;        /* [num_envs] */
+  float* out;                       /* [num_envs, horizon] */
+  float* advantages_or_null;        /* [num_envs, horizon] */
+  double* moment_partials_or_null;  /* [rlg_gae_envmajor_num_partials(num_envs), 6] */
+  void* ev_start_or_null;           /* HIP events (rlg_event_create) on THIS dispatch; not for launches inside a graph */
+  void* ev_stop_or_null;
+  int num_envs, horizon;
+  float gamma, gamma_tau;           /* rounded to fp32 by the host, as for rlg_gae_envmajor_fused */
+  int raw;
+} rlg_gae_long_desc;  /* 104 bytes: asserted with RLG_ABI_SIZE where the entries are defined (csrc/gae.hip) */
+
+int rlg_gae_long_supported(int horizon);
+int rlg_gae_long(const rlg_gae_long_desc* desc, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Rollout buffer (ExperienceBuffer) writes and per-step glue
  *   replaces rl_games/common/experience.py: ExperienceBuffer.update_data :433-456 and the

@@ -35,6 +35,8 @@ _PROTOTYPES = {
     'rlg_event_elapsed_us': [_P, _P, ctypes.POINTER(_c_float)],
     'rlg_gae_envmajor_fused_timed': [_P, _P, _P, _P, _P, _P, _P, _P, _c_int, _c_int, _c_float,
                                      _c_float, _P, _P, _P],
+    'rlg_gae_long_supported': [_c_int],
+    'rlg_gae_long': [_P, _P],                        # (GaeLongDesc, stream)
     # experience.hip
     'rlg_rollout_store_step': [_c_int, ctypes.POINTER(_P), ctypes.POINTER(_P),
                                ctypes.POINTER(_c_int), _c_int, _c_int, _c_int, _P],
@@ -221,6 +223,15 @@ def load():
         fn.restype = _c_ll if name in _RETURNS_LONG_LONG else _c_int
     _lib = lib
     return lib
+
+
+class GaeLongDesc(ctypes.Structure):
+    """rlg_gae_long_desc (include/rlg_hip.h): one launch of rlg_gae_long."""
+    _fields_ = ([(n, _P) for n in ('rewards', 'values', 'dones', 'last_values', 'last_dones', 'out',
+                                   'advantages_or_null', 'moment_partials_or_null', 'ev_start_or_null',
+                                   'ev_stop_or_null')]
+                + [('num_envs', _c_int), ('horizon', _c_int), ('gamma', _c_float), ('gamma_tau', _c_float),
+                   ('raw', _c_int)])
 
 
 class PpoLossDesc(ctypes.Structure):

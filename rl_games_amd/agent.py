@@ -648,7 +648,7 @@ class A2CAgent:
     def discount_values(self, fdones, last_extrinsic_values, mb_fdones, mb_extrinsic_values, mb_rewards):
         """a2c_common.py:729-734 (function seam kept for subclasses)."""
         return compute_gae(mb_rewards, mb_extrinsic_values, mb_fdones, last_extrinsic_values, fdones,
-                           self.gamma, self.tau)
+                           self.gamma, self.tau, long_horizon=bool(self.config.get('long_horizon_gae', False)))
 
     def clear_stats(self, clean_rewards=True):
         self.game_rewards.clear()
@@ -700,7 +700,12 @@ class A2CAgent:
             last_values = self._fast_values(self.obs)
         else:
             last_values = self.get_values(self.obs)
-        if self.value_size == 1 and ops._lib.load().rlg_gae_envmajor_supported(H):
+        lib = ops._lib.load()
+        # `long_horizon_gae: True` (default off): horizons above 64 take the chunked kernel of csrc/gae.hip and with it
+        # this branch; off, they run the strided scan and prepare_dataset's own moments, as before the kernel existed
+        fused = lib.rlg_gae_envmajor_supported(H) or (self.config.get('long_horizon_gae', False)
+                                                      and lib.rlg_gae_long_supported(H))
+        if self.value_size == 1 and fused:
             lv = last_values.reshape(-1).contiguous()
             timers = self.kernel_timers
             ev = None

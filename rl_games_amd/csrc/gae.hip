@@ -14,7 +14,7 @@
 // multiplied in double first, as Python does).  The file is compiled with
 // -ffp-contract=off, so none of the products above fuse into an FMA.
 //
-// Two kernels:
+// Three kernels:
 //  * gae_strided_kernel   - any layout / any H / V>1 / float or u8 dones.  One
 //                           thread per (env, value) pair, loads prefetched eight
 //                           timesteps at a time.  This is the function seam
@@ -31,9 +31,17 @@
 //                           of (advantages, values, returns) for the normalisers.
 //                           Algorithmic traffic: 4+4+1 B read, 4+4 B written per
 //                           env-step = 17 B.
+//  * gae_long_kernel      - the same layout, outputs and tile-to-partial-row mapping for
+//                           H % 4 == 0, H > 64: the wave walks time from the end in
+//                           chunks of 32 steps, each chunk the tile pass above in small,
+//                           the recurrence state and the moment sums carried in registers,
+//                           the next chunk's loads in flight under the scan (see there).
 
 #include "rlg_device.hpp"
+#include "rlg_hip.h"
 #include <hip/hip_ext.h>
+
+RLG_ABI_SIZE(rlg_gae_long_desc, 104);
 
 namespace rlg {
 
@@ -405,6 +413,225 @@ static int dispatch_envmajor(int H, const float* rewards, const float* values,
 #undef RLG_CASE
 }
 
+// ---------------------------------------------------------------------------------
+// Env-major fused kernel for long horizons (H % 4 == 0, H > 64): chunked scan
+// ---------------------------------------------------------------------------------
+//
+// A row of more than 64 steps fits neither a lane's registers nor a wave's LDS tile, so the wave walks its 64 env rows
+// from the end of time in chunks of C steps.  A chunk is the short kernel in small: the 64 x C sub-tiles of rewards and
+// values (row stride H) arrive through coalesced 16-byte loads, go through the wave's padded LDS tile pair (TileGeom<C>:
+// the layout of the short kernel at horizon C), every lane scans its own row, and the returns leave the tile in the
+// layout they came in.  Between chunks a lane keeps (A, v_next, nnt) and its six fp64 moment sums in registers: the
+// recurrence runs through the chunk boundaries in the order of the scalar loop, nothing is re-associated.
+//
+// The ragged chunk (H mod C steps, a multiple of 4) is the first one, at the end of time, so every later chunk is full
+// and starts at a multiple of C.  It runs the same code with its columns behind `len` switched off: their loads re-read
+// the chunk's first quad, their scan steps are skipped (wave-uniform), their stores do not happen.
+//
+// The loads of the next chunk (earlier in time) are issued before the current chunk is scanned and land in the register
+// stage (f32x4 x C/4 per array) while the wave scans and stores; the stage is the second buffer, the LDS tile pair is
+// single.  Done flags: every lane reads its own row's C bytes as dwords (a row of dones is 4-byte aligned only).
+
+constexpr int kGaeLongChunk = 32;      // steps per chunk; 16 and 64 timed beside it in profiles/gae_long.txt
+// One wave per workgroup: 18 KB of LDS a wave let 8 of them share a CU whatever the grouping, and at 4,096 envs the 64
+// waves of a launch spread over 64 CUs instead of 16.
+constexpr int kGaeLongWavesPerBlock = 1;
+constexpr int kGaeLongMaxHorizon = 1 << 20;
+
+// Sub-tile (rows x len floats at `g`, row stride H) -> register stage.  Quad c = k*64 + lane -> row c/(C/4), column
+// 4*(c%(C/4)); quads behind the live rows or behind `len` re-read quad 0 of the chunk, which always exists.
+template <int C>
+__device__ __forceinline__ void chunk_load_issue(const float* __restrict__ g, int H, int rows, int len,
+                                                 f32x4 (&buf)[C / 4]) {
+  constexpr int CPR = TileGeom<C>::kChunksPerRow;
+  const int lane = lane_id();
+#pragma unroll
+  for (int k = 0; k < C / 4; ++k) {
+    const int c = k * kWave + lane;
+    const int row = c / CPR;
+    const int col = (c - row * CPR) * 4;
+    const bool ok = row < rows && col < len;
+    buf[k] = *reinterpret_cast<const f32x4*>(g + (ok ? static_cast<long long>(row) * H + col : 0ll));
+  }
+}
+
+// This lane's done bytes of the chunk, 4 per dword (little endian); dwords behind `len` re-read the first one.
+template <int C>
+__device__ __forceinline__ void chunk_dones_issue(const uint8_t* __restrict__ drow, int len, uint32_t (&dw)[C / 4]) {
+#pragma unroll
+  for (int j = 0; j < C / 4; ++j) dw[j] = *reinterpret_cast<const uint32_t*>(drow + (4 * j < len ? 4 * j : 0));
+}
+
+// The recurrence over one chunk, on this lane's row of the LDS tiles: reads r and v a quad at a time from the end,
+// leaves A_t (kRaw) or A_t + v_t in place of r.  kFull = false: quads behind `len` are skipped.
+template <int C, bool kRaw, bool kFull>
+__device__ __forceinline__ void chunk_scan(float* tile_r, const float* tile_v, const uint32_t (&dw)[C / 4], int len,
+                                           float gamma, float gamma_tau, float& A, float& nv, float& nnt) {
+  constexpr int ROW = TileGeom<C>::kRow;
+  float* rrow = tile_r + lane_id() * ROW;
+  const float* vrow = tile_v + lane_id() * ROW;
+#pragma unroll
+  for (int j = C / 4 - 1; j >= 0; --j) {
+    if (kFull || 4 * j < len) {
+      f32x4 qr = *reinterpret_cast<const f32x4*>(rrow + 4 * j);
+      const f32x4 qv = *reinterpret_cast<const f32x4*>(vrow + 4 * j);
+#pragma unroll
+      for (int e = 3; e >= 0; --e) {
+        const float vt = qv[e];
+        const float delta = (qr[e] + (gamma * nv) * nnt) - vt;
+        A = delta + (gamma_tau * nnt) * A;
+        qr[e] = kRaw ? A : A + vt;       // raw GAE, or returns = A + v (a2c_common.py:1060)
+        nv = vt;
+        nnt = 1.0f - static_cast<float>((dw[j] >> (8 * e)) & 0xffu);
+      }
+      *reinterpret_cast<f32x4*>(rrow + 4 * j) = qr;
+    }
+  }
+}
+
+// Tile -> global in the layout of chunk_load_issue: returns (or raw A_t) to out0, returns - values to out1, and this
+// lane's share of the fp64 moments.  Only live rows and columns below `len` are stored or summed.
+template <int C, bool kRaw, bool kFull>
+__device__ __forceinline__ void chunk_store(const float* tile_r, const float* tile_v, float* __restrict__ out0,
+                                            float* __restrict__ out1, int H, int rows, int len, bool moments,
+                                            double (&m)[6]) {
+  constexpr int CPR = TileGeom<C>::kChunksPerRow;
+  constexpr int ROW = TileGeom<C>::kRow;
+  const int lane = lane_id();
+#pragma unroll
+  for (int k = 0; k < C / 4; ++k) {
+    const int c = k * kWave + lane;
+    const int row = c / CPR;
+    const int col = (c - row * CPR) * 4;
+    const f32x4 ret = *reinterpret_cast<const f32x4*>(tile_r + row * ROW + col);
+    if (row < rows && (kFull || col < len)) {
+      const long long off = static_cast<long long>(row) * H + col;
+      *reinterpret_cast<f32x4*>(out0 + off) = ret;
+      if constexpr (!kRaw) {
+        const f32x4 val = *reinterpret_cast<const f32x4*>(tile_v + row * ROW + col);
+        const f32x4 adv = ret - val;     // a2c_common.py:1598, the same single fp32 subtraction
+        *reinterpret_cast<f32x4*>(out1 + off) = adv;
+        if (moments) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const double da = adv[e], dv = val[e], dr = ret[e];
+            m[0] += da;
+            m[1] = fma(da, da, m[1]);
+            m[2] += dv;
+            m[3] = fma(dv, dv, m[3]);
+            m[4] += dr;
+            m[5] = fma(dr, dr, m[5]);
+          }
+        }
+      }
+    }
+  }
+}
+
+// One chunk [t0, t0 + len): stage -> LDS, request chunk [t0 - C, t0) into the stage, scan, store.
+template <int C, bool kRaw, bool kFull>
+__device__ __forceinline__ void chunk_step(const float* __restrict__ rewards, const float* __restrict__ values,
+                                           const uint8_t* __restrict__ drow, float* __restrict__ out0,
+                                           float* __restrict__ out1, float* tile_r, float* tile_v, int H, int rows,
+                                           int t0, int len, f32x4 (&rbuf)[C / 4], f32x4 (&vbuf)[C / 4],
+                                           uint32_t (&dnext)[C / 4], float gamma, float gamma_tau, float& A, float& nv,
+                                           float& nnt, bool moments, double (&m)[6]) {
+  tile_regs_to_lds<C>(rbuf, tile_r);
+  tile_regs_to_lds<C>(vbuf, tile_v);
+  uint32_t dw[C / 4];
+#pragma unroll
+  for (int j = 0; j < C / 4; ++j) dw[j] = dnext[j];
+  wave_lds_fence();
+  if (t0 > 0) {       // wave-uniform; t0 is a multiple of C here, the earlier chunk is full
+    chunk_load_issue<C>(rewards + (t0 - C), H, rows, C, rbuf);
+    chunk_load_issue<C>(values + (t0 - C), H, rows, C, vbuf);
+    chunk_dones_issue<C>(drow + (t0 - C), C, dnext);
+  }
+  chunk_scan<C, kRaw, kFull>(tile_r, tile_v, dw, len, gamma, gamma_tau, A, nv, nnt);
+  wave_lds_fence();
+  chunk_store<C, kRaw, kFull>(tile_r, tile_v, out0 + t0, kRaw ? out1 : out1 + t0, H, rows, len, moments, m);
+  wave_lds_fence();   // the next chunk rewrites the tiles
+}
+
+template <int C, bool kRaw>
+__global__ __launch_bounds__(64 * kGaeLongWavesPerBlock) void gae_long_kernel(
+    const float* __restrict__ rewards,      // [N, H]
+    const float* __restrict__ values,       // [N, H]
+    const uint8_t* __restrict__ dones,      // [N, H]
+    const float* __restrict__ last_values,  // [N]
+    const uint8_t* __restrict__ last_dones, // [N]
+    float* __restrict__ out0,               // kRaw ? gae [N,H] : returns [N,H]
+    float* __restrict__ out1,               // kRaw ? unused    : advantages [N,H]
+    double* __restrict__ partials,          // !kRaw: [num_tiles, 6] or nullptr
+    int N, int H, float gamma, float gamma_tau) {
+  static_assert(C % 4 == 0 && C >= 4 && C <= 64, "chunk length");
+  __shared__ __attribute__((aligned(16))) float lds[kGaeLongWavesPerBlock * 2 * TileGeom<C>::kTileFloats];
+  const int tile = blockIdx.x * kGaeLongWavesPerBlock + wave_id();
+  const int env0 = tile * kWave;
+  if (env0 >= N) return;  // whole wave exits together; no block-wide barrier is used below
+  float* tile_r = lds + wave_id() * 2 * TileGeom<C>::kTileFloats;
+  float* tile_v = tile_r + TileGeom<C>::kTileFloats;
+
+  const int rows = min(kWave, N - env0);
+  const int lane = lane_id();
+  const int env = lane < rows ? env0 + lane : env0;     // dead lanes compute along on the tile's first row
+  const long long base = static_cast<long long>(env0) * H;
+  rewards += base;
+  values += base;
+  out0 += base;
+  if constexpr (!kRaw) out1 += base;
+  const uint8_t* drow = dones + static_cast<long long>(env) * H;
+
+  int len = H % C;
+  if (len == 0) len = C;
+  int t0 = H - len;
+  f32x4 rbuf[C / 4], vbuf[C / 4];
+  uint32_t dnext[C / 4];
+  chunk_load_issue<C>(rewards + t0, H, rows, len, rbuf);
+  chunk_load_issue<C>(values + t0, H, rows, len, vbuf);
+  chunk_dones_issue<C>(drow + t0, len, dnext);
+  float nv = last_values[env];
+  float nnt = 1.0f - static_cast<float>(last_dones[env]);
+  float A = 0.0f;
+  double m[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  const bool moments = !kRaw && partials != nullptr;
+
+  chunk_step<C, kRaw, false>(rewards, values, drow, out0, out1, tile_r, tile_v, H, rows, t0, len, rbuf, vbuf, dnext,
+                             gamma, gamma_tau, A, nv, nnt, moments, m);
+  while (t0 > 0) {
+    t0 -= C;
+    chunk_step<C, kRaw, true>(rewards, values, drow, out0, out1, tile_r, tile_v, H, rows, t0, C, rbuf, vbuf, dnext,
+                              gamma, gamma_tau, A, nv, nnt, moments, m);
+  }
+
+  if (moments) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) m[k] = wave_sum(m[k]);
+    if (lane == 0) {
+#pragma unroll
+      for (int k = 0; k < 6; ++k) partials[static_cast<long long>(tile) * 6 + k] = m[k];
+    }
+  }
+}
+
+template <bool kRaw>
+static int launch_long(const rlg_gae_long_desc& d, hipStream_t stream) {
+  const int tiles = (d.num_envs + kWave - 1) / kWave;
+  const dim3 grid((tiles + kGaeLongWavesPerBlock - 1) / kGaeLongWavesPerBlock), block(kWave * kGaeLongWavesPerBlock);
+  if (d.ev_start_or_null) {
+    // events bound to this dispatch's begin / end timestamps, as in launch_envmajor
+    hipExtLaunchKernelGGL((gae_long_kernel<kGaeLongChunk, kRaw>), grid, block, 0, stream,
+                          static_cast<hipEvent_t>(d.ev_start_or_null), static_cast<hipEvent_t>(d.ev_stop_or_null), 0,
+                          d.rewards, d.values, d.dones, d.last_values, d.last_dones, d.out, d.advantages_or_null,
+                          d.moment_partials_or_null, d.num_envs, d.horizon, d.gamma, d.gamma_tau);
+  } else {
+    hipLaunchKernelGGL((gae_long_kernel<kGaeLongChunk, kRaw>), grid, block, 0, stream, d.rewards, d.values, d.dones,
+                       d.last_values, d.last_dones, d.out, d.advantages_or_null, d.moment_partials_or_null, d.num_envs,
+                       d.horizon, d.gamma, d.gamma_tau);
+  }
+  RLG_RETURN_LAUNCH_STATUS();
+}
+
 }  // namespace rlg
 
 // ---------------------------------------------------------------------------------
@@ -469,6 +696,26 @@ int rlg_gae_envmajor_raw(const float* rewards, const float* values, const uint8_
   return rlg::dispatch_envmajor<true>(horizon, rewards, values, dones, last_values, last_dones,
                                       gae_out, nullptr, nullptr, num_envs, gamma, gamma_tau,
                                       static_cast<hipStream_t>(stream));
+}
+
+int rlg_gae_long_supported(int horizon) {
+  return (horizon % 4 == 0 && horizon > 64 && horizon <= rlg::kGaeLongMaxHorizon) ? 1 : 0;
+}
+
+int rlg_gae_long(const rlg_gae_long_desc* d, void* stream) {
+  const int bad = static_cast<int>(hipErrorInvalidValue);
+  if (!d || !rlg_gae_long_supported(d->horizon) || d->num_envs < 0) return bad;
+  if (!d->rewards || !d->values || !d->dones || !d->last_values || !d->last_dones || !d->out) return bad;
+  if (!d->raw && !d->advantages_or_null) return bad;
+  if ((d->ev_start_or_null == nullptr) != (d->ev_stop_or_null == nullptr)) return bad;
+  for (const void* p : {static_cast<const void*>(d->rewards), static_cast<const void*>(d->values),
+                        static_cast<const void*>(d->dones), static_cast<const void*>(d->out),
+                        static_cast<const void*>(d->raw ? nullptr : d->advantages_or_null)}) {
+    if (reinterpret_cast<uintptr_t>(p) & 15u) return bad;
+  }
+  if (d->num_envs == 0) return 0;
+  return d->raw ? rlg::launch_long<true>(*d, static_cast<hipStream_t>(stream))
+                : rlg::launch_long<false>(*d, static_cast<hipStream_t>(stream));
 }
 
 int rlg_gae_strided(const float* rewards, const float* values, const void* dones,

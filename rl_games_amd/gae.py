@@ -40,9 +40,24 @@ def _is_envmajor(x, H, N):
     return (N == 1 or st[1] == H) and (H == 1 or st[0] == 1)
 
 
-def compute_gae(mb_rewards, mb_values, mb_dones, last_values, last_dones, gamma, tau):
+def _launch_long(lib, rewards, values, dones, last_values, last_dones, out, advantages, partials, N, H, g, gt,
+                 raw, events=None):
+    """rlg_gae_long: the chunked env-major kernel of horizons above 64 (csrc/gae.hip)."""
+    desc = _lib.GaeLongDesc(
+        rewards=rewards.data_ptr(), values=values.data_ptr(), dones=dones.data_ptr(),
+        last_values=last_values.data_ptr(), last_dones=last_dones.data_ptr(), out=out.data_ptr(),
+        advantages_or_null=_lib.ptr(advantages), moment_partials_or_null=_lib.ptr(partials),
+        ev_start_or_null=events.start if events is not None else None,
+        ev_stop_or_null=events.stop if events is not None else None,
+        num_envs=N, horizon=H, gamma=g, gamma_tau=gt, raw=1 if raw else 0)
+    _lib.check(lib.rlg_gae_long(ctypes.addressof(desc), _lib.stream_handle(rewards.device)), 'rlg_gae_long')
+
+
+def compute_gae(mb_rewards, mb_values, mb_dones, last_values, last_dones, gamma, tau, long_horizon=True):
     """Advantages `A_t` of shape [horizon, num_envs, value_size] (same maths, op order and
-    done semantics as gae_kernel.py:63-80; dones[0] is never read)."""
+    done semantics as gae_kernel.py:63-80; dones[0] is never read).  long_horizon=False keeps
+    env-major views of more than 64 steps on the strided kernel (the agent without its
+    `long_horizon_gae` key)."""
     lib = _lib.load()
     _lib.require_gpu(mb_rewards, 'compute_gae')
     if mb_rewards.dim() != 3:
@@ -63,13 +78,18 @@ def compute_gae(mb_rewards, mb_values, mb_dones, last_values, last_dones, gamma,
     g, gt = _f32_scalars(gamma, tau)
     stream = _lib.stream_handle(mb_rewards.device)
 
-    fast = (V == 1 and not want_float and lib.rlg_gae_envmajor_supported(H)
+    short = lib.rlg_gae_envmajor_supported(H)
+    fast = (V == 1 and not want_float and (short or (long_horizon and lib.rlg_gae_long_supported(H)))
             and _is_envmajor(mb_rewards, H, N) and _is_envmajor(mb_values, H, N)
             and _is_envmajor(mb_dones, H, N) and last_values.is_contiguous()
             and last_dones.is_contiguous()
             and all(t.data_ptr() % 16 == 0 for t in (mb_rewards, mb_values, mb_dones)))
     if fast:
         out = torch.empty((N, H), dtype=torch.float32, device=mb_rewards.device)
+        if not short:
+            _launch_long(lib, mb_rewards, mb_values, mb_dones, last_values, last_dones, out, None, None, N, H,
+                         g, gt, raw=True)
+            return out.t().unsqueeze(2)
         _lib.check(lib.rlg_gae_envmajor_raw(
             mb_rewards.data_ptr(), mb_values.data_ptr(), mb_dones.data_ptr(),
             last_values.data_ptr(), last_dones.data_ptr(), out.data_ptr(), N, H, g, gt, stream),
@@ -123,14 +143,16 @@ def gae_returns_advantages(rewards, values, dones, last_values, last_dones, gamm
     last_dones: [N] uint8.  Returns (returns [N,H], advantages [N,H], partials) where
     `returns = A + values` (a2c_common.py:1060), `advantages = returns - values`
     (a2c_common.py:1598) and partials [ceil(N/64), 6] fp64 hold per-tile sums
-    {adv, adv^2, v, v^2, ret, ret^2}.
+    {adv, adv^2, v, v^2, ret, ret^2}.  H a multiple of 4: up to 64 on the one-tile kernel,
+    above on the chunked one (rlg_gae_long), same results.
     """
     lib = _lib.load()
     _lib.require_gpu(rewards, 'gae_returns_advantages')
     N, H = rewards.shape
-    if not lib.rlg_gae_envmajor_supported(H):
-        raise ValueError(f'horizon {H} is not supported by the fused env-major GAE kernel '
-                         f'(multiple of 4, 4..64)')
+    short = lib.rlg_gae_envmajor_supported(H)
+    if not short and not lib.rlg_gae_long_supported(H):
+        raise ValueError(f'horizon {H} is not supported by the fused env-major GAE kernels '
+                         f'(a multiple of 4, 4..2^20)')
     for name, t, dt in (('rewards', rewards, torch.float32), ('values', values, torch.float32),
                         ('dones', dones, torch.uint8), ('last_dones', last_dones, torch.uint8),
                         ('last_values', last_values, torch.float32)):
@@ -144,6 +166,10 @@ def gae_returns_advantages(rewards, values, dones, last_values, last_dones, gamm
     if moment_partials is None:
         moment_partials = torch.empty((num_moment_partials(N), 6), dtype=torch.float64, device=dev)
     g, gt = _f32_scalars(gamma, tau)
+    if not short:
+        _launch_long(lib, rewards, values, dones, last_values, last_dones, out_returns, out_advantages,
+                     moment_partials, N, H, g, gt, raw=False, events=events)
+        return out_returns, out_advantages, moment_partials
     args = (rewards.data_ptr(), values.data_ptr(), dones.data_ptr(), last_values.data_ptr(),
             last_dones.data_ptr(), out_returns.data_ptr(), out_advantages.data_ptr(),
             moment_partials.data_ptr(), N, H, g, gt, _lib.stream_handle(dev))
