@@ -1032,6 +1032,36 @@ int rlg_mlp_chain_twin_forward(const rlg_chain_net* actor, const rlg_chain_net* 
 int rlg_mlp_chain_twin_backward(const rlg_chain_net* actor, const rlg_chain_net* critic, const rlg_chain_bwd* actor_bwd,
                                 const rlg_chain_bwd* critic_bwd, const rlg_chain_launch* launch, void* stream);
 
+/* ---- dense-to-dense (D2RL) trunks as one chain (csrc/mlp_chain_d2rl.hip) -------------------------------------------------
+ * `mlp.d2rl: True` (rl_games/algos_torch/d2rl.py): H_0 = act(W_0 xn + b_0), H_l = act(W_l [H_{l-1} | xn] + b_l), a linear
+ * head (the chain's last layer) over H_last alone.  Exact f32 products; the descriptors of rlg_mlp_chain_forward /
+ * _backward.  A D2RL net is recognised by its shape: in_features[l] == out_features[l-1] + in_features[0] for every hidden
+ * layer l >= 1 and in_features[last] == out_features[last-1]; any other shape is hipErrorInvalidValue, like a NULL
+ * descriptor, a missing array or rows <= 0 (unlike the other chain entries: these answer no call with "nothing to do") -
+ * all on the host, before anything is asked of the device.
+ * forward : the observations are read and normalised once per row tile (the RunningMeanStd eval formula, rms_batch_or_null
+ *           folded first as for rlg_mlp_chain_forward) and stay in LDS for every layer: no concatenation is materialised
+ *           for the products.  W_l is read at its own row stride u_{l-1} + in_0, whatever its alignment.  Training (hidden
+ *           act_out given): act_out[l] of a hidden layer l < last-1 receives the row [H_l | xn] - H_l in columns
+ *           [0, out_l), the normalised observations behind them - so act_ld[l] >= out_l + in_0; it is X of the weight
+ *           gradient dW_{l+1} = dZ_{l+1}^T [H_l | xn] as it stands.  act_out[last-1] receives H_last, act_out[last] the heads.
+ * backward: dZ_last = d_out; dZ_{l-1} = (dZ_l W_l[:, :out_{l-1}]) * act'(H_{l-1}) - the left column block only, there is
+ *           no dX of the observations; act_in[l] / act_ld[l] are the forward's act_out (H_l is read at that row stride);
+ *           dz_out and bias_partials as for rlg_mlp_chain_backward ([rlg_mlp_chain_num_blocks(rows, resolved groups), out_l]
+ *           fp64 rows, plain stores).
+ * weight_form_or_null, pack_backward_planes_or_null, ppo_loss_or_null, maxima_or_null: hipErrorNotSupported, nothing is
+ * launched.  A network outside the envelope: hipErrorNotSupported.
+ * rlg_mlp_chain_d2rl_supported: the 16-row groups per workgroup (1 / 2 / 4) a launch with groups = 0 runs - 2 from 8,192
+ * rows, 4 from 16,384, while two workgroups fit a CU's LDS - or 0 outside the envelope: 2 to 4 hidden layers, one activation
+ * kind (elu / relu / tanh), hidden widths multiples of 4 up to 512, an identity head of at most 512 columns, an observation
+ * width whose tile fits the 160 KiB LDS beside the two hidden regions with one group, no normalisation layer (a non-NULL
+ * gamma in ln_or_null).  Only the shape and the activation kinds of the net are read.  direction: 0 inference forward,
+ * 1 backward, 2 training forward.  It also raises the kernels' LDS limit, once per process: call it outside stream capture
+ * before the first captured launch. */
+int rlg_mlp_chain_d2rl_supported(const rlg_chain_net* net, const rlg_chain_ln* ln_or_null, long long rows, int direction);
+int rlg_mlp_chain_d2rl_forward(const rlg_chain_net* net, const rlg_chain_fwd* fwd, const rlg_chain_launch* launch, void* stream);
+int rlg_mlp_chain_d2rl_backward(const rlg_chain_net* net, const rlg_chain_bwd* bwd, const rlg_chain_launch* launch, void* stream);
+
 /* The 16-row launches of a data-parallel rank's minibatches (< 16,384 rows; rollouts of that size) in their LEAN form
  * (round 4; csrc/mlp_chain_lean.hip, mlp_chain_fwd_lean_kernel / mlp_chain_bwd_lean_kernel): the weights as FRAGMENTS (round 6: two fp16 planes of 64 w per group of 32 k values where rounds 4 - 5 had two fp32 chunks - the same bytes; csrc/split_f16.hpp) in
  * the order each of the 8 waves of a workgroup consumes them - one linear stream per wave across blocks and layers, zero

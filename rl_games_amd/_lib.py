@@ -103,6 +103,10 @@ _PROTOTYPES = {
     'rlg_mlp_chain_twin_supported': [_P, _P, _P, _P, _c_ll, _c_int],   # (ChainNet x 2, ChainLn or NULL x 2, rows, direction)
     'rlg_mlp_chain_twin_forward': [_P, _P, _P, _P, _P, _P],    # (ChainNet x 2, ChainFwd x 2, ChainLaunch, stream)
     'rlg_mlp_chain_twin_backward': [_P, _P, _P, _P, _P, _P],   # (ChainNet x 2, ChainBwd x 2, ChainLaunch, stream)
+    # mlp_chain_d2rl.hip: dense-to-dense trunks, the observations resident in LDS
+    'rlg_mlp_chain_d2rl_supported': [_P, _P, _c_ll, _c_int],   # (ChainNet, ChainLn or NULL, rows, direction)
+    'rlg_mlp_chain_d2rl_forward': [_P, _P, _P, _P],            # (ChainNet, ChainFwd, ChainLaunch, stream)
+    'rlg_mlp_chain_d2rl_backward': [_P, _P, _P, _P],           # (ChainNet, ChainBwd, ChainLaunch, stream)
     # lean 16-row forward (csrc/mlp_chain_lean.hip, mlp_chain_fwd_lean_kernel)
     'rlg_mlp_chain_frags_bytes': [_c_int, _P, _P, _c_int],
     'rlg_mlp_chain_pack_frags': [_c_int, _P, _P, _P, _P, _c_int, _P, _P],

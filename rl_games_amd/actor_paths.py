@@ -11,8 +11,8 @@ import torch
 from torch import nn
 
 from . import ops
-from .chain_net import (ChainNet, RecurrentChainNet, RecurrentChainPair, TwinChainNet, arena_layout, plain_trunk,
-                        rnn_cell_declined)
+from .chain_net import (ChainNet, RecurrentChainNet, RecurrentChainPair, TwinChainNet, arena_layout, d2rl_trunk,
+                        plain_trunk, rnn_cell_declined)
 from .mlp_engine import ManualMLP
 from .normalizers import launch_stats
 from .weight_forms import _ChainForms
@@ -29,6 +29,20 @@ def wide_rnn(agent, config):
     """`wide_rnn_kernels: True` (default off): a single-layer 256-unit LSTM / GRU runs on the streamed kernels of
     csrc/rnn_stream.hip.  Training agents only: a player keeps the answer it always got for such a network."""
     return bool(config.get('wide_rnn_kernels', False)) and getattr(agent, 'trains', True)
+
+
+def d2rl_declined(net, config, trains=True):
+    """`d2rl_kernels: True` (default off): the feed-forward dense-to-dense trunks of a network (`mlp.d2rl: True`) run on
+    the chain of csrc/mlp_chain_d2rl.hip.  Why such a network stays off it, or None: it is eligible.  Training agents
+    only: a player keeps the answer it always got.  The LDS is the library's to answer, when the engine is built."""
+    if not (config.get('d2rl_kernels', False) and trains):
+        return 'sequential Linear + activation (+ layer norm) trunks only'
+    try:
+        for trunk in [net.actor_mlp] + ([net.critic_mlp] if net.is_separate_critic() else []):
+            d2rl_trunk(trunk)
+    except NotImplementedError as e:
+        return str(e)
+    return None
 
 
 def fp32_space(space):
@@ -500,7 +514,8 @@ class SigmaPath(AutogradPath):
 
 class ChainsPath(AutogradPath):
     """A feed-forward discrete network on the fused chain kernels: one ChainNet over [value | logits] behind a shared
-    trunk, one per trunk with `separate: True` ([logits], [value])."""
+    trunk, one per trunk with `separate: True` ([logits], [value]).  The trunks are sequential (plain or layer-normed) or,
+    with `d2rl_kernels: True`, dense-to-dense (d2rl_declined)."""
     kind = 'chains'
     rollout_ok = property(lambda self: len(self.agent.branch_sizes) <= ops.CATEGORICAL_MAX_BRANCHES)
 
@@ -621,6 +636,8 @@ class Plan:
                 self.why = rnn_why
             elif not getattr(net, 'chain_trunk', getattr(net, 'plain_trunk', True)):
                 self.why = 'sequential Linear + activation (+ layer norm) trunks only'
+                if getattr(net, '_trunk_kw', {}).get('d2rl'):
+                    self.why = d2rl_declined(net, config, getattr(agent, 'trains', True))
             return
         general = (agent.value_size != 1 or not getattr(net, 'fixed_sigma', True) or not getattr(net, 'plain_sigma', True))
         if general:

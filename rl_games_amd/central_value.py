@@ -21,7 +21,7 @@ from torch import nn
 
 from . import distributed as rdist
 from . import ops, range_guard
-from .actor_paths import fp32_space, train_forward
+from .actor_paths import d2rl_declined, fp32_space, train_forward
 from .chain_net import ChainNet, RecurrentChainNet, arena_layout, rnn_cell_declined
 from .flat_optim import FlatAdam
 from .lr_control import IdentityScheduler, LinearScheduler
@@ -30,14 +30,19 @@ from .normalizers import launch_stats
 from .weight_forms import _ChainForms
 
 
-def _value_chain(net, arena, max_rows):
+def _value_chain(net, arena, max_rows, config=None):
     """Trunk + value head of a central value network on the fused chain kernels (chain_net.ChainNet): what autograd does
     for `CentralValueTrain.calc_gradients` (rl_games/algos_torch/central_value.py:278-335) between the loss kernel and
-    the optimiser.  Raises NotImplementedError for networks outside the kernels' envelope (the caller keeps autograd)."""
+    the optimiser.  Raises NotImplementedError for networks outside the kernels' envelope (the caller keeps autograd).
+    config: the critic's - its `d2rl_kernels: True` puts a dense-to-dense trunk on the chain of csrc/mlp_chain_d2rl.hip."""
     if not isinstance(net.value_act, nn.Identity) or net.value.out_features != 1:
         raise NotImplementedError('one linear value column only')
     if not getattr(net, 'chain_trunk', getattr(net, 'plain_trunk', True)) or net.is_rnn():
-        raise NotImplementedError('sequential Linear + activation (+ layer norm) trunks only')
+        why = 'sequential Linear + activation (+ layer norm) trunks only'
+        if getattr(net, '_trunk_kw', {}).get('d2rl') and not net.is_rnn():
+            why = d2rl_declined(net, config or {})
+        if why is not None:
+            raise NotImplementedError(why)
     return ChainNet(net.actor_mlp, [net.value], arena, max_rows)
 
 
@@ -121,7 +126,7 @@ class CentralValueTrain(nn.Module):
                       f'using autograd')
         elif config.get('fused_mlp', True) and value_size == 1:
             try:
-                self._engine = _value_chain(net, self.optimizer, self.minibatch_size)
+                self._engine = _value_chain(net, self.optimizer, self.minibatch_size, config)
             except NotImplementedError as e:
                 print(f'rl_games_amd: central value network outside the fused chain kernels ({e}); using autograd')
         self.set_chain_products(self.chain_products)

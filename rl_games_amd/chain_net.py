@@ -19,6 +19,8 @@ RecurrentChainNet and mlp_engine.ManualMLP alike; each engine keeps its own trun
 Users: the central value network (central_value.py, one value column) and the discrete-action agent (discrete_agent.py:
 [value | logits] behind a shared trunk, or one chain per trunk with `separate: True` as in ppo_cartpole.yaml).  The
 continuous actor's engine is mlp_engine.ManualMLP (loss inside the backward launch, a per-layer trunk mode, HIP graphs).
+Both users' trunks may be dense-to-dense (`mlp.d2rl: True` with the agents' `d2rl_kernels` key; d2rl_trunk): ChainNet then
+runs the chain of csrc/mlp_chain_d2rl.hip (`ops.MlpChainD2rl`), whose activation buffers are the rows [H_l | xn].
 Both users' trunks may end their layers in a layer norm (`network.normalization: layer_norm`, norm_trunk): ChainNet then
 runs the chain of csrc/mlp_chain_ln.hip (`ops.MlpChainLn`) and finishes the norms' gradients with the bias gradients.
 RecurrentChainNet is the recurrent engine of the discrete agent and the central value critic: the trunk + gate-input
@@ -98,6 +100,23 @@ def norm_trunk(trunk):
                 norms.append(None)
     linears, name = plain_trunk(plain)
     return linears, norms, name
+
+
+def d2rl_trunk(trunk):
+    """(linears, activation name) of a `policy.D2RLNet` (`mlp.d2rl: True`) whose norm layers are identities - what an
+    `ops.MlpChainD2rl` takes: layer l >= 1 reads [H_{l-1} | x].  Raises NotImplementedError with the reason otherwise."""
+    from .policy import D2RLNet
+    if not isinstance(trunk, D2RLNet):
+        raise NotImplementedError('not a D2RL trunk')
+    if any(not isinstance(m, nn.Identity) for m in trunk.norm_layers):
+        raise NotImplementedError('D2RL trunks without layer_norm / batch_norm only')
+    linears, name = plain_trunk([m for pair in zip(trunk.linears, trunk.activations) for m in pair], identity_ok=False)
+    in0 = linears[0].in_features
+    if any(l.in_features != p.out_features + in0 for p, l in zip(linears, linears[1:])):
+        raise NotImplementedError('unexpected D2RL structure')
+    if not 2 <= len(linears) <= 4 or any(l.out_features > 512 for l in linears):
+        raise NotImplementedError('D2RL trunks of 2 to 4 hidden layers of at most 512 units only')
+    return linears, name
 
 
 def head_span(heads, arena):
@@ -378,12 +397,18 @@ def _rows_of(buffers, rows):
 
 class ChainNet:
     """trunk: nn.Sequential of Linear + activation pairs, each optionally followed by an nn.LayerNorm over the layer's
-    width (norm_trunk: such a trunk runs ops.MlpChainLn, one without any norm ops.MlpChain as ever); heads: list of nn.Linear over the trunk's output whose
+    width (norm_trunk: such a trunk runs ops.MlpChainLn, one without any norm ops.MlpChain as ever), or a policy.D2RLNet
+    with identity norm layers (d2rl_trunk: it runs ops.MlpChainD2rl); heads: list of nn.Linear over the trunk's output whose
     weights (and biases) are adjacent in `arena`, in that order (arena_layout) - their columns side by side are the
     chain's last layer.  Raises NotImplementedError for networks outside the kernels' envelope."""
 
     def __init__(self, trunk, heads, arena, max_rows, infer_rows=0):
-        self.linears, self.norms, name = norm_trunk(trunk)
+        self.d2rl = not isinstance(trunk, nn.Sequential) and hasattr(trunk, 'norm_layers')
+        if self.d2rl:
+            self.linears, name = d2rl_trunk(trunk)
+            self.norms = [None] * len(self.linears)
+        else:
+            self.linears, self.norms, name = norm_trunk(trunk)
         heads = list(heads)
         if any(h.in_features != self.linears[-1].out_features for h in heads):
             raise NotImplementedError('heads must read the last hidden layer')
@@ -397,9 +422,15 @@ class ChainNet:
             # the next layer's input and X of its weight gradient; the backward reads pre[l] (the activation) and stats[l]
             norms = [None if m is None else (m.weight, m.bias, m.eps) for m in self.norms] + [None]
             self.chain = ops.MlpChainLn(layers, norms, dev, weights_version=arena.weights_token)
+        elif self.d2rl:
+            self.chain = ops.MlpChainD2rl(layers, dev, weights_version=arena.weights_token)
         else:
             self.chain = ops.MlpChain(layers, dev, weights_version=arena.weights_token)
-        self.Hs = [torch.empty(max_rows, w, device=dev) for w in widths]
+        # a D2RL trunk: Hs[l] of every layer but the last is the row [H_l | xn] - the next layer's whole input, written by
+        # the forward launch, X of that layer's weight gradient as it stands (trunk_jobs); the backward reads H_l in it
+        in0 = self.linears[0].in_features
+        cat = [in0 if self.d2rl and k + 1 < len(widths) else 0 for k in range(len(widths))]
+        self.Hs = [torch.empty(max_rows, w + c, device=dev) for w, c in zip(widths, cat)]
         self.dA = [torch.empty(max_rows, w, device=dev) for w in widths]
         self.heads = torch.empty(max_rows, self.head_cols, device=dev)
         self.d_heads = torch.empty(max_rows, self.head_cols, device=dev)

@@ -151,6 +151,21 @@ def cartpole_discrete(num_actors=16, **over):
     return {'algo': {'name': 'a2c_discrete'}, 'model': {'name': 'discrete_a2c'}, 'network': net, 'config': cfg}
 
 
+def discrete_d2rl(num_actors=64, units=(64, 36), activation='elu', obs_dim=33, actions=6, separate=False,
+                  d2rl_kernels=True, **over):
+    """Discrete PPO over dense-to-dense trunks (`mlp.d2rl: True`, rl_games/algos_torch/d2rl.py: every layer behind the
+    first reads [previous layer | observations]) - cartpole_discrete's hyper-parameters with normalised observations and
+    values on a synthetic env of `obs_dim` observations and `actions` actions.  No reference yaml switches d2rl on; the
+    builder option is public.  d2rl_kernels (this library's key, default here: on): the trunks run on the chain of
+    csrc/mlp_chain_d2rl.hip (actor_paths.ChainsPath) instead of torch modules under autograd."""
+    params = cartpole_discrete(num_actors, normalize_input=True, normalize_value=True, d2rl_kernels=bool(d2rl_kernels), **over)
+    params['network'].update(separate=bool(separate))
+    params['network']['mlp'].update(units=list(units), activation=activation, d2rl=True)
+    params['config']['name'] = 'discrete_d2rl'
+    params['config']['env_config'].update(obs_dim=int(obs_dim), discrete_actions=int(actions), autoreset_mode='same_step')
+    return params
+
+
 def smac_rnn_discrete(num_actors=8, cell='lstm', units=128, layer_norm=False, actions=14, **over):
     """The shape of the reference's recurrent SMAC runs (rl_games/configs/smac/v1/runs/MMM2_rnn.yaml, 6h_vs_8z_rnn.yaml;
     `layer_norm: True` as in 5m_vs_6m_rnn.yaml): discrete PPO, a shared ReLU trunk, one LSTM / GRU layer of `units`

@@ -1536,6 +1536,72 @@ class MlpChainLn(_ChainArgs):
                                stream=_stream(d_heads), groups=groups), 'rlg_mlp_chain_ln_backward')
 
 
+class MlpChainD2rl(_ChainArgs):
+    """MlpChain's counterpart for a dense-to-dense trunk (`mlp.d2rl: True`, csrc/mlp_chain_d2rl.hip): H_0 = act(W_0 xn + b_0),
+    H_l = act(W_l [H_{l-1} | xn] + b_l) and the linear head(s) over H_last, as ONE forward and ONE backward launch on exact
+    f32 products - the normalised observations stay in LDS for every layer, no concatenation is made for the products.
+    `layers` as for MlpChain, weight l >= 1 of shape [out_l, out_{l-1} + in_0], the head last; tensors are referenced, not
+    copied.  norms: the `norms` list of MlpChainLn or None - the kernels have no normalisation station, the library's
+    query says so.  Raises NotImplementedError for a network outside the envelope (rlg_mlp_chain_d2rl_supported: 2 - 4
+    hidden layers, one of elu / relu / tanh, hidden widths multiples of 4 up to 512 that fit the LDS, no layer norm) -
+    nothing is launched.  Towards weight_forms.ChainFormSet it answers like MlpChainLn: no derived weight copies."""
+
+    def __init__(self, layers, device, weights_version=None, norms=None):
+        self._state(layers, device, weights_version, norms)
+        if any(self.groups(1, d) == 0 for d in (0, 1)):                 # (also raises the kernels' LDS limit)
+            raise NotImplementedError('D2RL trunk outside the envelope of the dense-to-dense chain kernels')
+
+    def _state(self, layers, device, weights_version, norms):
+        self._state_net(layers, device, weights_version)
+        self._ln = MlpChainTwin._ln_query(self, norms)
+        self.products = 'auto'      # one product form, exact f32: the attribute only travels (ChainFormSet.set_products)
+
+    @classmethod
+    def supported(cls, layers, norms=None, rows=1, direction=0):
+        """rlg_mlp_chain_d2rl_supported for this network: the 16-row groups of such a launch, 0 outside the envelope."""
+        self = cls.__new__(cls)
+        self._state(layers, layers[0][0].device, None, norms)
+        return self.groups(rows, direction)
+
+    def forms_read(self, launches):
+        return False, False
+
+    def cache_state(self):
+        return weight_forms.ChainSnapshot(None, None, None, False, self.products)
+
+    def restore_cache_state(self, state):
+        self.products = state.products
+
+    def groups(self, rows, direction, requested=0):
+        """16-row groups per workgroup of a launch: `requested` (1 / 2 / 4), else the library's choice from the rows and the
+        LDS the widths need; 0: outside the envelope.  direction: 0 inference forward, 1 backward, 2 training forward."""
+        ln = None if self._ln is None else ctypes.byref(self._ln)
+        G = int(_lib.load().rlg_mlp_chain_d2rl_supported(ctypes.byref(self._net), ln, int(rows), int(direction)))
+        return requested if (G and requested in (1, 2, 4)) else G
+
+    def num_blocks(self, rows, direction, requested=0):
+        return _lib.load().rlg_mlp_chain_num_blocks(int(rows), self.groups(rows, direction, requested))
+
+    def forward(self, x, heads, act_out=None, rms=None, eps=1e-5, xn_out=None, groups=0, rms_fold=None):
+        """x [rows, in0] (row stride free), heads [rows, out_last] out.  Training: act_out per hidden layer - [rows, out_l +
+        in0] for every layer but the last hidden one, which receives the row [H_l | xn] (X of the next layer's weight
+        gradient), [rows, out_l] for the last.  rms / xn_out / rms_fold as for MlpChain.forward."""
+        rows = x.shape[0]
+        outs = list(act_out) if act_out is not None else [None] * (self.n - 1)
+        fwd = self._forward_args(x, outs + [heads], rms, eps, xn_out, rms_fold)
+        _lib.check(_chain_call('fwd_train' if act_out is not None else 'fwd_infer', _lib.load().rlg_mlp_chain_d2rl_forward,
+                               self._net, fwd, rows=rows, stream=_stream(x), groups=groups), 'rlg_mlp_chain_d2rl_forward')
+
+    def backward(self, d_heads, acts, dz_out, bias_partials=None, groups=0):
+        """d_heads [rows, out_last]; acts: the forward's act_out (H_l is read in its first out_l columns); dz_out: per
+        hidden layer the dZ_l output [rows, out_l]; bias_partials: fp64 [num_blocks(rows, 1), out_l] per hidden layer or
+        None."""
+        rows = d_heads.shape[0]
+        bwd = self._backward_args(d_heads, acts, dz_out, bias_partials, None)
+        _lib.check(_chain_call('bwd', _lib.load().rlg_mlp_chain_d2rl_backward, self._net, bwd, rows=rows,
+                               stream=_stream(d_heads), groups=groups), 'rlg_mlp_chain_d2rl_backward')
+
+
 class _TrunkArgs(_ChainArgs):
     """One trunk of an MlpChainTwin: its rlg_chain_net and the builders of its descriptor halves."""
 
