@@ -1315,6 +1315,23 @@ typedef struct rlg_dw_ragged {
 long long rlg_mlp_dw_ragged_workspace(long long rows, int out_features, int in_features);
 int rlg_mlp_dw_ragged(const rlg_dw_ragged* desc, void* stream);
 
+/* The same product in ONE launch, for minibatches of 1 .. 20,479 rows (longer ones run, they are not what it is built
+ * for).  Same descriptor, same envelope, same error rules.  A workgroup issues every load of a burst of its rows before
+ * it waits for the first, stores its fp32 partial tile, fences once, and draws a ticket from its tile's counter word (one
+ * agent-scope atomic add); whoever draws a tile's last ticket sums the tile's partials in index order in fp64, writes grad and
+ * stores 0 into the counter.  Arrival decides who sums, never in what order: the same inputs give the same bits, and no
+ * workgroup waits for another.  A tile with one workgroup writes grad directly.
+ *   workspace = [counter words | partial tiles], in floats; rlg_mlp_dw_ragged_short_workspace returns its size, or 0
+ *     outside the envelope.  The caller zero-fills it ONCE, when it allocates it; every call leaves the counter words
+ *     zero, and no call reads a partial that the same call did not write, or a byte outside the workspace (the sum's
+ *     loads are range-checked against the partials of their call).  The counter words are as many for every
+ *     shape (a shape with one workgroup per tile, 1 x 1 x 1 say, needs them and nothing else): one zero-filled
+ *     workspace may serve calls of different shapes in stream order.
+ *   rlg_mlp_dw_ragged_short: a shape or an alignment outside the envelope: hipErrorNotSupported (801), nothing
+ *     launched.  A NULL pointer or a workspace that is too small: hipErrorInvalidValue. */
+long long rlg_mlp_dw_ragged_short_workspace(long long rows, int out_features, int in_features);
+int rlg_mlp_dw_ragged_short(const rlg_dw_ragged* desc, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * In-graph gradient all-reduce over peer-mapped device memory (csrc/ipc_allreduce.hip)
  *   replaces dist.all_reduce(SUM) of the flattened gradients in A2CBase.trancate_gradients_and_step

@@ -85,6 +85,8 @@ _PROTOTYPES = {
     # mlp_dw_ragged.hip: widths that are no multiples of 4
     'rlg_mlp_dw_ragged_workspace': [_c_ll, _c_int, _c_int],
     'rlg_mlp_dw_ragged': [_P, _P],                   # (DwRagged, stream)
+    'rlg_mlp_dw_ragged_short_workspace': [_c_ll, _c_int, _c_int],
+    'rlg_mlp_dw_ragged_short': [_P, _P],             # (DwRagged, stream): one launch, minibatches below 20,480 rows
     # mlp_chain.hip
     'rlg_mlp_chain_prepare': [],
     'rlg_mlp_chain_groups': [_c_ll, _c_int, _c_int],
@@ -202,7 +204,8 @@ def exported_prototypes():
 
 
 _RETURNS_LONG_LONG = {'rlg_mlp_dw_plan', 'rlg_stats_sync_flat_size', 'rlg_mlp_chain_planes_bytes', 'rlg_mlp_chain_planes_offset',
-                      'rlg_mlp_chain_frags_bytes', 'rlg_mlp_dw_ragged_workspace', 'rlg_rnn_stream_pack_bytes'}
+                      'rlg_mlp_chain_frags_bytes', 'rlg_mlp_dw_ragged_workspace', 'rlg_mlp_dw_ragged_short_workspace',
+                      'rlg_rnn_stream_pack_bytes'}
 
 
 def load():

@@ -335,6 +335,11 @@ class A2CAgent:
         self.optimizer = FlatAdam(self.model.parameters(), self.last_lr, eps=1e-08,
                                   weight_decay=self.weight_decay, layout=plan.layout)
         self._path = plan.build(self)
+        # `short_ragged_dw: True` (default off): a first layer over a width off a multiple of 4 finishes its weight
+        # gradient on the one-launch kernel of csrc/mlp_dw_ragged.hip below ops.RAGGED_MIN_ROWS rows too, where the
+        # default is the library product (other bits; README.md says at which shapes it is also the faster choice)
+        for e in self._path.engines:
+            e.weight_grads.ragged_short = bool(config.get('short_ragged_dw', False))
         # where a step or a minibatch goes whose observations the path does not take (takes()): the plan's fallback -
         # GeneralPath for a network the fused loss kernels do not carry (a sigma head on SigmaPath), else AutogradPath
         self._autograd = self._path if type(self._path) is plan.fallback else plan.fallback(self)

@@ -130,6 +130,8 @@ class CentralValueTrain(nn.Module):
             except NotImplementedError as e:
                 print(f'rl_games_amd: central value network outside the fused chain kernels ({e}); using autograd')
         self.set_chain_products(self.chain_products)
+        for eng in self.engines():             # the critic's own `short_ragged_dw` key (agent.py)
+            eng.weight_grads.ragged_short = bool(config.get('short_ragged_dw', False))
         if self.split_range != 'warn':
             self._guard = ops.guard_record(ppo_device)
             self.optimizer.guard = self._guard

@@ -154,13 +154,16 @@ class WeightGrads:
     PPO loss partials.  What is left - a first layer over 9 state features, say - is a launch each: with `narrow` the
     narrow kernel of csrc/mlp_narrow.hip where it applies, else with `ragged` the MFMA kernel for widths off a multiple
     of 4 (csrc/mlp_dw_ragged.hip: GPU tensors, dense, 16-byte aligned, ops.ragged_dw_supported), else a library product
-    (the three give different bits).
+    (the three give different bits).  `ragged_short` (default off; the agents' `short_ragged_dw: True`): what would be
+    a library product goes to the one-launch kernel for short minibatches instead (ops.ragged_dw_short) when the long
+    route's conditions hold but for its row count - a fourth set of bits.
     mfma=False: no MFMA launch at all.  Plans (and the shapes the launch declined) are kept per shape key.
     form: the product form of the MFMA launch (ops.MlpDwPlan.launch) - None: the library's choice, 'exact': f32 products
     whatever maxima the step carries (an agent on `chain_products: exact`)."""
 
-    def __init__(self, mfma=True, narrow=False, ragged=True):
+    def __init__(self, mfma=True, narrow=False, ragged=True, ragged_short=False):
         self.mfma, self.narrow, self.ragged = bool(mfma), bool(narrow), bool(ragged)
+        self.ragged_short = bool(ragged_short)
         self.form = None
         self._plans = {}
         self.last_dw_path = None            # 'mfma' / 'library': whether the last finish() had an MFMA launch
@@ -226,6 +229,10 @@ class WeightGrads:
             elif (self.ragged and g.is_cuda and all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in (dz, x, g))
                     and ops.ragged_dw_supported(dz.shape[0], g.shape[0], g.shape[1])):
                 ops.ragged_dw(dz, x, g)            # a first layer over 98 observations (SMAC), 17, 105 (MuJoCo)
+            elif (self.ragged_short and g.is_cuda
+                    and all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in (dz, x, g))
+                    and ops.ragged_dw_short_supported(dz.shape[0], g.shape[0], g.shape[1])):
+                ops.ragged_dw_short(dz, x, g)      # the same layers on minibatches below ops.RAGGED_MIN_ROWS rows
             else:
                 torch.mm(dz.t(), x, out=g)
                 self.last_dw_library_jobs += 1

@@ -1039,6 +1039,39 @@ def ragged_dw(dz, x, grad):
     _lib.check(err, 'rlg_mlp_dw_ragged')
 
 
+_ragged_short_scratch = {}
+
+
+def ragged_dw_short_supported(rows, No, Mi):
+    """Whether ragged_dw_short takes the shape: its envelope (No 1 .. 1024, Mi 1 .. 512), at any row count."""
+    return _lib.load().rlg_mlp_dw_ragged_short_workspace(rows, No, Mi) > 0
+
+
+def ragged_dw_short(dz, x, grad):
+    """ragged_dw in ONE launch, built for minibatches below RAGGED_MIN_ROWS rows (csrc/mlp_dw_ragged.hip,
+    mlp_dw_ragged_short_kernel): same product, same envelope, same errors, other bits (another split of the rows).  Its
+    workspace starts with counter words that every call leaves zero: allocated zero-filled, once per (device, floats)."""
+    rows, No = dz.shape
+    Mi = x.shape[1]
+    if x.shape[0] != rows or tuple(grad.shape) != (No, Mi) or dz.stride(1) != 1 or x.stride(1) != 1:
+        raise ValueError('ragged_dw_short: shape mismatch')
+    _lib.require_gpu(dz, 'dz')
+    lib = _lib.load()
+    need = lib.rlg_mlp_dw_ragged_short_workspace(rows, No, Mi)
+    if need <= 0 or not (dz.is_contiguous() and x.is_contiguous()):
+        raise NotImplementedError(f'ragged_dw_short: [{rows} x {No}]^T [{rows} x {Mi}] with strides {dz.stride()}, '
+                                  f'{x.stride()} is outside the kernel\'s envelope')
+    key = (str(dz.device), need)
+    if key not in _ragged_short_scratch:    # (fixed address per shape: the launch is replayed from HIP graphs)
+        _ragged_short_scratch[key] = torch.zeros(need, dtype=F32, device=dz.device)
+    desc = _lib.DwRagged(_need(dz, F32, 'dz'), _need(x, F32, 'x'), _need(grad, F32, 'grad'),
+                         _ragged_short_scratch[key].data_ptr(), need, rows, No, Mi)
+    err = lib.rlg_mlp_dw_ragged_short(ctypes.addressof(desc), _stream(dz))
+    if err == 801:
+        raise NotImplementedError('ragged_dw_short: operands outside the kernel\'s envelope (16-byte aligned base pointers)')
+    _lib.check(err, 'rlg_mlp_dw_ragged_short')
+
+
 # ------------------------------------------------------------------ fused MLP chain (MFMA, LDS-resident)
 
 chain_timers = None     # bench.py: {'fwd': [...], 'bwd': [...]} of gae.HipEventPair, one per eager chain launch

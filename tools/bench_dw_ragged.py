@@ -11,7 +11,11 @@ that replays its launches sees).  Both settings are warmed up, then alternate fo
 synchronisations.  One JSON line per measurement: median and spread (min .. max) over the rounds per setting, ms per call,
 the ratio of the medians, and for a shape the largest difference between the two results over the largest |G|.
 
-    python tools/bench_dw_ragged.py [--what shapes,update20480,update2560] [--rounds 7] [--calls 200]
+  --short: the one-launch kernel for short minibatches (ops.ragged_dw_short) instead, at the first-layer shapes of the
+           reference's MuJoCo and SMAC configs on minibatches of 2,048 .. 16,384 rows: against the library product and
+           against ops.ragged_dw (the long kernel, forced on), same method; no update measurement (profiles/dw_ragged_short.txt)
+
+    python tools/bench_dw_ragged.py [--what shapes,update20480,update2560] [--rounds 7] [--calls 200] [--short]
 """
 import argparse
 import json
@@ -28,6 +32,7 @@ from rl_games_amd import ops  # noqa: E402
 from bench_chain_ln import _agent, _minibatch, _timed  # noqa: E402
 
 SHAPES = [(2560, 512, 98), (20480, 512, 98), (32768, 256, 17), (32768, 400, 105), (4096, 256, 11)]
+SHORT_SHAPES = [(2560, 512, 98), (4096, 256, 11), (2048, 256, 17), (8192, 512, 98), (16384, 400, 105)]
 
 
 GRAPH_CALLS = 20
@@ -53,7 +58,9 @@ def _measure(name, fns, rounds, calls, extra=None):
     out = {'what': name, 'unit': 'ms per call', 'rounds': rounds, 'calls': calls}
     for k, ts in times.items():
         out[k] = {'median': round(statistics.median(ts), 4), 'min': round(min(ts), 4), 'max': round(max(ts), 4)}
-    out['library_over_ragged'] = round(out['library']['median'] / out['ragged']['median'], 3)
+    for k in times:
+        if k != 'library':
+            out[f'library_over_{k}'] = round(out['library']['median'] / out[k]['median'], 3)
     out.update(extra or {})
     print(json.dumps(out), flush=True)
 
@@ -63,17 +70,22 @@ def main():
     ap.add_argument('--what', default='shapes,update20480,update2560')
     ap.add_argument('--rounds', type=int, default=7)
     ap.add_argument('--calls', type=int, default=200)
+    ap.add_argument('--short', action='store_true')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('bench_dw_ragged.py measures on the GPU; none found')
     dev = 'cuda:0'
-    for what in args.what.split(','):
+    for what in (['shapes'] if args.short else args.what.split(',')):
         if what == 'shapes':
-            for rows, No, Mi in SHAPES:
+            for rows, No, Mi in (SHORT_SHAPES if args.short else SHAPES):
                 torch.manual_seed(rows + No + Mi)
                 dz, x = torch.randn(rows, No, device=dev), torch.randn(rows, Mi, device=dev)
                 g, gl = torch.empty(No, Mi, device=dev), torch.empty(No, Mi, device=dev)
                 fns = {'ragged': lambda: ops.ragged_dw(dz, x, g), 'library': lambda: torch.mm(dz.t(), x, out=gl)}
+                if args.short:
+                    g2 = torch.empty(No, Mi, device=dev)
+                    fns = {'short': lambda: ops.ragged_dw_short(dz, x, g), 'library': fns['library'],
+                           'ragged': lambda: ops.ragged_dw(dz, x, g2)}
                 for fn in fns.values():
                     fn()
                 diff = ((g - gl).abs().max() / gl.abs().max()).item()
